@@ -21,6 +21,10 @@ under strong scaling + SyncBatchNorm (the reference's global batch 128 and its s
 configs[4] (1e6 / N cells generated per rank, 128 cells per GPU), each with the step's collective alone (`allreduce_us`), the same
 per-GPU step without a communicator (`nocomm_ms_per_step`) and their difference (`dp_overhead_us`), beside DESIGN.md section 5's
 predictions for N = 8.
+
+--dump-outputs DIR: what the timed steps hand their caller after the last of them -- the parameters, the BatchNorm moving statistics
+and that step's ELBO scalars -- is written as DIR/<name>.npy (float32, 64 MB at most), so that two builds of the project run with the
+same arguments (the same inputs: every draw is seeded) can be compared output for output.
 """
 import argparse
 import json
@@ -35,6 +39,7 @@ import numpy as np  # noqa: E402
 
 LOSS_REPEAT = 8   # SMX_LOSS_TIMING_REPEAT in sisua_amd/csrc/smx_model.h
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (6.3 TB/s achievable)
+DUMP_BYTES = 64 << 20  # --dump-outputs: everything written, .npy headers included
 
 
 import functools  # noqa: E402
@@ -142,6 +147,39 @@ def make_order(n_cells: int, batch: int, n_steps: int):
     have += len(bs)
     ep += 1
   return np.concatenate(chunks[:n_steps]).astype(np.int32)
+
+
+def step_outputs(eng, hist):
+  """What a caller of the timed path holds after its last step: the parameters, the BatchNorm moving statistics and the step's ELBO
+  scalars (the last row of `hist`, eng.metrics_history of that call) -- host copies."""
+  out = {f"metrics.{k}": np.asarray(v[-1:], np.float32) for k, v in hist.items()}
+  out.update({"params." + n.replace("/", "."): a for n, a in eng.get_params().items()})
+  for i, st in eng.get_bn().items():
+    out.update({f"bn{i}.{k}": a for k, a in st.items()})
+  return out
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+  """Write every array as <path>/<name>.npy in float32, `budget` bytes in all.  Over the budget, each array of more than 65 536 elements
+  keeps the same fraction of its elements, flattened: a sorted sample drawn with default_rng(0), a function of the arrays' sizes alone,
+  so two runs' files hold the same elements.  Returns a summary for the JSON line."""
+  arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in sorted(arrays.items())}
+  room = budget - 256 * len(arrays)   # (a .npy header is 128 bytes)
+  small = sum(a.nbytes for a in arrays.values() if a.size <= 1 << 16)
+  large = sum(a.nbytes for a in arrays.values() if a.size > 1 << 16)
+  frac = 1.0 if small + large <= room else (room - small) / large
+  if frac <= 0.0:
+    raise ValueError(f"--dump-outputs: {small} bytes of small arrays exceed the budget of {budget}")
+  os.makedirs(path, exist_ok=True)
+  written, sampled = 0, []
+  for name, a in arrays.items():
+    if frac < 1.0 and a.size > 1 << 16:
+      idx = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False))
+      a = a.reshape(-1)[idx]
+      sampled.append(name)
+    np.save(os.path.join(path, name + ".npy"), a)
+    written += a.nbytes
+  return {"dir": path, "files": len(arrays), "bytes": written, "sampled": sampled}
 
 
 def cpu_baseline(cfg, xt, batch, budget_s=12.0, threads=None, extra=None):
@@ -304,7 +342,11 @@ def main():
                   help="N > 1: weak = the configuration's batch per GPU; strong = the global batch is preserved (batch / N per GPU)")
   ap.add_argument("--sync-bn", action="store_true", help="N > 1: SyncBatchNorm (global-batch statistics)")
   ap.add_argument("--no-scaling-modes", action="store_true", help="N > 1: skip the in-run weak / strong + SyncBatchNorm / C5 measurements")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write what the timed steps computed in the last of them (parameters, BatchNorm statistics, ELBO scalars) as DIR/<name>.npy")
   args = ap.parse_args()
+  if args.steps < 1:
+    ap.error("--steps must be at least 1")
 
   rank = int(os.environ.get("RANK", "0"))
   local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -399,6 +441,8 @@ def main():
   m = {k: float(v[-1]) for k, v in hist.items()}
   if not np.isfinite(hist["loss"]).all():
     sys.exit("bench: non-finite loss in the timed steps")
+  # (copied now: the runs below train the same engine further)
+  outputs = step_outputs(eng, hist) if args.dump_outputs and rank == 0 else None
   # a longer run beside the contract's K steps (the driver's 20 steps are a 1.6 ms window): 300 more steps of the SAME engine,
   # ids staged, one library call, the same brackets -- reported as value_300 / ms_per_step_300, never as `value`
   n300 = 300
@@ -653,6 +697,8 @@ def main():
       if np.isfinite(h2["loss"]).all() and dt_sel < dt and rank == 0:
         out.update(value=round(args.steps * batch * world / dt_sel, 1), ms_per_step=round(1e3 * dt_sel / args.steps, 4), final_loss=round(float(h2["loss"][-1]), 4))
         dp_line["value_is"] = "the selected form's K steps"
+        if outputs is not None:
+          outputs = step_outputs(eng, h2)
       elif rank == 0:
         dp_line["value_is"] = "the first form's K steps (the selected form was not faster over the contract's K)"
     else:
@@ -706,6 +752,8 @@ def main():
         out["cpu_baseline"] = cpu_baseline(cfg, xt, batch, args.cpu_budget, extra=extra)
       except Exception as err:   # the GPU line must not be lost to the host-side baseline (e.g. no compiler on the box)
         out["cpu_baseline"] = {"value": None, "unit": "cells/s", "cores": 0, "kind": "port", "sample": f"failed: {err}"[:200]}
+    if outputs is not None:
+      out["dump_outputs"] = dump_outputs(args.dump_outputs, outputs)
     print(json.dumps(out), flush=True)
   eng.close()
   cp.close()

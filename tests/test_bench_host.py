@@ -78,3 +78,26 @@ def test_the_line_carries_a_longer_run_and_the_graph_flag_is_gone():
   r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
   assert r.returncode == 0 and "--graph" not in r.stdout and "--steps" in r.stdout
 
+
+
+def test_dump_outputs_are_float32_within_the_budget_and_sampled_alike(tmp_path):
+  """--dump-outputs: one float32 .npy per array; over the budget, the large arrays keep a seeded sample of their elements -- the same
+  elements on every run, so two builds' dumps compare element for element."""
+  rng = np.random.default_rng(0)
+  arrays = {"params.out.W": rng.normal(size=(128, 6000)), "params.out.b": rng.normal(size=6000), "metrics.loss": np.array([1.5])}
+  whole = bench.dump_outputs(str(tmp_path / "whole"), arrays)
+  assert whole["files"] == 3 and whole["sampled"] == []
+  for k, v in arrays.items():
+    got = np.load(tmp_path / "whole" / f"{k}.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+  budget = 1 << 20
+  cut = [bench.dump_outputs(str(tmp_path / d), arrays, budget=budget) for d in ("a", "b")]
+  assert cut[0] == dict(cut[1], dir=cut[0]["dir"]) and cut[0]["sampled"] == ["params.out.W"]
+  assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= budget
+  for k in arrays:
+    assert np.array_equal(np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy"))
+  sample = np.load(tmp_path / "a" / "params.out.W.npy")
+  assert sample.ndim == 1 and 0 < sample.size < arrays["params.out.W"].size
+  assert np.isin(sample, arrays["params.out.W"].astype(np.float32)).all()
+  r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
+  assert r.returncode == 0 and "--dump-outputs" in r.stdout
