@@ -237,6 +237,14 @@ int smx_metrics_history(smx_model* m, int32_t n_steps, float* host);
 /* Validation loss: eval-mode forward (moving BN stats, no dropout) + ELBO, no
  * update (valid_freq loop of BetaVAE.fit). */
 int smx_eval_step(smx_model* m, const int32_t* row_ids, int32_t batch, smx_metrics* out);
+/* Monte-Carlo draws per cell of the later smx_train_step(_graph) / smx_train_steps / smx_eval_step calls
+ * (SingleCellModel.fit(sample_shape), sisua/train.py:138,146; default 1).  A step of `batch` cells then runs on
+ * n_draws x batch stacked rows, draw-major (row r = draw r / batch of cell r % batch): the encoder-side noise of
+ * every row is its cell's (sample index 0), the draw-side noise (latent draws, the decoder's dropout) takes sample
+ * index r / batch, and the ELBO scalars are means over cells and draws.  The row buffers grow to n_draws x
+ * max_batch on first use; captured graphs are dropped whenever the count changes.  SMX_ERR_INVALID for
+ * n_draws < 1, for FactorVAE / SemiFVAE with n_draws > 1 and for a data-parallel model (world > 1). */
+int smx_set_train_draws(smx_model* m, int32_t n_draws);
 
 /* Eval-mode forward for predict/encode/decode (single_cell_model.py:119-211):
  * writes distribution parameters into caller-owned buffers (any may be NULL).

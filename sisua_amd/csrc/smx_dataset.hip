@@ -61,7 +61,7 @@ int smx_dataset_upload_csr(smx_model* m, const int64_t* indptr, const int32_t* c
   int rc;
   m->x_csr = true;
   if ((rc = dmalloc(&m->csr_indptr, (size_t)n_cells + 1)) || (rc = dmalloc(&m->csr_cols, (size_t)std::max<int64_t>(nnz, 1))) ||
-      (rc = dmalloc(&m->csr_vals, (size_t)std::max<int64_t>(nnz, 1))) || (rc = dmalloc(&m->xbatch, (size_t)m->Bmax * m->Gp)) ||
+      (rc = dmalloc(&m->csr_vals, (size_t)std::max<int64_t>(nnz, 1))) || (rc = dmalloc(&m->xbatch, (size_t)m->Rmax * m->Gp)) ||
       (rc = dmalloc(&m->lgx1, (size_t)n_cells)))
     return rc;
   m->X = m->xbatch;   // (non-null: "a dataset is resident"; csr_stage fills it per pass)

@@ -37,11 +37,19 @@ struct NoiseKey {
   uint32_t step;     // optimiser step (counter word 2) when step_ptr == nullptr
   uint32_t stream;   // stream | sample << 8 (counter word 3)
   const uint32_t* step_ptr;  // device-resident step counter (graph replay); overrides `step`
+  uint32_t draw_rows;        // rows per Monte-Carlo draw of a stacked pass (row r is draw r / draw_rows); 0: one draw
 };
 
 __device__ inline U4 philox_block(const NoiseKey& nk, uint32_t cell_id, uint32_t col_block) {
   const uint32_t step = nk.step_ptr ? *nk.step_ptr : nk.step;
   return philox4x32_10(col_block, cell_id, step, nk.stream, nk.k0, nk.k1);
+}
+
+// the key of row `row` of a stacked pass: draw s = row / draw_rows takes sample index (sample + s) of the stream word
+__device__ inline U4 philox_row(const NoiseKey& nk, uint32_t row, uint32_t cell_id, uint32_t col_block) {
+  const uint32_t step = nk.step_ptr ? *nk.step_ptr : nk.step;
+  const uint32_t stream = nk.draw_rows ? nk.stream + ((row / nk.draw_rows) << 8) : nk.stream;
+  return philox4x32_10(col_block, cell_id, step, stream, nk.k0, nk.k1);
 }
 
 __device__ inline float u24(uint32_t w) { return (float)(w >> 8) * 5.9604644775390625e-08f; }  // 2^-24

@@ -383,7 +383,7 @@ int smx_k_noise(uint64_t seed, int32_t stream, int32_t step, int32_t sample, con
   SMX_HIP(hipMemcpy(dIds, cell_ids, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice));
   NoiseKey nk;
   nk.k0 = (uint32_t)(seed & 0xFFFFFFFFu); nk.k1 = (uint32_t)(seed >> 32); nk.step = (uint32_t)step;
-  nk.stream = (uint32_t)((stream & 0xFF) | ((sample & 0xFFFFFF) << 8)); nk.step_ptr = nullptr;
+  nk.stream = (uint32_t)((stream & 0xFF) | ((sample & 0xFFFFFF) << 8)); nk.step_ptr = nullptr; nk.draw_rows = 0;
   rc = launch_noise_probe(nullptr, nk, dIds, B, width, dropout_p, dM, dN);
   if (rc == SMX_OK) {
     SMX_HIP(hipDeviceSynchronize());

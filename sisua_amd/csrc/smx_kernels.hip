@@ -324,7 +324,7 @@ __device__ inline void latent_tile_to_lds(const LatentArgs& a, float* zs, bool s
       const float4 mq = m4[it];
       if (a.stochastic) {
         float4 nq = n4[it];
-        if (!a.inj_eps) nq = normal4(philox_block(a.nk, a.cell_base + cell[it], (uint32_t)(d0 >> 2)));
+        if (!a.inj_eps) nq = normal4(philox_row(a.nk, (uint32_t)b, a.cell_base + cell[it], (uint32_t)(d0 >> 2)));
         const float4 sr = s4[it];
         auto one = [&](int e, float mu, float s_raw, float nn, float& z, float& s, float& en) {
           if (d0 + e < a.D) {
@@ -556,7 +556,7 @@ __device__ inline void bn_act_fwd_body(const BnFwdArgs& a, const int bid) {
       if (a.inj_mask) mult = SMALL ? mahead : a.inj_mask[(long)r * a.inj_ld + col];
       else {
         const uint32_t cell = a.cell_base + (uint32_t)(a.rows ? a.rows[r] : r);
-        const U4 w = philox_block(a.nk, cell, (uint32_t)(col >> 2));
+        const U4 w = philox_row(a.nk, (uint32_t)r, cell, (uint32_t)(col >> 2));
         mult = dropout_mult1(w, col & 3, a.drop_p, scale);
       }
       h *= mult;
@@ -1108,7 +1108,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_wide_fwd_kernel(BnFwdArgs a) {
     float mult = mpre;
     if (!a.inj_mask) {
       const uint32_t cell = a.cell_base + (uint32_t)(a.rows ? a.rows[r] : r);
-      const U4 w = philox_block(a.nk, cell, (uint32_t)(col >> 2));
+      const U4 w = philox_row(a.nk, (uint32_t)r, cell, (uint32_t)(col >> 2));
       mult = dropout_mult1(w, col & 3, a.drop_p, scale);
     }
     h *= mult;
@@ -1252,7 +1252,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_sync_apply_fwd_kernel(BnFwdArgs
       if (a.inj_mask) mult = a.inj_mask[(long)r * a.inj_ld + col];
       else {
         const uint32_t cell = a.cell_base + (uint32_t)(a.rows ? a.rows[r] : r);
-        mult = dropout_mult1(philox_block(a.nk, cell, (uint32_t)(col >> 2)), col & 3, a.drop_p, scale);
+        mult = dropout_mult1(philox_row(a.nk, (uint32_t)r, cell, (uint32_t)(col >> 2)), col & 3, a.drop_p, scale);
       }
       h *= mult;
     }
@@ -1347,7 +1347,7 @@ __global__ __launch_bounds__(64) void latent_fwd_quad_kernel(LatentArgs a) {
       const float sr[4] = {s4.x, s4.y, s4.z, s4.w};
       float4 n4;
       if (a.inj_eps) n4 = *reinterpret_cast<const float4*>(a.inj_eps + (long)b * a.inj_ld + d0);
-      else n4 = normal4(philox_block(a.nk, a.cell_base + (uint32_t)(a.rows ? a.rows[b] : b), (uint32_t)(d0 >> 2)));
+      else n4 = normal4(philox_row(a.nk, (uint32_t)b, a.cell_base + (uint32_t)(a.rows ? a.rows[b] : b), (uint32_t)(d0 >> 2)));
       const float nn[4] = {n4.x, n4.y, n4.z, n4.w};
 #pragma unroll
       for (int e = 0; e < 4; ++e)
@@ -1388,7 +1388,7 @@ __global__ __launch_bounds__(256) void latent_fwd_kernel(LatentArgs a) {
         sig = softplusf(a.lat[(long)b * a.ld + a.Dp + d] + SMX_SOFTPLUS_INV_1);
         if (a.inj_eps) eps = a.inj_eps[(long)b * a.inj_ld + d];
         else {
-          const float4 n = normal4(philox_block(a.nk, cell, (uint32_t)(d >> 2)));
+          const float4 n = normal4(philox_row(a.nk, (uint32_t)b, cell, (uint32_t)(d >> 2)));
           eps = (d & 3) == 0 ? n.x : (d & 3) == 1 ? n.y : (d & 3) == 2 ? n.z : n.w;
         }
         z = mu + sig * eps;
@@ -1435,7 +1435,7 @@ __global__ __launch_bounds__(256) void mixlat_fwd_kernel(MixLatArgs a) {
   float logpi, pi;
   mixlat_softmax(a, lat, lane, logpi, pi);
   // the component: the first c whose running sum of pi reaches the cell's uniform (sums in component order)
-  const float u = u24(philox_block(a.nk_pick, cell, 0u).x);
+  const float u = u24(philox_row(a.nk_pick, (uint32_t)b, cell, 0u).x);
   int k = 0;
   float run = 0.f;
   for (int c = 0; c < a.C; ++c) {
@@ -1448,7 +1448,7 @@ __global__ __launch_bounds__(256) void mixlat_fwd_kernel(MixLatArgs a) {
   if (live) {
     if (a.inj_eps) eps = a.inj_eps[(long)b * a.inj_ld + lane];
     else {
-      const float4 n = normal4(philox_block(a.nk, cell, (uint32_t)(lane >> 2)));
+      const float4 n = normal4(philox_row(a.nk, (uint32_t)b, cell, (uint32_t)(lane >> 2)));
       eps = (lane & 3) == 0 ? n.x : (lane & 3) == 1 ? n.y : (lane & 3) == 2 ? n.z : n.w;
     }
   }
@@ -1967,7 +1967,7 @@ __global__ void lib_latent_fwd_kernel(LibLatentArgs a) {
   const float mu = a.latl[(long)b * a.ld], sig = softplusf(a.latl[(long)b * a.ld + 1] + SMX_SOFTPLUS_INV_1);
   float eps;
   if (a.inj_eps) eps = a.inj_eps[(long)b * a.inj_ld];
-  else eps = normal4(philox_block(a.nk, a.cell_base + (uint32_t)src, 0u)).x;
+  else eps = normal4(philox_row(a.nk, (uint32_t)b, a.cell_base + (uint32_t)src, 0u)).x;
   const float mp = a.library[src * 2], vp = a.library[src * 2 + 1];
   const float sp = sqrtf(vp);
   a.l[b] = mu + sig * eps;

@@ -193,6 +193,9 @@ struct smx_model {
   // sum-of-squares slots written by the weight-gradient products (per-tensor clipnorm without a separate pass)
   float* sq_slots = nullptr; std::vector<int> sq_first, sq_count; std::vector<char> sq_reduced; int sq_total_first = 0;
   int G = 0, Gp = 0, D = 0, Dp = 0, k = 0, Bmax = 0;
+  // Monte-Carlo draws per cell of a training / evaluation step (smx_set_train_draws): the step runs on draws x batch stacked rows
+  // (draw-major), row-proportional buffers hold Rmax >= draws x Bmax rows
+  int train_draws = 1, Rmax = 0;
   bool stochastic = true, scvi = false, scale = false, fvae = false;
   bool mixpost = false;      // SMX_MODEL_SCALE_POST: q(z|x) a mixture of cfg.n_components diagonal Gaussians (lat head: 1 + 2 C planes)
   int lat_planes = 2;        // planes of width Dp of the latent head's output: 2 (mu, raw sigma), 1 (deterministic), 1 + 2 C (mixture posterior)
@@ -234,7 +237,7 @@ struct smx_model {
   float* metrics_pin = nullptr;   // pinned landing area of read_metrics: 8 ELBO scalars + one gradient norm per tensor
   float* score_pin = nullptr; size_t score_pin_floats = 0;   // pinned landing area of the scoring entry points' results (smx_scoring.hip: score_landing)
   float* mhist = nullptr; size_t mhist_cap = 0; int32_t mhist_steps = 0;   // ELBO scalars of every step of the last train_steps call
-  int32_t staged_steps = 0, staged_batch = 0;   // row ids made resident by smx_train_stage for the next smx_train_steps(order = NULL)
+  int32_t staged_steps = 0, staged_batch = 0, staged_draws = 1;   // row ids made resident by smx_train_stage for the next smx_train_steps(order = NULL)
   StepState* state3 = nullptr;  // [0],[1]: per-step state by parity, [2]: master counter
   int par = 0; uint32_t h_next = 0;
   MetricsArgs pending_metrics; bool have_pending_metrics = false, metrics_before_allreduce = false;
@@ -342,6 +345,7 @@ struct Pass {
   int training = 1;
   int sample = 0;
   int global_batch = 0;
+  int draw_rows = 0;               // > 0: the pass stacks B / draw_rows Monte-Carlo draws of draw_rows cells; the draw-side noise keys carry it
 };
 
 // smx_model.hip
@@ -350,6 +354,8 @@ int build_mlp(smx_model* m, std::vector<MlpLayer>& mlp, const char* prefix, int 
               int stream0, float drop_p, bool batchnorm, float leak = 0.f);
 void release_csr(smx_model* m);
 NoiseKey make_key(smx_model* m, int stream, int sample, bool training);
+int alloc_rows(smx_model* m, size_t R);
+void set_row_caps(smx_model* m, size_t rows);
 const Injected* inj(smx_model* m, int stream);
 void pack(const TensorInfo& t, const float* host, std::vector<float>& dev);
 void unpack(const TensorInfo& t, const std::vector<float>& dev, float* host, float scale);
@@ -373,7 +379,7 @@ int csr_stage(smx_model* m, Pass& ps);
 int check_rows(smx_model* m, const int32_t* ids, size_t n);
 int read_metrics(smx_model* m, smx_metrics* out);
 int setup_pass(smx_model* m, Pass& ps, const int32_t* row_ids, const float* host_x, const float* host_library,
-               int32_t batch, int training, int sample);
+               int32_t batch, int training, int sample, int draw_rows = 0);   // draw_rows > 0: row_ids are stacked draws (up to Rmax rows)
 // smx_predict.hip
 bool stacked_scoring_ok(const smx_model* m);
 bool head_fused_ok(const smx_model* m, int B);   // a training step of B cells takes the one-launch output head (smx_step.hip)

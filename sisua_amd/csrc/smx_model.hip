@@ -61,6 +61,7 @@ NoiseKey make_key(smx_model* m, int stream, int sample, bool training) {
   nk.step = 0;
   nk.stream = (uint32_t)((stream & 0xFF) | ((sample & 0xFFFFFF) << 8));
   nk.step_ptr = training ? &cur_state(m)->step : nullptr;
+  nk.draw_rows = 0;
   return nk;
 }
 
@@ -124,6 +125,115 @@ double tuning(const char* name, double dflt) {
   auto it = mp.find(name);
   return it == mp.end() ? dflt : it->second;
 }
+}  // namespace smx
+
+namespace smx {
+
+// the buffers with one row per row of a pass (what alloc_rows owns)
+static std::vector<void**> row_buffers(smx_model* m) {
+  std::vector<void**> v;
+  auto add = [&](auto*& p) { v.push_back(reinterpret_cast<void**>(&p)); };
+  for (auto* mlp : {&m->enc, &m->encl, &m->dec})
+    for (auto& L : *mlp) { add(L.xhat); add(L.out_buf); add(L.dpre); add(L.inv_std); add(L.noise); }
+  add(m->bigk_part); add(m->slab); add(m->latbuf); add(m->dlat); add(m->z); add(m->noise_eps); add(m->sig); add(m->eps); add(m->kl);
+  add(m->P); add(m->dP); add(m->llk_part); add(m->llk_y); add(m->llk_o); add(m->rows2[0]); add(m->rows2[1]);
+  add(m->resp); add(m->dklz); add(m->tril_part); add(m->zmean); add(m->zpick);
+  add(m->raw); add(m->draw); add(m->rho); add(m->latlbuf); add(m->dlatl); add(m->lsmp); add(m->lsig); add(m->leps); add(m->kl_l); add(m->dl);
+  for (int j = 0; j < SMX_MAX_LABELS; ++j) { add(m->laby_raw[j]); add(m->laby_draw[j]); }
+  if (m->x_csr) add(m->xbatch);
+  return v;
+}
+
+// allocates every row buffer for R rows into the (null) pointers of row_buffers.  Knob alloc_rows_fail = n (test hook): the n-th
+// allocation reports SMX_ERR_NOMEM, as a hipMalloc beyond the device's memory would
+static int alloc_rows_into(smx_model* m, size_t R) {
+  const smx_config* cfg = &m->cfg;
+  const size_t B = R;
+  const int fail_at = (int)tuning("alloc_rows_fail", 0.0);
+  int n_alloc = 0;
+  auto dm = [&](auto** p, size_t n) -> int {
+    if (fail_at > 0 && ++n_alloc >= fail_at) { set_error("hipMalloc failed: out of memory (knob alloc_rows_fail)"); return SMX_ERR_NOMEM; }
+    return dmalloc(p, n);
+  };
+  int rc = SMX_OK;
+  if (m->x_csr && (rc = dm(&m->xbatch, B * m->Gp))) return rc;
+  m->max_feat_p = m->Dp;
+  auto alloc_mlp = [&](std::vector<MlpLayer>& mlp) {
+    for (auto& L : mlp) {
+      if (L.out_p > m->max_feat_p) m->max_feat_p = L.out_p;
+      if ((rc = dm(&L.xhat, B * L.out_p))) return rc;
+      if ((rc = dm(&L.out_buf, B * L.out_p))) return rc;
+      if ((rc = dm(&L.dpre, B * L.out_p))) return rc;
+      if ((rc = dm(&L.inv_std, (size_t)L.out_p))) return rc;
+      if ((rc = dm(&L.noise, B * L.out_p))) return rc;
+    }
+    return (int)SMX_OK;
+  };
+  if ((rc = alloc_mlp(m->enc)) || (rc = alloc_mlp(m->encl)) || (rc = alloc_mlp(m->dec))) return rc;
+  for (auto& L : m->disc) if (L.out_p > m->max_feat_p) m->max_feat_p = L.out_p;
+  const size_t lat_ld = (size_t)m->lat_planes * (size_t)m->Dp;
+  const size_t ldp = (size_t)m->k * m->Gp;
+  // wide panels: scratch for the per-slice slabs of the products that contract over the gene axis (smx_bigk.hip)
+  if (m->Gp >= std::min(4096, head_fused_min_genes())) {
+    if ((rc = dm(&m->bigk_part, (size_t)SMX_BIGK_MAX_SLICES * B * m->max_feat_p))) return rc;
+    if (!m->hf_tab) {   // (not a row buffer: allocated once, at model creation)
+      float* tab = nullptr;
+      if ((rc = dmalloc(&tab, (size_t)SMX_HEAD_FUSED_TAB_BYTES / 4))) return rc;
+      m->hf_tab = tab;
+      if ((rc = head_fused_prepare())) return rc;
+    }
+  }
+  if ((rc = dm(&m->slab, (size_t)(64 * 3 + SMX_MAX_LABELS + 1) * B * m->max_feat_p)) || (rc = dm(&m->latbuf, B * lat_ld)) || (rc = dm(&m->dlat, B * lat_ld)) ||
+      (rc = dm(&m->z, B * m->Dp)) || (rc = dm(&m->noise_eps, B * m->Dp)) || (rc = dm(&m->sig, B * m->Dp)) || (rc = dm(&m->eps, B * m->Dp)) ||
+      (rc = dm(&m->kl, B)) || (rc = dm(&m->P, B * ldp)) || (rc = dm(&m->dP, B * ldp)) ||
+      (rc = dm(&m->llk_part, B * (size_t)std::max(std::max(loss_chunks_max(m->Gp), head_loss_chunks(m->Gp)), 256))) || (rc = dm(&m->llk_y, B)) || (rc = dm(&m->llk_o, B)) ||
+      (rc = dm(&m->rows2[0], B)) || (rc = dm(&m->rows2[1], B)))
+    return rc;
+  if (m->scale && ((rc = dm(&m->resp, B * 32)) || (rc = dm(&m->dklz, B * m->Dp)))) return rc;
+  if (m->scale_tril && (rc = dm(&m->tril_part, (size_t)cfg->n_components * ((B + 7) / 8) * m->D * (m->D + 2)))) return rc;
+  if (m->mixpost && ((rc = dm(&m->resp, B * 32)) || (rc = dm(&m->zmean, B * m->Dp)) || (rc = dm(&m->zpick, B)))) return rc;
+  if (m->scvi) {
+    if ((rc = dm(&m->raw, B * ldp)) || (rc = dm(&m->draw, B * ldp)) || (rc = dm(&m->rho, B * m->Gp)) ||
+        (rc = dm(&m->latlbuf, B * 32)) || (rc = dm(&m->dlatl, B * 32)) || (rc = dm(&m->lsmp, B)) ||
+        (rc = dm(&m->lsig, B)) || (rc = dm(&m->leps, B)) || (rc = dm(&m->kl_l, B)) || (rc = dm(&m->dl, B)))
+      return rc;
+  }
+  for (int j = 0; j < m->n_heads; ++j) {
+    const size_t ld = m->tensors[m->t_labW[j]].ld;
+    if ((rc = dm(&m->laby_raw[j], B * ld)) || (rc = dm(&m->laby_draw[j], B * ld))) return rc;
+  }
+  return SMX_OK;
+}
+
+// Every buffer with one row per row of a pass, for R rows: at model creation R = max_batch; smx_set_train_draws regrows them to
+// draws x max_batch (the stacked rows of a multi-draw step).  All or nothing: the new set is allocated beside the old one, which is
+// freed only when every allocation succeeded; on failure the model keeps its previous buffers and Rmax.  The caller has synchronised
+// and sets the routing capacities (set_row_caps).
+int alloc_rows(smx_model* m, size_t R) {
+  const std::vector<void**> bufs = row_buffers(m);
+  std::vector<void*> old(bufs.size());
+  for (size_t i = 0; i < bufs.size(); ++i) { old[i] = *bufs[i]; *bufs[i] = nullptr; }
+  const int rc = alloc_rows_into(m, R);
+  for (size_t i = 0; i < bufs.size(); ++i) {
+    void* drop = rc == SMX_OK ? old[i] : *bufs[i];
+    if (rc != SMX_OK) *bufs[i] = old[i];
+    if (drop) hipFree(drop);
+  }
+  if (rc != SMX_OK) return rc;
+  m->Rmax = (int)R;
+  if (m->x_csr) m->X = m->xbatch;   // (the sparse store: m->X aliases its expansion tile)
+  return SMX_OK;
+}
+
+// The capacities the routing predicates of smx_step.hip read (slab / bigk scratch, the tril prior's partials), for `rows` rows of a
+// pass -- max_batch at one draw, draws x max_batch otherwise -- not the allocation's: an engine grown for several draws and set back to
+// one routes exactly as a fresh engine.  rows <= Rmax.
+void set_row_caps(smx_model* m, size_t rows) {
+  m->slab_cap = (size_t)(64 * 3 + SMX_MAX_LABELS + 1) * rows * m->max_feat_p;
+  m->bigk_floats = m->bigk_part ? (size_t)SMX_BIGK_MAX_SLICES * rows * m->max_feat_p : 0;
+  m->tril_part_floats = m->scale_tril ? (size_t)m->cfg.n_components * ((rows + 7) / 8) * m->D * (m->D + 2) : 0;
+}
+
 }  // namespace smx
 
 extern "C" {
@@ -331,24 +441,10 @@ int smx_model_create(const smx_config* cfg, smx_model** out) {
   }
   // ---- activations ----
   const size_t B = m->Bmax;
-  m->max_feat_p = m->Dp;
-  auto alloc_mlp = [&](std::vector<MlpLayer>& mlp) {
-    for (auto& L : mlp) {
-      if (L.out_p > m->max_feat_p) m->max_feat_p = L.out_p;
-      if ((rc = dmalloc(&L.xhat, B * L.out_p))) return rc;
-      if ((rc = dmalloc(&L.out_buf, B * L.out_p))) return rc;
-      if ((rc = dmalloc(&L.dpre, B * L.out_p))) return rc;
-      if ((rc = dmalloc(&L.inv_std, (size_t)L.out_p))) return rc;
-      if ((rc = dmalloc(&L.noise, B * L.out_p))) return rc;
-    }
-    return (int)SMX_OK;
-  };
-  if ((rc = alloc_mlp(m->enc)) || (rc = alloc_mlp(m->encl)) || (rc = alloc_mlp(m->dec))) return fail(rc);
   if (m->fvae) {   // the discriminator sees the stacked batch [z ; z_perm]: 2 B rows
     int up = 32;
     for (auto& L : m->disc) {
       up = std::max(up, L.out_p);
-      if (L.out_p > m->max_feat_p) m->max_feat_p = L.out_p;
       if ((rc = dmalloc(&L.xhat, 2 * B * L.out_p)) || (rc = dmalloc(&L.out_buf, 2 * B * L.out_p)) || (rc = dmalloc(&L.dpre, 3 * B * L.out_p)))   // (d pre: both backward sweeps as rows of one buffer)
         return fail(rc);
     }
@@ -358,41 +454,10 @@ int smx_model_create(const smx_config* cfg, smx_model** out) {
         (rc = dmalloc(&m->disc_dpre, B * up)) || (rc = dmalloc(&m->disc_db, (size_t)up)))
       return fail(rc);
   }
-  m->slab_cap = (size_t)(64 * 3 + SMX_MAX_LABELS + 1) * B * m->max_feat_p;
-  const size_t lat_ld = (size_t)m->lat_planes * (size_t)m->Dp;
-  const size_t ldp = (size_t)m->k * m->Gp;
-  // wide panels: scratch for the per-slice slabs of the products that contract over the gene axis (smx_bigk.hip)
-  if (m->Gp >= std::min(4096, head_fused_min_genes())) {
-    m->bigk_floats = (size_t)SMX_BIGK_MAX_SLICES * B * m->max_feat_p;
-    if ((rc = dmalloc(&m->bigk_part, m->bigk_floats))) return fail(rc);
-    float* tab = nullptr;
-    if ((rc = dmalloc(&tab, (size_t)SMX_HEAD_FUSED_TAB_BYTES / 4))) return fail(rc);
-    m->hf_tab = tab;
-    if ((rc = head_fused_prepare())) return fail(rc);
-  }
-  if ((rc = dmalloc(&m->slab, m->slab_cap)) || (rc = dmalloc(&m->latbuf, B * lat_ld)) || (rc = dmalloc(&m->dlat, B * lat_ld)) ||
-      (rc = dmalloc(&m->z, B * m->Dp)) || (rc = dmalloc(&m->noise_eps, B * m->Dp)) || (rc = dmalloc(&m->sig, B * m->Dp)) || (rc = dmalloc(&m->eps, B * m->Dp)) ||
-      (rc = dmalloc(&m->kl, B)) || (rc = dmalloc(&m->P, B * ldp)) || (rc = dmalloc(&m->dP, B * ldp)) ||
-      (rc = dmalloc(&m->llk_part, B * (size_t)std::max(std::max(loss_chunks_max(m->Gp), head_loss_chunks(m->Gp)), 256))) || (rc = dmalloc(&m->llk_y, B)) || (rc = dmalloc(&m->llk_o, B)) ||
-      (rc = dmalloc(&m->rows2[0], B)) || (rc = dmalloc(&m->rows2[1], B)) || (rc = dmalloc(&m->state3, (size_t)3)) ||
-      (rc = dmalloc(&m->hostX, B * m->Gp)) || (rc = dmalloc(&m->hostLib, B * 2)) || (rc = dmalloc(&m->hostLgx1, B)))
+  if ((rc = dmalloc(&m->state3, (size_t)3)) || (rc = dmalloc(&m->hostX, B * m->Gp)) || (rc = dmalloc(&m->hostLib, B * 2)) ||
+      (rc = dmalloc(&m->hostLgx1, B)) || (rc = alloc_rows(m, B)))
     return fail(rc);
-  if (m->scale && ((rc = dmalloc(&m->resp, B * 32)) || (rc = dmalloc(&m->dklz, B * m->Dp)))) return fail(rc);
-  if (m->scale_tril) {
-    m->tril_part_floats = (size_t)cfg->n_components * ((B + 7) / 8) * m->D * (m->D + 2);
-    if ((rc = dmalloc(&m->tril_part, m->tril_part_floats))) return fail(rc);
-  }
-  if (m->mixpost && ((rc = dmalloc(&m->resp, B * 32)) || (rc = dmalloc(&m->zmean, B * m->Dp)) || (rc = dmalloc(&m->zpick, B)))) return fail(rc);
-  if (m->scvi) {
-    if ((rc = dmalloc(&m->raw, B * ldp)) || (rc = dmalloc(&m->draw, B * ldp)) || (rc = dmalloc(&m->rho, B * m->Gp)) ||
-        (rc = dmalloc(&m->latlbuf, B * 32)) || (rc = dmalloc(&m->dlatl, B * 32)) || (rc = dmalloc(&m->lsmp, B)) ||
-        (rc = dmalloc(&m->lsig, B)) || (rc = dmalloc(&m->leps, B)) || (rc = dmalloc(&m->kl_l, B)) || (rc = dmalloc(&m->dl, B)))
-      return fail(rc);
-  }
-  for (int j = 0; j < m->n_heads; ++j) {
-    const size_t ld = m->tensors[m->t_labW[j]].ld;
-    if ((rc = dmalloc(&m->laby_raw[j], B * ld)) || (rc = dmalloc(&m->laby_draw[j], B * ld))) return fail(rc);
-  }
+  set_row_caps(m, B);
   // ---- optimiser chunk table ----
   std::vector<OptChunk> chunks;
   // floats per optimiser workgroup

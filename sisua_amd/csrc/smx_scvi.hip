@@ -92,7 +92,7 @@ __global__ __launch_bounds__(NT) void scvi_head_train_kernel(ScviTrainArgs a) {
       mu_l = p0 + bl0; sraw_l = p1 + bl1;
       sig_l = softplusf(sraw_l + SMX_SOFTPLUS_INV_1);
       if (a.inj_eps) eps_l = eps_in;
-      else eps_l = normal4(philox_block(a.nk, a.cell_base + (uint32_t)src, 0u)).x;
+      else eps_l = normal4(philox_row(a.nk, (uint32_t)b, a.cell_base + (uint32_t)src, 0u)).x;
       mp = mp_in; vp = vp_in;
       const float sp = sqrtf(vp);
       const float l = mu_l + sig_l * eps_l;

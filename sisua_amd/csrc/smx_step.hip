@@ -23,6 +23,13 @@ static bool front_shapes_ok(smx_model* m, const Pass& ps) {
 }
 
 
+// a stream of the draw side (the latent draws, the decoder's dropout): row r of a stacked pass takes sample index r / draw_rows
+static NoiseKey draw_key(smx_model* m, int stream, const Pass& ps) {
+  NoiseKey nk = make_key(m, stream, ps.sample, ps.training != 0);
+  nk.draw_rows = (uint32_t)ps.draw_rows;
+  return nk;
+}
+
 // the model's products run from bf16 MFMAs on three-way split operands (flag "bf16x3": -1 = by size, SMX_BF16X3_MIN_WORK)
 static bool b3_on(const smx_model* m, const Pass& ps) {
   return m->flags.bf16x3 < 0 ? use_bf16x3((long)ps.B * m->Gp * m->k) : m->flags.bf16x3 != 0;
@@ -71,6 +78,7 @@ int mlp_forward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps, const 
     b.xhat = L.xhat; b.inv_std = L.inv_std; b.out = L.out_buf;
     b.drop_p = ps.training ? L.drop_p : 0.f;
     b.nk = make_key(m, L.stream, ps.sample, true);
+    if (&mlp == &m->dec) b.nk.draw_rows = (uint32_t)ps.draw_rows;   // (decoder dropout: a stream of the draw side)
     b.rows = ps.rows; b.cell_base = ps.cell_base;
     if (const Injected* ij = inj(m, L.stream)) { b.inj_mask = ij->d; b.inj_ld = ij->ld; }
     return b;
@@ -159,7 +167,7 @@ int mlp_forward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps, const 
     BnFwdArgs b = make_bn(L, m->slab, eff, g.slab_stride);
     if (bigk && bk.colmajor) { b.pre = bk.part; b.n_slabs = bk.n_slices; b.slab_stride = bk.slab_stride; b.wide = 1; }
     else if (!bigk && !dual && !with_front && g.c_colmajor) b.wide = 1;
-    if (!no_ahead && !sync && i == 0 && in_is_x && &mlp == &m->enc && ps.training && front_shapes_ok(m, ps) &&
+    if (!no_ahead && !sync && i == 0 && in_is_x && &mlp == &m->enc && ps.training && ps.draw_rows == 0 && front_shapes_ok(m, ps) &&
         !with_front && b.n_jobs == 0) {
       // the decoder's front launch (latent sample + first decoder layer) computes the whole latent tile in EVERY one of
       // its workgroups: its Philox draws (eps: ~1.2 us at batch 128, twice that at 256; dropout ~1 us) are made here
@@ -636,7 +644,7 @@ static bool scvi_train_args(smx_model* m, const Pass& ps, ScviTrainArgs* out) {
   a.hl = lL.out_buf; a.ldh = lL.out_p; a.Kl = lL.out_p;
   a.Wl = P_(m, m->t_latlW); a.ldwl = twl.ld; a.bl = P_(m, m->t_latlb);
   a.library = ps.lib; a.cell_base = ps.cell_base;
-  a.nk = make_key(m, ST_EPS_L, ps.sample, ps.training != 0);
+  a.nk = draw_key(m, ST_EPS_L, ps);
   if (const Injected* ij = inj(m, ST_EPS_L)) { a.inj_eps = ij->d; a.inj_ld = ij->ld; }
   a.kl_scale = c.beta / (float)ps.global_batch;
   a.latl = m->latlbuf; a.ldl = 32; a.l = m->lsmp; a.sig = m->lsig; a.eps = m->leps; a.kl = m->kl_l;
@@ -677,7 +685,7 @@ int forward_pass(smx_model* m, const Pass& ps, bool with_loss, bool backward, in
   if (m->mixpost) {   // SCALE read literally: the draw from the mixture-density posterior and its Monte-Carlo KL (never the fused front)
     MixLatArgs ma;
     ma.lat = m->latbuf; ma.ld = lat_ld; ma.B = ps.B; ma.D = m->D; ma.Dp = m->Dp; ma.C = c.n_components;
-    ma.nk = make_key(m, ST_EPS_Z, ps.sample, ps.training != 0); ma.nk_pick = make_key(m, ST_MIX_PICK, ps.sample, ps.training != 0);
+    ma.nk = draw_key(m, ST_EPS_Z, ps); ma.nk_pick = draw_key(m, ST_MIX_PICK, ps);
     ma.rows = ps.rows; ma.cell_base = ps.cell_base;
     if (const Injected* ij = inj(m, ST_EPS_Z)) { ma.inj_eps = ij->d; ma.inj_ld = ij->ld; }
     ma.z = m->z; ma.eps = m->eps; ma.zmean = m->zmean; ma.zstd = m->sig; ma.kl = m->kl; ma.resp = m->resp; ma.pick = m->zpick;
@@ -687,7 +695,7 @@ int forward_pass(smx_model* m, const Pass& ps, bool with_loss, bool backward, in
   LatentArgs la;
   la.stochastic = m->stochastic; la.relu = (c.latent_activation == SMX_ACT_RELU); la.training = ps.training;
   la.lat = m->latbuf; la.ld = lat_ld; la.B = ps.B; la.D = m->D; la.Dp = m->Dp;
-  la.nk = make_key(m, ST_EPS_Z, ps.sample, ps.training != 0);
+  la.nk = draw_key(m, ST_EPS_Z, ps);
   la.rows = ps.rows; la.cell_base = ps.cell_base;
   if (const Injected* ij = inj(m, ST_EPS_Z)) { la.inj_eps = ij->d; la.inj_ld = ij->ld; }
   if (m->ahead_front_eps && !la.inj_eps) { la.inj_eps = m->noise_eps; la.inj_ld = m->Dp; }
@@ -728,7 +736,7 @@ int forward_pass(smx_model* m, const Pass& ps, bool with_loss, bool backward, in
     if (!m->scvi_fused) {
       LibLatentArgs ll;
       ll.latl = m->latlbuf; ll.ld = 32; ll.B = ps.B; ll.library = ps.lib; ll.rows = ps.rows; ll.cell_base = ps.cell_base;
-      ll.nk = make_key(m, ST_EPS_L, ps.sample, ps.training != 0);
+      ll.nk = draw_key(m, ST_EPS_L, ps);
       if (const Injected* ij = inj(m, ST_EPS_L)) { ll.inj_eps = ij->d; ll.inj_ld = ij->ld; }
       ll.clip_library = c.clip_library;
       ll.l = m->lsmp; ll.sig = m->lsig; ll.eps = m->leps; ll.kl = m->kl_l;
@@ -1585,7 +1593,7 @@ int optimizer_pass(smx_model* m) {
 // identity rows; everything else -- labels, library prior, label mask, lgx1, noise keys -- keeps the resident row ids)
 int csr_stage(smx_model* m, Pass& ps) {
   if (!m->x_csr || ps.Xsrc != m->X) return SMX_OK;
-  SMX_REQUIRE(ps.rows != nullptr && ps.B <= m->Bmax, "sparse store: resident rows only");
+  SMX_REQUIRE(ps.rows != nullptr && ps.B <= m->Rmax, "sparse store: resident rows only");
   SMX_REQUIRE(!(ps.training && m->cfg.input_dropout > 0.f), "sparse store: input dropout is keyed by the dense store's rows (use the float32 / uint16 store)");
   SMX_CHECK(launch_csr_expand(m->st, m->csr_indptr, m->csr_cols, m->csr_vals, ps.rows, 0, ps.B, m->Gp, m->xbatch));
   ps.Xsrc = m->xbatch; ps.xrows = nullptr; ps.x_u16 = 0;
@@ -1600,6 +1608,7 @@ int train_sequence(smx_model* m, int B, bool with_begin, bool begin_from_master,
   Pass ps;
   ps.B = B; ps.rows = cur_rows(m); ps.xrows = ps.rows; ps.Xsrc = m->X; ps.x_u16 = m->x_u16; ps.lib = m->library; ps.lgx1 = m->lgx1;
   ps.cell_base = (uint32_t)m->cell_base; ps.training = 1; ps.sample = 0; ps.global_batch = B * m->world;
+  ps.draw_rows = m->train_draws > 1 ? B / m->train_draws : 0;   // (B: the stacked rows, draws x cells)
   m->seq_batch = B; m->seq_prepare_next = prepare_next ? 1 : 0;
   Timed t(m, "step");
   if (with_begin)
@@ -1736,9 +1745,9 @@ int launch_train(smx_model* m, int B, bool use_graph, int s_idx, int n_steps) {
 }
 
 int setup_pass(smx_model* m, Pass& ps, const int32_t* row_ids, const float* host_x, const float* host_library,
-                      int32_t batch, int training, int sample) {
-  SMX_REQUIRE(batch > 0 && batch <= m->Bmax, "batch must be in 1..max_batch");
-  ps.B = batch; ps.training = training; ps.sample = sample; ps.global_batch = batch;
+                      int32_t batch, int training, int sample, int draw_rows) {
+  SMX_REQUIRE(batch > 0 && batch <= (draw_rows > 0 ? m->Rmax : m->Bmax), "batch must be in 1..max_batch");
+  ps.B = batch; ps.training = training; ps.sample = sample; ps.global_batch = batch; ps.draw_rows = draw_rows;
   if (row_ids) {
     SMX_CHECK(check_rows(m, row_ids, (size_t)batch));
     // (through pinned staging of the library's own: measured, no gain -- 512 bytes from a pageable array take the runtime's fast path)
@@ -1758,9 +1767,55 @@ int setup_pass(smx_model* m, Pass& ps, const int32_t* row_ids, const float* host
   return SMX_OK;
 }
 
+// several draws per cell (smx_set_train_draws): what the step cannot take along
+int check_draws(smx_model* m) {
+  if (m->train_draws == 1) return SMX_OK;
+  SMX_REQUIRE(m->world == 1, "several draws per cell are single-GPU only: smx_set_train_draws(m, 1) before a data-parallel step");
+  SMX_REQUIRE(!m->use_injected, "injected noise (smx_set_noise) covers one draw: smx_set_train_draws(m, 1) first");
+  return SMX_OK;
+}
+
+// the routing capacities of stacked passes (set_row_caps) for the life of a train / eval call with several draws; every other pass -- one
+// draw, predict, scoring -- routes by the max_batch capacities, as on an engine that never took several draws
+struct DrawCaps {
+  smx_model* m;
+  explicit DrawCaps(smx_model* m_) : m(m_) { if (m->train_draws > 1) set_row_caps(m, (size_t)m->train_draws * m->Bmax); }
+  ~DrawCaps() { if (m->train_draws > 1) set_row_caps(m, (size_t)m->Bmax); }
+};
+
+// the row ids of n_steps minibatches of `batch` cells as the stacked rows of train_draws draws each, draw-major (row r of a step is
+// draw r / batch of cell r % batch); empty with one draw
+std::vector<int32_t> tile_draws(const smx_model* m, const int32_t* ids, int n_steps, int batch) {
+  std::vector<int32_t> out;
+  const int S = m->train_draws;
+  if (S == 1) return out;
+  out.resize((size_t)n_steps * S * batch);
+  for (int t = 0; t < n_steps; ++t)
+    for (int s = 0; s < S; ++s)
+      memcpy(out.data() + ((size_t)t * S + s) * batch, ids + (size_t)t * batch, (size_t)batch * sizeof(int32_t));
+  return out;
+}
+
 }  // namespace smx
 
 extern "C" {
+
+int smx_set_train_draws(smx_model* m, int32_t n_draws) {
+  SMX_REQUIRE(m, "null model");
+  SMX_REQUIRE(n_draws >= 1, "smx_set_train_draws: the number of draws must be >= 1");
+  SMX_REQUIRE(n_draws == 1 || !m->fvae, "smx_set_train_draws: FactorVAE / SemiFVAE train with one draw (permute_dims over stacked draws has no agreed reading)");
+  SMX_REQUIRE(n_draws == 1 || m->world == 1, "smx_set_train_draws: several draws per cell are single-GPU only (data parallel world > 1)");
+  SMX_REQUIRE((int64_t)n_draws * m->Bmax <= (int64_t)1 << 20, "smx_set_train_draws: draws x max_batch exceeds 2^20 stacked rows");
+  if (n_draws == m->train_draws) return SMX_OK;
+  SMX_CHECK(smx::head_sweep_join(m));
+  SMX_HIP(hipStreamSynchronize(m->st));
+  smx::drop_graphs(m);   // (a captured step bakes the stacked batch and the buffers in)
+  // (all or nothing: a failed grow leaves the buffers, Rmax and the draw count as they were)
+  if ((int64_t)n_draws * m->Bmax > m->Rmax) SMX_CHECK(smx::alloc_rows(m, (size_t)n_draws * m->Bmax));
+  m->train_draws = n_draws;
+  m->staged_steps = 0;
+  return SMX_OK;
+}
 
 int smx_train_step(smx_model* m, const int32_t* row_ids, int32_t batch, smx_metrics* out) {
   return smx_train_steps(m, row_ids, 1, batch, 0, out);
@@ -1772,11 +1827,14 @@ int smx_train_step_graph(smx_model* m, const int32_t* row_ids, int32_t batch, sm
 int smx_train_steps(smx_model* m, const int32_t* order, int32_t n_steps, int32_t batch, int use_graph, smx_metrics* out) {
   SMX_REQUIRE(m && n_steps > 0, "bad arguments");
   SMX_REQUIRE(batch > 0 && batch <= m->Bmax, "batch must be in 1..max_batch");
+  SMX_CHECK(smx::check_draws(m));
   if (order) {
     SMX_CHECK(check_rows(m, order, (size_t)n_steps * batch));
-    SMX_CHECK(upload_order(m, order, (size_t)n_steps * batch, (size_t)n_steps));
+    const std::vector<int32_t> tiled = smx::tile_draws(m, order, n_steps, batch);
+    SMX_CHECK(upload_order(m, tiled.empty() ? order : tiled.data(), (size_t)n_steps * batch * m->train_draws, (size_t)n_steps));
   } else {
-    SMX_REQUIRE(m->staged_steps == n_steps && m->staged_batch == batch, "order = NULL: no ids staged for this n_steps x batch (smx_train_stage)");
+    SMX_REQUIRE(m->staged_steps == n_steps && m->staged_batch == batch && m->staged_draws == m->train_draws,
+              "order = NULL: no ids staged for this n_steps x batch (smx_train_stage) and draw count");
   }
   m->staged_steps = 0;   // (staged ids serve one call)
   // flag opt_shard: the heads' Adam moments outside this rank's slice are stale.  Steps that will NOT take the sharded chain (a captured graph,
@@ -1785,7 +1843,8 @@ int smx_train_steps(smx_model* m, const int32_t* order, int32_t n_steps, int32_t
   if (m->opt_stale && (use_graph || !(m->flags.opt_shard && smx::dp_chain_ok(m) && smx::dp_shard_available(m)))) SMX_CHECK(smx_opt_gather(m));
   int rc = SMX_OK;
   ++m->params_epoch;   // (the parameters are about to change)
-  for (int s = 0; s < n_steps && rc == SMX_OK; ++s) rc = launch_train(m, batch, use_graph != 0, s, n_steps);
+  smx::DrawCaps caps(m);
+  for (int s = 0; s < n_steps && rc == SMX_OK; ++s) rc = launch_train(m, batch * m->train_draws, use_graph != 0, s, n_steps);
   { const int rj = smx::head_sweep_join(m); if (rc == SMX_OK) rc = rj; }   // every other entry point sees one stream
   if (rc != SMX_OK) return rc;
   if (m->use_injected) { m->use_injected = false; }
@@ -1798,9 +1857,11 @@ int smx_train_steps(smx_model* m, const int32_t* order, int32_t n_steps, int32_t
 int smx_train_stage(smx_model* m, const int32_t* order, int32_t n_steps, int32_t batch) {
   SMX_REQUIRE(m && order && n_steps > 0, "bad arguments");
   SMX_REQUIRE(batch > 0 && batch <= m->Bmax, "batch must be in 1..max_batch");
+  SMX_CHECK(smx::check_draws(m));
   SMX_CHECK(check_rows(m, order, (size_t)n_steps * batch));
-  SMX_CHECK(upload_order(m, order, (size_t)n_steps * batch, (size_t)n_steps));
-  m->staged_steps = n_steps; m->staged_batch = batch;
+  const std::vector<int32_t> tiled = smx::tile_draws(m, order, n_steps, batch);
+  SMX_CHECK(upload_order(m, tiled.empty() ? order : tiled.data(), (size_t)n_steps * batch * m->train_draws, (size_t)n_steps));
+  m->staged_steps = n_steps; m->staged_batch = batch; m->staged_draws = m->train_draws;
   return SMX_OK;
 }
 
@@ -1813,8 +1874,18 @@ int smx_metrics_history(smx_model* m, int32_t n_steps, float* host) {
 
 int smx_eval_step(smx_model* m, const int32_t* row_ids, int32_t batch, smx_metrics* out) {
   SMX_REQUIRE(m && row_ids, "bad arguments");
+  SMX_CHECK(smx::check_draws(m));
   Pass ps;
-  SMX_CHECK(setup_pass(m, ps, row_ids, nullptr, nullptr, batch, 0, 0));
+  smx::DrawCaps caps(m);
+  if (m->train_draws > 1) {   // the same draws as training, in eval mode: draw s of every cell keyed by sample index s
+    SMX_REQUIRE(batch > 0 && batch <= m->Bmax, "batch must be in 1..max_batch");
+    SMX_CHECK(check_rows(m, row_ids, (size_t)batch));
+    const std::vector<int32_t> tiled = smx::tile_draws(m, row_ids, 1, batch);
+    SMX_CHECK(setup_pass(m, ps, tiled.data(), nullptr, nullptr, batch * m->train_draws, 0, 0, batch));
+    SMX_HIP(hipStreamSynchronize(m->st));   // (the row ids went from `tiled`, a host vector about to go)
+  } else {
+    SMX_CHECK(setup_pass(m, ps, row_ids, nullptr, nullptr, batch, 0, 0));
+  }
   SMX_CHECK(forward_pass(m, ps, true, false));
   SMX_CHECK(read_metrics(m, out));
   return SMX_OK;

@@ -288,6 +288,12 @@ class Engine:
     check(self.lib.smx_metrics_history(self._h, int(n_steps), _fp(h)))
     return {k: h[:, i].copy() for i, k in enumerate(("loss", "nllk_x", "nllk_y", "kl", "kl_l", "tc", "dtc_loss", "nllk_o"))}
 
+  def set_train_draws(self, n_draws: int):
+    """Monte-Carlo draws per cell of the later train / eval steps (fit(sample_shape)): a step of B cells runs on n_draws x B
+    stacked rows, draw s of every cell keyed by Philox sample index s on the draw side (latent draws, decoder dropout); the ELBO
+    scalars are means over cells and draws (smx_set_train_draws)."""
+    check(self.lib.smx_set_train_draws(self._h, int(n_draws)))
+
   def eval_step(self, row_ids):
     ids = self._ids(row_ids)
     m = smx_metrics()

@@ -51,6 +51,19 @@ def _flatten(x):
   return [x]
 
 
+def train_draws(sample_shape) -> int:
+  """Monte-Carlo draws per cell of a training step: S = prod(sample_shape); (), [] and 1 all mean one draw."""
+  shape = (sample_shape,) if np.isscalar(sample_shape) else tuple(sample_shape)
+  dims = []
+  for s in shape:
+    if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, np.integer)):
+      raise ValueError(f"sample_shape must hold integers, got {sample_shape!r}")
+    if s <= 0:
+      raise ValueError(f"sample_shape must hold positive sizes, got {sample_shape!r}")
+    dims.append(int(s))
+  return int(np.prod(dims)) if dims else 1
+
+
 def _to_data(x, batch_size=64) -> BatchDataset:
   """single_cell_model.py:44-61: SingleCellOMIC -> its dataset; prepared dataset -> itself;
   raw ndarray(s) -> wrapped, further arrays assigned the next OMIC names in order."""
@@ -316,9 +329,21 @@ class SingleCellModel:
     draws `batch_size / world` of them per step (`dp_batch='global'`: the reference's global batch is preserved,
     SURVEY.md 8e) or `batch_size` (`dp_batch='per_rank'`); ONE RCCL all-reduce of the gradients per step;
     `sync_bn=True` adds SyncBatchNorm (statistics over the global batch, as the single process computes them);
-    every rank evaluates the validation cells; only rank 0 runs `checkpoint`."""
+    every rank evaluates the validation cells; only rank 0 runs `checkpoint`.
+
+    `sample_shape` (train.py:138,146): S = prod(sample_shape) latent draws per cell and step (smx_set_train_draws).  The
+    encoders run on the cells, each cell gets S draws (draw s: Philox sample index s on the draw side -- the latent draws and
+    the decoder's dropout), the decoder and the heads run on the S x B stacked rows (BatchNorm statistics over all of them),
+    and the loss is the mean over cells and draws of -(llk_x + llk_outputs + alpha mask llk_y) + beta KL -- the plain
+    Monte-Carlo ELBO, not an importance-weighted bound ([3P-recall] odin's VariationalModel.elbo: the ELBO terms of the
+    `sample_shape` draws averaged over the sample axis).  Validation uses the same S in eval mode.  FactorVAE / SemiFVAE
+    and data parallel jobs take S = 1 only (ValueError)."""
     if str(optimizer).lower() != "adam":
       raise ValueError("only the 'adam' optimizer of configs/base.yaml is built")
+    n_draws = train_draws(sample_shape)
+    if n_draws > 1 and self._make_config().model == "fvae":
+      raise ValueError(f"{type(self).__name__}: sample_shape {sample_shape!r} -- FactorVAE / SemiFVAE train with one draw per cell "
+                       "(the discriminator's permute_dims over stacked draws has no agreed reading)")
     from sisua_amd import data as _data
     from sisua_amd.parallel import ControlPlane, attach_engine, env_rank_world
     self._opt = dict(lr=float(learning_rate), clipnorm=float(clipnorm or 0.0))
@@ -332,6 +357,8 @@ class SingleCellModel:
       cp, rank, local_rank, world = distributed, distributed.rank, self.device, distributed.world
     else:
       rank, local_rank, world = 0, 0, 1
+    if n_draws > 1 and world > 1:
+      raise ValueError(f"sample_shape {sample_shape!r}: several draws per cell are single-GPU only (world {world})")
     B, drop_rem, lo, hi = train.batch_size, train.drop_remainder, 0, train.n_obs
     if world > 1:
       if dp_batch == "global":
@@ -345,6 +372,7 @@ class SingleCellModel:
       self.device = local_rank
       cp = cp or ControlPlane(rank, world)
     e = self._ensure_engine(max(B, valid.batch_size if valid is not None else 1))
+    e.set_train_draws(n_draws)
     if world > 1 and e.world != world:
       self._dp_mode = attach_engine(e, cp)
       self._dp_calibrated = False

@@ -3,6 +3,7 @@
 timed steps' ids staged, all of them queued by ONE library call) -- without the rest of the bench line: the quick A/B of a knob or a build.
     SMX_TUNING=no_fold_dz python tools/dev/step_time.py 8kly            # knobs: docs/LAB_NOTES.md
     python tools/dev/step_time.py c5-shard --storage u16 --steps 100
+    python tools/dev/step_time.py 8kly --draws 4                           # fit(sample_shape=4): 4 x 128 stacked rows per step
 Prints three repetitions; under rocprofv3 (`rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 tools/dev/step_time.py ...`)
 `tools/prof_summary.py DIR` gives the per-kernel table and one step's timeline."""
 import argparse
@@ -19,6 +20,7 @@ def main():
   ap.add_argument("--storage", default=None, help="f32 / u16 / csr (default: f32, u16 at the c5-shard width as bench.py's secondary entry)")
   ap.add_argument("--steps", type=int, default=0)
   ap.add_argument("--warmup", type=int, default=30)
+  ap.add_argument("--draws", type=int, default=1, help="Monte-Carlo draws per cell (fit(sample_shape), smx_set_train_draws)")
   args = ap.parse_args()
   import bench
   from sisua_amd.engine import Engine
@@ -26,6 +28,7 @@ def main():
   extra.pop("cell_id_base", None)
   steps = args.steps or (100 if args.workload.startswith("c5") else 300)
   e = Engine(cfg, max_batch=b, device=0)
+  e.set_train_draws(args.draws)
   e.upload(x, storage=args.storage or ("u16" if args.workload.startswith("c5") else "f32"), **extra)
   o = bench.make_order(x.shape[0], b, steps + args.warmup)
   for _ in range(50):
@@ -37,7 +40,8 @@ def main():
     t = time.perf_counter()
     e.train_steps(None, steps, b, graph=False)
     e.synchronize()
-    print("%s: %.1f us per step (%d steps of %d cells)" % (args.workload, 1e6 * (time.perf_counter() - t) / steps, steps, b), flush=True)
+    print("%s: %.1f us per step (%d steps of %d cells, %d draws)" % (args.workload, 1e6 * (time.perf_counter() - t) / steps, steps, b, args.draws),
+          flush=True)
   e.close()
 
 
