@@ -1,7 +1,7 @@
 // smx_factor.hip -- the two small kernels of the FactorVAE discriminator (sisua/models/fvae.py:9-18: FVAE / SemiFVAE
 // are thin subclasses of odin's factorVAE / SemifactorVAE; the algorithm is Kim & Mnih 2018, Algorithm 2).  The
 // discriminator's Dense layers run on the generic products (smx_gemm.hip) and the bias + leaky-ReLU launches
-// (smx_kernels.hip); what is specific is
+// (smx_bn.hip); what is specific is
 //   permute_dims_kernel   z_perm: every latent dimension permuted over the minibatch independently.  The permutation of
 //                         dimension d is the rank of the cell's Philox uniform u[cell][d] within column d (ties by row),
 //                         so it depends on (seed, step, cell ids) only and the oracle draws the same one;

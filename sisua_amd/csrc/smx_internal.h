@@ -110,7 +110,7 @@ int launch_dgemm(hipStream_t st, const GemmArgs& g);
 int suggest_split_k(int M, int N, int K);
 
 // --------------------------------------------------------------------------
-// Fused kernels (smx_kernels.hip)
+// Fused kernels (smx_loss.hip, smx_bn.hip, smx_latent.hip, smx_scvi.hip, smx_adam.hip, smx_kapi.hip)
 // --------------------------------------------------------------------------
 struct LossArgs {
   int likelihood = 0;   // smx_likelihood
@@ -314,7 +314,7 @@ bool bn_dual_supported(int B);
 int launch_bn_act_fwd_dual(hipStream_t st, const BnFwdArgs& a, const BnFwdArgs& b);
 int launch_bn_act_bwd_dual(hipStream_t st, const BnBwdArgs& a, const BnBwdArgs& b);   // both with the gradient front
 
-// SyncBatchNorm (smx_kernels.hip): phase 0 leaves this rank's column statistics in `gather` [world][2][Hp],
+// SyncBatchNorm (smx_bn.hip): phase 0 leaves this rank's column statistics in `gather` [world][2][Hp],
 // the caller all-reduces it, phase 1 finishes the pass with the global statistics.
 struct BnSyncArgs { float* gather = nullptr; int rank = 0, world = 1; };
 int launch_bn_sync_fwd(hipStream_t st, const BnFwdArgs& a, const BnSyncArgs& y, int phase);

@@ -23,6 +23,29 @@ __global__ void count_diff_kernel(const uint32_t* a, const uint32_t* b, long n, 
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) mine += a[i] != b[i];
   if (mine) atomicAdd(out, mine);
 }
+
+// ===========================================================================
+// noise probe (tests): what the kernels draw for (cell, column)
+// ===========================================================================
+__global__ void noise_probe_kernel(NoiseKey nk, const int64_t* cell_ids, int B, int width, float p, float* mult,
+                                   float* normal) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= B * width) return;
+  const int b = idx / width, c = idx % width;
+  const U4 w = philox_block(nk, (uint32_t)cell_ids[b], (uint32_t)(c >> 2));
+  if (mult) mult[idx] = (p > 0.f) ? dropout_mult1(w, c & 3, p, 1.f / (1.f - p)) : 1.f;
+  if (normal) {
+    const float4 n = normal4(w);
+    normal[idx] = (c & 3) == 0 ? n.x : (c & 3) == 1 ? n.y : (c & 3) == 2 ? n.z : n.w;
+  }
+}
+int launch_noise_probe(hipStream_t st, NoiseKey nk, const int64_t* cell_ids, int B, int width, float p, float* mult,
+                       float* normal) {
+  hipLaunchKernelGGL(noise_probe_kernel, dim3((B * width + 255) / 256), dim3(256), 0, st, nk, cell_ids, B, width, p,
+                     mult, normal);
+  SMX_HIP(hipGetLastError());
+  return SMX_OK;
+}
 }  // namespace smx
 
 extern "C" {

@@ -1,5 +1,5 @@
 // smx_loss.h -- elementwise NB / ZINB / NBD / ZINBD log-likelihood and its gradients wrt the parameter
-// planes; shared by the standalone loss kernel (smx_kernels.hip) and the
+// planes; shared by the standalone loss kernel and the label heads (smx_loss.hip) and the
 // fused output-head kernel (smx_head.hip).
 #ifndef SMX_LOSS_H_
 #define SMX_LOSS_H_

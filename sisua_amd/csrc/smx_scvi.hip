@@ -10,7 +10,7 @@
 // in registers from the raw head outputs to their gradients: the activated planes, their gradients and the saved
 // softmax never exist in memory.  It replaces five launches of the separate form (library-latent product,
 // lib_latent_fwd, scvi_head_fwd, count_loss, scvi_head_bwd) and lib_latent_bwd: 6 launches, ~33 us of a 180 us step
-// at batch 256.  Evaluation / prediction / scoring keep the separate kernels (they hand the planes back).
+// at batch 256.  Evaluation / prediction / scoring keep the separate kernels (they hand the planes back: the end of this file).
 #include <stdlib.h>
 
 #include "smx_internal.h"
@@ -269,6 +269,269 @@ int launch_plane_fill(hipStream_t st, float* dst, long ld, const float* v, int B
 int launch_plane_colsum(hipStream_t st, const float* src, long ld, float* dst, int B, int Np, int single_G) {
   if (single_G > 0) hipLaunchKernelGGL(plane_sum_kernel, dim3(1), dim3(256), 0, st, src, ld, dst, B, single_G);
   else hipLaunchKernelGGL(plane_colsum_kernel, dim3((Np + 255) / 256), dim3(256), 0, st, src, ld, dst, B, Np);
+  SMX_HIP(hipGetLastError());
+  return SMX_OK;
+}
+
+// ===========================================================================
+// scvi head, separate form (evaluation / prediction / scoring, and training steps without the row-local launch above):
+// raw [B][3][Gp] -> planes (rate, theta, gate) and back, one workgroup per cell
+// ===========================================================================
+// Register-resident forms for gene panels up to 1024 * NV genes: one read of the raw planes (16-byte accesses),
+// the softmax terms stay in registers between the max, the sum and the write (the _vec forms below sweep
+// the row three times).
+template <int NV>
+__global__ __launch_bounds__(256) void scvi_head_fwd_reg_kernel(ScviHeadArgs a) {
+  __shared__ float sh[4];
+  const int b = blockIdx.x;
+  const float* raw = a.raw + (long)b * a.ld;
+  float* pl = a.planes + (long)b * a.ld;
+  float4 r0[NV], r1[NV], r2[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int g = (threadIdx.x + 256 * j) * 4;
+    const bool ok = g < a.Gp;
+    r0[j] = ok ? *reinterpret_cast<const float4*>(raw + g) : zero4();
+    r1[j] = ok ? *reinterpret_cast<const float4*>(raw + a.plane_stride + g) : zero4();
+    r2[j] = (ok && a.k == 3) ? *reinterpret_cast<const float4*>(raw + 2 * a.plane_stride + g) : zero4();
+  }
+  float mx = -3.0e38f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int g = (threadIdx.x + 256 * j) * 4;
+    const float v[4] = {r0[j].x, r0[j].y, r0[j].z, r0[j].w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) if (g + e < a.G) mx = fmaxf(mx, v[e]);
+  }
+  mx = block_max(mx, sh);
+  float ex[NV][4];
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int g = (threadIdx.x + 256 * j) * 4;
+    const float v[4] = {r0[j].x, r0[j].y, r0[j].z, r0[j].w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      ex[j][e] = (g + e < a.G) ? fexp(v[e] - mx) : 0.f;
+      sum += ex[j][e];
+    }
+  }
+  sum = block_sum(sum, sh);
+  const float inv = 1.f / sum;
+  const float el = expf(fminf(fmaxf(a.l[b], 0.f), a.clip_library));
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int g = (threadIdx.x + 256 * j) * 4;
+    if (g >= a.Gp) continue;
+    const float t[4] = {r1[j].x, r1[j].y, r1[j].z, r1[j].w};
+    const float gt[4] = {r2[j].x, r2[j].y, r2[j].z, r2[j].w};
+    float rho[4], rate[4], th[4], gate[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bool live = g + e < a.G;
+      rho[e] = live ? ex[j][e] * inv : 0.f;
+      rate[e] = live ? el * fminf(fmaxf(rho[e], 1e-7f), 1.f - 1e-7f) : 0.f;
+      th[e] = live ? fexp(t[e]) : 0.f;
+      gate[e] = live ? gt[e] : 0.f;
+    }
+    *reinterpret_cast<float4*>(a.rho_raw + (long)b * a.Gp + g) = make_float4(rho[0], rho[1], rho[2], rho[3]);
+    *reinterpret_cast<float4*>(pl + g) = make_float4(rate[0], rate[1], rate[2], rate[3]);
+    *reinterpret_cast<float4*>(pl + a.plane_stride + g) = make_float4(th[0], th[1], th[2], th[3]);
+    if (a.k == 3) *reinterpret_cast<float4*>(pl + 2 * a.plane_stride + g) = make_float4(gate[0], gate[1], gate[2], gate[3]);
+  }
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void scvi_head_bwd_reg_kernel(ScviHeadArgs a) {
+  __shared__ float sh[4];
+  const int b = blockIdx.x;
+  const float* pl = a.planes + (long)b * a.ld;
+  const float* dp = a.dplanes + (long)b * a.ld;
+  float* dr = a.draw + (long)b * a.ld;
+  const float* rho = a.rho_raw + (long)b * a.Gp;
+  const float lraw = a.l[b];
+  const float el = expf(fminf(fmaxf(lraw, 0.f), a.clip_library));
+  float4 rh[NV], d0v[NV], p0v[NV], d1v[NV], p1v[NV], d2v[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int g = (threadIdx.x + 256 * j) * 4;
+    const bool ok = g < a.Gp;
+    rh[j] = ok ? *reinterpret_cast<const float4*>(rho + g) : zero4();
+    d0v[j] = ok ? *reinterpret_cast<const float4*>(dp + g) : zero4();
+    p0v[j] = ok ? *reinterpret_cast<const float4*>(pl + g) : zero4();
+    d1v[j] = ok ? *reinterpret_cast<const float4*>(dp + a.plane_stride + g) : zero4();
+    p1v[j] = ok ? *reinterpret_cast<const float4*>(pl + a.plane_stride + g) : zero4();
+    d2v[j] = (ok && a.k == 3) ? *reinterpret_cast<const float4*>(dp + 2 * a.plane_stride + g) : zero4();
+  }
+  float s = 0.f, dlh = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int g = (threadIdx.x + 256 * j) * 4;
+    const float r[4] = {rh[j].x, rh[j].y, rh[j].z, rh[j].w};
+    const float dd[4] = {d0v[j].x, d0v[j].y, d0v[j].z, d0v[j].w};
+    const float pp[4] = {p0v[j].x, p0v[j].y, p0v[j].z, p0v[j].w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (g + e < a.G) {
+        const float inside = (r[e] > 1e-7f && r[e] < 1.f - 1e-7f) ? 1.f : 0.f;
+        s += dd[e] * el * inside * r[e];
+        dlh += dd[e] * pp[e];
+      }
+  }
+  s = block_sum(s, sh);
+  dlh = block_sum(dlh, sh);
+  if (threadIdx.x == 0) a.dl[b] = (lraw > 0.f && lraw < a.clip_library) ? dlh : 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int g = (threadIdx.x + 256 * j) * 4;
+    if (g >= a.Gp) continue;
+    const float r[4] = {rh[j].x, rh[j].y, rh[j].z, rh[j].w};
+    const float dd[4] = {d0v[j].x, d0v[j].y, d0v[j].z, d0v[j].w};
+    const float d1[4] = {d1v[j].x, d1v[j].y, d1v[j].z, d1v[j].w};
+    const float p1[4] = {p1v[j].x, p1v[j].y, p1v[j].z, p1v[j].w};
+    const float d2[4] = {d2v[j].x, d2v[j].y, d2v[j].z, d2v[j].w};
+    float o0[4], o1[4], o2[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bool live = g + e < a.G;
+      const float inside = (r[e] > 1e-7f && r[e] < 1.f - 1e-7f) ? 1.f : 0.f;
+      o0[e] = live ? r[e] * (dd[e] * el * inside - s) : 0.f;
+      o1[e] = live ? d1[e] * p1[e] : 0.f;
+      o2[e] = live ? d2[e] : 0.f;
+    }
+    *reinterpret_cast<float4*>(dr + g) = make_float4(o0[0], o0[1], o0[2], o0[3]);
+    *reinterpret_cast<float4*>(dr + a.plane_stride + g) = make_float4(o1[0], o1[1], o1[2], o1[3]);
+    if (a.k == 3) *reinterpret_cast<float4*>(dr + 2 * a.plane_stride + g) = make_float4(o2[0], o2[1], o2[2], o2[3]);
+  }
+}
+
+// Panels beyond the register forms (more than 8192 genes outside a training step's row-local launch, more than 20 480 inside one): three
+// sweeps over the row (max, sum, write) with 1024 threads and 16-byte accesses (round 6: 256 threads with 4-byte loads took 87 + 104 us per
+// step at 20 000 genes).  Same arithmetic per element as the register forms; the row sums are taken in another order.
+__device__ inline float block_sum16(float v, float* sh) {   // 16 waves
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = 0.f;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) t += sh[w];
+  return t;
+}
+__device__ inline float block_max16(float v, float* sh) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = sh[0];
+#pragma unroll
+  for (int w = 1; w < 16; ++w) t = fmaxf(t, sh[w]);
+  return t;
+}
+__global__ __launch_bounds__(1024) void scvi_head_fwd_vec_kernel(ScviHeadArgs a) {
+  __shared__ float sh[16];
+  const int b = blockIdx.x;
+  const float* raw = a.raw + (long)b * a.ld;
+  float* pl = a.planes + (long)b * a.ld;
+  float mx = -3.0e38f;
+  for (int g = threadIdx.x * 4; g < a.Gp; g += 4096) {
+    const float4 v = *reinterpret_cast<const float4*>(raw + g);
+    const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) if (g + e < a.G) mx = fmaxf(mx, x[e]);
+  }
+  mx = block_max16(mx, sh);
+  float sum = 0.f;
+  for (int g = threadIdx.x * 4; g < a.Gp; g += 4096) {
+    const float4 v = *reinterpret_cast<const float4*>(raw + g);
+    const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) if (g + e < a.G) sum += fexp(x[e] - mx);
+  }
+  sum = block_sum16(sum, sh);
+  const float inv = 1.f / sum;
+  const float el = expf(fminf(fmaxf(a.l[b], 0.f), a.clip_library));
+  for (int g = threadIdx.x * 4; g < a.Gp; g += 4096) {
+    const float4 v0 = *reinterpret_cast<const float4*>(raw + g), v1 = *reinterpret_cast<const float4*>(raw + a.plane_stride + g);
+    const float4 v2 = a.k == 3 ? *reinterpret_cast<const float4*>(raw + 2 * a.plane_stride + g) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float x0[4] = {v0.x, v0.y, v0.z, v0.w}, x1[4] = {v1.x, v1.y, v1.z, v1.w}, x2[4] = {v2.x, v2.y, v2.z, v2.w};
+    float rho[4], rate[4], th[4], gate[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bool live = g + e < a.G;
+      rho[e] = live ? fexp(x0[e] - mx) * inv : 0.f;
+      rate[e] = live ? el * fminf(fmaxf(rho[e], 1e-7f), 1.f - 1e-7f) : 0.f;
+      th[e] = live ? fexp(x1[e]) : 0.f;
+      gate[e] = live ? x2[e] : 0.f;
+    }
+    *reinterpret_cast<float4*>(a.rho_raw + (long)b * a.Gp + g) = make_float4(rho[0], rho[1], rho[2], rho[3]);
+    *reinterpret_cast<float4*>(pl + g) = make_float4(rate[0], rate[1], rate[2], rate[3]);
+    *reinterpret_cast<float4*>(pl + a.plane_stride + g) = make_float4(th[0], th[1], th[2], th[3]);
+    if (a.k == 3) *reinterpret_cast<float4*>(pl + 2 * a.plane_stride + g) = make_float4(gate[0], gate[1], gate[2], gate[3]);
+  }
+}
+__global__ __launch_bounds__(1024) void scvi_head_bwd_vec_kernel(ScviHeadArgs a) {
+  __shared__ float sh[16];
+  const int b = blockIdx.x;
+  const float* pl = a.planes + (long)b * a.ld;
+  const float* dp = a.dplanes + (long)b * a.ld;
+  float* dr = a.draw + (long)b * a.ld;
+  const float* rho = a.rho_raw + (long)b * a.Gp;
+  const float lraw = a.l[b];
+  const float el = expf(fminf(fmaxf(lraw, 0.f), a.clip_library));
+  float s = 0.f, dlh = 0.f;
+  for (int g = threadIdx.x * 4; g < a.Gp; g += 4096) {
+    const float4 r4 = *reinterpret_cast<const float4*>(rho + g), d4 = *reinterpret_cast<const float4*>(dp + g), p4 = *reinterpret_cast<const float4*>(pl + g);
+    const float r[4] = {r4.x, r4.y, r4.z, r4.w}, dd[4] = {d4.x, d4.y, d4.z, d4.w}, pp[4] = {p4.x, p4.y, p4.z, p4.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (g + e < a.G) {
+        const float inside = (r[e] > 1e-7f && r[e] < 1.f - 1e-7f) ? 1.f : 0.f;
+        s += dd[e] * el * inside * r[e];
+        dlh += dd[e] * pp[e];
+      }
+  }
+  s = block_sum16(s, sh);
+  dlh = block_sum16(dlh, sh);
+  if (threadIdx.x == 0) a.dl[b] = (lraw > 0.f && lraw < a.clip_library) ? dlh : 0.f;
+  for (int g = threadIdx.x * 4; g < a.Gp; g += 4096) {
+    const float4 r4 = *reinterpret_cast<const float4*>(rho + g), d4 = *reinterpret_cast<const float4*>(dp + g);
+    const float4 d14 = *reinterpret_cast<const float4*>(dp + a.plane_stride + g), p14 = *reinterpret_cast<const float4*>(pl + a.plane_stride + g);
+    const float4 d24 = a.k == 3 ? *reinterpret_cast<const float4*>(dp + 2 * a.plane_stride + g) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float r[4] = {r4.x, r4.y, r4.z, r4.w}, dd[4] = {d4.x, d4.y, d4.z, d4.w}, d1[4] = {d14.x, d14.y, d14.z, d14.w}, p1[4] = {p14.x, p14.y, p14.z, p14.w},
+                d2[4] = {d24.x, d24.y, d24.z, d24.w};
+    float o0[4], o1[4], o2[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bool live = g + e < a.G;
+      const float inside = (r[e] > 1e-7f && r[e] < 1.f - 1e-7f) ? 1.f : 0.f;
+      o0[e] = live ? r[e] * (dd[e] * el * inside - s) : 0.f;
+      o1[e] = live ? d1[e] * p1[e] : 0.f;
+      o2[e] = live ? d2[e] : 0.f;
+    }
+    *reinterpret_cast<float4*>(dr + g) = make_float4(o0[0], o0[1], o0[2], o0[3]);
+    *reinterpret_cast<float4*>(dr + a.plane_stride + g) = make_float4(o1[0], o1[1], o1[2], o1[3]);
+    if (a.k == 3) *reinterpret_cast<float4*>(dr + 2 * a.plane_stride + g) = make_float4(o2[0], o2[1], o2[2], o2[3]);
+  }
+}
+// every form moves the rows 16 bytes at a time; a step's planes always allow it (ld = k Gp, plane_stride = Gp, Gp = round_up(G, 32))
+static bool scvi_head_aligned(const ScviHeadArgs& a) { return (a.ld % 4) == 0 && (a.plane_stride % 4) == 0 && (a.Gp % 4) == 0; }
+
+int launch_scvi_head_fwd(hipStream_t st, const ScviHeadArgs& a) {
+  if (!scvi_head_aligned(a)) { set_error("scvi_head_fwd: ld, plane_stride and Gp must be multiples of 4"); return SMX_ERR_INVALID; }
+  if (a.Gp <= 2048) hipLaunchKernelGGL(scvi_head_fwd_reg_kernel<2>, dim3(a.B), dim3(256), 0, st, a);
+  else if (a.Gp <= 4096) hipLaunchKernelGGL(scvi_head_fwd_reg_kernel<4>, dim3(a.B), dim3(256), 0, st, a);
+  else if (a.Gp <= 8192) hipLaunchKernelGGL(scvi_head_fwd_reg_kernel<8>, dim3(a.B), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(scvi_head_fwd_vec_kernel, dim3(a.B), dim3(1024), 0, st, a);
+  SMX_HIP(hipGetLastError());
+  return SMX_OK;
+}
+int launch_scvi_head_bwd(hipStream_t st, const ScviHeadArgs& a) {
+  if (!scvi_head_aligned(a)) { set_error("scvi_head_bwd: ld, plane_stride and Gp must be multiples of 4"); return SMX_ERR_INVALID; }
+  if (a.Gp <= 2048) hipLaunchKernelGGL(scvi_head_bwd_reg_kernel<2>, dim3(a.B), dim3(256), 0, st, a);
+  else if (a.Gp <= 4096) hipLaunchKernelGGL(scvi_head_bwd_reg_kernel<4>, dim3(a.B), dim3(256), 0, st, a);
+  else if (a.Gp <= 8192) hipLaunchKernelGGL(scvi_head_bwd_reg_kernel<8>, dim3(a.B), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(scvi_head_bwd_vec_kernel, dim3(a.B), dim3(1024), 0, st, a);
   SMX_HIP(hipGetLastError());
   return SMX_OK;
 }

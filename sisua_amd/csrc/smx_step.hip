@@ -576,7 +576,7 @@ int mlp_backward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps, const
     int effs[2] = {1, 1};
     if (defer && i == 0 && lat_epi && m->fold_dz_now) {
       // fold_dz: no launch here -- the encoder's last BatchNorm-backward launch computes d z and the latent head's backward itself
-      // (BnBwdArgs::fold_dz, smx_kernels.hip: fold_dz_tile); d W joins the final grouped launch as before
+      // (BnBwdArgs::fold_dz, smx_bn.hip: fold_dz_tile); d W joins the final grouped launch as before
       defer->push_back(g);
     } else if (defer && i == 0 && lat_epi) {   // d z (+ latent-head backward) alone; d W joins the final grouped launch
       defer->push_back(g);

@@ -811,7 +811,7 @@ class SingleCellModel:
   def _mixture_prior_log_prob(self, z):
     r"""log p(z) under SCALE's trainable mixture prior for z [..., D] (float64): p(z) = sum_c softmax(a)_c N(z; m_c, S_c), S_c diagonal with
     s = softplus1(raw) or L_c L_c^T with a softplus diagonal + 1e-5 (covariance = 'tril': tfp's FillScaleTriL) -- the prior kernel's
-    arithmetic (smx_kernels.hip: scale_prior_*), from the model's current parameters."""
+    arithmetic (smx_latent.hip: scale_prior_*), from the model's current parameters."""
     cfg = self._cfg
     pr = {k: np.asarray(v, np.float64) for k, v in self._engine.get_params().items() if k.startswith("prior/")}
     a, m_c = pr["prior/logits"], pr["prior/loc"]

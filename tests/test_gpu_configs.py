@@ -582,7 +582,7 @@ def test_background_sweep_with_label_heads_covers_the_output_head_only(Engine, c
 def test_dz_product_and_latent_backward_inside_the_batchnorm_backward_launch(Engine, lk, B, G, units, latent):
   """Round 6 (launches off the C2 chain): at a latent of at most 32 dimensions, a first decoder layer of 128 units and
   at most 128 cells the encoder's last BatchNorm-backward launch computes d z = d pre_dec W_dec^T (bf16 x 3 MFMAs) and the latent head's
-  backward itself, in every workgroup (smx_kernels.hip: fold_dz_tile) -- gemm_latent_bwd_kernel's launch is gone.  Against the separate
+  backward itself, in every workgroup (smx_bn.hip: fold_dz_tile) -- gemm_latent_bwd_kernel's launch is gone.  Against the separate
   launches (knob no_fold_dz): the same step to rounding -- every gradient, the losses of four steps, parameters and moments --, ragged
   minibatches and a latent narrower than its padding included.  (Against the oracle: every step test of the suite runs the fold.)"""
   from sisua_amd import _hip
@@ -621,7 +621,7 @@ def test_dz_product_and_latent_backward_inside_the_batchnorm_backward_launch(Eng
                                                        ("nb", 90, 4128, "u16", 96, False), ("zinb", 128, 1998, "f32", 128, True), ("nb", 50, 700, "u16", 64, True),
                                                        ("zinb", 100, 1200, "f32", 96, False)])
 def test_batchnorm_launch_sums_column_major_slabs_itself(Engine, lk, B, G, storage, units, bnorm):
-  """Wide panels, at most 128 cells (smx_kernels.hip: bn_wide_fwd_kernel / bn_wide_bwd_kernel): the encoder front's K slices and the one-launch
+  """Wide panels, at most 128 cells (smx_bn.hip: bn_wide_fwd_kernel / bn_wide_bwd_kernel): the encoder front's K slices and the one-launch
   head's workgroups leave their [128][128] partial sums as COLUMN-major slabs and the BatchNorm launch behind them -- one workgroup per
   column -- sums them itself: no reduce launch in either pass.  The additions keep the order of the reduce launch + 8-column BatchNorm launch
   they replace (knob no_bn_wide): losses of every step, an evaluation pass, parameters, both Adam moments and the BatchNorm moving statistics
