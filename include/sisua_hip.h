@@ -186,6 +186,12 @@ int smx_dataset_upload_csr(smx_model* m, const int64_t* indptr, const int32_t* c
  * probability `density` (0.14 leaves ~93 % zeros), capped at 65535, gene 0 >= 1.  storage_u16 != 0: the compact store
  * (40 GB for 1e6 x 20 000).  Replaces the resident matrix; no labels / library prior (VAE / DCA models).  Bit-for-bit the
  * oracle's generate_lognormal_rows up to exp() rounding at integer boundaries. */
+/* A dense store (float32; uint16 with storage_u16 != 0, integer counts <= 65535) from cells given as CSR (layout as smx_dataset_upload_csr):
+ * blocks of rows cross as CSR and are expanded into the store on the device, so the host never holds the dense matrix.  The store, its
+ * row constants and every later result are those of smx_dataset_upload / smx_dataset_upload_u16 on the same counts. */
+int smx_dataset_upload_csr_dense(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_cells,
+                                 const float* const* labels, const float* library, const uint8_t* label_mask, int64_t cell_id_base,
+                                 int32_t storage_u16);
 int smx_dataset_generate_lognormal(smx_model* m, uint64_t seed, int32_t rank, int64_t n_cells, int32_t storage_u16, double density);
 
 int64_t smx_dataset_size(const smx_model* m);
@@ -296,6 +302,19 @@ int smx_predict(smx_model* m, const float* host_x, const float* host_library, in
 int smx_predict_stat(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
                      int32_t stat, int32_t count_only, const float* target, float* out);
 
+/* Host rows given as CSR instead of a dense host_x: indptr int64 [n_cells + 1] (absolute offsets: row i is entries
+ * indptr[i] .. indptr[i + 1] - 1 of cols / vals), cols int32 (sorted within a row, each < n_genes), vals float32.  Rows hold at most
+ * n_genes entries.  Every other argument, and every result bit, is that of the dense entry point on the same counts: a chunk's rows are
+ * expanded on the device into the tile a dense chunk is re-pitched into, their likelihood constants from the same launch.  Chunks are
+ * cut by non-zeros as well as by cells.  smx_predict_stat_csr: the log_prob target (stat 3) is dense (`target`), CSR (t_indptr /
+ * t_cols / t_vals, n_cells rows, same layout) or neither (the input rows themselves). */
+int smx_predict_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                    int64_t n_cells, int32_t batch, int32_t n_samples, float* z_mean, float* z_scale, float* z_samples,
+                    float* l_mean, float* l_scale, float* l_samples, float* x_params, float* const* y_params);
+int smx_predict_stat_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                         int64_t n_cells, int32_t batch, int32_t n_samples, int32_t stat, int32_t count_only, const float* target,
+                         const int64_t* t_indptr, const int32_t* t_cols, const float* t_vals, float* out);
+
 /* Decoder only (SingleCellModel.decode, single_cell_model.py:141-151; scvi.py:108-171):
  * z [batch,D] (and l [batch] for scvi) -> the same x_params / y_params as smx_forward,
  * eval mode. */
@@ -309,6 +328,9 @@ int smx_decode(smx_model* m, const float* z, const float* l, int32_t batch, floa
  * llk_mean[batch] = mean_s log p(x|z_s) (may be NULL).  Cells: row_ids or host_x (+ host_library for scvi). */
 int smx_marginal_llk(smx_model* m, const int32_t* row_ids, const float* host_x, const float* host_library, int32_t batch,
                      int32_t n_samples, float* mllk, float* llk_mean);
+/* The same for `batch` host rows given as CSR (layout as smx_predict_csr); the same bits as smx_marginal_llk on the dense rows. */
+int smx_marginal_llk_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                         int32_t batch, int32_t n_samples, float* mllk, float* llk_mean);
 
 /* Posterior-predictive scoring, Posterior.cal_llk (sisua/analysis/posterior.py:919-938): the cells given by
  * row_ids / host_x are encoded once, then n_samples posterior draws are decoded and the output distribution is

@@ -60,6 +60,7 @@ class smx_metrics(C.Structure):
 
 _FP = C.POINTER(C.c_float)
 _IP = C.POINTER(C.c_int32)
+_LP = C.POINTER(C.c_int64)
 _VP = C.c_void_p
 
 # name -> (restype, argtypes); every symbol include/sisua_hip.h declares
@@ -84,6 +85,8 @@ SIGNATURES = {
     "smx_dataset_upload_u16": (C.c_int, [_VP, C.POINTER(C.c_uint16), C.c_int64, C.POINTER(_FP), _FP, C.POINTER(C.c_uint8), C.c_int64]),
     "smx_dataset_upload_csr": (C.c_int, [_VP, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _FP, C.c_int64, C.POINTER(_FP), _FP,
                                          C.POINTER(C.c_uint8), C.c_int64]),
+    "smx_dataset_upload_csr_dense": (C.c_int, [_VP, _LP, _IP, _FP, C.c_int64, C.POINTER(_FP), _FP, C.POINTER(C.c_uint8), C.c_int64,
+                                               C.c_int32]),
     "smx_dataset_size": (C.c_int64, [_VP]),
     "smx_dataset_generate_lognormal": (C.c_int, [_VP, C.c_uint64, C.c_int32, C.c_int64, C.c_int32, C.c_double]),
     "smx_train_step": (C.c_int, [_VP, _IP, C.c_int32, C.POINTER(smx_metrics)]),
@@ -101,11 +104,16 @@ SIGNATURES = {
     "smx_predict": (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
                               C.POINTER(_FP)]),
     "smx_predict_stat": (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]),
+    "smx_predict_csr": (C.c_int, [_VP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
+                                  C.POINTER(_FP)]),
+    "smx_predict_stat_csr": (C.c_int, [_VP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP,
+                                       _LP, _IP, _FP, _FP]),
     "smx_decode": (C.c_int, [_VP, _FP, _FP, C.c_int32, _FP, C.POINTER(_FP)]),
     "smx_dataset_library": (C.c_int, [_VP, _FP]),
     "smx_dataset_corrupt": (C.c_int, [_VP, C.c_double, C.c_double, C.c_uint64, C.POINTER(C.c_int64)]),
     "smx_dataset_read": (C.c_int, [_VP, C.c_int64, C.c_int64, _FP, _FP, _FP]),
     "smx_marginal_llk": (C.c_int, [_VP, _IP, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP]),
+    "smx_marginal_llk_csr": (C.c_int, [_VP, _LP, _IP, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP]),
     "smx_score_llk": (C.c_int, [_VP, _IP, _FP, _FP, C.POINTER(_FP), C.c_int32, C.c_int32, C.c_int32, _FP]),
     "smx_set_noise": (C.c_int, [_VP, C.c_int32, _FP, C.c_int32, C.c_int32]),
     "smx_clear_noise": (C.c_int, [_VP]),

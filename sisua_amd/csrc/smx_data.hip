@@ -88,6 +88,78 @@ int launch_csr_expand(hipStream_t st, const int64_t* indptr, const int32_t* cols
   return SMX_OK;
 }
 
+// Host rows handed in as CSR (smx_predict_csr and kin): rows [0, n) of a chunk -> the dense [n][ld] float32 tile every
+// consumer of a host batch reads, and the rows' lgx1 in the same launch -- what the dense path gets from a re-pitch, a
+// memset and launch_row_stats.  indptr holds the chunk's n + 1 ABSOLUTE offsets; cols / vals start at entry indptr[0].
+// One workgroup per row.  The row is built in LDS one segment of CSR_SEG columns at a time (zero, scatter the segment's
+// non-zeros, write it out as coalesced float4 stores): every element of the tile is written once, no separate memset.
+// Wave 0 folds lgamma(x + 1) from the LDS segment in row_stats_kernel's lane order (lane l: columns 4 l + 256 t + q, in
+// column order) and the same wave_sum_f64, so lgx1 has the dense path's bits.  Columns outside [0, G) are skipped.
+// U16: the tile is the uint16 store (counts checked by the caller), same pitch in elements.
+#define CSR_SEG 4096
+template <int U16>
+__global__ __launch_bounds__(256) void csr_rows_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ cols,
+                                                       const float* __restrict__ vals, int G, long ld, void* __restrict__ outv,
+                                                       float* __restrict__ lgx1) {
+  __shared__ float4 seg4[CSR_SEG / 4];
+  float* seg = reinterpret_cast<float*>(seg4);
+  const long row = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int64_t base = indptr[0], p0 = indptr[row] - base, p1 = indptr[row + 1] - base;
+  float* o = reinterpret_cast<float*>(outv) + row * ld;
+  uint16_t* oh = reinterpret_cast<uint16_t*>(outv) + row * ld;
+  double lg = 0.0;
+  for (long s0 = 0; s0 < ld; s0 += CSR_SEG) {
+    const int w = (int)(ld - s0 < CSR_SEG ? ld - s0 : CSR_SEG);   // (ld is a multiple of 4)
+    for (int j = tid; j < w / 4; j += 256) seg4[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    // the segment's entries: cols are sorted within a row, so [lo, hi) is found by bisection (a single segment: the whole row)
+    int64_t lo = p0, hi = p1;
+    if (ld > CSR_SEG) {
+      int64_t a = p0, b = p1;
+      while (a < b) { const int64_t c = (a + b) >> 1; if (cols[c] < s0) a = c + 1; else b = c; }
+      lo = a; b = p1;
+      while (a < b) { const int64_t c = (a + b) >> 1; if (cols[c] < s0 + w) a = c + 1; else b = c; }
+      hi = a;
+    }
+    __syncthreads();
+    for (int64_t i = lo + tid; i < hi; i += 256) {
+      const long c = (long)cols[i] - s0;
+      if (c >= 0 && c < w && c + s0 < G) seg[c] = vals[i];
+    }
+    __syncthreads();
+    for (int j = tid; j < w / 4; j += 256) {
+      const float4 v = seg4[j];
+      if (U16) reinterpret_cast<ushort4*>(oh + s0)[j] = make_ushort4((unsigned short)v.x, (unsigned short)v.y, (unsigned short)v.z, (unsigned short)v.w);
+      else reinterpret_cast<float4*>(o + s0)[j] = v;
+    }
+    if (lgx1 && tid < 64)
+      for (int g = lane * 4; g < w; g += 256) {
+        const float4 v = seg4[g >> 2];
+        const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (e[q] > 0.f) lg += lgamma((double)e[q] + 1.0);
+      }
+    __syncthreads();
+  }
+  if (lgx1 && tid < 64) {
+    lg = wave_sum_f64(lg);
+    if (lane == 0) lgx1[row] = (float)lg;
+  }
+}
+int launch_csr_rows(hipStream_t st, const int64_t* indptr, const int32_t* cols, const float* vals, long n, int G, long ld, void* out,
+                    float* lgx1, int u16) {
+  if (n <= 0) return SMX_OK;
+  if (ld % 4 != 0 || ld < G || n >= 0x7FFFFFFFL) {
+    set_error("launch_csr_rows: ld must be a multiple of 4, at least G");
+    return SMX_ERR_INVALID;
+  }
+  if (u16) hipLaunchKernelGGL(csr_rows_kernel<1>, dim3((unsigned)n), dim3(256), 0, st, indptr, cols, vals, G, ld, out, lgx1);
+  else hipLaunchKernelGGL(csr_rows_kernel<0>, dim3((unsigned)n), dim3(256), 0, st, indptr, cols, vals, G, ld, out, lgx1);
+  SMX_HIP(hipGetLastError());
+  return SMX_OK;
+}
+
 // ---- on-device generator of the synthetic scaling configuration (BASELINE.json configs[4]; SURVEY.md 8d: "x =
 // floor(LogNormal(mu_g, 1)) thinned to ~93 % zeros, generated on-device per shard from (seed, rank)") --------------------
 // Entry (cell c, gene g) is a pure function of (seed, GLOBAL cell id, g) -- a shard is the rows [rank n, (rank + 1) n) of

@@ -9,11 +9,13 @@ static int dataset_upload_impl(smx_model* m, const void* X, bool u16, int64_t n_
 
 int smx_dataset_upload(smx_model* m, const float* X, int64_t n_cells, const float* const* labels, const float* library,
                        const uint8_t* label_mask, int64_t cell_id_base) {
+  SMX_REQUIRE(X, "bad dataset");
   return dataset_upload_impl(m, X, false, n_cells, labels, library, label_mask, cell_id_base);
 }
 
 int smx_dataset_upload_u16(smx_model* m, const uint16_t* X, int64_t n_cells, const float* const* labels, const float* library,
                            const uint8_t* label_mask, int64_t cell_id_base) {
+  SMX_REQUIRE(X, "bad dataset");
   return dataset_upload_impl(m, X, true, n_cells, labels, library, label_mask, cell_id_base);
 }
 
@@ -74,9 +76,35 @@ int smx_dataset_upload_csr(smx_model* m, const int64_t* indptr, const int32_t* c
   return upload_side_arrays(m, n_cells, labels, library, label_mask);
 }
 
+// A dense store (float32, or uint16 with storage_u16: integer counts <= 65535, checked) from host rows given as CSR: the host never holds
+// the dense matrix.  Blocks of rows cross as CSR and are expanded on the device into their place in the store (launch_csr_rows, which also
+// gives their lgx1); the store's bits are those of smx_dataset_upload(_u16) on the dense rows.
+int smx_dataset_upload_csr_dense(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_cells,
+                                 const float* const* labels, const float* library, const uint8_t* label_mask, int64_t cell_id_base,
+                                 int32_t storage_u16) {
+  SMX_REQUIRE(m && indptr && n_cells > 0, "bad dataset");
+  const CsrRows cx{indptr, cols, vals};
+  SMX_CHECK(check_csr_rows(cx, (size_t)n_cells, m->G));
+  for (int64_t i = indptr[0]; i < indptr[n_cells]; ++i) {
+    SMX_REQUIRE(cols[i] >= 0 && cols[i] < m->G, "CSR column index out of range");
+    SMX_REQUIRE(!storage_u16 || (vals[i] >= 0.f && vals[i] <= 65535.f && vals[i] == floorf(vals[i])), "storage u16 needs integer counts in [0, 65535]");
+  }
+  SMX_CHECK(dataset_upload_impl(m, nullptr, storage_u16 != 0, n_cells, labels, library, label_mask, cell_id_base));
+  // blocks of at most 8 M entries as dense rows (64 MB of staging at most)
+  const size_t rows_per = std::max<size_t>(1, ((size_t)8 << 20) / (size_t)m->G);
+  for (size_t r0 = 0; r0 < (size_t)n_cells; r0 += rows_per) {
+    const size_t n = std::min(rows_per, (size_t)n_cells - r0);
+    void* out = storage_u16 ? (void*)(reinterpret_cast<uint16_t*>(m->X) + r0 * m->Gp) : (void*)(m->X + r0 * m->Gp);
+    SMX_CHECK(csr_host_rows(m, cx, r0, n, out, m->lgx1 + r0, storage_u16 ? 1 : 0));
+  }
+  SMX_HIP(hipStreamSynchronize(m->st));
+  return SMX_OK;
+}
+
+// X = NULL: allocate the store and the side arrays, the caller fills X and lgx1 (smx_dataset_upload_csr_dense)
 static int dataset_upload_impl(smx_model* m, const void* X, bool u16, int64_t n_cells, const float* const* labels,
                                const float* library, const uint8_t* label_mask, int64_t cell_id_base) {
-  SMX_REQUIRE(m && X && n_cells > 0, "bad dataset");
+  SMX_REQUIRE(m && n_cells > 0, "bad dataset");
   SMX_REQUIRE(n_cells < (int64_t)1 << 31, "row ids are int32");
   SMX_REQUIRE(!m->scvi || library, "scvi needs the library prior (scvi.py:100-105)");
   for (int j = 0; j < m->cfg.n_labels; ++j) SMX_REQUIRE(labels && labels[j], "missing label matrix");
@@ -94,15 +122,15 @@ static int dataset_upload_impl(smx_model* m, const void* X, bool u16, int64_t n_
     uint16_t* xh = nullptr;
     if ((rc = dmalloc(&xh, (size_t)n_cells * m->Gp)) || (rc = dmalloc(&m->lgx1, (size_t)n_cells))) return rc;
     m->X = reinterpret_cast<float*>(xh);
-    SMX_HIP(hipMemcpy2D(xh, (size_t)m->Gp * sizeof(uint16_t), X, (size_t)m->G * sizeof(uint16_t), (size_t)m->G * sizeof(uint16_t),
+    if (X) SMX_HIP(hipMemcpy2D(xh, (size_t)m->Gp * sizeof(uint16_t), X, (size_t)m->G * sizeof(uint16_t), (size_t)m->G * sizeof(uint16_t),
                         (size_t)n_cells, hipMemcpyHostToDevice));
   } else {
     if ((rc = dmalloc(&m->X, (size_t)n_cells * m->Gp)) || (rc = dmalloc(&m->lgx1, (size_t)n_cells))) return rc;
-    SMX_HIP(hipMemcpy2D(m->X, (size_t)m->Gp * sizeof(float), X, (size_t)m->G * sizeof(float), (size_t)m->G * sizeof(float),
+    if (X) SMX_HIP(hipMemcpy2D(m->X, (size_t)m->Gp * sizeof(float), X, (size_t)m->G * sizeof(float), (size_t)m->G * sizeof(float),
                         (size_t)n_cells, hipMemcpyHostToDevice));
   }
   // per-row constant sum_g lgamma(x+1) of the likelihood, on the device (one wave per row)
-  SMX_CHECK(launch_row_stats(m->st, m->X, m->x_u16 ? 1 : 0, m->Gp, m->N, m->G, m->lgx1, nullptr));
+  if (X) SMX_CHECK(launch_row_stats(m->st, m->X, m->x_u16 ? 1 : 0, m->Gp, m->N, m->G, m->lgx1, nullptr));
   return upload_side_arrays(m, n_cells, labels, library, label_mask);
 }
 

@@ -233,6 +233,7 @@ struct smx_model {
   // pinned staging for the row ids of a train_steps call: hipMemcpyAsync from the caller's pageable array cost ~80 us per call
   int32_t* order_pin = nullptr; size_t order_pin_cap = 0; hipEvent_t ev_order = nullptr; bool order_pin_busy = false;
   int32_t* pred_ids = nullptr; int pred_ids_batch = 0;   // smx_predict super-batches: noise ids (row % batch)
+  char* csr_host = nullptr; size_t csr_host_bytes = 0;   // a batch of host rows given as CSR, staged (smx_marginal_llk_csr, CSR log_prob targets)
   float* pred_target = nullptr; size_t pred_target_floats = 0;   // smx_predict_stat(log_prob): a batch of target rows [Bmax][Gp]
   float* metrics_pin = nullptr;   // pinned landing area of read_metrics: 8 ELBO scalars + one gradient norm per tensor
   float* score_pin = nullptr; size_t score_pin_floats = 0;   // pinned landing area of the scoring entry points' results (smx_scoring.hip: score_landing)
@@ -378,6 +379,10 @@ int optimizer_pass(smx_model* m);
 int csr_stage(smx_model* m, Pass& ps);
 int check_rows(smx_model* m, const int32_t* ids, size_t n);
 int read_metrics(smx_model* m, smx_metrics* out);
+// host rows given as CSR (smx_predict.hip): indptr int64 [n + 1] (absolute offsets into cols / vals), cols int32, vals float32
+struct CsrRows { const int64_t* indptr; const int32_t* cols; const float* vals; };
+int check_csr_rows(const CsrRows& c, size_t n, int G);
+int csr_host_rows(smx_model* m, const CsrRows& c, size_t r0, size_t n, void* out, float* lgx1, int u16 = 0);
 int setup_pass(smx_model* m, Pass& ps, const int32_t* row_ids, const float* host_x, const float* host_library,
                int32_t batch, int training, int sample, int draw_rows = 0);   // draw_rows > 0: row_ids are stacked draws (up to Rmax rows)
 // smx_predict.hip

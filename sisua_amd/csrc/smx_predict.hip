@@ -166,7 +166,54 @@ static int launch_plane_stat(hipStream_t st, const StatArgs& a) {
   return SMX_OK;
 }
 // what smx_predict_stat asks of the batch loop below in place of the parameter planes
-struct StatReq { int stat = 0, count_only = 0; const float* target = nullptr; float* out = nullptr; };
+struct StatReq { int stat = 0, count_only = 0; const float* target = nullptr; const CsrRows* tcsr = nullptr; float* out = nullptr; };
+
+// ---- host rows given as CSR (smx_predict_csr and kin): (indptr int64 [n + 1], cols int32, vals float32), indptr absolute ----
+// what the C entry points check before any device work: offsets that never go back, at most G entries per row (so a batch of rows
+// holds at most batch x G of them: the bound every staging buffer is sized by)
+int check_csr_rows(const CsrRows& c, size_t n, int G) {
+  SMX_REQUIRE(c.indptr, "CSR rows need indptr");
+  SMX_REQUIRE(c.indptr[0] >= 0, "CSR indptr[0] must be >= 0");
+  for (size_t i = 0; i < n; ++i)
+    SMX_REQUIRE(c.indptr[i + 1] >= c.indptr[i] && c.indptr[i + 1] - c.indptr[i] <= (int64_t)G,
+                "CSR indptr must be non-decreasing with at most n_genes entries per row");
+  SMX_REQUIRE((c.cols && c.vals) || c.indptr[n] == c.indptr[0], "CSR rows need cols and vals");
+  return SMX_OK;
+}
+
+// bytes of a block of n CSR rows with nnz entries as staged on the device: indptr | cols | vals, each 16-byte aligned
+static size_t csr_stage_bytes(size_t n, size_t nnz) {
+  auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  return al((n + 1) * 8) + 2 * al(nnz * 4);
+}
+// rows [r0, r0 + n) of host CSR arrays -> device staging at `dst` (csr_stage_bytes of room) -> the dense tile out [n][Gp] and their
+// lgx1 (may be NULL), in ONE launch (launch_csr_rows).  Three contiguous host-to-device copies: the indptr slice, the cols and vals.
+static int stage_csr_rows(smx_model* m, const CsrRows& c, size_t r0, size_t n, char* dst, void* out, float* lgx1, int u16 = 0) {
+  auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const int64_t e0 = c.indptr[r0];
+  const size_t nnz = (size_t)(c.indptr[r0 + n] - e0);
+  int64_t* d_ptr = reinterpret_cast<int64_t*>(dst);
+  int32_t* d_cols = reinterpret_cast<int32_t*>(dst + al((n + 1) * 8));
+  float* d_vals = reinterpret_cast<float*>(dst + al((n + 1) * 8) + al(nnz * 4));
+  SMX_HIP(hipMemcpyAsync(d_ptr, c.indptr + r0, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, m->st));
+  if (nnz) {
+    SMX_HIP(hipMemcpyAsync(d_cols, c.cols + e0, nnz * sizeof(int32_t), hipMemcpyHostToDevice, m->st));
+    SMX_HIP(hipMemcpyAsync(d_vals, c.vals + e0, nnz * sizeof(float), hipMemcpyHostToDevice, m->st));
+  }
+  return launch_csr_rows(m->st, d_ptr, d_cols, d_vals, (long)n, m->G, (long)m->Gp, out, lgx1, u16);
+}
+// the same through the model's growable buffer m->csr_host (one batch of rows: smx_marginal_llk_csr, a batch of CSR targets; a block of
+// a dense store uploaded from CSR, u16: the uint16 store)
+int csr_host_rows(smx_model* m, const CsrRows& c, size_t r0, size_t n, void* out, float* lgx1, int u16) {
+  const size_t need = csr_stage_bytes(n, (size_t)(c.indptr[r0 + n] - c.indptr[r0]));
+  if (need > m->csr_host_bytes) {
+    if (m->csr_host) { SMX_HIP(hipStreamSynchronize(m->st)); hipFree(m->csr_host); }
+    m->csr_host = nullptr; m->csr_host_bytes = 0;
+    SMX_CHECK(dmalloc(&m->csr_host, need));
+    m->csr_host_bytes = need;
+  }
+  return stage_csr_rows(m, c, r0, n, m->csr_host, out, lgx1, u16);
+}
 
 // Decoder layers over `rows` stacked rows (evaluation mode: moving statistics, no dropout; smx_score.hip).  The last
 // layer's output: last_form 0 row-major f32 in place, 1 k-major f32 in ht [Hp][rows], 2 its three-way bf16 split in ht.
@@ -251,11 +298,14 @@ int smx_forward_samples(smx_model* m, const int32_t* row_ids, const float* host_
   return SMX_OK;
 }
 
-static int predict_core(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
-                        float* z_mean, float* z_scale, float* z_samples, float* l_mean, float* l_scale, float* l_samples,
+// host_x: dense rows [n_cells][G]; or cx: the same rows as CSR (exactly one of the two)
+static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, const float* host_library, int64_t n_cells, int32_t batch,
+                        int32_t n_samples, float* z_mean, float* z_scale, float* z_samples, float* l_mean, float* l_scale, float* l_samples,
                         float* x_params, float* const* y_params, const StatReq* sr) {
-  SMX_REQUIRE(m && host_x && n_cells > 0 && n_samples > 0, "bad arguments");
+  SMX_REQUIRE(m && (host_x != nullptr) != (cx != nullptr) && n_cells > 0 && n_samples > 0, "bad arguments");
   SMX_REQUIRE(batch > 0 && batch <= m->Bmax, "batch must be in 1..max_batch");
+  if (cx) SMX_CHECK(check_csr_rows(*cx, (size_t)n_cells, m->G));
+  if (sr && sr->tcsr) SMX_CHECK(check_csr_rows(*sr->tcsr, (size_t)n_cells, m->G));
   const size_t N = (size_t)n_cells, G = (size_t)m->G, D = (size_t)m->D, k = (size_t)m->k, S = (size_t)n_samples;
   const int Dp = m->Dp, lat_ld = m->lat_planes * Dp;
   if (!m->stochastic) z_scale = nullptr;
@@ -279,9 +329,11 @@ static int predict_core(smx_model* m, const float* host_x, const float* host_lib
   // the INPUT rows of a chunk travel as ONE contiguous copy too (raw [C][G] -> a device re-pitch to [C][Gp]; library prior; the rows'
   // likelihood constants from one launch): a host-to-device copy per minibatch from the caller's pageable array is staged
   // synchronously by the runtime -- ~60 us per batch, at batch 8 (Posterior's default) most of the call
+  // CSR rows: no raw [C][G] segment; the chunk's indptr slice, cols and vals take a region of their own, sized by non-zeros (below)
   const size_t Gp = (size_t)m->Gp;
-  per_cell += G + Gp + 3;
-  if (sr && sr->stat == 3 && sr->target && (size_t)batch * m->Gp > m->pred_target_floats) {   // device copy of a batch of target rows
+  per_cell += (cx ? 0 : G) + Gp + 3;
+  const bool t_dev = sr && sr->stat == 3 && (sr->target || sr->tcsr);   // targets other than the input rows
+  if (t_dev && (size_t)batch * m->Gp > m->pred_target_floats) {   // device copy of a batch of target rows
     if (m->pred_target) hipFree(m->pred_target);
     m->pred_target = nullptr; m->pred_target_floats = 0;
     SMX_CHECK(dmalloc(&m->pred_target, (size_t)m->Bmax * m->Gp));
@@ -291,13 +343,21 @@ static int predict_core(smx_model* m, const float* host_x, const float* host_lib
   const size_t cap_floats = (size_t)std::max(1.0, tuning("predict_stage_floats", (double)((size_t)32 << 20)));
   size_t C = std::max<size_t>((size_t)batch, cap_floats / per_cell / (size_t)batch * (size_t)batch);   // whole batches per chunk
   C = std::min(C, (N + (size_t)batch - 1) / (size_t)batch * (size_t)batch);
-  if (C * per_cell > m->pred_floats) {
+  // CSR rows: a chunk is also cut, at a batch boundary, where its non-zeros would pass nnz_cap; a batch holds at most batch x G of them
+  // (check_csr_rows), so one batch always fits and a dense region only makes the chunks shorter
+  const size_t nnz_cap = cx ? std::max((size_t)batch * G, std::min(C * G, cap_floats / 2)) : 0;
+  const size_t csr_floats = cx ? csr_stage_bytes(C, nnz_cap) / 4 : 0;   // (a multiple of 16 bytes)
+  const size_t stage_need = csr_floats + C * per_cell;
+  if (stage_need > m->pred_floats) {
     if (m->pred_stage) hipFree(m->pred_stage);
     m->pred_stage = nullptr; m->pred_floats = 0;
-    SMX_CHECK(dmalloc(&m->pred_stage, C * per_cell));
-    m->pred_floats = C * per_cell;
+    SMX_CHECK(dmalloc(&m->pred_stage, stage_need));
+    m->pred_floats = stage_need;
   }
-  float* st = m->pred_stage;
+  char* csr_st = reinterpret_cast<char*>(m->pred_stage);
+  float* st = m->pred_stage + csr_floats;
+  float* in_x = nullptr;
+  if (cx) { in_x = st; st += C * Gp; }   // (CSR: the tile right after the CSR region, 16-byte aligned for launch_csr_rows' float4 stores)
   float *s_zm = nullptr, *s_zs = nullptr, *s_lm = nullptr, *s_ls = nullptr, *s_zd = nullptr, *s_ld = nullptr, *s_xp = nullptr, *s_y[SMX_MAX_LABELS] = {nullptr, nullptr, nullptr, nullptr};
   if (z_mean) { s_zm = st; st += C * D; }
   if (z_scale) { s_zs = st; st += C * D; }
@@ -308,8 +368,9 @@ static int predict_core(smx_model* m, const float* host_x, const float* host_lib
   if (x_params) { s_xp = st; st += S * k * C * G; }
   float* s_st = nullptr;
   if (w_stat) { s_st = st; st += C * w_stat; }
-  float* in_raw = st; st += C * G;
-  float* in_x = st; st += C * Gp;
+  float* in_raw = nullptr;
+  if (!cx) { in_raw = st; st += C * G; }
+  if (!cx) { in_x = st; st += C * Gp; }
   float* in_lib = st; st += C * 2;
   float* in_lgx1 = st; st += C;
   for (int j = 0; j < m->n_heads; ++j)
@@ -323,7 +384,7 @@ static int predict_core(smx_model* m, const float* host_x, const float* host_lib
     if (sr->stat == 2) { a.dst = s_st + b0 * G; a.dst_draw = 0; }
     else if (sr->stat == 3) {
       a.dst = s_st + s0 * Cn + b0; a.dst_draw = (long)Cn;
-      if (sr->target) { a.T = m->pred_target; a.ldt = m->Gp; }
+      if (sr->target || sr->tcsr) { a.T = m->pred_target; a.ldt = m->Gp; }
       else { a.T = ps.Xsrc; a.ldt = m->Gp; a.trows = ps.xrows; a.t_u16 = ps.x_u16; }   // the input rows themselves
     } else { a.dst = s_st + (s0 * Cn + b0) * G; a.dst_draw = (long)(Cn * G); }
     return launch_plane_stat(m->st, a);
@@ -353,9 +414,21 @@ static int predict_core(smx_model* m, const float* host_x, const float* host_lib
   bool any_y = false;
   for (int j = 0; j < m->n_heads; ++j) any_y = any_y || s_y[j] != nullptr;
   const bool need_dec = s_xp || s_st || any_y;   // (latents only: the decoder and the heads are not run at all)
-  for (size_t c0 = 0; c0 < N; c0 += C) {
-    const size_t Cn = std::min(C, N - c0);   // cells of this chunk
-    {
+  for (size_t c0 = 0, Cn = 0; c0 < N; c0 += Cn) {
+    Cn = std::min(C, N - c0);   // cells of this chunk
+    if (cx) {   // whole batches while the non-zeros fit (the first batch always does)
+      size_t end = c0;
+      while (end < c0 + Cn) {
+        const size_t nxt = std::min(end + (size_t)batch, c0 + Cn);
+        if (end > c0 && (size_t)(cx->indptr[nxt] - cx->indptr[c0]) > nnz_cap) break;
+        end = nxt;
+      }
+      Cn = end - c0;
+      SMX_REQUIRE((size_t)(cx->indptr[c0 + Cn] - cx->indptr[c0]) <= nnz_cap, "CSR chunk exceeds its staging");
+      // the chunk's rows as the [Cn][Gp] tile and their likelihood constants: one launch, as the dense path's re-pitch + row_stats
+      SMX_CHECK(stage_csr_rows(m, *cx, c0, Cn, csr_st, in_x, in_lgx1));
+      if (host_library) SMX_HIP(hipMemcpyAsync(in_lib, host_library + c0 * 2, Cn * 2 * sizeof(float), hipMemcpyHostToDevice, m->st));
+    } else {
       SMX_HIP(hipMemcpyAsync(in_raw, host_x + c0 * G, Cn * G * sizeof(float), hipMemcpyHostToDevice, m->st));
       if (Gp != G) SMX_HIP(hipMemsetAsync(in_x, 0, Cn * Gp * sizeof(float), m->st));
       PackJobs J; J.n = 1;
@@ -372,7 +445,8 @@ static int predict_core(smx_model* m, const float* host_x, const float* host_lib
       Pass ps;   // (what setup_pass leaves for a host batch, on the chunk's resident copy)
       ps.B = B; ps.training = 0; ps.sample = 0; ps.global_batch = B;
       ps.rows = nullptr; ps.Xsrc = in_x + b0 * Gp; ps.lib = in_lib + b0 * 2; ps.lgx1 = in_lgx1 + b0; ps.cell_base = 0;
-      if (sr && sr->stat == 3 && sr->target)
+      if (sr && sr->stat == 3 && sr->tcsr) SMX_CHECK(csr_host_rows(m, *sr->tcsr, g0, (size_t)B, m->pred_target, nullptr));
+      else if (sr && sr->stat == 3 && sr->target)
         SMX_HIP(hipMemcpy2DAsync(m->pred_target, (size_t)m->Gp * sizeof(float), sr->target + g0 * G, G * sizeof(float), G * sizeof(float), (size_t)B,
                                  hipMemcpyHostToDevice, m->st));
       if (stack) {
@@ -529,7 +603,17 @@ static int predict_core(smx_model* m, const float* host_x, const float* host_lib
 int smx_predict(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
                 float* z_mean, float* z_scale, float* z_samples, float* l_mean, float* l_scale, float* l_samples,
                 float* x_params, float* const* y_params) {
-  return predict_core(m, host_x, host_library, n_cells, batch, n_samples, z_mean, z_scale, z_samples, l_mean, l_scale, l_samples, x_params, y_params, nullptr);
+  return predict_core(m, host_x, nullptr, host_library, n_cells, batch, n_samples, z_mean, z_scale, z_samples, l_mean, l_scale, l_samples, x_params,
+                      y_params, nullptr);
+}
+
+int smx_predict_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library, int64_t n_cells,
+                    int32_t batch, int32_t n_samples, float* z_mean, float* z_scale, float* z_samples, float* l_mean, float* l_scale,
+                    float* l_samples, float* x_params, float* const* y_params) {
+  SMX_REQUIRE(indptr, "null indptr");
+  const CsrRows cx{indptr, cols, vals};
+  return predict_core(m, nullptr, &cx, host_library, n_cells, batch, n_samples, z_mean, z_scale, z_samples, l_mean, l_scale, l_samples, x_params,
+                      y_params, nullptr);
 }
 
 int smx_predict_stat(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
@@ -538,7 +622,20 @@ int smx_predict_stat(smx_model* m, const float* host_x, const float* host_librar
   SMX_REQUIRE(!(count_only && m->cfg.likelihood == SMX_LLK_MSE), "the deterministic 'mse' output has no count distribution");
   StatReq sr;
   sr.stat = stat; sr.count_only = count_only ? 1 : 0; sr.target = target; sr.out = out;
-  return predict_core(m, host_x, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr);
+  return predict_core(m, host_x, nullptr, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr);
+}
+
+int smx_predict_stat_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library, int64_t n_cells,
+                         int32_t batch, int32_t n_samples, int32_t stat, int32_t count_only, const float* target, const int64_t* t_indptr,
+                         const int32_t* t_cols, const float* t_vals, float* out) {
+  SMX_REQUIRE(m && out && stat >= 0 && stat <= 3, "bad arguments (stat: 0 mean, 1 variance, 2 mean over the draws, 3 log_prob)");
+  SMX_REQUIRE(!(count_only && m->cfg.likelihood == SMX_LLK_MSE), "the deterministic 'mse' output has no count distribution");
+  SMX_REQUIRE(!(target && t_indptr), "a target is dense or CSR, not both");
+  const CsrRows cx{indptr, cols, vals}, tc{t_indptr, t_cols, t_vals};
+  const CsrRows* in = indptr ? &cx : nullptr;
+  StatReq sr;
+  sr.stat = stat; sr.count_only = count_only ? 1 : 0; sr.target = target; sr.tcsr = t_indptr ? &tc : nullptr; sr.out = out;
+  return predict_core(m, nullptr, in, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr);
 }
 
 int smx_decode(smx_model* m, const float* z, const float* l, int32_t batch, float* x_params, float* const* y_params) {

@@ -217,16 +217,8 @@ static int score_landing(smx_model* m, size_t floats, float** out) {
   return SMX_OK;
 }
 
-}  // namespace smx
-
-extern "C" {
-
-int smx_marginal_llk(smx_model* m, const int32_t* row_ids, const float* host_x, const float* host_library, int32_t batch,
-                     int32_t n_samples, float* mllk, float* llk_mean) {
-  SMX_REQUIRE(m && mllk && n_samples > 0, "bad arguments");
-  SMX_REQUIRE(m->cfg.likelihood != SMX_LLK_MSE, "the 'mse' output is not a normalised density: no marginal likelihood");
-  Pass ps;
-  SMX_CHECK(setup_pass(m, ps, row_ids, host_x, host_library, batch, 0, 0));
+// smx_marginal_llk(_csr) after the batch's pass is set up
+static int marginal_llk_run(smx_model* m, Pass& ps, int32_t batch, int32_t n_samples, float* mllk, float* llk_mean) {
   const bool stacked = stacked_scoring_ok(m);
   // a deterministic latent (DCA) decodes to the same parameters in every draw: one pass is the whole estimate
   if (!m->stochastic) n_samples = 1;
@@ -268,6 +260,36 @@ int smx_marginal_llk(smx_model* m, const int32_t* row_ids, const float* host_x, 
     hipStreamSynchronize(m->st);
   }
   return rc;
+}
+
+}  // namespace smx
+
+extern "C" {
+
+int smx_marginal_llk(smx_model* m, const int32_t* row_ids, const float* host_x, const float* host_library, int32_t batch,
+                     int32_t n_samples, float* mllk, float* llk_mean) {
+  SMX_REQUIRE(m && mllk && n_samples > 0, "bad arguments");
+  SMX_REQUIRE(m->cfg.likelihood != SMX_LLK_MSE, "the 'mse' output is not a normalised density: no marginal likelihood");
+  Pass ps;
+  SMX_CHECK(setup_pass(m, ps, row_ids, host_x, host_library, batch, 0, 0));
+  return marginal_llk_run(m, ps, batch, n_samples, mllk, llk_mean);
+}
+
+int smx_marginal_llk_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library, int32_t batch,
+                         int32_t n_samples, float* mllk, float* llk_mean) {
+  SMX_REQUIRE(m && mllk && n_samples > 0, "bad arguments");
+  SMX_REQUIRE(m->cfg.likelihood != SMX_LLK_MSE, "the 'mse' output is not a normalised density: no marginal likelihood");
+  SMX_REQUIRE(batch > 0 && batch <= m->Bmax, "batch must be in 1..max_batch");
+  SMX_REQUIRE(!m->scvi || host_library, "scvi needs host_library with host rows");
+  const CsrRows cx{indptr, cols, vals};
+  SMX_CHECK(check_csr_rows(cx, (size_t)batch, m->G));
+  // (what setup_pass does for dense host rows; the rows' tile and constants from one launch)
+  Pass ps;
+  ps.B = batch; ps.training = 0; ps.sample = 0; ps.global_batch = batch; ps.draw_rows = 0;
+  SMX_CHECK(csr_host_rows(m, cx, 0, (size_t)batch, m->hostX, m->hostLgx1));
+  if (host_library) SMX_HIP(hipMemcpy(m->hostLib, host_library, (size_t)batch * 2 * sizeof(float), hipMemcpyHostToDevice));
+  ps.rows = nullptr; ps.Xsrc = m->hostX; ps.lib = m->hostLib; ps.lgx1 = m->hostLgx1; ps.cell_base = 0;
+  return marginal_llk_run(m, ps, batch, n_samples, mllk, llk_mean);
 }
 
 int smx_score_llk(smx_model* m, const int32_t* row_ids, const float* host_x, const float* host_library,

@@ -12,6 +12,10 @@ WHICH values reach the step.
 
 Bit-exactness of the first three against the reference's own code is pinned by
 tests/golden/reference_data_fixtures.npz.
+
+Sparse counts: every function here also takes a scipy.sparse matrix, held as canonical float32 CSR (`as_csr`: sorted
+column indices, duplicates summed, explicit zeros dropped) and never densified whole.  `corrupt` and `library_size` give
+the dense twin's bits (for library_size: integer counts with row sums below 2**24, which float32 holds exactly).
 """
 from __future__ import annotations
 
@@ -20,6 +24,36 @@ from typing import List, Optional, Sequence, Tuple
 import ctypes as _C
 
 import numpy as np
+import scipy.sparse as sp
+
+
+def is_sparse(x) -> bool:
+  return sp.issparse(x)
+
+
+def as_csr(x, copy: bool = True) -> sp.csr_matrix:
+  """Any scipy.sparse matrix (COO, CSC, CSR, any dtype) -> canonical float32 CSR: indices sorted within a row, duplicates
+  summed (in the input's dtype, as its toarray() would), explicit zeros dropped.  copy=False returns `x` itself when it is
+  canonical float32 CSR already."""
+  if (not copy and isinstance(x, sp.csr_matrix) and x.dtype == np.float32 and x.has_canonical_format
+      and not (x.data == 0).any()):
+    return x
+  x = sp.csr_matrix(x, copy=True)
+  x.sum_duplicates()   # (sorts the indices too)
+  x = x.astype(np.float32, copy=False)
+  x.eliminate_zeros()
+  x.sort_indices()
+  return x
+
+
+def row_sums(x) -> np.ndarray:
+  """float32 row sums: dense `x.sum(axis=1)`; CSR from its non-zeros (fp64 accumulation, exact -- and so equal to the dense
+  float32 sum -- for integer counts with row sums below 2**24)."""
+  if not is_sparse(x):
+    return x.sum(axis=1)
+  x = as_csr(x, copy=False)
+  rows = np.repeat(np.arange(x.shape[0]), np.diff(x.indptr))
+  return np.bincount(rows, weights=x.data, minlength=x.shape[0]).astype(np.float32)
 
 
 def split_indices(n_obs: int, train_percent: float = 0.8, seed: int = 1) -> Tuple[np.ndarray, np.ndarray]:
@@ -31,10 +65,14 @@ def split_indices(n_obs: int, train_percent: float = 0.8, seed: int = 1) -> Tupl
 
 def corrupt(x: np.ndarray, dropout_rate: float = 0.2, retain_rate: float = 0.2, distribution: str = "binomial",
             seed: int = 8, inplace: bool = False) -> np.ndarray:
+  """x sparse: canonical CSR (`as_csr`) in, CSR out (inplace: `x` itself), the dense twin's values bit for bit -- its non-zeros
+  are np.nonzero's row-major order, so the same RandomState picks the same entries; entries set to 0 leave the structure."""
   distribution = str(distribution).lower()
   dropout_rate = float(dropout_rate)
   if not 0 <= dropout_rate < 1:
     raise ValueError(f"dropout value must be >= 0 and < 1, given: {dropout_rate}")
+  if is_sparse(x):
+    return _corrupt_csr(x, dropout_rate, retain_rate, distribution, seed, inplace)
   out = x if inplace else np.array(x, copy=True)
   if not (0.0 < dropout_rate < 1.0 or 0.0 < retain_rate < 1.0):
     return out
@@ -59,12 +97,38 @@ def corrupt(x: np.ndarray, dropout_rate: float = 0.2, retain_rate: float = 0.2, 
   return out
 
 
+def _corrupt_csr(x, dropout_rate, retain_rate, distribution, seed, inplace):
+  if not (isinstance(x, sp.csr_matrix) and x.dtype == np.float32 and x.has_canonical_format):
+    if inplace:
+      raise ValueError("in-place corruption of a sparse matrix needs canonical float32 CSR (data.as_csr)")
+    x = as_csr(x)
+  out = x if inplace else x.copy()
+  if not (0.0 < dropout_rate < 1.0 or 0.0 < retain_rate < 1.0):
+    return out
+  rand = np.random.RandomState(seed=seed)
+  nz = np.flatnonzero(out.data != 0)   # (the stored entries in row-major order: np.nonzero of the dense twin)
+  n_sel = int(np.floor(dropout_rate * len(nz)))
+  if distribution not in ("binomial", "uniform"):
+    raise ValueError("Only support 2 corruption distribution: 'uniform' and 'binomial', "
+                     f"but given: '{distribution}'")
+  if n_sel == 0:
+    return out
+  ix = nz[rand.choice(range(len(nz)), size=n_sel, replace=False)]
+  if distribution == "binomial":
+    vals = rand.binomial(n=out.data[ix].astype(np.int32), p=retain_rate)
+  else:
+    vals = np.multiply(out.data[ix], rand.binomial(n=np.ones(len(ix), dtype=np.int32), p=retain_rate))
+  out.data[ix] = vals
+  out.eliminate_zeros()
+  return out
+
+
 def library_size(x: np.ndarray):
   """-> (log_counts [N], local_mean, local_var); the model receives
-  library = [[local_mean, local_var]] * N (data/_single_cell_base.py:568-570)."""
+  library = [[local_mean, local_var]] * N (data/_single_cell_base.py:568-570).  x may be sparse (row sums: `row_sums`)."""
   if x.ndim != 2:
     raise ValueError("Only support 2-D matrix")
-  total = x.sum(axis=1)
+  total = row_sums(x)
   log_counts = np.log(total + 1e-8)
   return log_counts, np.float32(np.mean(log_counts)), np.float32(np.var(log_counts))
 
@@ -212,7 +276,9 @@ class BatchDataset:
 
   def __init__(self, arrays: Sequence[np.ndarray], omics: Sequence[str], library: np.ndarray, mask: np.ndarray,
                batch_size: int = 64, drop_remainder: bool = False, shuffle: int = 1000, seed: int = 1):
-    self.arrays = [np.ascontiguousarray(a, dtype=np.float32) for a in arrays]
+    # the counts (arrays[0]) may be sparse: kept as canonical float32 CSR, batches are CSR row blocks; other omics are dense
+    self.arrays = [as_csr(a, copy=False) if (i == 0 and is_sparse(a)) else
+                   np.ascontiguousarray(a.toarray() if is_sparse(a) else a, dtype=np.float32) for i, a in enumerate(arrays)]
     self.omics = list(omics)
     self.library = np.ascontiguousarray(library, dtype=np.float32)
     self.mask = np.ascontiguousarray(mask, dtype=bool)
@@ -245,7 +311,8 @@ class SingleCellOMIC:
     self.add_omic(omic, X, var_names)
 
   def add_omic(self, omic: str, X, var_names=None):
-    X = np.ascontiguousarray(X, dtype=np.float32)
+    """X: dense (stored as float32) or any scipy.sparse matrix (stored as canonical float32 CSR, never densified)."""
+    X = as_csr(X) if is_sparse(X) else np.ascontiguousarray(X, dtype=np.float32)
     if self._data and X.shape[0] != self.n_obs:
       raise ValueError(f"Number of cell mismatch {self.n_obs} and {X.shape[0]}")
     self._data[str(omic)] = X
@@ -274,6 +341,9 @@ class SingleCellOMIC:
 
   def numpy(self, omic=None):
     return self._data[str(omic) if omic is not None else self.omics[0]]
+
+  def is_sparse(self, omic=None) -> bool:
+    return is_sparse(self.numpy(omic))
 
   def get_dim(self, omic):
     return self._data[str(omic)].shape[1]
@@ -304,7 +374,10 @@ class SingleCellOMIC:
     return om
 
   def sparsity(self, omic=None):
-    return float((self.numpy(omic) == 0).mean())
+    x = self.numpy(omic)
+    if is_sparse(x):   # (canonical CSR: every stored entry is non-zero)
+      return float((x.shape[0] * x.shape[1] - x.nnz) / (x.shape[0] * x.shape[1]))
+    return float((x == 0).mean())
 
   def library_size(self, omic=None):
     return library_matrix(self.numpy(omic))

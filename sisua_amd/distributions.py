@@ -13,6 +13,7 @@ from __future__ import annotations
 from typing import List, Optional, Sequence
 
 import numpy as np
+import scipy.sparse as _sp
 from scipy.special import gammaln
 
 SOFTPLUS_INV_1 = float(np.log(np.expm1(1.0)))
@@ -552,8 +553,11 @@ class LazyCountOutput(Distribution):
     return self._stat("mean_over_samples", out=out)
 
   def log_prob(self, x=None):
-    """log p(x) summed over the genes, [n_samples, n_cells] ([n_cells] without a draw axis); x = None: of the input counts."""
-    return self._stat("log_prob", target=None if x is None else np.asarray(x, np.float32))
+    """log p(x) summed over the genes, [n_samples, n_cells] ([n_cells] without a draw axis); x = None: of the input counts.  x may be
+    scipy.sparse."""
+    if x is not None and not _sp.issparse(x):   # (a sparse target goes to the device as CSR)
+      x = np.asarray(x, np.float32)
+    return self._stat("log_prob", target=x)
 
   # ---- everything else through the eager result ----------------------------------------
   def materialize(self):

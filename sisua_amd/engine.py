@@ -34,6 +34,25 @@ def _f32(a, shape=None):
   return a
 
 
+def _csr3(x, n_genes: int, n_rows: Optional[int] = None):
+  """scipy.sparse rows -> (indptr int64, cols int32, vals float32) of their canonical float32 CSR (data.as_csr), shape-checked."""
+  from sisua_amd.data import as_csr
+  if x.ndim != 2 or x.shape[1] != n_genes or (n_rows is not None and x.shape[0] != n_rows):
+    raise ValueError(f"expected sparse rows [{'n_cells' if n_rows is None else n_rows}, {n_genes}], got {x.shape}")
+  c = as_csr(x, copy=False)
+  return (np.ascontiguousarray(c.indptr, dtype=np.int64), np.ascontiguousarray(c.indices, dtype=np.int32),
+          np.ascontiguousarray(c.data, dtype=np.float32))
+
+
+def _csr_ptrs(t):
+  return (t[0].ctypes.data_as(C.POINTER(C.c_int64)), t[1].ctypes.data_as(C.POINTER(C.c_int32)), _fp(t[2]))
+
+
+def _sparse(x) -> bool:
+  from sisua_amd.data import is_sparse
+  return is_sparse(x)
+
+
 def make_smx_config(cfg: ModelConfig, max_batch: int) -> smx_config:
   c = smx_config()
   c.abi_version = _hip.SMX_ABI_VERSION
@@ -177,6 +196,8 @@ class Engine:
       raise ValueError("storage must be 'f32', 'u16' or 'csr'")
     if storage == "csr":
       return self._upload_csr(X, labels, library, label_mask, cell_id_base)
+    if _sparse(X):   # a dense store from sparse rows: expanded block by block on the device, never whole on the host
+      return self._upload_csr(X, labels, library, label_mask, cell_id_base, dense_store=storage)
     if storage == "u16":
       Xf = np.asarray(X)
       if Xf.size and (Xf.min() < 0 or Xf.max() > 65535 or not np.array_equal(Xf, np.floor(Xf))):
@@ -201,16 +222,14 @@ class Engine:
       check(self.lib.smx_dataset_upload(self._h, _fp(X), n, lab_ptrs, _fp(lib_arr), mask_ptr, int(cell_id_base)))
     self.n_cells = n
 
-  def _upload_csr(self, X, labels, library, label_mask, cell_id_base):
+  def _upload_csr(self, X, labels, library, label_mask, cell_id_base, dense_store=None):
     G = self.cfg.n_genes
     if isinstance(X, tuple) and len(X) == 3:
       indptr, indices, data = X
     elif hasattr(X, "tocsr"):   # scipy.sparse
       if X.shape[1] != G:
         raise ValueError(f"X must be [n_cells, {G}]")
-      X = X.tocsr()
-      X.sort_indices()
-      indptr, indices, data = X.indptr, X.indices, X.data
+      indptr, indices, data = _csr3(X, G)
     else:
       Xd = _f32(X)
       if Xd.ndim != 2 or Xd.shape[1] != G:
@@ -232,8 +251,14 @@ class Engine:
     lib_arr = None if library is None else _f32(library, (n, 2))
     mask_arr = None if label_mask is None else np.ascontiguousarray(label_mask, dtype=np.uint8).reshape(n)
     mask_ptr = None if mask_arr is None else mask_arr.ctypes.data_as(C.POINTER(C.c_uint8))
-    check(self.lib.smx_dataset_upload_csr(self._h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), indices.ctypes.data_as(C.POINTER(C.c_int32)),
-                                          _fp(data), n, lab_ptrs, _fp(lib_arr), mask_ptr, int(cell_id_base)))
+    if dense_store is not None:
+      if dense_store == "u16" and data.size and (data.min() < 0 or data.max() > 65535 or not np.array_equal(data, np.floor(data))):
+        raise ValueError("storage='u16' needs integer counts in [0, 65535]")
+      check(self.lib.smx_dataset_upload_csr_dense(self._h, *_csr_ptrs((indptr, indices, data)), n, lab_ptrs, _fp(lib_arr), mask_ptr,
+                                                  int(cell_id_base), 1 if dense_store == "u16" else 0))
+    else:
+      check(self.lib.smx_dataset_upload_csr(self._h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), indices.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            _fp(data), n, lab_ptrs, _fp(lib_arr), mask_ptr, int(cell_id_base)))
     self.n_cells = n
 
   # ---- steps -----------------------------------------------------------------------
@@ -357,10 +382,11 @@ class Engine:
   def predict(self, x, library=None, n_samples: int = 1, batch: Optional[int] = None, want_x_params: bool = True):
     """Eval-mode forward of a whole host matrix in one call (smx_predict): arrays over ALL cells, with a leading draw
     axis for z_sample / l_sample / x_params / y_params -- the layout of forward_samples with n = every cell.
-    want_x_params=False: everything but the gene output's parameter planes (what a lazy result keeps on the device side)."""
+    want_x_params=False: everything but the gene output's parameter planes (what a lazy result keeps on the device side).
+    x may be scipy.sparse (smx_predict_csr: the same results bit for bit)."""
     cfg = self.cfg
-    xa = _f32(x)
-    N, S = xa.shape[0], int(n_samples)
+    xa = _csr3(x, cfg.n_genes) if _sparse(x) else _f32(x)
+    N, S = (xa[0].size - 1 if isinstance(xa, tuple) else xa.shape[0]), int(n_samples)
     B = min(int(batch or self.max_batch), self.max_batch)
     la = None if library is None else _f32(library, (N, 2))
     D, G, k = cfg.latent_dim, cfg.n_genes, cfg.k
@@ -371,9 +397,12 @@ class Engine:
     out["x_params"] = np.empty((S, k, N, G), np.float32) if want_x_params else None
     ys = [np.empty((S, N, label_planes(llk, P) * P), np.float32) for P, llk in cfg.head_labels]
     yptrs = (C.POINTER(C.c_float) * max(1, len(ys)))(*[_fp(y) for y in ys]) if ys else None
-    check(self.lib.smx_predict(self._h, _fp(xa), _fp(la), N, B, S, _fp(out["z_mean"]), _fp(out.get("z_scale")),
-                               _fp(out["z_sample"]), _fp(out.get("l_mean")), _fp(out.get("l_scale")), _fp(out.get("l_sample")),
-                               _fp(out["x_params"]), yptrs))
+    res = (_fp(out["z_mean"]), _fp(out.get("z_scale")), _fp(out["z_sample"]), _fp(out.get("l_mean")), _fp(out.get("l_scale")),
+           _fp(out.get("l_sample")), _fp(out["x_params"]), yptrs)
+    if isinstance(xa, tuple):
+      check(self.lib.smx_predict_csr(self._h, *_csr_ptrs(xa), _fp(la), N, B, S, *res))
+    else:
+      check(self.lib.smx_predict(self._h, _fp(xa), _fp(la), N, B, S, *res))
     out["y_params"] = ys
     return out
 
@@ -384,10 +413,11 @@ class Engine:
     """A statistic of the gene output over a whole host matrix (smx_predict_stat): the same passes and draws as predict(), but only the
     statistic leaves the device.  'mean' / 'variance' [n_samples, N, G]; 'mean_over_samples' [N, G]; 'log_prob' [n_samples, N] of `target`
     (default: of x itself).  count_only: the count distribution without the zero-inflation wrapper.  `out`: a float32 array of the
-    result's shape to write into (a reused array saves the first-touch page faults of a fresh one)."""
+    result's shape to write into (a reused array saves the first-touch page faults of a fresh one).  x and target may be scipy.sparse
+    (smx_predict_stat_csr)."""
     cfg = self.cfg
-    xa = _f32(x)
-    N, S, G = xa.shape[0], int(n_samples), cfg.n_genes
+    xa = _csr3(x, cfg.n_genes) if _sparse(x) else _f32(x)
+    N, S, G = (xa[0].size - 1 if isinstance(xa, tuple) else xa.shape[0]), int(n_samples), cfg.n_genes
     B = min(int(batch or self.max_batch), self.max_batch)
     la = None if library is None else _f32(library, (N, 2))
     code = self.STATS[stat]
@@ -396,8 +426,17 @@ class Engine:
       out = np.empty(shape, np.float32)
     elif out.dtype != np.float32 or tuple(out.shape) != shape or not out.flags.c_contiguous:
       raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
-    ta = None if target is None else _f32(target, (N, G))
-    check(self.lib.smx_predict_stat(self._h, _fp(xa), _fp(la), N, B, S, code, int(bool(count_only)), _fp(ta), _fp(out)))
+    tc = _csr3(target, G, N) if (target is not None and _sparse(target)) else None
+    ta = None if (target is None or tc is not None) else _f32(target, (N, G))
+    if isinstance(xa, tuple) or tc is not None:
+      if not isinstance(xa, tuple):   # (a dense input with a CSR target: the CSR entry point takes both)
+        import scipy.sparse as sp
+        xa = _csr3(sp.csr_matrix(xa), G)
+      xc = xa
+      tp = _csr_ptrs(tc) if tc is not None else (None, None, None)
+      check(self.lib.smx_predict_stat_csr(self._h, *_csr_ptrs(xc), _fp(la), N, B, S, code, int(bool(count_only)), _fp(ta), *tp, _fp(out)))
+    else:
+      check(self.lib.smx_predict_stat(self._h, _fp(xa), _fp(la), N, B, S, code, int(bool(count_only)), _fp(ta), _fp(out)))
     return out
 
   def decode(self, z, l=None):
@@ -415,7 +454,15 @@ class Engine:
     return dict(x_params=xp, y_params=ys)
 
   def marginal_llk(self, row_ids=None, x=None, library=None, n_samples: int = 100):
-    """Importance-weighted log p(x) per cell and the mean reconstruction log-likelihood (GPU)."""
+    """Importance-weighted log p(x) per cell and the mean reconstruction log-likelihood (GPU).  x may be scipy.sparse
+    (smx_marginal_llk_csr)."""
+    if row_ids is None and _sparse(x):
+      xc = _csr3(x, self.cfg.n_genes)
+      B = xc[0].size - 1
+      la = None if library is None else _f32(library, (B, 2))
+      mllk, llk = np.empty(B, np.float32), np.empty(B, np.float32)
+      check(self.lib.smx_marginal_llk_csr(self._h, *_csr_ptrs(xc), _fp(la), B, int(n_samples), _fp(mllk), _fp(llk)))
+      return mllk, llk
     if row_ids is not None:
       ids = self._ids(row_ids)
       B, idp, xp, lp = ids.size, ids.ctypes.data_as(C.POINTER(C.c_int32)), None, None
@@ -463,7 +510,11 @@ class Engine:
   def score_llk(self, targets, row_ids=None, x=None, library=None, n_samples: int = 10):
     """Posterior-predictive log-likelihood per cell (Posterior.cal_llk, posterior.py:919-938), on the GPU.
     `targets`: list of [B, G] matrices (None = the input cells).  Returns [len(targets), 2, B]:
-    [:, 0] under the output distribution, [:, 1] under its count distribution without zero inflation."""
+    [:, 0] under the output distribution, [:, 1] under its count distribution without zero inflation.
+    x and the targets may be scipy.sparse: a call holds one batch (<= max_batch rows), densified here as a row block."""
+    if _sparse(x):
+      x = x.toarray()
+    targets = [t.toarray() if _sparse(t) else t for t in targets]
     if row_ids is not None:
       ids = self._ids(row_ids)
       B, idp, xp, lp = ids.size, ids.ctypes.data_as(C.POINTER(C.c_int32)), None, None

@@ -22,7 +22,7 @@ import numpy as np
 
 from sisua_amd import distributions as D
 from sisua_amd.config import ModelConfig, NetConf, RVmeta, init_params
-from sisua_amd.data import BatchDataset, SingleCellOMIC, library_matrix
+from sisua_amd.data import BatchDataset, SingleCellOMIC, as_csr, is_sparse, library_matrix
 from sisua_amd.engine import Engine
 
 __all__ = ["SingleCellModel", "VAE", "SISUA", "MISA", "SCALE", "SCVI", "DeepCountAutoencoder", "NetConf", "RVmeta", "get_model",
@@ -51,6 +51,12 @@ def _flatten(x):
   return [x]
 
 
+def _rows(a):
+  """Host rows as the engine takes them: scipy.sparse -> canonical float32 CSR (no copy when it is one already), else a dense
+  float32 array."""
+  return as_csr(a, copy=False) if is_sparse(a) else np.ascontiguousarray(a, dtype=np.float32)
+
+
 def train_draws(sample_shape) -> int:
   """Monte-Carlo draws per cell of a training step: S = prod(sample_shape); (), [] and 1 all mean one draw."""
   shape = (sample_shape,) if np.isscalar(sample_shape) else tuple(sample_shape)
@@ -72,9 +78,9 @@ def _to_data(x, batch_size=64) -> BatchDataset:
   if isinstance(x, BatchDataset):
     return x
   arrs = _flatten(x)
-  sco = SingleCellOMIC(np.asarray(arrs[0]))
+  sco = SingleCellOMIC(arrs[0] if is_sparse(arrs[0]) else np.asarray(arrs[0]))
   for arr, om in zip(arrs[1:], _OMIC_ORDER[1:]):
-    sco.add_omic(om, np.asarray(arr))
+    sco.add_omic(om, arr if is_sparse(arr) else np.asarray(arr))
   return sco.create_dataset(sco.omics, batch_size=batch_size, drop_remainder=True)
 
 
@@ -315,7 +321,7 @@ class SingleCellModel:
            earlystop_threshold=0.001, earlystop_progress_length=0, earlystop_patience=20, earlystop_min_epoch=-1,
            terminate_on_nan=True, checkpoint=None, allow_rollback=False, allow_none_gradients=False,
            track_gradient_norms=False, log_tag=None, verbose=False, distributed="auto",
-           dp_batch="global", sync_bn=False, storage="f32", epochs_are_total=False, **ignored):
+           dp_batch="global", sync_bn=False, storage=None, epochs_are_total=False, **ignored):
     r"""The training loop (odin Trainer under single_cell_model.py:213-236).
 
     The minibatch schedule is a pure function of the optimiser step count: iteration `it` visits batch
@@ -337,7 +343,11 @@ class SingleCellModel:
     and the loss is the mean over cells and draws of -(llk_x + llk_outputs + alpha mask llk_y) + beta KL -- the plain
     Monte-Carlo ELBO, not an importance-weighted bound ([3P-recall] odin's VariationalModel.elbo: the ELBO terms of the
     `sample_shape` draws averaged over the sample axis).  Validation uses the same S in eval mode.  FactorVAE / SemiFVAE
-    and data parallel jobs take S = 1 only (ValueError)."""
+    and data parallel jobs take S = 1 only (ValueError).
+
+    `storage`: how the counts are resident ('f32', 'u16', 'csr'; Engine.upload).  Default: 'csr' for sparse counts (a sparse
+    SingleCellOMIC / BatchDataset), whose rows reach the device as CSR without a dense host matrix, unless the model has input dropout
+    (keyed by the dense store's rows); 'f32' otherwise.  'f32' / 'u16' of sparse counts are expanded on the device block by block."""
     if str(optimizer).lower() != "adam":
       raise ValueError("only the 'adam' optimizer of configs/base.yaml is built")
     n_draws = train_draws(sample_shape)
@@ -385,8 +395,15 @@ class SingleCellModel:
     X = train.arrays[0][lo:hi]
     labs = [train.arrays[1 + j][lo:hi] for j in range(n_lab)]
     lib, mask = train.library[lo:hi], train.mask[lo:hi]
+    sparse_x = is_sparse(X) or (valid is not None and is_sparse(valid.arrays[0]))
+    if storage is None:   # (the sparse store cannot key input dropout: such a model keeps the float32 store, filled from the CSR rows)
+      storage = "csr" if (sparse_x and not self._make_config().input_dropout > 0) else "f32"
     if valid is not None:
-      X = np.concatenate([X, valid.arrays[0]], 0)
+      if sparse_x:   # (sparse counts stay sparse: the rows are joined as CSR)
+        import scipy.sparse as sp
+        X = sp.vstack([as_csr(sp.csr_matrix(a), copy=False) for a in (X, valid.arrays[0])], format="csr")
+      else:
+        X = np.concatenate([X, valid.arrays[0]], 0)
       labs = [np.concatenate([a, valid.arrays[1 + j]], 0) for j, a in enumerate(labs)]
       lib = np.concatenate([lib, valid.library], 0)
       mask = np.concatenate([mask, valid.mask], 0)
@@ -620,11 +637,21 @@ class SingleCellModel:
 
   def __call__(self, inputs=None, library=None, mask=None, training=None, sample_shape=(), **kwargs):
     arrs = _flatten(inputs)
-    x = np.ascontiguousarray(arrs[0], dtype=np.float32)
+    x = _rows(arrs[0])
     if self._cfg.model == "scvi" and library is None:
       library = library_matrix(x)
     n = int(np.prod(sample_shape)) if np.size(sample_shape) else 0
     e = self._ensure_engine(x.shape[0])
+    if is_sparse(x):   # the whole input is one batch of smx_predict_csr: the numbers of smx_forward(_samples) on the dense rows
+      o = e.predict(x, library=library, n_samples=max(n, 1), batch=x.shape[0])
+      if n > 1:
+        pX = self._output_dists(o["x_params"], o["y_params"], stacked=True)
+      else:
+        pX = self._output_dists([o["x_params"][0]], [[y[0] for y in o["y_params"]]])
+      first = dict(o, z_sample=o["z_sample"][0])
+      if "l_sample" in o:
+        first["l_sample"] = o["l_sample"][0]
+      return pX, self._latent_dists(first)
     if n > 1:   # every draw in one call: the encoders run once, the draws re-sample the latents and decode
       o = e.forward_samples(n, x=x, library=library)
       pX = self._output_dists(o["x_params"], o["y_params"], stacked=True)
@@ -640,11 +667,17 @@ class SingleCellModel:
     r"""log1p + encoder network + latent posterior (single_cell_model.py:119-139); SCVI
     returns [q(z|x), q(l|x)] (scvi.py:88-106)."""
     arrs = _flatten(inputs)[:self._n_inputs]
-    x = np.ascontiguousarray(arrs[0], dtype=np.float32)
+    x = _rows(arrs[0])
     if self._cfg.model == "scvi" and library is None:
       library = library_matrix(x)
     e = self._ensure_engine(x.shape[0])
-    out = e.forward(x=x, library=library, want_x_params=False)
+    if is_sparse(x):   # (one batch of smx_predict_csr; the whole forward pass, as smx_forward runs it)
+      o = e.predict(x, library=library, n_samples=1, batch=x.shape[0])
+      out = dict(o, z_sample=o["z_sample"][0])
+      if "l_sample" in o:
+        out["l_sample"] = o["l_sample"][0]
+    else:
+      out = e.forward(x=x, library=library, want_x_params=False)
     return self._latent_dists(out)
 
   def decode(self, latents, training=None, mask=None, sample_shape=(), **kwargs):
@@ -684,7 +717,7 @@ class SingleCellModel:
     ds = _to_data(inputs, batch_size=batch_size) if not isinstance(inputs, BatchDataset) else inputs
     if not isinstance(inputs, (BatchDataset, SingleCellOMIC)):
       ds.drop_remainder = False
-    ds.shuffle = 0 if isinstance(inputs, (np.ndarray, list, tuple)) else ds.shuffle
+    ds.shuffle = 0 if (isinstance(inputs, (np.ndarray, list, tuple)) or is_sparse(inputs)) else ds.shuffle
     if ds.shuffle == 0 and ds.n_obs > 0:
       # cells in their own order: the minibatch loop runs inside the library (smx_predict) and every result is written
       # once, straight into the arrays the returned distributions hold -- no per-batch arrays, no concatenation
@@ -725,7 +758,7 @@ class SingleCellModel:
       # the gene output stays a handle (its planes never leave the device); the small head outputs and the latents are eager as always
       heads = self._output_dists(None, o["y_params"], stacked=True, heads_only=True) if n > 1 else \
           self._output_dists(None, [[y[0] for y in o["y_params"]]], heads_only=True)
-      px = D.LazyCountOutput(self, np.ascontiguousarray(x, dtype=np.float32), lib, n, B, self._outputs[0].name or "transcriptomic")
+      px = D.LazyCountOutput(self, _rows(x), lib, n, B, self._outputs[0].name or "transcriptomic")
       pX = (px,) + tuple(heads) if heads else px
     elif n > 1:
       pX = self._output_dists(o["x_params"], o["y_params"], stacked=True)
@@ -747,7 +780,7 @@ class SingleCellModel:
     arrs = _flatten(inputs)
     if len(self._outputs) > 1:
       return self._joint_marginal_log_prob(arrs, library, sample_shape, batch_size)
-    x = np.ascontiguousarray(arrs[0], dtype=np.float32)
+    x = _rows(arrs[0])
     S = int(np.prod(sample_shape)) if np.size(sample_shape) else 1
     if self._cfg.model == "scvi" and library is None:
       library = library_matrix(x)
@@ -776,8 +809,8 @@ class SingleCellModel:
                                 "built: the joint estimate needs the per-draw log q_mix(z | x) from the device")
     if len(arrs) < n_out:
       raise ValueError(f"marginal_log_prob of this model needs the {n_out} output variables' arrays as inputs=[x, y, ...]")
-    x = np.ascontiguousarray(arrs[0], dtype=np.float32)
-    ys = [np.ascontiguousarray(a, dtype=np.float32) for a in arrs[1:n_out]]
+    x = _rows(arrs[0])
+    ys = [np.ascontiguousarray(a.toarray() if is_sparse(a) else a, dtype=np.float32) for a in arrs[1:n_out]]
     S = int(np.prod(sample_shape)) if np.size(sample_shape) else 1
     if cfg.model == "scvi" and library is None:
       library = library_matrix(x)
@@ -840,8 +873,8 @@ class SingleCellModel:
     the 'reconstructed' (output distribution) and 'imputed' (count distribution without zero inflation)
     likelihoods of the original and of the corrupted counts are reduced as
     mean_cells(logsumexp_draws - log n_draws).  Returns the dict with the reference's keys."""
-    x_cor = np.ascontiguousarray(_flatten(corrupted)[0], dtype=np.float32)
-    x_org = x_cor if original is None else np.ascontiguousarray(_flatten(original)[0], dtype=np.float32)
+    x_cor = _rows(_flatten(corrupted)[0])
+    x_org = x_cor if original is None else _rows(_flatten(original)[0])
     S = int(np.prod(sample_shape)) if np.size(sample_shape) else 1
     if self._cfg.model == "scvi" and library is None:
       library = library_matrix(x_cor)
