@@ -261,12 +261,7 @@ int ensure_sync_buf(smx_model* m) {
   int wmax = 0;
   for (int w : m->bn_wp) wmax = std::max(wmax, w);
   const size_t need = (size_t)m->world * 2 * (size_t)wmax;
-  if (!m->sync_bn || need <= m->sync_cap) return SMX_OK;
-  if (m->sync_buf) hipFree(m->sync_buf);
-  m->sync_buf = nullptr; m->sync_cap = 0;
-  SMX_CHECK(dmalloc(&m->sync_buf, need));
-  m->sync_cap = need;
-  return SMX_OK;
+  return m->sync_bn ? dgrow(m, &m->sync_buf, &m->sync_cap, need) : SMX_OK;
 }
 }  // namespace smx
 extern "C" {
@@ -317,12 +312,7 @@ int smx_comm_init_local(smx_model* const* models, int n) {
     int wmax = 0;
     for (int w : m->bn_wp) wmax = std::max(wmax, w);
     const size_t need = std::max(m->grads_count + (size_t)m->n_chunks, (size_t)n * 2 * (size_t)wmax);
-    if (need > m->local_scratch_cap) {
-      if (m->local_scratch) hipFree(m->local_scratch);
-      m->local_scratch = nullptr; m->local_scratch_cap = 0;
-      SMX_CHECK(dmalloc(&m->local_scratch, need));
-      m->local_scratch_cap = need;
-    }
+    SMX_CHECK(dgrow(m, &m->local_scratch, &m->local_scratch_cap, need));
     SMX_CHECK(ensure_sync_buf(m));
     SMX_CHECK(ensure_comm_stream(m));   // (the chained two-bucket form runs on the loopback too: smx_step.hip, dp_chain_start)
   }

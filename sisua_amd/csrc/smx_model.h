@@ -326,6 +326,26 @@ int dmalloc(T** p, size_t n) {
   if (e != hipSuccess) { set_error(std::string("hipMemset failed: ") + hipGetErrorString(e)); return SMX_ERR_HIP; }
   return SMX_OK;
 }
+// a scratch buffer kept across calls (*p, *cap elements): when need passes the capacity, the stream drains (work in flight may read the
+// buffer) and it is reallocated with max(need, want) elements
+template <typename T>
+int dgrow(smx_model* m, T** p, size_t* cap, size_t need, size_t want = 0) {
+  if (need <= *cap) return SMX_OK;
+  if (*p) { SMX_HIP(hipStreamSynchronize(m->st)); hipFree(*p); }
+  *p = nullptr; *cap = 0;
+  SMX_CHECK(dmalloc(p, std::max(need, want)));
+  *cap = std::max(need, want);
+  return SMX_OK;
+}
+// ... the same for a pinned host buffer
+inline int hgrow(smx_model* m, float** p, size_t* cap, size_t need, size_t want = 0) {
+  if (need <= *cap) return SMX_OK;
+  if (*p) { SMX_HIP(hipStreamSynchronize(m->st)); hipHostFree(*p); }
+  *p = nullptr; *cap = 0;
+  SMX_HIP(hipHostMalloc((void**)p, std::max(need, want) * sizeof(float), hipHostMallocDefault));
+  *cap = std::max(need, want);
+  return SMX_OK;
+}
 
 inline int32_t* cur_rows(smx_model* m) { return m->rows2[m->par]; }
 inline StepState* cur_state(smx_model* m) { return m->state3 + m->par; }
@@ -348,6 +368,12 @@ struct Pass {
   int global_batch = 0;
   int draw_rows = 0;               // > 0: the pass stacks B / draw_rows Monte-Carlo draws of draw_rows cells; the draw-side noise keys carry it
 };
+// an evaluation pass over B host rows already on the device: counts X [B][Gp], library prior lib [B][2], constants lgx1 [B]; no row ids
+inline Pass host_rows_pass(int B, const float* X, const float* lib, const float* lgx1) {
+  Pass ps;
+  ps.B = B; ps.global_batch = B; ps.training = 0; ps.Xsrc = X; ps.lib = lib; ps.lgx1 = lgx1;
+  return ps;
+}
 
 // smx_model.hip
 int add_tensor(smx_model* m, const std::string& name, int rows, int cols, int chunks, bool vec);

@@ -9,13 +9,7 @@ namespace smx {
 static int fetch_planes(smx_model* m, int B, float* x_params) {
   if (!x_params) return SMX_OK;
   const size_t n = (size_t)B * m->k * m->Gp;
-  if (n > m->pinned_floats) {
-    if (m->pinned) hipHostFree(m->pinned);
-    m->pinned = nullptr; m->pinned_floats = 0;
-    const size_t cap = (size_t)m->Bmax * m->k * m->Gp;
-    SMX_HIP(hipHostMalloc((void**)&m->pinned, (cap > n ? cap : n) * sizeof(float), hipHostMallocDefault));
-    m->pinned_floats = cap > n ? cap : n;
-  }
+  SMX_CHECK(hgrow(m, &m->pinned, &m->pinned_floats, n, (size_t)m->Bmax * m->k * m->Gp));
   SMX_HIP(hipMemcpyAsync(m->pinned, m->P, n * sizeof(float), hipMemcpyDeviceToHost, m->st));
   SMX_HIP(hipStreamSynchronize(m->st));
   const size_t G = (size_t)m->G, ldp = (size_t)m->k * m->Gp;
@@ -25,14 +19,31 @@ static int fetch_planes(smx_model* m, int B, float* x_params) {
   return SMX_OK;
 }
 
+// The label heads' outputs of a batch, device [B][ld] per head -> caller's [B][ky * P] at y_params[j] + y_draw * B * ky * P (a NULL
+// y_params or y_params[j]: not asked for)
+static int fetch_labels(smx_model* m, int B, float* const* y_params, size_t y_draw) {
+  if (!y_params) return SMX_OK;
+  std::vector<float> tmp;
+  for (int j = 0; j < m->n_heads; ++j) {
+    if (!y_params[j]) continue;
+    const int P = m->cfg.label_dim[j], Pp = m->lab_Pp[j], ld = m->tensors[m->t_labW[j]].ld;
+    float* dst = y_params[j] + y_draw * (size_t)B * m->lab_ky[j] * P;
+    tmp.resize((size_t)B * ld);
+    SMX_HIP(hipMemcpy(tmp.data(), m->laby_raw[j], tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; ++b)
+      for (int c = 0; c < m->lab_ky[j]; ++c)
+        memcpy(dst + ((size_t)b * m->lab_ky[j] + c) * P, &tmp[(size_t)b * ld + (size_t)c * Pp], sizeof(float) * P);
+  }
+  return SMX_OK;
+}
+
 // copy the results of the forward pass in flight back to the caller's arrays (any pointer may be NULL);
-// y_off: element offset into every y_params[j] (draw index * batch * width)
+// y_draw: draw index of the label outputs (fetch_labels)
 static int fetch_forward(smx_model* m, int B, float* z_mean, float* z_scale, float* z_sample, float* l_mean, float* l_scale,
                          float* l_sample, float* x_params, float* const* y_params, size_t y_draw) {
   SMX_HIP(hipStreamSynchronize(m->st));
   const int D = m->D, Dp = m->Dp;
   const int lat_ld = m->lat_planes * Dp;
-  std::vector<float> tmp;
   auto fetch2d = [&](float* dst, const float* src, int ld, int w) -> int {
     if (!dst) return SMX_OK;
     SMX_HIP(hipMemcpy2D(dst, (size_t)w * sizeof(float), src, (size_t)ld * sizeof(float), (size_t)w * sizeof(float), (size_t)B,
@@ -48,19 +59,7 @@ static int fetch_forward(smx_model* m, int B, float* z_mean, float* z_scale, flo
     SMX_CHECK(fetch2d(l_sample, m->lsmp, 1, 1));
   }
   SMX_CHECK(fetch_planes(m, B, x_params));
-  if (y_params) {
-    for (int j = 0; j < m->n_heads; ++j) {
-      if (!y_params[j]) continue;
-      const int P = m->cfg.label_dim[j], Pp = m->lab_Pp[j], ld = m->tensors[m->t_labW[j]].ld;
-      float* dst = y_params[j] + y_draw * (size_t)B * m->lab_ky[j] * P;
-      tmp.resize((size_t)B * ld);
-      SMX_HIP(hipMemcpy(tmp.data(), m->laby_raw[j], tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
-      for (int b = 0; b < B; ++b)
-        for (int c = 0; c < m->lab_ky[j]; ++c)
-          memcpy(dst + ((size_t)b * m->lab_ky[j] + c) * P, &tmp[(size_t)b * ld + (size_t)c * Pp], sizeof(float) * P);
-    }
-  }
-  return SMX_OK;
+  return fetch_labels(m, B, y_params, y_draw);
 }
 
 // SingleCellModel.predict over a whole host matrix in ONE call.  The batch loop runs here; after every forward pass one
@@ -87,6 +86,27 @@ __global__ __launch_bounds__(256) void pack_kernel(PackJobs jobs_by_value) {
     dst[r * j.dpitch + c] = src[r * j.spitch + c];
   }
 }
+// One site's job list: add() launches the list when it is full and starts the next one, flush() launches what is left.  Every launch runs
+// gx workgroups per job and gz repetitions (each job's n_rep); every job copies `height` rows.
+struct PackList {
+  hipStream_t st; unsigned gx, gz; int height;
+  PackJobs J;
+  PackList(hipStream_t st_, unsigned gx_, unsigned gz_, int height_) : st(st_), gx(gx_), gz(gz_), height(height_) { J.n = 0; }
+  // rows of `width` floats, src (pitch spitch) -> dst (pitch dpitch); repetition q reads src + q src_rep, writes dst + q dst_rep (no dst: no job)
+  int add(float* dst, size_t dpitch, const float* src, size_t spitch, size_t width, size_t dst_rep = 0, size_t src_rep = 0) {
+    if (!dst) return SMX_OK;
+    if (J.n == SMX_PACK_MAX) SMX_CHECK(flush());
+    J.j[J.n++] = PackJob{dst, (long)dpitch, src, (long)spitch, (int)width, height, (int)gz, (long)dst_rep, (long)src_rep};
+    return SMX_OK;
+  }
+  int flush() {
+    if (!J.n) return SMX_OK;
+    hipLaunchKernelGGL(pack_kernel, dim3(gx, (unsigned)J.n, gz), dim3(256), 0, st, J);
+    J.n = 0;
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
+  }
+};
 
 // ---- statistics of the gene output on the device (smx_predict_stat): what the reference's callers ask of predict()'s result --
 // y.mean() / .variance() / .log_prob(x), posterior.py:187-255 -- computed from the parameter planes of a pass WITHOUT the planes leaving
@@ -205,13 +225,7 @@ static int stage_csr_rows(smx_model* m, const CsrRows& c, size_t r0, size_t n, c
 // the same through the model's growable buffer m->csr_host (one batch of rows: smx_marginal_llk_csr, a batch of CSR targets; a block of
 // a dense store uploaded from CSR, u16: the uint16 store)
 int csr_host_rows(smx_model* m, const CsrRows& c, size_t r0, size_t n, void* out, float* lgx1, int u16) {
-  const size_t need = csr_stage_bytes(n, (size_t)(c.indptr[r0 + n] - c.indptr[r0]));
-  if (need > m->csr_host_bytes) {
-    if (m->csr_host) { SMX_HIP(hipStreamSynchronize(m->st)); hipFree(m->csr_host); }
-    m->csr_host = nullptr; m->csr_host_bytes = 0;
-    SMX_CHECK(dmalloc(&m->csr_host, need));
-    m->csr_host_bytes = need;
-  }
+  SMX_CHECK(dgrow(m, &m->csr_host, &m->csr_host_bytes, csr_stage_bytes(n, (size_t)(c.indptr[r0 + n] - c.indptr[r0]))));
   return stage_csr_rows(m, c, r0, n, m->csr_host, out, lgx1, u16);
 }
 
@@ -260,6 +274,161 @@ bool stacked_scoring_ok(const smx_model* m) {
   return m->dec[0].in_p == m->Dp;
 }
 
+// ---- smx_predict's batch loop (predict_core below) -------------------------------------------------------------------------------------
+// The device staging of one chunk of cells: its input rows and every requested output, each output segment laid out like the caller's
+// array for the chunk's Cn cells (NULL: not asked for)
+struct PredChunk {
+  size_t Cn = 0, S = 0;   // cells of the chunk, draws per cell
+  const StatReq* sr = nullptr;
+  char* csr = nullptr;    // CSR input: the chunk's indptr slice | cols | vals (csr_stage_bytes)
+  float *in_raw = nullptr, *in_x = nullptr, *in_lib = nullptr, *in_lgx1 = nullptr;   // input: raw rows [Cn][G] (dense), the tile [Cn][Gp], library prior, constants
+  float *zm = nullptr, *zs = nullptr, *lm = nullptr, *ls = nullptr;   // latent moments [Cn][D] / [Cn]
+  float *zd = nullptr, *ld = nullptr, *xp = nullptr, *st = nullptr;   // draws [S][Cn][D] / [S][Cn], planes [S][k][Cn][G], the statistic
+  float* y[SMX_MAX_LABELS] = {};    // label outputs [S][Cn][wy]
+  size_t wy[SMX_MAX_LABELS] = {};   // ... their widths per cell and draw
+};
+
+// the chunk's input rows from c0 on -> in_x [Cn][Gp], in_lib, in_lgx1 as ONE contiguous copy each: a host-to-device copy per minibatch from
+// the caller's pageable array is staged synchronously by the runtime -- ~60 us per batch, at batch 8 (Posterior's default) most of the call.
+// Dense rows: raw [Cn][G] -> a device re-pitch to [Cn][Gp] and the rows' likelihood constants from row_stats.  CSR rows: whole batches while
+// their non-zeros fit nnz_cap (the first batch always does; Cn shrinks to them), the tile and the constants from one launch.
+static int load_chunk(smx_model* m, PredChunk& c, const float* host_x, const CsrRows* cx, const float* host_library, size_t c0, size_t batch,
+                      size_t nnz_cap) {
+  const size_t G = (size_t)m->G, Gp = (size_t)m->Gp;
+  if (cx) {
+    size_t end = c0;
+    while (end < c0 + c.Cn) {
+      const size_t nxt = std::min(end + batch, c0 + c.Cn);
+      if (end > c0 && (size_t)(cx->indptr[nxt] - cx->indptr[c0]) > nnz_cap) break;
+      end = nxt;
+    }
+    c.Cn = end - c0;
+    SMX_REQUIRE((size_t)(cx->indptr[c0 + c.Cn] - cx->indptr[c0]) <= nnz_cap, "CSR chunk exceeds its staging");
+    SMX_CHECK(stage_csr_rows(m, *cx, c0, c.Cn, c.csr, c.in_x, c.in_lgx1));
+  } else {
+    SMX_HIP(hipMemcpyAsync(c.in_raw, host_x + c0 * G, c.Cn * G * sizeof(float), hipMemcpyHostToDevice, m->st));
+    if (Gp != G) SMX_HIP(hipMemsetAsync(c.in_x, 0, c.Cn * Gp * sizeof(float), m->st));
+    PackList pl(m->st, (unsigned)std::min<size_t>(1024, (c.Cn * G + 255) / 256), 1, (int)c.Cn);
+    SMX_CHECK(pl.add(c.in_x, Gp, c.in_raw, G, G));
+    SMX_CHECK(pl.flush());
+    SMX_CHECK(launch_row_stats(m->st, c.in_x, 0, (long)Gp, (long)c.Cn, m->G, c.in_lgx1, nullptr));
+  }
+  if (host_library) SMX_HIP(hipMemcpyAsync(c.in_lib, host_library + c0 * 2, c.Cn * 2 * sizeof(float), hipMemcpyHostToDevice, m->st));
+  return SMX_OK;
+}
+
+// the statistic of the planes P of Sn draws (stacked rows) of the batch at b0 into the chunk's staging
+static int stat_of(smx_model* m, const PredChunk& c, const Pass& ps, const float* P, long ldp, int Sn, size_t s0, size_t b0) {
+  const StatReq& sr = *c.sr;
+  const size_t G = (size_t)m->G, Cn = c.Cn;
+  StatArgs a;
+  a.P = P; a.ldp = ldp; a.plane_stride = m->Gp; a.B = ps.B; a.Sn = Sn; a.G = m->G; a.lk = m->cfg.likelihood; a.direct = m->scvi ? 1 : 0;
+  a.count_only = sr.count_only; a.stat = sr.stat; a.inv_S = 1.f / (float)c.S; a.accumulate = s0 > 0 ? 1 : 0;
+  a.T = nullptr; a.ldt = 0; a.trows = nullptr; a.t_u16 = 0;
+  if (sr.stat == 2) { a.dst = c.st + b0 * G; a.dst_draw = 0; }
+  else if (sr.stat == 3) {
+    a.dst = c.st + s0 * Cn + b0; a.dst_draw = (long)Cn;
+    if (sr.target || sr.tcsr) { a.T = m->pred_target; a.ldt = m->Gp; }
+    else { a.T = ps.Xsrc; a.ldt = m->Gp; a.trows = ps.xrows; a.t_u16 = ps.x_u16; }   // the input rows themselves
+  } else { a.dst = c.st + (s0 * Cn + b0) * G; a.dst_draw = (long)(Cn * G); }
+  return launch_plane_stat(m->st, a);
+}
+
+// the latent moments of the batch at b0 (the encoders' outputs of the pass in flight) onto a pack list into the chunk's staging
+static int add_latent_moments(smx_model* m, PackList& pl, const PredChunk& c, size_t b0) {
+  const size_t D = (size_t)m->D, Dp = (size_t)m->Dp;
+  SMX_CHECK(pl.add(c.zm ? c.zm + b0 * D : nullptr, D, m->mixpost ? m->zmean : m->latbuf, m->mixpost ? Dp : m->lat_planes * Dp, D));
+  SMX_CHECK(pl.add(c.zs ? c.zs + b0 * D : nullptr, D, m->sig, Dp, D));
+  SMX_CHECK(pl.add(c.lm ? c.lm + b0 : nullptr, 1, m->latlbuf, 32, 1));
+  return pl.add(c.ls ? c.ls + b0 : nullptr, 1, m->lsig, 1, 1);
+}
+
+// One batch in the stacked form: the encoder once, then the draws of the batch as rows of one decoder pass (as the scoring paths,
+// smx_score.hip) -- at batch 8 x 10 draws (Posterior's defaults, posterior.py:114-115) the draw-by-draw form is 50 launches per 8 cells.
+// ids: the draw kernel's noise ids of the pass's rows (NULL: the row index).  need_dec: run the decoder and the heads at all.
+static int predict_batch_stacked(smx_model* m, const PredChunk& c, const Pass& ps, size_t b0, const int32_t* ids, bool need_dec) {
+  const int B = ps.B, Dp = m->Dp;
+  const size_t S = c.S, Cn = c.Cn, G = (size_t)m->G, D = (size_t)m->D, k = (size_t)m->k;
+  SMX_CHECK(forward_pass(m, ps, false, false, 3));   // encoder + latent moments only
+  int Hmax = 0, lab_floats = 0;
+  for (const MlpLayer& L : m->dec) Hmax = std::max(Hmax, L.out_p);
+  for (int j = 0; j < m->n_heads; ++j) lab_floats += c.y[j] ? m->tensors[m->t_labW[j]].ld : 0;
+  const size_t ldp = k * (size_t)m->Gp;
+  const int Sc = (int)std::min<size_t>(S, std::max<size_t>(1, (size_t)4096 / (size_t)B));   // draws per pass
+  const size_t R = (size_t)Sc * B;
+  SMX_CHECK(dgrow(m, &m->score_buf, &m->score_floats, R * ((size_t)Dp + 1 + 2 * (size_t)Hmax + ldp + (size_t)lab_floats)));
+  float* zst = m->score_buf;
+  float* lwst = zst + R * Dp;
+  float* hb[2] = {lwst + R, lwst + R + R * Hmax};
+  float* Pst = hb[1] + R * Hmax;
+  float* yst = Pst + R * ldp;
+  {
+    PackList pl(m->st, 8, 1, B);
+    SMX_CHECK(add_latent_moments(m, pl, c, b0));
+    SMX_CHECK(pl.flush());
+  }
+  for (size_t s0 = 0; s0 < S; s0 += (size_t)Sc) {
+    const int Sn = (int)std::min<size_t>((size_t)Sc, S - s0);
+    const long rows = (long)Sn * B;
+    ScoreDrawArgs d;
+    d.lat = m->latbuf; d.ld = 2 * Dp; d.B = B; d.D = m->D; d.Dp = Dp; d.S = Sn; d.s0 = (int)s0;
+    d.nk = make_key(m, ST_EPS_Z, 0, false); d.rows = ids; d.cell_base = ps.cell_base; d.z = zst; d.lw = lwst;
+    SMX_CHECK(launch_score_draws(m->st, d));
+    const float* hl = nullptr; int hld = 0;
+    if (need_dec) SMX_CHECK(stacked_decoder(m, zst, rows, hb, 0, nullptr, &hl, &hld));
+    PackList pl(m->st, (unsigned)std::min<size_t>(64, ((size_t)B * std::max(G, D) + 255) / 256), (unsigned)Sn, B);
+    SMX_CHECK(pl.add(c.zd ? c.zd + (s0 * Cn + b0) * D : nullptr, D, zst, (size_t)Dp, D, Cn * D, (size_t)B * Dp));
+    if (c.xp || c.st) {
+      GemmArgs g;
+      g.A = hl; g.lda = hld; g.B = P_(m, m->t_outW[0]); g.ldb = m->tensors[m->t_outW[0]].ld;
+      g.C = Pst; g.ldc = (int)ldp; g.M = (int)rows; g.N = (int)ldp; g.K = hld; g.bias = P_(m, m->t_outb[0]); g.split_k = 1;
+      SMX_CHECK(launch_gemm(m->st, g));
+      for (size_t q = 0; q < k && c.xp; ++q)
+        SMX_CHECK(pl.add(c.xp + ((s0 * k + q) * Cn + b0) * G, G, Pst + q * (size_t)m->Gp, ldp, G, k * Cn * G, (size_t)B * ldp));
+      if (c.st) SMX_CHECK(stat_of(m, c, ps, Pst, (long)ldp, Sn, s0, b0));
+    }
+    float* ycur = yst;
+    for (int j = 0; j < m->n_heads; ++j) {
+      if (!c.y[j]) continue;
+      const TensorInfo& tw = m->tensors[m->t_labW[j]];
+      GemmArgs g;
+      g.A = hl; g.lda = hld; g.B = P_(m, m->t_labW[j]); g.ldb = tw.ld;
+      g.C = ycur; g.ldc = tw.ld; g.M = (int)rows; g.N = tw.ld; g.K = hld; g.bias = P_(m, m->t_labb[j]); g.split_k = 1;
+      SMX_CHECK(launch_gemm(m->st, g));
+      const size_t P = (size_t)m->cfg.label_dim[j], Pp = (size_t)m->lab_Pp[j], ld = (size_t)tw.ld, wy = c.wy[j];
+      for (size_t q = 0; q < (size_t)m->lab_ky[j]; ++q)
+        SMX_CHECK(pl.add(c.y[j] + (s0 * Cn + b0) * wy + q * P, wy, ycur + q * Pp, ld, P, Cn * wy, (size_t)B * ld));
+      ycur += R * ld;
+    }
+    SMX_CHECK(pl.flush());
+  }
+  return SMX_OK;
+}
+
+// One batch draw by draw (smx_forward's kernels: bit-identical with it batch by batch).  The encoders run once per batch (eval mode: no
+// noise in them); later draws re-sample the latents and decode.
+static int predict_batch_drawwise(smx_model* m, const PredChunk& c, Pass& ps, size_t b0, bool need_dec) {
+  const int B = ps.B;
+  const size_t S = c.S, Cn = c.Cn, G = (size_t)m->G, D = (size_t)m->D, k = (size_t)m->k;
+  for (size_t s = 0; s < S; ++s) {
+    ps.sample = (int)s;
+    SMX_CHECK(forward_pass(m, ps, false, false, s == 0 ? ((need_dec || S > 1) ? 0 : 3) : 2));
+    PackList pl(m->st, (unsigned)std::min<size_t>(256, ((size_t)B * std::max(G, D) + 255) / 256), 1, B);
+    if (s == 0) SMX_CHECK(add_latent_moments(m, pl, c, b0));
+    SMX_CHECK(pl.add(c.zd ? c.zd + (s * Cn + b0) * D : nullptr, D, m->z, (size_t)m->Dp, D));
+    SMX_CHECK(pl.add(c.ld ? c.ld + s * Cn + b0 : nullptr, 1, m->lsmp, 1, 1));
+    for (size_t q = 0; q < k && c.xp; ++q) SMX_CHECK(pl.add(c.xp + ((s * k + q) * Cn + b0) * G, G, m->P + q * (size_t)m->Gp, k * (size_t)m->Gp, G));
+    if (c.st) SMX_CHECK(stat_of(m, c, ps, m->P, (long)(k * (size_t)m->Gp), 1, s, b0));
+    for (int j = 0; j < m->n_heads; ++j) {
+      if (!c.y[j]) continue;
+      const size_t P = (size_t)m->cfg.label_dim[j], Pp = (size_t)m->lab_Pp[j], ld = (size_t)m->tensors[m->t_labW[j]].ld, wy = c.wy[j];
+      for (size_t q = 0; q < (size_t)m->lab_ky[j]; ++q) SMX_CHECK(pl.add(c.y[j] + (s * Cn + b0) * wy + q * P, wy, m->laby_raw[j] + q * Pp, ld, P));
+    }
+    SMX_CHECK(pl.flush());
+  }
+  return SMX_OK;
+}
+
 }  // namespace smx
 
 extern "C" {
@@ -306,39 +475,33 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
   SMX_REQUIRE(batch > 0 && batch <= m->Bmax, "batch must be in 1..max_batch");
   if (cx) SMX_CHECK(check_csr_rows(*cx, (size_t)n_cells, m->G));
   if (sr && sr->tcsr) SMX_CHECK(check_csr_rows(*sr->tcsr, (size_t)n_cells, m->G));
-  const size_t N = (size_t)n_cells, G = (size_t)m->G, D = (size_t)m->D, k = (size_t)m->k, S = (size_t)n_samples;
-  const int Dp = m->Dp, lat_ld = m->lat_planes * Dp;
+  const size_t N = (size_t)n_cells, G = (size_t)m->G, Gp = (size_t)m->Gp, D = (size_t)m->D, k = (size_t)m->k, S = (size_t)n_samples;
   if (!m->stochastic) z_scale = nullptr;
   if (!m->scvi) l_mean = l_scale = l_samples = nullptr;
-  // ---- staging layout for a chunk of C cells (segments in floats; per-cell widths) ----
-  size_t wy[SMX_MAX_LABELS] = {0, 0, 0, 0};
-  size_t per_cell = 0;
-  if (z_mean) per_cell += D;
-  if (z_scale) per_cell += D;
-  if (l_mean) per_cell += 1;
-  if (l_scale) per_cell += 1;
-  if (z_samples) per_cell += S * D;
-  if (l_samples) per_cell += S;
-  if (x_params) per_cell += S * k * G;
+  PredChunk ch;
+  ch.S = S; ch.sr = sr;
+  for (int j = 0; j < m->n_heads; ++j)
+    if (y_params && y_params[j]) ch.wy[j] = (size_t)m->lab_ky[j] * (size_t)m->cfg.label_dim[j];
   // the requested statistic of the gene output, per cell: S G (mean / variance per draw), G (mean over the draws), S (log_prob)
   const size_t w_stat = !sr ? 0 : sr->stat == 2 ? G : sr->stat == 3 ? S : S * G;
-  per_cell += w_stat;
-  for (int j = 0; j < m->n_heads; ++j)
-    if (y_params && y_params[j]) { wy[j] = (size_t)m->lab_ky[j] * (size_t)m->cfg.label_dim[j]; per_cell += S * wy[j]; }
-  SMX_REQUIRE(per_cell > 0, "no output requested");
-  // the INPUT rows of a chunk travel as ONE contiguous copy too (raw [C][G] -> a device re-pitch to [C][Gp]; library prior; the rows'
-  // likelihood constants from one launch): a host-to-device copy per minibatch from the caller's pageable array is staged
-  // synchronously by the runtime -- ~60 us per batch, at batch 8 (Posterior's default) most of the call
-  // CSR rows: no raw [C][G] segment; the chunk's indptr slice, cols and vals take a region of their own, sized by non-zeros (below)
-  const size_t Gp = (size_t)m->Gp;
-  per_cell += (cx ? 0 : G) + Gp + 3;
+  // ---- the staging of a chunk of C cells, segment by segment in this order: (where, floats per cell, asked for).  Input rows: see
+  // load_chunk; CSR rows have no raw [C][G] segment, their tile comes right after the CSR region (16-byte aligned for launch_csr_rows'
+  // float4 stores) ----
+  struct Seg { float** at; size_t w; bool on; };
+  static_assert(SMX_MAX_LABELS == 4, "one segment per label head");
+  const Seg plan[] = {
+      {&ch.in_x, Gp, cx != nullptr},
+      {&ch.zm, D, z_mean != nullptr}, {&ch.zs, D, z_scale != nullptr}, {&ch.lm, 1, l_mean != nullptr}, {&ch.ls, 1, l_scale != nullptr},
+      {&ch.zd, S * D, z_samples != nullptr}, {&ch.ld, S, l_samples != nullptr}, {&ch.xp, S * k * G, x_params != nullptr},
+      {&ch.st, w_stat, w_stat > 0},
+      {&ch.in_raw, G, !cx}, {&ch.in_x, Gp, !cx}, {&ch.in_lib, 2, true}, {&ch.in_lgx1, 1, true},
+      {&ch.y[0], S * ch.wy[0], ch.wy[0] > 0}, {&ch.y[1], S * ch.wy[1], ch.wy[1] > 0}, {&ch.y[2], S * ch.wy[2], ch.wy[2] > 0},
+      {&ch.y[3], S * ch.wy[3], ch.wy[3] > 0}};
+  size_t per_cell = 0;
+  for (const Seg& g : plan) per_cell += g.on ? g.w : 0;
+  SMX_REQUIRE(per_cell > (cx ? 0 : G) + Gp + 3, "no output requested");
   const bool t_dev = sr && sr->stat == 3 && (sr->target || sr->tcsr);   // targets other than the input rows
-  if (t_dev && (size_t)batch * m->Gp > m->pred_target_floats) {   // device copy of a batch of target rows
-    if (m->pred_target) hipFree(m->pred_target);
-    m->pred_target = nullptr; m->pred_target_floats = 0;
-    SMX_CHECK(dmalloc(&m->pred_target, (size_t)m->Bmax * m->Gp));
-    m->pred_target_floats = (size_t)m->Bmax * m->Gp;
-  }
+  if (t_dev) SMX_CHECK(dgrow(m, &m->pred_target, &m->pred_target_floats, (size_t)batch * Gp, (size_t)m->Bmax * Gp));   // a batch of target rows
   // 128 MB of staging (knob predict_stage_floats: tests force several chunks on small problems)
   const size_t cap_floats = (size_t)std::max(1.0, tuning("predict_stage_floats", (double)((size_t)32 << 20)));
   size_t C = std::max<size_t>((size_t)batch, cap_floats / per_cell / (size_t)batch * (size_t)batch);   // whole batches per chunk
@@ -347,52 +510,11 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
   // (check_csr_rows), so one batch always fits and a dense region only makes the chunks shorter
   const size_t nnz_cap = cx ? std::max((size_t)batch * G, std::min(C * G, cap_floats / 2)) : 0;
   const size_t csr_floats = cx ? csr_stage_bytes(C, nnz_cap) / 4 : 0;   // (a multiple of 16 bytes)
-  const size_t stage_need = csr_floats + C * per_cell;
-  if (stage_need > m->pred_floats) {
-    if (m->pred_stage) hipFree(m->pred_stage);
-    m->pred_stage = nullptr; m->pred_floats = 0;
-    SMX_CHECK(dmalloc(&m->pred_stage, stage_need));
-    m->pred_floats = stage_need;
-  }
-  char* csr_st = reinterpret_cast<char*>(m->pred_stage);
-  float* st = m->pred_stage + csr_floats;
-  float* in_x = nullptr;
-  if (cx) { in_x = st; st += C * Gp; }   // (CSR: the tile right after the CSR region, 16-byte aligned for launch_csr_rows' float4 stores)
-  float *s_zm = nullptr, *s_zs = nullptr, *s_lm = nullptr, *s_ls = nullptr, *s_zd = nullptr, *s_ld = nullptr, *s_xp = nullptr, *s_y[SMX_MAX_LABELS] = {nullptr, nullptr, nullptr, nullptr};
-  if (z_mean) { s_zm = st; st += C * D; }
-  if (z_scale) { s_zs = st; st += C * D; }
-  if (l_mean) { s_lm = st; st += C; }
-  if (l_scale) { s_ls = st; st += C; }
-  if (z_samples) { s_zd = st; st += S * C * D; }
-  if (l_samples) { s_ld = st; st += S * C; }
-  if (x_params) { s_xp = st; st += S * k * C * G; }
-  float* s_st = nullptr;
-  if (w_stat) { s_st = st; st += C * w_stat; }
-  float* in_raw = nullptr;
-  if (!cx) { in_raw = st; st += C * G; }
-  if (!cx) { in_x = st; st += C * Gp; }
-  float* in_lib = st; st += C * 2;
-  float* in_lgx1 = st; st += C;
-  for (int j = 0; j < m->n_heads; ++j)
-    if (wy[j]) { s_y[j] = st; st += S * C * wy[j]; }
-  // the statistic of the planes of Sn draws (stacked rows) of the batch at b0 into the chunk's staging
-  auto stat_of = [&](const float* P, long ldp_, int B, int Sn, size_t s0, size_t Cn, size_t b0, const Pass& ps) -> int {
-    StatArgs a;
-    a.P = P; a.ldp = ldp_; a.plane_stride = m->Gp; a.B = B; a.Sn = Sn; a.G = m->G; a.lk = m->cfg.likelihood; a.direct = m->scvi ? 1 : 0;
-    a.count_only = sr->count_only; a.stat = sr->stat; a.inv_S = 1.f / (float)S; a.accumulate = s0 > 0 ? 1 : 0;
-    a.T = nullptr; a.ldt = 0; a.trows = nullptr; a.t_u16 = 0;
-    if (sr->stat == 2) { a.dst = s_st + b0 * G; a.dst_draw = 0; }
-    else if (sr->stat == 3) {
-      a.dst = s_st + s0 * Cn + b0; a.dst_draw = (long)Cn;
-      if (sr->target || sr->tcsr) { a.T = m->pred_target; a.ldt = m->Gp; }
-      else { a.T = ps.Xsrc; a.ldt = m->Gp; a.trows = ps.xrows; a.t_u16 = ps.x_u16; }   // the input rows themselves
-    } else { a.dst = s_st + (s0 * Cn + b0) * G; a.dst_draw = (long)(Cn * G); }
-    return launch_plane_stat(m->st, a);
-  };
-  auto out = [&](float* dst, const float* src, size_t count) -> int {   // one contiguous device -> host copy
-    SMX_HIP(hipMemcpyAsync(dst, src, count * sizeof(float), hipMemcpyDeviceToHost, m->st));
-    return SMX_OK;
-  };
+  SMX_CHECK(dgrow(m, &m->pred_stage, &m->pred_floats, csr_floats + C * per_cell));
+  ch.csr = reinterpret_cast<char*>(m->pred_stage);
+  float* at = m->pred_stage + csr_floats;
+  for (const Seg& g : plan)
+    if (g.on) { *g.at = at; at += C * g.w; }
   // the stacked form: with several draws, and for a statistic request at any draw count (smx_predict itself keeps the draw-by-draw
   // kernels at one draw: bit-identical with smx_forward batch by batch)
   const bool stack = (S > 1 || sr != nullptr) && stacked_scoring_ok(m) && !m->scvi;
@@ -412,188 +534,44 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
   }
   SMX_REQUIRE(!m->scvi || host_library, "scvi needs host_library with host_x");
   bool any_y = false;
-  for (int j = 0; j < m->n_heads; ++j) any_y = any_y || s_y[j] != nullptr;
-  const bool need_dec = s_xp || s_st || any_y;   // (latents only: the decoder and the heads are not run at all)
-  for (size_t c0 = 0, Cn = 0; c0 < N; c0 += Cn) {
-    Cn = std::min(C, N - c0);   // cells of this chunk
-    if (cx) {   // whole batches while the non-zeros fit (the first batch always does)
-      size_t end = c0;
-      while (end < c0 + Cn) {
-        const size_t nxt = std::min(end + (size_t)batch, c0 + Cn);
-        if (end > c0 && (size_t)(cx->indptr[nxt] - cx->indptr[c0]) > nnz_cap) break;
-        end = nxt;
-      }
-      Cn = end - c0;
-      SMX_REQUIRE((size_t)(cx->indptr[c0 + Cn] - cx->indptr[c0]) <= nnz_cap, "CSR chunk exceeds its staging");
-      // the chunk's rows as the [Cn][Gp] tile and their likelihood constants: one launch, as the dense path's re-pitch + row_stats
-      SMX_CHECK(stage_csr_rows(m, *cx, c0, Cn, csr_st, in_x, in_lgx1));
-      if (host_library) SMX_HIP(hipMemcpyAsync(in_lib, host_library + c0 * 2, Cn * 2 * sizeof(float), hipMemcpyHostToDevice, m->st));
-    } else {
-      SMX_HIP(hipMemcpyAsync(in_raw, host_x + c0 * G, Cn * G * sizeof(float), hipMemcpyHostToDevice, m->st));
-      if (Gp != G) SMX_HIP(hipMemsetAsync(in_x, 0, Cn * Gp * sizeof(float), m->st));
-      PackJobs J; J.n = 1;
-      PackJob& q = J.j[0];
-      q.dst = in_x; q.dpitch = (long)Gp; q.src = in_raw; q.spitch = (long)G; q.width = (int)G; q.height = (int)Cn; q.n_rep = 1; q.dst_rep = 0; q.src_rep = 0;
-      hipLaunchKernelGGL(pack_kernel, dim3((unsigned)std::min<size_t>(1024, (Cn * G + 255) / 256), 1, 1), dim3(256), 0, m->st, J);
-      SMX_HIP(hipGetLastError());
-      SMX_CHECK(launch_row_stats(m->st, in_x, 0, (long)Gp, (long)Cn, m->G, in_lgx1, nullptr));
-      if (host_library) SMX_HIP(hipMemcpyAsync(in_lib, host_library + c0 * 2, Cn * 2 * sizeof(float), hipMemcpyHostToDevice, m->st));
-    }
+  for (int j = 0; j < m->n_heads; ++j) any_y = any_y || ch.y[j] != nullptr;
+  const bool need_dec = ch.xp || ch.st || any_y;   // (latents only: the decoder and the heads are not run at all)
+  auto out = [&](float* dst, const float* src, size_t count) -> int {   // one contiguous device -> host copy
+    SMX_HIP(hipMemcpyAsync(dst, src, count * sizeof(float), hipMemcpyDeviceToHost, m->st));
+    return SMX_OK;
+  };
+  for (size_t c0 = 0; c0 < N; c0 += ch.Cn) {
+    ch.Cn = std::min(C, N - c0);   // cells of this chunk (CSR rows: load_chunk may take fewer)
+    SMX_CHECK(load_chunk(m, ch, host_x, cx, host_library, c0, (size_t)batch, nnz_cap));
+    const size_t Cn = ch.Cn;
     for (size_t b0 = 0; b0 < Cn; b0 += step) {
       const int B = (int)std::min<size_t>(step, Cn - b0);
       const size_t g0 = c0 + b0;
-      Pass ps;   // (what setup_pass leaves for a host batch, on the chunk's resident copy)
-      ps.B = B; ps.training = 0; ps.sample = 0; ps.global_batch = B;
-      ps.rows = nullptr; ps.Xsrc = in_x + b0 * Gp; ps.lib = in_lib + b0 * 2; ps.lgx1 = in_lgx1 + b0; ps.cell_base = 0;
+      Pass ps = host_rows_pass(B, ch.in_x + b0 * Gp, ch.in_lib + b0 * 2, ch.in_lgx1 + b0);   // (on the chunk's resident copy)
       if (sr && sr->stat == 3 && sr->tcsr) SMX_CHECK(csr_host_rows(m, *sr->tcsr, g0, (size_t)B, m->pred_target, nullptr));
       else if (sr && sr->stat == 3 && sr->target)
-        SMX_HIP(hipMemcpy2DAsync(m->pred_target, (size_t)m->Gp * sizeof(float), sr->target + g0 * G, G * sizeof(float), G * sizeof(float), (size_t)B,
+        SMX_HIP(hipMemcpy2DAsync(m->pred_target, Gp * sizeof(float), sr->target + g0 * G, G * sizeof(float), G * sizeof(float), (size_t)B,
                                  hipMemcpyHostToDevice, m->st));
-      if (stack) {
-        // ---- several draws: the encoder once, then the draws of this batch as rows of one decoder pass (as the scoring
-        // paths, smx_score.hip) -- at batch 8 x 10 draws (Posterior's defaults, posterior.py:114-115) the draw-by-draw form
-        // is 50 launches per 8 cells ----
-        ps.sample = 0;
-        SMX_CHECK(forward_pass(m, ps, false, false, 3));   // encoder + latent moments only
-        int Hmax = 0, lab_floats = 0;
-        for (const MlpLayer& L : m->dec) Hmax = std::max(Hmax, L.out_p);
-        for (int j = 0; j < m->n_heads; ++j) lab_floats += s_y[j] ? m->tensors[m->t_labW[j]].ld : 0;
-        const size_t ldp = k * (size_t)m->Gp;
-        const int Sc = (int)std::min<size_t>(S, std::max<size_t>(1, (size_t)4096 / (size_t)B));   // draws per pass
-        const size_t R = (size_t)Sc * B;
-        const size_t need = R * ((size_t)Dp + 1 + 2 * (size_t)Hmax + ldp + (size_t)lab_floats);
-        if (need > m->score_floats) {
-          if (m->score_buf) { SMX_HIP(hipStreamSynchronize(m->st)); hipFree(m->score_buf); }
-          m->score_buf = nullptr; m->score_floats = 0;
-          SMX_CHECK(dmalloc(&m->score_buf, need));
-          m->score_floats = need;
-        }
-        float* zst = m->score_buf;
-        float* lwst = zst + R * Dp;
-        float* hb[2] = {lwst + R, lwst + R + R * Hmax};
-        float* Pst = hb[1] + R * Hmax;
-        float* yst = Pst + R * ldp;
-        {
-          PackJobs J; J.n = 0;
-          auto add1 = [&](float* dst, size_t dpitch, const float* src, size_t spitch, size_t width) {
-            if (!dst) return;
-            PackJob& q = J.j[J.n++];
-            q.dst = dst; q.dpitch = (long)dpitch; q.src = src; q.spitch = (long)spitch; q.width = (int)width; q.height = B; q.n_rep = 1; q.dst_rep = 0; q.src_rep = 0;
-          };
-          add1(s_zm ? s_zm + b0 * D : nullptr, D, m->mixpost ? m->zmean : m->latbuf, (size_t)(m->mixpost ? Dp : lat_ld), D);
-          add1(s_zs ? s_zs + b0 * D : nullptr, D, m->sig, (size_t)Dp, D);
-          if (J.n) { hipLaunchKernelGGL(pack_kernel, dim3(8, (unsigned)J.n, 1), dim3(256), 0, m->st, J); SMX_HIP(hipGetLastError()); }
-        }
-        for (size_t s0 = 0; s0 < S; s0 += (size_t)Sc) {
-          const int Sn = (int)std::min<size_t>((size_t)Sc, S - s0);
-          const long rows = (long)Sn * B;
-          ScoreDrawArgs d;
-          d.lat = m->latbuf; d.ld = 2 * Dp; d.B = B; d.D = m->D; d.Dp = Dp; d.S = Sn; d.s0 = (int)s0;
-          d.nk = make_key(m, ST_EPS_Z, 0, false); d.rows = step > (size_t)batch ? m->pred_ids : ps.rows; d.cell_base = ps.cell_base; d.z = zst; d.lw = lwst;
-          SMX_CHECK(launch_score_draws(m->st, d));
-          const float* hl = nullptr; int hld = 0;
-          if (need_dec) SMX_CHECK(stacked_decoder(m, zst, rows, hb, 0, nullptr, &hl, &hld));
-          PackJobs J; J.n = 0;
-          int pack_err = SMX_OK;
-          auto flush = [&]() {
-            if (!J.n || pack_err != SMX_OK) return;
-            const unsigned gx = (unsigned)std::min<size_t>(64, ((size_t)B * std::max(G, D) + 255) / 256);
-            hipLaunchKernelGGL(pack_kernel, dim3(gx, (unsigned)J.n, (unsigned)Sn), dim3(256), 0, m->st, J);
-            if (hipGetLastError() != hipSuccess) { set_error("pack_kernel launch failed"); pack_err = SMX_ERR_HIP; }
-            J.n = 0;
-          };
-          auto addr = [&](float* dst, size_t dpitch, size_t dst_rep, const float* src, size_t spitch, size_t src_rep, size_t width) {
-            if (!dst) return;
-            if (J.n == SMX_PACK_MAX) flush();
-            PackJob& q = J.j[J.n++];
-            q.dst = dst; q.dpitch = (long)dpitch; q.src = src; q.spitch = (long)spitch; q.width = (int)width; q.height = B;
-            q.n_rep = Sn; q.dst_rep = (long)dst_rep; q.src_rep = (long)src_rep;
-          };
-          addr(s_zd ? s_zd + (s0 * Cn + b0) * D : nullptr, D, Cn * D, zst, (size_t)Dp, (size_t)B * Dp, D);
-          if (s_xp || s_st) {
-            GemmArgs g;
-            g.A = hl; g.lda = hld; g.B = P_(m, m->t_outW[0]); g.ldb = m->tensors[m->t_outW[0]].ld;
-            g.C = Pst; g.ldc = (int)ldp; g.M = (int)rows; g.N = (int)ldp; g.K = hld; g.bias = P_(m, m->t_outb[0]); g.split_k = 1;
-            SMX_CHECK(launch_gemm(m->st, g));
-            for (size_t c = 0; c < k && s_xp; ++c)
-              addr(s_xp + ((s0 * k + c) * Cn + b0) * G, G, k * Cn * G, Pst + c * (size_t)m->Gp, ldp, (size_t)B * ldp, G);
-            if (s_st) SMX_CHECK(stat_of(Pst, (long)ldp, B, Sn, s0, Cn, b0, ps));
-          }
-          float* ycur = yst;
-          for (int j = 0; j < m->n_heads; ++j) {
-            if (!s_y[j]) continue;
-            const TensorInfo& tw = m->tensors[m->t_labW[j]];
-            GemmArgs g;
-            g.A = hl; g.lda = hld; g.B = P_(m, m->t_labW[j]); g.ldb = tw.ld;
-            g.C = ycur; g.ldc = tw.ld; g.M = (int)rows; g.N = tw.ld; g.K = hld; g.bias = P_(m, m->t_labb[j]); g.split_k = 1;
-            SMX_CHECK(launch_gemm(m->st, g));
-            const size_t P = (size_t)m->cfg.label_dim[j], Pp = (size_t)m->lab_Pp[j], ld = (size_t)tw.ld;
-            for (size_t c = 0; c < (size_t)m->lab_ky[j]; ++c)
-              addr(s_y[j] + (s0 * Cn + b0) * wy[j] + c * P, wy[j], Cn * wy[j], ycur + c * Pp, ld, (size_t)B * ld, P);
-            ycur += R * ld;
-          }
-          flush();
-          SMX_CHECK(pack_err);
-        }
-        continue;
-      }
-      for (size_t s = 0; s < S; ++s) {
-        ps.sample = (int)s;
-        // the encoders run once per batch (eval mode: no noise in them); later draws re-sample the latents and decode
-        SMX_CHECK(forward_pass(m, ps, false, false, s == 0 ? ((need_dec || S > 1) ? 0 : 3) : 2));
-        PackJobs J; J.n = 0;
-        int pack_err = SMX_OK;
-        auto flush = [&]() {
-          if (!J.n || pack_err != SMX_OK) return;
-          const unsigned gx = (unsigned)std::min<size_t>(256, ((size_t)B * std::max(G, D) + 255) / 256);
-          hipLaunchKernelGGL(pack_kernel, dim3(gx, (unsigned)J.n), dim3(256), 0, m->st, J);
-          if (hipGetLastError() != hipSuccess) { set_error("pack_kernel launch failed"); pack_err = SMX_ERR_HIP; }
-          J.n = 0;
-        };
-        auto add = [&](float* dst, size_t dpitch, const float* src, size_t spitch, size_t width) {
-          if (!dst) return;
-          if (J.n == SMX_PACK_MAX) flush();
-          PackJob& q = J.j[J.n++];
-          q.dst = dst; q.dpitch = (long)dpitch; q.src = src; q.spitch = (long)spitch; q.width = (int)width; q.height = B;
-          q.n_rep = 1; q.dst_rep = 0; q.src_rep = 0;
-        };
-        if (s == 0) {
-          add(s_zm ? s_zm + b0 * D : nullptr, D, m->mixpost ? m->zmean : m->latbuf, (size_t)(m->mixpost ? Dp : lat_ld), D);
-          add(s_zs ? s_zs + b0 * D : nullptr, D, m->sig, (size_t)Dp, D);
-          add(s_lm ? s_lm + b0 : nullptr, 1, m->latlbuf, 32, 1);
-          add(s_ls ? s_ls + b0 : nullptr, 1, m->lsig, 1, 1);
-        }
-        add(s_zd ? s_zd + (s * Cn + b0) * D : nullptr, D, m->z, (size_t)Dp, D);
-        add(s_ld ? s_ld + s * Cn + b0 : nullptr, 1, m->lsmp, 1, 1);
-        if (s_xp)
-          for (size_t c = 0; c < k; ++c) add(s_xp + ((s * k + c) * Cn + b0) * G, G, m->P + c * (size_t)m->Gp, k * (size_t)m->Gp, G);
-        if (s_st) SMX_CHECK(stat_of(m->P, (long)(k * (size_t)m->Gp), B, 1, s, Cn, b0, ps));
-        for (int j = 0; j < m->n_heads; ++j) {
-          if (!s_y[j]) continue;
-          const size_t P = (size_t)m->cfg.label_dim[j], Pp = (size_t)m->lab_Pp[j], ld = (size_t)m->tensors[m->t_labW[j]].ld;
-          for (size_t c = 0; c < (size_t)m->lab_ky[j]; ++c) add(s_y[j] + (s * Cn + b0) * wy[j] + c * P, wy[j], m->laby_raw[j] + c * Pp, ld, P);
-        }
-        flush();
-        SMX_CHECK(pack_err);
-      }
+      if (stack) SMX_CHECK(predict_batch_stacked(m, ch, ps, b0, step > (size_t)batch ? m->pred_ids : nullptr, need_dec));
+      else SMX_CHECK(predict_batch_drawwise(m, ch, ps, b0, need_dec));
     }
     // ---- the chunk leaves the device: every segment's rows are contiguous here and in the caller's arrays ----
-    if (s_zm) SMX_CHECK(out(z_mean + c0 * D, s_zm, Cn * D));
-    if (s_zs) SMX_CHECK(out(z_scale + c0 * D, s_zs, Cn * D));
-    if (s_lm) SMX_CHECK(out(l_mean + c0, s_lm, Cn));
-    if (s_ls) SMX_CHECK(out(l_scale + c0, s_ls, Cn));
-    if (s_st && sr->stat == 2) SMX_CHECK(out(sr->out + c0 * G, s_st, Cn * G));
-    for (size_t s = 0; s < S && s_st && sr->stat != 2; ++s) {
-      if (sr->stat == 3) SMX_CHECK(out(sr->out + s * N + c0, s_st + s * Cn, Cn));
-      else SMX_CHECK(out(sr->out + (s * N + c0) * G, s_st + s * Cn * G, Cn * G));
+    if (ch.zm) SMX_CHECK(out(z_mean + c0 * D, ch.zm, Cn * D));
+    if (ch.zs) SMX_CHECK(out(z_scale + c0 * D, ch.zs, Cn * D));
+    if (ch.lm) SMX_CHECK(out(l_mean + c0, ch.lm, Cn));
+    if (ch.ls) SMX_CHECK(out(l_scale + c0, ch.ls, Cn));
+    if (ch.st && sr->stat == 2) SMX_CHECK(out(sr->out + c0 * G, ch.st, Cn * G));
+    for (size_t s = 0; s < S && ch.st && sr->stat != 2; ++s) {
+      if (sr->stat == 3) SMX_CHECK(out(sr->out + s * N + c0, ch.st + s * Cn, Cn));
+      else SMX_CHECK(out(sr->out + (s * N + c0) * G, ch.st + s * Cn * G, Cn * G));
     }
     for (size_t s = 0; s < S; ++s) {
-      if (s_zd) SMX_CHECK(out(z_samples + (s * N + c0) * D, s_zd + s * Cn * D, Cn * D));
-      if (s_ld) SMX_CHECK(out(l_samples + s * N + c0, s_ld + s * Cn, Cn));
-      if (s_xp)
-        for (size_t c = 0; c < k; ++c) SMX_CHECK(out(x_params + ((s * k + c) * N + c0) * G, s_xp + (s * k + c) * Cn * G, Cn * G));
+      if (ch.zd) SMX_CHECK(out(z_samples + (s * N + c0) * D, ch.zd + s * Cn * D, Cn * D));
+      if (ch.ld) SMX_CHECK(out(l_samples + s * N + c0, ch.ld + s * Cn, Cn));
+      if (ch.xp)
+        for (size_t c = 0; c < k; ++c) SMX_CHECK(out(x_params + ((s * k + c) * N + c0) * G, ch.xp + (s * k + c) * Cn * G, Cn * G));
       for (int j = 0; j < m->n_heads; ++j)
-        if (s_y[j]) SMX_CHECK(out(y_params[j] + (s * N + c0) * wy[j], s_y[j] + s * Cn * wy[j], Cn * wy[j]));
+        if (ch.y[j]) SMX_CHECK(out(y_params[j] + (s * N + c0) * ch.wy[j], ch.y[j] + s * Cn * ch.wy[j], Cn * ch.wy[j]));
     }
     SMX_HIP(hipStreamSynchronize(m->st));
   }
@@ -642,30 +620,15 @@ int smx_decode(smx_model* m, const float* z, const float* l, int32_t batch, floa
   SMX_REQUIRE(m && z, "null argument");
   SMX_REQUIRE(batch > 0 && batch <= m->Bmax, "batch must be in 1..max_batch");
   SMX_REQUIRE(!m->scvi || l, "scvi decode needs the library latent");
-  Pass ps;
-  ps.B = batch; ps.training = 0; ps.sample = 0; ps.global_batch = batch; ps.rows = nullptr; ps.Xsrc = m->hostX;
-  ps.lib = m->hostLib; ps.lgx1 = m->hostLgx1; ps.cell_base = 0;
+  const Pass ps = host_rows_pass(batch, m->hostX, m->hostLib, m->hostLgx1);
   SMX_HIP(hipMemsetAsync(m->z, 0, (size_t)batch * m->Dp * sizeof(float), m->st));
   SMX_HIP(hipMemcpy2DAsync(m->z, (size_t)m->Dp * sizeof(float), z, (size_t)m->D * sizeof(float), (size_t)m->D * sizeof(float),
                            (size_t)batch, hipMemcpyHostToDevice, m->st));
   if (m->scvi) SMX_HIP(hipMemcpyAsync(m->lsmp, l, (size_t)batch * sizeof(float), hipMemcpyHostToDevice, m->st));
   SMX_CHECK(forward_pass(m, ps, false, false, 1));
   SMX_HIP(hipStreamSynchronize(m->st));
-  const int B = batch;
-  SMX_CHECK(fetch_planes(m, B, x_params));
-  if (y_params) {
-    std::vector<float> tmp;
-    for (int j = 0; j < m->n_heads; ++j) {
-      if (!y_params[j]) continue;
-      const int P = m->cfg.label_dim[j], Pp = m->lab_Pp[j], ld = m->tensors[m->t_labW[j]].ld;
-      tmp.resize((size_t)B * ld);
-      SMX_HIP(hipMemcpy(tmp.data(), m->laby_raw[j], tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
-      for (int b = 0; b < B; ++b)
-        for (int c = 0; c < m->lab_ky[j]; ++c)
-          memcpy(y_params[j] + ((size_t)b * m->lab_ky[j] + c) * P, &tmp[(size_t)b * ld + (size_t)c * Pp], sizeof(float) * P);
-    }
-  }
-  return SMX_OK;
+  SMX_CHECK(fetch_planes(m, batch, x_params));
+  return fetch_labels(m, batch, y_params, 0);
 }
 
 }  // extern "C"

@@ -65,13 +65,7 @@ static int stacked_scores(smx_model* m, const Pass& ps, int n_samples, const Sco
   const int Sc = (int)std::min<long>(std::min<long>(n_samples, SMX_SCORE_MAX_DRAWS), std::max<long>(1, cap_rows / B));
   const size_t R = (size_t)Sc * B;
   const size_t raw_ld = (size_t)m->k * m->Gp;
-  const size_t need = R * ((size_t)m->Dp + 2 + 4 * (size_t)Hmax + (size_t)n_gt + (m->scvi ? raw_ld : 0));
-  if (need > m->score_floats) {
-    if (m->score_buf) hipFree(m->score_buf);
-    m->score_buf = nullptr; m->score_floats = 0;
-    SMX_CHECK(dmalloc(&m->score_buf, need));
-    m->score_floats = need;
-  }
+  SMX_CHECK(dgrow(m, &m->score_buf, &m->score_floats, R * ((size_t)m->Dp + 2 + 4 * (size_t)Hmax + (size_t)n_gt + (m->scvi ? raw_ld : 0))));
   float* z = m->score_buf;
   float* lw = z + R * m->Dp;
   float* hb[2] = {lw + R, lw + R + R * Hmax};
@@ -89,12 +83,8 @@ static int stacked_scores(smx_model* m, const Pass& ps, int n_samples, const Sco
     for (int j = 0; j < n_jobs; ++j) use_np[(jobs[j].likelihood == SMX_LLK_ZINB || jobs[j].likelihood == SMX_LLK_ZINBD) ? 3 : 2] = true;
     const size_t per_plane = (size_t)n_gt * nslab * 3 * 1024;   // bf16 elements per plane of an image set
     const size_t wneed = (per_plane * ((use_np[2] ? 2 : 0) + (use_np[3] ? 3 : 0)) + 1) / 2;   // ... as floats
-    if (wneed > m->score_wimg_floats) {
-      if (m->score_wimg) hipFree(m->score_wimg);
-      m->score_wimg = nullptr; m->score_wimg_floats = 0; m->wimg_epoch = 0;
-      SMX_CHECK(dmalloc(&m->score_wimg, wneed));
-      m->score_wimg_floats = wneed;
-    }
+    if (wneed > m->score_wimg_floats) m->wimg_epoch = 0;   // (new memory: no images yet)
+    SMX_CHECK(dgrow(m, &m->score_wimg, &m->score_wimg_floats, wneed));
     __bf16* at = reinterpret_cast<__bf16*>(m->score_wimg);
     // (the images stand while the parameters do: a scoring sweep over a dataset splits W once, not once per batch)
     const int key = n_gt * 64 + nslab * 4 + (use_np[2] ? 1 : 0) + (use_np[3] ? 2 : 0);
@@ -192,28 +182,30 @@ static int marginal_llk_stacked(smx_model* m, const Pass& ps, int n_samples, flo
   return stacked_scores(m, ps, n_samples, &q, 1);
 }
 
-// scratch of the scoring entry points, kept across calls (hipMalloc + hipFree per call cost more than the stacked pass)
-static int score_aux(smx_model* m, size_t floats, float** out) {
-  if (floats > m->score_aux_floats) {
-    if (m->score_aux) { SMX_HIP(hipStreamSynchronize(m->st)); hipFree(m->score_aux); }
-    m->score_aux = nullptr; m->score_aux_floats = 0;
-    SMX_CHECK(dmalloc(&m->score_aux, floats));
-    m->score_aux_floats = floats;
-  }
-  *out = m->score_aux;
+// One draw of the draw-by-draw form, on the pass in flight: log p(X | the draw's planes) under `likelihood` (count_loss), folded into the
+// running log-sum-exp of `a` (iw_accum_kernel).  The caller fills a's latent terms, constants and running state; the partial sums' fields here.
+static int iw_draw(smx_model* m, const Pass& ps, int likelihood, const float* X, int x_u16, const int32_t* xrows, IwArgs a) {
+  LossArgs lo;
+  lo.likelihood = likelihood; lo.direct = m->scvi; lo.backward = 0;
+  lo.X = X; lo.x_u16 = x_u16; lo.ldx = m->Gp; lo.rows = xrows;
+  lo.P = m->P; lo.ldp = (long)m->k * m->Gp; lo.plane_stride = m->Gp; lo.dP = m->dP; lo.llk_part = m->llk_part;
+  lo.B = ps.B; lo.G = m->G; lo.Gp = m->Gp; lo.grad_scale = 0.f;
+  SMX_CHECK(launch_count_loss(m->st, lo));
+  a.llk_part = m->llk_part; a.n_chunks = loss_chunks(m->Gp, ps.B); a.D = m->D; a.Dp = m->Dp; a.B = ps.B;
+  hipLaunchKernelGGL(iw_accum_kernel, dim3((ps.B + 3) / 4), dim3(256), 0, m->st, a);
   return SMX_OK;
 }
 
-// the results' landing area on the host, pinned and kept across calls: into a pageable array the runtime's copy waits for the stream, stages, and the
-// hipStreamSynchronize behind it is a second trip through the runtime for nothing
-static int score_landing(smx_model* m, size_t floats, float** out) {
-  if (floats > m->score_pin_floats) {
-    if (m->score_pin) { SMX_HIP(hipStreamSynchronize(m->st)); hipHostFree(m->score_pin); }
-    m->score_pin = nullptr; m->score_pin_floats = 0;
-    SMX_HIP(hipHostMalloc((void**)&m->score_pin, floats * sizeof(float), hipHostMallocDefault));
-    m->score_pin_floats = floats;
-  }
-  *out = m->score_pin;
+// The end of a scoring call: rc is the status of its launches.  The running state `run` (floats of it) lands in the pinned area *h, kept
+// across calls: into a pageable array the runtime's copy waits for the stream, stages, and the hipStreamSynchronize behind it is a second
+// trip through the runtime for nothing.  After a failure the stream is only drained.
+static int land_scores(smx_model* m, int rc, const float* run, size_t floats, const char* what, float** h) {
+  if (rc != SMX_OK) { hipStreamSynchronize(m->st); return rc; }
+  SMX_CHECK(hgrow(m, &m->score_pin, &m->score_pin_floats, floats));
+  *h = m->score_pin;
+  hipError_t e = hipMemcpyAsync(*h, run, floats * sizeof(float), hipMemcpyDeviceToHost, m->st);
+  if (e == hipSuccess) e = hipStreamSynchronize(m->st);
+  if (e != hipSuccess) { set_error(std::string(what) + " readback failed: " + hipGetErrorString(e)); return SMX_ERR_HIP; }
   return SMX_OK;
 }
 
@@ -222,44 +214,30 @@ static int marginal_llk_run(smx_model* m, Pass& ps, int32_t batch, int32_t n_sam
   const bool stacked = stacked_scoring_ok(m);
   // a deterministic latent (DCA) decodes to the same parameters in every draw: one pass is the whole estimate
   if (!m->stochastic) n_samples = 1;
-  float* run = nullptr;   // [3][B]: running max, running sum, sum of log p(x|z)
-  SMX_CHECK(score_aux(m, (size_t)3 * batch, &run));
+  // [3][B]: running max, running sum, sum of log p(x|z) (scratch kept across calls: hipMalloc + hipFree per call cost more than the stacked pass)
+  SMX_CHECK(dgrow(m, &m->score_aux, &m->score_aux_floats, (size_t)3 * batch));
+  float* run = m->score_aux;
   int rc = SMX_OK;
   if (stacked) rc = marginal_llk_stacked(m, ps, n_samples, run);
   for (int s = 0; !stacked && s < n_samples && rc == SMX_OK; ++s) {
     ps.sample = s;
     rc = forward_pass(m, ps, false, false, s == 0 ? 0 : 2);
     if (rc != SMX_OK) break;
-    LossArgs lo;
-    lo.likelihood = m->cfg.likelihood; lo.direct = m->scvi; lo.backward = 0;
-    lo.X = ps.Xsrc; lo.x_u16 = ps.x_u16; lo.ldx = m->Gp; lo.rows = ps.xrows;
-    lo.P = m->P; lo.ldp = (long)m->k * m->Gp; lo.plane_stride = m->Gp; lo.dP = m->dP; lo.llk_part = m->llk_part;
-    lo.B = ps.B; lo.G = m->G; lo.Gp = m->Gp; lo.grad_scale = 0.f;
-    rc = launch_count_loss(m->st, lo);
-    if (rc != SMX_OK) break;
-    IwArgs a;
-    a.llk_part = m->llk_part; a.n_chunks = loss_chunks(m->Gp, ps.B); a.lgx1 = ps.lgx1; a.rows = ps.rows;
-    a.z = m->z; a.sig = m->sig; a.eps = m->eps; a.D = m->D; a.Dp = m->Dp; a.stochastic = m->stochastic;
+    IwArgs a{};
+    a.lgx1 = ps.lgx1; a.rows = ps.rows;
+    a.z = m->z; a.sig = m->sig; a.eps = m->eps; a.stochastic = m->stochastic;
     a.l = m->scvi ? m->lsmp : nullptr; a.lsig = m->lsig; a.leps = m->leps; a.library = ps.lib;
-    a.run_max = run; a.run_sum = run + batch; a.llk_sum = run + 2 * batch; a.B = batch; a.first = (s == 0);
+    a.run_max = run; a.run_sum = run + batch; a.llk_sum = run + 2 * batch; a.first = (s == 0);
     a.klmc = (m->scale || m->mixpost) ? m->kl : nullptr;   // (Monte-Carlo KL models: log p(z) - log q(z|x) of the draw is minus that term)
-    hipLaunchKernelGGL(iw_accum_kernel, dim3((batch + 3) / 4), dim3(256), 0, m->st, a);
+    rc = iw_draw(m, ps, m->cfg.likelihood, ps.Xsrc, ps.x_u16, ps.xrows, a);
   }
-  if (rc == SMX_OK) {
-    float* h = nullptr;
-    SMX_CHECK(score_landing(m, (size_t)3 * batch, &h));
-    hipError_t e = hipMemcpyAsync(h, run, (size_t)3 * batch * sizeof(float), hipMemcpyDeviceToHost, m->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(m->st);
-    if (e != hipSuccess) { set_error(std::string("marginal_llk readback failed: ") + hipGetErrorString(e)); rc = SMX_ERR_HIP; }
-    else
-      for (int b = 0; b < batch; ++b) {
-        mllk[b] = h[b] + logf(h[batch + b]) - logf((float)n_samples);
-        if (llk_mean) llk_mean[b] = h[2 * batch + b] / (float)n_samples;
-      }
-  } else {
-    hipStreamSynchronize(m->st);
+  float* h = nullptr;
+  SMX_CHECK(land_scores(m, rc, run, (size_t)3 * batch, "marginal_llk", &h));
+  for (int b = 0; b < batch; ++b) {
+    mllk[b] = h[b] + logf(h[batch + b]) - logf((float)n_samples);
+    if (llk_mean) llk_mean[b] = h[2 * batch + b] / (float)n_samples;
   }
-  return rc;
+  return SMX_OK;
 }
 
 }  // namespace smx
@@ -284,11 +262,9 @@ int smx_marginal_llk_csr(smx_model* m, const int64_t* indptr, const int32_t* col
   const CsrRows cx{indptr, cols, vals};
   SMX_CHECK(check_csr_rows(cx, (size_t)batch, m->G));
   // (what setup_pass does for dense host rows; the rows' tile and constants from one launch)
-  Pass ps;
-  ps.B = batch; ps.training = 0; ps.sample = 0; ps.global_batch = batch; ps.draw_rows = 0;
   SMX_CHECK(csr_host_rows(m, cx, 0, (size_t)batch, m->hostX, m->hostLgx1));
   if (host_library) SMX_HIP(hipMemcpy(m->hostLib, host_library, (size_t)batch * 2 * sizeof(float), hipMemcpyHostToDevice));
-  ps.rows = nullptr; ps.Xsrc = m->hostX; ps.lib = m->hostLib; ps.lgx1 = m->hostLgx1; ps.cell_base = 0;
+  Pass ps = host_rows_pass(batch, m->hostX, m->hostLib, m->hostLgx1);
   return marginal_llk_run(m, ps, batch, n_samples, mllk, llk_mean);
 }
 
@@ -305,11 +281,8 @@ int smx_score_llk(smx_model* m, const int32_t* row_ids, const float* host_x, con
   const size_t plane = (size_t)batch * m->Gp;
   float *tX = nullptr, *tLg = nullptr, *run = nullptr;   // run: [n_targets][2]{max, sum}[batch]
   int rc = SMX_OK;
-  {
-    float* aux = nullptr;
-    SMX_CHECK(score_aux(m, plane * n_targets + (size_t)batch * n_targets + (size_t)n_targets * 2 * 2 * batch, &aux));
-    tX = aux; tLg = tX + plane * n_targets; run = tLg + (size_t)batch * n_targets;
-  }
+  SMX_CHECK(dgrow(m, &m->score_aux, &m->score_aux_floats, plane * n_targets + (size_t)batch * n_targets + (size_t)n_targets * 2 * 2 * batch));
+  tX = m->score_aux; tLg = tX + plane * n_targets; run = tLg + (size_t)batch * n_targets;
   hipError_t e = hipMemsetAsync(tX, 0, plane * n_targets * sizeof(float), m->st);
   for (int t = 0; t < n_targets && e == hipSuccess && rc == SMX_OK; ++t) {
     const float* src = targets ? targets[t] : nullptr;
@@ -345,43 +318,25 @@ int smx_score_llk(smx_model* m, const int32_t* row_ids, const float* host_x, con
     for (int t = 0; t < n_targets && rc == SMX_OK; ++t) {
       const bool own = !(targets && targets[t]);
       for (int j = 0; j < n_dist && rc == SMX_OK; ++j) {
-        LossArgs lo;
-        // j == 1: the count distribution under the zero-inflation wrapper (first two planes, no gate)
-        lo.likelihood = (j == 0) ? lk : (lk == SMX_LLK_ZINB ? SMX_LLK_NB : SMX_LLK_NBD);
-        lo.direct = m->scvi; lo.backward = 0;
-        lo.X = own ? ps.Xsrc : tX + plane * t; lo.x_u16 = own ? ps.x_u16 : 0; lo.ldx = m->Gp; lo.rows = own ? ps.xrows : nullptr;
-        lo.P = m->P; lo.ldp = (long)m->k * m->Gp; lo.plane_stride = m->Gp; lo.dP = m->dP; lo.llk_part = m->llk_part;
-        lo.B = ps.B; lo.G = m->G; lo.Gp = m->Gp; lo.grad_scale = 0.f;
-        rc = launch_count_loss(m->st, lo);
-        if (rc != SMX_OK) break;
-        IwArgs a;
-        memset(&a, 0, sizeof(a));
-        a.llk_part = m->llk_part; a.n_chunks = loss_chunks(m->Gp, ps.B);
+        IwArgs a{};   // (no latent terms: the draws' likelihoods alone)
         a.lgx1 = own ? ps.lgx1 : tLg + (size_t)batch * t; a.rows = own ? ps.rows : nullptr;
-        a.D = m->D; a.Dp = m->Dp; a.stochastic = 0; a.l = nullptr;
         float* r = run + ((size_t)t * 2 + j) * 2 * batch;
-        a.run_max = r; a.run_sum = r + batch; a.llk_sum = nullptr; a.B = batch; a.first = (s == 0);
-        hipLaunchKernelGGL(iw_accum_kernel, dim3((batch + 3) / 4), dim3(256), 0, m->st, a);
+        a.run_max = r; a.run_sum = r + batch; a.first = (s == 0);
+        // j == 1: the count distribution under the zero-inflation wrapper (first two planes, no gate)
+        rc = iw_draw(m, ps, (j == 0) ? lk : (lk == SMX_LLK_ZINB ? SMX_LLK_NB : SMX_LLK_NBD), own ? ps.Xsrc : tX + plane * t,
+                     own ? ps.x_u16 : 0, own ? ps.xrows : nullptr, a);
       }
     }
   }
-  if (rc == SMX_OK) {
-    float* h = nullptr;
-    SMX_CHECK(score_landing(m, (size_t)n_targets * 2 * 2 * batch, &h));
-    e = hipMemcpyAsync(h, run, (size_t)n_targets * 2 * 2 * batch * sizeof(float), hipMemcpyDeviceToHost, m->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(m->st);
-    if (e != hipSuccess) { set_error(std::string("score_llk readback failed: ") + hipGetErrorString(e)); rc = SMX_ERR_HIP; }
-    else
-      for (int t = 0; t < n_targets; ++t)
-        for (int j = 0; j < 2; ++j) {
-          const float* r = h + ((size_t)t * 2 + (j < n_dist ? j : 0)) * 2 * batch;
-          for (int b = 0; b < batch; ++b)
-            out[((size_t)t * 2 + j) * batch + b] = r[b] + logf(r[batch + b]) - logf((float)n_samples);
-        }
-  } else {
-    hipStreamSynchronize(m->st);
-  }
-  return rc;
+  float* h = nullptr;
+  SMX_CHECK(land_scores(m, rc, run, (size_t)n_targets * 2 * 2 * batch, "score_llk", &h));
+  for (int t = 0; t < n_targets; ++t)
+    for (int j = 0; j < 2; ++j) {
+      const float* r = h + ((size_t)t * 2 + (j < n_dist ? j : 0)) * 2 * batch;
+      for (int b = 0; b < batch; ++b)
+        out[((size_t)t * 2 + j) * batch + b] = r[b] + logf(r[batch + b]) - logf((float)n_samples);
+    }
+  return SMX_OK;
 }
 
 }  // extern "C"

@@ -1762,7 +1762,8 @@ int setup_pass(smx_model* m, Pass& ps, const int32_t* row_ids, const float* host
                              (size_t)m->G * sizeof(float), (size_t)batch, hipMemcpyHostToDevice, m->st));
     SMX_CHECK(launch_row_stats(m->st, m->hostX, 0, m->Gp, batch, m->G, m->hostLgx1, nullptr));
     if (host_library) SMX_HIP(hipMemcpy(m->hostLib, host_library, (size_t)batch * 2 * sizeof(float), hipMemcpyHostToDevice));
-    ps.rows = nullptr; ps.Xsrc = m->hostX; ps.lib = m->hostLib; ps.lgx1 = m->hostLgx1; ps.cell_base = 0;
+    ps = host_rows_pass(batch, m->hostX, m->hostLib, m->hostLgx1);
+    ps.training = training; ps.sample = sample; ps.draw_rows = draw_rows;
   }
   return SMX_OK;
 }

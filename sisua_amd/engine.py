@@ -48,6 +48,16 @@ def _csr_ptrs(t):
   return (t[0].ctypes.data_as(C.POINTER(C.c_int64)), t[1].ctypes.data_as(C.POINTER(C.c_int32)), _fp(t[2]))
 
 
+def _fps(arrays):
+  """A C array of float pointers to `arrays` (label heads), None without any; the caller keeps `arrays` alive through the call."""
+  return (C.POINTER(C.c_float) * max(1, len(arrays)))(*[_fp(a) for a in arrays]) if arrays else None
+
+
+def _check_u16(a):
+  if a.size and (a.min() < 0 or a.max() > 65535 or not np.array_equal(a, np.floor(a))):
+    raise ValueError("storage='u16' needs integer counts in [0, 65535]")
+
+
 def _sparse(x) -> bool:
   from sisua_amd.data import is_sparse
   return is_sparse(x)
@@ -200,27 +210,30 @@ class Engine:
       return self._upload_csr(X, labels, library, label_mask, cell_id_base, dense_store=storage)
     if storage == "u16":
       Xf = np.asarray(X)
-      if Xf.size and (Xf.min() < 0 or Xf.max() > 65535 or not np.array_equal(Xf, np.floor(Xf))):
-        raise ValueError("storage='u16' needs integer counts in [0, 65535]")
+      _check_u16(Xf)
       X = np.ascontiguousarray(Xf, dtype=np.uint16)
     else:
       X = _f32(X)
     if X.ndim != 2 or X.shape[1] != self.cfg.n_genes:
       raise ValueError(f"X must be [n_cells, {self.cfg.n_genes}]")
     n = X.shape[0]
+    keep, side = self._upload_side(n, labels, library, label_mask)
+    if storage == "u16":
+      check(self.lib.smx_dataset_upload_u16(self._h, X.ctypes.data_as(C.POINTER(C.c_uint16)), n, *side, int(cell_id_base)))
+    else:
+      check(self.lib.smx_dataset_upload(self._h, _fp(X), n, *side, int(cell_id_base)))
+    self.n_cells = n
+
+  def _upload_side(self, n, labels, library, label_mask):
+    """The per-cell side arrays of an upload of n cells: (the arrays, their pointers (labels, library, label mask)); the caller keeps
+    the arrays alive through the call."""
     labs = [_f32(y, (n, P)) for y, (P, _) in zip(labels, self.cfg.targets)]
     if len(labs) != len(self.cfg.targets):
       raise ValueError("one label matrix per label head is required")
-    lab_ptrs = (C.POINTER(C.c_float) * max(1, len(labs)))(*[_fp(y) for y in labs]) if labs else None
     lib_arr = None if library is None else _f32(library, (n, 2))
     mask_arr = None if label_mask is None else np.ascontiguousarray(label_mask, dtype=np.uint8).reshape(n)
     mask_ptr = None if mask_arr is None else mask_arr.ctypes.data_as(C.POINTER(C.c_uint8))
-    if storage == "u16":
-      check(self.lib.smx_dataset_upload_u16(self._h, X.ctypes.data_as(C.POINTER(C.c_uint16)), n, lab_ptrs, _fp(lib_arr),
-                                            mask_ptr, int(cell_id_base)))
-    else:
-      check(self.lib.smx_dataset_upload(self._h, _fp(X), n, lab_ptrs, _fp(lib_arr), mask_ptr, int(cell_id_base)))
-    self.n_cells = n
+    return (labs, lib_arr, mask_arr), (_fps(labs), _fp(lib_arr), mask_ptr)
 
   def _upload_csr(self, X, labels, library, label_mask, cell_id_base, dense_store=None):
     G = self.cfg.n_genes
@@ -244,21 +257,14 @@ class Engine:
     n = indptr.size - 1
     if n < 1 or indptr[0] != 0 or indptr[-1] != indices.size or indices.size != data.size:
       raise ValueError("inconsistent CSR arrays")
-    labs = [_f32(y, (n, P)) for y, (P, _) in zip(labels, self.cfg.targets)]
-    if len(labs) != len(self.cfg.targets):
-      raise ValueError("one label matrix per label head is required")
-    lab_ptrs = (C.POINTER(C.c_float) * max(1, len(labs)))(*[_fp(y) for y in labs]) if labs else None
-    lib_arr = None if library is None else _f32(library, (n, 2))
-    mask_arr = None if label_mask is None else np.ascontiguousarray(label_mask, dtype=np.uint8).reshape(n)
-    mask_ptr = None if mask_arr is None else mask_arr.ctypes.data_as(C.POINTER(C.c_uint8))
+    keep, side = self._upload_side(n, labels, library, label_mask)
     if dense_store is not None:
-      if dense_store == "u16" and data.size and (data.min() < 0 or data.max() > 65535 or not np.array_equal(data, np.floor(data))):
-        raise ValueError("storage='u16' needs integer counts in [0, 65535]")
-      check(self.lib.smx_dataset_upload_csr_dense(self._h, *_csr_ptrs((indptr, indices, data)), n, lab_ptrs, _fp(lib_arr), mask_ptr,
-                                                  int(cell_id_base), 1 if dense_store == "u16" else 0))
+      if dense_store == "u16":
+        _check_u16(data)
+      check(self.lib.smx_dataset_upload_csr_dense(self._h, *_csr_ptrs((indptr, indices, data)), n, *side, int(cell_id_base),
+                                                  1 if dense_store == "u16" else 0))
     else:
-      check(self.lib.smx_dataset_upload_csr(self._h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), indices.ctypes.data_as(C.POINTER(C.c_int32)),
-                                            _fp(data), n, lab_ptrs, _fp(lib_arr), mask_ptr, int(cell_id_base)))
+      check(self.lib.smx_dataset_upload_csr(self._h, *_csr_ptrs((indptr, indices, data)), n, *side, int(cell_id_base)))
     self.n_cells = n
 
   # ---- steps -----------------------------------------------------------------------
@@ -325,58 +331,46 @@ class Engine:
     self._step_check(self.lib.smx_eval_step(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32)), ids.size, C.byref(m)))
     return m.as_dict()
 
+  def _cells(self, row_ids, x, library):
+    """The cells of a call: resident row ids, or host rows x [B, G] with their library prior [B, 2] (optional): (B, the arrays, their
+    pointers (row ids, rows, library)); the caller keeps the arrays alive through the call."""
+    if row_ids is not None:
+      ids = self._ids(row_ids)
+      return ids.size, (ids,), (ids.ctypes.data_as(C.POINTER(C.c_int32)), None, None)
+    xa = _f32(x)
+    la = None if library is None else _f32(library, (xa.shape[0], 2))
+    return xa.shape[0], (xa, la), (None, _fp(xa), _fp(la))
+
+  def _outputs(self, B: int, S: Optional[int] = None, want_x_params: bool = True):
+    """The result arrays of a forward pass over B cells -- S: with a leading draw axis on z_sample / l_sample / x_params / y_params --
+    and their pointers in the order of smx_forward's output arguments: (dict of arrays, pointers)."""
+    cfg = self.cfg
+    D, G, k = cfg.latent_dim, cfg.n_genes, cfg.k
+    lead = () if S is None else (S,)
+    out = dict(z_mean=np.empty((B, D), np.float32), z_sample=np.empty(lead + (B, D), np.float32))
+    out["z_scale"] = np.empty((B, D), np.float32) if cfg.stochastic else None
+    if cfg.model == "scvi":
+      out.update(l_mean=np.empty((B,), np.float32), l_scale=np.empty((B,), np.float32), l_sample=np.empty(lead + (B,), np.float32))
+    out["x_params"] = np.empty(lead + (k, B, G), np.float32) if want_x_params else None
+    out["y_params"] = [np.empty(lead + (B, label_planes(llk, P) * P), np.float32) for P, llk in cfg.head_labels]
+    return out, (_fp(out["z_mean"]), _fp(out["z_scale"]), _fp(out["z_sample"]), _fp(out.get("l_mean")), _fp(out.get("l_scale")),
+                 _fp(out.get("l_sample")), _fp(out["x_params"]), _fps(out["y_params"]))
+
   def forward(self, row_ids=None, x=None, library=None, sample_index: int = 0, training: bool = False,
               want_x_params: bool = True):
     """Eval-mode forward; returns dict of logical-shape arrays."""
-    cfg = self.cfg
-    if row_ids is not None:
-      ids = self._ids(row_ids)
-      B, idp, xp, lp = ids.size, ids.ctypes.data_as(C.POINTER(C.c_int32)), None, None
-    else:
-      xa = _f32(x)
-      B, idp, xp = xa.shape[0], None, _fp(xa)
-      la = None if library is None else _f32(library, (B, 2))
-      lp = _fp(la)
-    D, G, k = cfg.latent_dim, cfg.n_genes, cfg.k
-    out = dict(z_mean=np.empty((B, D), np.float32), z_sample=np.empty((B, D), np.float32))
-    out["z_scale"] = np.empty((B, D), np.float32) if cfg.stochastic else None
-    if cfg.model == "scvi":
-      out.update(l_mean=np.empty((B,), np.float32), l_scale=np.empty((B,), np.float32), l_sample=np.empty((B,), np.float32))
-    if want_x_params:
-      out["x_params"] = np.empty((k, B, G), np.float32)
-    ys = [np.empty((B, label_planes(llk, P) * P), np.float32) for P, llk in cfg.head_labels]
-    yptrs = (C.POINTER(C.c_float) * max(1, len(ys)))(*[_fp(y) for y in ys]) if ys else None
-    check(self.lib.smx_forward(self._h, idp, xp, lp, B, int(sample_index), int(training), _fp(out["z_mean"]),
-                               _fp(out.get("z_scale")), _fp(out["z_sample"]), _fp(out.get("l_mean")),
-                               _fp(out.get("l_scale")), _fp(out.get("l_sample")), _fp(out.get("x_params")), yptrs))
-    out["y_params"] = ys
+    B, keep, cells = self._cells(row_ids, x, library)
+    out, res = self._outputs(B, want_x_params=want_x_params)
+    check(self.lib.smx_forward(self._h, *cells, B, int(sample_index), int(training), *res))
     return out
 
   def forward_samples(self, n_samples: int, row_ids=None, x=None, library=None):
     """n_samples Monte-Carlo draws of one batch in one call (the encoders run once): arrays with a leading draw axis
     for z_sample / l_sample / x_params / y_params, one copy of the posterior means and scales."""
-    cfg = self.cfg
     S = int(n_samples)
-    if row_ids is not None:
-      ids = self._ids(row_ids)
-      B, idp, xp, lp = ids.size, ids.ctypes.data_as(C.POINTER(C.c_int32)), None, None
-    else:
-      xa = _f32(x)
-      B, idp, xp = xa.shape[0], None, _fp(xa)
-      la = None if library is None else _f32(library, (B, 2))
-      lp = _fp(la)
-    D, G, k = cfg.latent_dim, cfg.n_genes, cfg.k
-    out = dict(z_mean=np.empty((B, D), np.float32), z_sample=np.empty((S, B, D), np.float32))
-    out["z_scale"] = np.empty((B, D), np.float32) if cfg.stochastic else None
-    if cfg.model == "scvi":
-      out.update(l_mean=np.empty((B,), np.float32), l_scale=np.empty((B,), np.float32), l_sample=np.empty((S, B), np.float32))
-    out["x_params"] = np.empty((S, k, B, G), np.float32)
-    ys = [np.empty((S, B, label_planes(llk, P) * P), np.float32) for P, llk in cfg.head_labels]
-    yptrs = (C.POINTER(C.c_float) * max(1, len(ys)))(*[_fp(y) for y in ys]) if ys else None
-    check(self.lib.smx_forward_samples(self._h, idp, xp, lp, B, S, _fp(out["z_mean"]), _fp(out.get("z_scale")),
-                                       _fp(out["z_sample"]), _fp(out.get("l_mean")), _fp(out.get("l_scale")),
-                                       _fp(out.get("l_sample")), _fp(out["x_params"]), yptrs))
-    out["y_params"] = ys
+    B, keep, cells = self._cells(row_ids, x, library)
+    out, res = self._outputs(B, S)
+    check(self.lib.smx_forward_samples(self._h, *cells, B, S, *res))
     return out
 
   def predict(self, x, library=None, n_samples: int = 1, batch: Optional[int] = None, want_x_params: bool = True):
@@ -389,21 +383,11 @@ class Engine:
     N, S = (xa[0].size - 1 if isinstance(xa, tuple) else xa.shape[0]), int(n_samples)
     B = min(int(batch or self.max_batch), self.max_batch)
     la = None if library is None else _f32(library, (N, 2))
-    D, G, k = cfg.latent_dim, cfg.n_genes, cfg.k
-    out = dict(z_mean=np.empty((N, D), np.float32), z_sample=np.empty((S, N, D), np.float32))
-    out["z_scale"] = np.empty((N, D), np.float32) if cfg.stochastic else None
-    if cfg.model == "scvi":
-      out.update(l_mean=np.empty((N,), np.float32), l_scale=np.empty((N,), np.float32), l_sample=np.empty((S, N), np.float32))
-    out["x_params"] = np.empty((S, k, N, G), np.float32) if want_x_params else None
-    ys = [np.empty((S, N, label_planes(llk, P) * P), np.float32) for P, llk in cfg.head_labels]
-    yptrs = (C.POINTER(C.c_float) * max(1, len(ys)))(*[_fp(y) for y in ys]) if ys else None
-    res = (_fp(out["z_mean"]), _fp(out.get("z_scale")), _fp(out["z_sample"]), _fp(out.get("l_mean")), _fp(out.get("l_scale")),
-           _fp(out.get("l_sample")), _fp(out["x_params"]), yptrs)
+    out, res = self._outputs(N, S, want_x_params)
     if isinstance(xa, tuple):
       check(self.lib.smx_predict_csr(self._h, *_csr_ptrs(xa), _fp(la), N, B, S, *res))
     else:
       check(self.lib.smx_predict(self._h, _fp(xa), _fp(la), N, B, S, *res))
-    out["y_params"] = ys
     return out
 
   STATS = {"mean": 0, "variance": 1, "mean_over_samples": 2, "log_prob": 3}
@@ -449,8 +433,7 @@ class Engine:
     la = None if l is None else _f32(np.reshape(l, (B,)))
     xp = np.empty((cfg.k, B, cfg.n_genes), np.float32)
     ys = [np.empty((B, label_planes(llk, P) * P), np.float32) for P, llk in cfg.head_labels]
-    yptrs = (C.POINTER(C.c_float) * max(1, len(ys)))(*[_fp(y) for y in ys]) if ys else None
-    check(self.lib.smx_decode(self._h, _fp(za), _fp(la), B, _fp(xp), yptrs))
+    check(self.lib.smx_decode(self._h, _fp(za), _fp(la), B, _fp(xp), _fps(ys)))
     return dict(x_params=xp, y_params=ys)
 
   def marginal_llk(self, row_ids=None, x=None, library=None, n_samples: int = 100):
@@ -463,16 +446,9 @@ class Engine:
       mllk, llk = np.empty(B, np.float32), np.empty(B, np.float32)
       check(self.lib.smx_marginal_llk_csr(self._h, *_csr_ptrs(xc), _fp(la), B, int(n_samples), _fp(mllk), _fp(llk)))
       return mllk, llk
-    if row_ids is not None:
-      ids = self._ids(row_ids)
-      B, idp, xp, lp = ids.size, ids.ctypes.data_as(C.POINTER(C.c_int32)), None, None
-    else:
-      xa = _f32(x)
-      B, idp, xp = xa.shape[0], None, _fp(xa)
-      la = None if library is None else _f32(library, (B, 2))
-      lp = _fp(la)
+    B, keep, cells = self._cells(row_ids, x, library)
     mllk, llk = np.empty(B, np.float32), np.empty(B, np.float32)
-    check(self.lib.smx_marginal_llk(self._h, idp, xp, lp, B, int(n_samples), _fp(mllk), _fp(llk)))
+    check(self.lib.smx_marginal_llk(self._h, *cells, B, int(n_samples), _fp(mllk), _fp(llk)))
     return mllk, llk
 
   # ---- resident-matrix preprocessing ---------------------------------------
@@ -515,18 +491,11 @@ class Engine:
     if _sparse(x):
       x = x.toarray()
     targets = [t.toarray() if _sparse(t) else t for t in targets]
-    if row_ids is not None:
-      ids = self._ids(row_ids)
-      B, idp, xp, lp = ids.size, ids.ctypes.data_as(C.POINTER(C.c_int32)), None, None
-    else:
-      xa = _f32(x)
-      B, idp, xp = xa.shape[0], None, _fp(xa)
-      la = None if library is None else _f32(library, (B, 2))
-      lp = _fp(la)
+    B, cells_keep, cells = self._cells(row_ids, x, library)
     keep = [None if t is None else _f32(t, (B, self.cfg.n_genes)) for t in targets]
     arr = (C.POINTER(C.c_float) * len(keep))(*[_fp(t) if t is not None else C.POINTER(C.c_float)() for t in keep])
     out = np.empty((len(keep), 2, B), np.float32)
-    check(self.lib.smx_score_llk(self._h, idp, xp, lp, arr, len(keep), B, int(n_samples), _fp(out)))
+    check(self.lib.smx_score_llk(self._h, *cells, arr, len(keep), B, int(n_samples), _fp(out)))
     return out
 
   # ---- noise injection (parity tests) ----------------------------------------------

@@ -635,6 +635,21 @@ class SingleCellModel:
       return outs
     return outs[0] if len(outs) == 1 else tuple(outs)
 
+  def _drawn(self, o, n, outputs="all"):
+    """An Engine.predict (or forward_samples) result of max(n, 1) draws -> (output distributions, the first draw's results as
+    Engine.forward gives them: what _latent_dists takes).  outputs: "all", "heads" (the label heads alone: a lazy gene output) or None."""
+    pX = None
+    if outputs is not None:
+      heads = outputs == "heads"
+      if n > 1:
+        pX = self._output_dists(None if heads else o["x_params"], o["y_params"], stacked=True, heads_only=heads)
+      else:
+        pX = self._output_dists(None if heads else [o["x_params"][0]], [[y[0] for y in o["y_params"]]], heads_only=heads)
+    first = dict(o, z_sample=o["z_sample"][0])
+    if "l_sample" in o:
+      first["l_sample"] = o["l_sample"][0]
+    return pX, first
+
   def __call__(self, inputs=None, library=None, mask=None, training=None, sample_shape=(), **kwargs):
     arrs = _flatten(inputs)
     x = _rows(arrs[0])
@@ -643,21 +658,10 @@ class SingleCellModel:
     n = int(np.prod(sample_shape)) if np.size(sample_shape) else 0
     e = self._ensure_engine(x.shape[0])
     if is_sparse(x):   # the whole input is one batch of smx_predict_csr: the numbers of smx_forward(_samples) on the dense rows
-      o = e.predict(x, library=library, n_samples=max(n, 1), batch=x.shape[0])
-      if n > 1:
-        pX = self._output_dists(o["x_params"], o["y_params"], stacked=True)
-      else:
-        pX = self._output_dists([o["x_params"][0]], [[y[0] for y in o["y_params"]]])
-      first = dict(o, z_sample=o["z_sample"][0])
-      if "l_sample" in o:
-        first["l_sample"] = o["l_sample"][0]
+      pX, first = self._drawn(e.predict(x, library=library, n_samples=max(n, 1), batch=x.shape[0]), n)
       return pX, self._latent_dists(first)
     if n > 1:   # every draw in one call: the encoders run once, the draws re-sample the latents and decode
-      o = e.forward_samples(n, x=x, library=library)
-      pX = self._output_dists(o["x_params"], o["y_params"], stacked=True)
-      first = dict(o, z_sample=o["z_sample"][0])
-      if "l_sample" in o:
-        first["l_sample"] = o["l_sample"][0]
+      pX, first = self._drawn(e.forward_samples(n, x=x, library=library), n)
       return pX, self._latent_dists(first)
     outs = [e.forward(x=x, library=library, sample_index=s) for s in range(max(n, 1))]
     pX = self._output_dists([o["x_params"] for o in outs], [o["y_params"] for o in outs])
@@ -672,10 +676,7 @@ class SingleCellModel:
       library = library_matrix(x)
     e = self._ensure_engine(x.shape[0])
     if is_sparse(x):   # (one batch of smx_predict_csr; the whole forward pass, as smx_forward runs it)
-      o = e.predict(x, library=library, n_samples=1, batch=x.shape[0])
-      out = dict(o, z_sample=o["z_sample"][0])
-      if "l_sample" in o:
-        out["l_sample"] = o["l_sample"][0]
+      _, out = self._drawn(e.predict(x, library=library, n_samples=1, batch=x.shape[0]), 1, outputs=None)
     else:
       out = e.forward(x=x, library=library, want_x_params=False)
     return self._latent_dists(out)
@@ -754,19 +755,11 @@ class SingleCellModel:
     lazy = lazy and self._cfg.likelihood != "mse"
     B = min(int(batch_size), e.max_batch)
     o = e.predict(x, library=lib, n_samples=max(n, 1), batch=B, want_x_params=not lazy)
+    pX, first = self._drawn(o, n, outputs="heads" if lazy else "all")
     if lazy:
       # the gene output stays a handle (its planes never leave the device); the small head outputs and the latents are eager as always
-      heads = self._output_dists(None, o["y_params"], stacked=True, heads_only=True) if n > 1 else \
-          self._output_dists(None, [[y[0] for y in o["y_params"]]], heads_only=True)
       px = D.LazyCountOutput(self, _rows(x), lib, n, B, self._outputs[0].name or "transcriptomic")
-      pX = (px,) + tuple(heads) if heads else px
-    elif n > 1:
-      pX = self._output_dists(o["x_params"], o["y_params"], stacked=True)
-    else:
-      pX = self._output_dists([o["x_params"][0]], [[y[0] for y in o["y_params"]]])
-    first = dict(o, z_sample=o["z_sample"][0])
-    if "l_sample" in o:
-      first["l_sample"] = o["l_sample"][0]
+      pX = (px,) + tuple(pX) if pX else px
     qZ = self._latent_dists(first)
     return pX, (tuple(qZ) if isinstance(qZ, list) else qZ)
 
