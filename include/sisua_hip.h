@@ -71,6 +71,9 @@ typedef enum { SMX_LLK_NB = 0, SMX_LLK_ZINB = 1, SMX_LLK_NBD = 2, SMX_LLK_ZINBD 
 typedef enum { SMX_LABEL_NB = 0, SMX_LABEL_ONEHOT = 1, SMX_LABEL_MIXNB = 2, SMX_LABEL_MIXGAUSS = 3, SMX_LABEL_MIXTRIL = 4, SMX_LABEL_MIXZINB = 5,
                SMX_LABEL_NBD = 6, SMX_LABEL_ZINB = 7, SMX_LABEL_ZINBD = 8 } smx_label_likelihood;
 typedef enum { SMX_ACT_RELU = 0, SMX_ACT_LINEAR = 1 } smx_activation;
+/* Optimiser rules (smx_set_optimizer; tf.keras 2.x Adam, SGD, RMSprop, Adagrad, Adamax). */
+typedef enum { SMX_OPT_ADAM = 0, SMX_OPT_SGD = 1, SMX_OPT_RMSPROP = 2, SMX_OPT_ADAGRAD = 3, SMX_OPT_ADAMAX = 4 } smx_optimizer;
+#define SMX_OPT_MAX_HP 4
 
 /* Constructor arguments of SingleCellModel / SCVI / SISUA / DeepCountAutoencoder
  * (single_cell_model.py:74-97, scvi.py:33-48, vae.py:40-44, dca.py:16-28) plus
@@ -145,7 +148,10 @@ int smx_num_tensors(const smx_model* m);
 int smx_tensor_info(const smx_model* m, int index, char* name, int name_cap, int32_t* rows, int32_t* cols);
 /* which: 0 = parameters, 1 = gradients of the last step (after all-reduce, before
  * clipping), 2 = Adam m, 3 = Adam v.  Replaces save_weights/load_weights
- * (single_cell_model.py:283-306) and serves the parity tests. */
+ * (single_cell_model.py:283-306) and serves the parity tests.
+ * Under the other rules of smx_set_optimizer, which = 2 / 3 are that rule's slots: sgd the momentum accumulator / - (no
+ * slot at momentum 0), rmsprop mom / ms (mom unused at momentum 0), adagrad - / the accumulator, adamax m / u.  A slot a
+ * rule does not use keeps whatever it holds and is not read. */
 int smx_get_tensor(smx_model* m, int which, int index, float* host);
 int smx_set_tensor(smx_model* m, int which, int index, const float* host);
 /* Batch-norm moving statistics, layer order = oracle bn_manifest; which: 0 mean, 1 var. */
@@ -251,6 +257,22 @@ int smx_eval_step(smx_model* m, const int32_t* row_ids, int32_t batch, smx_metri
  * max_batch on first use; captured graphs are dropped whenever the count changes.  SMX_ERR_INVALID for
  * n_draws < 1, for FactorVAE / SemiFVAE with n_draws > 1 and for a data-parallel model (world > 1). */
 int smx_set_train_draws(smx_model* m, int32_t n_draws);
+/* The optimiser rule of the later training steps (the `optimizer:` key of configs/base.yaml:45-50, handed to the Keras optimiser
+ * registry by the reference): rule = smx_optimizer, hp[n_hp] its hyper-parameters in this order (entries not given take the
+ * tf.keras 2.x defaults in parentheses):
+ *   SMX_OPT_ADAM      beta_1, beta_2, epsilon (smx_config.adam_beta1 / adam_beta2 / adam_eps -- the rule a model is created with)
+ *   SMX_OPT_SGD       momentum (0), nesterov (0 / 1)
+ *   SMX_OPT_RMSPROP   rho (0.9), momentum (0), epsilon (1e-7)
+ *   SMX_OPT_ADAGRAD   initial_accumulator_value (0.1), epsilon (1e-7)
+ *   SMX_OPT_ADAMAX    beta_1 (0.9), beta_2 (0.999), epsilon (1e-7)
+ * Every rule keeps smx_config.lr, the per-tensor clipnorm in front of the update and the tied-variable norm of SCALE.  The rule
+ * starts FRESH, as a new Keras optimiser object does: its slots (smx_get_tensor which = 2 / 3) are set to 0 -- Adagrad's
+ * accumulator to initial_accumulator_value -- and t0 = the model's step count now (smx_set_step first to record another); the
+ * rule's step count is t = step + 1 - t0 (Adam's and Adamax's bias correction).  Captured graphs are dropped.  With opt_shard
+ * the fresh slots are whole on every rank.  SMX_ERR_INVALID for an unknown rule, n_hp > SMX_OPT_MAX_HP or a value out of range. */
+int smx_set_optimizer(smx_model* m, int32_t rule, const float* hp, int32_t n_hp);
+/* The rule in force, its SMX_OPT_MAX_HP hyper-parameters (defaults filled in, unused entries 0) and t0; any output may be NULL. */
+int smx_get_optimizer(const smx_model* m, int32_t* rule, float* hp, int32_t* t0);
 
 /* Eval-mode forward for predict/encode/decode (single_cell_model.py:119-211):
  * writes distribution parameters into caller-owned buffers (any may be NULL).
@@ -487,6 +509,10 @@ int smx_k_count_llk(int likelihood, int direct, const float* x, const float* pla
  * device as in a training step).  norms[n_tensors] (may be NULL): gradient norms before clipping. */
 int smx_k_adam(int32_t n_tensors, const int32_t* sizes, float* params, const float* grads, float* m, float* v,
                int32_t step, float lr, float beta1, float beta2, float eps, float clipnorm, float* norms);
+/* The same launch under any rule of smx_set_optimizer (rule, hp[n_hp] as there): m / v are the rule's slots 2 / 3 (both host
+ * arrays are always given; a slot the rule does not use is left as it is).  step = the rule's 1-based count t. */
+int smx_k_opt(int32_t rule, const float* hp, int32_t n_hp, int32_t n_tensors, const int32_t* sizes, float* params, const float* grads,
+              float* m, float* v, int32_t step, float lr, float clipnorm, float* norms);
 /* C[M,N] = op(A) * op(B) in fp32 on the MFMA path; transA: A given as [K,M];
  * transB: B given as [N,K]; split_k >= 1 (slabs summed on return).  tile_cfg 0: the library's choice of LDS tile; 100: the
  * direct bf16 x 3 form for deep contractions (transA = 0, K >= 512); 101 / 102: the minibatch-contracted weight-gradient forms

@@ -96,6 +96,8 @@ SIGNATURES = {
     "smx_metrics_history": (C.c_int, [_VP, C.c_int32, _FP]),
     "smx_eval_step": (C.c_int, [_VP, _IP, C.c_int32, C.POINTER(smx_metrics)]),
     "smx_set_train_draws": (C.c_int, [_VP, C.c_int32]),
+    "smx_set_optimizer": (C.c_int, [_VP, C.c_int32, _FP, C.c_int32]),
+    "smx_get_optimizer": (C.c_int, [_VP, _IP, _FP, _IP]),
     "smx_forward": (C.c_int, [_VP, _IP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
                               C.POINTER(_FP)]),
     "smx_forward_samples": (C.c_int, [_VP, _IP, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
@@ -133,6 +135,7 @@ SIGNATURES = {
     "smx_comm_init_local": (C.c_int, [C.POINTER(_VP), C.c_int]),
     "smx_k_adam": (C.c_int, [C.c_int32, _IP, _FP, _FP, _FP, _FP, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
                              C.c_float, _FP]),
+    "smx_k_opt": (C.c_int, [C.c_int32, _FP, C.c_int32, C.c_int32, _IP, _FP, _FP, _FP, _FP, C.c_int32, C.c_float, C.c_float, _FP]),
     "smx_set_flag": (C.c_int, [_VP, C.c_char_p, C.c_int]),
     "smx_set_tuning": (C.c_int, [C.c_char_p, C.c_double]),
     "smx_clear_tuning": (C.c_int, [C.c_char_p]),

@@ -1,4 +1,5 @@
-// smx_adam.h -- the optimiser's workgroup body (per-tensor clipnorm + Adam over one chunk of the flat buffer),
+// smx_adam.h -- the optimiser's workgroup body (per-tensor clipnorm + Adam, or the rule smx_set_optimizer chose, over one chunk of the
+// flat buffer),
 // shared by the optimiser launch (smx_adam.hip), by the launches that carry chunks as riders -- the BatchNorm-backward kernels
 // (smx_bn.hip) and the latent head's backward product (smx_gemm.hip) -- and by the heads' background sweep on the second stream
 // (adam_sweep_body; smx_step.hip: head_sweep_*).  Also the bodies of the ELBO scalars and of the sum-of-squares reductions, which
@@ -73,41 +74,159 @@ __device__ inline void adam_apply4(const AdamArgs& a, float clip, float lr_t, co
   adam_apply4(a.b1, a.b2, a.eps, clip, lr_t, g, m, v, p);
 }
 
+// the other rules (smx_set_optimizer; the forms of TensorFlow's training ops): slot 2 = m, slot 3 = v as OptSlots
+// say -- a rule reads and writes only the slots it uses.  Spelled like adam_apply4, for the same reason.
+template <int F> struct OptSlots {
+  static constexpr bool m = F == OPT_ADAM || F == OPT_SGD_MOM || F == OPT_SGD_NESTEROV || F == OPT_RMSPROP_MOM || F == OPT_ADAMAX;
+  static constexpr bool v = F == OPT_ADAM || F == OPT_RMSPROP || F == OPT_RMSPROP_MOM || F == OPT_ADAGRAD || F == OPT_ADAMAX;
+};
+template <int F>
+__device__ __attribute__((always_inline)) inline void opt_apply1(const AdamArgs& a, float lr_t, float ge, float& m, float& v, float& p) {
+#pragma clang fp contract(off)
+  const float b1 = a.b1, b2 = a.b2, eps = a.eps, mu = a.momentum;
+  if constexpr (F == OPT_SGD) {                      // w -= lr g
+    p = __builtin_fmaf(-lr_t, ge, p);
+  } else if constexpr (F == OPT_SGD_MOM) {           // a = momentum a - lr g;  w += a
+    m = __builtin_fmaf(mu, m, -(lr_t * ge));
+    p = p + m;
+  } else if constexpr (F == OPT_SGD_NESTEROV) {      // a = momentum a - lr g;  w += momentum a - lr g
+    m = __builtin_fmaf(mu, m, -(lr_t * ge));
+    p = p + __builtin_fmaf(mu, m, -(lr_t * ge));
+  } else if constexpr (F == OPT_RMSPROP) {           // ms = rho ms + (1 - rho) g^2;  w -= lr g / (sqrt(ms) + eps)
+    v = __builtin_fmaf(b1, v, ((1.f - b1) * ge) * ge);
+    p = __builtin_fmaf(-(lr_t * ge), frcp(fsqrt(v) + eps), p);
+  } else if constexpr (F == OPT_RMSPROP_MOM) {       // ms as above;  mom = momentum mom + lr g / sqrt(ms + eps);  w -= mom
+    v = __builtin_fmaf(b1, v, ((1.f - b1) * ge) * ge);
+    m = __builtin_fmaf(mu, m, (lr_t * ge) * frcp(fsqrt(v + eps)));
+    p = p - m;
+  } else if constexpr (F == OPT_ADAGRAD) {           // acc += g^2;  w -= lr g / (sqrt(acc) + eps)
+    v = __builtin_fmaf(ge, ge, v);
+    p = __builtin_fmaf(-(lr_t * ge), frcp(fsqrt(v) + eps), p);
+  } else {                                           // Adamax: m = b1 m + (1 - b1) g;  u = max(b2 u, |g|);  w -= lr_t m / (u + eps)
+    m = __builtin_fmaf(b1, m, (1.f - b1) * ge);
+    v = fmaxf(b2 * v, fabsf(ge));
+    p = __builtin_fmaf(-(lr_t * m), frcp(v + eps), p);
+  }
+}
+template <int F>
+__device__ __attribute__((always_inline)) inline void opt_apply4(const AdamArgs& a, float clip, float lr_t, const smx_f32x4& g, smx_f32x4& m, smx_f32x4& v, smx_f32x4& p) {
+  if constexpr (F == OPT_ADAM) {
+    adam_apply4(a, clip, lr_t, g, m, v, p);
+  } else {   // (element by element with constant indices: a loop over a vector's elements left the vectors in scratch memory here)
+    float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], v0 = v[0], v1 = v[1], v2 = v[2], v3 = v[3], p0 = p[0], p1 = p[1], p2 = p[2], p3 = p[3];
+    opt_apply1<F>(a, lr_t, g[0] * clip, m0, v0, p0);
+    opt_apply1<F>(a, lr_t, g[1] * clip, m1, v1, p1);
+    opt_apply1<F>(a, lr_t, g[2] * clip, m2, v2, p2);
+    opt_apply1<F>(a, lr_t, g[3] * clip, m3, v3, p3);
+    m = smx_f32x4{m0, m1, m2, m3}; v = smx_f32x4{v0, v1, v2, v3}; p = smx_f32x4{p0, p1, p2, p3};
+  }
+}
+
+// CALL(F) for the chunk's rule F = a.form: the one branch a carrier takes per chunk (a.form is uniform over the launch).  ALL = false: Adam
+// only -- the riders of the BatchNorm-backward and latent-head launches, and the Adam instantiations of the optimiser's own kernels, hold
+// no code of the other rules (with it, the same Adam instructions ran 0.9 us per C2 step slower: DESIGN.md 4d)
+#define SMX_OPT_SWITCH(ALL, form, CALL)                                                                                               \
+  if constexpr (!(ALL)) {                                                                                                             \
+    CALL(OPT_ADAM);                                                                                                                   \
+  } else {                                                                                                                            \
+    switch (form) {                                                                                                                   \
+      case OPT_SGD: CALL(OPT_SGD); break;                                                                                             \
+      case OPT_SGD_MOM: CALL(OPT_SGD_MOM); break;                                                                                     \
+      case OPT_SGD_NESTEROV: CALL(OPT_SGD_NESTEROV); break;                                                                           \
+      case OPT_RMSPROP: CALL(OPT_RMSPROP); break;                                                                                     \
+      case OPT_RMSPROP_MOM: CALL(OPT_RMSPROP_MOM); break;                                                                             \
+      case OPT_ADAGRAD: CALL(OPT_ADAGRAD); break;                                                                                     \
+      case OPT_ADAMAX: CALL(OPT_ADAMAX); break;                                                                                       \
+      default: CALL(OPT_ADAM); break;                                                                                                 \
+    }                                                                                                                                 \
+  }
+
 // clip + Adam for one chunk of the flat buffer; NT = 256 threads, or 512 as a rider of a 512-thread launch (the tensor's norm is
 // summed by the first 256 threads in the same order either way: both forms give the same bits).  A thread's first operands are
 // requested BEFORE the norm is reduced and each later round's before the current round's arithmetic: a workgroup lives for 2-4
 // rounds, so the reduction's barrier and the first loads' latency were a third of its life.  (Nontemporal loads / stores of the
 // moments, to keep the weights in the last-level cache, measured slower: c5-shard 198.0 -> 200.0 us, C2 80.4 -> 81.7.)
-template <int NT = 256>
-__device__ inline void adam_chunk_body(const AdamArgs& a, int chunk) {
+// the element loop of a chunk under the rule F: under Adam a thread's next quads are requested before the current quad's arithmetic
+template <int NT, int F>
+__device__ __attribute__((always_inline)) inline void opt_chunk_loop(const AdamArgs& a, float clip, float lr_t, int i, int n4, const smx_f32x4* g4, smx_f32x4* m4, smx_f32x4* v4,
+                                      smx_f32x4* p4, smx_f32x4 g, smx_f32x4 m, smx_f32x4 v, smx_f32x4 p) {
+  constexpr bool UM = OptSlots<F>::m, UV = OptSlots<F>::v;
+  if constexpr (F != OPT_ADAM) {   // (the other rules one quad at a time)
+    for (; i < n4; i += NT) {
+      if (UM) m = m4[i];
+      if (UV) v = v4[i];
+      p = p4[i];
+      opt_apply4<F>(a, clip, lr_t, g4[i], m, v, p);
+      if (UM) m4[i] = m;
+      if (UV) v4[i] = v;
+      p4[i] = p;
+    }
+    return;
+  }
+  while (i < n4) {
+    const int j = i + NT;
+    smx_f32x4 gn = g, mn = m, vn = v, pn = p;
+    if (j < n4) { gn = g4[j]; if (UM) mn = m4[j]; if (UV) vn = v4[j]; pn = p4[j]; }
+    opt_apply4<F>(a, clip, lr_t, g, m, v, p);
+    if (UM) m4[i] = m;
+    if (UV) v4[i] = v;
+    p4[i] = p;
+    g = gn; m = mn; v = vn; p = pn; i = j;
+  }
+}
+template <int NT, int F>
+__device__ __attribute__((always_inline)) inline void opt_chunk_body(const AdamArgs& a, int chunk) {
   const OptChunk ch = a.chunks[chunk];
   const smx_f32x4* g4 = reinterpret_cast<const smx_f32x4*>(a.grads + ch.offset);
   smx_f32x4* m4 = reinterpret_cast<smx_f32x4*>(a.m + ch.offset);
   smx_f32x4* v4 = reinterpret_cast<smx_f32x4*>(a.v + ch.offset);
   smx_f32x4* p4 = reinterpret_cast<smx_f32x4*>(a.params + ch.offset);
   const int n4 = ch.count / 4;
-  int i = threadIdx.x;
+  const int i = threadIdx.x;
   smx_f32x4 g = {0.f, 0.f, 0.f, 0.f}, m = g, v = g, p = g;
-  auto fetch = [&](int j, smx_f32x4& go, smx_f32x4& mo, smx_f32x4& vo, smx_f32x4& po) {
-    go = g4[j]; mo = m4[j]; vo = v4[j]; po = p4[j];
-  };
   const float lr_t = a.state->lr_t;   // (ahead of the norm's barriers: behind them it was a round trip of its own)
-  if (i < n4) fetch(i, g, m, v, p);
+  if (F == OPT_ADAM && i < n4) { g = g4[i]; m = m4[i]; v = v4[i]; p = p4[i]; }
   const float clip = adam_tensor_clip<NT>(a, ch, chunk);
-  while (i < n4) {
-    const int j = i + NT;
-    smx_f32x4 gn = g, mn = m, vn = v, pn = p;
-    if (j < n4) fetch(j, gn, mn, vn, pn);
-    adam_apply4(a, clip, lr_t, g, m, v, p);
-    m4[i] = m; v4[i] = v; p4[i] = p;
-    g = gn; m = mn; v = vn; p = pn; i = j;
-  }
+  opt_chunk_loop<NT, F>(a, clip, lr_t, i, n4, g4, m4, v4, p4, g, m, v, p);
+}
+// (one whole body per rule: a body shared by the rules up to the element loop raised the register counts by up to 6)
+template <int NT = 256, bool ALL = false>
+__device__ inline void adam_chunk_body(const AdamArgs& a, int chunk) {
+#define SMX_OPT_BODY(F) opt_chunk_body<NT, F>(a, chunk)
+  SMX_OPT_SWITCH(ALL, a.form, SMX_OPT_BODY)
+#undef SMX_OPT_BODY
 }
 
 // the background sweep's workgroup (smx_adam.hip: adam_sweep_kernel): chunks first + blockIdx.x, + gridDim.x, ... -- the tensor's factor is
 // worked out when the tensor changes (the output head's matrix is ~1900 chunks of one tensor), and a thread keeps two quads of every operand in
 // flight; element by element the same arithmetic as adam_chunk_body: the same bits
-template <int NT>
+// a chunk of the sweep under the rule F: two quads of every operand in flight
+template <int NT, int F>
+__device__ __attribute__((always_inline)) inline void opt_sweep_chunk(const AdamArgs& a, float clip, float lr_t, int n4, const smx_f32x4* g4, smx_f32x4* m4, smx_f32x4* v4,
+                                       smx_f32x4* p4) {
+  constexpr bool UM = OptSlots<F>::m, UV = OptSlots<F>::v;
+  const smx_f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  for (int i = threadIdx.x; i < n4; i += 2 * NT) {
+    const int j = i + NT;
+    const bool two = j < n4;
+    const int jj = two ? j : i;
+    const smx_f32x4 g0 = g4[i], m0 = UM ? m4[i] : z, v0 = UV ? v4[i] : z, p0 = p4[i];
+    const smx_f32x4 g1 = g4[jj], m1 = UM ? m4[jj] : z, v1 = UV ? v4[jj] : z, p1 = p4[jj];
+    smx_f32x4 m = m0, v = v0, p = p0;
+    opt_apply4<F>(a, clip, lr_t, g0, m, v, p);
+    if (UM) m4[i] = m;
+    if (UV) v4[i] = v;
+    p4[i] = p;
+    if (two) {
+      m = m1; v = v1; p = p1;
+      opt_apply4<F>(a, clip, lr_t, g1, m, v, p);
+      if (UM) m4[j] = m;
+      if (UV) v4[j] = v;
+      p4[j] = p;
+    }
+  }
+}
+template <int NT, bool ALL = false>
 __device__ inline void adam_sweep_body(const AdamArgs& a, int first, int count) {
   int cur_t = -1;
   float clip = 0.f;
@@ -121,21 +240,9 @@ __device__ inline void adam_sweep_body(const AdamArgs& a, int first, int count) 
     smx_f32x4* v4 = reinterpret_cast<smx_f32x4*>(a.v + ch.offset);
     smx_f32x4* p4 = reinterpret_cast<smx_f32x4*>(a.params + ch.offset);
     const int n4 = ch.count / 4;
-    for (int i = threadIdx.x; i < n4; i += 2 * NT) {
-      const int j = i + NT;
-      const bool two = j < n4;
-      const int jj = two ? j : i;
-      const smx_f32x4 g0 = g4[i], m0 = m4[i], v0 = v4[i], p0 = p4[i];
-      const smx_f32x4 g1 = g4[jj], m1 = m4[jj], v1 = v4[jj], p1 = p4[jj];
-      smx_f32x4 m = m0, v = v0, p = p0;
-      adam_apply4(a, clip, lr_t, g0, m, v, p);
-      m4[i] = m; v4[i] = v; p4[i] = p;
-      if (two) {
-        m = m1; v = v1; p = p1;
-        adam_apply4(a, clip, lr_t, g1, m, v, p);
-        m4[j] = m; v4[j] = v; p4[j] = p;
-      }
-    }
+#define SMX_OPT_SWEEP(F) opt_sweep_chunk<NT, F>(a, clip, lr_t, n4, g4, m4, v4, p4)
+    SMX_OPT_SWITCH(ALL, a.form, SMX_OPT_SWEEP)
+#undef SMX_OPT_SWEEP
   }
 }
 

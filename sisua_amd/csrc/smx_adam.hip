@@ -1,5 +1,5 @@
 // smx_adam.hip -- the per-step launches around the optimiser (gfx950): step begin, the ELBO scalars (a-15), per-tensor clipnorm +
-// Adam over the flat buffer (a-16) as one launch, a background sweep or a sharded chain, and the norms.  The workgroup bodies they
+// Adam (or the rule of smx_set_optimizer) over the flat buffer (a-16) as one launch, a background sweep or a sharded chain, and the norms.  The workgroup bodies they
 // share with the riders of other launches are smx_adam.h's.
 #include "smx_internal.h"
 #include "smx_adam.h"
@@ -12,9 +12,17 @@ namespace smx {
 __device__ inline float adam_lr_t(float lr, float b1, float b2, uint32_t t /* 1-based */) {
   return lr * sqrtf(1.f - powf(b2, (float)t)) / (1.f - powf(b1, (float)t));
 }
+// the step size of the step with index `step` under the rule `form`, whose state began at step t0: t = step + 1 - t0 (t0 = 0 for Adam unless
+// the rule was switched: Adam's bits as before).  Adamax: lr / (1 - b1^t); the rules without bias correction: lr.
+__device__ inline float opt_lr_t(int form, float lr, float b1, float b2, uint32_t step, uint32_t t0) {
+  const uint32_t t = step >= t0 ? step + 1u - t0 : 1u;
+  if (form == OPT_ADAM) return adam_lr_t(lr, b1, b2, t);
+  if (form == OPT_ADAMAX) return lr / (1.f - powf(b1, (float)t));
+  return lr;
+}
 
 __global__ void step_begin_kernel(StepState* master, StepState* dst, const int32_t* order, int32_t* rows, int batch,
-                                  int cursor_from_master, uint32_t cursor, float lr, float b1, float b2) {
+                                  int cursor_from_master, uint32_t cursor, float lr, float b1, float b2, int form, uint32_t t0) {
   const uint32_t cur = cursor_from_master ? master->cursor : cursor;
   if (order)
     for (int i = threadIdx.x; i < batch; i += blockDim.x) rows[i] = order[(long)cur * batch + i];
@@ -23,14 +31,14 @@ __global__ void step_begin_kernel(StepState* master, StepState* dst, const int32
     const uint32_t step = master->next;
     dst->step = step;
     dst->cursor = cur;
-    dst->lr_t = adam_lr_t(lr, b1, b2, step + 1);
+    dst->lr_t = opt_lr_t(form, lr, b1, b2, step, t0);
     if (cursor_from_master) master->cursor = cur + 1;
   }
 }
 int launch_step_begin(hipStream_t st, StepState* master, StepState* dst, const int32_t* order, int32_t* rows,
-                      int batch, int cursor_from_master, uint32_t cursor, float lr, float b1, float b2) {
+                      int batch, int cursor_from_master, uint32_t cursor, float lr, float b1, float b2, int form, uint32_t t0) {
   hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(256), 0, st, master, dst, order, rows, batch, cursor_from_master,
-                     cursor, lr, b1, b2);
+                     cursor, lr, b1, b2, form, t0);
   SMX_HIP(hipGetLastError());
   return SMX_OK;
 }
@@ -65,13 +73,15 @@ __global__ __launch_bounds__(256) void grad_sqsum_kernel(AdamArgs a) {
   if (threadIdx.x == 0) a.partial[blockIdx.x] = s;
 }
 
+// ALL = false: Adam (the rule a model is created with) without a line of the other rules' code; ALL = true: every rule (AdamArgs.form)
+template <bool ALL>
 __global__ __launch_bounds__(256) void adam_update_kernel(AdamArgs a) {
   if ((int)blockIdx.x == a.n_launch && a.use_sq && a.with_metrics) {  // use_sq form: the ELBO scalars ride along here
     metrics_body(a.metrics);
     return;
   }
   if ((int)blockIdx.x < a.n_launch) {
-    adam_chunk_body(a, (int)blockIdx.x >= a.gap_from ? (int)blockIdx.x + a.gap_len : (int)blockIdx.x);
+    adam_chunk_body<256, ALL>(a, (int)blockIdx.x >= a.gap_from ? (int)blockIdx.x + a.gap_len : (int)blockIdx.x);
     return;
   }
   // the LAST workgroup closes the step (nobody reads next_state / next_rows during this step).  As a duty of workgroup 0 behind its chunk --
@@ -86,7 +96,7 @@ __global__ __launch_bounds__(256) void adam_update_kernel(AdamArgs a) {
       if (a.prepare_next) {
         a.next_state->step = step + 1;
         a.next_state->cursor = cur + 1;
-        a.next_state->lr_t = adam_lr_t(a.lr, a.b1, a.b2, step + 2);
+        a.next_state->lr_t = opt_lr_t(ALL ? a.form : (int)OPT_ADAM, a.lr, a.b1, a.b2, step + 1, a.t0);
       }
     }
   }
@@ -95,9 +105,9 @@ __global__ __launch_bounds__(256) void adam_update_kernel(AdamArgs a) {
 // the heads' update as a background sweep beside the launches that follow the output head (smx_step.hip: head_sweep_*): a FIXED
 // number of workgroups walk the chunks, so the sweep never holds more than a few wave slots per CU and the small dependent
 // launches of the main stream are placed at once
-template <int NT>
+template <int NT, bool ALL>
 __global__ __launch_bounds__(NT) void adam_sweep_kernel(AdamArgs a, int first, int count) {
-  adam_sweep_body<NT>(a, first, count);
+  adam_sweep_body<NT, ALL>(a, first, count);
 }
 // the chunks' sums of squares for a RANGE of chunks (data parallel, chained form: the heads' chunks on the communication stream behind
 // their bucket's all-reduce; the optimiser launch's own pass then covers the front chunks only)
@@ -124,7 +134,10 @@ int launch_adam_sweep(hipStream_t st, const AdamArgs& a, int first, int count, i
   if (count <= 0) return SMX_OK;
   // (norms from the products' sum-of-squares partials, or -- use_sq = 0 -- from a.partial, filled by launch_grad_sqsum_range before)
   if (wgs <= 0) { set_error("adam sweep: no workgroups"); return SMX_ERR_INVALID; }
-  hipLaunchKernelGGL(adam_sweep_kernel<256>, dim3((unsigned)std::min(wgs, count)), dim3(256), 0, st, a, first, count);   // (512-thread workgroups: 181-184 us per c5-shard step against 175-176)
+  if (a.form == OPT_ADAM)   // (512-thread workgroups: 181-184 us per c5-shard step against 175-176)
+    hipLaunchKernelGGL((adam_sweep_kernel<256, false>), dim3((unsigned)std::min(wgs, count)), dim3(256), 0, st, a, first, count);
+  else
+    hipLaunchKernelGGL((adam_sweep_kernel<256, true>), dim3((unsigned)std::min(wgs, count)), dim3(256), 0, st, a, first, count);
   SMX_HIP(hipGetLastError());
   return SMX_OK;
 }
@@ -168,6 +181,21 @@ __global__ __launch_bounds__(256) void head_norms_kernel(AdamArgs a, int first, 
   if (ch.tensor == a.tied_t0 || ch.tensor == a.tied_t1) s *= a.tied_inv;
   if (threadIdx.x == 0) a.tensor_norm[ch.tensor] = sqrtf(s) * a.grad_scale;
 }
+// the elements [i_lo, i_hi) of a chunk under the rule F
+template <int F>
+__device__ __attribute__((always_inline)) inline void opt_shard_range(const AdamArgs& a, float clip, float lr_t, int i_lo, int i_hi, const smx_f32x4* g4, smx_f32x4* m4,
+                                       smx_f32x4* v4, smx_f32x4* p4) {
+  constexpr bool UM = OptSlots<F>::m, UV = OptSlots<F>::v;
+  const smx_f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  for (int i = i_lo + (int)threadIdx.x; i < i_hi; i += 256) {
+    smx_f32x4 m = UM ? m4[i] : z, v = UV ? v4[i] : z, p = p4[i];
+    opt_apply4<F>(a, clip, lr_t, g4[i], m, v, p);
+    if (UM) m4[i] = m;
+    if (UV) v4[i] = v;
+    p4[i] = p;
+  }
+}
+template <bool ALL>
 __global__ __launch_bounds__(256) void adam_shard_kernel(AdamArgs a, int first, int count) {
   int cur_t = -1;
   float clip = 0.f;
@@ -186,11 +214,9 @@ __global__ __launch_bounds__(256) void adam_shard_kernel(AdamArgs a, int first, 
     smx_f32x4* m4 = reinterpret_cast<smx_f32x4*>(a.m + ch.offset);
     smx_f32x4* v4 = reinterpret_cast<smx_f32x4*>(a.v + ch.offset);
     smx_f32x4* p4 = reinterpret_cast<smx_f32x4*>(a.params + ch.offset);
-    for (int i = i_lo + (int)threadIdx.x; i < i_hi; i += 256) {
-      smx_f32x4 m = m4[i], v = v4[i], p = p4[i];
-      adam_apply4(a, clip, lr_t, g4[i], m, v, p);
-      m4[i] = m; v4[i] = v; p4[i] = p;
-    }
+#define SMX_OPT_RANGE(F) opt_shard_range<F>(a, clip, lr_t, i_lo, i_hi, g4, m4, v4, p4)
+    SMX_OPT_SWITCH(ALL, a.form, SMX_OPT_RANGE)
+#undef SMX_OPT_RANGE
   }
 }
 int launch_grad_sqsum_shard(hipStream_t st, const AdamArgs& a, int first, int count) {
@@ -208,7 +234,10 @@ int launch_head_norms(hipStream_t st, const AdamArgs& a, int first, int count) {
 int launch_adam_shard(hipStream_t st, const AdamArgs& a, int first, int count, int wgs) {
   if (count <= 0) return SMX_OK;
   if (wgs <= 0 || a.use_sq || a.shard_hi <= a.shard_lo || (a.shard_lo % 4) || (a.shard_hi % 4)) { set_error("adam shard: bad arguments"); return SMX_ERR_INVALID; }
-  hipLaunchKernelGGL(adam_shard_kernel, dim3((unsigned)std::min(wgs, count)), dim3(256), 0, st, a, first, count);
+  if (a.form == OPT_ADAM)
+    hipLaunchKernelGGL((adam_shard_kernel<false>), dim3((unsigned)std::min(wgs, count)), dim3(256), 0, st, a, first, count);
+  else
+    hipLaunchKernelGGL((adam_shard_kernel<true>), dim3((unsigned)std::min(wgs, count)), dim3(256), 0, st, a, first, count);
   SMX_HIP(hipGetLastError());
   return SMX_OK;
 }
@@ -218,12 +247,26 @@ int launch_adam_shard(hipStream_t st, const AdamArgs& a, int first, int count, i
 // an agent-scope acquire/release round across the 8 XCDs costs far more than a kernel boundary (1.5 us).
 int launch_adam(hipStream_t st, const AdamArgs& a) {
   if (a.use_sq) {   // norms come from the weight-gradient products: no pass over the gradient buffer
-    hipLaunchKernelGGL(adam_update_kernel, dim3(a.n_launch + (a.with_metrics ? 1 : 0) + (a.master ? 1 : 0)), dim3(256), 0, st, a);
+    const dim3 grid(a.n_launch + (a.with_metrics ? 1 : 0) + (a.master ? 1 : 0));
+    if (a.form == OPT_ADAM) hipLaunchKernelGGL(adam_update_kernel<false>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(adam_update_kernel<true>, grid, dim3(256), 0, st, a);
     SMX_HIP(hipGetLastError());
     return SMX_OK;
   }
   hipLaunchKernelGGL(grad_sqsum_kernel, dim3((a.sq_chunks >= 0 ? a.sq_chunks : a.n_chunks) + (a.with_metrics ? 1 : 0) + (a.bn_total + 255) / 256), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(adam_update_kernel, dim3(a.n_launch + (a.master ? 1 : 0)), dim3(256), 0, st, a);
+  if (a.form == OPT_ADAM) hipLaunchKernelGGL(adam_update_kernel<false>, dim3(a.n_launch + (a.master ? 1 : 0)), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(adam_update_kernel<true>, dim3(a.n_launch + (a.master ? 1 : 0)), dim3(256), 0, st, a);
+  SMX_HIP(hipGetLastError());
+  return SMX_OK;
+}
+
+// the slots of a rule that starts fresh (smx_set_optimizer): every float of [0, n) set to `value`
+__global__ __launch_bounds__(256) void opt_fill_kernel(float* dst, long n, float value) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = value;
+}
+int launch_opt_fill(hipStream_t st, float* dst, long n, float value) {
+  if (n <= 0) return SMX_OK;
+  hipLaunchKernelGGL(opt_fill_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 4096)), dim3(256), 0, st, dst, n, value);
   SMX_HIP(hipGetLastError());
   return SMX_OK;
 }

@@ -213,7 +213,7 @@ bool bn_front_supported(int B, int Dp);
 struct StepState {
   uint32_t step;      // index of the step in flight (Philox counter word 2)
   uint32_t next;      // master copy only: optimiser steps completed so far
-  float lr_t;         // bias-corrected Adam step size of the step in flight
+  float lr_t;         // step size of the step in flight: Adam's bias-corrected one, lr / (1 - b1^t) under Adamax, lr otherwise (opt_lr_t)
   uint32_t cursor;    // position (in steps) of the step in flight inside the uploaded row-id order
 };
 
@@ -242,12 +242,17 @@ int launch_metrics(hipStream_t st, const MetricsArgs& a);
 #define SMX_SQR_MIN_SLOTS 4096     // tensors with fewer sum-of-squares slots are summed by the optimiser's workgroups themselves
 #define SMX_SQ_SMALL_TENSOR 131072  // floats: below this a workgroup re-derives the tensor's norm by itself (the output bias of three planes up to 43 000 genes)
 struct OptChunk { int32_t tensor; int32_t offset; int32_t count; int32_t first_chunk; int32_t n_chunks; int32_t tensor_count; int32_t pad[2]; };
+// the element update a chunk takes (smx_set_optimizer; smx_adam.h: opt_apply4): a rule with its compile-time settings (momentum 0 or not,
+// Nesterov) -- the carriers branch on it once per chunk, outside the element loop
+enum OptForm { OPT_ADAM = 0, OPT_SGD = 1, OPT_SGD_MOM = 2, OPT_SGD_NESTEROV = 3, OPT_RMSPROP = 4, OPT_RMSPROP_MOM = 5, OPT_ADAGRAD = 6,
+               OPT_ADAMAX = 7 };
 struct AdamArgs {
   // ELBO scalars ride along as one extra workgroup of the gradient-norm kernel
   MetricsArgs metrics; int with_metrics = 0;
   // the optimiser's workgroup 0 finishes the step: master counter, and the state + row ids of the next step
   StepState* master = nullptr; StepState* next_state = nullptr; const int32_t* order = nullptr; int32_t* next_rows = nullptr;
   int batch = 0, prepare_next = 0; float lr = 1e-3f;
+  int form = OPT_ADAM;          // the rule (OptForm; smx_set_optimizer): in the padding beside `params`, in a kernarg line every chunk body reads already
   float* params = nullptr; float* grads = nullptr; float* m = nullptr; float* v = nullptr;
   const OptChunk* chunks = nullptr; int n_chunks = 0;
   int n_launch = 0;             // workgroups of the optimiser launch: every chunk but [gap_from, gap_from + gap_len) (those rode along earlier)
@@ -270,10 +275,15 @@ struct AdamArgs {
   // data parallel, world > 1: the moving BatchNorm statistics take the all-reduced batch statistics (mean over the ranks)
   // in extra workgroups of the gradient-norm launch (it was a launch of its own)
   float* bn_moving = nullptr; const float* bn_batch = nullptr; int bn_total = 0; float bn_inv_world = 1.f, bn_momentum = 0.99f;
+  // the rule's other scalars: b1 is also RMSprop's rho, `momentum` SGD's / RMSprop's; t0: the step at which the rule's state began (opt_lr_t)
+  float momentum = 0.f; uint32_t t0 = 0;
 };
 int launch_adam(hipStream_t st, const AdamArgs& a);
 int launch_adam_sweep(hipStream_t st, const AdamArgs& a, int first, int count, int wgs);   // chunks [first, first + count) by `wgs` persistent workgroups
 int launch_grad_sqsum_range(hipStream_t st, const AdamArgs& a, int first, int count);   // a.partial[chunk] = the chunk's sum of squares, chunks [first, first + count)
+int opt_resolve(int rule, const float* hp, int n_hp, const float* adam_hp, float out[4]);   // smx_set_optimizer's hyper-parameters, defaults filled in
+void opt_scalars(int rule, const float hp[4], AdamArgs& a);   // form, b1, b2, eps, momentum of AdamArgs from a rule and its resolved hyper-parameters
+int launch_opt_fill(hipStream_t st, float* dst, long n, float value);   // dst[0 .. n) = value (the slots of a rule that starts fresh)
 
 struct BnBwdArgs {
   const float* dout = nullptr; int n_slabs = 1; long slab_stride = 0; int ld = 0;  // d loss / d out slabs
@@ -415,7 +425,8 @@ int launch_label_loss(hipStream_t st, const LabelArgs& a);
 // counter.  Eager mode runs it once per train_steps call (later steps are prepared by the optimiser
 // kernel of the step before); graph mode runs it as the first node of every step.
 int launch_step_begin(hipStream_t st, StepState* master, StepState* dst, const int32_t* order, int32_t* rows,
-                      int batch, int cursor_from_master, uint32_t cursor, float lr, float b1, float b2);
+                      int batch, int cursor_from_master, uint32_t cursor, float lr, float b1, float b2,
+                      int form = OPT_ADAM, uint32_t t0 = 0);
 
 
 

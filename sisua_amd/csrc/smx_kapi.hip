@@ -105,8 +105,9 @@ int smx_k_count_llk(int likelihood, int direct, const float* x, const float* pla
   return rc;
 }
 
-int smx_k_adam(int32_t n_tensors, const int32_t* sizes, float* params, const float* grads, float* mom, float* vel,
-               int32_t step, float lr, float beta1, float beta2, float eps, float clipnorm, float* norms) {
+// the optimiser launch over caller-given tensors under `rule` (resolved hyper-parameters hp[4]): smx_k_adam / smx_k_opt
+static int k_opt_launch(int rule, const float* hp, int32_t n_tensors, const int32_t* sizes, float* params, const float* grads, float* mom,
+                        float* vel, int32_t step, float lr, float clipnorm, float* norms) {
   SMX_REQUIRE(n_tensors > 0 && n_tensors <= SMX_MAX_TENSORS && sizes && params && grads && mom && vel && step >= 1, "bad arguments");
   // the model's own layout: every tensor padded to a multiple of 64 floats, 4096-float optimiser chunks
   std::vector<size_t> off((size_t)n_tensors), pad((size_t)n_tensors);
@@ -157,12 +158,13 @@ int smx_k_adam(int32_t n_tensors, const int32_t* sizes, float* params, const flo
   st3[2].next = (uint32_t)(step - 1);   // optimiser steps completed so far
   if (rc == SMX_OK && hipMemcpy(dSt, st3, sizeof(st3), hipMemcpyHostToDevice) != hipSuccess) rc = SMX_ERR_HIP;
   // the step's scalars exactly as a training step prepares them (bias-corrected step size on the device)
-  if (rc == SMX_OK) rc = launch_step_begin(nullptr, dSt + 2, dSt, nullptr, nullptr, 0, 0, 0u, lr, beta1, beta2);
+  AdamArgs a;
+  opt_scalars(rule, hp, a);   // (t0 = 0: the rule's count t is the step given)
+  if (rc == SMX_OK) rc = launch_step_begin(nullptr, dSt + 2, dSt, nullptr, nullptr, 0, 0, 0u, lr, a.b1, a.b2, a.form, 0u);
   if (rc == SMX_OK) {
-    AdamArgs a;
     a.params = dP; a.grads = dG; a.m = dM; a.v = dV; a.chunks = dCh; a.n_chunks = (int)chunks.size(); a.n_launch = a.n_chunks; a.gap_from = a.n_chunks; a.gap_len = 0;
     a.partial = dPart; a.tensor_norm = dNorm; a.use_sq = 0; a.state = dSt;
-    a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.clipnorm = clipnorm; a.grad_scale = 1.f; a.lr = lr;
+    a.clipnorm = clipnorm; a.grad_scale = 1.f; a.lr = lr;
     rc = launch_adam(nullptr, a);
   }
   if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_adam: device synchronize failed"); rc = SMX_ERR_HIP; }
@@ -172,6 +174,20 @@ int smx_k_adam(int32_t n_tensors, const int32_t* sizes, float* params, const flo
   if (rc == SMX_OK && norms && hipMemcpy(norms, dNorm, (size_t)n_tensors * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = SMX_ERR_HIP;
   hipFree(dP); hipFree(dG); hipFree(dM); hipFree(dV); hipFree(dPart); hipFree(dNorm); hipFree(dCh); hipFree(dSt);
   return rc;
+}
+
+int smx_k_adam(int32_t n_tensors, const int32_t* sizes, float* params, const float* grads, float* mom, float* vel,
+               int32_t step, float lr, float beta1, float beta2, float eps, float clipnorm, float* norms) {
+  const float hp[4] = {beta1, beta2, eps, 0.f};
+  return k_opt_launch(SMX_OPT_ADAM, hp, n_tensors, sizes, params, grads, mom, vel, step, lr, clipnorm, norms);
+}
+
+int smx_k_opt(int32_t rule, const float* hp, int32_t n_hp, int32_t n_tensors, const int32_t* sizes, float* params, const float* grads,
+              float* m, float* v, int32_t step, float lr, float clipnorm, float* norms) {
+  static const float adam_hp[3] = {0.9f, 0.999f, 1e-7f};
+  float res[4];
+  SMX_CHECK(opt_resolve(rule, hp, n_hp, adam_hp, res));
+  return k_opt_launch(rule, res, n_tensors, sizes, params, grads, m, v, step, lr, clipnorm, norms);
 }
 
 int smx_k_gemm(int transA, int transB, const float* A, const float* B, int32_t M, int32_t N, int32_t K, int32_t split_k,

@@ -212,6 +212,9 @@ struct smx_model {
   std::vector<TensorInfo> tensors;
   size_t flat_count = 0, tail_off_bn = 0, tail_off_metrics = 0, grads_count = 0;
   float *params = nullptr, *grads = nullptr, *adam_m = nullptr, *adam_v = nullptr;
+  // the optimiser rule (smx_set_optimizer): smx_optimizer, its hyper-parameters (defaults filled in; Adam's from the config) and t0 -- the
+  // model step at which the rule's state began.  adam_m / adam_v are the rule's slots 2 / 3.
+  int opt_rule = 0; float opt_hp[4] = {0.f, 0.f, 0.f, 0.f}; uint32_t opt_t0 = 0;
   std::vector<MlpLayer> enc, encl, dec;
   int t_latW = -1, t_latb = -1, t_latlW = -1, t_latlb = -1;
   int t_outW[3] = {-1, -1, -1}, t_outb[3] = {-1, -1, -1};

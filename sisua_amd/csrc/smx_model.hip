@@ -205,6 +205,34 @@ static int alloc_rows_into(smx_model* m, size_t R) {
   return SMX_OK;
 }
 
+// smx_set_optimizer's hyper-parameters with the defaults filled in (Adam's from `adam_hp`: the config's beta_1, beta_2, epsilon), checked
+int opt_resolve(int rule, const float* hp, int n_hp, const float* adam_hp, float out[4]) {
+  static const float defaults[5][4] = {{0.9f, 0.999f, 1e-7f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.9f, 0.f, 1e-7f, 0.f}, {0.1f, 1e-7f, 0.f, 0.f},
+                                       {0.9f, 0.999f, 1e-7f, 0.f}};
+  static const int counts[5] = {3, 2, 3, 2, 3};
+  SMX_REQUIRE(rule >= 0 && rule <= 4, "smx_set_optimizer: unknown rule (SMX_OPT_ADAM, SGD, RMSPROP, ADAGRAD, ADAMAX)");
+  SMX_REQUIRE(n_hp >= 0 && n_hp <= counts[rule] && (n_hp == 0 || hp), "smx_set_optimizer: too many hyper-parameters for the rule");
+  for (int i = 0; i < 4; ++i) out[i] = i < n_hp ? hp[i] : (rule == 0 && i < 3 ? adam_hp[i] : defaults[rule][i]);
+  for (int i = 0; i < counts[rule]; ++i) SMX_REQUIRE(std::isfinite(out[i]), "smx_set_optimizer: a hyper-parameter is not finite");
+  switch (rule) {
+    case 0: case 4: SMX_REQUIRE(out[0] >= 0.f && out[0] < 1.f && out[1] >= 0.f && out[1] < 1.f && out[2] >= 0.f, "smx_set_optimizer: beta_1, beta_2 in [0, 1), epsilon >= 0"); break;
+    case 1: SMX_REQUIRE(out[0] >= 0.f && (out[1] == 0.f || out[1] == 1.f), "smx_set_optimizer: sgd momentum >= 0, nesterov 0 or 1"); break;
+    case 2: SMX_REQUIRE(out[0] >= 0.f && out[0] <= 1.f && out[1] >= 0.f && out[2] >= 0.f, "smx_set_optimizer: rmsprop rho in [0, 1], momentum >= 0, epsilon >= 0"); break;
+    case 3: SMX_REQUIRE(out[0] >= 0.f && out[1] >= 0.f, "smx_set_optimizer: adagrad initial_accumulator_value >= 0, epsilon >= 0"); break;
+  }
+  return SMX_OK;
+}
+void opt_scalars(int rule, const float hp[4], AdamArgs& a) {
+  a.momentum = 0.f;
+  switch (rule) {
+    case 1: a.momentum = hp[0]; a.form = hp[0] == 0.f ? OPT_SGD : (hp[1] != 0.f ? OPT_SGD_NESTEROV : OPT_SGD_MOM); break;
+    case 2: a.b1 = hp[0]; a.momentum = hp[1]; a.eps = hp[2]; a.form = hp[1] == 0.f ? OPT_RMSPROP : OPT_RMSPROP_MOM; break;
+    case 3: a.eps = hp[1]; a.form = OPT_ADAGRAD; break;
+    case 4: a.b1 = hp[0]; a.b2 = hp[1]; a.eps = hp[2]; a.form = OPT_ADAMAX; break;
+    default: a.b1 = hp[0]; a.b2 = hp[1]; a.eps = hp[2]; a.form = OPT_ADAM; break;
+  }
+}
+
 // Every buffer with one row per row of a pass, for R rows: at model creation R = max_batch; smx_set_train_draws regrows them to
 // draws x max_batch (the stacked rows of a multi-draw step).  All or nothing: the new set is allocated beside the old one, which is
 // freed only when every allocation succeeded; on failure the model keeps its previous buffers and Rmax.  The caller has synchronised
@@ -343,6 +371,7 @@ int smx_model_create(const smx_config* cfg, smx_model** out) {
   SMX_HIP(hipGetDevice(&dev));
   smx_model* m = new smx_model();
   m->cfg = *cfg; m->device = dev;
+  m->opt_hp[0] = cfg->adam_beta1; m->opt_hp[1] = cfg->adam_beta2; m->opt_hp[2] = cfg->adam_eps;   // (SMX_OPT_ADAM, t0 = 0)
   m->G = cfg->n_genes; m->Gp = round_up(m->G, 32); m->D = cfg->latent_dim; m->Dp = round_up(m->D, 32);
   m->k = llk_planes(cfg->likelihood);
   m->stochastic = cfg->model != SMX_MODEL_DCA; m->scvi = cfg->model == SMX_MODEL_SCVI; m->scale = cfg->model == SMX_MODEL_SCALE || cfg->model == SMX_MODEL_SCALE_TRIL; m->scale_tril = cfg->model == SMX_MODEL_SCALE_TRIL;

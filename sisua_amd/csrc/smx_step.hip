@@ -254,7 +254,8 @@ void attach_early_adam(smx_model* m, BnBwdArgs& b) {
   }
   m->adam_early_pending = false;
   static const bool off = tuning_on("no_adam_early");
-  if (off || dp_active(m) || !m->sq_slots || m->chunk_first_head >= m->n_chunks || tuning_on("no_sq_partials")) return;
+  // (the riders carry Adam only -- smx_adam.h: SMX_OPT_SWITCH --: under another rule every chunk stays with the optimiser launch or the sweep)
+  if (off || m->opt_rule != SMX_OPT_ADAM || dp_active(m) || !m->sq_slots || m->chunk_first_head >= m->n_chunks || tuning_on("no_sq_partials")) return;
   for (size_t t = (size_t)m->t_outW[0]; t < m->tensors.size(); ++t)   // head tensors are the last ones of the manifest
     if (m->sq_count[t] == 0 && m->tensors[t].count > SMX_SQ_SMALL_TENSOR) return;
   // riders use half of a 512-thread BatchNorm workgroup: fine while the heads' update is a few MB (C2: 22 MB, hidden
@@ -1522,7 +1523,8 @@ void fill_adam_args(smx_model* m, AdamArgs& a) {
     if (m->sq_reduced[t]) { a.sq_first[t] = m->sq_total_first + (int)t * SMX_SQR_PER_TENSOR; a.sq_count[t] = m->sq_reduced[t]; }   // riders have summed the slots
   }
   a.sq_slots = m->sq_slots;
-  a.state = cur_state(m); a.b1 = c.adam_beta1; a.b2 = c.adam_beta2; a.eps = c.adam_eps; a.clipnorm = c.clipnorm;
+  a.state = cur_state(m); a.clipnorm = c.clipnorm;
+  opt_scalars(m->opt_rule, m->opt_hp, a); a.t0 = m->opt_t0;   // (the rule of smx_set_optimizer: Adam with the config's betas and epsilon unless set)
   // the likelihood / KL / label kernels already scale by 1 / (batch * world), so the SUM all-reduce leaves the
   // global-mean gradient: nothing more to divide by (it used to be divided by world once more here)
   a.grad_scale = 1.f;
@@ -1611,9 +1613,12 @@ int train_sequence(smx_model* m, int B, bool with_begin, bool begin_from_master,
   ps.draw_rows = m->train_draws > 1 ? B / m->train_draws : 0;   // (B: the stacked rows, draws x cells)
   m->seq_batch = B; m->seq_prepare_next = prepare_next ? 1 : 0;
   Timed t(m, "step");
-  if (with_begin)
+  if (with_begin) {
+    AdamArgs o;
+    opt_scalars(m->opt_rule, m->opt_hp, o);
     SMX_CHECK(launch_step_begin(m->st, master_state(m), cur_state(m), m->order, cur_rows(m), B, begin_from_master ? 1 : 0,
-                                cursor, m->cfg.lr, m->cfg.adam_beta1, m->cfg.adam_beta2));
+                                cursor, m->cfg.lr, o.b1, o.b2, o.form, m->opt_t0));
+  }
   m->chain_started = false;
   { Timed null_pair(m, "null"); }  // an event pair around nothing: the timing method's own overhead
   SMX_CHECK(csr_stage(m, ps));     // sparse store: this minibatch's rows as a dense tile (no-op otherwise)
@@ -1815,6 +1820,34 @@ int smx_set_train_draws(smx_model* m, int32_t n_draws) {
   if ((int64_t)n_draws * m->Bmax > m->Rmax) SMX_CHECK(smx::alloc_rows(m, (size_t)n_draws * m->Bmax));
   m->train_draws = n_draws;
   m->staged_steps = 0;
+  return SMX_OK;
+}
+
+int smx_set_optimizer(smx_model* m, int32_t rule, const float* hp, int32_t n_hp) {
+  SMX_REQUIRE(m, "null model");
+  const float adam_hp[3] = {m->cfg.adam_beta1, m->cfg.adam_beta2, m->cfg.adam_eps};
+  float res[4];
+  SMX_CHECK(smx::opt_resolve(rule, hp, n_hp, adam_hp, res));
+  SMX_CHECK(smx::head_sweep_join(m));
+  SMX_HIP(hipStreamSynchronize(m->st));
+  smx::drop_graphs(m);   // (a captured step bakes the rule and t0 into its launches' arguments)
+  // the rule starts fresh: both slot buffers whole (the SMX_SHARD_SLACK tail included), on every rank alike -- nothing is stale after this
+  const long n = (long)(m->flat_count + SMX_SHARD_SLACK);
+  SMX_CHECK(smx::launch_opt_fill(m->st, m->adam_m, n, 0.f));
+  SMX_CHECK(smx::launch_opt_fill(m->st, m->adam_v, n, rule == SMX_OPT_ADAGRAD ? res[0] : 0.f));
+  SMX_HIP(hipStreamSynchronize(m->st));
+  m->opt_stale = false;
+  m->opt_rule = rule;
+  for (int i = 0; i < 4; ++i) m->opt_hp[i] = res[i];
+  m->opt_t0 = m->h_next;
+  return SMX_OK;
+}
+
+int smx_get_optimizer(const smx_model* m, int32_t* rule, float* hp, int32_t* t0) {
+  SMX_REQUIRE(m, "null model");
+  if (rule) *rule = m->opt_rule;
+  if (hp) for (int i = 0; i < SMX_OPT_MAX_HP; ++i) hp[i] = m->opt_hp[i];
+  if (t0) *t0 = (int32_t)m->opt_t0;
   return SMX_OK;
 }
 

@@ -11,7 +11,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from sisua_amd import _hip
+from sisua_amd import _hip, optimizers
 from sisua_amd._hip import SmxError, check, smx_config, smx_metrics
 from sisua_amd.config import ModelConfig, init_params, label_planes, manifest
 
@@ -175,16 +175,62 @@ class Engine:
       check(self.lib.smx_set_bn(self._h, int(i), 1, _fp(_f32(st["moving_var"]))))
 
   def snapshot(self) -> dict:
-    """Everything a training step changes -- parameters, both Adam moments, the BatchNorm moving statistics, the step counter -- as host
-    arrays (what models.py keeps in a checkpoint; parallel.calibrate_forms restores it after its trial steps)."""
-    return dict(params=self.get_params(0), m=self.get_params(2), v=self.get_params(3), bn=self.get_bn(), step=self.step)
+    """Everything a training step changes -- parameters, both optimiser slots, the BatchNorm moving statistics, the step counter -- and
+    the optimiser rule as host values (what models.py keeps in a checkpoint; parallel.calibrate_forms restores it after its trial steps)."""
+    return dict(params=self.get_params(0), m=self.get_params(2), v=self.get_params(3), bn=self.get_bn(), step=self.step,
+                opt=self.get_optimizer())
 
   def restore(self, st: dict):
+    if st.get("opt") is not None:
+      self.restore_optimizer(*st["opt"])
     self.set_params(st["params"], 0)
     self.set_params(st["m"], 2)
     self.set_params(st["v"], 3)
     self.set_bn(st["bn"])
     self.step = int(st["step"])
+
+  # ---- optimiser rule -------------------------------------------------------------
+  def get_optimizer(self):
+    """(rule name, {hyper-parameter: value}, t0): the rule of the training steps and the step at which its state began."""
+    rule, t0 = C.c_int32(), C.c_int32()
+    hp = np.zeros(4, np.float32)
+    check(self.lib.smx_get_optimizer(self._h, C.byref(rule), _fp(hp), C.byref(t0)))
+    name = optimizers.NAMES[rule.value]
+    return name, optimizers.hp_dict(name, hp.astype(np.float64)), int(t0.value)
+
+  def set_optimizer(self, name: str = "adam", **hp) -> bool:
+    """The optimiser rule of the later training steps: 'adam', 'sgd' (momentum, nesterov), 'rmsprop' (rho, momentum, epsilon), 'adagrad'
+    (initial_accumulator_value, epsilon), 'adamax' (beta_1, beta_2, epsilon); tf.keras 2.x defaults (Adam's: the config's).  The same
+    rule with the same hyper-parameters again: nothing changes, the state continues.  Anything else starts the rule fresh, as a new
+    Keras optimiser object does -- slots initialised, t0 = the current step (smx_set_optimizer).  True when the rule started fresh."""
+    name, full = optimizers.canonical(name, **hp)
+    if name == "adam" and not hp:   # (Adam's defaults are the config's)
+      full = dict(beta_1=self.cfg.adam_beta1, beta_2=self.cfg.adam_beta2, epsilon=self.cfg.adam_eps)
+    cur = self.get_optimizer()
+    if optimizers.same_rule((name, full), cur[:2]):
+      return False
+    self._set_optimizer(name, full)
+    return True
+
+  def _set_optimizer(self, name, full):
+    v = optimizers.hp_vector(name, full)
+    check(self.lib.smx_set_optimizer(self._h, optimizers.RULES[name][0], _fp(v), len(v)))
+
+  def restore_optimizer(self, name: str, hp: Optional[dict], t0: int):
+    """Set the rule with its state beginning at step t0 (a checkpoint's entries; the slots are restored by the caller).  hp None: the
+    rule's defaults (a checkpoint from before the rules: Adam with the config's betas)."""
+    if name == "adam" and hp is None:
+      hp = dict(beta_1=self.cfg.adam_beta1, beta_2=self.cfg.adam_beta2, epsilon=self.cfg.adam_eps)
+    name, full = optimizers.canonical(name, **(hp or {}))
+    cur = self.get_optimizer()
+    if optimizers.same_rule((name, full), cur[:2]) and cur[2] == int(t0):
+      return
+    step = self.step
+    self.step = int(t0)   # (smx_set_optimizer records t0 = the step count at the call)
+    try:
+      self._set_optimizer(name, full)
+    finally:
+      self.step = step
 
   @property
   def step(self) -> int:
@@ -670,6 +716,24 @@ def k_adam(params, grads, m, v, step: int, lr=1e-3, beta1=0.9, beta2=0.999, eps=
   norms = np.empty(len(sizes), np.float32)
   check(lib.smx_k_adam(len(sizes), sizes.ctypes.data_as(C.POINTER(C.c_int32)), _fp(P), _fp(G), _fp(M), _fp(V), int(step),
                        float(lr), float(beta1), float(beta2), float(eps), float(clipnorm), _fp(norms)))
+  cut = np.cumsum(sizes)[:-1]
+  shp = [np.shape(p) for p in params]
+  un = lambda flat: [a.reshape(sh) for a, sh in zip(np.split(flat, cut), shp)]
+  return un(P), un(M), un(V), norms
+
+
+def k_opt(rule: str, params, grads, m, v, step: int, lr=1e-3, clipnorm=100.0, **hp):
+  """The optimiser launch by itself under any rule of Engine.set_optimizer (smx_k_opt); m / v are the rule's slots 2 / 3.  Updated copies
+  are returned: (params, m, v, norms)."""
+  lib = _hip.require_gpu()
+  name, full = optimizers.canonical(rule, **hp)
+  hv = optimizers.hp_vector(name, full)
+  sizes = np.array([int(np.size(p)) for p in params], dtype=np.int32)
+  cat = lambda xs: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).ravel() for x in xs]))
+  P, G, M, V = cat(params), cat(grads), cat(m), cat(v)
+  norms = np.empty(len(sizes), np.float32)
+  check(lib.smx_k_opt(optimizers.RULES[name][0], _fp(hv), len(hv), len(sizes), sizes.ctypes.data_as(C.POINTER(C.c_int32)), _fp(P), _fp(G),
+                      _fp(M), _fp(V), int(step), float(lr), float(clipnorm), _fp(norms)))
   cut = np.cumsum(sizes)[:-1]
   shp = [np.shape(p) for p in params]
   un = lambda flat: [a.reshape(sh) for a, sh in zip(np.split(flat, cut), shp)]

@@ -21,6 +21,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from sisua_amd import distributions as D
+from sisua_amd import optimizers
 from sisua_amd.config import ModelConfig, NetConf, RVmeta, init_params
 from sisua_amd.data import BatchDataset, SingleCellOMIC, as_csr, is_sparse, library_matrix
 from sisua_amd.engine import Engine
@@ -207,11 +208,14 @@ class SingleCellModel:
 
   def _get_state(self):
     e = self._engine
-    return dict(params=e.get_params(0), m=e.get_params(2), v=e.get_params(3), bn=e.get_bn(), step=e.step)
+    return dict(params=e.get_params(0), m=e.get_params(2), v=e.get_params(3), bn=e.get_bn(), step=e.step, opt=e.get_optimizer())
 
   def _set_state(self, st):
     e = self._engine
     self._param_version = getattr(self, "_param_version", 0) + 1   # (lazy prediction handles are keyed by it: distributions.LazyCountOutput)
+    if st.get("opt") is not None:   # (the rule first: setting it initialises the slots restored below)
+      e.restore_optimizer(*st["opt"])
+      self._opt_rule = optimizers.canonical(st["opt"][0], **(st["opt"][1] or {}))
     e.set_params(st["params"], 0)
     e.set_params(st["m"], 2)
     e.set_params(st["v"], 3)
@@ -348,8 +352,9 @@ class SingleCellModel:
     `storage`: how the counts are resident ('f32', 'u16', 'csr'; Engine.upload).  Default: 'csr' for sparse counts (a sparse
     SingleCellOMIC / BatchDataset), whose rows reach the device as CSR without a dense host matrix, unless the model has input dropout
     (keyed by the dense store's rows); 'f32' otherwise.  'f32' / 'u16' of sparse counts are expanded on the device block by block."""
-    if str(optimizer).lower() != "adam":
-      raise ValueError("only the 'adam' optimizer of configs/base.yaml is built")
+    # the rule (sisua_amd.optimizers; ValueError for one that is not built, before any device work): a name or the Keras registry's dict
+    # form, whose learning_rate / clipnorm override fit's own
+    opt_name, opt_hp, learning_rate, clipnorm = optimizers.resolve(optimizer, learning_rate, clipnorm)
     n_draws = train_draws(sample_shape)
     if n_draws > 1 and self._make_config().model == "fvae":
       raise ValueError(f"{type(self).__name__}: sample_shape {sample_shape!r} -- FactorVAE / SemiFVAE train with one draw per cell "
@@ -383,6 +388,9 @@ class SingleCellModel:
       cp = cp or ControlPlane(rank, world)
     e = self._ensure_engine(max(B, valid.batch_size if valid is not None else 1))
     e.set_train_draws(n_draws)
+    if (opt_name, opt_hp) != optimizers.canonical("adam") or getattr(self, "_opt_rule", None) not in (None, optimizers.canonical("adam")):
+      e.set_optimizer(opt_name, **opt_hp)   # (the same rule again: the state continues; another one starts fresh at this step)
+    self._opt_rule = (opt_name, opt_hp)
     if world > 1 and e.world != world:
       self._dp_mode = attach_engine(e, cp)
       self._dp_calibrated = False
@@ -917,6 +925,7 @@ class SingleCellModel:
     for i, b in st["bn"].items():
       flat[f"bn/{i}/moving_mean"], flat[f"bn/{i}/moving_var"] = b["moving_mean"], b["moving_var"]
     flat["step"] = np.array(st["step"], dtype=np.int64)
+    flat.update(optimizers.to_npz(*st["opt"]))   # the rule, its hyper-parameters and t0 (m/ and v/ hold its slots 2 / 3)
     d = os.path.dirname(os.path.abspath(filepath))
     os.makedirs(d, exist_ok=True)
     tmp = f"{filepath}.tmp{os.getpid()}"
@@ -944,7 +953,8 @@ class SingleCellModel:
         bn.setdefault(int(i), {})[nm] = z[k]
     self._set_state(dict(params={k[2:]: z[k] for k in z.files if k.startswith("p/")},
                          m={k[2:]: z[k] for k in z.files if k.startswith("m/")},
-                         v={k[2:]: z[k] for k in z.files if k.startswith("v/")}, bn=bn, step=int(z["step"])))
+                         v={k[2:]: z[k] for k in z.files if k.startswith("v/")}, bn=bn, step=int(z["step"]),
+                         opt=optimizers.from_npz(z)))   # (a checkpoint without the optimiser's entries: Adam)
     metamodel_path = f"{filepath}.metamodel"
     if os.path.exists(metamodel_path):
       class_name, dataset, metadata, kwargs = read_metamodel(metamodel_path)
