@@ -68,8 +68,13 @@ typedef enum { SMX_LLK_NB = 0, SMX_LLK_ZINB = 1, SMX_LLK_NBD = 2, SMX_LLK_ZINBD 
 /* SMX_LABEL_NBD / ZINB / ZINBD: the remaining count posteriors of RVmeta as heads (vae.py:30 "'onehot'/'nbd'/'nb'"; the second OUTPUT of
  * tests/test_singlecell_models.py:133-134 is 'nbd'): planes as for the gene output -- (mean, dispersion) through softplus / softplus1,
  * (log total_count, logits, gate logits), (mean, dispersion, gate logits). */
+/* SMX_LABEL_BERNOULLI ('bernoulli'): every label dimension its own binary variable (binarised protein markers, multi-label), ONE
+ * plane of logits l: log p(y) = y l - softplus(l), defined for any y in [0, 1] (a probability matrix trains too).
+ * SMX_LABEL_NORMAL ('normal' / 'gaussian' / 'diag'): an independent normal per label dimension, TWO planes -- loc m | raw scale s,
+ * sigma = softplus(s + softplus^-1(1)) ([3P-recall] odin's softplus1: the scale activation of the latents and of SMX_LABEL_MIXGAUSS's
+ * components). */
 typedef enum { SMX_LABEL_NB = 0, SMX_LABEL_ONEHOT = 1, SMX_LABEL_MIXNB = 2, SMX_LABEL_MIXGAUSS = 3, SMX_LABEL_MIXTRIL = 4, SMX_LABEL_MIXZINB = 5,
-               SMX_LABEL_NBD = 6, SMX_LABEL_ZINB = 7, SMX_LABEL_ZINBD = 8 } smx_label_likelihood;
+               SMX_LABEL_NBD = 6, SMX_LABEL_ZINB = 7, SMX_LABEL_ZINBD = 8, SMX_LABEL_BERNOULLI = 9, SMX_LABEL_NORMAL = 10 } smx_label_likelihood;
 typedef enum { SMX_ACT_RELU = 0, SMX_ACT_LINEAR = 1 } smx_activation;
 /* Optimiser rules (smx_set_optimizer; tf.keras 2.x Adam, SGD, RMSprop, Adagrad, Adamax). */
 typedef enum { SMX_OPT_ADAM = 0, SMX_OPT_SGD = 1, SMX_OPT_RMSPROP = 2, SMX_OPT_ADAGRAD = 3, SMX_OPT_ADAMAX = 4 } smx_optimizer;

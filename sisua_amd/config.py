@@ -16,6 +16,9 @@ import numpy as np
 SOFTPLUS_INV_1 = float(np.log(np.expm1(1.0)))   # softplus(SOFTPLUS_INV_1) == 1
 LIKELIHOODS = ("nb", "zinb", "nbd", "zinbd")
 OUTPUT_POSTERIORS = LIKELIHOODS + ("mse",)   # 'mse': deterministic output, -log_prob(x) = mean squared error (tests/test_singlecell_models.py:82-91)
+# head kinds on the decoder output (label variables and outputs[1:]); the mixtures carry their component count: 'mixnb2' .. 'mixtril4'
+HEAD_KINDS = ("nb", "nbd", "zinb", "zinbd", "onehot", "bernoulli", "normal")
+MIXTURE_HEAD_KINDS = ("mixnb", "mixgauss", "mixtril", "mixzinb")
 
 
 def label_planes(llk: str, P: int = 0) -> int:
@@ -24,7 +27,10 @@ def label_planes(llk: str, P: int = 0) -> int:
   logits, C locations, C raw scales: its mixture-of-Gaussians labels for continuous variables, vae.py:86-92), 'mixtrilC'
   C (2 + P) (the docstring example of vae.py:58: C full-covariance Gaussians over the whole label vector -- C planes whose
   first column is a component's mixture logit, C planes of locations, per component P planes = the columns of its
-  lower-triangular scale factor; the other entries are inert)."""
+  lower-triangular scale factor; the other entries are inert); 'bernoulli' 1 (logits: every dimension its own binary variable),
+  'normal' 2 (locations, raw scales: an independent normal per dimension, scale softplus(raw + softplus^-1(1)))."""
+  if llk in ("bernoulli", "normal"):
+    return 1 if llk == "bernoulli" else 2
   if llk.startswith("mixtril"):
     if P <= 0:
       raise ValueError("label_planes('mixtrilC') needs the label dimension")
@@ -139,6 +145,11 @@ class ModelConfig:
   disc_layers: int = 5
   gamma: float = 6.0
   disc_leak: float = 0.2
+
+  def __post_init__(self):
+    for P, kind in tuple(self.extra_outputs) + tuple(self.labels):
+      if not (kind in HEAD_KINDS or (kind[:-1] in MIXTURE_HEAD_KINDS and kind[-1] in "234")):
+        raise ValueError(f"unknown head kind {kind!r} (built: {', '.join(HEAD_KINDS)}, and the mixtures {', '.join(k + 'C' for k in MIXTURE_HEAD_KINDS)} with C = 2..4)")
 
   @property
   def k(self) -> int:

@@ -1,7 +1,7 @@
 // smx_loss.hip -- the count likelihoods over smx_loss.h's elementwise terms (gfx950):
 //  count_loss  NB / ZINB / NBD / ZINBD log-likelihood, forward + gradient wrt the parameter planes, one pass over B x G
 //              (the bandwidth-bound kernel the roofline is quoted on: SURVEY.md 8d, rows a-10/a-11)
-//  label_loss  the masked NB / one-hot label heads of SISUA (a-13) and the mixture (tril) label head
+//  label_loss  the masked NB / one-hot label heads of SISUA (a-13), the Bernoulli / normal heads and the mixture (tril) label head
 // One unit for both: count_loss calls count_elem only on its diagnostic path (likelihood -2), with x = 0.  Without the label heads'
 // calls beside it the compiler specialises count_elem<ZINB / ZINBD> to that constant, and all 24 ZINB / ZINBD count_loss kernels change.
 #include "smx_internal.h"
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void label_loss_kernel(LabelArgs a) {
   float llk = 0.f;
   if (m == 0.f) {   // wave-uniform
     if (a.backward) {
-      const int width = ((a.kind == SMX_LABEL_NB || a.kind == SMX_LABEL_NBD) ? 2 : (a.kind == SMX_LABEL_ZINB || a.kind == SMX_LABEL_ZINBD) ? 3 :
+      const int width = ((a.kind == SMX_LABEL_NB || a.kind == SMX_LABEL_NBD || a.kind == SMX_LABEL_NORMAL) ? 2 : (a.kind == SMX_LABEL_ZINB || a.kind == SMX_LABEL_ZINBD) ? 3 :
                          (a.kind == SMX_LABEL_MIXNB || a.kind == SMX_LABEL_MIXGAUSS) ? 3 * a.C : a.kind == SMX_LABEL_MIXZINB ? 4 * a.C : 1) * a.Pp;
       for (int p = lane; p < width; p += 64) a.draw[(long)b * a.ld + p] = 0.f;
     }
@@ -240,6 +240,36 @@ __global__ __launch_bounds__(256) void label_loss_kernel(LabelArgs a) {
         a.draw[(long)b * a.ld + p] = d0 * gs; a.draw[(long)b * a.ld + a.Pp + p] = d1 * gs;
         if (zi) a.draw[(long)b * a.ld + 2 * a.Pp + p] = d2 * gs;
       }
+    }
+    llk = wave_sum(llk);
+  } else if (a.kind == SMX_LABEL_BERNOULLI) {
+    // every label dimension its own binary variable, one plane of logits l (TFP Bernoulli.log_prob, any y in [0, 1]):
+    // log p(y) = y l - softplus(l), d / d l = y - sigmoid(l); softplus and sigmoid from one exp(-|l|): no overflow at saturation
+    for (int p = lane; p < a.Pp; p += 64) {
+      float d = 0.f;
+      if (p < a.P) {
+        const float l = raw[p];
+        const SpSg s = softplus_sigmoid(l);
+        llk += y[p] * l - s.sp;
+        d = y[p] - s.sg;
+      }
+      if (a.backward) a.draw[(long)b * a.ld + p] = d * gs;
+    }
+    llk = wave_sum(llk);
+  } else if (a.kind == SMX_LABEL_NORMAL) {
+    // an independent normal per label dimension, planes loc m | raw scale s, sigma = softplus(s + softplus^-1(1)) ([3P-recall] odin's
+    // 'softplus1', the scale activation of the latents and of one 'mixgaussian' component above):
+    // log p(y) = -z^2 / 2 - log sigma - log(2 pi) / 2, z = (y - m) / sigma; d m = z / sigma, d s = (z^2 - 1) / sigma * sigmoid(s + softplus^-1(1))
+    for (int p = lane; p < a.Pp; p += 64) {
+      float d0 = 0.f, d1 = 0.f;
+      if (p < a.P) {
+        const SpSg s = softplus_sigmoid(raw[a.Pp + p] + SMX_SOFTPLUS_INV_1);   // sp = sigma, sg = d sigma / d s
+        const float inv = frcp(s.sp), zz = (y[p] - raw[p]) * inv;
+        llk += -0.5f * zz * zz - flog(s.sp) - 0.9189385332046727f;   // 0.5 log(2 pi)
+        d0 = zz * inv;
+        d1 = (zz * zz - 1.f) * inv * s.sg;
+      }
+      if (a.backward) { a.draw[(long)b * a.ld + p] = d0 * gs; a.draw[(long)b * a.ld + a.Pp + p] = d1 * gs; }
     }
     llk = wave_sum(llk);
   } else {

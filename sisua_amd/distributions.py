@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 import scipy.sparse as _sp
-from scipy.special import gammaln
+from scipy.special import expit, gammaln
 
 SOFTPLUS_INV_1 = float(np.log(np.expm1(1.0)))
 
@@ -271,6 +271,38 @@ class OneHotCategorical(Distribution):
     return np.eye(p.shape[-1], dtype=np.float32)[idx]
 
 
+class Bernoulli(Distribution):
+  """Independent binary variables from logits (the 'bernoulli' head: binarised protein markers, several per cell at once).
+  TFP Bernoulli semantics: log_prob(y) = y logits - softplus(logits), defined for any y in [0, 1], so a probability matrix
+  scores too; sample() draws float 0 / 1."""
+
+  def __init__(self, logits, name="Bernoulli"):
+    self.logits, self.name = np.asarray(logits), name
+
+  def _params(self):
+    return [self.logits]
+
+  @property
+  def probs(self):
+    return expit(self.logits.astype(np.float64))
+
+  def mean(self):
+    return self.probs
+
+  def variance(self):
+    p = self.probs
+    return p * (1 - p)
+
+  def log_prob(self, x):
+    l = self.logits.astype(np.float64)
+    return np.asarray(x, np.float64) * l - _softplus(l)
+
+  def sample(self, sample_shape=(), seed=None):
+    rng = np.random.default_rng(seed)
+    p = self.probs
+    return (rng.uniform(size=self._sshape(sample_shape) + p.shape) < p).astype(np.float32)
+
+
 class MixtureNegativeBinomial(Distribution):
   """Per-dimension mixture of C negative binomials (MISA's label heads, sisua/models/vae.py:47-98; TFP
   MixtureSameFamily(Categorical(logits), NegativeBinomial) semantics).  Parameters [..., C, P]: mixture logits, total
@@ -447,6 +479,8 @@ def concat_distributions(dists: Sequence[Distribution], axis: int = 0, name: Opt
     return NegativeBinomialDisp(_cat([d.loc for d in dists], axis), _cat([d.disp for d in dists], axis), name=nm)
   if isinstance(d0, OneHotCategorical):
     return OneHotCategorical(_cat([d.logits for d in dists], axis), name=nm)
+  if isinstance(d0, Bernoulli):
+    return Bernoulli(_cat([d.logits for d in dists], axis), name=nm)
   if isinstance(d0, MixtureNormal):
     return MixtureNormal(_cat([d.mix_logits for d in dists], axis), _cat([d.components.loc for d in dists], axis),
                          _cat([d.components.scale for d in dists], axis), name=nm)

@@ -87,9 +87,13 @@ def _to_data(x, batch_size=64) -> BatchDataset:
 
 def _head_kind(rv: RVmeta, what: str):
   """(dim, kind) of a head on the decoder output for a label variable (`labels=`) or a further output variable (`outputs[1:]`):
-  the count posteriors of RVmeta ('nb' / 'nbd' / 'zinb' / 'zinbd', vae.py:30), 'onehot', and MISA's mixtures."""
-  if rv.posterior in ("nb", "nbd", "zinb", "zinbd"):
+  the count posteriors of RVmeta ('nb' / 'nbd' / 'zinb' / 'zinbd', vae.py:30), 'onehot', 'bernoulli' (every dimension its own binary
+  variable: binarised markers, multi-label), 'normal' / 'gaussian' / 'diag' (an independent normal per dimension, scale through
+  [3P-recall] odin's softplus1), and MISA's mixtures."""
+  if rv.posterior in ("nb", "nbd", "zinb", "zinbd", "bernoulli"):
     return (rv.event_shape, rv.posterior)
+  if rv.posterior in ("normal", "gaussian", "diag"):
+    return (rv.event_shape, "normal")
   if rv.posterior in ("onehot", "categorical"):
     return (rv.event_shape, "onehot")
   if rv.posterior in ("mixnb", "mixnbd", "mixzinb", "mixzinbd"):     # MISA (vae.py:47-98): mixture of negative binomials per label dimension
@@ -110,7 +114,7 @@ def _head_kind(rv: RVmeta, what: str):
     if cov in ("none", "diag"):
       return (rv.event_shape, f"mixgauss{C}")
     raise ValueError(f"mixture-of-Gaussians label heads are built with covariance 'none' / 'diag' (independent dimensions) or 'tril' / 'full', given: {cov}")
-  raise ValueError(f"{what} posterior '{rv.posterior}' is not built (supported: 'nb', 'nbd', 'zinb', 'zinbd', 'onehot', 'mixnb', 'mixgaussian', 'mixtril')")
+  raise ValueError(f"{what} posterior '{rv.posterior}' is not built (supported: 'nb', 'nbd', 'zinb', 'zinbd', 'onehot', 'bernoulli', 'normal' / 'gaussian' / 'diag', 'mixnb', 'mixgaussian', 'mixtril')")
 
 
 class _Layer:
@@ -612,9 +616,15 @@ class SingleCellModel:
     n_extra = len(cfg.extra_outputs)
     for j, (P, kind) in enumerate(cfg.head_labels):
       raw = yp_list[j] if stacked else stack([yp[j] for yp in yp_list])
-      nm = (self._outputs[1 + j].name or f"output{1 + j}") if j < n_extra else (self._labels[j - n_extra].name or f"label{j - n_extra}")
+      rv = self._outputs[1 + j] if j < n_extra else self._labels[j - n_extra]
+      nm = rv.name or (f"output{1 + j}" if j < n_extra else f"label{j - n_extra}")
       if kind in ("nb", "nbd", "zinb", "zinbd"):   # planes of width P, as for the gene output
         outs.append(D.count_distribution(kind, [raw[..., c * P:(c + 1) * P] for c in range(3 if kind[0] == "z" else 2)], nm, activated=False))
+      elif kind == "bernoulli":
+        outs.append(D.Independent(D.Bernoulli(logits=raw), 1, name=nm))
+      elif kind == "normal":   # planes: locations | raw scales; scale = softplus1(raw)
+        loc, scale = raw[..., :P], np.logaddexp(0.0, raw[..., P:].astype(np.float64) + np.log(np.expm1(1.0)))
+        outs.append(D.MultivariateNormalDiag(loc, scale, name=nm) if rv.posterior == "diag" else D.Independent(D.Normal(loc, scale), 1, name=nm))
       elif kind.startswith("mixnb"):
         C = int(kind[-1])
         pl = np.reshape(raw, raw.shape[:-1] + (3 * C, P))     # planes: C mixture logits | C log total_counts | C logits
