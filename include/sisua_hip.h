@@ -79,6 +79,22 @@ typedef enum { SMX_ACT_RELU = 0, SMX_ACT_LINEAR = 1 } smx_activation;
 /* Optimiser rules (smx_set_optimizer; tf.keras 2.x Adam, SGD, RMSprop, Adagrad, Adamax). */
 typedef enum { SMX_OPT_ADAM = 0, SMX_OPT_SGD = 1, SMX_OPT_RMSPROP = 2, SMX_OPT_ADAGRAD = 3, SMX_OPT_ADAMAX = 4 } smx_optimizer;
 #define SMX_OPT_MAX_HP 4
+/* Step-dependent weights (smx_set_schedule): the target, and the kind of schedule with its parameters in this order.
+ *   interpolations of the KL weight ([3P-recall] odin's `interpolation`, re-exported by the reference), keyed by the model's step:
+ *     SMX_SCHED_CONST         vmax
+ *     SMX_SCHED_LINEAR        vmin, vmax, norm, cyclical (0 / 1), delayIn, delayOut
+ *     SMX_SCHED_POWER         vmin, vmax, norm, cyclical, delayIn, delayOut, power
+ *     SMX_SCHED_COSINE        vmin, vmax, norm, cyclical, delayIn, delayOut
+ *   tf.keras 2.x learning-rate schedules, keyed by the optimiser's own count step - t0 (smx_get_optimizer):
+ *     SMX_SCHED_EXP_DECAY     initial_learning_rate, decay_steps, decay_rate, staircase (0 / 1)
+ *     SMX_SCHED_INVTIME_DECAY initial_learning_rate, decay_steps, decay_rate, staircase (0 / 1)
+ *     SMX_SCHED_PIECEWISE     boundaries[k], values[k + 1]  (n = 2 k + 1)
+ *     SMX_SCHED_POLY_DECAY    initial_learning_rate, decay_steps, end_learning_rate, power, cycle (0 / 1)
+ *     SMX_SCHED_COSINE_DECAY  initial_learning_rate, decay_steps, alpha
+ * Either kind may serve either target. */
+typedef enum { SMX_SCHED_BETA = 0, SMX_SCHED_LR = 1 } smx_schedule_target;
+typedef enum { SMX_SCHED_CONST = 0, SMX_SCHED_LINEAR = 1, SMX_SCHED_POWER = 2, SMX_SCHED_COSINE = 3, SMX_SCHED_EXP_DECAY = 4,
+               SMX_SCHED_INVTIME_DECAY = 5, SMX_SCHED_PIECEWISE = 6, SMX_SCHED_POLY_DECAY = 7, SMX_SCHED_COSINE_DECAY = 8 } smx_schedule_kind;
 
 /* Constructor arguments of SingleCellModel / SCVI / SISUA / DeepCountAutoencoder
  * (single_cell_model.py:74-97, scvi.py:33-48, vae.py:40-44, dca.py:16-28) plus
@@ -278,6 +294,19 @@ int smx_set_train_draws(smx_model* m, int32_t n_draws);
 int smx_set_optimizer(smx_model* m, int32_t rule, const float* hp, int32_t n_hp);
 /* The rule in force, its SMX_OPT_MAX_HP hyper-parameters (defaults filled in, unused entries 0) and t0; any output may be NULL. */
 int smx_get_optimizer(const smx_model* m, int32_t* rule, float* hp, int32_t* t0);
+/* The schedule of a step-dependent weight: target = smx_schedule_target, kind = smx_schedule_kind, params[n] as listed there.  The
+ * default is SMX_SCHED_CONST at smx_config.beta / .lr.  The schedule is evaluated on the host in double and rounded once to float: each
+ * smx_train_steps / smx_train_stage call uploads the (beta, lr) of its steps as a table beside the row ids, and every step -- eager or
+ * a replayed graph -- reads its own entry on the device (StepState).  Eval passes (smx_eval_step) take beta at the model's step.
+ * Learning rate: the rule's step size is taken from the scheduled value at step - t0.  Captured graphs stay valid.  SMX_ERR_INVALID for an
+ * unknown target or kind, a wrong n, norm / decay_steps <= 0, negative delays, boundaries that do not increase, non-finite values. */
+int smx_set_schedule(smx_model* m, int32_t target, int32_t kind, const double* params, int32_t n);
+/* The schedule in force: kind, and its parameters into params[cap] (may be NULL); *n = their count (a piecewise schedule may hold more
+ * than cap: *n tells). */
+int smx_get_schedule(const smx_model* m, int32_t target, int32_t* kind, double* params, int32_t cap, int32_t* n);
+/* Host evaluation of a schedule without a model or a device: out[i] = the float value at step first_step + i, i < count -- exactly what a
+ * training step's table holds.  SMX_ERR_INVALID as smx_set_schedule. */
+int smx_schedule_eval(int32_t kind, const double* params, int32_t n, int64_t first_step, int32_t count, float* out);
 
 /* Eval-mode forward for predict/encode/decode (single_cell_model.py:119-211):
  * writes distribution parameters into caller-owned buffers (any may be NULL).

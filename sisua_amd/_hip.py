@@ -98,6 +98,9 @@ SIGNATURES = {
     "smx_eval_step": (C.c_int, [_VP, _IP, C.c_int32, C.POINTER(smx_metrics)]),
     "smx_set_train_draws": (C.c_int, [_VP, C.c_int32]),
     "smx_set_optimizer": (C.c_int, [_VP, C.c_int32, _FP, C.c_int32]),
+    "smx_set_schedule": (C.c_int, [_VP, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32]),
+    "smx_get_schedule": (C.c_int, [_VP, C.c_int32, _IP, C.POINTER(C.c_double), C.c_int32, _IP]),
+    "smx_schedule_eval": (C.c_int, [C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int64, C.c_int32, _FP]),
     "smx_get_optimizer": (C.c_int, [_VP, _IP, _FP, _IP]),
     "smx_forward": (C.c_int, [_VP, _IP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
                               C.POINTER(_FP)]),

@@ -327,7 +327,8 @@ __device__ inline void metrics_body(const MetricsArgs& a) {
     st = a.tc ? tot(4) : st; sd = a.tc ? tot(5) : sd; so = a.llk_o ? tot(6) : so;
     const float s = a.inv_global_batch;
     float o[8];
-    o[0] = (a.gamma * st - (sx + so + a.alpha * sy - a.beta * (sk + sl))) * s;
+    const float beta = a.beta_ptr ? *a.beta_ptr : a.beta;
+    o[0] = (a.gamma * st - (sx + so + a.alpha * sy - beta * (sk + sl))) * s;
     o[1] = -sx * s;
     o[2] = -sy * s;
     o[3] = sk * s;

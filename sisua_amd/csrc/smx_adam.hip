@@ -22,23 +22,27 @@ __device__ inline float opt_lr_t(int form, float lr, float b1, float b2, uint32_
 }
 
 __global__ void step_begin_kernel(StepState* master, StepState* dst, const int32_t* order, int32_t* rows, int batch,
-                                  int cursor_from_master, uint32_t cursor, float lr, float b1, float b2, int form, uint32_t t0) {
+                                  int cursor_from_master, uint32_t cursor, const float2* sched, float b1, float b2, int form, uint32_t t0) {
   const uint32_t cur = cursor_from_master ? master->cursor : cursor;
   if (order)
     for (int i = threadIdx.x; i < batch; i += blockDim.x) rows[i] = order[(long)cur * batch + i];
   __syncthreads();
   if (threadIdx.x == 0) {
     const uint32_t step = master->next;
+    const float2 w = sched[cur];   // (beta, lr) of this step (smx_set_schedule)
     dst->step = step;
     dst->cursor = cur;
-    dst->lr_t = opt_lr_t(form, lr, b1, b2, step, t0);
+    dst->beta = w.x;
+    dst->lr = w.y;
+    dst->lr_t = opt_lr_t(form, w.y, b1, b2, step, t0);
     if (cursor_from_master) master->cursor = cur + 1;
   }
 }
 int launch_step_begin(hipStream_t st, StepState* master, StepState* dst, const int32_t* order, int32_t* rows,
-                      int batch, int cursor_from_master, uint32_t cursor, float lr, float b1, float b2, int form, uint32_t t0) {
+                      int batch, int cursor_from_master, uint32_t cursor, const float2* sched, float b1, float b2, int form, uint32_t t0) {
+  if (!sched) { set_error("step_begin: no schedule table"); return SMX_ERR_INVALID; }
   hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(256), 0, st, master, dst, order, rows, batch, cursor_from_master,
-                     cursor, lr, b1, b2, form, t0);
+                     cursor, sched, b1, b2, form, t0);
   SMX_HIP(hipGetLastError());
   return SMX_OK;
 }
@@ -89,6 +93,7 @@ __global__ __launch_bounds__(256) void adam_update_kernel(AdamArgs a) {
   if (a.master) {
     const uint32_t step = a.state->step, cur = a.state->cursor;
     if (a.hist_dp && threadIdx.x < 8) a.hist_dp[(long)cur * 8 + threadIdx.x] = a.tail_metrics[threadIdx.x];
+    const float2 w = a.prepare_next && threadIdx.x == 0 ? a.sched[cur + 1] : make_float2(0.f, 0.f);   // (beta, lr) of the next step, requested by cursor beside its row ids
     if (a.prepare_next)
       for (int i = threadIdx.x; i < a.batch; i += 256) a.next_rows[i] = a.order[(long)(cur + 1) * a.batch + i];
     if (threadIdx.x == 0) {
@@ -96,7 +101,9 @@ __global__ __launch_bounds__(256) void adam_update_kernel(AdamArgs a) {
       if (a.prepare_next) {
         a.next_state->step = step + 1;
         a.next_state->cursor = cur + 1;
-        a.next_state->lr_t = opt_lr_t(ALL ? a.form : (int)OPT_ADAM, a.lr, a.b1, a.b2, step + 1, a.t0);
+        a.next_state->beta = w.x;
+        a.next_state->lr = w.y;
+        a.next_state->lr_t = opt_lr_t(ALL ? a.form : (int)OPT_ADAM, w.y, a.b1, a.b2, step + 1, a.t0);
       }
     }
   }

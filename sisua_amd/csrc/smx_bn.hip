@@ -522,6 +522,7 @@ __device__ inline void fold_dz_tile(const BnBwdArgs& a, const int bid, float* ti
   // (1) what the latent backward reads at the accumulators' positions -- cell 16 w + 4 kg + r, latent dim 16 nb + li -- requested first (64-byte runs per
   // 16 lanes; the same unconditional loads from clamped rows as gemm_body's EPI = 2)
   float e_mu[2][4], e_sr[2][4], e_sg[2][4], e_ep[2][4];
+  const float kls = kl_scale_of(e.klw);   // (the step's KL weight, requested with them)
 #pragma unroll
   for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
@@ -578,8 +579,8 @@ __device__ inline void fold_dz_tile(const BnBwdArgs& a, const int bid, float* ti
       const int b = 16 * w + 4 * kg + r, d = 16 * nb + li;
       const bool live = d < e.D;
       const float dz = acc[nb][r];
-      const float o0 = live ? dz + e.kl_scale * e_mu[nb][r] : 0.f;
-      const float o1 = live ? (dz * e_ep[nb][r] + e.kl_scale * (e_sg[nb][r] - frcp(e_sg[nb][r]))) * sigmoidf(e_sr[nb][r] + SMX_SOFTPLUS_INV_1) : 0.f;
+      const float o0 = live ? dz + kls * e_mu[nb][r] : 0.f;
+      const float o1 = live ? (dz * e_ep[nb][r] + kls * (e_sg[nb][r] - frcp(e_sg[nb][r]))) * sigmoidf(e_sr[nb][r] + SMX_SOFTPLUS_INV_1) : 0.f;
       if (b < a.B) {
         tile[b * ldd + d] = o0;
         tile[b * ldd + e.Dp + d] = o1;

@@ -40,6 +40,21 @@ struct NoiseKey {
   uint32_t draw_rows;        // rows per Monte-Carlo draw of a stacked pass (row r is draw r / draw_rows); 0: one draw
 };
 
+// The KL weight of a launch, beta * scale (div != 0: beta / scale -- each site keeps the expression it had as a baked scalar).  Training
+// steps read beta from the step's state (beta_ptr = &StepState::beta, written by step_begin / the optimiser's closing workgroup from the
+// schedule table of smx_set_schedule), so a captured graph replays every step's own weight; eval passes give it by value (the NoiseKey
+// step / step_ptr pattern).
+struct KlWeight {
+  const float* beta_ptr;  // device-resident beta of the step in flight; overrides `beta`
+  float beta;
+  float scale;            // 1 / B_global (div: B_global)
+  int div;
+};
+__device__ inline float kl_scale_of(const KlWeight& k) {
+  const float b = k.beta_ptr ? *k.beta_ptr : k.beta;
+  return k.div ? b / k.scale : b * k.scale;
+}
+
 __device__ inline U4 philox_block(const NoiseKey& nk, uint32_t cell_id, uint32_t col_block) {
   const uint32_t step = nk.step_ptr ? *nk.step_ptr : nk.step;
   return philox4x32_10(col_block, cell_id, step, nk.stream, nk.k0, nk.k1);

@@ -180,8 +180,10 @@ __device__ inline void gemm_body(const GemmArgs& g, const int bx, const int by, 
   // partial tiles' exchange they were one more memory round trip at the end of a four-workgroup launch)
   constexpr int RPW_E = 16 / WK;
   float e_mu[RPW_E], e_sr[RPW_E], e_sg[RPW_E], e_ep[RPW_E], e_dk[RPW_E], e_za[RPW_E];
+  float e_kls = 0.f;   // the step's KL weight (KlWeight), requested with them
   if (EPI == 2) {
     const EpiLatentBwd& e = g.lb;
+    e_kls = kl_scale_of(e.klw);
     // (unconditional loads from clamped indices: a lane-predicated load per register was a block with a wait of its own -- four round trips in a row; what a
     // lane beyond the tile reads is never used.  And NO branch on the launch-uniform switches either: an absent operand is read from `lat` instead (valid
     // at every index used here) and replaced by its constant afterwards -- inside `if (e.stochastic) { loads }` the compiler folded the first USE of the
@@ -287,6 +289,7 @@ __device__ inline void gemm_body(const GemmArgs& g, const int bx, const int by, 
     const EpiLatentBwd& e = g.lb;
     const int d = n0 + wn * 32 + li;
     const bool live = d < e.D;
+    const float kls = e_kls;
     // (the operands were requested at entry)
     const float (&mu)[RPW_E] = e_mu; const float (&sr)[RPW_E] = e_sr; const float (&sg)[RPW_E] = e_sg;
     const float (&ep)[RPW_E] = e_ep; const float (&dk)[RPW_E] = e_dk; const float (&za)[RPW_E] = e_za;
@@ -295,12 +298,12 @@ __device__ inline void gemm_body(const GemmArgs& g, const int bx, const int by, 
     for (int j = 0; j < RPW; ++j) {
       const float dz = out[j] + za[j];
       if (e.stochastic && e.dklz) {   // SCALE: Monte-Carlo KL, log q depends on (sigma, eps) only
-        const float dzt = dz + e.kl_scale * dk[j];
+        const float dzt = dz + kls * dk[j];
         o0[j] = live ? dzt : 0.f;
-        o1[j] = live ? (dzt * ep[j] - e.kl_scale * frcp(sg[j])) * sigmoidf(sr[j] + SMX_SOFTPLUS_INV_1) : 0.f;
+        o1[j] = live ? (dzt * ep[j] - kls * frcp(sg[j])) * sigmoidf(sr[j] + SMX_SOFTPLUS_INV_1) : 0.f;
       } else if (e.stochastic) {
-        o0[j] = live ? dz + e.kl_scale * mu[j] : 0.f;
-        o1[j] = live ? (dz * ep[j] + e.kl_scale * (sg[j] - frcp(sg[j]))) * sigmoidf(sr[j] + SMX_SOFTPLUS_INV_1) : 0.f;
+        o0[j] = live ? dz + kls * mu[j] : 0.f;
+        o1[j] = live ? (dz * ep[j] + kls * (sg[j] - frcp(sg[j]))) * sigmoidf(sr[j] + SMX_SOFTPLUS_INV_1) : 0.f;
       } else {
         o0[j] = (live && !(e.relu && !(mu[j] > 0.f))) ? dz : 0.f;
         o1[j] = 0.f;

@@ -46,7 +46,7 @@ struct AXform {
 struct EpiLatentBwd {
   const float* lat = nullptr; int ld = 0;            // [B][ld]: mu | s_raw
   const float* sig = nullptr; const float* eps = nullptr;  // [B][Dp]
-  float kl_scale = 0.f; int D = 0, Dp = 0, stochastic = 1, relu = 0;
+  KlWeight klw{nullptr, 0.f, 0.f, 0}; int D = 0, Dp = 0, stochastic = 1, relu = 0;   // klw: beta / B_global
   float* dlat = nullptr;                             // [B][ld]
   // SCALE (Monte-Carlo KL against the mixture prior): d(-log p)/dz [B][Dp] from scale_prior_fwd; nullptr: analytic KL
   const float* dklz = nullptr;
@@ -153,7 +153,7 @@ struct LatentArgs {
   float* kl = nullptr;                                             // [B]
   // backward
   const float* dz = nullptr; int dz_slabs = 1; long dz_slab_stride = 0;
-  float kl_scale = 0.f;       // beta / B_global
+  KlWeight klw{nullptr, 0.f, 0.f, 0};   // beta / B_global
   float* dlat = nullptr;      // [B][2*Dp] or [B][Dp]
 };
 
@@ -172,7 +172,7 @@ struct MixLatArgs {
   int32_t* pick = nullptr;    // [B] the picked component
   // backward
   const float* dz = nullptr; int dz_slabs = 1; long dz_slab_stride = 0; int ldz = 0;
-  float kl_scale = 0.f;       // beta / B_global
+  KlWeight klw{nullptr, 0.f, 0.f, 0};   // beta / B_global
   float* dlat = nullptr;      // [B][ld]
 };
 int launch_mixlat_fwd(hipStream_t st, const MixLatArgs& a);
@@ -215,6 +215,8 @@ struct StepState {
   uint32_t next;      // master copy only: optimiser steps completed so far
   float lr_t;         // step size of the step in flight: Adam's bias-corrected one, lr / (1 - b1^t) under Adamax, lr otherwise (opt_lr_t)
   uint32_t cursor;    // position (in steps) of the step in flight inside the uploaded row-id order
+  float beta;         // KL weight of the step in flight, and
+  float lr;           // its learning rate before the rule's bias correction: entry `cursor` of the schedule table (smx_set_schedule)
 };
 
 // ELBO scalars of a step; computed by one workgroup that rides along with another launch
@@ -225,6 +227,7 @@ struct MetricsArgs {
   const float* llk_o = nullptr;   // [B] log-likelihood of the observed extra outputs (weight 1) or nullptr -> out[7]
   const float* kl = nullptr; const float* kl_l = nullptr;
   int B = 0; float alpha = 0.f, beta = 1.f; float inv_global_batch = 0.f;
+  const float* beta_ptr = nullptr;   // training: the step's beta (StepState::beta); overrides `beta`
   float* out = nullptr;           // [8]: loss, nllk_x, nllk_y, kl, kl_l, tc, dtc_loss, nllk_o
   // per-step history of a train_steps call (single GPU: written here; data parallel: by the optimiser launch,
   // after the all-reduce): hist[cursor * 8 + i] = out[i]
@@ -251,7 +254,7 @@ struct AdamArgs {
   MetricsArgs metrics; int with_metrics = 0;
   // the optimiser's workgroup 0 finishes the step: master counter, and the state + row ids of the next step
   StepState* master = nullptr; StepState* next_state = nullptr; const int32_t* order = nullptr; int32_t* next_rows = nullptr;
-  int batch = 0, prepare_next = 0; float lr = 1e-3f;
+  int batch = 0, prepare_next = 0; const float2* sched = nullptr;   // sched: the (beta, lr) table by cursor (upload_order)
   int form = OPT_ADAM;          // the rule (OptForm; smx_set_optimizer): in the padding beside `params`, in a kernarg line every chunk body reads already
   float* params = nullptr; float* grads = nullptr; float* m = nullptr; float* v = nullptr;
   const OptChunk* chunks = nullptr; int n_chunks = 0;
@@ -340,7 +343,7 @@ struct ScalePriorArgs {
   float* kl = nullptr;        // [B]  log q(z|x) - log p(z)
   float* resp = nullptr;      // [B][32] responsibilities
   float* dklz = nullptr;      // [B][Dp] d(-log p)/dz
-  float kl_scale = 0.f;       // beta / B_global
+  KlWeight klw{nullptr, 0.f, 0.f, 0};   // beta / B_global
   float* g_logits = nullptr; float* g_loc = nullptr; float* g_scale = nullptr;   // gradients (backward)
   int tie_mixtures = 0, tie_loc = 0, tie_scale = 0;   // scale.py:29-33: a tied tensor's rows all receive the sum of the rows' gradients (logits: none)
   float* tril_part = nullptr; size_t tril_part_floats = 0;   // covariance = 'tril', backward: partial sums [C][ceil(B / 16)][D][D + 2]
@@ -359,7 +362,7 @@ struct LibLatentArgs {
   float clip_library = 1e3f;
   float* l = nullptr; float* sig = nullptr; float* eps = nullptr; float* kl = nullptr;  // [B]
   const float* dl = nullptr;  // [B] d loss / d l (already masked by the clip)
-  float kl_scale = 0.f;
+  KlWeight klw{nullptr, 0.f, 0.f, 0};   // beta / B_global
   float* dlatl = nullptr;     // [B][ld]
 };
 int launch_lib_latent_fwd(hipStream_t st, const LibLatentArgs& a);
@@ -391,7 +394,7 @@ struct ScviTrainArgs {
   const float* library = nullptr; uint32_t cell_base = 0;
   NoiseKey nk{0, 0, 0, 0, nullptr};
   const float* inj_eps = nullptr; int inj_ld = 1;
-  float kl_scale = 0.f;
+  KlWeight klw{nullptr, 0.f, 0.f, 0};   // beta / B_global
   float* latl = nullptr; int ldl = 0;                                    // [B][ldl]: (mu_l, s_l) kept for inspection
   float* l = nullptr; float* sig = nullptr; float* eps = nullptr; float* kl = nullptr;   // [B]
   float* dlatl = nullptr;      // [B][ldl] gradient wrt (mu_l, s_l), zeros beyond
@@ -424,8 +427,9 @@ int launch_label_loss(hipStream_t st, const LabelArgs& a);
 // Prepares the per-step state `dst` (+ row ids) of the step at order position `cursor` from the master
 // counter.  Eager mode runs it once per train_steps call (later steps are prepared by the optimiser
 // kernel of the step before); graph mode runs it as the first node of every step.
+// `sched`: the (beta, lr) table of the call's steps, by cursor (upload_order).
 int launch_step_begin(hipStream_t st, StepState* master, StepState* dst, const int32_t* order, int32_t* rows,
-                      int batch, int cursor_from_master, uint32_t cursor, float lr, float b1, float b2,
+                      int batch, int cursor_from_master, uint32_t cursor, const float2* sched, float b1, float b2,
                       int form = OPT_ADAM, uint32_t t0 = 0);
 
 

@@ -129,11 +129,11 @@ static int k_opt_launch(int rule, const float* hp, int32_t n_tensors, const int3
     total += pad[t];
   }
   float *dP = nullptr, *dG = nullptr, *dM = nullptr, *dV = nullptr, *dPart = nullptr, *dNorm = nullptr;
-  OptChunk* dCh = nullptr; StepState* dSt = nullptr;
+  OptChunk* dCh = nullptr; StepState* dSt = nullptr; float2* dSch = nullptr;
   int rc;
   if ((rc = dmalloc(&dP, total)) || (rc = dmalloc(&dG, total)) || (rc = dmalloc(&dM, total)) || (rc = dmalloc(&dV, total)) ||
       (rc = dmalloc(&dPart, chunks.size())) || (rc = dmalloc(&dNorm, (size_t)n_tensors)) || (rc = dmalloc(&dCh, chunks.size())) ||
-      (rc = dmalloc(&dSt, (size_t)3)))
+      (rc = dmalloc(&dSt, (size_t)3)) || (rc = dmalloc(&dSch, (size_t)1)))
     return rc;
   auto put = [&](float* dst, const float* src) -> int {
     size_t lo = 0;
@@ -157,14 +157,16 @@ static int k_opt_launch(int rule, const float* hp, int32_t n_tensors, const int3
   memset(st3, 0, sizeof(st3));
   st3[2].next = (uint32_t)(step - 1);   // optimiser steps completed so far
   if (rc == SMX_OK && hipMemcpy(dSt, st3, sizeof(st3), hipMemcpyHostToDevice) != hipSuccess) rc = SMX_ERR_HIP;
+  const float2 sch = make_float2(0.f, lr);   // the one-step schedule table: (beta, lr)
+  if (rc == SMX_OK && hipMemcpy(dSch, &sch, sizeof(sch), hipMemcpyHostToDevice) != hipSuccess) rc = SMX_ERR_HIP;
   // the step's scalars exactly as a training step prepares them (bias-corrected step size on the device)
   AdamArgs a;
   opt_scalars(rule, hp, a);   // (t0 = 0: the rule's count t is the step given)
-  if (rc == SMX_OK) rc = launch_step_begin(nullptr, dSt + 2, dSt, nullptr, nullptr, 0, 0, 0u, lr, a.b1, a.b2, a.form, 0u);
+  if (rc == SMX_OK) rc = launch_step_begin(nullptr, dSt + 2, dSt, nullptr, nullptr, 0, 0, 0u, dSch, a.b1, a.b2, a.form, 0u);
   if (rc == SMX_OK) {
     a.params = dP; a.grads = dG; a.m = dM; a.v = dV; a.chunks = dCh; a.n_chunks = (int)chunks.size(); a.n_launch = a.n_chunks; a.gap_from = a.n_chunks; a.gap_len = 0;
     a.partial = dPart; a.tensor_norm = dNorm; a.use_sq = 0; a.state = dSt;
-    a.clipnorm = clipnorm; a.grad_scale = 1.f; a.lr = lr;
+    a.clipnorm = clipnorm; a.grad_scale = 1.f; a.sched = dSch;
     rc = launch_adam(nullptr, a);
   }
   if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_adam: device synchronize failed"); rc = SMX_ERR_HIP; }
@@ -172,7 +174,7 @@ static int k_opt_launch(int rule, const float* hp, int32_t n_tensors, const int3
   if (rc == SMX_OK) rc = get(mom, dM);
   if (rc == SMX_OK) rc = get(vel, dV);
   if (rc == SMX_OK && norms && hipMemcpy(norms, dNorm, (size_t)n_tensors * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = SMX_ERR_HIP;
-  hipFree(dP); hipFree(dG); hipFree(dM); hipFree(dV); hipFree(dPart); hipFree(dNorm); hipFree(dCh); hipFree(dSt);
+  hipFree(dP); hipFree(dG); hipFree(dM); hipFree(dV); hipFree(dPart); hipFree(dNorm); hipFree(dCh); hipFree(dSt); hipFree(dSch);
   return rc;
 }
 

@@ -166,6 +166,7 @@ __global__ __launch_bounds__(256) void mixlat_fwd_kernel(MixLatArgs a) {
 }
 // d lat from d z: log q depends on z and on every component's parameters, z on the picked component's (mu_k, sigma_k) only
 __global__ __launch_bounds__(256) void mixlat_bwd_kernel(MixLatArgs a) {
+  const float kls = kl_scale_of(a.klw);
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= a.B) return;
@@ -190,14 +191,14 @@ __global__ __launch_bounds__(256) void mixlat_bwd_kernel(MixLatArgs a) {
       dqz -= lane_bcast(rme, c) * (z - mu[c]) * is * is;
     }
   }
-  const float g = dz + a.kl_scale * (z + dqz);
-  for (int d = lane; d < a.Dp; d += 64) dl[d] = d < a.C ? a.kl_scale * (rme - pi) : 0.f;   // plane 0: logits (d == lane)
+  const float g = dz + kls * (z + dqz);
+  for (int d = lane; d < a.Dp; d += 64) dl[d] = d < a.C ? kls * (rme - pi) : 0.f;   // plane 0: logits (d == lane)
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     if (c < a.C) {
       const float rc = lane_bcast(rme, c), is = frcp(sg[c]);
       const float dzm = (z - mu[c]) * is;
-      float dmu = a.kl_scale * rc * dzm * is, dsg = a.kl_scale * rc * (dzm * dzm - 1.f) * is;
+      float dmu = kls * rc * dzm * is, dsg = kls * rc * (dzm * dzm - 1.f) * is;
       if (c == k) { dmu += g; dsg += g * eps; }
       for (int d = lane; d < a.Dp; d += 64) {
         dl[(1 + c) * a.Dp + d] = d < a.D ? dmu : 0.f;
@@ -223,6 +224,7 @@ int launch_mixlat_bwd(hipStream_t st, const MixLatArgs& a) {
 }
 
 __global__ __launch_bounds__(256) void latent_bwd_kernel(LatentArgs a) {
+  const float kls = kl_scale_of(a.klw);
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= a.B * a.Dp) return;
   const int b = idx / a.Dp, d = idx % a.Dp;
@@ -234,8 +236,8 @@ __global__ __launch_bounds__(256) void latent_bwd_kernel(LatentArgs a) {
       const float mu = a.lat[(long)b * a.ld + d];
       const float sraw = a.lat[(long)b * a.ld + a.Dp + d];
       const float sig = a.sig[idx], eps = a.eps[idx];
-      dmu = dz + a.kl_scale * mu;
-      ds = (dz * eps + a.kl_scale * (sig - frcp(sig))) * sigmoidf(sraw + SMX_SOFTPLUS_INV_1);
+      dmu = dz + kls * mu;
+      ds = (dz * eps + kls * (sig - frcp(sig))) * sigmoidf(sraw + SMX_SOFTPLUS_INV_1);
     }
     a.dlat[(long)b * a.ld + d] = dmu;
     a.dlat[(long)b * a.ld + a.Dp + d] = ds;
@@ -500,6 +502,7 @@ __global__ __launch_bounds__(64 * SMX_TRILB_WAVES) void scale_prior_tril_bwd_ker
   }
 }
 __global__ __launch_bounds__(256) void scale_prior_tril_reduce_kernel(ScalePriorArgs a, const float* gpart, int n_grp) {
+  const float kls = kl_scale_of(a.klw);
   const int c = blockIdx.x;
   const int D = a.D, lda = D + 2;
   const float* base = gpart + (long)c * n_grp * D * lda;
@@ -515,17 +518,17 @@ __global__ __launch_bounds__(256) void scale_prior_tril_reduce_kernel(ScalePrior
     const int p = i / lda, j = i - p * lda;
     if (j < D) {
       float g = 0.f;
-      if (j < p) g = -a.kl_scale * t;
-      else if (j == p) g = -a.kl_scale * t * sigmoidf(a.scale_raw[((long)c * D + p) * a.Dp + p]);
+      if (j < p) g = -kls * t;
+      else if (j == p) g = -kls * t * sigmoidf(a.scale_raw[((long)c * D + p) * a.Dp + p]);
       a.g_scale[((long)c * D + p) * a.Dp + j] = g;
     } else if (j == D) {
-      a.g_loc[(long)c * a.Dp + p] = -a.kl_scale * t;
+      a.g_loc[(long)c * a.Dp + p] = -kls * t;
     } else if (p == 0) {   // j == D + 1: the sum of the responsibilities
       float mx = -3.0e38f;
       for (int q = 0; q < a.C; ++q) mx = fmaxf(mx, a.logits[q]);
       float se = 0.f;
       for (int q = 0; q < a.C; ++q) se += fexp(a.logits[q] - mx);
-      a.g_logits[c] = a.kl_scale * ((float)a.B * fexp(a.logits[c] - mx) * frcp(se) - t);
+      a.g_logits[c] = kls * ((float)a.B * fexp(a.logits[c] - mx) * frcp(se) - t);
     }
   }
   for (int i = threadIdx.x; i < D * (a.Dp - D); i += 256) {   // the padded columns
@@ -550,6 +553,7 @@ int launch_scale_prior_fwd(hipStream_t st, const ScalePriorArgs& a) {
 }
 // gradients of the prior's parameters: one workgroup per component, lanes over the latent dims, waves over the cells
 __global__ __launch_bounds__(256) void scale_prior_bwd_kernel(ScalePriorArgs a) {
+  const float kls = kl_scale_of(a.klw);
   __shared__ float sh[4][3][64];
   const int c = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (int d0 = 0; d0 < a.Dp; d0 += 64) {
@@ -586,8 +590,8 @@ __global__ __launch_bounds__(256) void scale_prior_bwd_kernel(ScalePriorArgs a) 
       const float t0 = (sh[0][0][lane] + sh[1][0][lane]) + (sh[2][0][lane] + sh[3][0][lane]);
       const float t1 = (sh[0][1][lane] + sh[1][1][lane]) + (sh[2][1][lane] + sh[3][1][lane]);
       if (d < a.Dp) {
-        a.g_loc[(long)c * a.Dp + d] = live ? -a.kl_scale * t0 : 0.f;
-        a.g_scale[(long)c * a.Dp + d] = live ? -a.kl_scale * t1 * sigmoidf(raw + SMX_SOFTPLUS_INV_1) : 0.f;
+        a.g_loc[(long)c * a.Dp + d] = live ? -kls * t0 : 0.f;
+        a.g_scale[(long)c * a.Dp + d] = live ? -kls * t1 * sigmoidf(raw + SMX_SOFTPLUS_INV_1) : 0.f;
       }
       if (d0 == 0 && lane == 0) {
         const float rsum = (sh[0][2][0] + sh[1][2][0]) + (sh[2][2][0] + sh[3][2][0]);
@@ -596,7 +600,7 @@ __global__ __launch_bounds__(256) void scale_prior_bwd_kernel(ScalePriorArgs a) 
         for (int q = 0; q < a.C; ++q) mx = fmaxf(mx, a.logits[q]);
         float se = 0.f;
         for (int q = 0; q < a.C; ++q) se += fexp(a.logits[q] - mx);
-        a.g_logits[c] = a.kl_scale * ((float)a.B * fexp(a.logits[c] - mx) * frcp(se) - rsum);
+        a.g_logits[c] = kls * ((float)a.B * fexp(a.logits[c] - mx) * frcp(se) - rsum);
       }
     }
     __syncthreads();
@@ -658,6 +662,7 @@ int launch_lib_latent_fwd(hipStream_t st, const LibLatentArgs& a) {
   return SMX_OK;
 }
 __global__ void lib_latent_bwd_kernel(LibLatentArgs a) {
+  const float kls = kl_scale_of(a.klw);
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.B) return;
   const long src = a.rows ? a.rows[b] : b;
@@ -666,8 +671,8 @@ __global__ void lib_latent_bwd_kernel(LibLatentArgs a) {
   const float mp = a.library[src * 2], vp = a.library[src * 2 + 1];
   const float dl = a.dl[b];
   for (int j = 2; j < a.ld; ++j) a.dlatl[(long)b * a.ld + j] = 0.f;
-  a.dlatl[(long)b * a.ld] = dl + a.kl_scale * (mu - mp) / vp;
-  a.dlatl[(long)b * a.ld + 1] = (dl * eps + a.kl_scale * (sig / vp - 1.f / sig)) * sigmoidf(sraw + SMX_SOFTPLUS_INV_1);
+  a.dlatl[(long)b * a.ld] = dl + kls * (mu - mp) / vp;
+  a.dlatl[(long)b * a.ld + 1] = (dl * eps + kls * (sig / vp - 1.f / sig)) * sigmoidf(sraw + SMX_SOFTPLUS_INV_1);
 }
 int launch_lib_latent_bwd(hipStream_t st, const LibLatentArgs& a) {
   hipLaunchKernelGGL(lib_latent_bwd_kernel, dim3((a.B + 255) / 256), dim3(256), 0, st, a);

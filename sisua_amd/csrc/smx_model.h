@@ -215,6 +215,9 @@ struct smx_model {
   // the optimiser rule (smx_set_optimizer): smx_optimizer, its hyper-parameters (defaults filled in; Adam's from the config) and t0 -- the
   // model step at which the rule's state began.  adam_m / adam_v are the rule's slots 2 / 3.
   int opt_rule = 0; float opt_hp[4] = {0.f, 0.f, 0.f, 0.f}; uint32_t opt_t0 = 0;
+  // the schedules of the KL weight (SMX_SCHED_BETA) and the learning rate (SMX_SCHED_LR) (smx_set_schedule): a kind and its parameters in double;
+  // no parameters: const at smx_config.beta / .lr.  Evaluated on the host per train_steps call into sched_tab (beside `order`, same lifetime)
+  int sched_kind[2] = {0, 0}; std::vector<double> sched_p[2];
   std::vector<MlpLayer> enc, encl, dec;
   int t_latW = -1, t_latb = -1, t_latlW = -1, t_latlb = -1;
   int t_outW[3] = {-1, -1, -1}, t_outb[3] = {-1, -1, -1};
@@ -233,7 +236,8 @@ struct smx_model {
   float* hostX = nullptr; float* hostLib = nullptr; float* hostLgx1 = nullptr;
   // step state
   int32_t* rows2[2] = {nullptr, nullptr}; int32_t* order = nullptr; size_t order_cap = 0;
-  // pinned staging for the row ids of a train_steps call: hipMemcpyAsync from the caller's pageable array cost ~80 us per call
+  float2* sched_tab = nullptr; size_t sched_cap = 0;   // (beta, lr) of the call's steps by cursor: what step_begin / the optimiser's closing workgroup read
+  // pinned staging for the row ids (and, behind them, the schedule table) of a train_steps call: hipMemcpyAsync from the caller's pageable array cost ~80 us per call
   int32_t* order_pin = nullptr; size_t order_pin_cap = 0; hipEvent_t ev_order = nullptr; bool order_pin_busy = false;
   int32_t* pred_ids = nullptr; int pred_ids_batch = 0;   // smx_predict super-batches: noise ids (row % batch)
   char* csr_host = nullptr; size_t csr_host_bytes = 0;   // a batch of host rows given as CSR, staged (smx_marginal_llk_csr, CSR log_prob targets)
@@ -390,6 +394,9 @@ const Injected* inj(smx_model* m, int stream);
 void pack(const TensorInfo& t, const float* host, std::vector<float>& dev);
 void unpack(const TensorInfo& t, const std::vector<float>& dev, float* host, float scale);
 void drop_graphs(smx_model* m);
+// schedules (smx_schedule.hip): beta at a step, and the (beta, lr) table of the n_steps steps from the model's step on
+float sched_beta(const smx_model* m, uint32_t step);
+void sched_fill(const smx_model* m, float* dst, size_t n_steps);
 // smx_comm.hip
 bool dp_active(const smx_model* m);
 bool dp_shard_available(const smx_model* m);   // flag opt_shard can be honoured: the loopback communicator, or RCCL with ncclReduceScatter / ncclAllGather

@@ -559,7 +559,7 @@ int smx_model_destroy(smx_model* m) {
   release_csr(m);   // (the sparse store: m->X aliased its expansion tile)
   fr(m->X); fr(m->library); fr(m->mask); fr(m->lgx1); fr(m->hostX); fr(m->hostLib); fr(m->hostLgx1);
   for (int j = 0; j < SMX_MAX_LABELS; ++j) { fr(m->Y[j]); fr(m->laby_raw[j]); fr(m->laby_draw[j]); }
-  fr(m->rows2[0]); fr(m->rows2[1]); fr(m->order); fr(m->state3); fr(m->mhist);
+  fr(m->rows2[0]); fr(m->rows2[1]); fr(m->order); fr(m->sched_tab); fr(m->state3); fr(m->mhist);
   fr(m->resp); fr(m->dklz); fr(m->zmean); fr(m->zpick); fr(m->tril_part);
   for (auto& L : m->disc) { fr(L.xhat); fr(L.out_buf); fr(L.dpre); }
   fr(m->zz); fr(m->u_d); fr(m->tc_cell); fr(m->dl_cell); fr(m->dz_tc); fr(m->disc_dpre); fr(m->disc_db);

@@ -44,6 +44,7 @@ __device__ inline float scvi_block_max(float v, float* sh) {
 // dispersion and gate planes leave as soon as they are known, the softmax terms become rho in place.
 template <int NV, int LK, int U16, int NT = 256>
 __global__ __launch_bounds__(NT) void scvi_head_train_kernel(ScviTrainArgs a) {
+  const float kls = kl_scale_of(a.klw);
   constexpr int K3 = (LK == SMX_LLK_ZINBD) ? 1 : 0;
   __shared__ float sh[NT / 64];
   __shared__ float shl[2];
@@ -196,8 +197,8 @@ __global__ __launch_bounds__(NT) void scvi_head_train_kernel(ScviTrainArgs a) {
     const float dl = (lraw > 0.f && lraw < a.clip_library) ? dlh : 0.f;
     a.dl[b] = dl;
     float* o = a.dlatl + (long)b * a.ldl;
-    o[0] = dl + a.kl_scale * (mu_l - mp) / vp;
-    o[1] = (dl * eps_l + a.kl_scale * (sig_l / vp - 1.f / sig_l)) * sigmoidf(sraw_l + SMX_SOFTPLUS_INV_1);
+    o[0] = dl + kls * (mu_l - mp) / vp;
+    o[1] = (dl * eps_l + kls * (sig_l / vp - 1.f / sig_l)) * sigmoidf(sraw_l + SMX_SOFTPLUS_INV_1);
   }
   if (threadIdx.x >= 2 && (int)threadIdx.x < a.ldl) a.dlatl[(long)b * a.ldl + threadIdx.x] = 0.f;
 }

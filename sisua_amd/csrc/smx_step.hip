@@ -24,6 +24,15 @@ static bool front_shapes_ok(smx_model* m, const Pass& ps) {
 
 
 // a stream of the draw side (the latent draws, the decoder's dropout): row r of a stacked pass takes sample index r / draw_rows
+// the KL weight of a launch of this pass: a training step reads its own beta from its state (the schedule table's entry, so a captured graph
+// replays each step's weight); an eval pass takes beta at the model's step by value
+static KlWeight kl_weight(smx_model* m, const Pass& ps, float scale, int div) {
+  KlWeight w{nullptr, 0.f, scale, div};
+  if (ps.training) w.beta_ptr = &cur_state(m)->beta;
+  else w.beta = sched_beta(m, m->h_next);
+  return w;
+}
+
 static NoiseKey draw_key(smx_model* m, int stream, const Pass& ps) {
   NoiseKey nk = make_key(m, stream, ps.sample, ps.training != 0);
   nk.draw_rows = (uint32_t)ps.draw_rows;
@@ -647,7 +656,7 @@ static bool scvi_train_args(smx_model* m, const Pass& ps, ScviTrainArgs* out) {
   a.library = ps.lib; a.cell_base = ps.cell_base;
   a.nk = draw_key(m, ST_EPS_L, ps);
   if (const Injected* ij = inj(m, ST_EPS_L)) { a.inj_eps = ij->d; a.inj_ld = ij->ld; }
-  a.kl_scale = c.beta / (float)ps.global_batch;
+  a.klw = kl_weight(m, ps, (float)ps.global_batch, 1);
   a.latl = m->latlbuf; a.ldl = 32; a.l = m->lsmp; a.sig = m->lsig; a.eps = m->leps; a.kl = m->kl_l;
   a.dlatl = m->dlatl; a.dl = m->dl;
   if (!scvi_head_train_supported(a)) return false;
@@ -902,7 +911,8 @@ int forward_pass(smx_model* m, const Pass& ps, bool with_loss, bool backward, in
   me.llk_o = m->n_observed ? m->llk_o : nullptr;
   if (m->fvae) { me.tc = m->tc_cell; me.dl = m->dl_cell; me.gamma = c.gamma; }
   me.kl = m->stochastic ? m->kl : nullptr; me.kl_l = m->scvi ? m->kl_l : nullptr;
-  me.B = ps.B; me.alpha = c.alpha; me.beta = c.beta; me.inv_global_batch = inv_gb;
+  me.B = ps.B; me.alpha = c.alpha; me.inv_global_batch = inv_gb;
+  { const KlWeight w = kl_weight(m, ps, inv_gb, 0); me.beta = w.beta; me.beta_ptr = w.beta_ptr; }
   me.out = m->grads + m->tail_off_metrics;
   if (backward && !dp_active(m)) { me.hist = m->mhist; me.state = cur_state(m); }
   if (backward) {
@@ -1367,7 +1377,7 @@ int backward_pass(smx_model* m, const Pass& ps) {
   // ---- decoder MLP; the latent head's backward runs in the epilogue of the d z product ----
   const int lat_ld = m->lat_planes * m->Dp;
   EpiLatentBwd le;
-  le.lat = m->latbuf; le.ld = lat_ld; le.sig = m->sig; le.eps = m->eps; le.kl_scale = c.beta * inv_gb;
+  le.lat = m->latbuf; le.ld = lat_ld; le.sig = m->sig; le.eps = m->eps; le.klw = kl_weight(m, ps, inv_gb, 0);
   le.D = m->D; le.Dp = m->Dp; le.stochastic = m->stochastic; le.relu = (c.latent_activation == SMX_ACT_RELU);
   le.dlat = m->dlat;
   if (m->fvae) le.dz_add = m->dz_tc;
@@ -1376,7 +1386,7 @@ int backward_pass(smx_model* m, const Pass& ps) {
     ScalePriorArgs sp;
     sp.z = m->z; sp.B = ps.B; sp.D = m->D; sp.Dp = m->Dp; sp.C = c.n_components;
     sp.logits = P_(m, m->t_prLogits); sp.loc = P_(m, m->t_prLoc); sp.scale_raw = P_(m, m->t_prScale);
-    sp.resp = m->resp; sp.kl_scale = c.beta * inv_gb;
+    sp.resp = m->resp; sp.klw = kl_weight(m, ps, inv_gb, 0);
     sp.g_logits = G_(m, m->t_prLogits); sp.g_loc = G_(m, m->t_prLoc); sp.g_scale = G_(m, m->t_prScale);
     sp.tie_mixtures = m->flags.tie_mixtures; sp.tie_loc = m->flags.tie_loc; sp.tie_scale = m->flags.tie_scale; sp.tril = m->scale_tril;
     sp.tril_part = m->tril_part; sp.tril_part_floats = m->tril_part_floats;
@@ -1406,7 +1416,7 @@ int backward_pass(smx_model* m, const Pass& ps) {
     ma.lat = m->latbuf; ma.ld = lat_ld; ma.B = ps.B; ma.D = m->D; ma.Dp = m->Dp; ma.C = c.n_components;
     ma.z = m->z; ma.eps = m->eps; ma.resp = m->resp; ma.pick = m->zpick;
     ma.dz = m->slab; ma.dz_slabs = dz_slabs; ma.dz_slab_stride = (long)ps.B * m->dec[0].in_p; ma.ldz = m->dec[0].in_p;
-    ma.kl_scale = c.beta * inv_gb; ma.dlat = m->dlat;
+    ma.klw = kl_weight(m, ps, inv_gb, 0); ma.dlat = m->dlat;
     Timed t(m, "latent_bwd");
     SMX_CHECK(launch_mixlat_bwd(m->st, ma));
   } else {
@@ -1466,7 +1476,7 @@ int backward_pass(smx_model* m, const Pass& ps) {
     if (!m->scvi_fused) {
       LibLatentArgs ll;
       ll.latl = m->latlbuf; ll.ld = 32; ll.B = ps.B; ll.library = ps.lib; ll.rows = ps.rows;
-      ll.sig = m->lsig; ll.eps = m->leps; ll.dl = m->dl; ll.kl_scale = c.beta * inv_gb; ll.dlatl = m->dlatl;
+      ll.sig = m->lsig; ll.eps = m->leps; ll.dl = m->dl; ll.klw = kl_weight(m, ps, inv_gb, 0); ll.dlatl = m->dlatl;
       SMX_CHECK(launch_lib_latent_bwd(m->st, ll));
     }
     const MlpLayer& lL = m->encl.back();
@@ -1582,7 +1592,7 @@ int optimizer_pass(smx_model* m) {
   }
   m->adam_early_from = -1;
   if (m->have_pending_metrics) { a.metrics = m->pending_metrics; a.with_metrics = 1; m->have_pending_metrics = false; }
-  a.master = master_state(m); a.lr = c.lr; a.batch = m->seq_batch;
+  a.master = master_state(m); a.sched = m->sched_tab; a.batch = m->seq_batch;
   if (dp_active(m)) { a.hist_dp = m->mhist; a.tail_metrics = m->grads + m->tail_off_metrics; }
   a.prepare_next = m->seq_prepare_next;
   if (a.prepare_next) { a.next_state = m->state3 + (m->par ^ 1); a.next_rows = m->rows2[m->par ^ 1]; a.order = m->order; }
@@ -1617,7 +1627,7 @@ int train_sequence(smx_model* m, int B, bool with_begin, bool begin_from_master,
     AdamArgs o;
     opt_scalars(m->opt_rule, m->opt_hp, o);
     SMX_CHECK(launch_step_begin(m->st, master_state(m), cur_state(m), m->order, cur_rows(m), B, begin_from_master ? 1 : 0,
-                                cursor, m->cfg.lr, o.b1, o.b2, o.form, m->opt_t0));
+                                cursor, m->sched_tab, o.b1, o.b2, o.form, m->opt_t0));
   }
   m->chain_started = false;
   { Timed null_pair(m, "null"); }  // an event pair around nothing: the timing method's own overhead
@@ -1677,20 +1687,33 @@ int upload_order(smx_model* m, const int32_t* order, size_t n, size_t n_steps) {
     m->order_cap = n * 2 + (size_t)m->Bmax;
     SMX_CHECK(dmalloc(&m->order, m->order_cap));
   }
+  // the schedule table: (beta, lr) of each of the call's steps, by cursor (a captured graph keeps reading this buffer: it goes with the graphs)
+  if (n_steps > m->sched_cap) {
+    SMX_HIP(hipStreamSynchronize(m->st));
+    drop_graphs(m);
+    if (m->sched_tab) hipFree(m->sched_tab);
+    m->sched_tab = nullptr;
+    m->sched_cap = n_steps * 2 + 64;
+    SMX_CHECK(dmalloc(&m->sched_tab, m->sched_cap));
+  }
   // through a pinned buffer of the model's own: the copy is then a real asynchronous DMA (from pageable memory the runtime
   // stages it synchronously: ~80 us for 10 KB, 4 us per step of a 20-step call).  The buffer is reused only after the
-  // previous call's copy has run (an event; by then normally long done)
-  if (n > m->order_pin_cap) {
+  // previous call's copy has run (an event; by then normally long done).  The row ids, then the schedule table (2 floats per step)
+  const size_t need = n + 2 * n_steps;
+  if (need > m->order_pin_cap) {
     if (m->order_pin_busy) { SMX_HIP(hipEventSynchronize(m->ev_order)); m->order_pin_busy = false; }
     if (m->order_pin) hipHostFree(m->order_pin);
     m->order_pin = nullptr; m->order_pin_cap = 0;
-    SMX_HIP(hipHostMalloc((void**)&m->order_pin, (n * 2 + (size_t)m->Bmax) * sizeof(int32_t), hipHostMallocDefault));
-    m->order_pin_cap = n * 2 + (size_t)m->Bmax;
+    SMX_HIP(hipHostMalloc((void**)&m->order_pin, (need * 2 + (size_t)m->Bmax) * sizeof(int32_t), hipHostMallocDefault));
+    m->order_pin_cap = need * 2 + (size_t)m->Bmax;
   }
   if (!m->ev_order) SMX_HIP(hipEventCreateWithFlags(&m->ev_order, hipEventDisableTiming));
   if (m->order_pin_busy) { SMX_HIP(hipEventSynchronize(m->ev_order)); m->order_pin_busy = false; }
   memcpy(m->order_pin, order, n * sizeof(int32_t));
+  float* tab = reinterpret_cast<float*>(m->order_pin + n);
+  sched_fill(m, tab, n_steps);
   SMX_HIP(hipMemcpyAsync(m->order, m->order_pin, n * sizeof(int32_t), hipMemcpyHostToDevice, m->st));
+  SMX_HIP(hipMemcpyAsync(m->sched_tab, tab, n_steps * sizeof(float2), hipMemcpyHostToDevice, m->st));
   SMX_HIP(hipEventRecord(m->ev_order, m->st));
   m->order_pin_busy = true;
   SMX_HIP(hipMemsetAsync(&master_state(m)->cursor, 0, sizeof(uint32_t), m->st));

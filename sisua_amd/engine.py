@@ -11,7 +11,7 @@ from typing import Dict, Optional, Sequence
 
 import numpy as np
 
-from sisua_amd import _hip, optimizers
+from sisua_amd import _hip, interpolation, optimizers
 from sisua_amd._hip import SmxError, check, smx_config, smx_metrics
 from sisua_amd.config import ModelConfig, init_params, label_planes, manifest
 
@@ -98,6 +98,9 @@ def make_smx_config(cfg: ModelConfig, max_batch: int) -> smx_config:
   c.max_batch = int(max_batch)
   c.seed = int(cfg.seed) & 0xFFFFFFFFFFFFFFFF
   return c
+
+
+_SCHED_TARGETS = {"beta": 0, "lr": 1}   # smx_schedule_target
 
 
 class Engine:
@@ -231,6 +234,25 @@ class Engine:
       self._set_optimizer(name, full)
     finally:
       self.step = step
+
+  # ---- schedules -------------------------------------------------------------------
+  def set_schedule(self, target: str, value):
+    """The KL weight (target 'beta') or the learning rate ('lr') of the later training steps as a function of the step: a number or any
+    schedule sisua_amd.interpolation accepts (smx_set_schedule).  'beta' is keyed by the model's step, 'lr' by step - t0.  ValueError
+    for what is not built."""
+    rec = interpolation.as_schedule(value, target)
+    p = np.ascontiguousarray(rec.params, np.float64)
+    check(self.lib.smx_set_schedule(self._h, _SCHED_TARGETS[target], rec.kind, p.ctypes.data_as(C.POINTER(C.c_double)), len(p)))
+    return rec
+
+  def get_schedule(self, target: str):
+    """The schedule in force for 'beta' or 'lr' as an interpolation.Schedule record (const at the config's value by default)."""
+    kind, n = C.c_int32(), C.c_int32()
+    check(self.lib.smx_get_schedule(self._h, _SCHED_TARGETS[target], C.byref(kind), None, 0, C.byref(n)))
+    p = np.zeros(max(n.value, 1), np.float64)
+    check(self.lib.smx_get_schedule(self._h, _SCHED_TARGETS[target], C.byref(kind), p.ctypes.data_as(C.POINTER(C.c_double)), len(p),
+                                    C.byref(n)))
+    return interpolation.Schedule(kind.value, p[:n.value])
 
   @property
   def step(self) -> int:

@@ -21,12 +21,12 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from sisua_amd import distributions as D
-from sisua_amd import optimizers
+from sisua_amd import interpolation, optimizers
 from sisua_amd.config import ModelConfig, NetConf, RVmeta, init_params
 from sisua_amd.data import BatchDataset, SingleCellOMIC, as_csr, is_sparse, library_matrix
 from sisua_amd.engine import Engine
 
-__all__ = ["SingleCellModel", "VAE", "SISUA", "MISA", "SCALE", "SCVI", "DeepCountAutoencoder", "NetConf", "RVmeta", "get_model",
+__all__ = ["SingleCellModel", "interpolation", "VAE", "SISUA", "MISA", "SCALE", "SCVI", "DeepCountAutoencoder", "NetConf", "RVmeta", "get_model",
            "get_all_models", "load_model", "SCALAR"]
 
 _OMIC_ORDER = ["transcriptomic", "proteomic", "celltype", "disease", "progenitor", "chromatin"]
@@ -156,7 +156,10 @@ class SingleCellModel:
     self._encoder = _flatten(encoder)
     self._decoder = _flatten(decoder)[0]
     self._log_norm = bool(log_norm)
-    self.beta = float(beta)
+    # the KL weight: a number or a schedule keyed by the model's step (sisua_amd.interpolation; ValueError for what is not built).  The
+    # engine's config keeps a number (the value at step 0): the schedule itself is set on the engine (Engine.set_schedule)
+    self._beta_sched = interpolation.as_schedule(beta, "beta")
+    self._beta_cfg = float(np.float32(self._beta_sched.value(0)))
     self.alpha = float(kwargs.pop("alpha", 10.0))
     self.seed = int(kwargs.pop("seed", 8))
     self.clip_library = float(kwargs.pop("clip_library", 1e3))
@@ -188,7 +191,7 @@ class SingleCellModel:
                        enc_units=tuple(enc.units), dec_units=tuple(self._decoder.units),
                        latent_dim=self._latents[0].event_shape, encl_units=tuple(encl), labels=tuple(labels),
                        batchnorm=bool(enc.batchnorm), dropout_enc=float(enc.dropout), dropout_dec=float(self._decoder.dropout),
-                       input_dropout=float(enc.input_dropout), log_norm=self._log_norm, beta=self.beta, alpha=self.alpha,
+                       input_dropout=float(enc.input_dropout), log_norm=self._log_norm, beta=self._beta_cfg, alpha=self.alpha,
                        latent_activation=self._latent_activation(), clip_library=self.clip_library,
                        lr=float(self._opt["lr"]), clipnorm=float(self._opt["clipnorm"]), seed=self.seed,
                        extra_outputs=tuple(extras), dispersion=str(getattr(self, "_dispersion", "full")), inflation=str(getattr(self, "_inflation", "full")),
@@ -208,7 +211,23 @@ class SingleCellModel:
     self._engine = Engine(cfg, max_batch=max(int(max_batch), 64), device=self.device, init=state is None)
     if state is not None:
       self._set_state(state)
+    self._apply_schedules(self._engine)   # (a re-created engine keeps the schedules, as it keeps the optimiser rule)
     return self._engine
+
+  def _apply_schedules(self, e: Engine):
+    e.set_schedule("beta", self._beta_sched)
+    e.set_schedule("lr", getattr(self, "_lr_sched", None) or self._opt["lr"])
+
+  @property
+  def beta(self) -> float:
+    """The KL weight: the number given, or the schedule's value at the model's step (`step`)."""
+    if self._beta_sched.kind == interpolation.CONST:
+      return float(self._beta_sched.params[0])
+    return self._beta_sched(self.step)
+
+  @property
+  def beta_schedule(self) -> "interpolation.Schedule":
+    return self._beta_sched
 
   def _get_state(self):
     e = self._engine
@@ -365,7 +384,10 @@ class SingleCellModel:
                        "(the discriminator's permute_dims over stacked draws has no agreed reading)")
     from sisua_amd import data as _data
     from sisua_amd.parallel import ControlPlane, attach_engine, env_rank_world
-    self._opt = dict(lr=float(learning_rate), clipnorm=float(clipnorm or 0.0))
+    # the learning rate is a schedule record (a const one for a number), keyed by the rule's own count step - t0; the engine's config keeps a
+    # number (its value at count 0), the record itself is set on the engine -- on every rank of a data-parallel job alike
+    self._lr_sched = learning_rate
+    self._opt = dict(lr=float(learning_rate.value(0)), clipnorm=float(clipnorm or 0.0))
     n_lab = len(self._outputs) - 1 + len(self._labels)   # target arrays beside the counts: outputs[1:], then the label variables
     if len(train.arrays) < 1 + n_lab:
       raise ValueError(f"{type(self).__name__} needs {1 + n_lab} omics per batch, the dataset has {len(train.arrays)}")
@@ -420,6 +442,7 @@ class SingleCellModel:
       lib = np.concatenate([lib, valid.library], 0)
       mask = np.concatenate([mask, valid.mask], 0)
     e.upload(X, labs, lib, mask, cell_id_base=lo, storage=storage)   # Philox cell ids are GLOBAL: sharding-independent noise
+    self._apply_schedules(e)   # (before the first step: a resumed fit passes its learning-rate schedule again; the step keys both)
     if cp is not None:
       cp.barrier()   # every rank's shard is resident before the first collective (the exchange's waits are bounded: no upload skew inside them)
     seed_r = train.seed + 7919 * rank

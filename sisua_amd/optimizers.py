@@ -8,6 +8,8 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
+from sisua_amd import interpolation
+
 # name -> (smx_optimizer, ordered hyper-parameters with the tf.keras 2.x defaults; Adam's defaults are smx_config's)
 RULES: Dict[str, Tuple[int, Tuple[Tuple[str, float], ...]]] = {
     "adam": (0, (("beta_1", 0.9), ("beta_2", 0.999), ("epsilon", 1e-7))),
@@ -51,9 +53,11 @@ def canonical(name: str, **hp) -> Tuple[str, Dict[str, float]]:
   return key, out
 
 
-def resolve(optimizer, learning_rate: float, clipnorm: Optional[float]):
-  """fit()'s `optimizer` argument -> (rule name, hyper-parameters, learning_rate, clipnorm).  The dict form's `learning_rate` (or
-  `lr`) and `clipnorm` override fit's own arguments."""
+def resolve(optimizer, learning_rate, clipnorm: Optional[float]):
+  """fit()'s `optimizer` argument -> (rule name, hyper-parameters, learning-rate schedule, clipnorm).  The dict form's `learning_rate` (or
+  `lr`) and `clipnorm` override fit's own arguments.  The learning rate is a number or a schedule (sisua_amd.interpolation: a Keras
+  schedule in the registry's dict form or as a tf.keras object, or an interpolation); it comes back as an interpolation.Schedule record,
+  a const one for a number (equal to that number)."""
   if isinstance(optimizer, dict):
     if "class_name" not in optimizer:
       raise ValueError("optimizer dict needs 'class_name' (the Keras registry's form {'class_name': ..., 'config': {...}})")
@@ -64,13 +68,13 @@ def resolve(optimizer, learning_rate: float, clipnorm: Optional[float]):
     cfg.pop("name", None)   # (the Keras object's display name)
     for k in ("learning_rate", "lr"):
       if k in cfg:
-        learning_rate = float(cfg.pop(k))
+        learning_rate = cfg.pop(k)
     if "clipnorm" in cfg:
       clipnorm = cfg.pop("clipnorm")
     name, hp = canonical(optimizer["class_name"], **cfg)
   else:
     name, hp = canonical(optimizer)
-  return name, hp, float(learning_rate), clipnorm
+  return name, hp, interpolation.as_schedule(learning_rate, "learning_rate"), clipnorm
 
 
 def hp_vector(name: str, hp: Dict[str, float]) -> np.ndarray:
