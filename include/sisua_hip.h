@@ -75,7 +75,13 @@ typedef enum { SMX_LLK_NB = 0, SMX_LLK_ZINB = 1, SMX_LLK_NBD = 2, SMX_LLK_ZINBD 
  * components). */
 typedef enum { SMX_LABEL_NB = 0, SMX_LABEL_ONEHOT = 1, SMX_LABEL_MIXNB = 2, SMX_LABEL_MIXGAUSS = 3, SMX_LABEL_MIXTRIL = 4, SMX_LABEL_MIXZINB = 5,
                SMX_LABEL_NBD = 6, SMX_LABEL_ZINB = 7, SMX_LABEL_ZINBD = 8, SMX_LABEL_BERNOULLI = 9, SMX_LABEL_NORMAL = 10 } smx_label_likelihood;
-typedef enum { SMX_ACT_RELU = 0, SMX_ACT_LINEAR = 1 } smx_activation;
+/* Activations: smx_config.latent_activation (dca: RELU or LINEAR) and the hidden layers of each network (smx_set_activation: all of them).
+ * SMX_ACT_LEAKY_RELU has slope 0.2 (tf.nn.leaky_relu), SMX_ACT_ELU alpha 1, SMX_ACT_SELU the Keras constants lambda = 1.0507009873554805,
+ * alpha = 1.6732632423543772. */
+typedef enum { SMX_ACT_RELU = 0, SMX_ACT_LINEAR = 1, SMX_ACT_LEAKY_RELU = 2, SMX_ACT_ELU = 3, SMX_ACT_SELU = 4, SMX_ACT_TANH = 5,
+               SMX_ACT_SIGMOID = 6, SMX_ACT_SOFTPLUS = 7 } smx_activation;
+/* Networks of smx_set_activation. */
+typedef enum { SMX_NET_ENCODER = 0, SMX_NET_DECODER = 1, SMX_NET_LIBRARY_ENCODER = 2 } smx_network;
 /* Optimiser rules (smx_set_optimizer; tf.keras 2.x Adam, SGD, RMSprop, Adagrad, Adamax). */
 typedef enum { SMX_OPT_ADAM = 0, SMX_OPT_SGD = 1, SMX_OPT_RMSPROP = 2, SMX_OPT_ADAGRAD = 3, SMX_OPT_ADAMAX = 4 } smx_optimizer;
 #define SMX_OPT_MAX_HP 4
@@ -307,6 +313,12 @@ int smx_get_schedule(const smx_model* m, int32_t target, int32_t* kind, double* 
 /* Host evaluation of a schedule without a model or a device: out[i] = the float value at step first_step + i, i < count -- exactly what a
  * training step's table holds.  SMX_ERR_INVALID as smx_set_schedule. */
 int smx_schedule_eval(int32_t kind, const double* params, int32_t n, int64_t first_step, int32_t count, float* out);
+/* The activation of every hidden layer of one network: net = smx_network, act = smx_activation.  The default is SMX_ACT_RELU.  Latent and
+ * head layers, DCA's latent activation and the FactorVAE discriminator keep theirs.  Activations have no parameters: the tensor list does
+ * not change.  Layers other than ReLU take the general forms of the BatchNorm / activation launches; the fused forms that build ReLU in
+ * (latent-sample and gradient fronts, the paired first layers, the activation epilogues of the products) are not used for them.  Captured
+ * graphs are dropped.  SMX_ERR_INVALID for an unknown network or activation, or SMX_NET_LIBRARY_ENCODER on a model without one. */
+int smx_set_activation(smx_model* m, int32_t net, int32_t act);
 
 /* Eval-mode forward for predict/encode/decode (single_cell_model.py:119-211):
  * writes distribution parameters into caller-owned buffers (any may be NULL).

@@ -22,7 +22,12 @@ LIKELIHOODS = {"nb": 0, "zinb": 1, "nbd": 2, "zinbd": 3, "mse": 4}
 LABEL_LIKELIHOODS = {"nb": 0, "onehot": 1, "mixnb": 2, "mixgauss": 3, "mixtril": 4, "mixzinb": 5, "nbd": 6, "zinb": 7, "zinbd": 8,
                      "bernoulli": 9, "normal": 10}
 SCVI_PLANE_OPTIONS = {"full": 0, "share": 1, "single": 2}
-ACTIVATIONS = {"relu": 0, "linear": 1}
+ACTIVATIONS = {"relu": 0, "linear": 1}   # smx_config.latent_activation (dca)
+# smx_activation: hidden layers of a network (smx_set_activation)
+SMX_ACT_RELU, SMX_ACT_LINEAR, SMX_ACT_LEAKY_RELU, SMX_ACT_ELU, SMX_ACT_SELU, SMX_ACT_TANH, SMX_ACT_SIGMOID, SMX_ACT_SOFTPLUS = range(8)
+HIDDEN_ACTIVATIONS = {"relu": SMX_ACT_RELU, "linear": SMX_ACT_LINEAR, "leaky_relu": SMX_ACT_LEAKY_RELU, "elu": SMX_ACT_ELU,
+                      "selu": SMX_ACT_SELU, "tanh": SMX_ACT_TANH, "sigmoid": SMX_ACT_SIGMOID, "softplus": SMX_ACT_SOFTPLUS}
+SMX_NET_ENCODER, SMX_NET_DECODER, SMX_NET_LIBRARY_ENCODER = range(3)   # smx_network
 
 
 class SmxError(RuntimeError):
@@ -102,6 +107,7 @@ SIGNATURES = {
     "smx_get_schedule": (C.c_int, [_VP, C.c_int32, _IP, C.POINTER(C.c_double), C.c_int32, _IP]),
     "smx_schedule_eval": (C.c_int, [C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int64, C.c_int32, _FP]),
     "smx_get_optimizer": (C.c_int, [_VP, _IP, _FP, _IP]),
+    "smx_set_activation": (C.c_int, [_VP, C.c_int32, C.c_int32]),
     "smx_forward": (C.c_int, [_VP, _IP, _FP, _FP, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
                               C.POINTER(_FP)]),
     "smx_forward_samples": (C.c_int, [_VP, _IP, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP,

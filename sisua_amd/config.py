@@ -75,11 +75,32 @@ class RVmeta:
     return dataclasses.replace(self, kwargs=dict(self.kwargs))
 
 
+# Hidden-layer activations of NetConf (smx_set_activation; sisua_amd/csrc/smx_act.h).  'leaky_relu' has slope 0.2 ([3P-recall]
+# tf.nn.leaky_relu's default), 'elu' alpha 1, 'selu' the Keras constants.
+ACTIVATION_FIELDS = ("enc_activation", "dec_activation", "encl_activation")   # of ModelConfig
+HIDDEN_ACTIVATIONS = ("relu", "linear", "leaky_relu", "elu", "selu", "tanh", "sigmoid", "softplus")
+_ACTIVATION_ALIASES = {"identity": "linear"}
+
+
+def hidden_activation(name) -> str:
+  """Canonical name of a hidden-layer activation: case-insensitive, None / 'identity' = 'linear'.  ValueError for anything that is
+  not built (callables, 'swish', 'gelu', 'softmax', ...)."""
+  if name is None:
+    return "linear"
+  if not isinstance(name, str):
+    raise ValueError(f"NetConf activation {name!r} is not built: give one of {', '.join(HIDDEN_ACTIVATIONS)} (or None / 'identity')")
+  key = name.strip().lower()
+  key = _ACTIVATION_ALIASES.get(key, key)
+  if key not in HIDDEN_ACTIVATIONS:
+    raise ValueError(f"NetConf activation '{name}' is not built: give one of {', '.join(HIDDEN_ACTIVATIONS)} (or None / 'identity')")
+  return key
+
+
 @dataclass
 class NetConf:
-  """MLP description: NetConf(units, batchnorm, dropout, input_dropout)
+  """MLP description: NetConf(units, batchnorm, dropout, input_dropout, activation)
   (configs/base.yaml:10-17; single_cell_model.py:78-81).  Block order is
-  Dense -> BatchNorm -> ReLU -> Dropout (frozen third-party semantics)."""
+  Dense -> BatchNorm -> activation -> Dropout (frozen third-party semantics); `activation` is one of HIDDEN_ACTIVATIONS."""
   units: Sequence[int] = (64, 64)
   batchnorm: bool = True
   dropout: float = 0.0
@@ -89,7 +110,7 @@ class NetConf:
 
   def __post_init__(self):
     self.units = tuple(int(u) for u in (self.units if isinstance(self.units, (tuple, list)) else [self.units]))
-    assert self.activation == "relu", "only relu hidden activations are built"
+    self.activation = hidden_activation(self.activation)
 
   def copy(self):
     return dataclasses.replace(self)
@@ -122,6 +143,11 @@ class ModelConfig:
   alpha: float = 10.0
   latent_activation: str = "relu"
   clip_library: float = 1e3
+  # hidden-layer activations of the encoder / decoder / library encoder (NetConf.activation; HIDDEN_ACTIVATIONS).  Not in oracle.Spec:
+  # the engine sets them after creation (smx_set_activation), the tensor list does not depend on them
+  enc_activation: str = "relu"
+  dec_activation: str = "relu"
+  encl_activation: str = "relu"
   bn_momentum: float = 0.99
   bn_eps: float = 1e-3
   lr: float = 1e-3
@@ -147,6 +173,8 @@ class ModelConfig:
   disc_leak: float = 0.2
 
   def __post_init__(self):
+    for f in ACTIVATION_FIELDS:
+      object.__setattr__(self, f, hidden_activation(getattr(self, f)))
     for P, kind in tuple(self.extra_outputs) + tuple(self.labels):
       if not (kind in HEAD_KINDS or (kind[:-1] in MIXTURE_HEAD_KINDS and kind[-1] in "234")):
         raise ValueError(f"unknown head kind {kind!r} (built: {', '.join(HEAD_KINDS)}, and the mixtures {', '.join(k + 'C' for k in MIXTURE_HEAD_KINDS)} with C = 2..4)")
@@ -201,7 +229,13 @@ class ModelConfig:
     return (c == 1 and self.dispersion == "single") or (c == 2 and self.inflation == "single")
 
   def to_dict(self):
-    return dataclasses.asdict(self)
+    """The fields as keyword arguments of oracle.Spec: the hidden-layer activations are left out while they are 'relu' (Spec has
+    no such fields; a configuration with another activation keeps them, and Spec refuses it)."""
+    d = dataclasses.asdict(self)
+    for f in ACTIVATION_FIELDS:
+      if d[f] == "relu":
+        del d[f]
+    return d
 
 
 def manifest(cfg: ModelConfig) -> List[Tuple[str, Tuple[int, ...]]]:

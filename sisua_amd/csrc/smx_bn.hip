@@ -208,7 +208,7 @@ __device__ inline void latent_tile_to_lds(const LatentArgs& a, float* zs, bool s
   SMX_STAMP(1, 9);   // sample + KL computed, LDS / global stores issued
 }
 
-template <int RPT, int FRONT>
+template <int RPT, int FRONT, bool GEN_ACT = false>
 __device__ inline void bn_act_fwd_body(const BnFwdArgs& a, const int bid) {
   constexpr bool SMALL = RPT > 0;
   constexpr int BN_RPT = SMALL ? RPT : BN_RPT_DEFAULT;
@@ -397,8 +397,12 @@ __device__ inline void bn_act_fwd_body(const BnFwdArgs& a, const int bid) {
       y = __builtin_fmaf(gamma, v, beta);
     }
     if (a.batchnorm || SMALL) a.xhat[o] = v;
-    float h = fmaxf(y, 0.f);
-    if (a.leak != 0.f) h += a.leak * fminf(y, 0.f);
+    float h;
+    if constexpr (GEN_ACT) h = act_fwd(a.act, y);
+    else {
+      h = fmaxf(y, 0.f);
+      if (a.leak != 0.f) h += a.leak * fminf(y, 0.f);
+    }
     if (drop) {
       float mult;
       if (a.inj_mask) mult = SMALL ? mahead : a.inj_mask[(long)r * a.inj_ld + col];
@@ -423,6 +427,9 @@ __device__ inline void bn_act_fwd_body(const BnFwdArgs& a, const int bid) {
 
 template <int RPT, int FRONT = 0>
 __global__ __launch_bounds__(BN_THREADS) void bn_act_fwd_kernel(BnFwdArgs a) { bn_act_fwd_body<RPT, FRONT>(a, (int)blockIdx.x); }
+// hidden layers whose activation is not ReLU (BnFwdArgs::act; smx_act.h): the plain forms only (no front)
+template <int RPT>
+__global__ __launch_bounds__(BN_THREADS) void bn_act_fwd_gen_kernel(BnFwdArgs a) { bn_act_fwd_body<RPT, 0, true>(a, (int)blockIdx.x); }
 // two independent layers over the same minibatch in ONE launch (scvi: first layers of the encoder and of the library
 // encoder): blocks [0, na) belong to a (its column blocks, then its noise jobs), the rest to b
 template <int RPT>
@@ -434,6 +441,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_act_fwd_dual_kernel(BnFwdArgs a
 
 __global__ void bn_wide_fwd_kernel(BnFwdArgs a);   // (below: the forms that sum a wide panel's column-major slabs themselves)
 __global__ void bn_wide_bwd_kernel(BnBwdArgs a);
+__global__ void bn_wide_fwd_gen_kernel(BnFwdArgs a);
+__global__ void bn_wide_bwd_gen_kernel(BnBwdArgs a);
 
 bool bn_front_supported(int B, int Dp) {
   const int dq = Dp >> 2;
@@ -442,6 +451,8 @@ bool bn_front_supported(int B, int Dp) {
 
 int launch_bn_act_fwd(hipStream_t st, const BnFwdArgs& a_in) {
   BnFwdArgs a = a_in;
+  const bool gen = a.act != SMX_ACT_RELU;   // (GEN_ACT forms: the plain and wide ones)
+  if (gen && (a.act < SMX_ACT_RELU || a.act > SMX_ACT_SOFTPLUS || a.front)) { set_error("bn_act_fwd: activations other than ReLU take no front"); return SMX_ERR_INVALID; }
   if (a.front) {
     if (!bn_front_supported(a.B, a.lat.Dp) || a.n_jobs || !a.W || (a.lat.ld % 4) || (a.lat.inj_eps && (a.lat.inj_ld % 4)) ||
         (a.lat.Dp > 32 && a.lat.Dp != 64 && a.lat.Dp != 128)) {
@@ -469,11 +480,21 @@ int launch_bn_act_fwd(hipStream_t st, const BnFwdArgs& a_in) {
   if (a.Hp % BN_COLS || a.B <= 0) { set_error("bn_act_fwd: bad shapes"); return SMX_ERR_INVALID; }
   if (a.wide) {
     if (a.B > 128 || a.Hp > 128 || !a.pre || !a.xhat || a.slab_stride < (long)a.Hp * 128 || (a.slab_stride % 4)) { set_error("bn_act_fwd: wide slabs take at most 128 x 128"); return SMX_ERR_INVALID; }
-    hipLaunchKernelGGL(bn_wide_fwd_kernel, dim3(a.Hp + a.n_jobs * SMX_NOISE_BLOCKS_PER_JOB), dim3(BN_THREADS), 0, st, a);
+    if (gen) hipLaunchKernelGGL(bn_wide_fwd_gen_kernel, dim3(a.Hp + a.n_jobs * SMX_NOISE_BLOCKS_PER_JOB), dim3(BN_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(bn_wide_fwd_kernel, dim3(a.Hp + a.n_jobs * SMX_NOISE_BLOCKS_PER_JOB), dim3(BN_THREADS), 0, st, a);
     SMX_HIP(hipGetLastError());
     return SMX_OK;
   }
   const int grid = a.Hp / BN_COLS + a.n_jobs * SMX_NOISE_BLOCKS_PER_JOB;
+  if (gen) {
+    if (a.B <= BN_RL * 2) hipLaunchKernelGGL(bn_act_fwd_gen_kernel<2>, dim3(grid), dim3(BN_THREADS), 0, st, a);
+    else if (a.B <= BN_RL * 4) hipLaunchKernelGGL(bn_act_fwd_gen_kernel<4>, dim3(grid), dim3(BN_THREADS), 0, st, a);
+    else if (a.B <= BN_RL * 8) hipLaunchKernelGGL(bn_act_fwd_gen_kernel<8>, dim3(grid), dim3(BN_THREADS), 0, st, a);
+    else if (a.B <= BN_RL * 16) hipLaunchKernelGGL(bn_act_fwd_gen_kernel<16>, dim3(grid), dim3(BN_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(bn_act_fwd_gen_kernel<0>, dim3(grid), dim3(BN_THREADS), 0, st, a);
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
+  }
   if (a.B <= BN_RL * 2) hipLaunchKernelGGL(bn_act_fwd_kernel<2>, dim3(grid), dim3(BN_THREADS), 0, st, a);
   else if (a.B <= BN_RL * 4) hipLaunchKernelGGL(bn_act_fwd_kernel<4>, dim3(grid), dim3(BN_THREADS), 0, st, a);
   else if (a.B <= BN_RL * 8) hipLaunchKernelGGL(bn_act_fwd_kernel<8>, dim3(grid), dim3(BN_THREADS), 0, st, a);
@@ -486,8 +507,9 @@ int launch_bn_act_fwd(hipStream_t st, const BnFwdArgs& a_in) {
 // two layers over the same minibatch, one launch (no latent front, no SyncBatchNorm; register-resident forms only)
 bool bn_dual_supported(int B) { return B > 0 && B <= BN_RL * 4; }
 int launch_bn_act_fwd_dual(hipStream_t st, const BnFwdArgs& a, const BnFwdArgs& b) {
-  if (a.front || b.front || b.n_jobs || a.B != b.B || !bn_dual_supported(a.B) || a.Hp % BN_COLS || b.Hp % BN_COLS) {
-    set_error("bn_act_fwd_dual: bad shapes");
+  if (a.front || b.front || b.n_jobs || a.B != b.B || !bn_dual_supported(a.B) || a.Hp % BN_COLS || b.Hp % BN_COLS || a.act != SMX_ACT_RELU ||
+      b.act != SMX_ACT_RELU) {
+    set_error("bn_act_fwd_dual: bad shapes (or an activation other than ReLU)");
     return SMX_ERR_INVALID;
   }
   const int na = a.Hp / BN_COLS + a.n_jobs * SMX_NOISE_BLOCKS_PER_JOB;
@@ -589,7 +611,20 @@ __device__ inline void fold_dz_tile(const BnBwdArgs& a, const int bid, float* ti
     }
 }
 
-template <int RPT, int FRONT>
+// GEN_ACT forms: the multiplier the forward applied to element (r, col) -- from the same source, bit for bit (BnBwdArgs::act)
+__device__ inline float bn_keep(const BnBwdArgs& a, int r, int col) {
+  if (!(a.drop_p > 0.f)) return a.drop_scale;
+  if (a.inj_mask) return a.inj_mask[(long)r * a.inj_ld + col];
+  const uint32_t cell = a.cell_base + (uint32_t)(a.rows ? a.rows[r] : r);
+  return dropout_mult1(philox_row(a.nk, (uint32_t)r, cell, (uint32_t)(col >> 2)), col & 3, a.drop_p, a.drop_scale);
+}
+// ... and d out -> d y of that element: xv is the layer's xhat (y itself without BatchNorm)
+__device__ inline float bn_gen_dy(const BnBwdArgs& a, int r, int col, float dout, float xv, float gamma, float beta) {
+  const float y = a.batchnorm ? __builtin_fmaf(gamma, xv, beta) : xv;   // (the forward's y, bit for bit)
+  return dout * bn_keep(a, r, col) * act_grad(a.act, act_fwd(a.act, y));
+}
+
+template <int RPT, int FRONT, bool GEN_ACT = false>
 __device__ inline void bn_act_bwd_body(const BnBwdArgs& a, const int bid) {
   constexpr bool SMALL = RPT > 0;
   constexpr int BN_RPT = SMALL ? RPT : BN_RPT_DEFAULT;
@@ -626,10 +661,14 @@ __device__ inline void bn_act_bwd_body(const BnBwdArgs& a, const int bid) {
 #pragma unroll
     for (int i = 0; i < BN_RPT; ++i) {
       const long o = (long)min(rl + BN_RL * i, a.B - 1) * a.Hp + col;
-      outpre[i] = a.out[o];
-      xhpre[i] = a.batchnorm ? a.xhat[o] : 0.f;
+      if constexpr (!GEN_ACT) outpre[i] = a.out[o];
+      xhpre[i] = (GEN_ACT || a.batchnorm) ? a.xhat[o] : 0.f;
     }
     if (a.batchnorm) { gamma_pre = live ? a.gamma[col] : 0.f; inv_pre = a.inv_std[col]; }
+  }
+  float gamma_g = 0.f, beta_g = 0.f;   // (GEN_ACT: y = gamma xhat + beta inside the row loop)
+  if constexpr (GEN_ACT) {
+    if (a.batchnorm && live) { gamma_g = a.gamma[col]; beta_g = a.beta[col]; }
   }
   constexpr int FK = FRONT == 2 ? 128 : 64;   // FRONT = 2: K = 128 exactly (see bn_act_fwd_body)
   float wrow[FRONT ? FK : 1];
@@ -704,10 +743,16 @@ __device__ inline void bn_act_bwd_body(const BnBwdArgs& a, const int bid) {
       float dy = 0.f, xh = 0.f;
       if (r < a.B) {
         const long o = (long)r * a.Hp + col;
+        if constexpr (GEN_ACT) {
+          const float xv = SMALL ? xhpre[i] : a.xhat[o];
+          dy = live ? bn_gen_dy(a, r, col, acc[i], xv, gamma_g, beta_g) : 0.f;
+          if (a.batchnorm) xh = xv;
+        } else {
         const float ov = SMALL ? outpre[i] : a.out[o];
         dy = (live && ov > 0.f) ? acc[i] * a.drop_scale : 0.f;
         if (a.leak != 0.f && live && !(ov > 0.f)) dy = acc[i] * a.leak;
         if (a.batchnorm) xh = SMALL ? xhpre[i] : a.xhat[o];
+        }
         if (!SMALL) a.dpre[o] = dy;
         s1 += dy;
         { // (product, then sum: not fused -- see the moving statistics of bn_act_fwd_body)
@@ -754,6 +799,8 @@ __device__ inline void bn_act_bwd_body(const BnBwdArgs& a, const int bid) {
 
 template <int RPT, int FRONT = 0>
 __global__ __launch_bounds__(BN_THREADS) void bn_act_bwd_kernel(BnBwdArgs a) { bn_act_bwd_body<RPT, FRONT>(a, (int)blockIdx.x); }
+template <int RPT>
+__global__ __launch_bounds__(BN_THREADS) void bn_act_bwd_gen_kernel(BnBwdArgs a) { bn_act_bwd_body<RPT, 0, true>(a, (int)blockIdx.x); }
 // two independent layers in ONE launch, both with the gradient front (scvi: last layers of the encoder and of the
 // library encoder): blocks [0, na) belong to a (column blocks, then its riders), the rest to b (no riders)
 template <int RPT>
@@ -770,6 +817,11 @@ bool bn_bwd_front_supported(int B, int K) {
 
 int launch_bn_act_bwd(hipStream_t st, const BnBwdArgs& a_in) {
   BnBwdArgs a = a_in;
+  const bool gen = a.act != SMX_ACT_RELU;
+  if (gen && (a.act < SMX_ACT_RELU || a.act > SMX_ACT_SOFTPLUS || a.front || !a.xhat || (a.batchnorm && !a.beta))) {
+    set_error("bn_act_bwd: activations other than ReLU take no gradient front and need xhat (and beta)");
+    return SMX_ERR_INVALID;
+  }
   if (a.front) {
     if (!bn_bwd_front_supported(a.B, a.fK) || !a.fD || !a.fW || (a.fld % 4) || (a.fldw % 4) || a.Hp % BN_COLS) {
       set_error("bn_act_bwd: gradient front not applicable");
@@ -805,11 +857,21 @@ int launch_bn_act_bwd(hipStream_t st, const BnBwdArgs& a_in) {
   if (a.Hp % BN_COLS || a.B <= 0) { set_error("bn_act_bwd: bad shapes"); return SMX_ERR_INVALID; }
   if (a.wide) {
     if (a.B > 128 || a.Hp > 128 || !a.dout || a.slab_stride < (long)a.Hp * 128 || (a.slab_stride % 4)) { set_error("bn_act_bwd: wide slabs take at most 128 x 128"); return SMX_ERR_INVALID; }
-    hipLaunchKernelGGL(bn_wide_bwd_kernel, dim3(a.Hp + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count), dim3(BN_THREADS), 0, st, a);
+    if (gen) hipLaunchKernelGGL(bn_wide_bwd_gen_kernel, dim3(a.Hp + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count), dim3(BN_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(bn_wide_bwd_kernel, dim3(a.Hp + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count), dim3(BN_THREADS), 0, st, a);
     SMX_HIP(hipGetLastError());
     return SMX_OK;
   }
   const int grid = a.Hp / BN_COLS + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count;
+  if (gen) {
+    if (a.B <= BN_RL * 2) hipLaunchKernelGGL(bn_act_bwd_gen_kernel<2>, dim3(grid), dim3(BN_THREADS), 0, st, a);
+    else if (a.B <= BN_RL * 4) hipLaunchKernelGGL(bn_act_bwd_gen_kernel<4>, dim3(grid), dim3(BN_THREADS), 0, st, a);
+    else if (a.B <= BN_RL * 8) hipLaunchKernelGGL(bn_act_bwd_gen_kernel<8>, dim3(grid), dim3(BN_THREADS), 0, st, a);
+    else if (a.B <= BN_RL * 16) hipLaunchKernelGGL(bn_act_bwd_gen_kernel<16>, dim3(grid), dim3(BN_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(bn_act_bwd_gen_kernel<0>, dim3(grid), dim3(BN_THREADS), 0, st, a);
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
+  }
   if (a.B <= BN_RL * 2) hipLaunchKernelGGL(bn_act_bwd_kernel<2>, dim3(grid), dim3(BN_THREADS), 0, st, a);
   else if (a.B <= BN_RL * 4) hipLaunchKernelGGL(bn_act_bwd_kernel<4>, dim3(grid), dim3(BN_THREADS), 0, st, a);
   else if (a.B <= BN_RL * 8) hipLaunchKernelGGL(bn_act_bwd_kernel<8>, dim3(grid), dim3(BN_THREADS), 0, st, a);
@@ -826,7 +888,7 @@ int launch_bn_act_bwd_dual(hipStream_t st, const BnBwdArgs& a_in, const BnBwdArg
   auto ok = [](const BnBwdArgs& x) {
     return x.front && x.fK <= 64 && bn_bwd_front_supported(x.B, x.fK) && x.fD && x.fW && !(x.fld % 4) && !(x.fldw % 4) && !(x.Hp % BN_COLS);
   };
-  if (!ok(a) || !ok(b) || a.B != b.B || !bn_dual_supported(a.B) || b.with_metrics || b.adam_count || b.sqr_count) {
+  if (!ok(a) || !ok(b) || a.B != b.B || !bn_dual_supported(a.B) || b.with_metrics || b.adam_count || b.sqr_count || a.act != SMX_ACT_RELU || b.act != SMX_ACT_RELU) {
     set_error("bn_act_bwd_dual: gradient fronts not applicable");
     return SMX_ERR_INVALID;
   }
@@ -880,7 +942,8 @@ __device__ inline float wide_tree64(float p) { return wave_sum(p); }   // (lane 
 
 // (Which multiply-adds the compiler fuses in bn_act_fwd_body / bn_act_bwd_body<2, 0> was read off their ISA; the kernels below spell the
 // same operations out with contraction switched off, so that the two forms stay equal bit for bit.)
-__global__ __launch_bounds__(BN_THREADS) void bn_wide_fwd_kernel(BnFwdArgs a) {
+template <bool GEN_ACT>
+__device__ inline void bn_wide_fwd_body(const BnFwdArgs& a) {
 #pragma clang fp contract(off)
   const int bid = (int)blockIdx.x;
   if (bid >= a.Hp) { noise_fill(a, bid - a.Hp); return; }
@@ -948,8 +1011,12 @@ __global__ __launch_bounds__(BN_THREADS) void bn_wide_fwd_kernel(BnFwdArgs a) {
     y = __builtin_fmaf(gamma, v, beta);
   }
   a.xhat[o] = v;
-  float h = fmaxf(y, 0.f);
-  if (a.leak != 0.f) h += a.leak * fminf(y, 0.f);
+  float h;
+  if constexpr (GEN_ACT) h = act_fwd(a.act, y);
+  else {
+    h = fmaxf(y, 0.f);
+    if (a.leak != 0.f) h += a.leak * fminf(y, 0.f);
+  }
   if (drop) {
     float mult = mpre;
     if (!a.inj_mask) {
@@ -962,8 +1029,11 @@ __global__ __launch_bounds__(BN_THREADS) void bn_wide_fwd_kernel(BnFwdArgs a) {
   a.out[o] = live ? h : 0.f;
   SMX_STAMP(0, 6);   // stores issued
 }
+__global__ __launch_bounds__(BN_THREADS) void bn_wide_fwd_kernel(BnFwdArgs a) { bn_wide_fwd_body<false>(a); }
+__global__ __launch_bounds__(BN_THREADS) void bn_wide_fwd_gen_kernel(BnFwdArgs a) { bn_wide_fwd_body<true>(a); }
 
-__global__ __launch_bounds__(BN_THREADS) void bn_wide_bwd_kernel(BnBwdArgs a) {
+template <bool GEN_ACT>
+__device__ inline void bn_wide_bwd_body(const BnBwdArgs& a) {
 #pragma clang fp contract(off)
   const int bid = (int)blockIdx.x;
   {
@@ -987,12 +1057,21 @@ __global__ __launch_bounds__(BN_THREADS) void bn_wide_bwd_kernel(BnBwdArgs a) {
   const bool live = col < a.H, rowt = r < 128, on = rowt && r < a.B;
   // what the activation mask and the BatchNorm formula need of the forward pass, requested ahead of the slabs
   float ov = 0.f, xh = 0.f, gamma = 0.f, inv = 0.f;
+  float xv = 0.f, beta = 0.f;   // (GEN_ACT: xhat of every layer, beta)
   if (on) {
     const long o = (long)r * a.Hp + col;
-    ov = a.out[o];
-    if (a.batchnorm) xh = a.xhat[o];
+    if constexpr (GEN_ACT) {
+      xv = a.xhat[o];
+      if (a.batchnorm) xh = xv;
+    } else {
+      ov = a.out[o];
+      if (a.batchnorm) xh = a.xhat[o];
+    }
   }
   if (a.batchnorm) { gamma = live ? a.gamma[col] : 0.f; inv = a.inv_std[col]; }
+  if constexpr (GEN_ACT) {
+    if (a.batchnorm && live) beta = a.beta[col];
+  }
   SMX_STAMP(2, 0);
   wide_slab_column(a.dout, a.slab_stride, a.n_slabs, col, sh);
   SMX_STAMP(2, 3);
@@ -1000,8 +1079,11 @@ __global__ __launch_bounds__(BN_THREADS) void bn_wide_bwd_kernel(BnBwdArgs a) {
   float dy = 0.f;
   if (on) {
     const float acc = wide_row_value(sh, r);
-    dy = (live && ov > 0.f) ? acc * a.drop_scale : 0.f;
-    if (a.leak != 0.f && live && !(ov > 0.f)) dy = acc * a.leak;
+    if constexpr (GEN_ACT) dy = live ? bn_gen_dy(a, r, col, acc, xv, gamma, beta) : 0.f;
+    else {
+      dy = (live && ov > 0.f) ? acc * a.drop_scale : 0.f;
+      if (a.leak != 0.f && live && !(ov > 0.f)) dy = acc * a.leak;
+    }
   }
   if (rowt) { vs[r] = dy; xs[r] = xh; }
   __syncthreads();
@@ -1030,6 +1112,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_wide_bwd_kernel(BnBwdArgs a) {
   a.dpre[(long)r * a.Hp + col] = d;
   SMX_STAMP(2, 6);
 }
+__global__ __launch_bounds__(BN_THREADS) void bn_wide_bwd_kernel(BnBwdArgs a) { bn_wide_bwd_body<false>(a); }
+__global__ __launch_bounds__(BN_THREADS) void bn_wide_bwd_gen_kernel(BnBwdArgs a) { bn_wide_bwd_body<true>(a); }
 
 bool bn_wide_supported(int B, int Hp, int n_slabs) { return B > 0 && B <= 128 && Hp > 0 && Hp <= 128 && n_slabs > 0 && !tuning_on("no_bn_wide"); }
 
@@ -1067,7 +1151,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_sync_stats_fwd_kernel(BnFwdArgs
     }
 }
 
-__global__ __launch_bounds__(BN_THREADS) void bn_sync_apply_fwd_kernel(BnFwdArgs a, BnSyncArgs y) {
+template <bool GEN_ACT>
+__device__ inline void bn_sync_apply_fwd_body(const BnFwdArgs& a, const BnSyncArgs& y) {
   const int c = threadIdx.x % BN_COLS, rl = threadIdx.x / BN_COLS;
   const int col = blockIdx.x * BN_COLS + c;
   const bool live = col < a.H;
@@ -1092,7 +1177,9 @@ __global__ __launch_bounds__(BN_THREADS) void bn_sync_apply_fwd_kernel(BnFwdArgs
     const long o = (long)r * a.Hp + col;
     const float v = (a.xhat[o] - mean) * inv;
     a.xhat[o] = v;
-    float h = fmaxf(gamma * v + beta, 0.f);
+    float h;
+    if constexpr (GEN_ACT) h = act_fwd(a.act, __builtin_fmaf(gamma, v, beta));   // (the y bn_gen_dy recomputes)
+    else h = fmaxf(gamma * v + beta, 0.f);
     if (drop) {
       float mult;
       if (a.inj_mask) mult = a.inj_mask[(long)r * a.inj_ld + col];
@@ -1105,12 +1192,19 @@ __global__ __launch_bounds__(BN_THREADS) void bn_sync_apply_fwd_kernel(BnFwdArgs
     a.out[o] = live ? h : 0.f;
   }
 }
+__global__ __launch_bounds__(BN_THREADS) void bn_sync_apply_fwd_kernel(BnFwdArgs a, BnSyncArgs y) { bn_sync_apply_fwd_body<false>(a, y); }
+__global__ __launch_bounds__(BN_THREADS) void bn_sync_apply_fwd_gen_kernel(BnFwdArgs a, BnSyncArgs y) { bn_sync_apply_fwd_body<true>(a, y); }
 
-__global__ __launch_bounds__(BN_THREADS) void bn_sync_stats_bwd_kernel(BnBwdArgs a, BnSyncArgs y) {
+template <bool GEN_ACT>
+__device__ inline void bn_sync_stats_bwd_body(const BnBwdArgs& a, const BnSyncArgs& y) {
   __shared__ float sh[BN_WAVES * BN_COLS];
   const int c = threadIdx.x % BN_COLS, rl = threadIdx.x / BN_COLS;
   const int col = blockIdx.x * BN_COLS + c;
   const bool live = col < a.H;
+  float gamma_g = 0.f, beta_g = 0.f;
+  if constexpr (GEN_ACT) {
+    if (live) { gamma_g = a.gamma[col]; beta_g = a.beta[col]; }
+  }
   float s1 = 0.f, s2 = 0.f;
   for (int r0 = 0; r0 < a.B; r0 += BN_RL * 2) {
     float acc[2];
@@ -1120,7 +1214,9 @@ __global__ __launch_bounds__(BN_THREADS) void bn_sync_stats_bwd_kernel(BnBwdArgs
       const int r = r0 + rl + BN_RL * i;
       if (r < a.B) {
         const long o = (long)r * a.Hp + col;
-        const float dy = (live && a.out[o] > 0.f) ? acc[i] * a.drop_scale : 0.f;
+        float dy;
+        if constexpr (GEN_ACT) dy = live ? bn_gen_dy(a, r, col, acc[i], a.xhat[o], gamma_g, beta_g) : 0.f;
+        else dy = (live && a.out[o] > 0.f) ? acc[i] * a.drop_scale : 0.f;
         a.dpre[o] = dy;
         s1 += dy;
         s2 += dy * a.xhat[o];
@@ -1139,6 +1235,8 @@ __global__ __launch_bounds__(BN_THREADS) void bn_sync_stats_bwd_kernel(BnBwdArgs
     }
   }
 }
+__global__ __launch_bounds__(BN_THREADS) void bn_sync_stats_bwd_kernel(BnBwdArgs a, BnSyncArgs y) { bn_sync_stats_bwd_body<false>(a, y); }
+__global__ __launch_bounds__(BN_THREADS) void bn_sync_stats_bwd_gen_kernel(BnBwdArgs a, BnSyncArgs y) { bn_sync_stats_bwd_body<true>(a, y); }
 
 __global__ __launch_bounds__(BN_THREADS) void bn_sync_apply_bwd_kernel(BnBwdArgs a, BnSyncArgs y) {
   const int c = threadIdx.x % BN_COLS, rl = threadIdx.x / BN_COLS;
@@ -1161,13 +1259,16 @@ __global__ __launch_bounds__(BN_THREADS) void bn_sync_apply_bwd_kernel(BnBwdArgs
 int launch_bn_sync_fwd(hipStream_t st, const BnFwdArgs& a, const BnSyncArgs& y, int phase) {
   if (a.Hp % BN_COLS || a.B <= 0 || !a.batchnorm || !a.training || y.world < 1 || !y.gather) { set_error("bn_sync_fwd: bad arguments"); return SMX_ERR_INVALID; }
   if (phase == 0) hipLaunchKernelGGL(bn_sync_stats_fwd_kernel, dim3(a.Hp / BN_COLS), dim3(BN_THREADS), 0, st, a, y);
+  else if (a.act != SMX_ACT_RELU) hipLaunchKernelGGL(bn_sync_apply_fwd_gen_kernel, dim3(a.Hp / BN_COLS), dim3(BN_THREADS), 0, st, a, y);
   else hipLaunchKernelGGL(bn_sync_apply_fwd_kernel, dim3(a.Hp / BN_COLS), dim3(BN_THREADS), 0, st, a, y);
   SMX_HIP(hipGetLastError());
   return SMX_OK;
 }
 int launch_bn_sync_bwd(hipStream_t st, const BnBwdArgs& a, const BnSyncArgs& y, int phase) {
   if (a.Hp % BN_COLS || a.B <= 0 || !a.batchnorm || !a.training || y.world < 1 || !y.gather) { set_error("bn_sync_bwd: bad arguments"); return SMX_ERR_INVALID; }
-  if (phase == 0) hipLaunchKernelGGL(bn_sync_stats_bwd_kernel, dim3(a.Hp / BN_COLS), dim3(BN_THREADS), 0, st, a, y);
+  if (a.act != SMX_ACT_RELU && (!a.xhat || !a.beta)) { set_error("bn_sync_bwd: activations other than ReLU need xhat and beta"); return SMX_ERR_INVALID; }
+  if (phase == 0 && a.act != SMX_ACT_RELU) hipLaunchKernelGGL(bn_sync_stats_bwd_gen_kernel, dim3(a.Hp / BN_COLS), dim3(BN_THREADS), 0, st, a, y);
+  else if (phase == 0) hipLaunchKernelGGL(bn_sync_stats_bwd_kernel, dim3(a.Hp / BN_COLS), dim3(BN_THREADS), 0, st, a, y);
   else hipLaunchKernelGGL(bn_sync_apply_bwd_kernel, dim3(a.Hp / BN_COLS), dim3(BN_THREADS), 0, st, a, y);
   SMX_HIP(hipGetLastError());
   return SMX_OK;

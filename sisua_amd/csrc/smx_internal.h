@@ -6,6 +6,7 @@
 #include <string>
 
 #include "smx_device.h"
+#include "smx_act.h"
 #include "../../include/sisua_hip.h"
 
 namespace smx {
@@ -204,6 +205,7 @@ struct BnFwdArgs {
   // wide != 0: `pre` holds HUNDREDS of slabs (one per workgroup of a wide-panel product: smx_bigk.hip), each COLUMN-major [Hp][128 rows]; the
   // launch sums them itself, one workgroup per column, in the order of bigk_reduce_kernel (bn_wide_fwd_kernel: no reduce launch)
   int wide = 0;
+  int act = SMX_ACT_RELU;   // smx_activation of the layer: anything else takes the GEN_ACT forms (smx_act.h; leak unused there)
 };
 bool bn_wide_supported(int B, int Hp, int n_slabs);
 int launch_bn_act_fwd(hipStream_t st, const BnFwdArgs& a);
@@ -318,6 +320,13 @@ struct BnBwdArgs {
   int diag = 0;   // SMX_BN_DIAG bits 16 / 32 / 64: skip the front's dot products / tile load / W row load (timing only)
   float leak = 0.f;   // slope of the activation for out <= 0 (layers without dropout only)
   int wide = 0;       // as BnFwdArgs::wide: `dout` = column-major slabs [n_slabs][Hp][128], summed here (bn_wide_bwd_kernel)
+  // act != SMX_ACT_RELU (the GEN_ACT forms): the derivative comes from h = act(y), y recomputed from xhat (gamma xhat + beta with BatchNorm,
+  // xhat itself without: the forward leaves y there), and the keep mask from the forward's own source -- the injected mask or the Philox
+  // block of (nk, row, cell, column) -- since out == 0 does not tell a dropped unit from a kept one whose h is 0
+  int act = SMX_ACT_RELU; const float* beta = nullptr;
+  float drop_p = 0.f; NoiseKey nk{0, 0, 0, 0, nullptr};
+  const int32_t* rows = nullptr; uint32_t cell_base = 0;
+  const float* inj_mask = nullptr; int inj_ld = 0;
 };
 bool bn_bwd_front_supported(int B, int K);
 bool bn_bwd_fold_supported(int B, int fK, int Dp);   // BnBwdArgs::fold_dz
@@ -489,6 +498,7 @@ struct ScoreBnArgs {
   float eps = 1e-3f, leak = 0.f;
   float* out_t = nullptr; long ldt = 0;   // non-null: write the result transposed, out_t [Hp][ldt] (gamma may then be null: plain transpose)
   __bf16* out3 = nullptr;                 // non-null: write the result as its three-way bf16 split [3][R][Hp] (gamma may be null)
+  int act = SMX_ACT_RELU;                 // anything else: the GEN_ACT kernels, which apply act() with or without gamma (bias already added)
 };
 // a one-layer decoder with BatchNorm over the stacked rows in one launch (draws + product + BatchNorm + activation + split): score_decoder1_kernel
 struct ScoreDec1Args {

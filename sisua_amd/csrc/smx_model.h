@@ -66,6 +66,7 @@ struct MlpLayer {
   int stream = 0;
   float drop_p = 0.f;
   float leak = 0.f;         // activation slope for y <= 0 (0: ReLU; the FactorVAE discriminator: 0.2)
+  int act = SMX_ACT_RELU;   // smx_activation of the hidden layer (smx_set_activation); not ReLU: the GEN_ACT forms of the launches, leak unused
   float *xhat = nullptr, *out_buf = nullptr, *inv_std = nullptr, *dpre = nullptr;
   float* noise = nullptr;   // [Bmax][out_p] dropout multipliers drawn ahead of the layer (first decoder layer: by the first encoder BatchNorm launch)
 };

@@ -711,6 +711,18 @@ int smx_set_flag(smx_model* m, const char* name, int value) {
   return SMX_OK;
 }
 
+int smx_set_activation(smx_model* m, int32_t net, int32_t act) {
+  SMX_REQUIRE(m, "null model");
+  SMX_REQUIRE(act >= SMX_ACT_RELU && act <= SMX_ACT_SOFTPLUS, "smx_set_activation: unknown activation");
+  std::vector<MlpLayer>* mlp = net == SMX_NET_ENCODER ? &m->enc : net == SMX_NET_DECODER ? &m->dec : net == SMX_NET_LIBRARY_ENCODER ? &m->encl : nullptr;
+  SMX_REQUIRE(mlp, "smx_set_activation: unknown network (encoder 0, decoder 1, library encoder 2)");
+  SMX_REQUIRE(net != SMX_NET_LIBRARY_ENCODER || !m->encl.empty(), "smx_set_activation: the model has no library encoder");
+  SMX_HIP(hipStreamSynchronize(m->st));
+  for (auto& L : *mlp) L.act = act;
+  drop_graphs(m);   // a captured step bakes the launch forms in
+  return SMX_OK;
+}
+
 int smx_timing_enable(smx_model* m, const char* kernel) {
   SMX_REQUIRE(m, "null model");
   SMX_HIP(hipStreamSynchronize(m->st));

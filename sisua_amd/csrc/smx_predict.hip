@@ -239,12 +239,13 @@ int stacked_decoder(smx_model* m, const float* z, long rows, float* const* hb, i
     GemmArgs g;
     g.A = in; g.lda = ld; g.B = P_(m, L.tW); g.ldb = m->tensors[L.tW].ld;
     g.M = (int)rows; g.N = L.out_p; g.K = L.in_p; g.C = hb[i & 1]; g.ldc = L.out_p; g.split_k = 1;
-    if (L.bn < 0) { g.bias = P_(m, L.tBias); g.act = 1; g.leak = L.leak; }
+    const bool gen = L.act != SMX_ACT_RELU;   // (not ReLU: the product adds the bias only, score_bn_act's GEN_ACT kernels apply the activation)
+    if (L.bn < 0) { g.bias = P_(m, L.tBias); g.act = gen ? 0 : 1; g.leak = L.leak; }
     SMX_CHECK(launch_gemm(m->st, g));
     const bool last = (i + 1 == m->dec.size());
-    if (L.bn >= 0 || (last && last_form != 0)) {
+    if (L.bn >= 0 || (last && last_form != 0) || gen) {
       ScoreBnArgs b;
-      b.h = hb[i & 1]; b.R = rows; b.H = L.out; b.Hp = L.out_p; b.eps = m->cfg.bn_eps; b.leak = L.leak;
+      b.h = hb[i & 1]; b.R = rows; b.H = L.out; b.Hp = L.out_p; b.eps = m->cfg.bn_eps; b.leak = L.leak; b.act = L.act;
       if (L.bn >= 0) {
         b.gamma = P_(m, L.tGamma); b.beta = P_(m, L.tBeta);
         b.moving_mean = m->bn_moving + m->bn_off[L.bn]; b.moving_var = b.moving_mean + L.out_p;

@@ -90,7 +90,10 @@ int launch_score_draws(hipStream_t st, const ScoreDrawArgs& a) {
 }
 
 // evaluation-mode BatchNorm + activation of a decoder layer, in place, any number of rows (four columns per thread)
-__global__ __launch_bounds__(256) void score_bn_act_kernel(ScoreBnArgs a) {
+// GEN_ACT (ScoreBnArgs::act not ReLU; smx_act.h): act() of the BatchNorm output, or of the value itself when gamma is null (a layer without
+// BatchNorm whose product added the bias only)
+template <bool GEN_ACT>
+__device__ inline void score_bn_act_body(const ScoreBnArgs& a) {
   const int q = a.Hp >> 2;
   const long total = a.R * q;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
@@ -100,20 +103,33 @@ __global__ __launch_bounds__(256) void score_bn_act_kernel(ScoreBnArgs a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const bool live = c + j < a.H;
+      float h;
+      if constexpr (GEN_ACT) {
+        float y = e[j];
+        if (a.gamma) {
+          const float inv = rsqrtf(a.moving_var[c + j] + a.eps);
+          y = a.gamma[c + j] * ((e[j] - a.moving_mean[c + j]) * inv) + a.beta[c + j];
+        }
+        h = act_fwd(a.act, y);
+      } else {
       const float inv = rsqrtf(a.moving_var[c + j] + a.eps);
       const float y = a.gamma[c + j] * ((e[j] - a.moving_mean[c + j]) * inv) + a.beta[c + j];
-      float h = fmaxf(y, 0.f);
+      h = fmaxf(y, 0.f);
       if (a.leak != 0.f) h += a.leak * fminf(y, 0.f);
+      }
       e[j] = live ? h : 0.f;
     }
     *reinterpret_cast<float4*>(a.h + (i / q) * a.Hp + c) = v;
   }
 }
+__global__ __launch_bounds__(256) void score_bn_act_kernel(ScoreBnArgs a) { score_bn_act_body<false>(a); }
+__global__ __launch_bounds__(256) void score_bn_act_gen_kernel(ScoreBnArgs a) { score_bn_act_body<true>(a); }
 
 // the LAST decoder layer: the same, written TRANSPOSED (out_t [Hp][ldt], k-major) -- the output head reads its A operand
 // as 32 consecutive rows of one k per load instruction (2 cache lines) instead of 64 lanes in 64 different lines.
 // gamma == nullptr: plain transpose (bias and activation already applied in the product's store path).
-__global__ __launch_bounds__(256) void score_bn_act_t_kernel(ScoreBnArgs a) {
+template <bool GEN_ACT>
+__device__ inline void score_bn_act_t_body(const ScoreBnArgs& a) {
   __shared__ float tile[32][33];
   const long r0 = (long)blockIdx.x * 32;
   const int c0 = blockIdx.y * 32;
@@ -128,10 +144,14 @@ __global__ __launch_bounds__(256) void score_bn_act_t_kernel(ScoreBnArgs a) {
       if (a.gamma) {
         const float inv = rsqrtf(a.moving_var[c] + a.eps);
         const float y = a.gamma[c] * ((x - a.moving_mean[c]) * inv) + a.beta[c];
-        h = fmaxf(y, 0.f);
-        if (a.leak != 0.f) h += a.leak * fminf(y, 0.f);
+        if constexpr (GEN_ACT) h = act_fwd(a.act, y);
+        else {
+          h = fmaxf(y, 0.f);
+          if (a.leak != 0.f) h += a.leak * fminf(y, 0.f);
+        }
         if (c >= a.H) h = 0.f;
-      } else h = x;
+      } else if constexpr (GEN_ACT) h = c < a.H ? act_fwd(a.act, x) : 0.f;
+      else h = x;
     }
     tile[ty + 8 * p][tx] = h;
   }
@@ -143,8 +163,11 @@ __global__ __launch_bounds__(256) void score_bn_act_t_kernel(ScoreBnArgs a) {
     if (r < a.R) a.out_t[(long)c * a.ldt + r] = tile[tx][ty + 8 * p];
   }
 }
+__global__ __launch_bounds__(256) void score_bn_act_t_kernel(ScoreBnArgs a) { score_bn_act_t_body<false>(a); }
+__global__ __launch_bounds__(256) void score_bn_act_t_gen_kernel(ScoreBnArgs a) { score_bn_act_t_body<true>(a); }
 
 __global__ void score_bn_act_split_kernel(ScoreBnArgs a);   // (below, beside the kernel that reads its output)
+__global__ void score_bn_act_split_gen_kernel(ScoreBnArgs a);
 int launch_score_bn_act(hipStream_t st, const ScoreBnArgs& a) {
   if (a.out3) {
     if (a.R <= 0 || a.Hp <= 0 || (a.Hp % 4) || !a.h || (a.gamma && (!a.beta || !a.moving_mean || !a.moving_var))) {
@@ -152,7 +175,8 @@ int launch_score_bn_act(hipStream_t st, const ScoreBnArgs& a) {
       return SMX_ERR_INVALID;
     }
     const long total = a.R * (a.Hp >> 2);
-    hipLaunchKernelGGL(score_bn_act_split_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, st, a);
+    if (a.act != SMX_ACT_RELU) hipLaunchKernelGGL(score_bn_act_split_gen_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(score_bn_act_split_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, st, a);
     SMX_HIP(hipGetLastError());
     return SMX_OK;
   }
@@ -161,7 +185,18 @@ int launch_score_bn_act(hipStream_t st, const ScoreBnArgs& a) {
       set_error("score_bn_act: bad arguments (transposed form)");
       return SMX_ERR_INVALID;
     }
-    hipLaunchKernelGGL(score_bn_act_t_kernel, dim3((unsigned)((a.R + 31) / 32), (unsigned)(a.Hp / 32)), dim3(256), 0, st, a);
+    if (a.act != SMX_ACT_RELU) hipLaunchKernelGGL(score_bn_act_t_gen_kernel, dim3((unsigned)((a.R + 31) / 32), (unsigned)(a.Hp / 32)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(score_bn_act_t_kernel, dim3((unsigned)((a.R + 31) / 32), (unsigned)(a.Hp / 32)), dim3(256), 0, st, a);
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
+  }
+  if (a.act != SMX_ACT_RELU) {   // (gamma may be null here: the activation alone)
+    if (a.act < SMX_ACT_RELU || a.act > SMX_ACT_SOFTPLUS || a.R <= 0 || a.Hp <= 0 || (a.Hp % 4) || !a.h || (a.gamma && (!a.beta || !a.moving_mean || !a.moving_var))) {
+      set_error("score_bn_act: bad arguments");
+      return SMX_ERR_INVALID;
+    }
+    const long total = a.R * (a.Hp >> 2);
+    hipLaunchKernelGGL(score_bn_act_gen_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, st, a);
     SMX_HIP(hipGetLastError());
     return SMX_OK;
   }
@@ -208,7 +243,8 @@ __device__ inline void split3(float x, __bf16& x0, __bf16& x1, __bf16& x2) {
 
 // evaluation-mode BatchNorm + activation of the LAST decoder layer, written as the three-way bf16 split [3][R][Hp]
 // (gamma == nullptr: the split alone; bias and activation were applied in the product's store path)
-__global__ __launch_bounds__(256) void score_bn_act_split_kernel(ScoreBnArgs a) {
+template <bool GEN_ACT>
+__device__ inline void score_bn_act_split_body(const ScoreBnArgs& a) {
   const int q = a.Hp >> 2;
   // a thread keeps ONE column quad (q divides 256 at Hp = 32, 64, 128): its four columns' BatchNorm constants are loaded once, ahead of the
   // rows, and the index arithmetic is a shift -- as a flat walk every element paid a 64-bit division and 16 loads of per-column constants
@@ -234,10 +270,13 @@ __global__ __launch_bounds__(256) void score_bn_act_split_kernel(ScoreBnArgs a) 
       if (a.gamma) {
         const float inv = pre ? i4[j] : rsqrtf(a.moving_var[cc + j] + a.eps);
         const float y = (pre ? g4[j] : a.gamma[cc + j]) * ((e[j] - (pre ? m4[j] : a.moving_mean[cc + j])) * inv) + (pre ? b4[j] : a.beta[cc + j]);
-        hval = fmaxf(y, 0.f);
-        if (a.leak != 0.f) hval += a.leak * fminf(y, 0.f);
+        if constexpr (GEN_ACT) hval = act_fwd(a.act, y);
+        else {
+          hval = fmaxf(y, 0.f);
+          if (a.leak != 0.f) hval += a.leak * fminf(y, 0.f);
+        }
         if (cc + j >= a.H) hval = 0.f;
-      }
+      } else if constexpr (GEN_ACT) hval = cc + j < a.H ? act_fwd(a.act, hval) : 0.f;
       split3(hval, t[0][j], t[1][j], t[2][j]);
     }
 #pragma unroll
@@ -253,6 +292,8 @@ __global__ __launch_bounds__(256) void score_bn_act_split_kernel(ScoreBnArgs a) 
     one((i / q) * a.Hp + cc, cc, false);
   }
 }
+__global__ __launch_bounds__(256) void score_bn_act_split_kernel(ScoreBnArgs a) { score_bn_act_split_body<false>(a); }
+__global__ __launch_bounds__(256) void score_bn_act_split_gen_kernel(ScoreBnArgs a) { score_bn_act_split_body<true>(a); }
 
 // A ONE-layer decoder with BatchNorm in one launch: the draws, the product with the layer's [Dp][Hp] weights, evaluation-mode BatchNorm + activation and the
 // three-way bf16 split of 32 stacked rows per workgroup -- score_draws_kernel + the product + score_bn_act_split_kernel (8.5 + 5.7 + 8.2 us of launches at 128 cells x

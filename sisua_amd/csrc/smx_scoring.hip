@@ -103,6 +103,8 @@ static int stacked_scores(smx_model* m, const Pass& ps, int n_samples, const Sco
   }
   // (knob no_score_dec1: the three launches)
   const bool dec1 = !wide_head && !m->scvi && !m->scale && m->dec.size() == 1 && m->dec[0].bn >= 0 && m->dec[0].in_p == m->Dp &&
+                    m->dec[0].act == SMX_ACT_RELU &&   // (ReLU built in; other activations: the draws, the product and score_bn_act_split_gen_kernel)
+                   
                     score_decoder1_supported(m->Dp, m->dec[0].out_p) && !tuning_on("no_score_dec1");
   // the encoders and the latent heads
   SMX_CHECK(forward_pass(m, ps, false, false, (m->scale || m->mixpost) ? 3 : 4));   // (4: without the latent moments' launch -- the draws below read `latbuf`)

@@ -19,7 +19,8 @@ BnSyncArgs sync_args(smx_model* m) { BnSyncArgs y; y.gather = m->sync_buf; y.ran
 static bool front_shapes_ok(smx_model* m, const Pass& ps) {
   const int lat_ld = m->lat_planes * m->Dp;
   return m->flags.front && !m->scale && !m->mixpost && !sync_bn_on(m, ps.training) && bn_front_supported(ps.B, m->Dp) &&
-         (m->Dp == 32 || m->Dp == 64) && m->dec[0].in_p == m->Dp && m->dec[0].out_p % 8 == 0 && (lat_ld % 4) == 0;
+         (m->Dp == 32 || m->Dp == 64) && m->dec[0].in_p == m->Dp && m->dec[0].out_p % 8 == 0 && (lat_ld % 4) == 0 &&
+         m->dec[0].act == SMX_ACT_RELU;   // (the front forms build ReLU in)
 }
 
 
@@ -74,7 +75,7 @@ int mlp_forward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps, const 
   auto make_bn = [&](MlpLayer& L, const float* slab, int eff, long slab_stride) {
     BnFwdArgs b;
     b.pre = slab; b.n_slabs = eff; b.slab_stride = slab_stride; b.ld = L.out_p;
-    b.B = ps.B; b.H = L.out; b.Hp = L.out_p; b.batchnorm = L.bn >= 0; b.training = ps.training; b.leak = L.leak;
+    b.B = ps.B; b.H = L.out; b.Hp = L.out_p; b.batchnorm = L.bn >= 0; b.training = ps.training; b.leak = L.leak; b.act = L.act;
     if (L.bn >= 0) {
       b.gamma = P_(m, L.tGamma); b.beta = P_(m, L.tBeta);
       b.moving_mean = m->bn_moving + m->bn_off[L.bn]; b.moving_var = b.moving_mean + L.out_p;
@@ -105,7 +106,7 @@ int mlp_forward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps, const 
     // own columns as dot products -- the same front the first decoder layer uses for the latent sample, here as a plain
     // copy (no product launch; the reference's default networks are [64, 64], configs/base.yaml:10-17)
     LatentArgs dense_la;
-    const bool dense_front = m->flags.front && !sync && !(front != nullptr && i == 0) && !(i == 0 && in_is_x) && L.leak == 0.f &&
+    const bool dense_front = m->flags.front && !sync && !(front != nullptr && i == 0) && !(i == 0 && in_is_x) && L.leak == 0.f && L.act == SMX_ACT_RELU &&
                              (L.in_p == 32 || L.in_p == 64 || (L.in_p == 128 && ps.B <= 128)) && bn_front_supported(ps.B, L.in_p) && L.out_p % 8 == 0 &&
                              (ld % 4) == 0;
     if (dense_front) {
@@ -120,7 +121,8 @@ int mlp_forward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps, const 
     bool dual = false;
     GemmArgs g2;
     if (twin && i == 0 && !with_front && !sync && !no_twin && in_is_x && !twin->empty() && bn_dual_supported(ps.B) &&
-        !(ps.training && m->cfg.input_dropout > 0.f) && (*twin)[0].in_p == L.in_p && L.leak == 0.f && (*twin)[0].leak == 0.f) {
+        !(ps.training && m->cfg.input_dropout > 0.f) && (*twin)[0].in_p == L.in_p && L.leak == 0.f && (*twin)[0].leak == 0.f &&
+        L.act == SMX_ACT_RELU && (*twin)[0].act == SMX_ACT_RELU) {
       MlpLayer& T = (*twin)[0];
       float* slab2 = m->slab + (size_t)std::max(g.split_k, 1) * (size_t)g.slab_stride;
       g2 = make_gemm(T, in, ld, true, slab2);
@@ -129,7 +131,7 @@ int mlp_forward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps, const 
     // layers without BatchNorm and without dropout (the FactorVAE discriminator; plain autoencoders at evaluation): bias
     // and activation in the product's own store path -- no bias / activation launch
     const bool epi_act = m->flags.act_epilogue && !dual && !with_front && !sync && L.bn < 0 && !(ps.training && L.drop_p > 0.f) &&
-                         g.split_k <= 1 && !m->use_injected;
+                         g.split_k <= 1 && !m->use_injected && L.act == SMX_ACT_RELU;   // (other activations: the BatchNorm launch without BatchNorm)
     if (epi_act) {
       g.bias = P_(m, L.tBias); g.act = 1; g.leak = L.leak; g.C = L.out_buf; g.ldc = L.out_p; g.split_k = 1;
       Timed t(m, (i == 0 && in_is_x) ? label0 : "gemm_mlp_fwd");
@@ -479,6 +481,15 @@ int mlp_backward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps, const
     b.dpre = L.dpre;
     if (L.bn >= 0) { b.gamma = P_(m, L.tGamma); b.dgamma = G_(m, L.tGamma); b.dbeta = G_(m, L.tBeta); }
     else b.dbias = G_(m, L.tBias);
+    if (L.act != SMX_ACT_RELU) {   // the GEN_ACT forms: the keep mask from the forward's source (make_bn of forward_pass)
+      b.act = L.act;
+      if (L.bn >= 0) b.beta = P_(m, L.tBeta);
+      b.drop_p = ps.training ? L.drop_p : 0.f;
+      b.nk = make_key(m, L.stream, ps.sample, true);
+      if (&mlp == &m->dec) b.nk.draw_rows = (uint32_t)ps.draw_rows;
+      b.rows = ps.rows; b.cell_base = ps.cell_base;
+      if (const Injected* ij = inj(m, L.stream)) { b.inj_mask = ij->d; b.inj_ld = ij->ld; }
+    }
     if (front) {
       b.front = 1; b.fD = front->fD; b.fld = front->fld; b.fW = front->fW; b.fldw = front->fldw; b.fK = front->fK;
       b.fold_dz = front->fold_dz; b.zD = front->zD; b.zld = front->zld; b.zW = front->zW; b.zldw = front->zldw; b.zlb = front->zlb;
@@ -555,7 +566,7 @@ int mlp_backward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps, const
     }
     // hidden layers 32 / 64 / 128 wide: the layer below takes d in = dpre W^T as the gradient front of its BatchNorm-backward
     // launch (dot products over K = this layer's width) and d W joins the grouped launch at the end -- no product launch
-    if (defer && i > 0 && !(i == 0 && lat_epi) && m->flags.bwd_front && (L.out_p == 32 || L.out_p == 64 || L.out_p == 128) &&
+    if (defer && i > 0 && !(i == 0 && lat_epi) && m->flags.bwd_front && (L.out_p == 32 || L.out_p == 64 || L.out_p == 128) && mlp[i - 1].act == SMX_ACT_RELU &&
         bn_bwd_front_supported(ps.B, L.out_p) && mlp[i - 1].out_p % 8 == 0 && (tw.ld % 4) == 0 && (L.out_p % 4) == 0 &&
         !(sync_bn_on(m, ps.training) && mlp[i - 1].bn >= 0)) {
       defer->push_back(g);
@@ -577,7 +588,8 @@ int mlp_backward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps, const
     }
     // the layer below has neither BatchNorm nor dropout: its activation's derivative goes into this product's store path
     // and the result IS its d pre-activation (its bias gradient: the column sums its weight-gradient product takes along)
-    if (i > 0 && m->flags.act_epilogue && mlp[i - 1].bn < 0 && !(ps.training && mlp[i - 1].drop_p > 0.f) && h.split_k <= 1) {
+    if (i > 0 && m->flags.act_epilogue && mlp[i - 1].bn < 0 && !(ps.training && mlp[i - 1].drop_p > 0.f) && h.split_k <= 1 &&
+        mlp[i - 1].act == SMX_ACT_RELU) {
       MlpLayer& Lo = mlp[i - 1];
       h.split_k = 1; h.act = 2; h.leak = Lo.leak; h.act_out = Lo.out_buf; h.act_ld = Lo.out_p;
       h.C = Lo.dpre; h.ldc = Lo.out_p; h.slab_stride = 0;
@@ -1396,7 +1408,8 @@ int backward_pass(smx_model* m, const Pass& ps) {
   // the first encoder layers) run as ONE grouped launch at the end; the last encoder layer's BatchNorm-backward
   // launch computes d h = d lat W_lat^T itself.  SMX_NO_BWD_FRONT=1: the separate launches of before.
   const MlpLayer& eL = m->enc.back();
-  const bool bfront = m->flags.bwd_front && !sync_bn_on(m, ps.training) && bn_bwd_front_supported(ps.B, lat_ld) && eL.out_p % 8 == 0;
+  const bool bfront = m->flags.bwd_front && !sync_bn_on(m, ps.training) && bn_bwd_front_supported(ps.B, lat_ld) && eL.out_p % 8 == 0 &&
+                      eL.act == SMX_ACT_RELU;   // (the gradient fronts build ReLU in)
   // fold_dz (round 6): the d z product and the latent head's backward inside the encoder's last BatchNorm-backward launch -- the plain
   // reparameterised latent of VAE / SISUA at D <= 32, a first decoder layer of 128 units, at most 128 cells, below the wide-panel width,
   // no second MLP sharing the launch (scvi)
@@ -1464,7 +1477,7 @@ int backward_pass(smx_model* m, const Pass& ps) {
   if (m->scvi) {
     const MlpLayer& lL = m->encl.back();
     const TensorInfo& tw = m->tensors[m->t_latlW];
-    lfront = bfront && bn_bwd_front_supported(ps.B, 32) && lL.out_p % 8 == 0 && (tw.ld % 4) == 0;
+    lfront = bfront && bn_bwd_front_supported(ps.B, 32) && lL.out_p % 8 == 0 && (tw.ld % 4) == 0 && lL.act == SMX_ACT_RELU;
     gfl.fD = m->dlatl; gfl.fld = 32; gfl.fW = P_(m, m->t_latlW); gfl.fldw = tw.ld; gfl.fK = 32;
   }
   const bool twin_bwd = m->scvi && lfront && m->scvi_fused;

@@ -131,6 +131,14 @@ class Engine:
       for name in ("tie_mixtures", "tie_loc", "tie_scale"):
         if getattr(cfg, name, False):
           check(self.lib.smx_set_flag(self._h, name.encode(), 1))
+    # hidden-layer activations (NetConf.activation): set before any step; ReLU is the library's default
+    nets = [("enc_activation", _hip.SMX_NET_ENCODER), ("dec_activation", _hip.SMX_NET_DECODER)]
+    if cfg.model == "scvi":
+      nets.append(("encl_activation", _hip.SMX_NET_LIBRARY_ENCODER))
+    for field, net in nets:
+      act = getattr(cfg, field)
+      if act != "relu":
+        check(self.lib.smx_set_activation(self._h, net, _hip.HIDDEN_ACTIVATIONS[act]))
     if init:
       self.set_params(init_params(cfg))
 

@@ -187,12 +187,14 @@ class SingleCellModel:
     if len(extras) + len(labels) > 4:
       raise ValueError("at most 4 heads (outputs[1:] + label variables) are built")
     encl = self._encoder[1].units if len(self._encoder) > 1 else (64,)
+    encl_act = self._encoder[1].activation if len(self._encoder) > 1 else "relu"
     return ModelConfig(model=self._kind, n_genes=self._outputs[0].event_shape, likelihood=self._outputs[0].posterior,
                        enc_units=tuple(enc.units), dec_units=tuple(self._decoder.units),
                        latent_dim=self._latents[0].event_shape, encl_units=tuple(encl), labels=tuple(labels),
                        batchnorm=bool(enc.batchnorm), dropout_enc=float(enc.dropout), dropout_dec=float(self._decoder.dropout),
                        input_dropout=float(enc.input_dropout), log_norm=self._log_norm, beta=self._beta_cfg, alpha=self.alpha,
                        latent_activation=self._latent_activation(), clip_library=self.clip_library,
+                       enc_activation=enc.activation, dec_activation=self._decoder.activation, encl_activation=encl_act,
                        lr=float(self._opt["lr"]), clipnorm=float(self._opt["clipnorm"]), seed=self.seed,
                        extra_outputs=tuple(extras), dispersion=str(getattr(self, "_dispersion", "full")), inflation=str(getattr(self, "_inflation", "full")),
                        n_components=int(getattr(self, "_n_components", 10)), covariance=str(getattr(self, "_covariance", "none")), latent_mixture=bool(getattr(self, "_latent_mixture", False)),
@@ -1312,7 +1314,7 @@ def _shim_to_record(v):
     if nm in ("NetConf", "NetworkConfig"):
       return NetConf(units=st.get("units", (64, 64)), batchnorm=bool(st.get("batchnorm", True)),
                      dropout=float(st.get("dropout", 0.0) or 0.0), input_dropout=float(st.get("input_dropout", 0.0) or 0.0),
-                     name=st.get("name"))
+                     activation=st.get("activation", "relu"), name=st.get("name"))
     return st
   if isinstance(v, dict):
     return {k: _shim_to_record(x) for k, x in v.items()}
