@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 4
+#define SMX_ABI_VERSION 5
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -127,6 +127,11 @@ typedef struct {
    * it, gate logits = it), 2 = 'single' (ONE trainable scalar for every cell and gene: out1/b resp. out2/b of one element).  SMX_MODEL_SCVI only. */
   int32_t scvi_dispersion, scvi_inflation;
   int32_t n_components;                /* SMX_MODEL_SCALE: components of the mixture prior (scale.py:27), 1..32 */
+  /* RVmeta(latent_dim, 'mvntril') / 'tril': a full-covariance Gaussian posterior q(z|x) = N(mu, L L^T) (SMX_MODEL_VAE, SISUA, SCVI's z;
+   * 1 <= latent_dim <= 32).  The latent head has 1 + latent_dim planes of width latent_dim: plane 0 mu, plane 1 + i row i of the raw factor
+   * (L_ij = raw_ij for j < i, L_ii = softplus(raw_ii) + 1e-5, entries j > i inert).  z_scale outputs then hold the factor L
+   * [batch, latent_dim, latent_dim] (row-major, zeros above the diagonal) instead of [batch, latent_dim].  0: the diagonal posterior. */
+  int32_t latent_tril;
   int32_t disc_units, disc_layers;     /* SMX_MODEL_FVAE: hidden width / hidden layers of the discriminator (odin: 1000, 5) */
   float gamma, disc_leak;              /* SMX_MODEL_FVAE: weight of the TC term (6.0); leaky-ReLU slope (0.2) */
   int32_t batchnorm;                   /* NetConf.batchnorm */

@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsisua_hip.so")
 
-SMX_ABI_VERSION = 4
+SMX_ABI_VERSION = 5
 SMX_MAX_LAYERS = 8
 SMX_MAX_LABELS = 4
 
@@ -43,7 +43,7 @@ class smx_config(C.Structure):
       ("n_encl", C.c_int32), ("encl_units", C.c_int32 * SMX_MAX_LAYERS),
       ("n_labels", C.c_int32), ("label_dim", C.c_int32 * SMX_MAX_LABELS), ("label_llk", C.c_int32 * SMX_MAX_LABELS),
       ("label_components", C.c_int32 * SMX_MAX_LABELS), ("label_observed", C.c_int32 * SMX_MAX_LABELS),
-      ("scvi_dispersion", C.c_int32), ("scvi_inflation", C.c_int32), ("n_components", C.c_int32),
+      ("scvi_dispersion", C.c_int32), ("scvi_inflation", C.c_int32), ("n_components", C.c_int32), ("latent_tril", C.c_int32),
       ("disc_units", C.c_int32), ("disc_layers", C.c_int32), ("gamma", C.c_float), ("disc_leak", C.c_float),
       ("batchnorm", C.c_int32), ("log_norm", C.c_int32), ("latent_activation", C.c_int32),
       ("dropout_enc", C.c_float), ("dropout_dec", C.c_float), ("input_dropout", C.c_float),

@@ -19,6 +19,10 @@ OUTPUT_POSTERIORS = LIKELIHOODS + ("mse",)   # 'mse': deterministic output, -log
 # head kinds on the decoder output (label variables and outputs[1:]); the mixtures carry their component count: 'mixnb2' .. 'mixtril4'
 HEAD_KINDS = ("nb", "nbd", "zinb", "zinbd", "onehot", "bernoulli", "normal")
 MIXTURE_HEAD_KINDS = ("mixnb", "mixgauss", "mixtril", "mixzinb")
+# latent posteriors of RVmeta(D, name) that select the full-covariance Gaussian q(z|x) = N(mu, L L^T) (ModelConfig.latent_tril); every
+# other latent name keeps the model's own latent (the diagonal Gaussian of VAE / SISUA / SCVI)
+TRIL_LATENT_POSTERIORS = ("mvntril", "tril")
+TRIL_LATENT_MAX_DIM = 32
 
 
 def label_planes(llk: str, P: int = 0) -> int:
@@ -166,6 +170,10 @@ class ModelConfig:
   # scale.py:26,38-47 read literally: q(z|x) itself a mixture of n_components diagonal Gaussians (a (1 + 2 C) D-wide latent head: logits in
   # the first C columns of plane 0, C location planes, C raw-scale planes), standard-normal prior, Monte-Carlo KL; no prior/* tensors
   latent_mixture: bool = False
+  # RVmeta(latent_dim, 'mvntril') / 'tril': the full-covariance posterior N(mu, L L^T) of models 'vae', 'sisua' and 'scvi' (z only), 1 <= latent_dim
+  # <= 32.  Latent head: 1 + D planes of width D -- mu | row i of the raw factor (L_ij = raw_ij for j < i, L_ii = softplus(raw_ii) + 1e-5,
+  # [3P-recall] TFP's FillScaleTriL; entries j > i inert).  Not in oracle.Spec (tests/latent_tril_ref.py extends it)
+  latent_tril: bool = False
   # model 'fvae' (sisua/models/fvae.py:9-18; odin factorVAE defaults): the total-correlation discriminator
   disc_units: int = 1000
   disc_layers: int = 5
@@ -175,6 +183,11 @@ class ModelConfig:
   def __post_init__(self):
     for f in ACTIVATION_FIELDS:
       object.__setattr__(self, f, hidden_activation(getattr(self, f)))
+    if self.latent_tril:
+      if self.model not in ("vae", "sisua", "scvi"):
+        raise ValueError(f"the full-covariance latent posterior ('mvntril') is built for VAE, SISUA / MISA and SCVI, not model '{self.model}'")
+      if not 1 <= self.latent_dim <= TRIL_LATENT_MAX_DIM:
+        raise ValueError(f"the full-covariance latent posterior ('mvntril') is built for 1 <= latent_dim <= {TRIL_LATENT_MAX_DIM}, given: {self.latent_dim}")
     for P, kind in tuple(self.extra_outputs) + tuple(self.labels):
       if not (kind in HEAD_KINDS or (kind[:-1] in MIXTURE_HEAD_KINDS and kind[-1] in "234")):
         raise ValueError(f"unknown head kind {kind!r} (built: {', '.join(HEAD_KINDS)}, and the mixtures {', '.join(k + 'C' for k in MIXTURE_HEAD_KINDS)} with C = 2..4)")
@@ -230,11 +243,13 @@ class ModelConfig:
 
   def to_dict(self):
     """The fields as keyword arguments of oracle.Spec: the hidden-layer activations are left out while they are 'relu' (Spec has
-    no such fields; a configuration with another activation keeps them, and Spec refuses it)."""
+    no such fields; a configuration with another activation keeps them, and Spec refuses it).  latent_tril likewise, while it is False."""
     d = dataclasses.asdict(self)
     for f in ACTIVATION_FIELDS:
       if d[f] == "relu":
         del d[f]
+    if not d["latent_tril"]:
+      del d["latent_tril"]
     return d
 
 
@@ -257,7 +272,7 @@ def manifest(cfg: ModelConfig) -> List[Tuple[str, Tuple[int, ...]]]:
   G, D = cfg.n_genes, cfg.latent_dim
   h = mlp("enc", G, cfg.enc_units)
   _ = cfg.scale_tril, cfg.head_plane(0)   # (validates the SCALE / scvi options)
-  nl = (1 + 2 * cfg.n_components) * D if cfg.latent_mixture else (2 * D if cfg.stochastic else D)
+  nl = (1 + 2 * cfg.n_components) * D if cfg.latent_mixture else (1 + D) * D if cfg.latent_tril else (2 * D if cfg.stochastic else D)
   out += [("lat/W", (h, nl)), ("lat/b", (nl,))]
   if cfg.model == "scale" and not cfg.latent_mixture:
     C = cfg.n_components

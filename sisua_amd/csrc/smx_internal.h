@@ -179,6 +179,25 @@ struct MixLatArgs {
 int launch_mixlat_fwd(hipStream_t st, const MixLatArgs& a);
 int launch_mixlat_bwd(hipStream_t st, const MixLatArgs& a);
 
+// RVmeta(D, 'mvntril'): q(z|x) = N(mu, L L^T) from a latent head of 1 + D planes of width Dp = 32 (D <= 32): plane 0 mu, plane 1 + i
+// row i of the raw factor (L_ij = raw_ij for j < i, L_ii = softplus(raw_ii) + 1e-5; entries j > i inert).  z = mu + L eps with the
+// diagonal path's eps (stream ST_EPS_Z), KL = 1/2 (|L|_F^2 + |mu|^2 - D) - sum_i log L_ii.
+struct LatentTrilArgs {
+  const float* lat = nullptr; int ld = 0; int B = 0, D = 0, Dp = 0;
+  NoiseKey nk{0, 0, 0, 0, nullptr};
+  const int32_t* rows = nullptr; uint32_t cell_base = 0;
+  const float* inj_eps = nullptr; int inj_ld = 0;
+  float* z = nullptr; float* diag = nullptr; float* eps = nullptr;   // [B][Dp] the draw, L_ii (1 in the padding), its noise
+  float* kl = nullptr;        // [B]
+  float* factor = nullptr;    // [B][D * D] the factor L row-major, zeros above the diagonal (evaluation passes: predict / encode; NULL: not written)
+  // backward
+  const float* dz = nullptr; int dz_slabs = 1; long dz_slab_stride = 0; int ldz = 0;
+  KlWeight klw{nullptr, 0.f, 0.f, 0};   // beta / B_global
+  float* dlat = nullptr;      // [B][ld]
+};
+int launch_latent_tril_fwd(hipStream_t st, const LatentTrilArgs& a);
+int launch_latent_tril_bwd(hipStream_t st, const LatentTrilArgs& a);
+
 struct BnFwdArgs {
   const float* pre = nullptr; int n_slabs = 1; long slab_stride = 0; int ld = 0;  // pre-activation slabs [S][B][ld]
   int B = 0, H = 0, Hp = 0;

@@ -223,6 +223,122 @@ int launch_mixlat_bwd(hipStream_t st, const MixLatArgs& a) {
   return SMX_OK;
 }
 
+// ---- RVmeta(D, 'mvntril'): the full-covariance posterior (LatentTrilArgs) ------------------------------------------------------------
+// Half a wave per cell (two cells per wave64, SMX_LTRIL_CELLS per workgroup), lane i of the half = row i of L (D <= 32 = Dp).  Lane i reads
+// row i of the raw factor as eight 16-byte loads; a triangular mat-vec is at most 528 FMAs per cell.  The whole workgroup runs to the end
+// (cells past B and rows past D compute on zeros): half_wave_sum needs both halves of a wave.
+#define SMX_LTRIL_CELLS 8
+// row i of the raw factor of cell b (plane 1 + i; zeros for a row past D, whose plane does not exist)
+__device__ inline void ltril_row(const LatentTrilArgs& a, int b, int i, bool on, float (&r)[32]) {
+  const float4* row = reinterpret_cast<const float4*>(a.lat + (long)b * a.ld + (long)(1 + (on ? i : 0)) * 32);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float4 q = row[k];
+    r[4 * k] = on ? q.x : 0.f; r[4 * k + 1] = on ? q.y : 0.f; r[4 * k + 2] = on ? q.z : 0.f; r[4 * k + 3] = on ? q.w : 0.f;
+  }
+}
+// z = mu + L eps with the diagonal path's eps (lane i draws eps_i; eps_j for j < i from one LDS row of the cell, read as broadcasts);
+// KL = 1/2 (|L|_F^2 + |mu|^2 - D) - sum_i log L_ii as one half-wave sum of the rows' terms
+__global__ __launch_bounds__(256) void latent_tril_fwd_kernel(LatentTrilArgs a) {
+  __shared__ float4 se4[SMX_LTRIL_CELLS][8];
+  const int i = threadIdx.x & 31, c = threadIdx.x >> 5;
+  const int b = blockIdx.x * SMX_LTRIL_CELLS + c;
+  const bool cell_on = b < a.B, on = cell_on && i < a.D;
+  const int bb = cell_on ? b : a.B - 1;
+  float raw[32];
+  ltril_row(a, bb, i, on, raw);
+  const float mu = on ? a.lat[(long)bb * a.ld + i] : 0.f;
+  float eps = 0.f;
+  if (on) {
+    if (a.inj_eps) eps = a.inj_eps[(long)b * a.inj_ld + i];
+    else {
+      const uint32_t cell = a.cell_base + (uint32_t)(a.rows ? a.rows[b] : b);
+      const float4 n = normal4(philox_row(a.nk, (uint32_t)b, cell, (uint32_t)(i >> 2)));
+      eps = (i & 3) == 0 ? n.x : (i & 3) == 1 ? n.y : (i & 3) == 2 ? n.z : n.w;
+    }
+  }
+  reinterpret_cast<float*>(se4[c])[i] = eps;
+  __syncthreads();
+  float acc = 0.f, fro = 0.f, rii = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float4 e4 = se4[c][k];
+    const float ev[4] = {e4.x, e4.y, e4.z, e4.w};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int j = 4 * k + t;
+      if (j < i) { acc += raw[j] * ev[t]; fro += raw[j] * raw[j]; }
+      else if (j == i) rii = raw[j];
+    }
+  }
+  const float lii = softplusf(rii) + 1e-5f;
+  const float z = mu + acc + lii * eps;
+  const float kl = half_wave_sum(on ? 0.5f * (fro + lii * lii + mu * mu - 1.f) - flog(lii) : 0.f);
+  if (cell_on) {
+    const long o = (long)b * a.Dp + i;   // (Dp = 32: lane i owns column i of the padded rows)
+    a.z[o] = on ? z : 0.f;
+    a.diag[o] = on ? lii : 1.f;
+    a.eps[o] = eps;
+    if (i == 0 && a.kl) a.kl[b] = kl;
+    if (a.factor && on) {
+      float* f = a.factor + ((long)b * a.D + i) * a.D;
+#pragma unroll
+      for (int j = 0; j < 32; ++j)
+        if (j < a.D) f[j] = j < i ? raw[j] : j == i ? lii : 0.f;
+    }
+  }
+}
+// d mu = dz + k mu;  d raw_ij = dz_i eps_j + k L_ij (j < i);  d raw_ii = (dz_i eps_i + k (L_ii - 1 / L_ii)) sigmoid(raw_ii);  j > i: 0.
+// dz summed over its slabs; lane i stores its row of d raw whole (eight 16-byte stores)
+__global__ __launch_bounds__(256) void latent_tril_bwd_kernel(LatentTrilArgs a) {
+  const float kls = kl_scale_of(a.klw);
+  const int i = threadIdx.x & 31, c = threadIdx.x >> 5;
+  const int b = blockIdx.x * SMX_LTRIL_CELLS + c;
+  if (b >= a.B) return;   // (no cross-lane step below)
+  const bool on = i < a.D;
+  float raw[32], e[32];
+  ltril_row(a, b, i, on, raw);
+  const float4* erow = reinterpret_cast<const float4*>(a.eps + (long)b * a.Dp);   // (the same row in every lane of the half: broadcasts)
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float4 q = erow[k];
+    e[4 * k] = q.x; e[4 * k + 1] = q.y; e[4 * k + 2] = q.z; e[4 * k + 3] = q.w;
+  }
+  float dz = 0.f;
+  if (on) for (int s = 0; s < a.dz_slabs; ++s) dz += a.dz[(long)s * a.dz_slab_stride + (long)b * a.ldz + i];
+  const float mu = on ? a.lat[(long)b * a.ld + i] : 0.f;
+  const float lii = on ? a.diag[(long)b * a.Dp + i] : 1.f;
+  float* dl = a.dlat + (long)b * a.ld;
+  dl[i] = on ? dz + kls * mu : 0.f;   // plane 0
+  if (!on) return;
+  float rii = 0.f;
+#pragma unroll
+  for (int j = 0; j < 32; ++j) if (j == i) rii = raw[j];
+  const float sg = softplus_sigmoid(rii).sg;
+#pragma unroll
+  for (int j = 0; j < 32; ++j)
+    raw[j] = j < i ? dz * e[j] + kls * raw[j] : j == i ? (dz * e[j] + kls * (lii - frcp(lii))) * sg : 0.f;
+  float4* drow = reinterpret_cast<float4*>(dl + (long)(1 + i) * 32);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) drow[k] = make_float4(raw[4 * k], raw[4 * k + 1], raw[4 * k + 2], raw[4 * k + 3]);
+}
+static bool latent_tril_ok(const LatentTrilArgs& a) {
+  return a.B > 0 && a.D >= 1 && a.D <= 32 && a.Dp == 32 && a.ld == (1 + a.D) * a.Dp && a.lat && a.z && a.diag && a.eps &&
+         (!a.inj_eps || a.inj_ld >= a.D);
+}
+int launch_latent_tril_fwd(hipStream_t st, const LatentTrilArgs& a) {
+  if (!latent_tril_ok(a)) { set_error("latent_tril_fwd: bad arguments (1 <= latent_dim <= 32, a head of 1 + latent_dim planes of width 32)"); return SMX_ERR_INVALID; }
+  hipLaunchKernelGGL(latent_tril_fwd_kernel, dim3((a.B + SMX_LTRIL_CELLS - 1) / SMX_LTRIL_CELLS), dim3(256), 0, st, a);
+  SMX_HIP(hipGetLastError());
+  return SMX_OK;
+}
+int launch_latent_tril_bwd(hipStream_t st, const LatentTrilArgs& a) {
+  if (!latent_tril_ok(a) || !a.dz || !a.dlat || a.dz_slabs < 1 || a.ldz < a.D) { set_error("latent_tril_bwd: bad arguments"); return SMX_ERR_INVALID; }
+  hipLaunchKernelGGL(latent_tril_bwd_kernel, dim3((a.B + SMX_LTRIL_CELLS - 1) / SMX_LTRIL_CELLS), dim3(256), 0, st, a);
+  SMX_HIP(hipGetLastError());
+  return SMX_OK;
+}
+
 __global__ __launch_bounds__(256) void latent_bwd_kernel(LatentArgs a) {
   const float kls = kl_scale_of(a.klw);
   const int idx = blockIdx.x * 256 + threadIdx.x;

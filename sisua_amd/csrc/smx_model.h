@@ -199,7 +199,9 @@ struct smx_model {
   int train_draws = 1, Rmax = 0;
   bool stochastic = true, scvi = false, scale = false, fvae = false;
   bool mixpost = false;      // SMX_MODEL_SCALE_POST: q(z|x) a mixture of cfg.n_components diagonal Gaussians (lat head: 1 + 2 C planes)
-  int lat_planes = 2;        // planes of width Dp of the latent head's output: 2 (mu, raw sigma), 1 (deterministic), 1 + 2 C (mixture posterior)
+  int lat_planes = 2;        // planes of width Dp of the latent head's output: 2 (mu, raw sigma), 1 (deterministic), 1 + 2 C (mixture posterior), 1 + D (tril)
+  bool latent_tril = false;  // RVmeta(D, 'mvntril'): q(z|x) = N(mu, L L^T) (lat head: 1 + D planes; sig holds L_ii)
+  float* ltril = nullptr;    // latent_tril: the factor L [B][D * D] of an evaluation pass (what predict / encode report as z_scale)
   float* zmean = nullptr; int32_t* zpick = nullptr;   // mixture posterior: the mixture's mean [B][Dp] (what predict / encode report), the picked component [B]
   float* tril_part = nullptr; size_t tril_part_floats = 0;   // scale_tril: scratch of the prior's backward (partial sums per component and cell group)
   bool scale_tril = false;   // SCALE with full-covariance components (SMX_MODEL_SCALE_TRIL): prior/scale holds C lower-triangular D x D factors

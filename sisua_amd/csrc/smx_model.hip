@@ -137,7 +137,7 @@ static std::vector<void**> row_buffers(smx_model* m) {
     for (auto& L : *mlp) { add(L.xhat); add(L.out_buf); add(L.dpre); add(L.inv_std); add(L.noise); }
   add(m->bigk_part); add(m->slab); add(m->latbuf); add(m->dlat); add(m->z); add(m->noise_eps); add(m->sig); add(m->eps); add(m->kl);
   add(m->P); add(m->dP); add(m->llk_part); add(m->llk_y); add(m->llk_o); add(m->rows2[0]); add(m->rows2[1]);
-  add(m->resp); add(m->dklz); add(m->tril_part); add(m->zmean); add(m->zpick);
+  add(m->resp); add(m->dklz); add(m->tril_part); add(m->zmean); add(m->zpick); add(m->ltril);
   add(m->raw); add(m->draw); add(m->rho); add(m->latlbuf); add(m->dlatl); add(m->lsmp); add(m->lsig); add(m->leps); add(m->kl_l); add(m->dl);
   for (int j = 0; j < SMX_MAX_LABELS; ++j) { add(m->laby_raw[j]); add(m->laby_draw[j]); }
   if (m->x_csr) add(m->xbatch);
@@ -192,6 +192,7 @@ static int alloc_rows_into(smx_model* m, size_t R) {
   if (m->scale && ((rc = dm(&m->resp, B * 32)) || (rc = dm(&m->dklz, B * m->Dp)))) return rc;
   if (m->scale_tril && (rc = dm(&m->tril_part, (size_t)cfg->n_components * ((B + 7) / 8) * m->D * (m->D + 2)))) return rc;
   if (m->mixpost && ((rc = dm(&m->resp, B * 32)) || (rc = dm(&m->zmean, B * m->Dp)) || (rc = dm(&m->zpick, B)))) return rc;
+  if (m->latent_tril && (rc = dm(&m->ltril, B * (size_t)m->D * m->D))) return rc;
   if (m->scvi) {
     if ((rc = dm(&m->raw, B * ldp)) || (rc = dm(&m->draw, B * ldp)) || (rc = dm(&m->rho, B * m->Gp)) ||
         (rc = dm(&m->latlbuf, B * 32)) || (rc = dm(&m->dlatl, B * 32)) || (rc = dm(&m->lsmp, B)) ||
@@ -356,6 +357,11 @@ int smx_model_create(const smx_config* cfg, smx_model** out) {
     }
     SMX_REQUIRE(classes <= 32, "fvae: the label variables have at most 32 classes in all (the discriminator's logit layer)");
   }
+  if (cfg->latent_tril) {
+    SMX_REQUIRE(cfg->model == SMX_MODEL_VAE || cfg->model == SMX_MODEL_SISUA || cfg->model == SMX_MODEL_SCVI,
+                "latent_tril: the full-covariance posterior is built for VAE, SISUA / MISA and SCVI");
+    SMX_REQUIRE(cfg->latent_dim >= 1 && cfg->latent_dim <= 32, "latent_tril: 1 <= latent_dim <= 32");
+  }
   if (cfg->model == SMX_MODEL_SCALE_POST) SMX_REQUIRE(cfg->n_labels == n_observed, "scale with a mixture-density posterior: no label heads (observed outputs only)");
   SMX_REQUIRE(cfg->model == SMX_MODEL_SISUA || cfg->model == SMX_MODEL_FVAE || cfg->model == SMX_MODEL_SCALE || cfg->model == SMX_MODEL_SCALE_TRIL || cfg->n_labels == n_observed,
               "label heads need model = SISUA, SCALE (SCALAR) or FVAE (SemiFVAE)");
@@ -376,7 +382,8 @@ int smx_model_create(const smx_config* cfg, smx_model** out) {
   m->k = llk_planes(cfg->likelihood);
   m->stochastic = cfg->model != SMX_MODEL_DCA; m->scvi = cfg->model == SMX_MODEL_SCVI; m->scale = cfg->model == SMX_MODEL_SCALE || cfg->model == SMX_MODEL_SCALE_TRIL; m->scale_tril = cfg->model == SMX_MODEL_SCALE_TRIL;
   m->mixpost = cfg->model == SMX_MODEL_SCALE_POST;
-  m->lat_planes = m->mixpost ? 1 + 2 * cfg->n_components : (m->stochastic ? 2 : 1);
+  m->latent_tril = cfg->latent_tril != 0;
+  m->lat_planes = m->mixpost ? 1 + 2 * cfg->n_components : m->latent_tril ? 1 + cfg->latent_dim : (m->stochastic ? 2 : 1);
   m->fvae = cfg->model == SMX_MODEL_FVAE; m->n_heads = m->fvae ? n_observed : cfg->n_labels; m->n_observed = n_observed;
   m->out_has_W[1] = cfg->scvi_dispersion == 0; m->out_has_W[2] = cfg->scvi_inflation == 0;
   m->out_single[1] = cfg->scvi_dispersion == 2; m->out_single[2] = cfg->scvi_inflation == 2;
@@ -560,7 +567,7 @@ int smx_model_destroy(smx_model* m) {
   fr(m->X); fr(m->library); fr(m->mask); fr(m->lgx1); fr(m->hostX); fr(m->hostLib); fr(m->hostLgx1);
   for (int j = 0; j < SMX_MAX_LABELS; ++j) { fr(m->Y[j]); fr(m->laby_raw[j]); fr(m->laby_draw[j]); }
   fr(m->rows2[0]); fr(m->rows2[1]); fr(m->order); fr(m->sched_tab); fr(m->state3); fr(m->mhist);
-  fr(m->resp); fr(m->dklz); fr(m->zmean); fr(m->zpick); fr(m->tril_part);
+  fr(m->resp); fr(m->dklz); fr(m->zmean); fr(m->zpick); fr(m->tril_part); fr(m->ltril);
   for (auto& L : m->disc) { fr(L.xhat); fr(L.out_buf); fr(L.dpre); }
   fr(m->zz); fr(m->u_d); fr(m->tc_cell); fr(m->dl_cell); fr(m->dz_tc); fr(m->disc_dpre); fr(m->disc_db);
   fr(m->noise_eps); fr(m->latbuf); fr(m->dlat); fr(m->z); fr(m->sig); fr(m->eps); fr(m->kl);

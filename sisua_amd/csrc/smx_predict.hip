@@ -51,7 +51,7 @@ static int fetch_forward(smx_model* m, int B, float* z_mean, float* z_scale, flo
     return SMX_OK;
   };
   SMX_CHECK(fetch2d(z_mean, m->mixpost ? m->zmean : m->latbuf, m->mixpost ? Dp : lat_ld, D));   // (mixture-density posterior: the mixture's mean)
-  if (m->stochastic) SMX_CHECK(fetch2d(z_scale, m->sig, Dp, D));
+  if (m->stochastic) SMX_CHECK(m->latent_tril ? fetch2d(z_scale, m->ltril, D * D, D * D) : fetch2d(z_scale, m->sig, Dp, D));   // (tril: the factor L [D][D])
   SMX_CHECK(fetch2d(z_sample, m->z, Dp, D));
   if (m->scvi) {
     SMX_CHECK(fetch2d(l_mean, m->latlbuf, 32, 1));
@@ -267,6 +267,7 @@ int stacked_decoder(smx_model* m, const float* z, long rows, float* const* hb, i
 bool stacked_scoring_ok(const smx_model* m) {
   if (!m->flags.stacked_scoring || !m->stochastic || m->use_injected || m->dec.empty()) return false;
   if (m->mixpost) return false;   // (mixture-density posterior: every draw picks its component -- the draw-by-draw form)
+  if (m->latent_tril) return false;   // (full-covariance posterior: the draw-by-draw form, whose draws are latent_tril_fwd's)
   if (m->scale && (m->Dp > 64 || m->cfg.n_components > 32 || m->scale_tril)) return false;   // (full-covariance components: the draw-by-draw form, whose prior term is scale_prior_fwd's)
   if (m->scvi && !scvi_score_supported(m->Gp)) return false;
   if (!head_loss_supported(1, m->dec.back().out_p, m->Gp) || (m->dec.back().out_p % 4)) return false;
@@ -339,7 +340,8 @@ static int stat_of(smx_model* m, const PredChunk& c, const Pass& ps, const float
 static int add_latent_moments(smx_model* m, PackList& pl, const PredChunk& c, size_t b0) {
   const size_t D = (size_t)m->D, Dp = (size_t)m->Dp;
   SMX_CHECK(pl.add(c.zm ? c.zm + b0 * D : nullptr, D, m->mixpost ? m->zmean : m->latbuf, m->mixpost ? Dp : m->lat_planes * Dp, D));
-  SMX_CHECK(pl.add(c.zs ? c.zs + b0 * D : nullptr, D, m->sig, Dp, D));
+  if (m->latent_tril) SMX_CHECK(pl.add(c.zs ? c.zs + b0 * D * D : nullptr, D * D, m->ltril, D * D, D * D));   // (the factor L [D][D] per cell)
+  else SMX_CHECK(pl.add(c.zs ? c.zs + b0 * D : nullptr, D, m->sig, Dp, D));
   SMX_CHECK(pl.add(c.lm ? c.lm + b0 : nullptr, 1, m->latlbuf, 32, 1));
   return pl.add(c.ls ? c.ls + b0 : nullptr, 1, m->lsig, 1, 1);
 }
@@ -477,6 +479,7 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
   if (cx) SMX_CHECK(check_csr_rows(*cx, (size_t)n_cells, m->G));
   if (sr && sr->tcsr) SMX_CHECK(check_csr_rows(*sr->tcsr, (size_t)n_cells, m->G));
   const size_t N = (size_t)n_cells, G = (size_t)m->G, Gp = (size_t)m->Gp, D = (size_t)m->D, k = (size_t)m->k, S = (size_t)n_samples;
+  const size_t DS = m->latent_tril ? D * D : D;   // z_scale per cell: the factor L [D][D] of a tril posterior, the standard deviations otherwise
   if (!m->stochastic) z_scale = nullptr;
   if (!m->scvi) l_mean = l_scale = l_samples = nullptr;
   PredChunk ch;
@@ -492,7 +495,7 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
   static_assert(SMX_MAX_LABELS == 4, "one segment per label head");
   const Seg plan[] = {
       {&ch.in_x, Gp, cx != nullptr},
-      {&ch.zm, D, z_mean != nullptr}, {&ch.zs, D, z_scale != nullptr}, {&ch.lm, 1, l_mean != nullptr}, {&ch.ls, 1, l_scale != nullptr},
+      {&ch.zm, D, z_mean != nullptr}, {&ch.zs, DS, z_scale != nullptr}, {&ch.lm, 1, l_mean != nullptr}, {&ch.ls, 1, l_scale != nullptr},
       {&ch.zd, S * D, z_samples != nullptr}, {&ch.ld, S, l_samples != nullptr}, {&ch.xp, S * k * G, x_params != nullptr},
       {&ch.st, w_stat, w_stat > 0},
       {&ch.in_raw, G, !cx}, {&ch.in_x, Gp, !cx}, {&ch.in_lib, 2, true}, {&ch.in_lgx1, 1, true},
@@ -558,7 +561,7 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
     }
     // ---- the chunk leaves the device: every segment's rows are contiguous here and in the caller's arrays ----
     if (ch.zm) SMX_CHECK(out(z_mean + c0 * D, ch.zm, Cn * D));
-    if (ch.zs) SMX_CHECK(out(z_scale + c0 * D, ch.zs, Cn * D));
+    if (ch.zs) SMX_CHECK(out(z_scale + c0 * DS, ch.zs, Cn * DS));
     if (ch.lm) SMX_CHECK(out(l_mean + c0, ch.lm, Cn));
     if (ch.ls) SMX_CHECK(out(l_scale + c0, ch.ls, Cn));
     if (ch.st && sr->stat == 2) SMX_CHECK(out(sr->out + c0 * G, ch.st, Cn * G));

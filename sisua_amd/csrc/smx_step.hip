@@ -18,7 +18,7 @@ BnSyncArgs sync_args(smx_model* m) { BnSyncArgs y; y.gather = m->sync_buf; y.ran
 // (forward_pass adds what depends on injected noise)
 static bool front_shapes_ok(smx_model* m, const Pass& ps) {
   const int lat_ld = m->lat_planes * m->Dp;
-  return m->flags.front && !m->scale && !m->mixpost && !sync_bn_on(m, ps.training) && bn_front_supported(ps.B, m->Dp) &&
+  return m->flags.front && !m->scale && !m->mixpost && !m->latent_tril && !sync_bn_on(m, ps.training) && bn_front_supported(ps.B, m->Dp) &&
          (m->Dp == 32 || m->Dp == 64) && m->dec[0].in_p == m->Dp && m->dec[0].out_p % 8 == 0 && (lat_ld % 4) == 0 &&
          m->dec[0].act == SMX_ACT_RELU;   // (the front forms build ReLU in)
 }
@@ -714,6 +714,15 @@ int forward_pass(smx_model* m, const Pass& ps, bool with_loss, bool backward, in
     Timed t(m, "latent_fwd");
     SMX_CHECK(launch_mixlat_fwd(m->st, ma));
   }
+  if (m->latent_tril) {   // RVmeta(D, 'mvntril'): z = mu + L eps and the analytic KL (never the fused front); evaluation passes keep the factor
+    LatentTrilArgs ta;
+    ta.lat = m->latbuf; ta.ld = lat_ld; ta.B = ps.B; ta.D = m->D; ta.Dp = m->Dp;
+    ta.nk = draw_key(m, ST_EPS_Z, ps); ta.rows = ps.rows; ta.cell_base = ps.cell_base;
+    if (const Injected* ij = inj(m, ST_EPS_Z)) { ta.inj_eps = ij->d; ta.inj_ld = ij->ld; }
+    ta.z = m->z; ta.diag = m->sig; ta.eps = m->eps; ta.kl = m->kl; ta.factor = ps.training ? nullptr : m->ltril;
+    Timed t(m, "latent_fwd");
+    SMX_CHECK(launch_latent_tril_fwd(m->st, ta));
+  }
   LatentArgs la;
   la.stochastic = m->stochastic; la.relu = (c.latent_activation == SMX_ACT_RELU); la.training = ps.training;
   la.lat = m->latbuf; la.ld = lat_ld; la.B = ps.B; la.D = m->D; la.Dp = m->Dp;
@@ -726,7 +735,7 @@ int forward_pass(smx_model* m, const Pass& ps, bool with_loss, bool backward, in
   // launches fewer) when the shapes allow; SMX_NO_FRONT=1 keeps the three-launch form.
   front_ok = !encode_only && front_shapes_ok(m, ps) && (!la.inj_eps || (la.inj_ld % 4) == 0);
   front_la = la;
-  if (front_ok || m->mixpost) {
+  if (front_ok || m->mixpost || m->latent_tril) {
     // (launched below with the decoder / drawn above)
   } else if (no_moments && !m->scale) {
     // (the stacked scoring pass draws from the head's raw output itself: sigma, z and the KL of draw 0 would be a launch nobody reads)
@@ -1416,7 +1425,7 @@ int backward_pass(smx_model* m, const Pass& ps) {
   // (a property of the MODEL, not of the step: at a wide panel the optimiser's chunks may ride with the d z launch -- how many is scheduling
   // state --, so wide panels keep that launch whatever rides with it this step; the fold's rounding never depends on what else is going on)
   const bool wide_panel = m->Gp >= std::min(4096, head_fused_min_genes());
-  m->fold_dz_now = bfront && !m->mixpost && !m->scvi && !m->scale && !m->fvae && m->stochastic && !wide_panel && !m->dec.empty() &&
+  m->fold_dz_now = bfront && !m->mixpost && !m->latent_tril && !m->scvi && !m->scale && !m->fvae && m->stochastic && !wide_panel && !m->dec.empty() &&
                    m->dec[0].out_p == 128 && m->dec[0].in_p == m->Dp && (m->tensors[m->dec[0].tW].ld % 4) == 0 && m->tensors[m->dec[0].tW].ld >= 128 &&
                    bn_bwd_fold_supported(ps.B, lat_ld, m->Dp);
   std::vector<GemmArgs> tail;
@@ -1432,6 +1441,16 @@ int backward_pass(smx_model* m, const Pass& ps) {
     ma.klw = kl_weight(m, ps, inv_gb, 0); ma.dlat = m->dlat;
     Timed t(m, "latent_bwd");
     SMX_CHECK(launch_mixlat_bwd(m->st, ma));
+  } else if (m->latent_tril) {   // the full-covariance posterior: the same shape -- d z as slabs, then a launch of its own
+    int dz_slabs = 1;
+    SMX_CHECK(mlp_backward(m, m->dec, ps, m->z, m->Dp, false, n_slabs, false, &dz_slabs, "", nullptr, nullptr, nullptr, bfront ? &tail : nullptr));
+    LatentTrilArgs ta;
+    ta.lat = m->latbuf; ta.ld = lat_ld; ta.B = ps.B; ta.D = m->D; ta.Dp = m->Dp;
+    ta.z = m->z; ta.diag = m->sig; ta.eps = m->eps;
+    ta.dz = m->slab; ta.dz_slabs = dz_slabs; ta.dz_slab_stride = (long)ps.B * m->dec[0].in_p; ta.ldz = m->dec[0].in_p;
+    ta.klw = kl_weight(m, ps, inv_gb, 0); ta.dlat = m->dlat;
+    Timed t(m, "latent_bwd");
+    SMX_CHECK(launch_latent_tril_bwd(m->st, ta));
   } else {
     SMX_CHECK(mlp_backward(m, m->dec, ps, m->z, m->Dp, false, n_slabs, false, nullptr, "", &le, nullptr, nullptr, bfront ? &tail : nullptr));
   }
@@ -1458,7 +1477,7 @@ int backward_pass(smx_model* m, const Pass& ps) {
       h.C = m->slab; h.ldc = eL.out_p; h.slab_stride = (long)ps.B * eL.out_p;
       h.M = ps.B; h.N = eL.out_p; h.K = lat_ld;
       int effs[2] = {1, 1};
-      if (lat_ld > 128) {   // (a wide latent head -- the mixture-density posterior's (1 + 2 C) planes: d h contracts over all of them)
+      if (lat_ld > 128) {   // (a wide latent head -- the mixture-density posterior's (1 + 2 C) planes, the tril posterior's 1 + D: d h contracts over all of them)
         h.split_k = suggest_split_k(ps.B, eL.out_p, lat_ld);
         SMX_REQUIRE((size_t)std::max(h.split_k, 1) * (size_t)h.slab_stride <= m->slab_cap, "split-K slabs exceed the slab buffer");
       }

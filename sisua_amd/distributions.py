@@ -103,6 +103,58 @@ class MultivariateNormalDiag(Normal):
     return super().log_prob(x).sum(-1)
 
 
+class MultivariateNormalTriL(Distribution):
+  """Full-covariance Gaussian over the last axis, N(loc, L L^T) with L lower-triangular (the RVmeta(D, 'mvntril') latent posterior;
+  TFP MultivariateNormalTriL semantics).  Parameters: locations [..., D], scale factors [..., D, D] (entries above the diagonal ignored)."""
+  _event_ndims = 1
+
+  def __init__(self, loc, scale_tril, name="MultivariateNormalTriL"):
+    self.loc = np.asarray(loc)
+    self.scale_tril = np.tril(np.asarray(scale_tril))
+    self.name = name
+
+  def _params(self):
+    return [self.loc, self.scale_tril[..., 0]]
+
+  def mean(self):
+    return np.broadcast_to(self.loc, self.batch_shape + self.event_shape).copy()
+
+  def covariance(self):
+    L = self.scale_tril.astype(np.float64)
+    return L @ np.swapaxes(L, -1, -2)
+
+  def variance(self):
+    return (self.scale_tril.astype(np.float64) ** 2).sum(-1)
+
+  def stddev(self):
+    return np.sqrt(self.variance())
+
+  def _whiten(self, x):
+    """u = L^-1 (x - loc) by forward substitution (D is 32 at most)."""
+    d = np.asarray(x, np.float64) - self.loc
+    L = np.broadcast_to(self.scale_tril.astype(np.float64), d.shape[:-1] + self.scale_tril.shape[-2:])
+    u = np.zeros(d.shape)
+    for p in range(d.shape[-1]):
+      u[..., p] = (d[..., p] - (L[..., p, :p] * u[..., :p]).sum(-1)) / L[..., p, p]
+    return u
+
+  def _log_det(self):
+    return np.log(np.einsum("...pp->...p", self.scale_tril.astype(np.float64))).sum(-1)
+
+  def log_prob(self, x):
+    u = self._whiten(x)
+    return -0.5 * (u * u).sum(-1) - self._log_det() - 0.5 * u.shape[-1] * np.log(2.0 * np.pi)
+
+  def entropy(self):
+    D = self.scale_tril.shape[-1]
+    return 0.5 * D * (1.0 + np.log(2.0 * np.pi)) + self._log_det()
+
+  def sample(self, sample_shape=(), seed=None):
+    rng = np.random.default_rng(seed)
+    eps = rng.standard_normal(self._sshape(sample_shape) + self.batch_shape + self.event_shape)
+    return self.loc + np.einsum("...pq,...q->...p", self.scale_tril, eps)
+
+
 class Deterministic(Distribution):
   """Point mass (DCA's deterministic latent, dca.py:13-28)."""
   _event_ndims = 1
@@ -467,6 +519,8 @@ def concat_distributions(dists: Sequence[Distribution], axis: int = 0, name: Opt
   if isinstance(d0, ZeroInflated):
     return ZeroInflated(concat_distributions([d.count_distribution for d in dists], axis, d0.count_distribution.name),
                         _cat([d.logits for d in dists], axis), name=nm)
+  if isinstance(d0, MultivariateNormalTriL):
+    return MultivariateNormalTriL(_cat([d.loc for d in dists], axis), _cat([d.scale_tril for d in dists], axis), name=nm)
   if isinstance(d0, MultivariateNormalDiag):
     return MultivariateNormalDiag(_cat([d.loc for d in dists], axis), _cat([d.scale for d in dists], axis), name=nm)
   if isinstance(d0, Normal):

@@ -63,6 +63,14 @@ def _sparse(x) -> bool:
   return is_sparse(x)
 
 
+def _tril_scale(out):
+  """A full-covariance posterior's results: z_scale = the marginal standard deviations sqrt(diag(L L^T)) of the factor the device returned."""
+  L = out.get("scale_tril")
+  if L is not None:
+    out["z_scale"][...] = np.sqrt(np.square(L, dtype=np.float64).sum(-1))
+  return out
+
+
 def make_smx_config(cfg: ModelConfig, max_batch: int) -> smx_config:
   c = smx_config()
   c.abi_version = _hip.SMX_ABI_VERSION
@@ -93,6 +101,7 @@ def make_smx_config(cfg: ModelConfig, max_batch: int) -> smx_config:
   c.bn_momentum, c.bn_eps = cfg.bn_momentum, cfg.bn_eps
   c.lr, c.adam_beta1, c.adam_beta2, c.adam_eps, c.clipnorm = cfg.lr, cfg.adam_beta1, cfg.adam_beta2, cfg.adam_eps, cfg.clipnorm
   c.n_components = int(cfg.n_components)
+  c.latent_tril = int(bool(cfg.latent_tril))
   c.disc_units, c.disc_layers = int(cfg.disc_units), int(cfg.disc_layers)
   c.gamma, c.disc_leak = float(cfg.gamma), float(cfg.disc_leak)
   c.max_batch = int(max_batch)
@@ -425,11 +434,14 @@ class Engine:
     lead = () if S is None else (S,)
     out = dict(z_mean=np.empty((B, D), np.float32), z_sample=np.empty(lead + (B, D), np.float32))
     out["z_scale"] = np.empty((B, D), np.float32) if cfg.stochastic else None
+    zs = out["z_scale"]
+    if cfg.latent_tril:   # the full-covariance posterior: the device hands back the factor L [B, D, D]; z_scale = its marginal stddevs (_tril_scale)
+      out["scale_tril"] = zs = np.empty((B, D, D), np.float32)
     if cfg.model == "scvi":
       out.update(l_mean=np.empty((B,), np.float32), l_scale=np.empty((B,), np.float32), l_sample=np.empty(lead + (B,), np.float32))
     out["x_params"] = np.empty(lead + (k, B, G), np.float32) if want_x_params else None
     out["y_params"] = [np.empty(lead + (B, label_planes(llk, P) * P), np.float32) for P, llk in cfg.head_labels]
-    return out, (_fp(out["z_mean"]), _fp(out["z_scale"]), _fp(out["z_sample"]), _fp(out.get("l_mean")), _fp(out.get("l_scale")),
+    return out, (_fp(out["z_mean"]), _fp(zs), _fp(out["z_sample"]), _fp(out.get("l_mean")), _fp(out.get("l_scale")),
                  _fp(out.get("l_sample")), _fp(out["x_params"]), _fps(out["y_params"]))
 
   def forward(self, row_ids=None, x=None, library=None, sample_index: int = 0, training: bool = False,
@@ -438,7 +450,7 @@ class Engine:
     B, keep, cells = self._cells(row_ids, x, library)
     out, res = self._outputs(B, want_x_params=want_x_params)
     check(self.lib.smx_forward(self._h, *cells, B, int(sample_index), int(training), *res))
-    return out
+    return _tril_scale(out)
 
   def forward_samples(self, n_samples: int, row_ids=None, x=None, library=None):
     """n_samples Monte-Carlo draws of one batch in one call (the encoders run once): arrays with a leading draw axis
@@ -447,7 +459,7 @@ class Engine:
     B, keep, cells = self._cells(row_ids, x, library)
     out, res = self._outputs(B, S)
     check(self.lib.smx_forward_samples(self._h, *cells, B, S, *res))
-    return out
+    return _tril_scale(out)
 
   def predict(self, x, library=None, n_samples: int = 1, batch: Optional[int] = None, want_x_params: bool = True):
     """Eval-mode forward of a whole host matrix in one call (smx_predict): arrays over ALL cells, with a leading draw
@@ -464,7 +476,7 @@ class Engine:
       check(self.lib.smx_predict_csr(self._h, *_csr_ptrs(xa), _fp(la), N, B, S, *res))
     else:
       check(self.lib.smx_predict(self._h, _fp(xa), _fp(la), N, B, S, *res))
-    return out
+    return _tril_scale(out)
 
   STATS = {"mean": 0, "variance": 1, "mean_over_samples": 2, "log_prob": 3}
 

@@ -22,7 +22,7 @@ import numpy as np
 
 from sisua_amd import distributions as D
 from sisua_amd import interpolation, optimizers
-from sisua_amd.config import ModelConfig, NetConf, RVmeta, init_params
+from sisua_amd.config import TRIL_LATENT_POSTERIORS, ModelConfig, NetConf, RVmeta, init_params
 from sisua_amd.data import BatchDataset, SingleCellOMIC, as_csr, is_sparse, library_matrix
 from sisua_amd.engine import Engine
 
@@ -198,6 +198,7 @@ class SingleCellModel:
                        lr=float(self._opt["lr"]), clipnorm=float(self._opt["clipnorm"]), seed=self.seed,
                        extra_outputs=tuple(extras), dispersion=str(getattr(self, "_dispersion", "full")), inflation=str(getattr(self, "_inflation", "full")),
                        n_components=int(getattr(self, "_n_components", 10)), covariance=str(getattr(self, "_covariance", "none")), latent_mixture=bool(getattr(self, "_latent_mixture", False)),
+                       latent_tril=self._latents[0].posterior in TRIL_LATENT_POSTERIORS,
                        **getattr(self, "_ties", {}), **getattr(self, "_disc_cfg", {}))
 
   def _ensure_engine(self, max_batch: int) -> Engine:
@@ -617,7 +618,9 @@ class SingleCellModel:
   # ---- inference ------------------------------------------------------------------------------
   def _latent_dists(self, out, sl=slice(None)):
     cfg = self._cfg
-    if cfg.stochastic:
+    if cfg.latent_tril:
+      qz = D.MultivariateNormalTriL(out["z_mean"][sl], out["scale_tril"][sl], name=self._latents[0].name or "Latents")
+    elif cfg.stochastic:
       qz = D.MultivariateNormalDiag(out["z_mean"][sl], out["z_scale"][sl], name=self._latents[0].name or "Latents")
     else:
       qz = D.Deterministic(out["z_sample"][sl], name=self._latents[0].name or "Latents")
@@ -859,7 +862,13 @@ class SingleCellModel:
     for j, yj in enumerate(ys):   # (the observed heads come first)
       llk[self._outputs[1 + j].name or f"output{1 + j}"] = np.asarray(heads[j].log_prob(yj), np.float64)
     logw = sum(llk.values())
-    if cfg.stochastic:
+    if cfg.latent_tril:
+      # the full-covariance posterior: log N(z; 0, I) - log q(z | x) = -|z|^2 / 2 + |eps|^2 / 2 + sum_i log L_ii with eps = L^-1 (z - mu)
+      qz = D.MultivariateNormalTriL(o["z_mean"].astype(np.float64), o["scale_tril"].astype(np.float64))
+      z = o["z_sample"].astype(np.float64)
+      eps = qz._whiten(z)
+      logw = logw + (-0.5 * z ** 2 + 0.5 * eps ** 2).sum(-1) + qz._log_det()
+    elif cfg.stochastic:
       z, mu, sg = o["z_sample"].astype(np.float64), o["z_mean"].astype(np.float64), o["z_scale"].astype(np.float64)
       eps = (z - mu) / sg
       if cfg.model == "scale" and not cfg.latent_mixture:
