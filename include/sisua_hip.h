@@ -58,7 +58,14 @@ typedef enum { SMX_MODEL_VAE = 0, SMX_MODEL_DCA = 1, SMX_MODEL_SCVI = 2, SMX_MOD
  * data/_single_cell_base.py:518-533). */
 /* SMX_LLK_MSE: RVmeta(dim, 'mse') (the reference's tests/test_singlecell_models.py:82-91, 97-100): a deterministic output, ONE
  * parameter plane (the mean), log p(x) := -mean_g (x - mean)^2 -- exactly minus tf.losses.mse.  No marginal-likelihood scoring. */
-typedef enum { SMX_LLK_NB = 0, SMX_LLK_ZINB = 1, SMX_LLK_NBD = 2, SMX_LLK_ZINBD = 3, SMX_LLK_MSE = 4 } smx_likelihood;
+/* SMX_LLK_BERNOULLI: RVmeta(dim, 'bernoulli') (binarised peak matrices: SCALE / SCALAR's scATAC input), ONE plane of logits l:
+ * log p(x) = sum_g x l - softplus(l) (TFP Bernoulli.log_prob, defined for any x in [0, 1]).
+ * SMX_LLK_NORMAL: RVmeta(dim, 'normal' / 'gaussian' / 'diag') (real-valued inputs: log-normalised expression, CLR protein panels), TWO
+ * planes -- loc m | raw scale s, sigma = softplus(s + softplus^-1(1)): log p(x) = sum_g -z^2 / 2 - log sigma - log(2 pi) / 2, z = (x - m) / sigma.
+ * Both are normalised densities WITHOUT the count constant -sum_g lgamma(x + 1): they score (marginal likelihood, posterior_llk) like the
+ * count posteriors.  The same element forms as SMX_LABEL_BERNOULLI / SMX_LABEL_NORMAL. */
+typedef enum { SMX_LLK_NB = 0, SMX_LLK_ZINB = 1, SMX_LLK_NBD = 2, SMX_LLK_ZINBD = 3, SMX_LLK_MSE = 4, SMX_LLK_BERNOULLI = 5,
+               SMX_LLK_NORMAL = 6 } smx_likelihood;
 /* Label heads of SISUA (vae.py:19-44): NB (ADT counts), one-hot categorical (cell types); of MISA (vae.py:47-98): every
  * label dimension a mixture of label_components (2..4) negative binomials (SMX_LABEL_MIXNB) or, for continuous labels, normals
  * (SMX_LABEL_MIXGAUSS, 'mixgaussian', vae.py:86-92); SMX_LABEL_MIXTRIL ('mixtril', the class's docstring example vae.py:58): ONE

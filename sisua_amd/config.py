@@ -16,6 +16,11 @@ import numpy as np
 SOFTPLUS_INV_1 = float(np.log(np.expm1(1.0)))   # softplus(SOFTPLUS_INV_1) == 1
 LIKELIHOODS = ("nb", "zinb", "nbd", "zinbd")
 OUTPUT_POSTERIORS = LIKELIHOODS + ("mse",)   # 'mse': deterministic output, -log_prob(x) = mean squared error (tests/test_singlecell_models.py:82-91)
+# non-count first outputs: 'bernoulli' (binarised peak matrices, one plane of logits) and 'normal' (real-valued inputs: loc | raw scale,
+# scale softplus(raw + softplus^-1(1))); RVmeta's 'gaussian' / 'diag' are stored as 'normal'
+REAL_OUTPUTS = ("bernoulli", "normal")
+OUTPUT_POSTERIORS = OUTPUT_POSTERIORS + REAL_OUTPUTS
+OUTPUT_ALIASES = {"gaussian": "normal", "diag": "normal"}
 # head kinds on the decoder output (label variables and outputs[1:]); the mixtures carry their component count: 'mixnb2' .. 'mixtril4'
 HEAD_KINDS = ("nb", "nbd", "zinb", "zinbd", "onehot", "bernoulli", "normal")
 MIXTURE_HEAD_KINDS = ("mixnb", "mixgauss", "mixtril", "mixzinb")
@@ -194,7 +199,7 @@ class ModelConfig:
 
   @property
   def k(self) -> int:
-    return 1 if self.likelihood == "mse" else 3 if self.likelihood in ("zinb", "zinbd") else 2
+    return 1 if self.likelihood in ("mse", "bernoulli") else 3 if self.likelihood in ("zinb", "zinbd") else 2
 
   @property
   def stochastic(self) -> bool:

@@ -589,6 +589,7 @@ int head_fused_prepare() {
   SMX_HF_ATTR2((head_fused_kernel<LK, 0, 0>), NP); SMX_HF_ATTR2((head_fused_kernel<LK, 0, 1>), NP);                       \
   SMX_HF_ATTR2((head_fused_kernel<LK, 1, 0>), NP); SMX_HF_ATTR2((head_fused_kernel<LK, 1, 1>), NP)
   SMX_HF_ATTR(SMX_LLK_NB, 2); SMX_HF_ATTR(SMX_LLK_ZINB, 3); SMX_HF_ATTR(SMX_LLK_NBD, 2); SMX_HF_ATTR(SMX_LLK_ZINBD, 3);
+  SMX_HF_ATTR(SMX_LLK_NORMAL, 2);
 #undef SMX_HF_ATTR
 #undef SMX_HF_ATTR2
   done = true;
@@ -630,6 +631,7 @@ int launch_head_fused(hipStream_t st, const HeadFusedArgs& a_in, int* n_slabs, i
       case SMX_LLK_ZINB: rc = launch_hf<SMX_LLK_ZINB>(st, a, grid, c0 > 0, ev); break;
       case SMX_LLK_NBD: rc = launch_hf<SMX_LLK_NBD>(st, a, grid, c0 > 0, ev); break;
       case SMX_LLK_ZINBD: rc = launch_hf<SMX_LLK_ZINBD>(st, a, grid, c0 > 0, ev); break;
+      case SMX_LLK_NORMAL: rc = launch_hf<SMX_LLK_NORMAL>(st, a, grid, c0 > 0, ev); break;
       default: set_error("head_fused: unknown likelihood"); return SMX_ERR_INVALID;
     }
     if (rc != SMX_OK) return rc;

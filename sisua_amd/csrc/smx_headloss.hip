@@ -248,6 +248,7 @@ int launch_out_head_loss(hipStream_t st, const HeadLossArgs& a_in) {
     case SMX_LLK_ZINB: launch_hl<SMX_LLK_ZINB>(st, a, grid); break;
     case SMX_LLK_NBD: launch_hl<SMX_LLK_NBD>(st, a, grid); break;
     case SMX_LLK_ZINBD: launch_hl<SMX_LLK_ZINBD>(st, a, grid); break;
+    case SMX_LLK_NORMAL: launch_hl<SMX_LLK_NORMAL>(st, a, grid); break;   // (two planes like 'nb'; 'bernoulli' / 'mse': the product + count_loss pair)
     default: set_error("out_head_loss: unknown likelihood"); return SMX_ERR_INVALID;
   }
   SMX_HIP(hipGetLastError());

@@ -127,7 +127,11 @@ struct LossArgs {
   int B = 0, G = 0, Gp = 0;
   float grad_scale = 1.f;                 // d loss / d llk (= -1/B_global); 1 for the test entry
 };
-inline int llk_planes(int likelihood) { return likelihood == SMX_LLK_MSE ? 1 : (likelihood == SMX_LLK_ZINB || likelihood == SMX_LLK_ZINBD) ? 3 : 2; }
+inline int llk_planes(int likelihood) {
+  return (likelihood == SMX_LLK_MSE || likelihood == SMX_LLK_BERNOULLI) ? 1 : (likelihood == SMX_LLK_ZINB || likelihood == SMX_LLK_ZINBD) ? 3 : 2;
+}
+// the likelihood's data-only constant sum_g lgamma(x + 1) belongs to the count posteriors only
+inline bool llk_has_count_const(int likelihood) { return likelihood >= SMX_LLK_NB && likelihood <= SMX_LLK_ZINBD; }
 int loss_chunks(int Gp, int B);   // partial sums per cell written by a launch over B cells
 int loss_chunks_max(int Gp);      // upper bound over every batch size (allocation)
 int launch_count_loss(hipStream_t st, const LossArgs& a);

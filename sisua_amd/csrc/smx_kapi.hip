@@ -93,7 +93,8 @@ int smx_k_count_llk(int likelihood, int direct, const float* x, const float* pla
     for (int b = 0; b < B; ++b) {
       double s = 0.0;
       for (int c = 0; c < nch; ++c) s += part[(size_t)b * nch + c];
-      for (int g = 0; g < G; ++g) { const float v = x[(size_t)b * G + g]; if (v > 0.f) s -= lgamma((double)v + 1.0); }
+      if (likelihood != SMX_LLK_BERNOULLI && likelihood != SMX_LLK_NORMAL)   // (-sum lgamma(x + 1): not of the 'bernoulli' / 'normal' densities)
+        for (int g = 0; g < G; ++g) { const float v = x[(size_t)b * G + g]; if (v > 0.f) s -= lgamma((double)v + 1.0); }
       llk[b] = (float)s;
     }
     if (grads)
@@ -331,7 +332,8 @@ int smx_k_head_fused(int likelihood, int u16, const float* x, const float* d, co
     for (int b = 0; b < B; ++b) {
       double s = 0.0;
       for (int c = 0; c < n_gt; ++c) s += part[(size_t)b * n_gt + c];
-      for (int g = 0; g < G; ++g) { const float v = x[(size_t)b * G + g]; if (v > 0.f) s -= lgamma((double)v + 1.0); }
+      if (likelihood != SMX_LLK_BERNOULLI && likelihood != SMX_LLK_NORMAL)   // (-sum lgamma(x + 1): not of the 'bernoulli' / 'normal' densities)
+        for (int g = 0; g < G; ++g) { const float v = x[(size_t)b * G + g]; if (v > 0.f) s -= lgamma((double)v + 1.0); }
       llk[b] = (float)s;
     }
     for (int c = 0; c < k; ++c) {

@@ -1,4 +1,4 @@
-// smx_loss.h -- elementwise NB / ZINB / NBD / ZINBD log-likelihood and its gradients wrt the parameter
+// smx_loss.h -- elementwise NB / ZINB / NBD / ZINBD (and Bernoulli / normal) log-likelihood and its gradients wrt the parameter
 // planes; shared by the standalone loss kernel and the label heads (smx_loss.hip) and the
 // fused output-head kernel (smx_head.hip).
 #ifndef SMX_LOSS_H_
@@ -9,11 +9,37 @@
 namespace smx {
 
 // ===========================================================================
-// count likelihood, elementwise
+// Bernoulli and normal, elementwise: the gene output's SMX_LLK_BERNOULLI / SMX_LLK_NORMAL (count_elem / count_elem_vec below).  The
+// label heads SMX_LABEL_BERNOULLI / SMX_LABEL_NORMAL (label_loss_kernel, smx_loss.hip) spell out the same operations in the same order:
+// called from there, these functions moved two independent register copies of label_loss_kernel's mixture branch, and that
+// kernel is kept instruction for instruction
+// ===========================================================================
+// logits l (TFP Bernoulli.log_prob, any x in [0, 1]): log p(x) = x l - softplus(l), d / d l = x - sigmoid(l); softplus and sigmoid from
+// one exp(-|l|): no overflow at saturation
+__device__ inline void bernoulli_elem(float x, float l, float& llk, float& d) {
+  const SpSg s = softplus_sigmoid(l);
+  llk = x * l - s.sp;
+  d = x - s.sg;
+}
+// loc m, raw scale s, sigma = softplus(s + softplus^-1(1)) ([3P-recall] odin's 'softplus1', the scale activation of the latents and of
+// one 'mixgaussian' component): log p(x) = -z^2 / 2 - log sigma - log(2 pi) / 2, z = (x - m) / sigma;
+// d m = z / sigma, d s = (z^2 - 1) / sigma * sigmoid(s + softplus^-1(1))
+__device__ inline void normal_elem(float x, float m, float s_raw, float& llk, float& d0, float& d1) {
+  const SpSg s = softplus_sigmoid(s_raw + SMX_SOFTPLUS_INV_1);   // sp = sigma, sg = d sigma / d s
+  const float inv = frcp(s.sp), zz = (x - m) * inv;
+  llk = -0.5f * zz * zz - flog(s.sp) - 0.9189385332046727f;   // 0.5 log(2 pi)
+  d0 = zz * inv;
+  d1 = (zz * zz - 1.f) * inv * s.sg;
+}
+
+// ===========================================================================
+// count likelihood, elementwise (and the two non-count outputs above: no lgamma / digamma, p2 unused, d2 = 0; Bernoulli also d1 = 0)
 // ===========================================================================
 template <int LK, int DIRECT>
 __device__ inline void count_elem(float x, float p0, float p1, float p2, float& llk, float& d0, float& d1,
                                   float& d2) {
+  if (LK == SMX_LLK_BERNOULLI) { bernoulli_elem(x, p0, llk, d0); d1 = 0.f; d2 = 0.f; return; }
+  if (LK == SMX_LLK_NORMAL) { normal_elem(x, p0, p1, llk, d0, d1); d2 = 0.f; return; }
   float ell;
   if (LK == SMX_LLK_NB || LK == SMX_LLK_ZINB) {
     const float r = fexp(p0);
@@ -171,6 +197,15 @@ template <int LK, int DIRECT, int N, class Q = float2*>
 __device__ inline void count_elem_vec(const float (&x)[N], const float (&p0)[N], const float (&p1)[N], const float (&p2)[N],
                                       float (&llk)[N], float (&d0)[N], float (&d1)[N], float (&d2)[N],
                                       Q q = nullptr) {
+  if (LK == SMX_LLK_BERNOULLI || LK == SMX_LLK_NORMAL) {   // (no lgamma / digamma: the queue is not used)
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+      if (LK == SMX_LLK_BERNOULLI) { bernoulli_elem(x[e], p0[e], llk[e], d0[e]); d1[e] = 0.f; }
+      else normal_elem(x[e], p0[e], p1[e], llk[e], d0[e], d1[e]);
+      d2[e] = 0.f;
+    }
+    return;
+  }
   float ell[N];
   if (LK == SMX_LLK_NB || LK == SMX_LLK_ZINB) {
     float r[N], lg[N], dg[N];

@@ -1,5 +1,5 @@
 // smx_loss.hip -- the count likelihoods over smx_loss.h's elementwise terms (gfx950):
-//  count_loss  NB / ZINB / NBD / ZINBD log-likelihood, forward + gradient wrt the parameter planes, one pass over B x G
+//  count_loss  NB / ZINB / NBD / ZINBD / Bernoulli / normal log-likelihood, forward + gradient wrt the parameter planes, one pass over B x G
 //              (the bandwidth-bound kernel the roofline is quoted on: SURVEY.md 8d, rows a-10/a-11)
 //  label_loss  the masked NB / one-hot label heads of SISUA (a-13), the Bernoulli / normal heads and the mixture (tril) label head
 // One unit for both: count_loss calls count_elem only on its diagnostic path (likelihood -2), with x = 0.  Without the label heads'
@@ -33,10 +33,11 @@ __device__ inline void vstore(float* p, const float (&v)[VEC]) {
 
 template <int LK, int DIRECT, int BWD, int VEC, int BLOCK = 256, int U16 = 0>   // U16: counts from the compact uint16 store
 __global__ __launch_bounds__(BLOCK) void count_loss_kernel(LossArgs a) {
-  constexpr int K = LK == SMX_LLK_MSE ? 1 : (LK == SMX_LLK_ZINB || LK == SMX_LLK_ZINBD) ? 3 : 2;
+  constexpr int K = (LK == SMX_LLK_MSE || LK == SMX_LLK_BERNOULLI) ? 1 : (LK == SMX_LLK_ZINB || LK == SMX_LLK_ZINBD) ? 3 : 2;
   constexpr int LKC = LK == SMX_LLK_MSE ? SMX_LLK_NB : LK;
-  // every wave's non-zero counts go through ONE compacted pass of the lgamma / digamma code (smx_loss.h: lgamma_digamma_diff_queue)
-  __shared__ float2 lq[LK == SMX_LLK_MSE ? 1 : BLOCK * VEC];
+  // every wave's non-zero counts go through ONE compacted pass of the lgamma / digamma code (smx_loss.h: lgamma_digamma_diff_queue);
+  // 'bernoulli' / 'normal' have no lgamma / digamma
+  __shared__ float2 lq[(LK == SMX_LLK_MSE || LK == SMX_LLK_BERNOULLI || LK == SMX_LLK_NORMAL) ? 1 : BLOCK * VEC];
   const float inv_g = 1.f / (float)a.G;   // SMX_LLK_MSE: -log p = mean over the genes of (x - mean)^2
   const int b = blockIdx.y;
   const int g0 = (blockIdx.x * BLOCK + threadIdx.x) * VEC;
@@ -143,6 +144,8 @@ int launch_count_loss(hipStream_t st, const LossArgs& a) {
       if (a.direct) launch_loss_t<SMX_LLK_ZINBD, 1>(st, a, grid); else launch_loss_t<SMX_LLK_ZINBD, 0>(st, a, grid);
       break;
     case SMX_LLK_MSE: launch_loss_t<SMX_LLK_MSE, 0>(st, a, grid); break;
+    case SMX_LLK_BERNOULLI: launch_loss_t<SMX_LLK_BERNOULLI, 0>(st, a, grid); break;
+    case SMX_LLK_NORMAL: launch_loss_t<SMX_LLK_NORMAL, 0>(st, a, grid); break;
     default: set_error("count_loss: unknown likelihood"); return SMX_ERR_INVALID;
   }
   SMX_HIP(hipGetLastError());
@@ -243,6 +246,7 @@ __global__ __launch_bounds__(256) void label_loss_kernel(LabelArgs a) {
     }
     llk = wave_sum(llk);
   } else if (a.kind == SMX_LABEL_BERNOULLI) {
+    // (the operations of smx_loss.h's bernoulli_elem, the gene output's form)
     // every label dimension its own binary variable, one plane of logits l (TFP Bernoulli.log_prob, any y in [0, 1]):
     // log p(y) = y l - softplus(l), d / d l = y - sigmoid(l); softplus and sigmoid from one exp(-|l|): no overflow at saturation
     for (int p = lane; p < a.Pp; p += 64) {
@@ -257,6 +261,7 @@ __global__ __launch_bounds__(256) void label_loss_kernel(LabelArgs a) {
     }
     llk = wave_sum(llk);
   } else if (a.kind == SMX_LABEL_NORMAL) {
+    // (the operations of smx_loss.h's normal_elem, the gene output's form)
     // an independent normal per label dimension, planes loc m | raw scale s, sigma = softplus(s + softplus^-1(1)) ([3P-recall] odin's
     // 'softplus1', the scale activation of the latents and of one 'mixgaussian' component above):
     // log p(y) = -z^2 / 2 - log sigma - log(2 pi) / 2, z = (y - m) / sigma; d m = z / sigma, d s = (z^2 - 1) / sigma * sigmoid(s + softplus^-1(1))

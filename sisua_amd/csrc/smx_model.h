@@ -237,6 +237,7 @@ struct smx_model {
   float* library = nullptr; uint8_t* mask = nullptr; float* lgx1 = nullptr;
   // host-batch staging for smx_forward(host_x)
   float* hostX = nullptr; float* hostLib = nullptr; float* hostLgx1 = nullptr;
+  float* zero_rows = nullptr;   // [max_batch] zeros: the row constants of the 'bernoulli' / 'normal' outputs (no sum lgamma(x + 1)) in scoring
   // step state
   int32_t* rows2[2] = {nullptr, nullptr}; int32_t* order = nullptr; size_t order_cap = 0;
   float2* sched_tab = nullptr; size_t sched_cap = 0;   // (beta, lr) of the call's steps by cursor: what step_begin / the optimiser's closing workgroup read

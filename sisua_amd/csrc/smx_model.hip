@@ -339,7 +339,7 @@ int smx_model_create(const smx_config* cfg, smx_model** out) {
   if (cfg->model == SMX_MODEL_SCALE || cfg->model == SMX_MODEL_SCALE_TRIL) SMX_REQUIRE(cfg->n_components >= 2 && cfg->n_components <= 32, "scale: 2..32 mixture components");
   if (cfg->model == SMX_MODEL_SCALE_TRIL) SMX_REQUIRE(cfg->latent_dim <= 32, "scale with full-covariance components: at most 32 latent dimensions");
   if (cfg->model == SMX_MODEL_SCALE_POST) SMX_REQUIRE(cfg->n_components >= 2 && cfg->n_components <= 8 && cfg->n_components <= cfg->latent_dim && cfg->latent_dim <= 64, "scale with a mixture-density posterior: 2 .. min(latent_dim, 8) components, at most 64 latent dimensions");
-  SMX_REQUIRE(cfg->likelihood >= SMX_LLK_NB && cfg->likelihood <= SMX_LLK_MSE, "unknown likelihood");
+  SMX_REQUIRE(cfg->likelihood >= SMX_LLK_NB && cfg->likelihood <= SMX_LLK_NORMAL, "unknown likelihood");
   SMX_REQUIRE(cfg->n_labels >= 0 && cfg->n_labels <= SMX_MAX_LABELS, "too many label heads");
   // (SCALE with label heads = SCALAR, sisua/models/scale.py:52-59: the mixture prior of SCALE under SISUA's semi-supervised heads)
   int n_observed = 0;
@@ -495,6 +495,10 @@ int smx_model_create(const smx_config* cfg, smx_model** out) {
   if ((rc = dmalloc(&m->state3, (size_t)3)) || (rc = dmalloc(&m->hostX, B * m->Gp)) || (rc = dmalloc(&m->hostLib, B * 2)) ||
       (rc = dmalloc(&m->hostLgx1, B)) || (rc = alloc_rows(m, B)))
     return fail(rc);
+  if (!llk_has_count_const(cfg->likelihood)) {
+    if ((rc = dmalloc(&m->zero_rows, B))) return fail(rc);
+    if (hipMemset(m->zero_rows, 0, B * sizeof(float)) != hipSuccess) { set_error("zero_rows: hipMemset failed"); return fail(SMX_ERR_HIP); }
+  }
   set_row_caps(m, B);
   // ---- optimiser chunk table ----
   std::vector<OptChunk> chunks;
@@ -564,7 +568,7 @@ int smx_model_destroy(smx_model* m) {
   for (auto* mlp : {&m->enc, &m->encl, &m->dec})
     for (auto& L : *mlp) { fr(L.xhat); fr(L.out_buf); fr(L.dpre); fr(L.inv_std); fr(L.noise); }
   release_csr(m);   // (the sparse store: m->X aliased its expansion tile)
-  fr(m->X); fr(m->library); fr(m->mask); fr(m->lgx1); fr(m->hostX); fr(m->hostLib); fr(m->hostLgx1);
+  fr(m->X); fr(m->library); fr(m->mask); fr(m->lgx1); fr(m->hostX); fr(m->hostLib); fr(m->hostLgx1); fr(m->zero_rows);
   for (int j = 0; j < SMX_MAX_LABELS; ++j) { fr(m->Y[j]); fr(m->laby_raw[j]); fr(m->laby_draw[j]); }
   fr(m->rows2[0]); fr(m->rows2[1]); fr(m->order); fr(m->sched_tab); fr(m->state3); fr(m->mhist);
   fr(m->resp); fr(m->dklz); fr(m->zmean); fr(m->zpick); fr(m->tril_part); fr(m->ltril);

@@ -179,9 +179,50 @@ __global__ __launch_bounds__(256) void plane_logprob_kernel(StatArgs a) {
   __syncthreads();
   if (threadIdx.x == 0) a.dst[(long)s * a.dst_draw + b] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
+// The same statistics of the 'bernoulli' (logits) and 'normal' (loc | raw scale) outputs, as kernels of their own (the count kernels above
+// stay as they are): Bernoulli mean p = sigmoid(l), variance p (1 - p); normal mean m, variance sigma^2, sigma = softplus(s + softplus^-1(1));
+// log_prob = the sum over the genes of smx_loss.h's bernoulli_elem / normal_elem (no count constant).  count_only changes nothing here.
+__device__ inline void rv_moments(int lk, float p0, float p1, float& mean, float& var) {
+  if (lk == SMX_LLK_BERNOULLI) { const float p = 1.f / (1.f + expf(-p0)); mean = p; var = p * (1.f - p); }
+  else { const float sd = softplus_sigmoid(p1 + SMX_SOFTPLUS_INV_1).sp; mean = p0; var = sd * sd; }
+}
+__global__ __launch_bounds__(256) void plane_stat_rv_kernel(StatArgs a) {
+  const int g = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+  if (g >= a.G) return;
+  const bool two = a.lk == SMX_LLK_NORMAL;
+  float acc = 0.f;
+  for (int s = 0; s < a.Sn; ++s) {   // (draw order: the average over the draws is deterministic)
+    const float* p = a.P + ((long)s * a.B + b) * a.ldp + g;
+    float mean, var;
+    rv_moments(a.lk, p[0], two ? p[a.plane_stride] : 0.f, mean, var);
+    if (a.stat == 2) acc += mean;
+    else a.dst[(long)s * a.dst_draw + (long)b * a.G + g] = a.stat == 0 ? mean : var;
+  }
+  if (a.stat == 2) { float* d = a.dst + (long)b * a.G + g; *d = (a.accumulate ? *d : 0.f) + acc * a.inv_S; }
+}
+__global__ __launch_bounds__(256) void plane_logprob_rv_kernel(StatArgs a) {
+  __shared__ float sh[4];
+  const int row = blockIdx.x, b = row % a.B, s = row / a.B;
+  const float* p = a.P + (long)row * a.ldp;
+  const long trow = a.trows ? a.trows[b] : b;
+  const bool two = a.lk == SMX_LLK_NORMAL;
+  float acc = 0.f;
+  for (int g = threadIdx.x; g < a.G; g += 256) {
+    const float x = a.t_u16 ? (float)reinterpret_cast<const uint16_t*>(a.T)[trow * a.ldt + g] : a.T[trow * a.ldt + g];
+    float v, d0, d1;
+    if (two) normal_elem(x, p[g], p[a.plane_stride + g], v, d0, d1);
+    else bernoulli_elem(x, p[g], v, d0);
+    acc += v;
+  }
+  acc = wave_sum(acc);   // the four waves' sums meet in LDS, added in wave order
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) a.dst[(long)s * a.dst_draw + b] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
 static int launch_plane_stat(hipStream_t st, const StatArgs& a) {
-  if (a.stat == 3) hipLaunchKernelGGL(plane_logprob_kernel, dim3((unsigned)(a.Sn * a.B)), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(plane_stat_kernel, dim3((unsigned)((a.G + 255) / 256), (unsigned)a.B), dim3(256), 0, st, a);
+  const bool rv = a.lk == SMX_LLK_BERNOULLI || a.lk == SMX_LLK_NORMAL;
+  if (a.stat == 3) hipLaunchKernelGGL(rv ? plane_logprob_rv_kernel : plane_logprob_kernel, dim3((unsigned)(a.Sn * a.B)), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(rv ? plane_stat_rv_kernel : plane_stat_kernel, dim3((unsigned)((a.G + 255) / 256), (unsigned)a.B), dim3(256), 0, st, a);
   SMX_HIP(hipGetLastError());
   return SMX_OK;
 }

@@ -807,6 +807,7 @@ int launch_score_head(hipStream_t st, const ScoreHeadArgs& a_in) {
     case SMX_LLK_ZINB: return launch_score_head_lk<SMX_LLK_ZINB>(st, a, grid, walk);
     case SMX_LLK_NBD: return launch_score_head_lk<SMX_LLK_NBD>(st, a, grid, walk);
     case SMX_LLK_ZINBD: return launch_score_head_lk<SMX_LLK_ZINBD>(st, a, grid, walk);
+    case SMX_LLK_NORMAL: return launch_score_head_lk<SMX_LLK_NORMAL>(st, a, grid, walk);   // (2-plane images, like 'nb')
     default: set_error("score_head: unknown likelihood"); return SMX_ERR_INVALID;
   }
 }

@@ -177,9 +177,19 @@ static int stacked_scores(smx_model* m, const Pass& ps, int n_samples, const Sco
   return SMX_OK;
 }
 
+// the row constants the scores subtract: sum_g lgamma(x + 1) of the count posteriors; zeros for 'bernoulli' / 'normal', whose rows may hold
+// values (negative, fractional) for which row_stats' constant is not even finite
+static void row_consts(const smx_model* m, const float** lgx1, const int32_t** rows) {
+  if (llk_has_count_const(m->cfg.likelihood)) return;
+  *lgx1 = m->zero_rows; *rows = nullptr;
+}
+// the stacked form: two- and three-plane heads (score_head / out_head_loss); the one-plane 'bernoulli' output scores draw by draw (count_loss)
+static bool stacked_scores_ok(const smx_model* m) { return stacked_scoring_ok(m) && m->k >= 2; }
+
 static int marginal_llk_stacked(smx_model* m, const Pass& ps, int n_samples, float* run) {
   ScoreJob q;
   q.X = ps.Xsrc; q.x_u16 = ps.x_u16; q.xrows = ps.xrows; q.lgx1 = ps.lgx1; q.lgrows = ps.rows; q.likelihood = m->cfg.likelihood;
+  row_consts(m, &q.lgx1, &q.lgrows);
   q.with_lw = 1; q.run_max = run; q.run_sum = run + ps.B; q.llk_sum = run + 2 * ps.B;
   return stacked_scores(m, ps, n_samples, &q, 1);
 }
@@ -213,7 +223,7 @@ static int land_scores(smx_model* m, int rc, const float* run, size_t floats, co
 
 // smx_marginal_llk(_csr) after the batch's pass is set up
 static int marginal_llk_run(smx_model* m, Pass& ps, int32_t batch, int32_t n_samples, float* mllk, float* llk_mean) {
-  const bool stacked = stacked_scoring_ok(m);
+  const bool stacked = stacked_scores_ok(m);
   // a deterministic latent (DCA) decodes to the same parameters in every draw: one pass is the whole estimate
   if (!m->stochastic) n_samples = 1;
   // [3][B]: running max, running sum, sum of log p(x|z) (scratch kept across calls: hipMalloc + hipFree per call cost more than the stacked pass)
@@ -227,6 +237,7 @@ static int marginal_llk_run(smx_model* m, Pass& ps, int32_t batch, int32_t n_sam
     if (rc != SMX_OK) break;
     IwArgs a{};
     a.lgx1 = ps.lgx1; a.rows = ps.rows;
+    row_consts(m, &a.lgx1, &a.rows);
     a.z = m->z; a.sig = m->sig; a.eps = m->eps; a.stochastic = m->stochastic;
     a.l = m->scvi ? m->lsmp : nullptr; a.lsig = m->lsig; a.leps = m->leps; a.library = ps.lib;
     a.run_max = run; a.run_sum = run + batch; a.llk_sum = run + 2 * batch; a.first = (s == 0);
@@ -293,10 +304,10 @@ int smx_score_llk(smx_model* m, const int32_t* row_ids, const float* host_x, con
                          (size_t)m->G * sizeof(float), (size_t)batch, hipMemcpyHostToDevice, m->st);
     // sum lgamma(x + 1) per cell of the target, on the device (the kernel the resident matrix's constants come from;
     // on the host it was ~0.5 ms of lgamma() calls per call)
-    if (e == hipSuccess) rc = launch_row_stats(m->st, tX + plane * t, 0, m->Gp, batch, m->G, tLg + (size_t)batch * t, nullptr);
+    if (e == hipSuccess && llk_has_count_const(lk)) rc = launch_row_stats(m->st, tX + plane * t, 0, m->Gp, batch, m->G, tLg + (size_t)batch * t, nullptr);
   }
   if (e != hipSuccess) { set_error(std::string("score_llk upload failed: ") + hipGetErrorString(e)); rc = SMX_ERR_HIP; }
-  const bool stacked = stacked_scoring_ok(m);
+  const bool stacked = stacked_scores_ok(m);
   if (stacked && rc == SMX_OK) {
     // all draws as rows of one decoder pass; one likelihood-only head launch per (target, distribution)
     ScoreJob jobs[8];
@@ -308,6 +319,7 @@ int smx_score_llk(smx_model* m, const int32_t* row_ids, const float* host_x, con
         q.likelihood = (j == 0) ? lk : (lk == SMX_LLK_ZINB ? SMX_LLK_NB : SMX_LLK_NBD);
         q.X = own ? ps.Xsrc : tX + plane * t; q.x_u16 = own ? ps.x_u16 : 0; q.xrows = own ? ps.xrows : nullptr;
         q.lgx1 = own ? ps.lgx1 : tLg + (size_t)batch * t; q.lgrows = own ? ps.rows : nullptr;
+        row_consts(m, &q.lgx1, &q.lgrows);
         float* r = run + ((size_t)t * 2 + j) * 2 * batch;
         q.with_lw = 0; q.run_max = r; q.run_sum = r + batch; q.llk_sum = nullptr;
       }
@@ -322,6 +334,7 @@ int smx_score_llk(smx_model* m, const int32_t* row_ids, const float* host_x, con
       for (int j = 0; j < n_dist && rc == SMX_OK; ++j) {
         IwArgs a{};   // (no latent terms: the draws' likelihoods alone)
         a.lgx1 = own ? ps.lgx1 : tLg + (size_t)batch * t; a.rows = own ? ps.rows : nullptr;
+        row_consts(m, &a.lgx1, &a.rows);
         float* r = run + ((size_t)t * 2 + j) * 2 * batch;
         a.run_max = r; a.run_sum = r + batch; a.first = (s == 0);
         // j == 1: the count distribution under the zero-inflation wrapper (first two planes, no gate)

@@ -927,7 +927,7 @@ int forward_pass(smx_model* m, const Pass& ps, bool with_loss, bool backward, in
   if (m->fvae) SMX_CHECK(factor_forward(m, ps, backward));
   MetricsArgs me;
   me.llk_part = m->llk_part; me.n_chunks = n_llk_chunks; me.rows = ps.rows;
-  me.lgx1 = c.likelihood == SMX_LLK_MSE ? nullptr : ps.lgx1;   // (the count likelihoods' data-only constant sum_g lgamma(x + 1))
+  me.lgx1 = llk_has_count_const(c.likelihood) ? ps.lgx1 : nullptr;   // (the count likelihoods' data-only constant sum_g lgamma(x + 1); not 'mse' / 'bernoulli' / 'normal')
   me.llk_y = c.n_labels > m->n_observed ? m->llk_y : nullptr;
   me.llk_o = m->n_observed ? m->llk_o : nullptr;
   if (m->fvae) { me.tc = m->tc_cell; me.dl = m->dl_cell; me.gamma = c.gamma; }

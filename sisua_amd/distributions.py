@@ -554,9 +554,15 @@ def concat_distributions(dists: Sequence[Distribution], axis: int = 0, name: Opt
 def count_distribution(likelihood: str, planes, name: str, activated: bool) -> Distribution:
   """Build the output distribution from the parameter planes of smx_forward.
   nb/zinb planes: (log total_count, logits[, gate]); nbd/zinbd: pre-activation
-  (softplus mean, softplus1 dispersion) unless `activated` (scvi feeds mean/disp)."""
+  (softplus mean, softplus1 dispersion) unless `activated` (scvi feeds mean/disp);
+  bernoulli: logits; normal / gaussian / diag: (loc, softplus1 scale)."""
   if likelihood == "mse":   # one plane: the mean (RVmeta(dim, 'mse'): deterministic output)
     return VectorDeterministic(planes[0], name=name)
+  if likelihood == "bernoulli":   # one plane: logits (binarised peak matrices)
+    return Independent(Bernoulli(logits=planes[0]), 1, name=name)
+  if likelihood in ("normal", "gaussian", "diag"):   # loc | raw scale, scale = softplus(raw + softplus^-1(1)); 'diag': the reference's own test
+    loc, scale = planes[0], _softplus(np.asarray(planes[1], np.float64) + SOFTPLUS_INV_1)
+    return MultivariateNormalDiag(loc, scale, name=name) if likelihood == "diag" else Independent(Normal(loc, scale), 1, name=name)
   if likelihood in ("nb", "zinb"):
     base = NegativeBinomial(logits=planes[1], name="NegativeBinomial", log_total_count=planes[0])
   else:

@@ -22,7 +22,7 @@ import numpy as np
 
 from sisua_amd import distributions as D
 from sisua_amd import interpolation, optimizers
-from sisua_amd.config import TRIL_LATENT_POSTERIORS, ModelConfig, NetConf, RVmeta, init_params
+from sisua_amd.config import OUTPUT_ALIASES, REAL_OUTPUTS, TRIL_LATENT_POSTERIORS, ModelConfig, NetConf, RVmeta, init_params
 from sisua_amd.data import BatchDataset, SingleCellOMIC, as_csr, is_sparse, library_matrix
 from sisua_amd.engine import Engine
 
@@ -147,9 +147,9 @@ class SingleCellModel:
                       name=name, **kwargs)
     self.init_args = frame_args
     outs = [o.copy() for o in _flatten(outputs)]
-    if not outs or outs[0].posterior not in ("nb", "zinb", "nbd", "zinbd", "mse"):
-      raise ValueError("the first output must be a count distribution ('nb', 'zinb', 'nbd', 'zinbd') or the deterministic 'mse', "
-                       f"given: {outs[0].posterior if outs else None}")
+    if not outs or outs[0].posterior not in ("nb", "zinb", "nbd", "zinbd", "mse", "bernoulli", "normal", "gaussian", "diag"):
+      raise ValueError("the first output must be a count distribution ('nb', 'zinb', 'nbd', 'zinbd'), 'bernoulli', 'normal' / 'gaussian' / "
+                       f"'diag' or the deterministic 'mse', given: {outs[0].posterior if outs else None}")
     self._outputs = outs
     self._labels = [l.copy() for l in _flatten(kwargs.pop("labels", None))]
     self._latents = [l.copy() for l in _flatten(latents)]
@@ -188,7 +188,8 @@ class SingleCellModel:
       raise ValueError("at most 4 heads (outputs[1:] + label variables) are built")
     encl = self._encoder[1].units if len(self._encoder) > 1 else (64,)
     encl_act = self._encoder[1].activation if len(self._encoder) > 1 else "relu"
-    return ModelConfig(model=self._kind, n_genes=self._outputs[0].event_shape, likelihood=self._outputs[0].posterior,
+    llk = OUTPUT_ALIASES.get(self._outputs[0].posterior, self._outputs[0].posterior)   # ('gaussian' / 'diag' -> 'normal'; the RVmeta keeps its name)
+    return ModelConfig(model=self._kind, n_genes=self._outputs[0].event_shape, likelihood=llk,
                        enc_units=tuple(enc.units), dec_units=tuple(self._decoder.units),
                        latent_dim=self._latents[0].event_shape, encl_units=tuple(encl), labels=tuple(labels),
                        batchnorm=bool(enc.batchnorm), dropout_enc=float(enc.dropout), dropout_dec=float(self._decoder.dropout),
@@ -200,6 +201,15 @@ class SingleCellModel:
                        n_components=int(getattr(self, "_n_components", 10)), covariance=str(getattr(self, "_covariance", "none")), latent_mixture=bool(getattr(self, "_latent_mixture", False)),
                        latent_tril=self._latents[0].posterior in TRIL_LATENT_POSTERIORS,
                        **getattr(self, "_ties", {}), **getattr(self, "_disc_cfg", {}))
+
+  def _check_inputs(self, x):
+    """A 'normal' output with log_norm=True: the encoder's log1p is undefined at x <= -1 (ValueError before any device work)."""
+    if self._log_norm and OUTPUT_ALIASES.get(self._outputs[0].posterior, self._outputs[0].posterior) == "normal" and x is not None:
+      v = x.data if is_sparse(x) else np.asarray(x)
+      if v.size and float(np.min(v)) <= -1.0:
+        raise ValueError(f"{type(self).__name__}: log_norm=True takes log1p of the inputs, undefined at x <= -1 (min {float(np.min(v))}); "
+                         "pass log_norm=False for real-valued inputs of that range")
+    return x
 
   def _ensure_engine(self, max_batch: int) -> Engine:
     cfg = self._make_config()
@@ -392,6 +402,9 @@ class SingleCellModel:
     self._lr_sched = learning_rate
     self._opt = dict(lr=float(learning_rate.value(0)), clipnorm=float(clipnorm or 0.0))
     n_lab = len(self._outputs) - 1 + len(self._labels)   # target arrays beside the counts: outputs[1:], then the label variables
+    self._check_inputs(train.arrays[0])
+    if valid is not None:
+      self._check_inputs(valid.arrays[0])
     if len(train.arrays) < 1 + n_lab:
       raise ValueError(f"{type(self).__name__} needs {1 + n_lab} omics per batch, the dataset has {len(train.arrays)}")
     cp = None
@@ -640,7 +653,9 @@ class SingleCellModel:
     else:
       stack = (lambda a: a[0]) if len(yp_list if heads_only else xp_list) == 1 else (lambda a: np.stack(a, 0))
       planes = None if heads_only else [stack([xp[c] for xp in xp_list]) for c in range(cfg.k)]
-    outs = [] if heads_only else [D.count_distribution(cfg.likelihood, planes, self._outputs[0].name or "transcriptomic", activated=cfg.model == "scvi")]
+    # ('bernoulli' / 'normal' outputs: by the RVmeta's own name -- 'diag' is a MultivariateNormalDiag, 'normal' / 'gaussian' an Independent Normal)
+    kind0 = self._outputs[0].posterior if cfg.likelihood in REAL_OUTPUTS else cfg.likelihood
+    outs = [] if heads_only else [D.count_distribution(kind0, planes, self._outputs[0].name or "transcriptomic", activated=cfg.model == "scvi")]
     n_extra = len(cfg.extra_outputs)
     for j, (P, kind) in enumerate(cfg.head_labels):
       raw = yp_list[j] if stacked else stack([yp[j] for yp in yp_list])
@@ -698,7 +713,7 @@ class SingleCellModel:
 
   def __call__(self, inputs=None, library=None, mask=None, training=None, sample_shape=(), **kwargs):
     arrs = _flatten(inputs)
-    x = _rows(arrs[0])
+    x = self._check_inputs(_rows(arrs[0]))
     if self._cfg.model == "scvi" and library is None:
       library = library_matrix(x)
     n = int(np.prod(sample_shape)) if np.size(sample_shape) else 0
@@ -717,7 +732,7 @@ class SingleCellModel:
     r"""log1p + encoder network + latent posterior (single_cell_model.py:119-139); SCVI
     returns [q(z|x), q(l|x)] (scvi.py:88-106)."""
     arrs = _flatten(inputs)[:self._n_inputs]
-    x = _rows(arrs[0])
+    x = self._check_inputs(_rows(arrs[0]))
     if self._cfg.model == "scvi" and library is None:
       library = library_matrix(x)
     e = self._ensure_engine(x.shape[0])
@@ -792,6 +807,7 @@ class SingleCellModel:
     return Xc, Zc
 
   def _predict_all(self, x, library, sample_shape, batch_size, lazy=False):
+    self._check_inputs(x)
     n = int(np.prod(sample_shape)) if np.size(sample_shape) else 0
     # (room for super-batches: the library decodes several minibatches per pass when its max_batch allows, same numbers)
     e = self._ensure_engine(max(min(int(batch_size), x.shape[0]), 512 if x.shape[0] >= 1024 else 1))
@@ -819,7 +835,7 @@ class SingleCellModel:
     arrs = _flatten(inputs)
     if len(self._outputs) > 1:
       return self._joint_marginal_log_prob(arrs, library, sample_shape, batch_size)
-    x = _rows(arrs[0])
+    x = self._check_inputs(_rows(arrs[0]))
     S = int(np.prod(sample_shape)) if np.size(sample_shape) else 1
     if self._cfg.model == "scvi" and library is None:
       library = library_matrix(x)
@@ -848,7 +864,7 @@ class SingleCellModel:
                                 "built: the joint estimate needs the per-draw log q_mix(z | x) from the device")
     if len(arrs) < n_out:
       raise ValueError(f"marginal_log_prob of this model needs the {n_out} output variables' arrays as inputs=[x, y, ...]")
-    x = _rows(arrs[0])
+    x = self._check_inputs(_rows(arrs[0]))
     ys = [np.ascontiguousarray(a.toarray() if is_sparse(a) else a, dtype=np.float32) for a in arrs[1:n_out]]
     S = int(np.prod(sample_shape)) if np.size(sample_shape) else 1
     if cfg.model == "scvi" and library is None:
@@ -1192,6 +1208,8 @@ class SCVI(SingleCellModel):
                clip_library=1e3,
                **kwargs):
     outs = _flatten(outputs)
+    if outs and outs[0].posterior in ("bernoulli", "normal", "gaussian", "diag"):   # (its softmax-rate head is a count model)
+      raise ValueError(f"SCVI: the first output is a count distribution ('zinbd' or 'nbd'), given: {outs[0].posterior!r}")
     assert outs[0].posterior in ("zinbd", "nbd"), \
       "scVI only support transcriptomic distribution: 'zinbd' or 'nbd', " + "but given: %s" % str(outs)
     # scvi.py:55-56,66-86: 'full' = a Dense head per plane; otherwise NO head and the distribution layer keeps its own variable --
