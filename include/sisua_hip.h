@@ -395,6 +395,22 @@ int smx_predict_stat_csr(smx_model* m, const int64_t* indptr, const int32_t* col
                          int64_t n_cells, int32_t batch, int32_t n_samples, int32_t stat, int32_t count_only, const float* target,
                          const int64_t* t_indptr, const int32_t* t_cols, const float* t_vals, float* out);
 
+/* POSTERIOR-PREDICTIVE SAMPLES of the gene output, drawn on the device from the parameter planes of the same walk (its stat 4; the passes
+ * of a chunk run once): out [n_k, n_samples, n_cells, n_genes] float32, n_k independent draws x ~ p(x | planes) per Monte-Carlo draw, cell
+ * and gene -- `y.sample(n_k)` of predict()'s result.
+ *   nb / zinb: Poisson(Gamma(shape = exp(p0), scale = exp(p1))); nbd / zinbd: Poisson(Gamma(shape = theta, scale = mean / theta));
+ *   zero-inflated: kept with probability 1 - sigmoid(p2), else 0 (count_only != 0: the count distribution, no gate);
+ *   bernoulli: u < sigmoid(p0); normal: loc + softplus(raw + softplus^-1(1)) n; mse: the location itself.
+ * Counter-based: a draw is a function of (seed, sample k, draw s, row of the input, gene) alone -- philox4x32_10 under the key `seed` with
+ * the counter (gene, row, k, 96 | attempt << 8 | s << 16) -- so the batch size, the chunking and dense / CSR input change no bit.  Every
+ * rejection loop is bounded (16 Gamma attempts, 24 Poisson attempts, then the proposal's mean / the rounded rate).  Count outputs are
+ * non-negative integers in float32; a NaN parameter, or a Gamma-Poisson rate that is not finite, gives NaN.  n_cells < 2^32,
+ * n_samples <= 65536.  smx_predict_sample_csr: the rows as CSR (layout of smx_predict_csr), same bits. */
+int smx_predict_sample(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
+                       int32_t count_only, uint64_t seed, int32_t n_k, float* out);
+int smx_predict_sample_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                           int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, uint64_t seed, int32_t n_k, float* out);
+
 /* Decoder only (SingleCellModel.decode, single_cell_model.py:141-151; scvi.py:108-171):
  * z [batch,D] (and l [batch] for scvi) -> the same x_params / y_params as smx_forward,
  * eval mode. */
@@ -598,6 +614,11 @@ int smx_k_hiprand(uint64_t seed, int32_t n, const uint32_t* counters, uint32_t* 
 /* Philox words / dropout multipliers / normals exactly as the kernels draw them. */
 int smx_k_noise(uint64_t seed, int32_t stream, int32_t step, int32_t sample, const int64_t* cell_ids, int32_t B,
                 int32_t width, float dropout_p, float* dropout_mult, float* normal);
+/* The predictive sampler by itself on caller-given planes [k][rows][G] (host; k planes of `likelihood`, direct / count_only as
+ * smx_k_count_llk / smx_predict_sample): out [n_k][rows][G], the draws of rows 0 .. rows - 1 of a call with one Monte-Carlo draw
+ * (s = 0) under `seed`.  rows <= 65535. */
+int smx_k_plane_sample(int likelihood, int direct, int count_only, const float* planes, int32_t rows, int32_t G, uint64_t seed,
+                       int32_t n_k, float* out);
 
 #ifdef __cplusplus
 }

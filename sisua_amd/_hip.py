@@ -120,6 +120,8 @@ SIGNATURES = {
                                   C.POINTER(_FP)]),
     "smx_predict_stat_csr": (C.c_int, [_VP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP,
                                        _LP, _IP, _FP, _FP]),
+    "smx_predict_sample": (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _FP]),
+    "smx_predict_sample_csr": (C.c_int, [_VP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _FP]),
     "smx_decode": (C.c_int, [_VP, _FP, _FP, C.c_int32, _FP, C.POINTER(_FP)]),
     "smx_dataset_library": (C.c_int, [_VP, _FP]),
     "smx_dataset_corrupt": (C.c_int, [_VP, C.c_double, C.c_double, C.c_uint64, C.POINTER(C.c_int64)]),
@@ -162,6 +164,7 @@ SIGNATURES = {
     "smx_k_hiprand": (C.c_int, [C.c_uint64, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "smx_k_noise": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_int32,
                               C.c_float, _FP, _FP]),
+    "smx_k_plane_sample": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _FP]),
 }
 
 _lib = None

@@ -755,4 +755,16 @@ int launch_library_stats(hipStream_t st, const double* logcount, long N, double*
 int launch_corrupt_hist(hipStream_t st, const CorruptArgs& a, int pass);
 int launch_corrupt_apply(hipStream_t st, const CorruptArgs& a);
 
+// ---- posterior-predictive draws of the gene output (smx_sample.hip): one x ~ p(x | planes) per (sample k, draw s, cell, gene) -------
+enum { ST_PREDICTIVE = 96 };   // Philox stream of the predictive sampler (counter layout: smx_sample.hip)
+struct SampleArgs {
+  const float* P = nullptr; long ldp = 0; long plane_stride = 0;   // planes of Sn * B stacked rows (row s * B + b = draw s of cell b): StatArgs' view
+  int B = 0, Sn = 0, G = 0, lk = 0, direct = 0, count_only = 0;
+  int n_k = 1;                        // samples per (draw, cell, gene)
+  uint32_t k0 = 0, k1 = 0;            // the call's seed (Philox key)
+  uint32_t row0 = 0, s0 = 0;          // row of the call's input of cell b = 0; draw index of stacked draw s = 0
+  float* dst = nullptr; long dst_k = 0, dst_draw = 0;   // dst[k * dst_k + s * dst_draw + b * G + g]
+};
+int launch_plane_sample(hipStream_t st, const SampleArgs& a);
+
 }  // namespace smx

@@ -227,7 +227,11 @@ static int launch_plane_stat(hipStream_t st, const StatArgs& a) {
   return SMX_OK;
 }
 // what smx_predict_stat asks of the batch loop below in place of the parameter planes
-struct StatReq { int stat = 0, count_only = 0; const float* target = nullptr; const CsrRows* tcsr = nullptr; float* out = nullptr; };
+// (stat 4: n_k predictive samples per draw under `seed`, smx_sample.hip)
+struct StatReq {
+  int stat = 0, count_only = 0; const float* target = nullptr; const CsrRows* tcsr = nullptr; float* out = nullptr;
+  uint64_t seed = 0; int n_k = 1;
+};
 
 // ---- host rows given as CSR (smx_predict_csr and kin): (indptr int64 [n + 1], cols int32, vals float32), indptr absolute ----
 // what the C entry points check before any device work: offsets that never go back, at most G entries per row (so a batch of rows
@@ -322,6 +326,7 @@ bool stacked_scoring_ok(const smx_model* m) {
 // array for the chunk's Cn cells (NULL: not asked for)
 struct PredChunk {
   size_t Cn = 0, S = 0;   // cells of the chunk, draws per cell
+  size_t c0 = 0;          // the chunk's first cell: its row of the call's input
   const StatReq* sr = nullptr;
   char* csr = nullptr;    // CSR input: the chunk's indptr slice | cols | vals (csr_stage_bytes)
   float *in_raw = nullptr, *in_x = nullptr, *in_lib = nullptr, *in_lgx1 = nullptr;   // input: raw rows [Cn][G] (dense), the tile [Cn][Gp], library prior, constants
@@ -364,6 +369,14 @@ static int load_chunk(smx_model* m, PredChunk& c, const float* host_x, const Csr
 static int stat_of(smx_model* m, const PredChunk& c, const Pass& ps, const float* P, long ldp, int Sn, size_t s0, size_t b0) {
   const StatReq& sr = *c.sr;
   const size_t G = (size_t)m->G, Cn = c.Cn;
+  if (sr.stat == 4) {   // predictive samples: the chunk's staging is [n_k][S][Cn][G]
+    SampleArgs q;
+    q.P = P; q.ldp = ldp; q.plane_stride = m->Gp; q.B = ps.B; q.Sn = Sn; q.G = m->G; q.lk = m->cfg.likelihood; q.direct = m->scvi ? 1 : 0;
+    q.count_only = sr.count_only; q.n_k = sr.n_k; q.k0 = (uint32_t)(sr.seed & 0xFFFFFFFFu); q.k1 = (uint32_t)(sr.seed >> 32);
+    q.row0 = (uint32_t)(c.c0 + b0); q.s0 = (uint32_t)s0;
+    q.dst = c.st + (s0 * Cn + b0) * G; q.dst_k = (long)(c.S * Cn * G); q.dst_draw = (long)(Cn * G);
+    return launch_plane_sample(m->st, q);
+  }
   StatArgs a;
   a.P = P; a.ldp = ldp; a.plane_stride = m->Gp; a.B = ps.B; a.Sn = Sn; a.G = m->G; a.lk = m->cfg.likelihood; a.direct = m->scvi ? 1 : 0;
   a.count_only = sr.count_only; a.stat = sr.stat; a.inv_S = 1.f / (float)c.S; a.accumulate = s0 > 0 ? 1 : 0;
@@ -528,7 +541,8 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
   for (int j = 0; j < m->n_heads; ++j)
     if (y_params && y_params[j]) ch.wy[j] = (size_t)m->lab_ky[j] * (size_t)m->cfg.label_dim[j];
   // the requested statistic of the gene output, per cell: S G (mean / variance per draw), G (mean over the draws), S (log_prob)
-  const size_t w_stat = !sr ? 0 : sr->stat == 2 ? G : sr->stat == 3 ? S : S * G;
+  // (predictive samples: n_k S G)
+  const size_t w_stat = !sr ? 0 : sr->stat == 2 ? G : sr->stat == 3 ? S : sr->stat == 4 ? (size_t)sr->n_k * S * G : S * G;
   // ---- the staging of a chunk of C cells, segment by segment in this order: (where, floats per cell, asked for).  Input rows: see
   // load_chunk; CSR rows have no raw [C][G] segment, their tile comes right after the CSR region (16-byte aligned for launch_csr_rows'
   // float4 stores) ----
@@ -587,6 +601,7 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
   };
   for (size_t c0 = 0; c0 < N; c0 += ch.Cn) {
     ch.Cn = std::min(C, N - c0);   // cells of this chunk (CSR rows: load_chunk may take fewer)
+    ch.c0 = c0;
     SMX_CHECK(load_chunk(m, ch, host_x, cx, host_library, c0, (size_t)batch, nnz_cap));
     const size_t Cn = ch.Cn;
     for (size_t b0 = 0; b0 < Cn; b0 += step) {
@@ -606,7 +621,9 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
     if (ch.lm) SMX_CHECK(out(l_mean + c0, ch.lm, Cn));
     if (ch.ls) SMX_CHECK(out(l_scale + c0, ch.ls, Cn));
     if (ch.st && sr->stat == 2) SMX_CHECK(out(sr->out + c0 * G, ch.st, Cn * G));
-    for (size_t s = 0; s < S && ch.st && sr->stat != 2; ++s) {
+    for (size_t s = 0; s < S && ch.st && sr->stat == 4; ++s)
+      for (size_t q = 0; q < (size_t)sr->n_k; ++q) SMX_CHECK(out(sr->out + ((q * S + s) * N + c0) * G, ch.st + (q * S + s) * Cn * G, Cn * G));
+    for (size_t s = 0; s < S && ch.st && sr->stat != 2 && sr->stat != 4; ++s) {
       if (sr->stat == 3) SMX_CHECK(out(sr->out + s * N + c0, ch.st + s * Cn, Cn));
       else SMX_CHECK(out(sr->out + (s * N + c0) * G, ch.st + s * Cn * G, Cn * G));
     }
@@ -659,6 +676,29 @@ int smx_predict_stat_csr(smx_model* m, const int64_t* indptr, const int32_t* col
   StatReq sr;
   sr.stat = stat; sr.count_only = count_only ? 1 : 0; sr.target = target; sr.tcsr = t_indptr ? &tc : nullptr; sr.out = out;
   return predict_core(m, nullptr, in, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr);
+}
+
+// stat 4 of the walk: n_k samples of the gene output per draw and cell, out [n_k, n_samples, n_cells, n_genes]
+static int predict_sample(smx_model* m, const float* host_x, const CsrRows* cx, const float* host_library, int64_t n_cells, int32_t batch,
+                          int32_t n_samples, int32_t count_only, uint64_t seed, int32_t n_k, float* out) {
+  SMX_REQUIRE(m && out && n_k > 0, "bad arguments");
+  SMX_REQUIRE(!(count_only && m->cfg.likelihood == SMX_LLK_MSE), "the deterministic 'mse' output has no count distribution");
+  SMX_REQUIRE(n_cells <= (int64_t)0xFFFFFFFFll && n_samples <= 65536, "the sampler's counters hold 2^32 cells and 2^16 draws");
+  StatReq sr;
+  sr.stat = 4; sr.count_only = count_only ? 1 : 0; sr.out = out; sr.seed = seed; sr.n_k = n_k;
+  return predict_core(m, host_x, cx, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr);
+}
+
+int smx_predict_sample(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
+                       int32_t count_only, uint64_t seed, int32_t n_k, float* out) {
+  return predict_sample(m, host_x, nullptr, host_library, n_cells, batch, n_samples, count_only, seed, n_k, out);
+}
+
+int smx_predict_sample_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                           int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, uint64_t seed, int32_t n_k, float* out) {
+  SMX_REQUIRE(indptr, "null indptr");
+  const CsrRows cx{indptr, cols, vals};
+  return predict_sample(m, nullptr, &cx, host_library, n_cells, batch, n_samples, count_only, seed, n_k, out);
 }
 
 int smx_decode(smx_model* m, const float* z, const float* l, int32_t batch, float* x_params, float* const* y_params) {

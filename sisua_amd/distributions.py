@@ -662,8 +662,24 @@ class LazyCountOutput(Distribution):
       self._engine()   # (raises if the model moved on)
     return self._eager
 
-  def sample(self, sample_shape=(), seed=None):
-    return self.materialize().sample(sample_shape, seed=seed)
+  def sample(self, sample_shape=(), seed=None, out=None):
+    """Posterior-predictive draws on the device (smx_predict_sample): float32 of shape sample_shape + batch_shape + event_shape, as the
+    eager distributions return it -- `sample()` of S latent draws is [S, N, G], `sample(3)` [3, S, N, G], `sample((2, 3))` [2, 3, S, N, G];
+    on `.count_distribution`: without the zero-inflation gate.  An integer seed gives the same bits every time, at any batch size and
+    from a dense or a sparse input; seed=None takes fresh entropy.  `out`: a C-contiguous float32 array of the result's shape."""
+    sshape = self._sshape(sample_shape)
+    n = int(np.prod(sshape, dtype=np.int64)) if sshape else 1
+    shape = sshape + self.batch_shape + self.event_shape
+    if n < 1:
+      raise ValueError("sample_shape must have at least one element")
+    if seed is None:
+      seed = int(np.random.SeedSequence().generate_state(1, np.uint64)[0])
+    if out is not None and (out.dtype != np.float32 or tuple(out.shape) != shape or not out.flags.c_contiguous):
+      raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
+    S, N, G = max(self._S, 1), self._x.shape[0], self.event_shape[0]
+    r = self._engine().predict_stat(self._x, "sample", library=self._lib, n_samples=S, batch=self._B, count_only=self._count_only,
+                                    out=None if out is None else out.reshape(n, S, N, G), seed=seed, n=n)
+    return out if out is not None else r.reshape(shape)
 
   def __getattr__(self, name):
     # anything else a caller of the reference touches on the eager result (`.logits`, `.total_count`, `.inflated_distribution`, ...):

@@ -478,26 +478,36 @@ class Engine:
       check(self.lib.smx_predict(self._h, _fp(xa), _fp(la), N, B, S, *res))
     return _tril_scale(out)
 
-  STATS = {"mean": 0, "variance": 1, "mean_over_samples": 2, "log_prob": 3}
+  STATS = {"mean": 0, "variance": 1, "mean_over_samples": 2, "log_prob": 3, "sample": 4}
 
   def predict_stat(self, x, stat: str, library=None, n_samples: int = 1, batch: Optional[int] = None, count_only: bool = False,
-                   target=None, out=None):
+                   target=None, out=None, seed: int = 0, n: int = 1):
     """A statistic of the gene output over a whole host matrix (smx_predict_stat): the same passes and draws as predict(), but only the
     statistic leaves the device.  'mean' / 'variance' [n_samples, N, G]; 'mean_over_samples' [N, G]; 'log_prob' [n_samples, N] of `target`
     (default: of x itself).  count_only: the count distribution without the zero-inflation wrapper.  `out`: a float32 array of the
     result's shape to write into (a reused array saves the first-touch page faults of a fresh one).  x and target may be scipy.sparse
-    (smx_predict_stat_csr)."""
+    (smx_predict_stat_csr).  'sample': [n, n_samples, N, G], n posterior-predictive draws of the gene output per Monte-Carlo draw and cell
+    under the integer `seed` (smx_predict_sample / _csr: drawn on the device, the same bits at any batch size and from dense or sparse x)."""
     cfg = self.cfg
     xa = _csr3(x, cfg.n_genes) if _sparse(x) else _f32(x)
     N, S, G = (xa[0].size - 1 if isinstance(xa, tuple) else xa.shape[0]), int(n_samples), cfg.n_genes
     B = min(int(batch or self.max_batch), self.max_batch)
     la = None if library is None else _f32(library, (N, 2))
     code = self.STATS[stat]
-    shape = (N, G) if code == 2 else (S, N) if code == 3 else (S, N, G)
+    shape = (N, G) if code == 2 else (S, N) if code == 3 else (int(n), S, N, G) if code == 4 else (S, N, G)
+    if code == 4 and (int(n) < 1 or target is not None):
+      raise ValueError("'sample' takes n >= 1 and no target")
     if out is None:
       out = np.empty(shape, np.float32)
     elif out.dtype != np.float32 or tuple(out.shape) != shape or not out.flags.c_contiguous:
       raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
+    if code == 4:
+      sd = int(seed) & 0xFFFFFFFFFFFFFFFF
+      if isinstance(xa, tuple):
+        check(self.lib.smx_predict_sample_csr(self._h, *_csr_ptrs(xa), _fp(la), N, B, S, int(bool(count_only)), sd, int(n), _fp(out)))
+      else:
+        check(self.lib.smx_predict_sample(self._h, _fp(xa), _fp(la), N, B, S, int(bool(count_only)), sd, int(n), _fp(out)))
+      return out
     tc = _csr3(target, G, N) if (target is not None and _sparse(target)) else None
     ta = None if (target is None or tc is not None) else _f32(target, (N, G))
     if isinstance(xa, tuple) or tc is not None:
