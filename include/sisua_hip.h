@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 5
+#define SMX_ABI_VERSION 6
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -411,6 +411,34 @@ int smx_predict_sample(smx_model* m, const float* host_x, const float* host_libr
 int smx_predict_sample_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
                            int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, uint64_t seed, int32_t n_k, float* out);
 
+/* Stat 2 (the mean averaged over the draws) for n_sel gene columns only: out [n_cells, n_sel], column j = gene genes[j] (any order,
+ * repeats allowed, each in 0 .. n_genes - 1) -- the same bits as those columns of smx_predict_stat's [n_cells, n_genes]. */
+int smx_predict_stat_cols(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
+                          int32_t count_only, const int32_t* genes, int32_t n_sel, float* out);
+int smx_predict_stat_cols_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                              int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, const int32_t* genes, int32_t n_sel,
+                              float* out);
+
+/* IMPUTATION SCORES (sisua/analysis/imputation_benchmarks.py:102-127) of the matrix smx_predict_stat's stat 2 returns for host_x, the
+ * CORRUPTED counts -- same passes, same draws -- against `original` [n_cells, n_genes], reduced on the device: with
+ * d = |original - mean over the draws|,
+ *   cell_median [n_cells]   np.median(d[i]): 0.5f * (lo + hi) of the row's two middle order statistics, NaN if the row holds a NaN;
+ *   cell_changed [n_cells]  1 where sum(original[i]) != sum(host_x[i]) (both sums in float64: for integer counts with row sums below
+ *                           2^24 this is the reference's float32 np.sum comparison), else 0;
+ *   global_lohi [2]         the order statistics (NG - 1) / 2 and NG / 2 of all NG = n_cells x n_genes entries of d (64-bit ranks);
+ *                           both NaN if any entry is NaN.
+ * Every selection is exact (integer histograms of the float32 patterns; no float atomics): the results do not depend on the batch size,
+ * the chunking or the input form.  The global selection's later levels read d kept on the device when n_cells x n_genes x 4 bytes fit
+ * the knob "impute_keep_bytes" (default: half of the free device memory) and otherwise repeat the walk twice; same answer.
+ * smx_predict_impute_csr: the input rows dense (host_x) or CSR (indptr / cols / vals), the original rows dense (`original`) or CSR
+ * (o_indptr / o_cols / o_vals) -- exactly one of each pair, layout of smx_predict_csr. */
+int smx_predict_impute(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
+                       int32_t count_only, const float* original, float* cell_median, int32_t* cell_changed, float* global_lohi);
+int smx_predict_impute_csr(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals,
+                           const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only,
+                           const float* original, const int64_t* o_indptr, const int32_t* o_cols, const float* o_vals, float* cell_median,
+                           int32_t* cell_changed, float* global_lohi);
+
 /* Decoder only (SingleCellModel.decode, single_cell_model.py:141-151; scvi.py:108-171):
  * z [batch,D] (and l [batch] for scvi) -> the same x_params / y_params as smx_forward,
  * eval mode. */
@@ -619,6 +647,10 @@ int smx_k_noise(uint64_t seed, int32_t stream, int32_t step, int32_t sample, con
  * (s = 0) under `seed`.  rows <= 65535. */
 int smx_k_plane_sample(int likelihood, int direct, int count_only, const float* planes, int32_t rows, int32_t G, uint64_t seed,
                        int32_t n_k, float* out);
+/* The row selection of smx_predict_impute by itself: the two middle order statistics (G - 1) / 2 and G / 2 of each of n_rows rows
+ * [n_rows][ld] (host, ld >= G; what lies beyond G in a row is not read) -> lo, hi [n_rows].  Rows hold non-negative values or NaN (what
+ * an absolute difference is); -0 counts as +0 and a NaN sorts above +inf, as np.partition orders them. */
+int smx_k_row_select(const float* rows, int32_t n_rows, int32_t G, int32_t ld, float* lo, float* hi);
 
 #ifdef __cplusplus
 }

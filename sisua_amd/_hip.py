@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsisua_hip.so")
 
-SMX_ABI_VERSION = 5
+SMX_ABI_VERSION = 6
 SMX_MAX_LAYERS = 8
 SMX_MAX_LABELS = 4
 
@@ -122,6 +122,11 @@ SIGNATURES = {
                                        _LP, _IP, _FP, _FP]),
     "smx_predict_sample": (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _FP]),
     "smx_predict_sample_csr": (C.c_int, [_VP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _FP]),
+    "smx_predict_stat_cols": (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _IP, C.c_int32, _FP]),
+    "smx_predict_stat_cols_csr": (C.c_int, [_VP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _IP, C.c_int32, _FP]),
+    "smx_predict_impute": (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _IP, _FP]),
+    "smx_predict_impute_csr": (C.c_int, [_VP, _FP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _LP, _IP, _FP,
+                                         _FP, _IP, _FP]),
     "smx_decode": (C.c_int, [_VP, _FP, _FP, C.c_int32, _FP, C.POINTER(_FP)]),
     "smx_dataset_library": (C.c_int, [_VP, _FP]),
     "smx_dataset_corrupt": (C.c_int, [_VP, C.c_double, C.c_double, C.c_uint64, C.POINTER(C.c_int64)]),
@@ -165,6 +170,7 @@ SIGNATURES = {
     "smx_k_noise": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_int32,
                               C.c_float, _FP, _FP]),
     "smx_k_plane_sample": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _FP]),
+    "smx_k_row_select": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]),
 }
 
 _lib = None

@@ -246,6 +246,9 @@ struct smx_model {
   int32_t* pred_ids = nullptr; int pred_ids_batch = 0;   // smx_predict super-batches: noise ids (row % batch)
   char* csr_host = nullptr; size_t csr_host_bytes = 0;   // a batch of host rows given as CSR, staged (smx_marginal_llk_csr, CSR log_prob targets)
   float* pred_target = nullptr; size_t pred_target_floats = 0;   // smx_predict_stat(log_prob): a batch of target rows [Bmax][Gp]
+  float* imp_d = nullptr; size_t imp_d_floats = 0;   // smx_predict_impute: |original - mean| of every cell [N][G] (kept form) or of one pass's rows
+  unsigned long long* imp_hist = nullptr;            // ... its histograms: level 1 [2048] | levels 2 and 3 [2][1024] | NaN flag (smx_impute.hip)
+  int32_t* pred_sel = nullptr; size_t pred_sel_n = 0;   // smx_predict_stat_cols: the gene indices on the device
   float* metrics_pin = nullptr;   // pinned landing area of read_metrics: 8 ELBO scalars + one gradient norm per tensor
   float* score_pin = nullptr; size_t score_pin_floats = 0;   // pinned landing area of the scoring entry points' results (smx_scoring.hip: score_landing)
   float* mhist = nullptr; size_t mhist_cap = 0; int32_t mhist_steps = 0;   // ELBO scalars of every step of the last train_steps call
@@ -429,5 +432,22 @@ int setup_pass(smx_model* m, Pass& ps, const int32_t* row_ids, const float* host
 bool stacked_scoring_ok(const smx_model* m);
 bool head_fused_ok(const smx_model* m, int B);   // a training step of B cells takes the one-launch output head (smx_step.hip)
 int stacked_decoder(smx_model* m, const float* z, long rows, float* const* hb, int last_form, float* ht, const float** out, int* out_ld);
+// smx_impute.hip: the selection kernels of the imputation scores (header there)
+#define SMX_IMP_L1_BINS 2048   // level 1 of the global selection: bits 30..20 of the pattern
+#define SMX_IMP_LN_BINS 1024   // levels 2 and 3: bits 19..10, bits 9..0
+#define SMX_IMP_HIST_WORDS (SMX_IMP_L1_BINS + 2 * SMX_IMP_LN_BINS + 1)   // ... and the NaN flag, as one array of 64-bit words
+struct ImputeRowArgs {
+  const float* mean; long ldm;   // the rows' mean over the draws [rows][ldm]
+  const float* orig; long ldo;   // the original rows, the corrupted (input) rows
+  const float* cor; long ldc;
+  int G, d_only;                 // d_only: write d and nothing else (a repeated walk)
+  float* d;                      // |orig - mean| [rows][G] (NULL: not kept)
+  float* median; int32_t* changed;   // [rows]
+  unsigned long long* hist;      // SMX_IMP_HIST_WORDS (level 1 and the NaN flag are written here)
+};
+int launch_impute_rows(hipStream_t st, const ImputeRowArgs& a, int rows);
+// the histogram of bits shift .. shift + 9 of the n patterns of d whose bits under `mask` are prefix[t], t = 0, 1 -> hist [2][1024] (added)
+int launch_impute_level(hipStream_t st, const float* d, long n, const unsigned* prefix, unsigned mask, int shift, unsigned long long* hist);
+int launch_gather_cols(hipStream_t st, const float* src, long ld, long rows, const int32_t* idx, int n_sel, float* dst);
 
 }  // namespace smx

@@ -587,6 +587,9 @@ int smx_model_destroy(smx_model* m) {
   if (m->pred_target) hipFree(m->pred_target);
   if (m->csr_host) hipFree(m->csr_host);
   if (m->pred_ids) hipFree(m->pred_ids);
+  if (m->imp_d) hipFree(m->imp_d);
+  if (m->imp_hist) hipFree(m->imp_hist);
+  if (m->pred_sel) hipFree(m->pred_sel);
   if (m->score_buf) hipFree(m->score_buf);
   if (m->score_wimg) hipFree(m->score_wimg);
   if (m->score_aux) hipFree(m->score_aux);

@@ -231,6 +231,10 @@ static int launch_plane_stat(hipStream_t st, const StatArgs& a) {
 struct StatReq {
   int stat = 0, count_only = 0; const float* target = nullptr; const CsrRows* tcsr = nullptr; float* out = nullptr;
   uint64_t seed = 0; int n_k = 1;
+  // stat 2 only.  sel: n_sel gene indices (device) -- out is [n_cells][n_sel].  impute: nothing of the mean leaves the device; the scores
+  // of |target - mean| do (smx_impute.hip), `target` / `tcsr` being the original rows
+  const int32_t* sel = nullptr; int n_sel = 0;
+  int impute = 0; float* imp_median = nullptr; int32_t* imp_changed = nullptr; float* imp_lohi = nullptr;
 };
 
 // ---- host rows given as CSR (smx_predict_csr and kin): (indptr int64 [n + 1], cols int32, vals float32), indptr absolute ----
@@ -332,6 +336,7 @@ struct PredChunk {
   float *in_raw = nullptr, *in_x = nullptr, *in_lib = nullptr, *in_lgx1 = nullptr;   // input: raw rows [Cn][G] (dense), the tile [Cn][Gp], library prior, constants
   float *zm = nullptr, *zs = nullptr, *lm = nullptr, *ls = nullptr;   // latent moments [Cn][D] / [Cn]
   float *zd = nullptr, *ld = nullptr, *xp = nullptr, *st = nullptr;   // draws [S][Cn][D] / [S][Cn], planes [S][k][Cn][G], the statistic
+  float *sel = nullptr, *imed = nullptr, *ichg = nullptr;   // the statistic's selected columns [Cn][n_sel]; imputation: median, changed flag (int32) [Cn]
   float* y[SMX_MAX_LABELS] = {};    // label outputs [S][Cn][wy]
   size_t wy[SMX_MAX_LABELS] = {};   // ... their widths per cell and draw
 };
@@ -553,13 +558,15 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
       {&ch.zm, D, z_mean != nullptr}, {&ch.zs, DS, z_scale != nullptr}, {&ch.lm, 1, l_mean != nullptr}, {&ch.ls, 1, l_scale != nullptr},
       {&ch.zd, S * D, z_samples != nullptr}, {&ch.ld, S, l_samples != nullptr}, {&ch.xp, S * k * G, x_params != nullptr},
       {&ch.st, w_stat, w_stat > 0},
+      {&ch.sel, sr ? (size_t)sr->n_sel : 0, sr && sr->n_sel > 0}, {&ch.imed, 1, sr && sr->impute}, {&ch.ichg, 1, sr && sr->impute},
       {&ch.in_raw, G, !cx}, {&ch.in_x, Gp, !cx}, {&ch.in_lib, 2, true}, {&ch.in_lgx1, 1, true},
       {&ch.y[0], S * ch.wy[0], ch.wy[0] > 0}, {&ch.y[1], S * ch.wy[1], ch.wy[1] > 0}, {&ch.y[2], S * ch.wy[2], ch.wy[2] > 0},
       {&ch.y[3], S * ch.wy[3], ch.wy[3] > 0}};
   size_t per_cell = 0;
   for (const Seg& g : plan) per_cell += g.on ? g.w : 0;
   SMX_REQUIRE(per_cell > (cx ? 0 : G) + Gp + 3, "no output requested");
-  const bool t_dev = sr && sr->stat == 3 && (sr->target || sr->tcsr);   // targets other than the input rows
+  const bool impute = sr && sr->impute;
+  const bool t_dev = sr && (sr->stat == 3 || impute) && (sr->target || sr->tcsr);   // targets other than the input rows
   if (t_dev) SMX_CHECK(dgrow(m, &m->pred_target, &m->pred_target_floats, (size_t)batch * Gp, (size_t)m->Bmax * Gp));   // a batch of target rows
   // 128 MB of staging (knob predict_stage_floats: tests force several chunks on small problems)
   const size_t cap_floats = (size_t)std::max(1.0, tuning("predict_stage_floats", (double)((size_t)32 << 20)));
@@ -599,6 +606,27 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
     SMX_HIP(hipMemcpyAsync(dst, src, count * sizeof(float), hipMemcpyDeviceToHost, m->st));
     return SMX_OK;
   };
+  // ---- imputation (smx_impute.hip): the histograms of the global selection, and d = |original - mean| of all cells when N G floats fit the
+  // budget (knob impute_keep_bytes; default: half of the free device memory) -- otherwise levels 2 and 3 REPEAT the walk (level > 0 below:
+  // the same passes give the same bits, every draw being a function of counters), each pass's rows of d going through a small scratch ----
+  bool keep_d = false;
+  if (impute) {
+    SMX_REQUIRE(t_dev && sr->imp_median && sr->imp_changed && sr->imp_lohi, "imputation needs the original rows and its three outputs");
+    if (!m->imp_hist) SMX_CHECK(dmalloc(&m->imp_hist, (size_t)SMX_IMP_HIST_WORDS));
+    SMX_HIP(hipMemsetAsync(m->imp_hist, 0, (size_t)SMX_IMP_HIST_WORDS * sizeof(unsigned long long), m->st));
+    double budget = tuning("impute_keep_bytes", -1.0);
+    if (budget < 0.0) {
+      size_t fr = 0, tot = 0;
+      SMX_HIP(hipMemGetInfo(&fr, &tot));
+      budget = 0.5 * (double)(fr + m->imp_d_floats * sizeof(float));
+    }
+    keep_d = (double)N * (double)G * 4.0 <= budget;
+    SMX_CHECK(dgrow(m, &m->imp_d, &m->imp_d_floats, keep_d ? N * G : (size_t)m->Bmax * G));
+  }
+  unsigned long long* const lv_hist = impute ? m->imp_hist + SMX_IMP_L1_BINS : nullptr;
+  // level 0: the walk itself.  level 1 / 2 (imputation without the kept d): the passes again, nothing copied out, the pass's rows of d
+  // into the histogram of bits `shift`.. under the prefixes
+  auto walk = [&](int level, const unsigned* prefix, unsigned mask, int shift) -> int {
   for (size_t c0 = 0; c0 < N; c0 += ch.Cn) {
     ch.Cn = std::min(C, N - c0);   // cells of this chunk (CSR rows: load_chunk may take fewer)
     ch.c0 = c0;
@@ -608,19 +636,36 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
       const int B = (int)std::min<size_t>(step, Cn - b0);
       const size_t g0 = c0 + b0;
       Pass ps = host_rows_pass(B, ch.in_x + b0 * Gp, ch.in_lib + b0 * 2, ch.in_lgx1 + b0);   // (on the chunk's resident copy)
-      if (sr && sr->stat == 3 && sr->tcsr) SMX_CHECK(csr_host_rows(m, *sr->tcsr, g0, (size_t)B, m->pred_target, nullptr));
-      else if (sr && sr->stat == 3 && sr->target)
+      if (t_dev && sr->tcsr) SMX_CHECK(csr_host_rows(m, *sr->tcsr, g0, (size_t)B, m->pred_target, nullptr));
+      else if (t_dev && sr->target)
         SMX_HIP(hipMemcpy2DAsync(m->pred_target, Gp * sizeof(float), sr->target + g0 * G, G * sizeof(float), G * sizeof(float), (size_t)B,
                                  hipMemcpyHostToDevice, m->st));
       if (stack) SMX_CHECK(predict_batch_stacked(m, ch, ps, b0, step > (size_t)batch ? m->pred_ids : nullptr, need_dec));
       else SMX_CHECK(predict_batch_drawwise(m, ch, ps, b0, need_dec));
+      if (impute) {   // the rows' means over the draws are complete: their medians, flags and share of the level-1 histogram; or their d alone
+        ImputeRowArgs ia;
+        ia.mean = ch.st + b0 * G; ia.ldm = (long)G; ia.orig = m->pred_target; ia.ldo = (long)Gp; ia.cor = ch.in_x + b0 * Gp; ia.ldc = (long)Gp;
+        ia.G = m->G; ia.d_only = level > 0 ? 1 : 0; ia.d = keep_d ? m->imp_d + g0 * G : (level > 0 ? m->imp_d : nullptr);
+        ia.median = ch.imed + b0; ia.changed = reinterpret_cast<int32_t*>(ch.ichg) + b0; ia.hist = m->imp_hist;
+        SMX_CHECK(launch_impute_rows(m->st, ia, B));
+        if (level > 0) SMX_CHECK(launch_impute_level(m->st, m->imp_d, (long)((size_t)B * G), prefix, mask, shift, lv_hist));
+      }
     }
+    if (level > 0) { SMX_HIP(hipStreamSynchronize(m->st)); continue; }
     // ---- the chunk leaves the device: every segment's rows are contiguous here and in the caller's arrays ----
     if (ch.zm) SMX_CHECK(out(z_mean + c0 * D, ch.zm, Cn * D));
     if (ch.zs) SMX_CHECK(out(z_scale + c0 * DS, ch.zs, Cn * DS));
     if (ch.lm) SMX_CHECK(out(l_mean + c0, ch.lm, Cn));
     if (ch.ls) SMX_CHECK(out(l_scale + c0, ch.ls, Cn));
-    if (ch.st && sr->stat == 2) SMX_CHECK(out(sr->out + c0 * G, ch.st, Cn * G));
+    if (ch.st && sr->stat == 2 && !impute && !ch.sel) SMX_CHECK(out(sr->out + c0 * G, ch.st, Cn * G));
+    if (ch.sel) {
+      SMX_CHECK(launch_gather_cols(m->st, ch.st, (long)G, (long)Cn, sr->sel, sr->n_sel, ch.sel));
+      SMX_CHECK(out(sr->out + c0 * (size_t)sr->n_sel, ch.sel, Cn * (size_t)sr->n_sel));
+    }
+    if (impute) {
+      SMX_CHECK(out(sr->imp_median + c0, ch.imed, Cn));
+      SMX_CHECK(out(reinterpret_cast<float*>(sr->imp_changed) + c0, ch.ichg, Cn));
+    }
     for (size_t s = 0; s < S && ch.st && sr->stat == 4; ++s)
       for (size_t q = 0; q < (size_t)sr->n_k; ++q) SMX_CHECK(out(sr->out + ((q * S + s) * N + c0) * G, ch.st + (q * S + s) * Cn * G, Cn * G));
     for (size_t s = 0; s < S && ch.st && sr->stat != 2 && sr->stat != 4; ++s) {
@@ -636,6 +681,42 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
         if (ch.y[j]) SMX_CHECK(out(y_params[j] + (s * N + c0) * ch.wy[j], ch.y[j] + s * Cn * ch.wy[j], Cn * ch.wy[j]));
     }
     SMX_HIP(hipStreamSynchronize(m->st));
+  }
+  return SMX_OK;
+  };
+  SMX_CHECK(walk(0, nullptr, 0u, 0));
+  if (!impute) return SMX_OK;
+  // ---- the two middle order statistics of all N G entries of d: ranks (NG - 1) / 2 and NG / 2, 64-bit.  Level 1 (bits 30..20) came with
+  // the walk; the host picks each rank's bin, levels 2 (bits 19..10) and 3 (bits 9..0) count inside the picked prefixes ----
+  std::vector<unsigned long long> h((size_t)SMX_IMP_HIST_WORDS);
+  SMX_HIP(hipMemcpy(h.data(), m->imp_hist, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  const bool any_nan = h[(size_t)SMX_IMP_HIST_WORDS - 1] != 0;
+  const unsigned long long NG = (unsigned long long)N * (unsigned long long)G;
+  unsigned long long rank[2] = {(NG - 1) / 2, NG / 2};
+  unsigned prefix[2] = {0u, 0u};
+  auto pick = [&](const unsigned long long* bins, int n_bins, int t, int shift) -> int {
+    unsigned long long cum = 0;
+    for (int b = 0; b < n_bins; ++b) {
+      if (rank[t] < cum + bins[b]) { prefix[t] |= (unsigned)b << shift; rank[t] -= cum; return SMX_OK; }
+      cum += bins[b];
+    }
+    set_error("imputation: the selection histogram does not hold the rank");
+    return SMX_ERR_HIP;
+  };
+  for (int t = 0; t < 2; ++t) SMX_CHECK(pick(h.data(), SMX_IMP_L1_BINS, t, 20));
+  unsigned mask = 0xFFF00000u;
+  for (int shift = 10; shift >= 0; shift -= 10) {
+    SMX_HIP(hipMemsetAsync(lv_hist, 0, (size_t)2 * SMX_IMP_LN_BINS * sizeof(unsigned long long), m->st));
+    if (keep_d) SMX_CHECK(launch_impute_level(m->st, m->imp_d, (long)(N * G), prefix, mask, shift, lv_hist));
+    else SMX_CHECK(walk(shift == 10 ? 1 : 2, prefix, mask, shift));
+    SMX_HIP(hipStreamSynchronize(m->st));
+    SMX_HIP(hipMemcpy(h.data(), lv_hist, (size_t)2 * SMX_IMP_LN_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int t = 0; t < 2; ++t) SMX_CHECK(pick(h.data() + (size_t)t * SMX_IMP_LN_BINS, SMX_IMP_LN_BINS, t, shift));
+    mask |= (unsigned)(SMX_IMP_LN_BINS - 1) << shift;
+  }
+  for (int t = 0; t < 2; ++t) {   // (a NaN anywhere: np.median's answer)
+    const unsigned v = any_nan ? 0x7FC00000u : prefix[t];
+    memcpy(sr->imp_lohi + t, &v, sizeof(float));
   }
   return SMX_OK;
 }
@@ -676,6 +757,61 @@ int smx_predict_stat_csr(smx_model* m, const int64_t* indptr, const int32_t* col
   StatReq sr;
   sr.stat = stat; sr.count_only = count_only ? 1 : 0; sr.target = target; sr.tcsr = t_indptr ? &tc : nullptr; sr.out = out;
   return predict_core(m, nullptr, in, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr);
+}
+
+// stat 2 restricted to n_sel gene columns: the indices are checked here and go to the device once
+static int predict_stat_cols(smx_model* m, const float* host_x, const CsrRows* cx, const float* host_library, int64_t n_cells, int32_t batch,
+                             int32_t n_samples, int32_t count_only, const int32_t* genes, int32_t n_sel, float* out) {
+  SMX_REQUIRE(m && out && genes && n_sel > 0, "bad arguments");
+  SMX_REQUIRE(!(count_only && m->cfg.likelihood == SMX_LLK_MSE), "the deterministic 'mse' output has no count distribution");
+  for (int i = 0; i < n_sel; ++i) SMX_REQUIRE(genes[i] >= 0 && genes[i] < m->G, "gene index out of range");
+  SMX_CHECK(dgrow(m, &m->pred_sel, &m->pred_sel_n, (size_t)n_sel));
+  SMX_HIP(hipMemcpy(m->pred_sel, genes, (size_t)n_sel * sizeof(int32_t), hipMemcpyHostToDevice));
+  StatReq sr;
+  sr.stat = 2; sr.count_only = count_only ? 1 : 0; sr.out = out; sr.sel = m->pred_sel; sr.n_sel = n_sel;
+  return predict_core(m, host_x, cx, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr);
+}
+
+int smx_predict_stat_cols(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
+                          int32_t count_only, const int32_t* genes, int32_t n_sel, float* out) {
+  return predict_stat_cols(m, host_x, nullptr, host_library, n_cells, batch, n_samples, count_only, genes, n_sel, out);
+}
+
+int smx_predict_stat_cols_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                              int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, const int32_t* genes, int32_t n_sel,
+                              float* out) {
+  SMX_REQUIRE(indptr, "null indptr");
+  const CsrRows cx{indptr, cols, vals};
+  return predict_stat_cols(m, nullptr, &cx, host_library, n_cells, batch, n_samples, count_only, genes, n_sel, out);
+}
+
+// the imputation scores of the walk's stat 2 (smx_impute.hip)
+static int predict_impute(smx_model* m, const float* host_x, const CsrRows* cx, const float* host_library, int64_t n_cells, int32_t batch,
+                          int32_t n_samples, int32_t count_only, const float* original, const CsrRows* ocsr, float* cell_median,
+                          int32_t* cell_changed, float* global_lohi) {
+  SMX_REQUIRE(m && cell_median && cell_changed && global_lohi, "bad arguments");
+  SMX_REQUIRE((original != nullptr) != (ocsr != nullptr), "the original rows are dense or CSR (exactly one of the two)");
+  SMX_REQUIRE(!(count_only && m->cfg.likelihood == SMX_LLK_MSE), "the deterministic 'mse' output has no count distribution");
+  StatReq sr;
+  sr.stat = 2; sr.count_only = count_only ? 1 : 0; sr.target = original; sr.tcsr = ocsr;
+  sr.impute = 1; sr.imp_median = cell_median; sr.imp_changed = cell_changed; sr.imp_lohi = global_lohi;
+  return predict_core(m, host_x, cx, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr);
+}
+
+int smx_predict_impute(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
+                       int32_t count_only, const float* original, float* cell_median, int32_t* cell_changed, float* global_lohi) {
+  return predict_impute(m, host_x, nullptr, host_library, n_cells, batch, n_samples, count_only, original, nullptr, cell_median, cell_changed,
+                        global_lohi);
+}
+
+int smx_predict_impute_csr(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals,
+                           const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only,
+                           const float* original, const int64_t* o_indptr, const int32_t* o_cols, const float* o_vals, float* cell_median,
+                           int32_t* cell_changed, float* global_lohi) {
+  SMX_REQUIRE((host_x != nullptr) != (indptr != nullptr), "the input rows are dense or CSR (exactly one of the two)");
+  const CsrRows cx{indptr, cols, vals}, oc{o_indptr, o_cols, o_vals};
+  return predict_impute(m, host_x, indptr ? &cx : nullptr, host_library, n_cells, batch, n_samples, count_only, original,
+                        o_indptr ? &oc : nullptr, cell_median, cell_changed, global_lohi);
 }
 
 // stat 4 of the walk: n_k samples of the gene output per draw and cell, out [n_k, n_samples, n_cells, n_genes]

@@ -576,6 +576,18 @@ def count_distribution(likelihood: str, planes, name: str, activated: bool) -> D
   return Independent(base, 1, name=name)
 
 
+def imputation_scores_from_cells(cell_median, cell_changed, global_lohi):
+  """The reference's closing reductions (imputation_benchmarks.py:102-127) of what the device selected: np.mean / np.std of the float32
+  medians of the changed cells (0 for none), and np.median's mean of the two middle values, 0.5 (lo + hi) in float32."""
+  cells = [m for m, c in zip(np.asarray(cell_median, np.float32), np.asarray(cell_changed)) if c]
+  lo, hi = np.asarray(global_lohi, np.float32)
+  with np.errstate(over="ignore", invalid="ignore"):
+    med = np.float32(0.5) * (lo + hi)
+  return {"imputation_med": float(med),
+          "imputation_mean": float(np.mean(cells)) if len(cells) > 0 else 0.0,
+          "imputation_std": float(np.std(cells)) if len(cells) > 0 else 0.0}
+
+
 # ---------------------------------------------------------------------------
 class LazyCountOutput(Distribution):
   """predict()'s gene output as a handle on the DEVICE side: the parameter planes (4 k G bytes per cell and draw: 24 KB at 1998 genes)
@@ -642,9 +654,36 @@ class LazyCountOutput(Distribution):
   def variance(self, out=None):
     return self._stat("variance", out=out)
 
-  def mean_over_samples(self, out=None):
-    """E_s[mean] over the Monte-Carlo draws, [n_cells, n_genes] (what `np.mean(imputed.mean(), axis=0)` computes, posterior.py:985-987)."""
-    return self._stat("mean_over_samples", out=out)
+  def mean_over_samples(self, genes=None, out=None):
+    """E_s[mean] over the Monte-Carlo draws, [n_cells, n_genes] (what `np.mean(imputed.mean(), axis=0)` computes, posterior.py:985-987).
+    genes: a list of gene indices (any order, repeats allowed) -- only those columns leave the device, [n_cells, len(genes)], the same
+    bits as `mean_over_samples()[:, genes]` (smx_predict_stat_cols: what the marker correlations of sc_metrics.py:287-348 read)."""
+    if genes is None:
+      return self._stat("mean_over_samples", out=out)
+    return self._engine().predict_stat(self._x, "mean_over_samples", library=self._lib, n_samples=max(self._S, 1), batch=self._B,
+                                       count_only=self._count_only, out=out, genes=genes)
+
+  def imputation_cells(self, original):
+    """What the device reduces for `imputation_scores` (Engine.predict_impute): dict(cell_median [N], cell_changed [N], global_lohi [2]).
+    On a zero-inflated output the count distribution is scored, as the reference does (posterior.py:218-225)."""
+    if original is None:
+      raise ValueError("imputation scores need the original counts")
+    n, g = self._x.shape[0], self.event_shape[0]
+    if not _sp.issparse(original):
+      original = np.asarray(original, np.float32)
+    if tuple(original.shape) != (n, g):
+      raise ValueError(f"original must have the prediction's shape {(n, g)}, got {tuple(original.shape)}")
+    count_only = self._count_only or self.is_zero_inflated
+    return self._engine().predict_impute(self._x, original, library=self._lib, n_samples=max(self._S, 1), batch=self._B, count_only=count_only)
+
+  def imputation_scores(self, original):
+    """The three scores of `Posterior.cal_imputation_scores` (posterior.py:978-993; imputation_benchmarks.py:102-127) of this prediction,
+    the handle's own input being the CORRUPTED matrix: {'imputation_med': median of |original - imputed| over all entries,
+    'imputation_mean' / 'imputation_std': mean / standard deviation of the per-cell medians over the cells whose total count the
+    corruption changed (0 without any)}, `imputed` = `mean_over_samples()` of the count distribution.  The medians are selected on the
+    device (exactly; smx_impute.hip) -- 8 bytes per cell leave it instead of 4 n_genes; the closing lines are the reference's, on the host."""
+    r = self.imputation_cells(original)
+    return imputation_scores_from_cells(r["cell_median"], r["cell_changed"], r["global_lohi"])
 
   def log_prob(self, x=None):
     """log p(x) summed over the genes, [n_samples, n_cells] ([n_cells] without a draw axis); x = None: of the input counts.  x may be

@@ -71,6 +71,16 @@ def _tril_scale(out):
   return out
 
 
+def gene_indices(genes, n_genes: int) -> np.ndarray:
+  """A list of gene indices as int32 [n_sel] (any order, repeats allowed); an index outside 0 .. n_genes - 1 or an empty list raises."""
+  g = np.asarray(genes)
+  if g.ndim != 1 or g.size == 0 or not np.issubdtype(g.dtype, np.integer):
+    raise ValueError("genes must be a non-empty 1-D list of integer gene indices")
+  if g.min() < 0 or g.max() >= n_genes:
+    raise IndexError(f"gene index out of range 0 .. {n_genes - 1}")
+  return np.ascontiguousarray(g, dtype=np.int32)
+
+
 def make_smx_config(cfg: ModelConfig, max_batch: int) -> smx_config:
   c = smx_config()
   c.abi_version = _hip.SMX_ABI_VERSION
@@ -481,14 +491,17 @@ class Engine:
   STATS = {"mean": 0, "variance": 1, "mean_over_samples": 2, "log_prob": 3, "sample": 4}
 
   def predict_stat(self, x, stat: str, library=None, n_samples: int = 1, batch: Optional[int] = None, count_only: bool = False,
-                   target=None, out=None, seed: int = 0, n: int = 1):
+                   target=None, out=None, seed: int = 0, n: int = 1, genes=None):
     """A statistic of the gene output over a whole host matrix (smx_predict_stat): the same passes and draws as predict(), but only the
     statistic leaves the device.  'mean' / 'variance' [n_samples, N, G]; 'mean_over_samples' [N, G]; 'log_prob' [n_samples, N] of `target`
     (default: of x itself).  count_only: the count distribution without the zero-inflation wrapper.  `out`: a float32 array of the
     result's shape to write into (a reused array saves the first-touch page faults of a fresh one).  x and target may be scipy.sparse
     (smx_predict_stat_csr).  'sample': [n, n_samples, N, G], n posterior-predictive draws of the gene output per Monte-Carlo draw and cell
-    under the integer `seed` (smx_predict_sample / _csr: drawn on the device, the same bits at any batch size and from dense or sparse x)."""
+    under the integer `seed` (smx_predict_sample / _csr: drawn on the device, the same bits at any batch size and from dense or sparse x).
+    genes ('mean_over_samples' only): gene indices -- [N, len(genes)] leaves the device, the same bits as those columns (smx_predict_stat_cols)."""
     cfg = self.cfg
+    if genes is not None:
+      return self._predict_stat_cols(x, stat, library, n_samples, batch, count_only, target, out, genes)
     xa = _csr3(x, cfg.n_genes) if _sparse(x) else _f32(x)
     N, S, G = (xa[0].size - 1 if isinstance(xa, tuple) else xa.shape[0]), int(n_samples), cfg.n_genes
     B = min(int(batch or self.max_batch), self.max_batch)
@@ -520,6 +533,54 @@ class Engine:
     else:
       check(self.lib.smx_predict_stat(self._h, _fp(xa), _fp(la), N, B, S, code, int(bool(count_only)), _fp(ta), _fp(out)))
     return out
+
+  def _predict_stat_cols(self, x, stat, library, n_samples, batch, count_only, target, out, genes):
+    cfg = self.cfg
+    if stat != "mean_over_samples" or target is not None:
+      raise ValueError("genes= goes with 'mean_over_samples' (and no target)")
+    idx = gene_indices(genes, cfg.n_genes)
+    xa = _csr3(x, cfg.n_genes) if _sparse(x) else _f32(x)
+    N, S = (xa[0].size - 1 if isinstance(xa, tuple) else xa.shape[0]), int(n_samples)
+    B = min(int(batch or self.max_batch), self.max_batch)
+    la = None if library is None else _f32(library, (N, 2))
+    shape = (N, idx.size)
+    if out is None:
+      out = np.empty(shape, np.float32)
+    elif out.dtype != np.float32 or tuple(out.shape) != shape or not out.flags.c_contiguous:
+      raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
+    ip = idx.ctypes.data_as(C.POINTER(C.c_int32))
+    if isinstance(xa, tuple):
+      check(self.lib.smx_predict_stat_cols_csr(self._h, *_csr_ptrs(xa), _fp(la), N, B, S, int(bool(count_only)), ip, idx.size, _fp(out)))
+    else:
+      check(self.lib.smx_predict_stat_cols(self._h, _fp(xa), _fp(la), N, B, S, int(bool(count_only)), ip, idx.size, _fp(out)))
+    return out
+
+  def predict_impute(self, x, original, library=None, n_samples: int = 1, batch: Optional[int] = None, count_only: bool = False):
+    """The imputation scores of predict_stat(x, 'mean_over_samples') against `original`, reduced on the device (smx_predict_impute): x is
+    the CORRUPTED matrix the prediction is made from.  Returns dict(cell_median [N] float32: np.median(|original - mean|) of every cell;
+    cell_changed [N] int32: sum(original row) != sum(x row); global_lohi [2] float32: the two middle order statistics of all N G absolute
+    differences).  x and original may each be scipy.sparse; the bits do not depend on that, on the batch size or on the chunking."""
+    cfg = self.cfg
+    G = cfg.n_genes
+    xa = _csr3(x, G) if _sparse(x) else _f32(x)
+    N, S = (xa[0].size - 1 if isinstance(xa, tuple) else xa.shape[0]), int(n_samples)
+    if not isinstance(xa, tuple) and (xa.ndim != 2 or xa.shape[1] != G):
+      raise ValueError(f"expected rows [n_cells, {G}], got {xa.shape}")
+    if original is None:
+      raise ValueError("predict_impute needs the original counts")
+    oc = _csr3(original, G, N) if _sparse(original) else None
+    oa = None if oc is not None else _f32(original, (N, G))
+    B = min(int(batch or self.max_batch), self.max_batch)
+    la = None if library is None else _f32(library, (N, 2))
+    med, chg, lohi = np.empty((N,), np.float32), np.empty((N,), np.int32), np.empty((2,), np.float32)
+    res = (_fp(med), chg.ctypes.data_as(C.POINTER(C.c_int32)), _fp(lohi))
+    if isinstance(xa, tuple) or oc is not None:
+      xp = (None,) + _csr_ptrs(xa) if isinstance(xa, tuple) else (_fp(xa), None, None, None)
+      op = _csr_ptrs(oc) if oc is not None else (None, None, None)
+      check(self.lib.smx_predict_impute_csr(self._h, *xp, _fp(la), N, B, S, int(bool(count_only)), _fp(oa), *op, *res))
+    else:
+      check(self.lib.smx_predict_impute(self._h, _fp(xa), _fp(la), N, B, S, int(bool(count_only)), _fp(oa), *res))
+    return dict(cell_median=med, cell_changed=chg, global_lohi=lohi)
 
   def decode(self, z, l=None):
     """Decoder + output heads from given latents (eval mode)."""
@@ -800,6 +861,17 @@ def k_gemm(A, B, trans_a=False, trans_b=False, split_k=1, tile=0):
   Cm = np.empty((M, N), np.float32)
   check(lib.smx_k_gemm(int(trans_a), int(trans_b), _fp(A), _fp(B), M, N, K, int(split_k), int(tile), _fp(Cm)))
   return Cm
+
+
+def k_row_select(rows, n_genes: Optional[int] = None):
+  """smx_k_row_select: the two middle order statistics of the first n_genes entries of every row of `rows` [n, ld] (non-negative or NaN) -> (lo, hi) [n]"""
+  lib = _hip.require_gpu()
+  r = _f32(rows)
+  n, ld = r.shape
+  G = ld if n_genes is None else int(n_genes)
+  lo, hi = np.empty((n,), np.float32), np.empty((n,), np.float32)
+  check(lib.smx_k_row_select(_fp(r), n, G, ld, _fp(lo), _fp(hi)))
+  return lo, hi
 
 
 def k_noise(seed, stream, step, cell_ids, width, p=0.0, sample=0):

@@ -1,0 +1,79 @@
+"""Evaluation metrics of a fitted model as plain callables `metric(model) -> dict` (the reference's training-time metrics,
+sisua/analysis/sc_metrics.py:244-348, without its callback machinery): `ImputationError` and `CorrelationScores`.  What needs the
+[cells, genes] mean of the gene output is reduced on the device (smx_impute.hip); the correlations over a few marker columns are SciPy's,
+called as the reference calls them."""
+from __future__ import annotations
+
+from typing import Dict, Iterable, List, Mapping, Sequence, Tuple
+
+import numpy as np
+
+from sisua_amd.data import SingleCellOMIC, corrupt as _corrupt, is_sparse
+
+
+def _matrix(a):
+  """The first omic of a SingleCellOMIC, or the array / scipy.sparse matrix itself."""
+  return a.numpy() if isinstance(a, SingleCellOMIC) else a
+
+
+def _handle(model, x, sample_shape, batch_size):
+  return model._imputation_handle(x, None, sample_shape, batch_size)
+
+
+class ImputationError:
+  """`{'imp_med', 'imp_mean'}` of a model (sc_metrics.py:244-284): the cells are predicted from the corrupted counts with `sample_shape`
+  draws, and the mean of the count distribution is compared with the original counts `inputs` -- the median absolute difference over all
+  entries, and the mean over the changed cells of the per-cell medians.  corrupted=None: `data.corrupt(inputs)` with its defaults
+  (dropout_rate 0.2, retain_rate 0.2, seed 8), made once."""
+
+  def __init__(self, inputs, corrupted=None, sample_shape=1, batch_size=64):
+    self.original = _matrix(inputs)
+    self.corrupted = _matrix(corrupted) if corrupted is not None else _corrupt(self.original, inplace=False)
+    if tuple(self.original.shape) != tuple(self.corrupted.shape):
+      raise ValueError(f"inputs {tuple(self.original.shape)} and corrupted {tuple(self.corrupted.shape)} differ in shape")
+    self.sample_shape, self.batch_size = sample_shape, int(batch_size)
+
+  def __call__(self, model) -> Dict[str, float]:
+    s = _handle(model, self.corrupted, self.sample_shape, self.batch_size).imputation_scores(self.original)
+    return {"imp_med": s["imputation_med"], "imp_mean": s["imputation_mean"]}
+
+
+def marker_pairs(gene_names: Sequence[str], protein_names: Sequence[str], markers: Mapping[str, str]) -> List[Tuple[int, int]]:
+  """(gene index, extras column) of every protein in `protein_names` whose marker gene -- `markers[protein name]`, a mapping the CALLER
+  supplies -- is in `gene_names`; in the order of the proteins."""
+  where = {str(g): i for i, g in enumerate(gene_names)}
+  return [(where[str(markers[str(p)])], j) for j, p in enumerate(protein_names) if str(p) in markers and str(markers[str(p)]) in where]
+
+
+class CorrelationScores:
+  """The four keys of sc_metrics.py:287-348: the NEGATED Pearson / Spearman correlations between the imputed expression of a marker gene
+  and the level of its protein, mean and median over the pairs ({} without pairs).  inputs: the counts the prediction is made from;
+  extras: the protein matrix [cells, proteins]; pairs: a list of (gene index, extras column) (see `marker_pairs`).  Only the marker genes'
+  columns of the mean leave the device (`LazyCountOutput.mean_over_samples(genes=...)`)."""
+
+  def __init__(self, inputs, extras, pairs: Iterable[Tuple[int, int]], sample_shape=1, batch_size=64):
+    self.inputs = _matrix(inputs)
+    ex = _matrix(extras)
+    self.extras = np.asarray(ex.toarray() if is_sparse(ex) else ex, np.float64)
+    self.pairs = [(int(g), int(p)) for g, p in pairs]
+    if self.extras.ndim != 2 or self.extras.shape[0] != self.inputs.shape[0]:
+      raise ValueError("extras must be [cells, proteins] for the cells of inputs")
+    for g, p in self.pairs:
+      if not (0 <= g < self.inputs.shape[1]) or not (0 <= p < self.extras.shape[1]):
+        raise IndexError(f"pair {(g, p)} is outside genes 0 .. {self.inputs.shape[1] - 1} / extras columns 0 .. {self.extras.shape[1] - 1}")
+    self.sample_shape, self.batch_size = sample_shape, int(batch_size)
+
+  def __call__(self, model) -> Dict[str, float]:
+    from scipy.stats import pearsonr, spearmanr
+    if not self.pairs:
+      return {}
+    h = _handle(model, self.inputs, self.sample_shape, self.batch_size)
+    if h.is_zero_inflated:
+      h = h.count_distribution
+    cols = h.mean_over_samples(genes=[g for g, _ in self.pairs])
+    spearman, pearson = [], []
+    for j, (_, p) in enumerate(self.pairs):
+      spearman.append(-spearmanr(cols[:, j], self.extras[:, p]).correlation)
+      pearson.append(-pearsonr(cols[:, j], self.extras[:, p])[0])
+    return {"pearson_mean": float(np.mean(pearson)), "spearman_mean": float(np.mean(spearman)),
+            "pearson_med": float(np.median(pearson)), "spearman_med": float(np.median(spearman))}

@@ -951,6 +951,23 @@ class SingleCellModel:
     return {f"llk_{name}_imp_org": float(sc[0, 1]), f"llk_{name}_imp_cor": float(sc[1, 1]),
             f"llk_{name}_rec_cor": float(sc[1, 0]), f"llk_{name}_rec_org": float(sc[0, 0])}
 
+  def imputation_scores(self, corrupted, original, library=None, sample_shape=10, batch_size=128):
+    r"""The three scores of `Posterior.cal_imputation_scores` (analysis/posterior.py:978-993) on the GPU: cells are predicted from
+    `corrupted` with `sample_shape` posterior draws, the mean of the count distribution (no zero inflation) is averaged over the draws and
+    compared with `original` -- `imputation_med` (median absolute difference over all entries), `imputation_mean` / `imputation_std` (of
+    the per-cell medians over the cells the corruption changed).  Every median is selected on the device (`smx_predict_impute`); the
+    [cells, genes] mean never reaches the host.  Arguments as `posterior_llk` (dense or scipy.sparse, SCVI library default)."""
+    return self._imputation_handle(corrupted, library, sample_shape, batch_size).imputation_scores(_rows(_flatten(original)[0]))
+
+  def _imputation_handle(self, corrupted, library, sample_shape, batch_size):
+    x_cor = self._check_inputs(_rows(_flatten(corrupted)[0]))
+    S = int(np.prod(sample_shape)) if np.size(sample_shape) else 1
+    if self._cfg.model == "scvi" and library is None:
+      library = library_matrix(x_cor)
+    e = self._ensure_engine(max(min(int(batch_size), x_cor.shape[0]), 512 if x_cor.shape[0] >= 1024 else 1))
+    return D.LazyCountOutput(self, x_cor, library if self._cfg.model == "scvi" else None, S if S > 1 else 0, min(int(batch_size), e.max_batch),
+                             self._outputs[0].name or "transcriptomic")
+
   # ---- evaluation hand-off -----------------------------------------------------------------------
   def create_posterior(self, test_sco: SingleCellOMIC = None, **kwargs):
     r"""The reference builds `sisua.analysis.Posterior(scm=self, sco=test, ...)`
@@ -963,7 +980,7 @@ class SingleCellModel:
       from sisua.analysis.posterior import Posterior  # type: ignore
     except Exception as err:
       raise NotImplementedError("sisua.analysis.Posterior is not part of sisua_amd; install the reference "
-                                "package to score this model (predict / marginal_log_prob are provided)") from err
+                                "package to score this model (predict / marginal_log_prob / imputation_scores are provided)") from err
     return Posterior(scm=self, sco=test_sco, **kwargs)
 
   # ---- checkpoints --------------------------------------------------------------------------------
