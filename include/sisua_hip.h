@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 6
+#define SMX_ABI_VERSION 7
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -651,6 +651,25 @@ int smx_k_plane_sample(int likelihood, int direct, int count_only, const float* 
  * [n_rows][ld] (host, ld >= G; what lies beyond G in a row is not read) -> lo, hi [n_rows].  Rows hold non-negative values or NaN (what
  * an absolute difference is); -0 counts as +0 and a NaN sorts above +inf, as np.partition orders them. */
 int smx_k_row_select(const float* rows, int32_t n_rows, int32_t G, int32_t ld, float* lo, float* hi);
+
+/* ---- padding audit (test instrument; never on the path of a step) ----------- */
+/* The layout's invariant, read back from the device: every feature axis is padded to 32 and every tensor to 64 floats, and what lies
+ * outside a tensor's logical extent (rows >= its rows; within each chunk, columns >= the chunk's width) stays exactly zero.  Counts, over
+ * every tensor of the manifest, the elements of [offset, offset + count) outside the logical extent whose bits & 0x7fffffff != 0 (NaN and
+ * denormals count, -0 does not).  which 0..3 as smx_get_tensor (and its rule for sharded optimiser moments: refused until
+ * smx_opt_gather).  which = 4: the work buffers of the LAST pass, rows < its (stacked) batch, columns >= the logical width -- every MLP
+ * layer's output (encoder, library encoder, decoder, discriminator), the latent draw z, scvi's library-latent head [B][32] (2 columns
+ * in use), the gene head's gradient planes dP at columns >= n_genes of every plane, and what the last stacked evaluation decoder
+ * (smx_marginal_llk, smx_score_llk, smx_predict) left of its last two layers (row-major, k-major or bf16-split form).
+ * *n_bad: the count; first_tensor / first_offset / first_name (each may be NULL): the first offender -- its tensor index, the offset
+ * inside it, its name.  which = 4: the index counts the buffers in the order above, whose number depends on the model (layers, planes,
+ * scvi) -- identify a work buffer by first_name ("enc0 out", "z", "dP plane 1", "stacked dec0 (k-major)", ...).  Synchronises the model's stream; the buffer is walked on the host. */
+int smx_pad_audit(smx_model* m, int32_t which, int64_t* n_bad, int32_t* first_tensor, int64_t* first_offset, char* first_name,
+                  int32_t name_cap);
+/* Writes `value` into the FIRST padded element of tensor `index` of buffer which = 0..3 (SMX_ERR_INVALID when the tensor has no padding):
+ * exists so that a test can show that smx_pad_audit sees a violation.  which = 2 / 3 of a head's tensor: smx_get_tensor's rule for sharded
+ * moments (refused until smx_opt_gather). */
+int smx_pad_poke(smx_model* m, int32_t which, int32_t index, float value);
 
 #ifdef __cplusplus
 }

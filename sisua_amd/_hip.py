@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsisua_hip.so")
 
-SMX_ABI_VERSION = 6
+SMX_ABI_VERSION = 7
 SMX_MAX_LAYERS = 8
 SMX_MAX_LABELS = 4
 
@@ -171,6 +171,8 @@ SIGNATURES = {
                               C.c_float, _FP, _FP]),
     "smx_k_plane_sample": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _FP]),
     "smx_k_row_select": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]),
+    "smx_pad_audit": (C.c_int, [_VP, C.c_int32, _LP, _IP, _LP, C.c_char_p, C.c_int32]),
+    "smx_pad_poke": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_float]),
 }
 
 _lib = None

@@ -72,6 +72,10 @@ struct MlpLayer {
 };
 
 struct Injected { float* d = nullptr; int ld = 0; };
+// what the last stacked evaluation decoder left in score_buf, for smx_pad_audit(which = 4): the capacity in rows its layout was cut for
+// (z [cap][Dp] | lw [cap] | two alternating layer buffers [cap][Hmax] | the scoring call's last layer), the rows of the last pass, and
+// the last layer's form -- stacked_decoder's last_form 0 / 1 / 2, 3: the one-launch decoder (the bf16 split alone), -1: none yet
+struct AuditStacked { long cap = 0, rows = 0; int form = -1; };
 
 struct RcclApi {
   void* lib = nullptr;
@@ -305,6 +309,9 @@ struct smx_model {
   bool bucket1_in_flight = false;
   bool fold_dz_now = false;      // this backward pass: the d z product + latent backward run inside the encoder's BatchNorm-backward launch (smx_step.hip)
   bool chain_started = false;    // this step's head bucket went: all-reduce -> norms -> clip + Adam sweep on the communication stream (smx_step.hip: dp_chain_start)
+  // padding audit (smx_pad_audit, which = 4): rows of the last pass (stacked draws included), of the last discriminator pass, and the
+  // layout the last stacked evaluation decoder used (set by its two callers, smx_predict.hip / smx_scoring.hip)
+  int audit_rows = 0, audit_disc_rows = 0; AuditStacked audit_stk;
   // graphs
   std::map<int, hipGraphExec_t> graphs;
   bool capturing = false;
@@ -419,6 +426,7 @@ bool dp_chain_ok(const smx_model* m);
 int forward_pass(smx_model* m, const Pass& ps, bool with_loss, bool backward, int mode = 0);
 int backward_pass(smx_model* m, const Pass& ps);
 int optimizer_pass(smx_model* m);
+int head_sweep_join(smx_model* m);
 int csr_stage(smx_model* m, Pass& ps);
 int check_rows(smx_model* m, const int32_t* ids, size_t n);
 int read_metrics(smx_model* m, smx_metrics* out);

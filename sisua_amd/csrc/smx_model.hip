@@ -649,6 +649,137 @@ int smx_set_tensor(smx_model* m, int which, int index, const float* host) {
   return SMX_OK;
 }
 
+// ---- padding audit (test instrument: the invariant of smx_model.h's layout note, read back from the device) ----------------------
+namespace smx {
+// one work buffer as the audit walks it.  form 0: f32 [rows][ld], padding = columns >= width; 1: f32 k-major [wp][ld] (ld >= rows),
+// padding = rows of it >= width; 2: the three-way bf16 split [3][rows][wp], padding = columns >= width
+struct AuditBuf { std::string name; const void* p = nullptr; long rows = 0; int ld = 0, width = 0, wp = 0, form = 0; };
+static inline bool pad_nonzero(float v) { uint32_t b; memcpy(&b, &v, 4); return (b & 0x7fffffffu) != 0u; }
+// whether element i of tensor t's [offset, offset + count) lies outside the logical extent (rows < rows, columns < chunk_w of their chunk)
+static inline bool pad_element(const TensorInfo& t, size_t i) {
+  const size_t r = i / (size_t)t.ld, c = i % (size_t)t.ld;
+  return (int)r >= t.rows || (int)(c % (size_t)t.chunk_wp) >= t.chunk_w;
+}
+struct PadTally {
+  int64_t n_bad = 0, first_offset = -1; int first = -1; std::string first_name;
+  void hit(int index, const std::string& name, int64_t off) {
+    if (n_bad++ == 0) { first = index; first_name = name; first_offset = off; }
+  }
+};
+// one work buffer of the last pass (AuditBuf): its padding alone copied to the host, walked there
+static int pad_audit_buf(const AuditBuf& b, int index, PadTally& tl) {
+  if (!b.p || b.rows <= 0 || b.wp <= b.width) return SMX_OK;
+  const size_t pw = (size_t)(b.wp - b.width);
+  if (b.form == 2) {   // three images [rows][wp] of bf16, one behind the other: 3 x rows rows of wp
+    const size_t nr = (size_t)3 * b.rows;
+    std::vector<uint16_t> h(nr * pw);
+    SMX_HIP(hipMemcpy2D(h.data(), pw * 2, static_cast<const uint16_t*>(b.p) + b.width, (size_t)b.wp * 2, pw * 2, nr, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i)
+      if (h[i] & 0x7fffu) tl.hit(index, b.name, (int64_t)((i / pw) * b.wp + b.width + i % pw));
+    return SMX_OK;
+  }
+  const float* src = static_cast<const float*>(b.p);
+  if (b.form == 1) {   // k-major [wp][ld]: rows width .. wp - 1 of it, the first `rows` entries of each
+    std::vector<float> h(pw * (size_t)b.rows);
+    SMX_HIP(hipMemcpy2D(h.data(), (size_t)b.rows * 4, src + (size_t)b.width * b.ld, (size_t)b.ld * 4, (size_t)b.rows * 4, pw, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i)
+      if (pad_nonzero(h[i])) tl.hit(index, b.name, (int64_t)((b.width + i / b.rows) * b.ld + i % b.rows));
+    return SMX_OK;
+  }
+  std::vector<float> h((size_t)b.rows * pw);
+  SMX_HIP(hipMemcpy2D(h.data(), pw * 4, src + b.width, (size_t)b.ld * 4, pw * 4, (size_t)b.rows, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < h.size(); ++i)
+    if (pad_nonzero(h[i])) tl.hit(index, b.name, (int64_t)((i / pw) * b.ld + b.width + i % pw));
+  return SMX_OK;
+}
+// the work buffers smx_pad_audit(which = 4) covers, as the last pass left them
+static std::vector<AuditBuf> pad_work_buffers(smx_model* m) {
+  std::vector<AuditBuf> v;
+  auto add = [&](const std::string& name, const float* p, long rows, int ld, int width, int wp, int col0 = 0) {
+    AuditBuf b;
+    b.name = name; b.p = p ? p + col0 : nullptr; b.rows = rows; b.ld = ld; b.width = width; b.wp = wp;
+    v.push_back(b);
+  };
+  const long R = std::min(m->audit_rows, m->Rmax);
+  const char* const pre[3] = {"enc", "encl", "dec"};
+  int n = 0;
+  for (auto* mlp : {&m->enc, &m->encl, &m->dec}) {
+    for (size_t i = 0; i < mlp->size(); ++i) add(std::string(pre[n]) + std::to_string(i) + " out", (*mlp)[i].out_buf, R, (*mlp)[i].out_p, (*mlp)[i].out, (*mlp)[i].out_p);
+    ++n;
+  }
+  const long R2 = std::min(m->audit_disc_rows, 2 * m->Bmax);
+  for (size_t i = 0; i < m->disc.size(); ++i) add("disc" + std::to_string(i) + " out", m->disc[i].out_buf, R2, m->disc[i].out_p, m->disc[i].out, m->disc[i].out_p);
+  add("z", m->z, R, m->Dp, m->D, m->Dp);
+  if (m->scvi) add("library latent head", m->latlbuf, R, 32, 2, 32);
+  for (int c = 0; c < m->k; ++c) add("dP plane " + std::to_string(c), m->dP, R, m->k * m->Gp, m->G, m->Gp, c * m->Gp);
+  // the stacked evaluation decoder's buffers, from score_buf's layout as its callers cut it (smx_scoring.hip / smx_predict.hip): the two
+  // alternating buffers hold the last two layers' outputs; a scoring call's last layer also stands k-major or bf16-split behind them
+  const AuditStacked& sk = m->audit_stk;
+  int Hmax = 0;
+  for (const MlpLayer& L : m->dec) Hmax = std::max(Hmax, L.out_p);
+  const size_t need = sk.form < 0 ? 0 : (size_t)sk.cap * ((size_t)m->Dp + 1 + (size_t)(sk.form == 0 ? 2 : 4) * Hmax);
+  if (sk.form >= 0 && m->score_buf && sk.rows <= sk.cap && need <= m->score_floats) {   // (a scratch regrown smaller since: nothing of it is left)
+    float* hb[2] = {m->score_buf + (size_t)sk.cap * (m->Dp + 1), m->score_buf + (size_t)sk.cap * (m->Dp + 1 + Hmax)};
+    const float* ht = hb[1] + (size_t)sk.cap * Hmax;
+    const size_t n = m->dec.size();
+    for (size_t i = n >= 2 ? n - 2 : 0; i < n && sk.form != 3; ++i)
+      add("stacked dec" + std::to_string(i), hb[i & 1], sk.rows, m->dec[i].out_p, m->dec[i].out, m->dec[i].out_p);
+    if (sk.form >= 1) {
+      const MlpLayer& L = m->dec.back();
+      AuditBuf b;
+      b.name = std::string("stacked dec") + std::to_string(n - 1) + (sk.form == 1 ? " (k-major)" : " (bf16 split)");
+      b.p = ht; b.rows = sk.rows; b.width = L.out; b.wp = L.out_p; b.form = sk.form == 1 ? 1 : 2; b.ld = sk.form == 1 ? (int)sk.rows : L.out_p;
+      v.push_back(b);
+    }
+  }
+  return v;
+}
+}  // namespace smx
+
+int smx_pad_audit(smx_model* m, int32_t which, int64_t* n_bad, int32_t* first_tensor, int64_t* first_offset, char* first_name, int32_t name_cap) {
+  SMX_REQUIRE(m && n_bad, "null argument");
+  SMX_REQUIRE(which >= 0 && which <= 4, "which must be 0..4");
+  SMX_REQUIRE(!(m->opt_stale && (which == 2 || which == 3)),
+              "the heads' Adam moments are sharded over the ranks (flag opt_shard): call smx_opt_gather on every rank first");
+  SMX_CHECK(head_sweep_join(m));   // (the heads' background update, if one is under way on the second stream)
+  SMX_HIP(hipStreamSynchronize(m->st));
+  PadTally tl;
+  if (which == 4) {
+    const std::vector<AuditBuf> bufs = pad_work_buffers(m);
+    for (size_t i = 0; i < bufs.size(); ++i) SMX_CHECK(pad_audit_buf(bufs[i], (int)i, tl));
+  } else {
+    std::vector<float> h(m->flat_count);
+    SMX_HIP(hipMemcpy(h.data(), which_buf(m, which), h.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t t = 0; t < m->tensors.size(); ++t) {
+      const TensorInfo& ti = m->tensors[t];
+      for (size_t i = 0; i < ti.count; ++i)
+        if (pad_element(ti, i) && pad_nonzero(h[ti.offset + i])) tl.hit((int)t, ti.name, (int64_t)i);
+    }
+  }
+  *n_bad = tl.n_bad;
+  if (first_tensor) *first_tensor = tl.first;
+  if (first_offset) *first_offset = tl.first_offset;
+  if (first_name && name_cap > 0) { strncpy(first_name, tl.first_name.c_str(), name_cap - 1); first_name[name_cap - 1] = 0; }
+  return SMX_OK;
+}
+
+int smx_pad_poke(smx_model* m, int32_t which, int32_t index, float value) {
+  SMX_REQUIRE(m && index >= 0 && index < (int)m->tensors.size(), "bad tensor index");
+  float* base = which_buf(m, which);
+  SMX_REQUIRE(base, "which must be 0..3");
+  const TensorInfo& t = m->tensors[index];
+  size_t at = t.count;
+  for (size_t i = 0; i < t.count; ++i) if (pad_element(t, i)) { at = i; break; }
+  SMX_REQUIRE(at < t.count, "smx_pad_poke: the tensor has no padding");
+  SMX_REQUIRE(!(m->opt_stale && (which == 2 || which == 3) && t.offset >= m->bucket1_off),
+              "the heads' Adam moments are sharded over the ranks (flag opt_shard): call smx_opt_gather on every rank first");
+  SMX_CHECK(head_sweep_join(m));
+  SMX_HIP(hipStreamSynchronize(m->st));
+  SMX_HIP(hipMemcpy(base + t.offset + at, &value, sizeof(float), hipMemcpyHostToDevice));
+  if (which == 0) ++m->params_epoch;
+  return SMX_OK;
+}
+
 int smx_num_bn_layers(const smx_model* m) { return m ? (int)m->bn_w.size() : 0; }
 
 int smx_get_bn(smx_model* m, int layer, int which, float* host, int32_t* width) {

@@ -437,7 +437,7 @@ static int predict_batch_stacked(smx_model* m, const PredChunk& c, const Pass& p
     d.nk = make_key(m, ST_EPS_Z, 0, false); d.rows = ids; d.cell_base = ps.cell_base; d.z = zst; d.lw = lwst;
     SMX_CHECK(launch_score_draws(m->st, d));
     const float* hl = nullptr; int hld = 0;
-    if (need_dec) SMX_CHECK(stacked_decoder(m, zst, rows, hb, 0, nullptr, &hl, &hld));
+    if (need_dec) { SMX_CHECK(stacked_decoder(m, zst, rows, hb, 0, nullptr, &hl, &hld)); m->audit_stk = {(long)R, rows, 0}; }
     PackList pl(m->st, (unsigned)std::min<size_t>(64, ((size_t)B * std::max(G, D) + 255) / 256), (unsigned)Sn, B);
     SMX_CHECK(pl.add(c.zd ? c.zd + (s0 * Cn + b0) * D : nullptr, D, zst, (size_t)Dp, D, Cn * D, (size_t)B * Dp));
     if (c.xp || c.st) {

@@ -129,9 +129,11 @@ static int stacked_scores(smx_model* m, const Pass& ps, int n_samples, const Sco
       f.gamma = P_(m, L.tGamma); f.beta = P_(m, L.tBeta); f.moving_mean = m->bn_moving + m->bn_off[L.bn]; f.moving_var = f.moving_mean + L.out_p;
       f.eps = m->cfg.bn_eps; f.leak = L.leak; f.out3 = reinterpret_cast<__bf16*>(ht);
       SMX_CHECK(launch_score_decoder1(m->st, f));
+      m->audit_stk = {(long)R, rows, 3};
     } else {
       SMX_CHECK(launch_score_draws(m->st, d));
       SMX_CHECK(stacked_decoder(m, z, rows, hb, m->scvi ? 0 : (wide_head ? 1 : 2), ht, &in, &ld));
+      m->audit_stk = {(long)R, rows, m->scvi ? 0 : (wide_head ? 1 : 2)};
     }
     if (m->scvi) {
       for (int ch = 0; ch < m->k; ++ch) {

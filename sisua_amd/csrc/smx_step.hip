@@ -685,6 +685,7 @@ int forward_pass(smx_model* m, const Pass& ps, bool with_loss, bool backward, in
   const bool no_moments = (mode == 4);                  // ... and not even the moments / draw 0: the caller reads the latent head's raw output only
   const smx_config& c = m->cfg;
   const float inv_gb = 1.f / (float)ps.global_batch;
+  m->audit_rows = ps.B;
   m->head_loss = false; m->head_fused = false; m->ev_hf_fresh = false; m->wide_dd_slabs = 0;
   m->ahead_front_eps = m->ahead_front_drop = false;
   m->scvi_fused = false; m->encl_twinned = false;
@@ -959,6 +960,7 @@ int factor_forward(smx_model* m, const Pass& ps, bool backward) {
   const smx_config& c = m->cfg;
   const int B = ps.B, B2 = 2 * ps.B;
   SMX_REQUIRE(B2 <= 2 * m->Bmax, "batch exceeds max_batch");
+  m->audit_disc_rows = B2;
   PermuteArgs pa;
   pa.z = m->z; pa.ldz = m->Dp; pa.zz = m->zz; pa.ld = m->Dp; pa.B = B; pa.D = m->D;
   pa.nk = make_key(m, ST_PERMUTE, ps.sample, ps.training != 0);
@@ -1792,6 +1794,7 @@ int launch_train(smx_model* m, int B, bool use_graph, int s_idx, int n_steps) {
       it = m->graphs.emplace(B, exec).first;
     }
     m->par = 0;
+    m->audit_rows = B; if (m->fvae) m->audit_disc_rows = 2 * B;   // (a replay runs none of the host code that records them)
     SMX_HIP(hipGraphLaunch(it->second, m->st));
   } else {
     // eager: the preparation kernel runs once per call; afterwards each optimiser kernel prepares the
@@ -1889,7 +1892,17 @@ int smx_set_optimizer(smx_model* m, int32_t rule, const float* hp, int32_t n_hp)
   // the rule starts fresh: both slot buffers whole (the SMX_SHARD_SLACK tail included), on every rank alike -- nothing is stale after this
   const long n = (long)(m->flat_count + SMX_SHARD_SLACK);
   SMX_CHECK(smx::launch_opt_fill(m->st, m->adam_m, n, 0.f));
-  SMX_CHECK(smx::launch_opt_fill(m->st, m->adam_v, n, rule == SMX_OPT_ADAGRAD ? res[0] : 0.f));
+  SMX_CHECK(smx::launch_opt_fill(m->st, m->adam_v, n, 0.f));
+  if (rule == SMX_OPT_ADAGRAD && res[0] != 0.f) {
+    // the accumulator's initial value goes into the LOGICAL elements only: the padding stays exactly zero (smx_model.h), its gradient being zero
+    std::vector<float> h((size_t)n, 0.f);
+    for (const TensorInfo& t : m->tensors)
+      for (int r = 0; r < t.rows; ++r)
+        for (int ch = 0; ch < t.chunks; ++ch)
+          std::fill_n(h.begin() + (long)(t.offset + (size_t)r * t.ld + (size_t)ch * t.chunk_wp), t.chunk_w, res[0]);
+    SMX_HIP(hipStreamSynchronize(m->st));
+    SMX_HIP(hipMemcpy(m->adam_v, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
   SMX_HIP(hipStreamSynchronize(m->st));
   m->opt_stale = false;
   m->opt_rule = rule;

@@ -757,6 +757,21 @@ class Engine:
     v = -1 if (name == "bf16x3" and not isinstance(value, bool) and int(value) < 0) else int(bool(value))
     check(self.lib.smx_set_flag(self._h, name.encode(), v))
 
+  # ---- padding audit (tests) ---------------------------------------------------------------
+  def pad_audit(self, which: int):
+    """Elements outside the logical extent of the tensors that are not exactly zero (smx_pad_audit): which 0 parameters, 1 gradients,
+    2 / 3 the optimiser's slots, 4 the work buffers of the last pass.  Returns (n_bad, name of the first offender or None, its offset)."""
+    n, t, off = C.c_int64(0), C.c_int32(-1), C.c_int64(-1)
+    name = C.create_string_buffer(64)
+    check(self.lib.smx_pad_audit(self._h, int(which), C.byref(n), C.byref(t), C.byref(off), name, 64))
+    return int(n.value), (name.value.decode() if n.value else None), int(off.value)
+
+  def pad_poke(self, which: int, tensor, value: float = 1.0):
+    """Write `value` into the first padded element of a tensor (name or index) of buffer `which` (smx_pad_poke); SmxError when the tensor
+    has no padding.  Exists to show that pad_audit sees a violation."""
+    index = self.index[tensor] if isinstance(tensor, str) else int(tensor)
+    check(self.lib.smx_pad_poke(self._h, int(which), index, float(value)))
+
   # ---- measurement ----------------------------------------------------------------------
   def timing_enable(self, kernel: Optional[str]):
     check(self.lib.smx_timing_enable(self._h, kernel.encode() if kernel else None))
