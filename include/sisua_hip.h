@@ -439,6 +439,27 @@ int smx_predict_impute_csr(smx_model* m, const float* host_x, const int64_t* ind
                            const float* original, const int64_t* o_indptr, const int32_t* o_cols, const float* o_vals, float* cell_median,
                            int32_t* cell_changed, float* global_lohi);
 
+/* GENE x PROTEIN CORRELATION SUMS (SingleCellOMIC.get_correlation, sisua/data/_single_cell_analysis.py:1199-1245: pearsonr and spearmanr of
+ * every pair) of the matrix smx_predict_stat's stat 2 returns -- same passes, same draws -- against P protein columns the caller has
+ * prepared on the host: prot_rank2 [P][n_cells] int32, 2 x the average rank of each cell within the protein's column; prot_unit
+ * [P][n_cells] float64, the column centred and scaled to unit norm.  Arguments as smx_predict_stat_cols; genes = NULL: every gene
+ * (n_sel ignored).  For selected gene j, with a = 2 x the average ranks of its column x (float32; -0 ties with +0):
+ *   sp_Sa, sp_Saa [n_sel]      sum a, sum a a             sp_Sab [n_sel][P]   sum a prot_rank2[p]     (int64, exact)
+ *   pe_mean, pe_Sxx [n_sel]    mean x, sum (x - mean)^2   pe_Sxy [n_sel][P]   sum (x - mean) prot_unit[p]   (float64, two passes, in an
+ *                                                                             order that is a function of n_cells alone)
+ *   nonfinite [n_sel]          1 where the column holds a NaN or an infinity (its other outputs are then unspecified), else 0.
+ * Spearman = (N Sab - Sa Sb) / sqrt((N Saa - Sa^2)(N Sbb - Sb^2)), Pearson = Sxy / sqrt(Sxx).  Nothing depends on the batch size, the
+ * chunking or the input form.  n_cells <= 2^20 (4 n_cells^3 < 2^63), else SMX_ERR_INVALID before any device work.  The kept columns, their
+ * ranks and the sort arrays take 16 n_cells bytes per gene: as many genes at a time as fit the knob "correlate_keep_bytes" (default: half
+ * of the free device memory), the walk being repeated once per such chunk -- same bits.  smx_predict_correlate_csr: the rows as CSR. */
+int smx_predict_correlate(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
+                          int32_t count_only, const int32_t* genes, int32_t n_sel, const int32_t* prot_rank2, const double* prot_unit, int32_t P,
+                          int64_t* sp_Sa, int64_t* sp_Saa, int64_t* sp_Sab, double* pe_mean, double* pe_Sxx, double* pe_Sxy, int32_t* nonfinite);
+int smx_predict_correlate_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                              int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, const int32_t* genes, int32_t n_sel,
+                              const int32_t* prot_rank2, const double* prot_unit, int32_t P, int64_t* sp_Sa, int64_t* sp_Saa, int64_t* sp_Sab,
+                              double* pe_mean, double* pe_Sxx, double* pe_Sxy, int32_t* nonfinite);
+
 /* Decoder only (SingleCellModel.decode, single_cell_model.py:141-151; scvi.py:108-171):
  * z [batch,D] (and l [batch] for scvi) -> the same x_params / y_params as smx_forward,
  * eval mode. */
@@ -651,6 +672,12 @@ int smx_k_plane_sample(int likelihood, int direct, int count_only, const float* 
  * [n_rows][ld] (host, ld >= G; what lies beyond G in a row is not read) -> lo, hi [n_rows].  Rows hold non-negative values or NaN (what
  * an absolute difference is); -0 counts as +0 and a NaN sorts above +inf, as np.partition orders them. */
 int smx_k_row_select(const float* rows, int32_t n_rows, int32_t G, int32_t ld, float* lo, float* hi);
+/* The column kernels of smx_predict_correlate by themselves, on host columns cols [n_cols][n_cells] (gene-major).  smx_k_col_rank2:
+ * rank2 [n_cols][n_cells] = 2 x scipy.stats.rankdata(column, 'average') and the nonfinite flags [n_cols].  smx_k_col_correlate: the ranks,
+ * then the sums, with the operands and outputs of smx_predict_correlate (n_sel = n_cols).  n_cells <= 2^20. */
+int smx_k_col_rank2(const float* cols, int32_t n_cols, int64_t n_cells, int32_t* rank2, int32_t* nonfinite);
+int smx_k_col_correlate(const float* cols, int32_t n_cols, int64_t n_cells, const int32_t* prot_rank2, const double* prot_unit, int32_t P,
+                        int64_t* sp_Sa, int64_t* sp_Saa, int64_t* sp_Sab, double* pe_mean, double* pe_Sxx, double* pe_Sxy, int32_t* nonfinite);
 
 /* ---- padding audit (test instrument; never on the path of a step) ----------- */
 /* The layout's invariant, read back from the device: every feature axis is padded to 32 and every tensor to 64 floats, and what lies

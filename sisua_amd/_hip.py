@@ -67,6 +67,7 @@ class smx_metrics(C.Structure):
 _FP = C.POINTER(C.c_float)
 _IP = C.POINTER(C.c_int32)
 _LP = C.POINTER(C.c_int64)
+_DP = C.POINTER(C.c_double)
 _VP = C.c_void_p
 
 # name -> (restype, argtypes); every symbol include/sisua_hip.h declares
@@ -127,6 +128,10 @@ SIGNATURES = {
     "smx_predict_impute": (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _IP, _FP]),
     "smx_predict_impute_csr": (C.c_int, [_VP, _FP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _LP, _IP, _FP,
                                          _FP, _IP, _FP]),
+    "smx_predict_correlate": (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _IP, C.c_int32, _IP, _DP, C.c_int32,
+                                        _LP, _LP, _LP, _DP, _DP, _DP, _IP]),
+    "smx_predict_correlate_csr": (C.c_int, [_VP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _IP, C.c_int32, _IP, _DP,
+                                            C.c_int32, _LP, _LP, _LP, _DP, _DP, _DP, _IP]),
     "smx_decode": (C.c_int, [_VP, _FP, _FP, C.c_int32, _FP, C.POINTER(_FP)]),
     "smx_dataset_library": (C.c_int, [_VP, _FP]),
     "smx_dataset_corrupt": (C.c_int, [_VP, C.c_double, C.c_double, C.c_uint64, C.POINTER(C.c_int64)]),
@@ -171,6 +176,8 @@ SIGNATURES = {
                               C.c_float, _FP, _FP]),
     "smx_k_plane_sample": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _FP]),
     "smx_k_row_select": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]),
+    "smx_k_col_rank2": (C.c_int, [_FP, C.c_int32, C.c_int64, _IP, _IP]),
+    "smx_k_col_correlate": (C.c_int, [_FP, C.c_int32, C.c_int64, _IP, _DP, C.c_int32, _LP, _LP, _LP, _DP, _DP, _DP, _IP]),
     "smx_pad_audit": (C.c_int, [_VP, C.c_int32, _LP, _IP, _LP, C.c_char_p, C.c_int32]),
     "smx_pad_poke": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_float]),
 }

@@ -253,6 +253,10 @@ struct smx_model {
   float* imp_d = nullptr; size_t imp_d_floats = 0;   // smx_predict_impute: |original - mean| of every cell [N][G] (kept form) or of one pass's rows
   unsigned long long* imp_hist = nullptr;            // ... its histograms: level 1 [2048] | levels 2 and 3 [2][1024] | NaN flag (smx_impute.hip)
   int32_t* pred_sel = nullptr; size_t pred_sel_n = 0;   // smx_predict_stat_cols: the gene indices on the device
+  // smx_predict_correlate (smx_correlate.hip): a gene chunk's kept columns | ranks | sort A | sort B, each [Gc][N] of 4 bytes (knob
+  // correlate_keep_bytes); the protein unit columns f64 [P][N] | their ranks i32 [P][N] | the chunk's sums
+  char* cor_keep = nullptr; size_t cor_keep_bytes = 0;
+  char* cor_ops = nullptr; size_t cor_ops_bytes = 0;
   float* metrics_pin = nullptr;   // pinned landing area of read_metrics: 8 ELBO scalars + one gradient norm per tensor
   float* score_pin = nullptr; size_t score_pin_floats = 0;   // pinned landing area of the scoring entry points' results (smx_scoring.hip: score_landing)
   float* mhist = nullptr; size_t mhist_cap = 0; int32_t mhist_steps = 0;   // ELBO scalars of every step of the last train_steps call
@@ -457,5 +461,23 @@ int launch_impute_rows(hipStream_t st, const ImputeRowArgs& a, int rows);
 // the histogram of bits shift .. shift + 9 of the n patterns of d whose bits under `mask` are prefix[t], t = 0, 1 -> hist [2][1024] (added)
 int launch_impute_level(hipStream_t st, const float* d, long n, const unsigned* prefix, unsigned mask, int shift, unsigned long long* hist);
 int launch_gather_cols(hipStream_t st, const float* src, long ld, long rows, const int32_t* idx, int n_sel, float* dst);
+// smx_correlate.hip: the column kernels of the correlation matrices (header there)
+#define SMX_COR_MAX_CELLS (1l << 20)   // 4 N^3 < 2^63: the integer sums of the doubled ranks cannot overflow
+struct CorrelateArgs {
+  const float* cols; const int32_t* rank2; int N, P;   // the genes' columns and their doubled average ranks [n_cols][N]
+  const int32_t* prot_rank2; const double* prot_unit;  // [P][N]: the proteins' doubled average ranks; their columns centred, unit norm
+  long long *sp_Sa, *sp_Saa, *sp_Sab;                  // [n_cols], [n_cols], [n_cols][P]
+  double *pe_mean, *pe_Sxx, *pe_Sxy;
+};
+struct CorrelateWork {   // device: the columns of n genes and what their ranks and sums need
+  float* cols; int32_t* rank2; unsigned *sortA, *sortB; const int32_t* prot_rank2; const double* prot_unit; char* sums;
+};
+struct CorrelateOut { long long *sp_Sa, *sp_Saa, *sp_Sab; double *pe_mean, *pe_Sxx, *pe_Sxy; int32_t* nonfinite; };   // host
+inline size_t correlate_sums_bytes(size_t n, size_t P) { return n * ((2 + P) * 16 + 4); }
+// rows [c0, c0 + rows) of the selected columns of src [rows][ld] -> dst [n_sel][N], gene-major
+int launch_keep_cols(hipStream_t st, const float* src, long ld, long rows, const int32_t* idx, int n_sel, float* dst, long N, long c0);
+int launch_col_rank2(hipStream_t st, const float* cols, int n_cols, long N, unsigned* sortA, unsigned* sortB, int32_t* rank2, int32_t* nonfinite);
+int launch_col_correlate(hipStream_t st, const CorrelateArgs& a, int n_cols);
+int correlate_kept(hipStream_t st, const CorrelateWork& w, int n, long N, int P, const CorrelateOut& o);
 
 }  // namespace smx

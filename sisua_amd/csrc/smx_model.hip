@@ -590,6 +590,8 @@ int smx_model_destroy(smx_model* m) {
   if (m->imp_d) hipFree(m->imp_d);
   if (m->imp_hist) hipFree(m->imp_hist);
   if (m->pred_sel) hipFree(m->pred_sel);
+  if (m->cor_keep) hipFree(m->cor_keep);
+  if (m->cor_ops) hipFree(m->cor_ops);
   if (m->score_buf) hipFree(m->score_buf);
   if (m->score_wimg) hipFree(m->score_wimg);
   if (m->score_aux) hipFree(m->score_aux);

@@ -235,6 +235,8 @@ struct StatReq {
   // of |target - mean| do (smx_impute.hip), `target` / `tcsr` being the original rows
   const int32_t* sel = nullptr; int n_sel = 0;
   int impute = 0; float* imp_median = nullptr; int32_t* imp_changed = nullptr; float* imp_lohi = nullptr;
+  // keep_cols (with sel): nothing leaves the device; the selected columns are kept gene-major [n_sel][n_cells] there (smx_correlate.hip)
+  float* keep_cols = nullptr;
 };
 
 // ---- host rows given as CSR (smx_predict_csr and kin): (indptr int64 [n + 1], cols int32, vals float32), indptr absolute ----
@@ -558,7 +560,7 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
       {&ch.zm, D, z_mean != nullptr}, {&ch.zs, DS, z_scale != nullptr}, {&ch.lm, 1, l_mean != nullptr}, {&ch.ls, 1, l_scale != nullptr},
       {&ch.zd, S * D, z_samples != nullptr}, {&ch.ld, S, l_samples != nullptr}, {&ch.xp, S * k * G, x_params != nullptr},
       {&ch.st, w_stat, w_stat > 0},
-      {&ch.sel, sr ? (size_t)sr->n_sel : 0, sr && sr->n_sel > 0}, {&ch.imed, 1, sr && sr->impute}, {&ch.ichg, 1, sr && sr->impute},
+      {&ch.sel, sr ? (size_t)sr->n_sel : 0, sr && sr->n_sel > 0 && !sr->keep_cols}, {&ch.imed, 1, sr && sr->impute}, {&ch.ichg, 1, sr && sr->impute},
       {&ch.in_raw, G, !cx}, {&ch.in_x, Gp, !cx}, {&ch.in_lib, 2, true}, {&ch.in_lgx1, 1, true},
       {&ch.y[0], S * ch.wy[0], ch.wy[0] > 0}, {&ch.y[1], S * ch.wy[1], ch.wy[1] > 0}, {&ch.y[2], S * ch.wy[2], ch.wy[2] > 0},
       {&ch.y[3], S * ch.wy[3], ch.wy[3] > 0}};
@@ -657,7 +659,8 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
     if (ch.zs) SMX_CHECK(out(z_scale + c0 * DS, ch.zs, Cn * DS));
     if (ch.lm) SMX_CHECK(out(l_mean + c0, ch.lm, Cn));
     if (ch.ls) SMX_CHECK(out(l_scale + c0, ch.ls, Cn));
-    if (ch.st && sr->stat == 2 && !impute && !ch.sel) SMX_CHECK(out(sr->out + c0 * G, ch.st, Cn * G));
+    if (ch.st && sr->keep_cols) SMX_CHECK(launch_keep_cols(m->st, ch.st, (long)G, (long)Cn, sr->sel, sr->n_sel, sr->keep_cols, (long)N, (long)c0));
+    else if (ch.st && sr->stat == 2 && !impute && !ch.sel) SMX_CHECK(out(sr->out + c0 * G, ch.st, Cn * G));
     if (ch.sel) {
       SMX_CHECK(launch_gather_cols(m->st, ch.st, (long)G, (long)Cn, sr->sel, sr->n_sel, ch.sel));
       SMX_CHECK(out(sr->out + c0 * (size_t)sr->n_sel, ch.sel, Cn * (size_t)sr->n_sel));
@@ -783,6 +786,71 @@ int smx_predict_stat_cols_csr(smx_model* m, const int64_t* indptr, const int32_t
   SMX_REQUIRE(indptr, "null indptr");
   const CsrRows cx{indptr, cols, vals};
   return predict_stat_cols(m, nullptr, &cx, host_library, n_cells, batch, n_samples, count_only, genes, n_sel, out);
+}
+
+// the correlation sums of the walk's stat 2 (smx_correlate.hip): the selected genes in chunks of Gc whose kept columns, ranks and sort arrays
+// (16 N bytes per gene) fit the knob correlate_keep_bytes; every chunk repeats the walk -- the same passes, the same bits
+static int predict_correlate(smx_model* m, const float* host_x, const CsrRows* cx, const float* host_library, int64_t n_cells, int32_t batch,
+                             int32_t n_samples, int32_t count_only, const int32_t* genes, int32_t n_sel, const int32_t* prot_rank2,
+                             const double* prot_unit, int32_t P, int64_t* sp_Sa, int64_t* sp_Saa, int64_t* sp_Sab, double* pe_mean, double* pe_Sxx,
+                             double* pe_Sxy, int32_t* nonfinite) {
+  SMX_REQUIRE(m && prot_rank2 && prot_unit && P > 0 && sp_Sa && sp_Saa && sp_Sab && pe_mean && pe_Sxx && pe_Sxy && nonfinite, "bad arguments");
+  SMX_REQUIRE(n_cells > 0 && n_cells <= SMX_COR_MAX_CELLS, "correlations take 1 .. 2^20 cells");
+  SMX_REQUIRE(!(count_only && m->cfg.likelihood == SMX_LLK_MSE), "the deterministic 'mse' output has no count distribution");
+  SMX_REQUIRE(genes ? n_sel > 0 : true, "an empty gene list");
+  const size_t n = genes ? (size_t)n_sel : (size_t)m->G, N = (size_t)n_cells, pn = (size_t)P * N;
+  std::vector<int32_t> idx(n);
+  for (size_t i = 0; i < n; ++i) {
+    idx[i] = genes ? genes[i] : (int32_t)i;
+    SMX_REQUIRE(idx[i] >= 0 && idx[i] < m->G, "gene index out of range");
+  }
+  SMX_CHECK(dgrow(m, &m->pred_sel, &m->pred_sel_n, n));
+  SMX_HIP(hipMemcpy(m->pred_sel, idx.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
+  double budget = tuning("correlate_keep_bytes", -1.0);
+  if (budget < 0.0) {
+    size_t fr = 0, tot = 0;
+    SMX_HIP(hipMemGetInfo(&fr, &tot));
+    budget = 0.5 * (double)(fr + m->cor_keep_bytes);
+  }
+  const size_t Gc = (size_t)std::min((double)n, std::max(1.0, floor(budget / (16.0 * (double)N))));
+  SMX_CHECK(dgrow(m, &m->cor_keep, &m->cor_keep_bytes, Gc * N * 16));
+  SMX_CHECK(dgrow(m, &m->cor_ops, &m->cor_ops_bytes, pn * 12 + correlate_sums_bytes(Gc, (size_t)P) + 16));
+  CorrelateWork w;
+  w.cols = reinterpret_cast<float*>(m->cor_keep); w.rank2 = reinterpret_cast<int32_t*>(w.cols + Gc * N);
+  w.sortA = reinterpret_cast<unsigned*>(w.rank2 + Gc * N); w.sortB = w.sortA + Gc * N;
+  double* d_unit = reinterpret_cast<double*>(m->cor_ops);
+  int32_t* d_rank = reinterpret_cast<int32_t*>(d_unit + pn);
+  w.prot_unit = d_unit; w.prot_rank2 = d_rank;
+  w.sums = m->cor_ops + (pn * 12 + 15) / 16 * 16;
+  SMX_HIP(hipMemcpy(d_unit, prot_unit, pn * sizeof(double), hipMemcpyHostToDevice));
+  SMX_HIP(hipMemcpy(d_rank, prot_rank2, pn * sizeof(int32_t), hipMemcpyHostToDevice));
+  for (size_t g0 = 0; g0 < n; g0 += Gc) {
+    const int gc = (int)std::min(Gc, n - g0);
+    StatReq sr;
+    sr.stat = 2; sr.count_only = count_only ? 1 : 0; sr.sel = m->pred_sel + g0; sr.n_sel = gc; sr.keep_cols = w.cols;
+    SMX_CHECK(predict_core(m, host_x, cx, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr));
+    const CorrelateOut o{reinterpret_cast<long long*>(sp_Sa) + g0, reinterpret_cast<long long*>(sp_Saa) + g0, reinterpret_cast<long long*>(sp_Sab) + g0 * (size_t)P,
+                         pe_mean + g0, pe_Sxx + g0, pe_Sxy + g0 * (size_t)P, nonfinite + g0};
+    SMX_CHECK(correlate_kept(m->st, w, gc, (long)N, P, o));
+  }
+  return SMX_OK;
+}
+
+int smx_predict_correlate(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
+                          int32_t count_only, const int32_t* genes, int32_t n_sel, const int32_t* prot_rank2, const double* prot_unit, int32_t P,
+                          int64_t* sp_Sa, int64_t* sp_Saa, int64_t* sp_Sab, double* pe_mean, double* pe_Sxx, double* pe_Sxy, int32_t* nonfinite) {
+  return predict_correlate(m, host_x, nullptr, host_library, n_cells, batch, n_samples, count_only, genes, n_sel, prot_rank2, prot_unit, P, sp_Sa,
+                           sp_Saa, sp_Sab, pe_mean, pe_Sxx, pe_Sxy, nonfinite);
+}
+
+int smx_predict_correlate_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                              int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, const int32_t* genes, int32_t n_sel,
+                              const int32_t* prot_rank2, const double* prot_unit, int32_t P, int64_t* sp_Sa, int64_t* sp_Saa, int64_t* sp_Sab,
+                              double* pe_mean, double* pe_Sxx, double* pe_Sxy, int32_t* nonfinite) {
+  SMX_REQUIRE(indptr, "null indptr");
+  const CsrRows cx{indptr, cols, vals};
+  return predict_correlate(m, nullptr, &cx, host_library, n_cells, batch, n_samples, count_only, genes, n_sel, prot_rank2, prot_unit, P, sp_Sa,
+                           sp_Saa, sp_Sab, pe_mean, pe_Sxx, pe_Sxy, nonfinite);
 }
 
 // the imputation scores of the walk's stat 2 (smx_impute.hip)

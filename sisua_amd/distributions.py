@@ -588,6 +588,54 @@ def imputation_scores_from_cells(cell_median, cell_changed, global_lohi):
           "imputation_std": float(np.std(cells)) if len(cells) > 0 else 0.0}
 
 
+def protein_operands(extras):
+  """What the device's correlation sums read of the protein matrix `extras` [N, P] (dense or scipy.sparse), prepared once in float64:
+  dict(rank2 [P, N] int32: 2 x scipy.stats.rankdata(column) -- integers; unit [P, N] float64: the column centred and scaled to unit norm
+  (zeros for a constant column); Sb, Sbb: lists of P Python integers sum b, sum b b; constant [P] bool).  A NaN or an infinity raises."""
+  from scipy.stats import rankdata
+  ex = np.asarray(extras.toarray() if _sp.issparse(extras) else extras, np.float64)
+  if ex.ndim != 2 or ex.shape[1] < 1:
+    raise ValueError(f"extras must be [cells, proteins >= 1], got {ex.shape}")
+  if not np.isfinite(ex).all():
+    raise ValueError("extras holds a NaN or an infinity")
+  cols = np.ascontiguousarray(ex.T)
+  rank2 = np.stack([np.rint(2.0 * rankdata(c)).astype(np.int32) for c in cols])
+  constant = np.array([bool((c == c[0]).all()) for c in cols])
+  unit = np.zeros_like(cols)
+  for p, c in enumerate(cols):
+    if not constant[p]:
+      d = c - c.mean()
+      unit[p] = d / np.linalg.norm(d)
+  r = rank2.astype(np.int64)
+  return dict(rank2=rank2, unit=unit, Sb=[int(v) for v in r.sum(axis=1)], Sbb=[int(v) for v in (r * r).sum(axis=1)], constant=constant)
+
+
+def correlations_from_sums(n_cells, sp_Sa, sp_Saa, sp_Sab, sp_Sb, sp_Sbb, pe_Sxx, pe_Sxy, nonfinite=None, prot_constant=None):
+  """The closing arithmetic of the gene x protein correlation matrices -> {'pearson', 'spearman'}, each [G, P] float64.
+  Spearman = (N Sab - Sa Sb) / sqrt((N Saa - Sa^2)(N Sbb - Sb^2)) from the integer sums of the doubled average ranks (a of a gene, b of a
+  protein): numerator and both factors in Python integers -- exact -- then one float64 division.  Pearson = Sxy / sqrt(Sxx), Sxy against
+  the protein column of unit norm, clipped to [-1, 1] as scipy.stats.pearsonr clips.  NaN where the gene column is non-finite or constant
+  (N Saa == Sa^2: all its ranks tie) or the protein column is constant: SciPy's answer for a constant input."""
+  N = int(n_cells)
+  obj = lambda a: np.array([int(v) for v in np.ravel(a)], dtype=object).reshape(np.shape(a))
+  Sa, Saa, Sab, Sb, Sbb = obj(sp_Sa), obj(sp_Saa), obj(sp_Sab), obj(sp_Sb), obj(sp_Sbb)
+  G, P = Sab.shape
+  da, db = N * Saa - Sa * Sa, N * Sbb - Sb * Sb   # N^2 x the variance of the ranks: 0 exactly for a constant column
+  num = N * Sab - Sa[:, None] * Sb[None, :]
+  bad = np.broadcast_to((da == 0)[:, None] | (db == 0)[None, :], (G, P)).copy()
+  if nonfinite is not None:
+    bad |= (np.asarray(nonfinite) != 0)[:, None]
+  if prot_constant is not None:
+    bad |= np.asarray(prot_constant, bool)[None, :]
+  den = (da[:, None] * db[None, :]).astype(np.float64)
+  with np.errstate(divide="ignore", invalid="ignore"):
+    spearman = num.astype(np.float64) / np.sqrt(den)
+    pearson = np.clip(np.asarray(pe_Sxy, np.float64) / np.sqrt(np.asarray(pe_Sxx, np.float64))[:, None], -1.0, 1.0)
+  spearman[bad] = np.nan
+  pearson[bad] = np.nan
+  return {"pearson": pearson, "spearman": spearman}
+
+
 # ---------------------------------------------------------------------------
 class LazyCountOutput(Distribution):
   """predict()'s gene output as a handle on the DEVICE side: the parameter planes (4 k G bytes per cell and draw: 24 KB at 1998 genes)
@@ -684,6 +732,27 @@ class LazyCountOutput(Distribution):
     device (exactly; smx_impute.hip) -- 8 bytes per cell leave it instead of 4 n_genes; the closing lines are the reference's, on the host."""
     r = self.imputation_cells(original)
     return imputation_scores_from_cells(r["cell_median"], r["cell_changed"], r["global_lohi"])
+
+  def correlation_sums(self, operands, genes=None):
+    """What the device reduces for `correlation` (Engine.predict_correlate) against `protein_operands(extras)`; on a zero-inflated output
+    the count distribution's mean is correlated, as `metrics.CorrelationScores` does."""
+    if operands["rank2"].shape[1] != self._x.shape[0]:
+      raise ValueError(f"extras must have the prediction's {self._x.shape[0]} cells, got {operands['rank2'].shape[1]}")
+    count_only = self._count_only or self.is_zero_inflated
+    return self._engine().predict_correlate(self._x, operands["rank2"], operands["unit"], library=self._lib, n_samples=max(self._S, 1),
+                                            batch=self._B, count_only=count_only, genes=genes)
+
+  def correlation(self, extras, genes=None):
+    """The gene x protein correlation matrices of SingleCellOMIC.get_correlation (_single_cell_analysis.py:1199-1245: pearsonr and
+    spearmanr of every pair) between `mean_over_samples()` of this prediction and the protein levels `extras` [n_cells, P] (dense or
+    scipy.sparse; a NaN raises ValueError): {'pearson': [G', P], 'spearman': [G', P]} float64, G' = all genes or the list `genes` (any
+    order, repeats allowed).  The ranks and every sum over the cells are computed on the device (smx_correlate.hip) -- Spearman exactly,
+    from integer sums -- and 16 + 16 P bytes per gene leave it instead of 4 n_cells; the closing division is `correlations_from_sums`.  A
+    gene whose column is constant or not finite, and a constant protein, give NaN."""
+    ops = protein_operands(extras)
+    r = self.correlation_sums(ops, genes)
+    return correlations_from_sums(self._x.shape[0], r["sp_Sa"], r["sp_Saa"], r["sp_Sab"], ops["Sb"], ops["Sbb"], r["pe_Sxx"], r["pe_Sxy"],
+                                  r["nonfinite"], ops["constant"])
 
   def log_prob(self, x=None):
     """log p(x) summed over the genes, [n_samples, n_cells] ([n_cells] without a draw axis); x = None: of the input counts.  x may be

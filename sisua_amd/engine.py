@@ -582,6 +582,31 @@ class Engine:
       check(self.lib.smx_predict_impute(self._h, _fp(xa), _fp(la), N, B, S, int(bool(count_only)), _fp(oa), *res))
     return dict(cell_median=med, cell_changed=chg, global_lohi=lohi)
 
+  def predict_correlate(self, x, prot_rank2, prot_unit, library=None, n_samples: int = 1, batch: Optional[int] = None, count_only: bool = False,
+                        genes=None):
+    """The correlation sums of predict_stat(x, 'mean_over_samples') against P prepared protein columns, reduced on the device
+    (smx_predict_correlate): prot_rank2 [P, N] int32 (doubled average ranks), prot_unit [P, N] float64 (centred, unit norm).  Returns
+    dict(sp_Sa, sp_Saa [G'] int64, sp_Sab [G', P] int64, pe_mean, pe_Sxx [G'] float64, pe_Sxy [G', P] float64, nonfinite [G'] int32) for
+    the genes asked for (None: all) -- `distributions.correlations_from_sums` closes them.  x may be scipy.sparse; the bits do not depend
+    on that, on the batch size or on the chunking.  More than 2^20 cells: the library refuses (SmxError)."""
+    cfg = self.cfg
+    G = cfg.n_genes
+    xa = _csr3(x, G) if _sparse(x) else _f32(x)
+    N, S = (xa[0].size - 1 if isinstance(xa, tuple) else xa.shape[0]), int(n_samples)
+    if not isinstance(xa, tuple) and (xa.ndim != 2 or xa.shape[1] != G):
+      raise ValueError(f"expected rows [n_cells, {G}], got {xa.shape}")
+    idx = None if genes is None else gene_indices(genes, G)
+    pr, pu = _col_operands(prot_rank2, prot_unit, N)
+    B = min(int(batch or self.max_batch), self.max_batch)
+    la = None if library is None else _f32(library, (N, 2))
+    out, res = _col_outputs(G if idx is None else idx.size, pr.shape[0])
+    sel = (None, 0) if idx is None else (_ip(idx), idx.size)
+    if isinstance(xa, tuple):
+      check(self.lib.smx_predict_correlate_csr(self._h, *_csr_ptrs(xa), _fp(la), N, B, S, int(bool(count_only)), *sel, _ip(pr), _dp(pu), pr.shape[0], *res))
+    else:
+      check(self.lib.smx_predict_correlate(self._h, _fp(xa), _fp(la), N, B, S, int(bool(count_only)), *sel, _ip(pr), _dp(pu), pr.shape[0], *res))
+    return out
+
   def decode(self, z, l=None):
     """Decoder + output heads from given latents (eval mode)."""
     cfg = self.cfg
@@ -887,6 +912,52 @@ def k_row_select(rows, n_genes: Optional[int] = None):
   lo, hi = np.empty((n,), np.float32), np.empty((n,), np.float32)
   check(lib.smx_k_row_select(_fp(r), n, G, ld, _fp(lo), _fp(hi)))
   return lo, hi
+
+
+def _ip(a):
+  return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _dp(a):
+  return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _col_operands(prot_rank2, prot_unit, N):
+  pr, pu = np.ascontiguousarray(prot_rank2, dtype=np.int32), np.ascontiguousarray(prot_unit, dtype=np.float64)
+  if pr.ndim != 2 or pr.shape[0] < 1 or pr.shape[1] != N or pu.shape != pr.shape:
+    raise ValueError(f"prot_rank2 and prot_unit must both be [P >= 1, {N}], got {pr.shape} and {pu.shape}")
+  return pr, pu
+
+
+def _col_outputs(n, P):
+  """The result arrays of the correlation sums for n genes and P proteins, and their pointers in the order of smx_predict_correlate's outputs"""
+  out = dict(sp_Sa=np.empty((n,), np.int64), sp_Saa=np.empty((n,), np.int64), sp_Sab=np.empty((n, P), np.int64),
+             pe_mean=np.empty((n,), np.float64), pe_Sxx=np.empty((n,), np.float64), pe_Sxy=np.empty((n, P), np.float64),
+             nonfinite=np.empty((n,), np.int32))
+  lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+  return out, (lp(out["sp_Sa"]), lp(out["sp_Saa"]), lp(out["sp_Sab"]), _dp(out["pe_mean"]), _dp(out["pe_Sxx"]), _dp(out["pe_Sxy"]),
+               _ip(out["nonfinite"]))
+
+
+def k_col_rank2(cols):
+  """smx_k_col_rank2: cols [n_cols, N] (gene-major) -> (rank2 [n_cols, N] int32 = 2 x the average ranks of every column, nonfinite [n_cols] int32)"""
+  lib = _hip.require_gpu()
+  c = _f32(cols)
+  n, N = c.shape
+  rank2, nonfinite = np.empty((n, N), np.int32), np.empty((n,), np.int32)
+  check(lib.smx_k_col_rank2(_fp(c), n, N, _ip(rank2), _ip(nonfinite)))
+  return rank2, nonfinite
+
+
+def k_col_correlate(cols, prot_rank2, prot_unit):
+  """smx_k_col_correlate: the kernels of Engine.predict_correlate on host columns cols [n_cols, N] -> its dict of sums"""
+  lib = _hip.require_gpu()
+  c = _f32(cols)
+  n, N = c.shape
+  pr, pu = _col_operands(prot_rank2, prot_unit, N)
+  out, res = _col_outputs(n, pr.shape[0])
+  check(lib.smx_k_col_correlate(_fp(c), n, N, _ip(pr), _dp(pu), pr.shape[0], *res))
+  return out
 
 
 def k_noise(seed, stream, step, cell_ids, width, p=0.0, sample=0):

@@ -1,5 +1,6 @@
 """Evaluation metrics of a fitted model as plain callables `metric(model) -> dict` (the reference's training-time metrics,
-sisua/analysis/sc_metrics.py:244-348, without its callback machinery): `ImputationError` and `CorrelationScores`.  What needs the
+sisua/analysis/sc_metrics.py:244-348, without its callback machinery): `ImputationError` and `CorrelationScores`; and the views of the full gene x protein
+matrices of `SingleCellModel.correlation` that the reference's analysis reads (`correlation_list`, `marker_correlations`).  What needs the
 [cells, genes] mean of the gene output is reduced on the device (smx_impute.hip); the correlations over a few marker columns are SciPy's,
 called as the reference calls them."""
 from __future__ import annotations
@@ -77,3 +78,30 @@ class CorrelationScores:
       pearson.append(-pearsonr(cols[:, j], self.extras[:, p])[0])
     return {"pearson_mean": float(np.mean(pearson)), "spearman_mean": float(np.mean(spearman)),
             "pearson_med": float(np.median(pearson)), "spearman_med": float(np.median(spearman))}
+
+
+def correlation_list(pearson, spearman) -> List[Tuple[int, int, float, float]]:
+  """`SingleCellOMIC.get_correlation`'s return (_single_cell_analysis.py:1199-1245) from the two [G, P] matrices: (gene index, protein
+  index, pearson, spearman) of every pair, sorted by decreasing average of the two (the reference's `sorted(...)[::-1]`: among equal averages the later pair first); pairs whose
+  average is NaN go last, in index order."""
+  pe, sp = np.asarray(pearson, np.float64), np.asarray(spearman, np.float64)
+  if pe.ndim != 2 or pe.shape != sp.shape:
+    raise ValueError(f"pearson and spearman must be the same [genes, proteins], got {pe.shape} and {sp.shape}")
+  avg = ((pe + sp) / 2.0).ravel()
+  nan = np.isnan(avg)
+  order = np.concatenate([np.flatnonzero(~nan)[np.argsort(avg[~nan], kind="stable")[::-1]], np.flatnonzero(nan)])
+  P = pe.shape[1]
+  return [(int(i // P), int(i % P), float(pe.flat[i]), float(sp.flat[i])) for i in order]
+
+
+def marker_correlations(matrix, kind: str, gene_names: Sequence[str], protein_names: Sequence[str], markers: Mapping[str, str]) -> Dict[str, float]:
+  """`Posterior._matrix_scores` (posterior.py:996-1024) of a 'pearson' or 'spearman' matrix [genes, proteins]: {f"{kind}_{gene}_{protein}":
+  matrix[gene, protein]} for every protein of `markers` (protein name -> marker gene name, supplied by the caller) whose two names are known."""
+  if kind not in ("pearson", "spearman"):
+    raise NotImplementedError(f"No support for score_type='{kind}'")
+  m = np.asarray(matrix, np.float64)
+  if m.shape != (len(gene_names), len(protein_names)):
+    raise ValueError(f"matrix must be [{len(gene_names)}, {len(protein_names)}], got {m.shape}")
+  var1 = {str(n): i for i, n in enumerate(gene_names)}
+  var2 = {str(n): i for i, n in enumerate(protein_names)}
+  return {f"{kind}_{g}_{p}": float(m[var1[str(g)], var2[str(p)]]) for p, g in markers.items() if str(g) in var1 and str(p) in var2}

@@ -959,6 +959,15 @@ class SingleCellModel:
     [cells, genes] mean never reaches the host.  Arguments as `posterior_llk` (dense or scipy.sparse, SCVI library default)."""
     return self._imputation_handle(corrupted, library, sample_shape, batch_size).imputation_scores(_rows(_flatten(original)[0]))
 
+  def correlation(self, inputs, extras, library=None, sample_shape=10, batch_size=128, genes=None):
+    r"""The gene x protein Pearson and Spearman matrices of `SingleCellOMIC.get_correlation` (data/_single_cell_analysis.py:1199-1245; what
+    `Posterior.cal_pearson` / `cal_spearman` / `get_correlation_matrix` read) between the imputed expression -- cells predicted from
+    `inputs` with `sample_shape` draws, the mean of the count distribution averaged over the draws -- and the protein levels `extras`
+    [cells, proteins]: {'pearson': [G', P], 'spearman': [G', P]} float64 (`genes`: a list of gene indices, default all).  Ranks and sums
+    are reduced on the device (`smx_predict_correlate`); the [cells, genes] mean never reaches the host."""
+    ex = extras.numpy() if isinstance(extras, SingleCellOMIC) else extras
+    return self._imputation_handle(inputs, library, sample_shape, batch_size).correlation(ex, genes=genes)
+
   def _imputation_handle(self, corrupted, library, sample_shape, batch_size):
     x_cor = self._check_inputs(_rows(_flatten(corrupted)[0]))
     S = int(np.prod(sample_shape)) if np.size(sample_shape) else 1
