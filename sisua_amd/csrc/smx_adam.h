@@ -2,7 +2,7 @@
 // flat buffer),
 // shared by the optimiser launch (smx_adam.hip), by the launches that carry chunks as riders -- the BatchNorm-backward kernels
 // (smx_bn.hip) and the latent head's backward product (smx_gemm.hip) -- and by the heads' background sweep on the second stream
-// (adam_sweep_body; smx_step.hip: head_sweep_*).  Also the bodies of the ELBO scalars and of the sum-of-squares reductions, which
+// (adam_sweep_body; smx_backward.hip: head_sweep_*).  Also the bodies of the ELBO scalars and of the sum-of-squares reductions, which
 // ride on the optimiser's and the BatchNorm-backward launches (metrics_body, sq_reduce_body).
 #pragma once
 #include "smx_device.h"

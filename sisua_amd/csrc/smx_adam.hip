@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void adam_update_kernel(AdamArgs a) {
   }
 }
 
-// the heads' update as a background sweep beside the launches that follow the output head (smx_step.hip: head_sweep_*): a FIXED
+// the heads' update as a background sweep beside the launches that follow the output head (smx_backward.hip: head_sweep_*): a FIXED
 // number of workgroups walk the chunks, so the sweep never holds more than a few wave slots per CU and the small dependent
 // launches of the main stream are placed at once
 template <int NT, bool ALL>

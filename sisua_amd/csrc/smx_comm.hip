@@ -94,7 +94,7 @@ bool dp_active(const smx_model* m) {
 // model's stream.  Taken from SMX_DP_BUCKETS_MIN_BYTES of head gradients (3 MB: BASELINE configs[1] sits right at it) unless
 // SMX_DP_BUCKETS says 1 or 2.  Round 4's form -- BOTH buckets on the communication stream, the optimiser behind an event of that stream --
 // cost +32-35 us on ONE rank (profiles/r04_dp_overhead_one_rank.txt): two cross-queue hops (main -> comm -> main) on the critical path of
-// every step.  Since round 5 the two-bucket step is a CHAIN (smx_step.hip: dp_chain_start): head bucket all-reduce -> its norms -> the
+// every step.  Since round 5 the two-bucket step is a CHAIN (smx_backward.hip: dp_chain_start): head bucket all-reduce -> its norms -> the
 // heads' clip + Adam, all on the communication stream and joined in front of the NEXT step's output head; the main stream all-reduces the
 // front bucket itself and never waits for the other queue inside a step.
 bool dp_overlap(const smx_model* m) {
@@ -314,7 +314,7 @@ int smx_comm_init_local(smx_model* const* models, int n) {
     const size_t need = std::max(m->grads_count + (size_t)m->n_chunks, (size_t)n * 2 * (size_t)wmax);
     SMX_CHECK(dgrow(m, &m->local_scratch, &m->local_scratch_cap, need));
     SMX_CHECK(ensure_sync_buf(m));
-    SMX_CHECK(ensure_comm_stream(m));   // (the chained two-bucket form runs on the loopback too: smx_step.hip, dp_chain_start)
+    SMX_CHECK(ensure_comm_stream(m));   // (the chained two-bucket form runs on the loopback too: smx_backward.hip, dp_chain_start)
   }
   return SMX_OK;
 }

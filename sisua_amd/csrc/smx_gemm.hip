@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256) void gemm_latent_bwd_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) float smem[GemmSmem<1, 1, 4, 0, 1>::FLOATS];
   gemm_body<1, 1, 4, 0, 1, 0, 2>(g, blockIdx.x, blockIdx.y, blockIdx.z, smem);
 }
-// ... and with optimiser chunks riding along (the heads' update at a wide gene panel, smx_step.hip: attach_early_adam): workgroups
+// ... and with optimiser chunks riding along (the heads' update at a wide gene panel, smx_backward.hip: attach_early_adam): workgroups
 // [gx, gx + ride_count) of row 0 each apply one chunk; the product's own 4 workgroups leave the chip idle for ~6 us otherwise
 __global__ __launch_bounds__(256) void gemm_latent_bwd_ride_kernel(GemmArgs g, AdamArgs a, int gx, int ride_first) {
   __shared__ __attribute__((aligned(16))) float smem[GemmSmem<1, 1, 4, 0, 1>::FLOATS];

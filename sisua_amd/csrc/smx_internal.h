@@ -338,7 +338,7 @@ struct BnBwdArgs {
   // fold_dz (round 6; with front, fK = 64 = 2 Dp, at most 128 cells, a first decoder layer of 128 units): the launch computes fD ITSELF --
   // d z = zD zW^T (zD [B][128]: d pre-activation of the first decoder layer, zW [Dp = 32][128]: its weights) as bf16 x 3 MFMAs and the
   // latent head's backward (zlb: what gemm_latent_bwd_kernel's epilogue did) on it, in every workgroup; workgroup 0 also stores d lat for
-  // the weight-gradient launch.  One launch of the chain less (smx_step.hip: backward_pass).
+  // the weight-gradient launch.  One launch of the chain less (smx_backward.hip: backward_pass).
   int fold_dz = 0; const float* zD = nullptr; int zld = 0; const float* zW = nullptr; int zldw = 0; EpiLatentBwd zlb;
   int diag = 0;   // SMX_BN_DIAG bits 16 / 32 / 64: skip the front's dot products / tile load / W row load (timing only)
   float leak = 0.f;   // slope of the activation for out <= 0 (layers without dropout only)
@@ -635,7 +635,7 @@ int launch_bigk_reduce(hipStream_t st, const float* part, long slab_stride, int 
 #define SMX_HEAD_FUSED_MIN_GENES 4096
 int head_fused_min_genes();   // (knob head_fused_min_genes; smx_headfused.hip)
 #define SMX_HEAD_FUSED_MAX_CELLS 256   // (one launch per 128 cells)
-// the heads' background optimiser sweep (smx_step.hip: head_sweep_start): from this many 4096-float chunks of head parameters, one persistent
+// the heads' background optimiser sweep (smx_backward.hip: head_sweep_start): from this many 4096-float chunks of head parameters, one persistent
 // workgroup per so many chunks.  Measured at 128 x 20 000 (1880 chunks; c5-shard, us per step; 182.3 without), by workgroups: 48 -> 245,
 // 64 -> 176-215 (the next output head waits for the sweep), 96 -> 178-182, 128 -> 175.3-176.3, 160 -> 177.5-181, 192 -> 176.8, 256 -> 182.2,
 // 512 -> 185.7, 1024 -> 191.1 (the small dependent launches beside it slow down by more than it hides)

@@ -153,7 +153,7 @@ struct smx_model {
   struct Flags {
     int head_loss = tuning_on("no_head_loss") ? 0 : 1;    // output product + likelihood in one kernel
     int head_fused = tuning_on("no_head_fused") ? 0 : 1;  // wide panels: ... and both of the head's backward products in the same launch (smx_headfused.hip)
-    int head_sweep = tuning_on("no_head_sweep") ? 0 : 1;  // wide panels, one GPU, eager steps: the heads' optimiser update as a background sweep on a second stream (smx_step.hip)
+    int head_sweep = tuning_on("no_head_sweep") ? 0 : 1;  // wide panels, one GPU, eager steps: the heads' optimiser update as a background sweep on a second stream (smx_backward.hip)
     int front = tuning_on("no_front") ? 0 : 1;            // latent sample + first decoder product inside BatchNorm-forward
     int bwd_front = tuning_on("no_bwd_front") ? 0 : 1;    // d h inside BatchNorm-backward, weight gradients grouped at the end
     int head_bwd = tuning_on("no_head_bwd") ? 0 : 1;      // both backward products of the output head in one wide launch
@@ -166,7 +166,7 @@ struct smx_model {
     // training products of the output head (fused head, its backward, the encoder's weight gradient) from bf16 MFMAs on
     // three-way split operands: 1 always, 0 never (the exact-f32 MFMA forms), -1 from the width (SMX_BF16X3_MIN_WORK)
     int bf16x3 = -1;
-    // data parallel, chained two-bucket form: the heads' optimiser state SHARDED over the ranks (smx_step.hip: dp_chain_start) -- reduce-scatter of
+    // data parallel, chained two-bucket form: the heads' optimiser state SHARDED over the ranks (smx_backward.hip: dp_chain_start) -- reduce-scatter of
     // the head bucket, clip + Adam on this rank's 1 / world slice, all-gather of the updated parameters.  Off by default (the north star: one all-reduce).
     int opt_shard = 0;
   int tie_mixtures = 0, tie_loc = 0, tie_scale = 0;   // SCALE (scale.py:29-33): the prior's mixture weights fixed / one location / one scale for every component
@@ -180,7 +180,7 @@ struct smx_model {
   int adam_ride_b = 0;                // wide panels: this many of the waiting chunks go with the latent head's backward product
   int adam_rest_from = 0, adam_rest_to = 0;   // ... and [adam_rest_from, adam_rest_to) wait for the next BatchNorm-backward launch to carry them
   // wide panels, one GPU, eager steps: the heads' update as a background sweep on a second stream between this step's output head and
-  // the next step's (smx_step.hip: head_sweep_start / head_sweep_join)
+  // the next step's (smx_backward.hip: head_sweep_start / head_sweep_join)
   hipStream_t st_side = nullptr;
   hipEvent_t ev_hf = nullptr, ev_sweep = nullptr; int ev_mode = -1;   // (ev_mode: created with 1 / without 0 the system-scope fence: head_sweep_prepare)
   bool sweep_pending = false;          // the main stream has not been ordered behind the last sweep yet
@@ -311,8 +311,8 @@ struct smx_model {
   hipStream_t st_comm = nullptr; hipEvent_t ev_c1 = nullptr, ev_c2 = nullptr, ev_c3 = nullptr;
   size_t bucket1_off = 0, bucket1_count = 0;   // gradients of the output / label heads: ready first, reduced early
   bool bucket1_in_flight = false;
-  bool fold_dz_now = false;      // this backward pass: the d z product + latent backward run inside the encoder's BatchNorm-backward launch (smx_step.hip)
-  bool chain_started = false;    // this step's head bucket went: all-reduce -> norms -> clip + Adam sweep on the communication stream (smx_step.hip: dp_chain_start)
+  bool fold_dz_now = false;      // this backward pass: the d z product + latent backward run inside the encoder's BatchNorm-backward launch (smx_backward.hip)
+  bool chain_started = false;    // this step's head bucket went: all-reduce -> norms -> clip + Adam sweep on the communication stream (smx_backward.hip: dp_chain_start)
   // padding audit (smx_pad_audit, which = 4): rows of the last pass (stacked draws included), of the last discriminator pass, and the
   // layout the last stacked evaluation decoder used (set by its two callers, smx_predict.hip / smx_scoring.hip)
   int audit_rows = 0, audit_disc_rows = 0; AuditStacked audit_stk;
@@ -424,13 +424,110 @@ bool dp_overlap(const smx_model* m);
 int dp_allreduce_buf(smx_model* m, float* buf, size_t count, hipStream_t st, bool second = false);   // second: the heads' bucket (its own communicator / scratch)
 int dp_allreduce(smx_model* m, size_t off, size_t count, hipStream_t st, bool second = false);
 bool dp_chain_ok(const smx_model* m);
-// smx_step.hip
-// mode: 0 full forward; 1 decoder only (z given in m->z); 2 resample (encoder outputs m->latbuf / m->latlbuf kept,
-// only the latent draw and everything after it run again); 3 encoders + latent moments only
-int forward_pass(smx_model* m, const Pass& ps, bool with_loss, bool backward, int mode = 0);
+// ---- shared by smx_forward.hip / smx_backward.hip / smx_step.hip ----
+// SyncBatchNorm applies to training passes of a data-parallel job only (eval mode uses the moving statistics)
+inline bool sync_bn_on(const smx_model* m, int training) { return m->sync_bn && training && m->cfg.batchnorm && dp_active(m); }
+inline BnSyncArgs sync_args(smx_model* m) { BnSyncArgs y; y.gather = m->sync_buf; y.rank = m->rank; y.world = m->world; return y; }
+// the KL weight of a launch of this pass: a training step reads its own beta from its state (the schedule table's entry, so a captured graph
+// replays each step's weight); an eval pass takes beta at the model's step by value
+inline KlWeight kl_weight(smx_model* m, const Pass& ps, float scale, int div) {
+  KlWeight w{nullptr, 0.f, scale, div};
+  if (ps.training) w.beta_ptr = &cur_state(m)->beta;
+  else w.beta = sched_beta(m, m->h_next);
+  return w;
+}
+// a stream of the draw side (the latent draws, the decoder's dropout): row r of a stacked pass takes sample index r / draw_rows
+inline NoiseKey draw_key(smx_model* m, int stream, const Pass& ps) {
+  NoiseKey nk = make_key(m, stream, ps.sample, ps.training != 0);
+  nk.draw_rows = (uint32_t)ps.draw_rows;
+  return nk;
+}
+// where a latent draw of this pass takes its noise from (LatentArgs, MixLatArgs, LatentTrilArgs: the same five members)
+template <typename A>
+inline void latent_noise(smx_model* m, const Pass& ps, A& a) {
+  a.nk = draw_key(m, ST_EPS_Z, ps); a.rows = ps.rows; a.cell_base = ps.cell_base;
+  if (const Injected* ij = inj(m, ST_EPS_Z)) { a.inj_eps = ij->d; a.inj_ld = ij->ld; }
+}
+// the model's products run from bf16 MFMAs on three-way split operands (flag "bf16x3": -1 = by size, SMX_BF16X3_MIN_WORK)
+inline bool b3_on(const smx_model* m, int B) {
+  return m->flags.bf16x3 < 0 ? use_bf16x3((long)B * m->Gp * m->k) : m->flags.bf16x3 != 0;
+}
+// the sum-of-squares partials of the product that writes the gradient of tensor t (NULL: none kept) ...
+inline float* sq_part_of(smx_model* m, int t) {
+  return (m->sq_slots && !tuning_on("no_sq_partials")) ? m->sq_slots + m->sq_first[(size_t)t] : nullptr;   // read per call: tests toggle it
+}
+// ... asked of that product
+inline void want_sq(smx_model* m, GemmArgs& g, int t) {
+  if (!(g.sq_part = sq_part_of(m, t))) return;
+  g.sq_count = &m->sq_count[(size_t)t];
+}
+// The three products of a dense layer or head (Mat: a row-major operand and its pitch).  Sites that need more -- split_k, tile, the gather
+// transform, a raw plane's pitch -- set it on the result.
+struct Mat { const float* p; int ld; Mat(const float* p_, long ld_) : p(p_), ld((int)ld_) {} };
+// forward: Y [M][N] = H [M][K] W + bias
+inline GemmArgs dense_fwd(Mat H, Mat W, float* Y, int ldy, const float* bias, int M, int N, int K) {
+  GemmArgs g;
+  g.A = H.p; g.lda = H.ld; g.B = W.p; g.ldb = W.ld; g.C = Y; g.ldc = ldy; g.bias = bias; g.M = M; g.N = N; g.K = K;
+  return g;
+}
+// weight and bias gradient of tensor tW: dW [M][N] = H^T dY over K rows (H stored [K][M]), db = the column sums of dY (NULL: not taken)
+inline GemmArgs dense_wgrad(smx_model* m, Mat H, Mat dY, int tW, float* db, int M, int N, int K) {
+  GemmArgs g;
+  g.A = H.p; g.lda = H.ld; g.a_kmajor = 1; g.B = dY.p; g.ldb = dY.ld; g.C = G_(m, tW); g.ldc = m->tensors[tW].ld; g.colsum = db;
+  g.M = M; g.N = N; g.K = K;
+  want_sq(m, g, tW);
+  return g;
+}
+// input gradient: dH [M][N] = dY [M][K] W^T (W stored [N][K]) as split-K slabs of M x N from `slabs` on
+inline GemmArgs dense_dgrad(Mat dY, Mat W, float* slabs, int M, int N, int K) {
+  GemmArgs g;
+  g.A = dY.p; g.lda = dY.ld; g.B = W.p; g.ldb = W.ld; g.b_nmajor = 1; g.C = slabs; g.ldc = N; g.slab_stride = (long)M * N;
+  g.M = M; g.N = N; g.K = K;
+  return g;
+}
+// the A operand of g is X: gathered by the pass's rows, log1p and input dropout on the way in (an encoder's first layer and its weight gradient)
+inline void x_gather(smx_model* m, const Pass& ps, GemmArgs& g) {
+  g.use_xform = 1;
+  g.xf.rows = ps.xrows; g.xf.u16 = ps.x_u16; g.xf.log1p = m->cfg.log_norm; g.xf.cell_base = ps.cell_base;
+  if (ps.training && m->cfg.input_dropout > 0.f) {
+    g.xf.drop_p = m->cfg.input_dropout; g.xf.drop_scale = 1.f / (1.f - m->cfg.input_dropout);
+    g.xf.nk = make_key(m, ST_INPUT_DROPOUT, ps.sample, true);
+    if (const Injected* ij = inj(m, ST_INPUT_DROPOUT)) { g.xf.inj_mask = ij->d; g.xf.inj_ld = ij->ld; }
+  }
+}
+// the scvi head over the raw planes (forward; its backward adds the gradients' buffers)
+inline ScviHeadArgs scvi_head_args(smx_model* m, const Pass& ps) {
+  ScviHeadArgs sh;
+  sh.raw = m->raw; sh.planes = m->P; sh.ld = (long)m->k * m->Gp; sh.plane_stride = m->Gp; sh.B = ps.B; sh.G = m->G; sh.Gp = m->Gp;
+  sh.k = m->k; sh.l = m->lsmp; sh.clip_library = m->cfg.clip_library; sh.rho_raw = m->rho;
+  return sh;
+}
+
+// smx_forward.hip
+// What a forward pass covers:
+//   Full        encoders, latent heads and draw, decoder, output and label heads
+//   DecodeOnly  the decoder and the heads only (z given in m->z, scvi: the library sample in m->lsmp)
+//   Resample    the encoders' outputs m->latbuf / m->latlbuf are kept: only the latent draw and everything after it run again
+//   EncodeOnly  encoders + latent heads + latent moments / draw 0, no decoder (the stacked-draw paths)
+//   EncodeRaw   ... and not even the moments / draw 0: the caller reads the latent head's raw output m->latbuf only (the SCALE prior's and the
+//               mixture posterior's launches still run)
+enum class Fwd { Full, DecodeOnly, Resample, EncodeOnly, EncodeRaw };
+// ... and what it is for: the outputs alone, the ELBO scalars of an evaluation, or a training step (gradients of the losses for backward_pass)
+enum class Loss { None, Eval, Train };
+int forward_pass(smx_model* m, const Pass& ps, Loss loss, Fwd mode = Fwd::Full);
+int factor_forward(smx_model* m, const Pass& ps, bool backward);
+bool use_head_loss(const smx_model* m, int B);
+// smx_backward.hip
 int backward_pass(smx_model* m, const Pass& ps);
-int optimizer_pass(smx_model* m);
+int factor_backward(smx_model* m, const Pass& ps);
+// the heads' optimiser update beside the backward chain: as a background sweep on a second stream, as the data-parallel chain
+bool head_sweep_ok(smx_model* m);
+int head_sweep_prepare(smx_model* m);
 int head_sweep_join(smx_model* m);
+int dp_chain_start(smx_model* m);
+// smx_step.hip
+void fill_adam_args(smx_model* m, AdamArgs& a);
+int optimizer_pass(smx_model* m);
 int csr_stage(smx_model* m, Pass& ps);
 int check_rows(smx_model* m, const int32_t* ids, size_t n);
 int read_metrics(smx_model* m, smx_metrics* out);
@@ -438,11 +535,12 @@ int read_metrics(smx_model* m, smx_metrics* out);
 struct CsrRows { const int64_t* indptr; const int32_t* cols; const float* vals; };
 int check_csr_rows(const CsrRows& c, size_t n, int G);
 int csr_host_rows(smx_model* m, const CsrRows& c, size_t r0, size_t n, void* out, float* lgx1, int u16 = 0);
-int setup_pass(smx_model* m, Pass& ps, const int32_t* row_ids, const float* host_x, const float* host_library,
-               int32_t batch, int training, int sample, int draw_rows = 0);   // draw_rows > 0: row_ids are stacked draws (up to Rmax rows)
+// the cells of a pass: resident rows by id, or host rows x [batch][G] with their library prior [batch][2] (scvi)
+struct CellSrc { const int32_t* row_ids; const float* host_x; const float* host_library; };
+int setup_pass(smx_model* m, Pass& ps, const CellSrc& src, int32_t batch, int training, int sample, int draw_rows = 0);   // draw_rows > 0: row_ids are stacked draws (up to Rmax rows)
 // smx_predict.hip
 bool stacked_scoring_ok(const smx_model* m);
-bool head_fused_ok(const smx_model* m, int B);   // a training step of B cells takes the one-launch output head (smx_step.hip)
+bool head_fused_ok(const smx_model* m, int B);   // a training step of B cells takes the one-launch output head (smx_forward.hip)
 int stacked_decoder(smx_model* m, const float* z, long rows, float* const* hb, int last_form, float* ht, const float** out, int* out_ld);
 // smx_impute.hip: the selection kernels of the imputation scores (header there)
 #define SMX_IMP_L1_BINS 2048   // level 1 of the global selection: bits 30..20 of the pattern

@@ -254,7 +254,7 @@ int alloc_rows(smx_model* m, size_t R) {
   return SMX_OK;
 }
 
-// The capacities the routing predicates of smx_step.hip read (slab / bigk scratch, the tril prior's partials), for `rows` rows of a
+// The capacities the routing predicates of smx_forward.hip and smx_backward.hip read (slab / bigk scratch, the tril prior's partials), for `rows` rows of a
 // pass -- max_batch at one draw, draws x max_batch otherwise -- not the allocation's: an engine grown for several draws and set back to
 // one routes exactly as a fresh engine.  rows <= Rmax.
 void set_row_caps(smx_model* m, size_t rows) {
@@ -905,7 +905,7 @@ int64_t smx_loss_bytes_per_cell(const smx_model* m) {
   return (int64_t)(4 + 8 * m->k) * m->G + 16 * (int64_t)m->D + 4;
 }
 
-// (forward_pass's own predicate, smx_step.hip: head_fused_ok)
+// (forward_pass's own predicate, smx_forward.hip: head_fused_ok)
 int64_t smx_head_fused_bytes(const smx_model* m, int32_t batch) {
   if (!m || batch <= 0 || m->dec.empty()) return 0;
   return head_fused_ok(m, batch) ? (int64_t)head_fused_bytes(batch, m->G, m->Gp, m->k) : 0;

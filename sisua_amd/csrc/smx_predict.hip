@@ -413,7 +413,7 @@ static int add_latent_moments(smx_model* m, PackList& pl, const PredChunk& c, si
 static int predict_batch_stacked(smx_model* m, const PredChunk& c, const Pass& ps, size_t b0, const int32_t* ids, bool need_dec) {
   const int B = ps.B, Dp = m->Dp;
   const size_t S = c.S, Cn = c.Cn, G = (size_t)m->G, D = (size_t)m->D, k = (size_t)m->k;
-  SMX_CHECK(forward_pass(m, ps, false, false, 3));   // encoder + latent moments only
+  SMX_CHECK(forward_pass(m, ps, Loss::None, Fwd::EncodeOnly));
   int Hmax = 0, lab_floats = 0;
   for (const MlpLayer& L : m->dec) Hmax = std::max(Hmax, L.out_p);
   for (int j = 0; j < m->n_heads; ++j) lab_floats += c.y[j] ? m->tensors[m->t_labW[j]].ld : 0;
@@ -476,7 +476,9 @@ static int predict_batch_drawwise(smx_model* m, const PredChunk& c, Pass& ps, si
   const size_t S = c.S, Cn = c.Cn, G = (size_t)m->G, D = (size_t)m->D, k = (size_t)m->k;
   for (size_t s = 0; s < S; ++s) {
     ps.sample = (int)s;
-    SMX_CHECK(forward_pass(m, ps, false, false, s == 0 ? ((need_dec || S > 1) ? 0 : 3) : 2));
+    // the encoders run once; a single draw nobody decodes stops at the latent moments
+    const Fwd first = (need_dec || S > 1) ? Fwd::Full : Fwd::EncodeOnly;
+    SMX_CHECK(forward_pass(m, ps, Loss::None, s == 0 ? first : Fwd::Resample));
     PackList pl(m->st, (unsigned)std::min<size_t>(256, ((size_t)B * std::max(G, D) + 255) / 256), 1, B);
     if (s == 0) SMX_CHECK(add_latent_moments(m, pl, c, b0));
     SMX_CHECK(pl.add(c.zd ? c.zd + (s * Cn + b0) * D : nullptr, D, m->z, (size_t)m->Dp, D));
@@ -502,9 +504,9 @@ int smx_forward(smx_model* m, const int32_t* row_ids, const float* host_x, const
                 float* l_scale, float* l_sample, float* x_params, float* const* y_params) {
   SMX_REQUIRE(m, "null model");
   Pass ps;
-  SMX_CHECK(setup_pass(m, ps, row_ids, host_x, host_library, batch, training, sample_index));
+  SMX_CHECK(setup_pass(m, ps, {row_ids, host_x, host_library}, batch, training, sample_index));
   SMX_REQUIRE(!(training && !row_ids), "training-mode forward needs resident rows");
-  SMX_CHECK(forward_pass(m, ps, false, false));
+  SMX_CHECK(forward_pass(m, ps, Loss::None));
   return fetch_forward(m, batch, z_mean, z_scale, z_sample, l_mean, l_scale, l_sample, x_params, y_params, 0);
 }
 
@@ -517,12 +519,12 @@ int smx_forward_samples(smx_model* m, const int32_t* row_ids, const float* host_
   if (!row_ids && host_x && n_samples > 1 && batch > 0 && batch <= m->Bmax && stacked_scoring_ok(m) && !m->scvi)
     return smx_predict(m, host_x, host_library, batch, batch, n_samples, z_mean, z_scale, z_samples, l_mean, l_scale, l_samples, x_params, y_params);
   Pass ps;
-  SMX_CHECK(setup_pass(m, ps, row_ids, host_x, host_library, batch, 0, 0));
+  SMX_CHECK(setup_pass(m, ps, {row_ids, host_x, host_library}, batch, 0, 0));
   const size_t B = (size_t)batch;
   for (int s = 0; s < n_samples; ++s) {
     ps.sample = s;
     // the encoders run once (eval mode: no noise in them); later draws re-sample the latents and decode
-    SMX_CHECK(forward_pass(m, ps, false, false, s == 0 ? 0 : 2));
+    SMX_CHECK(forward_pass(m, ps, Loss::None, s == 0 ? Fwd::Full : Fwd::Resample));
     SMX_CHECK(fetch_forward(m, batch, s == 0 ? z_mean : nullptr, s == 0 ? z_scale : nullptr,
                             z_samples ? z_samples + (size_t)s * B * m->D : nullptr, s == 0 ? l_mean : nullptr,
                             s == 0 ? l_scale : nullptr, l_samples ? l_samples + (size_t)s * B : nullptr,
@@ -914,7 +916,7 @@ int smx_decode(smx_model* m, const float* z, const float* l, int32_t batch, floa
   SMX_HIP(hipMemcpy2DAsync(m->z, (size_t)m->Dp * sizeof(float), z, (size_t)m->D * sizeof(float), (size_t)m->D * sizeof(float),
                            (size_t)batch, hipMemcpyHostToDevice, m->st));
   if (m->scvi) SMX_HIP(hipMemcpyAsync(m->lsmp, l, (size_t)batch * sizeof(float), hipMemcpyHostToDevice, m->st));
-  SMX_CHECK(forward_pass(m, ps, false, false, 1));
+  SMX_CHECK(forward_pass(m, ps, Loss::None, Fwd::DecodeOnly));
   SMX_HIP(hipStreamSynchronize(m->st));
   SMX_CHECK(fetch_planes(m, batch, x_params));
   return fetch_labels(m, batch, y_params, 0);

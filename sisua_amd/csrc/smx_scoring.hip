@@ -107,7 +107,7 @@ static int stacked_scores(smx_model* m, const Pass& ps, int n_samples, const Sco
                    
                     score_decoder1_supported(m->Dp, m->dec[0].out_p) && !tuning_on("no_score_dec1");
   // the encoders and the latent heads
-  SMX_CHECK(forward_pass(m, ps, false, false, (m->scale || m->mixpost) ? 3 : 4));   // (4: without the latent moments' launch -- the draws below read `latbuf`)
+  SMX_CHECK(forward_pass(m, ps, Loss::None, (m->scale || m->mixpost) ? Fwd::EncodeOnly : Fwd::EncodeRaw));   // (EncodeRaw: the draws below read `latbuf`)
   for (int s0 = 0; s0 < n_samples; s0 += Sc) {
     const int S = std::min(Sc, n_samples - s0);
     const long rows = (long)S * B;
@@ -235,7 +235,7 @@ static int marginal_llk_run(smx_model* m, Pass& ps, int32_t batch, int32_t n_sam
   if (stacked) rc = marginal_llk_stacked(m, ps, n_samples, run);
   for (int s = 0; !stacked && s < n_samples && rc == SMX_OK; ++s) {
     ps.sample = s;
-    rc = forward_pass(m, ps, false, false, s == 0 ? 0 : 2);
+    rc = forward_pass(m, ps, Loss::None, s == 0 ? Fwd::Full : Fwd::Resample);
     if (rc != SMX_OK) break;
     IwArgs a{};
     a.lgx1 = ps.lgx1; a.rows = ps.rows;
@@ -264,7 +264,7 @@ int smx_marginal_llk(smx_model* m, const int32_t* row_ids, const float* host_x, 
   SMX_REQUIRE(m && mllk && n_samples > 0, "bad arguments");
   SMX_REQUIRE(m->cfg.likelihood != SMX_LLK_MSE, "the 'mse' output is not a normalised density: no marginal likelihood");
   Pass ps;
-  SMX_CHECK(setup_pass(m, ps, row_ids, host_x, host_library, batch, 0, 0));
+  SMX_CHECK(setup_pass(m, ps, {row_ids, host_x, host_library}, batch, 0, 0));
   return marginal_llk_run(m, ps, batch, n_samples, mllk, llk_mean);
 }
 
@@ -289,7 +289,7 @@ int smx_score_llk(smx_model* m, const int32_t* row_ids, const float* host_x, con
   SMX_REQUIRE(m->cfg.likelihood != SMX_LLK_MSE, "the 'mse' output is not a normalised density: no posterior-predictive scores");
   if (!m->stochastic) n_samples = 1;   // (deterministic latent: every draw decodes to the same parameters)
   Pass ps;
-  SMX_CHECK(setup_pass(m, ps, row_ids, host_x, host_library, batch, 0, 0));
+  SMX_CHECK(setup_pass(m, ps, {row_ids, host_x, host_library}, batch, 0, 0));
   const int lk = m->cfg.likelihood;
   const bool zi = (lk == SMX_LLK_ZINB || lk == SMX_LLK_ZINBD);
   const int n_dist = zi ? 2 : 1;
@@ -330,7 +330,7 @@ int smx_score_llk(smx_model* m, const int32_t* row_ids, const float* host_x, con
   }
   for (int s = 0; !stacked && s < n_samples && rc == SMX_OK; ++s) {
     ps.sample = s;
-    rc = forward_pass(m, ps, false, false, s == 0 ? 0 : 2);
+    rc = forward_pass(m, ps, Loss::None, s == 0 ? Fwd::Full : Fwd::Resample);
     for (int t = 0; t < n_targets && rc == SMX_OK; ++t) {
       const bool own = !(targets && targets[t]);
       for (int j = 0; j < n_dist && rc == SMX_OK; ++j) {

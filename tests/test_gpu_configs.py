@@ -320,7 +320,7 @@ def test_wide_panel_head_in_one_launch(Engine, lk, B, G, storage):
 
 @pytest.mark.parametrize("case", ["sisua_labels", "sisua_extra_output", "batch_256", "sisua_batch_200", "head_bwd_off"])
 def test_wide_panel_head_with_labels_and_two_cell_passes(Engine, case):
-  """What round 5 let into the one-launch head (smx_step.hip: head_fused_ok): SISUA models -- label heads and an
+  """What round 5 let into the one-launch head (smx_forward.hip: head_fused_ok): SISUA models -- label heads and an
   extra observed output beside the gene panel (their launches run beside it; their d d no longer rides with a head-backward launch that
   is not there) -- and minibatches of up to 256 cells (one launch per 128 cells, the second adding its dW / db).  One step: the ELBO terms
   and EVERY gradient against the oracle, the Adam moments; two more steps' losses.  `head_bwd_off`: with the separate-launch
@@ -372,7 +372,7 @@ def test_wide_panel_head_with_labels_and_two_cell_passes(Engine, case):
 @pytest.mark.parametrize("case", ["fvae", "semifvae_ragged", "fvae_extra_output"])
 def test_factor_vae_takes_the_one_launch_head(Engine, case):
   """Round 6 (VERDICT r05 Missing 4, its FactorVAE half): at a wide gene panel FactorVAE / SemiFVAE take the one-launch output head too
-  (smx_step.hip: head_fused_ok) -- the discriminator's passes use the slab buffer between the head's launch and the decoder's backward, which is
+  (smx_forward.hip: head_fused_ok) -- the discriminator's passes use the slab buffer between the head's launch and the decoder's backward, which is
   free where the head's d d lives in its column-major slabs (at most 128 cells, no observed output beside the genes; with one the separate
   launches stay).  One step against the oracle (ELBO terms, TC, the discriminator's loss, every gradient), the separate-launch form
   within rounding of it, two more steps' losses equal between the two forms to 1e-6.  (128 x 20 000 zinb: 276 -> 236 us per step.)"""
@@ -449,7 +449,7 @@ def test_scvi_row_local_head_at_wide_gene_panels(Engine, lk, G, B, storage, disp
 
 
 def test_wide_panel_heads_update_as_a_background_sweep(Engine):
-  """Flag head_sweep (smx_step.hip: head_sweep_start / head_sweep_join): with the fused head, clip + Adam of the heads' tensors runs as a fixed
+  """Flag head_sweep (smx_backward.hip: head_sweep_start / head_sweep_join): with the fused head, clip + Adam of the heads' tensors runs as a fixed
   number of workgroups on a second stream between this step's output head and the next step's.  Same arithmetic per element, the tensor's norm
   summed in the same order: losses of every step, parameters and both Adam moments equal the riders + optimiser-launch form BIT FOR BIT -- over
   two multi-step calls with an evaluation pass and a forward pass (which reads the head) between them, with few workgroups (the next head waits for a slow sweep) and many.  (The 20 000-gene width, where the sweep is the default: test_c5_*.)"""

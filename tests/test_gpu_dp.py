@@ -153,7 +153,7 @@ def test_world_n_steps_match_oracle(Engine, name, world, sync_bn):
 @pytest.mark.parametrize("name,world,sync_bn", [("vae_zinb", 2, False), ("vae_zinb", 3, True), ("sisua", 2, False), ("sisua_extra_output", 3, False),
                                                 ("misa_mix", 2, True), ("scale", 2, False)])
 def test_two_bucket_chain_matches_oracle(Engine, monkeypatch, name, world, sync_bn):
-  """The two-bucket step of round 5 (smx_step.hip: dp_chain_start; forced here with SMX_DP_BUCKETS=2, by default taken from 3 MB of head
+  """The two-bucket step of round 5 (smx_backward.hip: dp_chain_start; forced here with SMX_DP_BUCKETS=2, by default taken from 3 MB of head
   gradients): the heads' bucket is all-reduced, normed and APPLIED on the communication stream -- started where the heads' gradients are
   final (with label heads whose weight gradient rides with the last launch of the backward pass: in front of the optimiser), joined in front of
   the next step's output head --, the front bucket on the model's stream.  Four steps through ONE multi-step call and one single-step call
@@ -212,7 +212,7 @@ def test_two_bucket_chain_matches_oracle(Engine, monkeypatch, name, world, sync_
 @pytest.mark.parametrize("name,world,sync_bn", [("vae_zinb", 2, False), ("vae_zinb", 3, True), ("sisua", 2, False), ("sisua_extra_output", 3, False),
                                                 ("vae_zinb", 8, False), ("scale", 2, False)])
 def test_sharded_optimiser_state_matches_oracle(Engine, name, world, sync_bn):
-  """Flag opt_shard (smx_step.hip: dp_chain_start): the heads' bucket is reduce-SCATTERED, every rank clips and applies
+  """Flag opt_shard (smx_backward.hip: dp_chain_start): the heads' bucket is reduce-SCATTERED, every rank clips and applies
   Adam to its 1 / world slice only (slices cut at 64-float boundaries, through optimiser chunks and tensors where they fall; the per-tensor
   norm from the ranks' partial sums of squares), and the updated parameters are all-gathered.  Four steps through one multi-step call + a
   single-step call: losses of every step, the largest gradient norm, the parameters and -- after smx_opt_gather -- both Adam moments equal

@@ -7,7 +7,10 @@ fault that no test reached (the CSR store at a wide panel: docs/LAB_NOTES.md).
 
 Every configuration runs in a CHILD process (a fault names its configuration; the parent stops at the first abnormal exit -- a GPU fault is
 not to be repeated).  Run on the GPU box:
-    python tools/dev/matrix_probe.py [--only SUBSTRING] [--limit N] > gpurun_out/matrix_probe.txt
+    python tools/dev/matrix_probe.py [--only SUBSTRING] [--limit N] [--digest] > matrix_probe.txt
+--digest: each child also prints one SHA-256 over what its float32-store run left -- parameters, both optimiser moments, the BatchNorm moving
+statistics, the metric rows of the three steps and the evaluation's metrics, as raw float32 bytes -- on a line "digest <hex> <name>": two
+builds that launch the same kernels with the same arguments give the same lines (a host-side refactor is checked by diffing them).
 The oracle is test infrastructure: this tool is a checker like tests/, not part of the product path."""
 import argparse
 import json
@@ -97,7 +100,24 @@ def name_of(c):
                                                  "".join("-%s%s" % (k, json.dumps(c[k]).replace(" ", "")) for k in ("labels", "extra_outputs", "n_components", "dispersion") if c.get(k)))
 
 
-def run_one(c):
+def state_digest(e, history, evaluation):
+  """SHA-256 over the engine's trained state and the given metrics, every value as raw float32 bytes in a fixed order"""
+  import hashlib
+  import numpy as np
+  h = hashlib.sha256()
+  for which in (0, 2, 3):   # parameters, first and second optimiser moments
+    t = e.get_params(which=which)
+    for k in sorted(t):
+      h.update(np.ascontiguousarray(t[k], np.float32).tobytes())
+  for i, st in sorted(e.get_bn().items()):
+    h.update(st["moving_mean"].tobytes() + st["moving_var"].tobytes())
+  for m in (history, evaluation):
+    for k in sorted(m):
+      h.update(np.asarray(m[k], np.float32).tobytes())
+  return h.hexdigest()
+
+
+def run_one(c, digest=False):
   import numpy as np
   from oracle import sisua_oracle as so
   from sisua_amd.engine import Engine
@@ -164,7 +184,8 @@ def run_one(c):
     e.train_steps(order[: 3 * B], 3, B, graph=False)
     h = {k: np.asarray(v).copy() for k, v in e.metrics_history(3).items()}
     one = e.train_step(order[3 * B: 4 * B])["loss"]
-    ev_ = e.eval_step(rows)["loss"]
+    evm = e.eval_step(rows)
+    ev_ = evm["loss"]
     fw = e.forward(row_ids=rows)["x_params"]
     sc = None
     if spec.stochastic:
@@ -174,6 +195,8 @@ def run_one(c):
     # (scoring under the output distribution: the input cells as one target, a second matrix as another -- resident counts through every store's reader)
     sl = e.score_llk([None, x[rows[::-1]]], row_ids=rows, n_samples=2) if spec.stochastic and not heads else None
     outs[storage] = (h, one, ev_, fw, sc, e.get_params(), fs, sl)
+    if digest and storage == "f32":
+      print("digest %s %s" % (state_digest(e, h, evm), name_of(c)), flush=True)
     e.close()
   ref = outs["f32"]
   for storage, o in outs.items():
@@ -205,9 +228,10 @@ def main():
   ap.add_argument("--only", default="", help="substring of the configurations' names")
   ap.add_argument("--limit", type=int, default=0)
   ap.add_argument("--list", action="store_true")
+  ap.add_argument("--digest", action="store_true", help="one SHA-256 per configuration over the trained state and the metrics (see above)")
   args = ap.parse_args()
   if args.one:
-    problems = run_one(json.loads(args.one))
+    problems = run_one(json.loads(args.one), args.digest)
     print(json.dumps(problems))
     return 0
   cs = [c for c in configurations() if args.only in name_of(c)]
@@ -220,7 +244,8 @@ def main():
   bad = 0
   for c in cs:
     t0 = time.time()
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", json.dumps(c)], capture_output=True, text=True, timeout=600)
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--one", json.dumps(c)] + (["--digest"] if args.digest else []),
+                       capture_output=True, text=True, timeout=600)
     last = p.stdout.strip().splitlines()[-1] if p.stdout.strip() else ""
     if p.returncode != 0:
       print("ABNORMAL rc=%d  %s\n%s" % (p.returncode, name_of(c), (p.stderr or "")[-1500:]), flush=True)
@@ -230,6 +255,9 @@ def main():
       bad += 1
       continue
     problems = json.loads(last)
+    for line in p.stdout.splitlines():
+      if line.startswith("digest "):
+        print(line, flush=True)
     bad += 1 if problems else 0
     print("%s  %5.1fs  %s%s" % ("ok  " if not problems else "FAIL", time.time() - t0, name_of(c), "".join("\n      " + q for q in problems)), flush=True)
   print("matrix_probe: %d configuration(s), %d with problems" % (len(cs), bad), flush=True)

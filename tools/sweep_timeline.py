@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timeline around one background optimiser sweep (adam_sweep_kernel, smx_step.hip: head_sweep_start) from a rocprofv3
+"""Timeline around one background optimiser sweep (adam_sweep_kernel, smx_backward.hip: head_sweep_start) from a rocprofv3
 --kernel-trace CSV directory: every kernel that overlaps the window between two consecutive output-head launches, with its
 queue -- what the main stream's launches cost while the sweep runs beside them."""
 import csv
