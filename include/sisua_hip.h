@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 7
+#define SMX_ABI_VERSION 8
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -678,6 +678,29 @@ int smx_k_row_select(const float* rows, int32_t n_rows, int32_t G, int32_t ld, f
 int smx_k_col_rank2(const float* cols, int32_t n_cols, int64_t n_cells, int32_t* rank2, int32_t* nonfinite);
 int smx_k_col_correlate(const float* cols, int32_t n_cols, int64_t n_cells, const int32_t* prot_rank2, const double* prot_unit, int32_t P,
                         int64_t* sp_Sa, int64_t* sp_Saa, int64_t* sp_Sab, double* pe_mean, double* pe_Sxx, double* pe_Sxy, int32_t* nonfinite);
+
+/* ---- clustering scores of a latent space (smx_cluster.hip; model-free: smx_init only) ----------- */
+/* The distance sums of sklearn.metrics.silhouette_samples (Euclidean) for host cells Z [n_cells][D] with classes labels [n_cells] in
+ * 0 .. n_labels - 1: a[i] = (sum over j of i's class c of |z_i - z_j|) / (n_c - 1), 0 for a singleton class; b[i] = the smallest, over the
+ * classes c' != c with n_c' > 0, of (sum over j in c' of |z_i - z_j|) / n_c' (+inf when no other class has a cell).  Differences, squares,
+ * sums, square roots and the per-class accumulation are float64 in the direct form sqrt(sum_d (z_i[d] - z_j[d])^2); no float atomics: the
+ * order of every sum is a function of (n_cells, D, labels) alone, so two calls give the same bits.  A NaN or an infinity in Z (an infinity
+ * is read as NaN) gives NaN in the a / b of every cell whose sums it enters.  1 <= D <= 128, 2 <= n_labels <= 256, 1 <= n_cells < 2^31,
+ * every label in range: anything else is SMX_ERR_INVALID before any device work.  Device memory: 8 x slices x n_labels x n_cells bytes of
+ * partial sums, slices = max(1, min(32, 1024 / ceil(n_cells / 256))). */
+int smx_cluster_silhouette(const float* Z, int64_t n_cells, int32_t D, const int32_t* labels, int32_t n_labels, double* a, double* b);
+/* Lloyd's iterations of n_init restarts run together, restart r from the cells init_idx [n_init][K] as its initial centres.  Per iteration
+ * and restart: every cell goes to the centre with the smallest sum_d (z[d] - c[d])^2 (float64 on float64 centres, ties to the lowest index;
+ * a NaN distance is never the smallest), then each centre becomes the float64 mean of its members, summed in a fixed order; an EMPTY
+ * CLUSTER KEEPS ITS PREVIOUS CENTRE.  A restart stops at the first assignment that changes no label, at max_iter assignments at the latest;
+ * n_iter [n_init] counts its assignments, the confirming one included.  What is returned belongs to the LAST assignment: the labels, the
+ * centres it measured against (on convergence these are also the means of the labels) and inertia [n_init] = the float64 sum of its
+ * smallest squared distances, in a fixed order.  *best: the restart of lowest inertia, ties to the lowest index; labels_best [n_cells] and
+ * centres_best [K][D] are its; labels_all [n_init][n_cells] (may be NULL): every restart's.  A restart's results do not depend on the others
+ * of the call.  1 <= D <= 128, 2 <= K <= 256, K <= n_cells < 2^31, 1 <= n_init <= 4096, max_iter >= 1, every init_idx in 0 .. n_cells - 1:
+ * anything else is SMX_ERR_INVALID before any device work.  Device memory: 12 x n_init x n_cells bytes. */
+int smx_cluster_kmeans(const float* Z, int64_t n_cells, int32_t D, int32_t K, const int32_t* init_idx, int32_t n_init, int32_t max_iter,
+                       int32_t* labels_best, double* centres_best, double* inertia, int32_t* n_iter, int32_t* best, int32_t* labels_all);
 
 /* ---- padding audit (test instrument; never on the path of a step) ----------- */
 /* The layout's invariant, read back from the device: every feature axis is padded to 32 and every tensor to 64 floats, and what lies

@@ -436,21 +436,25 @@ class Engine:
     la = None if library is None else _f32(library, (xa.shape[0], 2))
     return xa.shape[0], (xa, la), (None, _fp(xa), _fp(la))
 
-  def _outputs(self, B: int, S: Optional[int] = None, want_x_params: bool = True):
+  def _outputs(self, B: int, S: Optional[int] = None, want_x_params: bool = True, want=None):
     """The result arrays of a forward pass over B cells -- S: with a leading draw axis on z_sample / l_sample / x_params / y_params --
-    and their pointers in the order of smx_forward's output arguments: (dict of arrays, pointers)."""
+    and their pointers in the order of smx_forward's output arguments: (dict of arrays, pointers).  want: the names to allocate and ask
+    for (of z_mean, z_scale, z_sample, l_mean, l_scale, l_sample, x_params, y_params); the others are None (NULL to the library, which
+    then does not fetch them).  Default: all."""
     cfg = self.cfg
     D, G, k = cfg.latent_dim, cfg.n_genes, cfg.k
     lead = () if S is None else (S,)
-    out = dict(z_mean=np.empty((B, D), np.float32), z_sample=np.empty(lead + (B, D), np.float32))
-    out["z_scale"] = np.empty((B, D), np.float32) if cfg.stochastic else None
+    w = (lambda name: True) if want is None else (lambda name: name in want)
+    new = lambda name, shape: np.empty(shape, np.float32) if w(name) else None
+    out = dict(z_mean=new("z_mean", (B, D)), z_sample=new("z_sample", lead + (B, D)))
+    out["z_scale"] = new("z_scale", (B, D)) if cfg.stochastic else None
     zs = out["z_scale"]
-    if cfg.latent_tril:   # the full-covariance posterior: the device hands back the factor L [B, D, D]; z_scale = its marginal stddevs (_tril_scale)
+    if cfg.latent_tril and zs is not None:   # the full-covariance posterior: the device hands back the factor L [B, D, D]; z_scale = its marginal stddevs (_tril_scale)
       out["scale_tril"] = zs = np.empty((B, D, D), np.float32)
     if cfg.model == "scvi":
-      out.update(l_mean=np.empty((B,), np.float32), l_scale=np.empty((B,), np.float32), l_sample=np.empty(lead + (B,), np.float32))
-    out["x_params"] = np.empty(lead + (k, B, G), np.float32) if want_x_params else None
-    out["y_params"] = [np.empty(lead + (B, label_planes(llk, P) * P), np.float32) for P, llk in cfg.head_labels]
+      out.update(l_mean=new("l_mean", (B,)), l_scale=new("l_scale", (B,)), l_sample=new("l_sample", lead + (B,)))
+    out["x_params"] = new("x_params", lead + (k, B, G)) if want_x_params else None
+    out["y_params"] = [np.empty(lead + (B, label_planes(llk, P) * P), np.float32) for P, llk in cfg.head_labels] if w("y_params") else []
     return out, (_fp(out["z_mean"]), _fp(zs), _fp(out["z_sample"]), _fp(out.get("l_mean")), _fp(out.get("l_scale")),
                  _fp(out.get("l_sample")), _fp(out["x_params"]), _fps(out["y_params"]))
 
@@ -471,17 +475,18 @@ class Engine:
     check(self.lib.smx_forward_samples(self._h, *cells, B, S, *res))
     return _tril_scale(out)
 
-  def predict(self, x, library=None, n_samples: int = 1, batch: Optional[int] = None, want_x_params: bool = True):
+  def predict(self, x, library=None, n_samples: int = 1, batch: Optional[int] = None, want_x_params: bool = True, want=None):
     """Eval-mode forward of a whole host matrix in one call (smx_predict): arrays over ALL cells, with a leading draw
     axis for z_sample / l_sample / x_params / y_params -- the layout of forward_samples with n = every cell.
     want_x_params=False: everything but the gene output's parameter planes (what a lazy result keeps on the device side).
+    want: only the named outputs leave the device (see `_outputs`; the clustering scores ask for the latent means alone).
     x may be scipy.sparse (smx_predict_csr: the same results bit for bit)."""
     cfg = self.cfg
     xa = _csr3(x, cfg.n_genes) if _sparse(x) else _f32(x)
     N, S = (xa[0].size - 1 if isinstance(xa, tuple) else xa.shape[0]), int(n_samples)
     B = min(int(batch or self.max_batch), self.max_batch)
     la = None if library is None else _f32(library, (N, 2))
-    out, res = self._outputs(N, S, want_x_params)
+    out, res = self._outputs(N, S, want_x_params and (want is None or "x_params" in want), want)
     if isinstance(xa, tuple):
       check(self.lib.smx_predict_csr(self._h, *_csr_ptrs(xa), _fp(la), N, B, S, *res))
     else:
@@ -957,6 +962,40 @@ def k_col_correlate(cols, prot_rank2, prot_unit):
   pr, pu = _col_operands(prot_rank2, prot_unit, N)
   out, res = _col_outputs(n, pr.shape[0])
   check(lib.smx_k_col_correlate(_fp(c), n, N, _ip(pr), _dp(pu), pr.shape[0], *res))
+  return out
+
+
+def k_cluster_silhouette(Z, labels, n_labels: int):
+  """smx_cluster_silhouette: cells Z [N, D] float32, classes labels [N] in 0 .. n_labels - 1 -> (a [N], b [N]) float64, the mean distance of
+  every cell to its own class and to the nearest other one"""
+  lib = _hip.require_gpu()
+  z = _f32(Z)
+  y = np.ascontiguousarray(labels, dtype=np.int32)
+  if z.ndim != 2 or y.shape != (z.shape[0],):
+    raise ValueError(f"Z must be [cells, D] and labels [cells], got {z.shape} and {y.shape}")
+  a, b = np.empty((z.shape[0],), np.float64), np.empty((z.shape[0],), np.float64)
+  check(lib.smx_cluster_silhouette(_fp(z), z.shape[0], z.shape[1], _ip(y), int(n_labels), _dp(a), _dp(b)))
+  return a, b
+
+
+def k_cluster_kmeans(Z, init_idx, max_iter: int = 300, all_labels: bool = False):
+  """smx_cluster_kmeans: Lloyd's iterations on cells Z [N, D] float32 from the initial centres Z[init_idx [n_init, K]], every restart in one
+  call -> dict(labels [N], centres [K, D], inertia [n_init], n_iter [n_init], best, and labels_all [n_init, N] when asked)"""
+  lib = _hip.require_gpu()
+  z = _f32(Z)
+  idx = np.ascontiguousarray(init_idx, dtype=np.int32)
+  if z.ndim != 2 or idx.ndim != 2:
+    raise ValueError(f"Z must be [cells, D] and init_idx [n_init, K], got {z.shape} and {idx.shape}")
+  (N, D), (R, K) = z.shape, idx.shape
+  out = dict(labels=np.empty((N,), np.int32), centres=np.empty((K, D), np.float64), inertia=np.empty((R,), np.float64),
+             n_iter=np.empty((R,), np.int32))
+  best = C.c_int32(-1)
+  every = np.empty((R, N), np.int32) if all_labels else None
+  check(lib.smx_cluster_kmeans(_fp(z), N, D, K, _ip(idx), R, int(max_iter), _ip(out["labels"]), _dp(out["centres"]), _dp(out["inertia"]),
+                               _ip(out["n_iter"]), C.byref(best), None if every is None else _ip(every)))
+  out["best"] = int(best.value)
+  if every is not None:
+    out["labels_all"] = every
   return out
 
 

@@ -1,5 +1,6 @@
 """Evaluation metrics of a fitted model as plain callables `metric(model) -> dict` (the reference's training-time metrics,
-sisua/analysis/sc_metrics.py:244-348, without its callback machinery): `ImputationError` and `CorrelationScores`; and the views of the full gene x protein
+sisua/analysis/sc_metrics.py:244-402, without its callback machinery): `ImputationError`, `CorrelationScores` and `ClusteringScores`
+(with `clustering_scores`, the function it is made of); and the views of the full gene x protein
 matrices of `SingleCellModel.correlation` that the reference's analysis reads (`correlation_list`, `marker_correlations`).  What needs the
 [cells, genes] mean of the gene output is reduced on the device (smx_impute.hip); the correlations over a few marker columns are SciPy's,
 called as the reference calls them."""
@@ -9,6 +10,7 @@ from typing import Dict, Iterable, List, Mapping, Sequence, Tuple
 
 import numpy as np
 
+from sisua_amd.clustering import clustering_scores   # noqa: F401  (latent_benchmarks.py:69-117; the distances and restarts on the device)
 from sisua_amd.data import SingleCellOMIC, corrupt as _corrupt, is_sparse
 
 
@@ -78,6 +80,31 @@ class CorrelationScores:
       pearson.append(-pearsonr(cols[:, j], self.extras[:, p])[0])
     return {"pearson_mean": float(np.mean(pearson)), "spearman_mean": float(np.mean(spearman)),
             "pearson_med": float(np.median(pearson)), "spearman_med": float(np.median(spearman))}
+
+
+class ClusteringScores:
+  """The scores of sc_metrics.py:351-402: `clustering_scores` of the mean of every latent posterior of the model against the protein
+  levels `extras` [cells, proteins] -- labels = argmax(extras, 1), n_labels = the number of proteins.  One entry per latent (`ASW_0`, ...;
+  `_1` is SCVI's library latent), plus the plain keys as the mean over the latents; all values NEGATED, as the reference does (a loss:
+  lower is better).  inputs: the counts the cells are encoded from; kw: keywords of `clustering_scores` (n_init, seed, max_iter)."""
+
+  def __init__(self, inputs, extras, batch_size=64, **kw):
+    self.inputs = _matrix(inputs)
+    ex = _matrix(extras)
+    ex = np.asarray(ex.toarray() if is_sparse(ex) else ex)
+    if ex.ndim != 2 or ex.shape[0] != self.inputs.shape[0] or ex.shape[1] < 2:
+      raise ValueError("extras must be [cells, proteins >= 2] for the cells of inputs")
+    self.labels, self.n_labels = np.argmax(ex, axis=1), int(ex.shape[1])
+    self.batch_size, self.kw = int(batch_size), dict(kw)
+
+  def __call__(self, model) -> Dict[str, float]:
+    scores, avg = {}, {}
+    for idx, z in enumerate(model._latent_means(self.inputs, None, self.batch_size)):
+      for key, val in clustering_scores(z, self.labels, self.n_labels, **self.kw).items():
+        scores[f"{key}_{idx}"] = -val
+        avg.setdefault(key, []).append(-val)
+    scores.update({k: float(np.mean(v)) for k, v in avg.items()})
+    return scores
 
 
 def correlation_list(pearson, spearman) -> List[Tuple[int, int, float, float]]:
