@@ -151,20 +151,10 @@ def _oracle_step(spec, params, bn, opt, x, ys, lib, mask, rows, step, cell_base=
   return so.train_step(spec, params, bn, opt, x[rows], noise, y=[y[rows] for y in ys], library=lib[rows], mask=mask[rows])
 
 
-@pytest.mark.parametrize("name", list(CASES))
-@pytest.mark.parametrize("batch", [32, 100, 160])
-def test_one_step_matches_oracle(Engine, name, batch):
-  kw = CASES[name]
-  spec, cfg, x, ys, lib, mask = _problem(kw)
-  params = perturbed_params(spec)
-  bn, opt = so.init_bn_state(spec), so.init_opt_state(params)
-  e = Engine(cfg, max_batch=max(128, batch), init=False)
-  e.set_params(params)
-  e.upload(x, ys, lib, mask, cell_id_base=1000)
-  rows = np.random.default_rng(1).choice(x.shape[0], size=batch, replace=False).astype(np.int32)
-  p0 = {k: v.copy() for k, v in params.items()}
-  res = _oracle_step(spec, params, bn, opt, x, ys, lib, mask, rows, 0, cell_base=1000)
-  m = e.train_step(rows)
+def check_one_step(e, m, res, spec, params, p0, bn, opt):
+  """The assertions of one first training step against the oracle's (`res`, and `params` / `bn` / `opt` as so.train_step left them;
+  `p0`: the parameters before the step): metrics, every gradient, the Adam moments, every weight's move and the BatchNorm moving
+  statistics.  Shared with tests/test_gpu_batch_ladder.py."""
   assert m["nan_flag"] == 0 and m["step"] == 1
   for key in ("loss", "nllk_x", "kl"):
     assert np.isclose(m[key], res["metrics"][key], rtol=RTOL, atol=1e-5), (key, m[key], res["metrics"][key])
@@ -196,6 +186,23 @@ def test_one_step_matches_oracle(Engine, name, batch):
   for i, st in e.get_bn().items():
     assert np.allclose(st["moving_mean"], bn[f"{names[i]}/moving_mean"], rtol=1e-4, atol=1e-6)
     assert np.allclose(st["moving_var"], bn[f"{names[i]}/moving_var"], rtol=1e-4, atol=1e-6)
+
+
+@pytest.mark.parametrize("name", list(CASES))
+@pytest.mark.parametrize("batch", [32, 100, 160])
+def test_one_step_matches_oracle(Engine, name, batch):
+  kw = CASES[name]
+  spec, cfg, x, ys, lib, mask = _problem(kw)
+  params = perturbed_params(spec)
+  bn, opt = so.init_bn_state(spec), so.init_opt_state(params)
+  e = Engine(cfg, max_batch=max(128, batch), init=False)
+  e.set_params(params)
+  e.upload(x, ys, lib, mask, cell_id_base=1000)
+  rows = np.random.default_rng(1).choice(x.shape[0], size=batch, replace=False).astype(np.int32)
+  p0 = {k: v.copy() for k, v in params.items()}
+  res = _oracle_step(spec, params, bn, opt, x, ys, lib, mask, rows, 0, cell_base=1000)
+  m = e.train_step(rows)
+  check_one_step(e, m, res, spec, params, p0, bn, opt)
   e.close()
 
 
