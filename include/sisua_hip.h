@@ -639,7 +639,9 @@ int smx_k_opt(int32_t rule, const float* hp, int32_t n_hp, int32_t n_tensors, co
 /* C[M,N] = op(A) * op(B) in fp32 on the MFMA path; transA: A given as [K,M];
  * transB: B given as [N,K]; split_k >= 1 (slabs summed on return).  tile_cfg 0: the library's choice of LDS tile; 100: the
  * direct bf16 x 3 form for deep contractions (transA = 0, K >= 512); 101 / 102: the minibatch-contracted weight-gradient forms
- * (transA = 1, transB = 0; 32 x 32 tiles / the gene-tile-owner panel form, N <= 128) -- test entries for those kernels. */
+ * (transA = 1, transB = 0; 32 x 32 tiles / the gene-tile-owner panel form, N <= 128); 103: the gene-axis contraction of wide
+ * panels (transA = 0, either layout of B, K >= 4096 after padding to 32, split_k = 1: one workgroup per K slice + the reduce
+ * launch, plain float32 rows) -- test entries for those kernels. */
 int smx_k_gemm(int transA, int transB, const float* A, const float* B, int32_t M, int32_t N, int32_t K,
                int32_t split_k, int32_t tile_cfg, float* C);
 /* The whole output head of a training step at a wide gene panel in ONE launch (smx_headfused.hip; rows a-9, a-10 / a-11 and the head's

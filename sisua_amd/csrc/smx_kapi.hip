@@ -198,13 +198,16 @@ int smx_k_gemm(int transA, int transB, const float* A, const float* B, int32_t M
   SMX_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0, "bad arguments");
   // tile_cfg 100 / 101 / 102: the bf16 x 3 forms outside the LDS-tiled kernel -- smx_dgemm.hip (A [M][K]; K padded to 32 with
   // zeros), the 32 x 32-tile weight-gradient kernel and the panel form of smx_panel.h (both: A [K][M], Bm [K][N], M padded to 32)
-  const bool direct = tile_cfg == 100, wg = tile_cfg == 101 || tile_cfg == 102;
+  // tile_cfg 103: the gene-axis contraction of smx_bigk.hip (A [M][K], B in either layout; K padded to 32 with zeros): slices from
+  // bigk_slices, per-slice slabs and the reduce launch as the step builds them (dd_bigk), identity rows, float32 A, no log1p
+  const bool direct = tile_cfg == 100, wg = tile_cfg == 101 || tile_cfg == 102, bigk = tile_cfg == 103;
   SMX_REQUIRE(!direct || !transA, "tile 100 (dgemm) takes A as [M][K]");
+  SMX_REQUIRE(!bigk || !transA, "tile 103 (bigk) takes A as [M][K]");
   SMX_REQUIRE(!wg || (transA && !transB), "tiles 101 / 102 (weight-gradient forms) take A as [K][M] and B as [K][N]");
   SMX_REQUIRE(tile_cfg != 102 || N <= 128, "tile 102 (panel form): N <= 128");
   // pad to the library's internal conventions: feature axes to 32, batch axes free
   const int Np = round_up(N, 32);
-  const int Kp = direct ? round_up(K, 32) : round_up(K, 4), Mp = wg ? round_up(M, 32) : round_up(M, 4);
+  const int Kp = (direct || bigk) ? round_up(K, 32) : round_up(K, 4), Mp = wg ? round_up(M, 32) : round_up(M, 4);
   const int lda = transA ? Mp : Kp, a_rows = transA ? K : M, a_cols = transA ? M : K;
   const int ldb = transB ? Kp : Np, b_rows = transB ? N : K, b_cols = transB ? K : N;
   float *dA = nullptr, *dB = nullptr, *dC = nullptr;
@@ -227,13 +230,26 @@ int smx_k_gemm(int transA, int transB, const float* A, const float* B, int32_t M
     g.K = Kp;   // (the padding of A and B is zero: dmalloc clears)
     SMX_REQUIRE(dgemm_supported(g), "tile 100 (dgemm): K >= 512 after padding to 32, split_k = 1");
     rc = launch_dgemm(nullptr, g);
+  } else if (bigk) {
+    BigKArgs bk;
+    bk.A = dA; bk.lda = lda; bk.Bm = dB; bk.ldb = ldb; bk.b_kmajor = transB ? 0 : 1;
+    bk.M = M; bk.N = Np; bk.K = Kp; bk.ldc = Np; bk.slab_stride = (long)M * Np; bk.out = dC;
+    bk.n_slices = bigk_slices(bk.K, SMX_BIGK_MAX_SLICES, &bk.k_chunk);
+    float* dPart = nullptr;
+    if ((rc = dmalloc(&dPart, (size_t)bk.n_slices * (size_t)bk.slab_stride))) return rc;
+    bk.part = dPart;
+    if (!(S == 1 && bigk_supported(bk))) { hipFree(dPart); hipFree(dA); hipFree(dB); hipFree(dC); }
+    SMX_REQUIRE(S == 1 && bigk_supported(bk), "tile 103 (bigk): K >= 4096 after padding to 32, split_k = 1");
+    rc = launch_bigk(nullptr, bk);
+    if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_gemm: device synchronize failed"); rc = SMX_ERR_HIP; }
+    hipFree(dPart);
   } else if (wg) {
     g.split_k = 1; g.panel_hint = tile_cfg == 102;
     SMX_REQUIRE(S == 1 && wgrad_supported(g, K), "tiles 101 / 102: split_k = 1");
     rc = launch_wgrad_group(nullptr, &g, 1, K, 1);
   } else
   rc = launch_gemm(nullptr, g, &eff);
-  if (rc == SMX_OK && tuning("kgemm_reps", 0) > 0 && !direct && !wg) {  // diagnostic: average launch time of this shape / tile
+  if (rc == SMX_OK && tuning("kgemm_reps", 0) > 0 && !direct && !wg && !bigk) {  // diagnostic: average launch time of this shape / tile
     const int reps = (int)tuning("kgemm_reps", 0);
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
