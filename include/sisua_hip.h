@@ -619,6 +619,9 @@ int64_t smx_loss_bytes_per_cell(const smx_model* m);
  * counts, d d, likelihood partials) when a training step of `batch` cells takes it -- a wide panel (>= 4096 genes), 128 decoder columns,
  * batch <= 128, no label heads --, else 0: bench.py's roofline entry at the C5 width. */
 int64_t smx_head_fused_bytes(const smx_model* m, int32_t batch);
+/* 1 when the model's LAST training step left the output head's dW / db to the decoder's BatchNorm-backward launch (a narrow panel, at most
+ * 128 cells, the plain bf16 x 3 head, one GPU: DESIGN.md section 4; knob no_dw_late), else 0: the tests' check that this form is what ran. */
+int32_t smx_head_dw_late(const smx_model* m);
 
 /* ---- kernel-level entry points (parity tests of single kernels) ------------ */
 /* Fused count log-likelihood forward+backward over host planes [k][B][G]:

@@ -46,7 +46,7 @@ static void attach_early_adam(smx_model* m, BnBwdArgs& b) {
     return;
   }
   m->adam_early_pending = false;
-  static const bool off = tuning_on("no_adam_early");
+  const bool off = tuning_on("no_adam_early");   // (read per step, like no_dw_late: a test flips it between engines)
   // (the riders carry Adam only -- smx_adam.h: SMX_OPT_SWITCH --: under another rule every chunk stays with the optimiser launch or the sweep)
   if (off || m->opt_rule != SMX_OPT_ADAM || dp_active(m) || !m->sq_slots || m->chunk_first_head >= m->n_chunks || tuning_on("no_sq_partials")) return;
   for (size_t t = (size_t)m->t_outW[0]; t < m->tensors.size(); ++t)   // head tensors are the last ones of the manifest
@@ -94,7 +94,10 @@ static void attach_early_adam(smx_model* m, BnBwdArgs& b) {
   // 6 for its own work) while the NEXT BatchNorm-backward launch of the step leaves the chip as idle: split them over the two
   // (SMX_ADAM_SPLIT = share of the first, default 0.5; a step with one such launch keeps them all, the final launch takes what
   // nobody carried)
-  static const float split = (float)tuning("adam_split", 0.5f);
+  static const float split_chain = (float)tuning("adam_split", 0.5f);
+  // (dw_late_now: the decoder's last layer's launch carried the head's dW instead of riders -- this is the launch behind it, with a one-layer decoder
+  // the encoder's and the last such launch of the step; what it leaves goes to the optimiser launch: adam_split_late, SMX_ADAM_SPLIT_LATE_DEFAULT)
+  const float split = m->dw_late_now ? (float)tuning("adam_split_late", SMX_ADAM_SPLIT_LATE_DEFAULT) : split_chain;
   const int total = early_to - m->chunk_first_head;
   const int first = std::max(1, std::min(total, (int)(total * std::min(std::max(split, 0.f), 1.f) + 0.5f)));
   b.adam_first = m->chunk_first_head;
@@ -251,6 +254,8 @@ struct MlpBwdOpts {
   // this one's: both in ONE launch (*twin_done); the caller then walks the twin with last_bn_done = true.
   std::vector<MlpLayer>* twin = nullptr; const BnBwdArgs* twin_front = nullptr; bool* twin_done = nullptr;
   bool last_bn_done = false;
+  // the LAST layer's wide BatchNorm-backward launch also carries the output head's dW / db (bn_wide_bwd_dw_kernel; dw_late below)
+  const HeadBwdArgs* head_dw = nullptr;
 };
 static int mlp_backward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps, Mat in0, bool in_is_x, int n_slabs, const MlpBwdOpts& o) {
   auto make_b = [&](MlpLayer& L, int slabs, const BnBwdArgs* front) {
@@ -283,6 +288,7 @@ static int mlp_backward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps
   if (o.twin_done) *o.twin_done = false;
   BnBwdArgs carried;            // gradient front handed from layer i + 1 to layer i (hidden layers up to 64 wide)
   bool have_carried = false;
+  bool dw_carried = false;      // o.head_dw went with the last layer's launch
   bool dpre_done = false;       // layer i's d pre-activation was written by the d in product of layer i + 1 (activation epilogue)
   for (int i = (int)mlp.size() - 1; i >= 0; --i) {
     MlpLayer& L = mlp[i];
@@ -305,12 +311,17 @@ static int mlp_backward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps
       if (m->metrics_before_allreduce && m->have_pending_metrics) {
         b.metrics = m->pending_metrics; b.with_metrics = 1; m->have_pending_metrics = false;
       }
-      attach_early_adam(m, b);
+      // (the carrier WRITES dW_out and its slots: the head's riders wait -- adam_early_pending stays set -- for the next BatchNorm-backward launch)
+      const HeadBwdArgs* hd = (last && o.head_dw && bn_wide_bwd_dw_supported(b, *o.head_dw)) ? o.head_dw : nullptr;
+      if (!hd) attach_early_adam(m, b);
       Timed t(m, "bn_bwd");
       const bool dual = last && b.front && b.fK <= 64 && o.twin && o.twin_front && o.twin_front->fK <= 64 && !o.twin->empty() && m->flags.twin && bn_dual_supported(ps.B) &&
                         bn_bwd_front_supported(ps.B, o.twin_front->fK) && o.twin->back().out_p % 8 == 0 &&
                         !(sync_bn_on(m, ps.training) && o.twin->back().bn >= 0);
-      if (dual) {
+      if (hd) {
+        SMX_CHECK(launch_bn_wide_bwd_dw(m->st, b, *hd));
+        dw_carried = true;
+      } else if (dual) {
         const BnBwdArgs b2 = make_b(o.twin->back(), 0, o.twin_front);
         SMX_CHECK(launch_bn_act_bwd_dual(m->st, b, b2));
         if (o.twin_done) *o.twin_done = true;
@@ -381,6 +392,7 @@ static int mlp_backward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps
     n_slabs = eff;
   }
   if (o.out_slabs) *o.out_slabs = n_slabs;
+  SMX_REQUIRE(!o.head_dw || dw_carried, "the output head's dW found no launch to carry it");
   return SMX_OK;
 }
 
@@ -555,6 +567,7 @@ struct BwdPass {
   int dh_slabs = 1;                     // slabs of d h the encoder's backward sums
   bool twin_done = false;               // the library encoder's last BatchNorm-backward ran beside the encoder's
   GemmArgs dw0[2]; int n_dw0 = 0;       // the first-layer weight gradients of the encoder and the library encoder
+  HeadBwdArgs hb_late;                  // m->dw_late_now: the head's arguments for the decoder's BatchNorm-backward launch, which carries its dW / db
 };
 
 // label heads (SISUA / MISA): d d += d Y W_lab^T as extra slabs of the output head's launch, the head's weight gradient with the
@@ -593,6 +606,17 @@ static int dd_bigk(smx_model* m, const Pass& ps, BwdPass& p, bool* done) {
   *done = true;
   p.n_slabs = 1;
   return SMX_OK;
+}
+
+// dW_out / db / the sum-of-squares slots leave the chain: the head's launch computes d d only and the decoder's BatchNorm-backward launch -- the
+// next on the chain, which waits for d d alone and leaves most of the chip idle -- carries the dW tiles (bn_wide_bwd_dw_kernel, the same role-0 body:
+// the same bits).  Where: the column-major d d slabs of a narrow panel (dd_wide), the plain bf16 x 3 form, a ReLU layer below the head; nobody that takes
+// the head's gradients as final in bwd_heads_final (the data-parallel chain and exchange, the background sweep); no SyncBatchNorm.  Knob no_dw_late
+// (read per step): the head's launch with both roles, as before.
+static bool dw_late(smx_model* m, const Pass& ps, const HeadBwdArgs& hb, bool dd_wide, bool fused_done, bool bigk) {
+  const MlpLayer& dL = m->dec.back();
+  return dd_wide && !fused_done && !bigk && hb.bf16x3 && !hb.sep && hb.n_extra == 0 && dL.act == SMX_ACT_RELU && !dp_active(m) && head_sweep_wgs(m) <= 0 &&
+         !sync_bn_on(m, ps.training) && !tuning_on("no_dw_late");
 }
 
 // ---- output head: count heads with raw planes -- both products of the output head in one launch of the wide direct-operand kernel
@@ -636,6 +660,11 @@ static int bwd_out_head(smx_model* m, const Pass& ps, BwdPass& p) {
   if (dd_wide && !fused_done && !bigk) {
     hb.dd_colmajor = 1; hb.slab_stride = 128L * dL.out_p;
     m->wide_dd_slabs = hb.n_slices; m->wide_dd_src = m->slab; m->wide_dd_stride = hb.slab_stride;
+  }
+  if (dw_late(m, ps, hb, dd_wide, fused_done, bigk)) {
+    p.hb_late = hb; p.hb_late.skip_dd = 1; p.hb_late.dd_colmajor = 0;
+    m->dw_late_now = true;
+    hb.skip_dw = 1;
   }
   // ... and then d W / d b with one workgroup per (gene tile, plane) that holds every row of H (smx_panel.h): the panel is
   // transformed and split once, not once per 32 rows of H
@@ -759,6 +788,7 @@ static int bwd_decoder(smx_model* m, const Pass& ps, BwdPass& p) {
                    bn_bwd_fold_supported(ps.B, p.lat_ld, m->Dp);
   MlpBwdOpts o;
   o.defer = p.bfront ? &p.tail : nullptr;
+  o.head_dw = m->dw_late_now ? &p.hb_late : nullptr;
   if (!m->mixpost && !m->latent_tril) {
     o.lat_epi = &le;
     return mlp_backward(m, m->dec, ps, {m->z, m->Dp}, false, p.n_slabs, o);
@@ -880,7 +910,7 @@ int backward_pass(smx_model* m, const Pass& ps) {
   std::fill(m->sq_reduced.begin(), m->sq_reduced.end(), 0);
   m->adam_early_pending = false; m->adam_rest_from = m->adam_rest_to = 0; m->adam_ride_b = 0;
   if (!m->chain_started) m->adam_early_from = -1;   // (forward_pass may have sent the heads' chunks down the data-parallel chain already)
-  m->lab_deferred = false;
+  m->lab_deferred = false; m->dw_late_now = false;
   if (m->fvae) SMX_CHECK(factor_backward(m, ps));   // first: it uses the slab buffer the head's backward fills next
   const MlpLayer& dL = m->dec.back();
   BwdPass p;

@@ -8,6 +8,10 @@ namespace smx {
 
 SMX_STAMP_TABLE
 
+}
+#include "smx_headdw.h"   // (behind the stamp table: the carried role's stamps go to this unit's)
+namespace smx {
+
 // ===========================================================================
 // BatchNorm + ReLU + Dropout.  A workgroup owns BN_COLS columns and all rows:
 // thread = (column c = tid % BN_COLS, row lane rl = tid / BN_COLS); rows are walked
@@ -1032,8 +1036,10 @@ __device__ inline void bn_wide_fwd_body(const BnFwdArgs& a) {
 __global__ __launch_bounds__(BN_THREADS) void bn_wide_fwd_kernel(BnFwdArgs a) { bn_wide_fwd_body<false>(a); }
 __global__ __launch_bounds__(BN_THREADS) void bn_wide_fwd_gen_kernel(BnFwdArgs a) { bn_wide_fwd_body<true>(a); }
 
+// `lds`: BN_WIDE_BWD_SMEM_FLOATS floats, 16-byte aligned, of the calling kernel (bn_wide_bwd_dw_kernel hands over a view of a larger array)
+constexpr int BN_WIDE_BWD_SMEM_FLOATS = 16 * 128 + 128 + 128 + 4;   // sh | vs | xs | st
 template <bool GEN_ACT>
-__device__ inline void bn_wide_bwd_body(const BnBwdArgs& a) {
+__device__ inline void bn_wide_bwd_body(const BnBwdArgs& a, float* lds) {
 #pragma clang fp contract(off)
   const int bid = (int)blockIdx.x;
   {
@@ -1050,8 +1056,8 @@ __device__ inline void bn_wide_bwd_body(const BnBwdArgs& a) {
       return;
     }
   }
-  __shared__ __attribute__((aligned(16))) float sh[16 * 128];
-  __shared__ float vs[128], xs[128], st[2];
+  float* const sh = lds;
+  float* const vs = lds + 16 * 128; float* const xs = vs + 128; float* const st = xs + 128;
   preload(a.dout, a.n_slabs, a.slab_stride, a.out, a.xhat, a.inv_std, a.gamma, a.B, a.H, a.Hp, a.batchnorm, a.training, a.drop_scale, a.dpre, a.dgamma, a.dbeta);
   const int col = bid, r = (int)threadIdx.x;
   const bool live = col < a.H, rowt = r < 128, on = rowt && r < a.B;
@@ -1112,8 +1118,59 @@ __device__ inline void bn_wide_bwd_body(const BnBwdArgs& a) {
   a.dpre[(long)r * a.Hp + col] = d;
   SMX_STAMP(2, 6);
 }
-__global__ __launch_bounds__(BN_THREADS) void bn_wide_bwd_kernel(BnBwdArgs a) { bn_wide_bwd_body<false>(a); }
-__global__ __launch_bounds__(BN_THREADS) void bn_wide_bwd_gen_kernel(BnBwdArgs a) { bn_wide_bwd_body<true>(a); }
+__global__ __launch_bounds__(BN_THREADS) void bn_wide_bwd_kernel(BnBwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float lds[BN_WIDE_BWD_SMEM_FLOATS];
+  bn_wide_bwd_body<false>(a, lds);
+}
+__global__ __launch_bounds__(BN_THREADS) void bn_wide_bwd_gen_kernel(BnBwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float lds[BN_WIDE_BWD_SMEM_FLOATS];
+  bn_wide_bwd_body<true>(a, lds);
+}
+
+// ---- bn_wide_bwd_kernel that also CARRIES the output head's dW / db / sum-of-squares slots (role 0 of out_head_bwd_kernel: smx_headdw.h) --------------
+// Only the optimiser reads those, while the chain waits for the head's launch: its two roles are bound by instruction issue and add
+// (4.0 + 4.9 -> 8.6 us at 128 x 1998 x 128), and this launch -- 128 light column workgroups -- leaves most of the chip idle.  Blocks
+// [0, Hp): the BatchNorm columns (the chain waits for these: dispatched first); then the riders as bn_wide_bwd_body indexes them; the LAST
+// h.n_w blocks: the head's dW tiles, block index rebased to 0.  A kernel of its own: role 0 needs 64 KB of LDS for two planes' partial tiles,
+// every other bn_wide_bwd launch keeps its 9 KB.  One array, each body its view (the maximum of the two, not their sum).
+// The plain (not SEP) bf16 x 3 form with 2 or 3 planes.  The head's arguments are a second by-value argument, never indexed at run time
+// (wgrad_group_kernel's note on scratch copies, smx_headbwd.hip).
+template <int NP>
+__global__ __launch_bounds__(BN_THREADS) void bn_wide_bwd_dw_kernel(BnBwdArgs a, HeadBwdArgs h) {
+  static_assert(SMX_HEAD_DW_SMEM_FLOATS >= BN_WIDE_BWD_SMEM_FLOATS && BN_THREADS == 512, "bn_wide_bwd_dw: role 0 is a 512-thread body with the larger LDS need");
+  __shared__ __attribute__((aligned(16))) float lds[SMX_HEAD_DW_SMEM_FLOATS];
+  const int first_dw = (int)gridDim.x - h.n_w;
+  if ((int)blockIdx.x >= first_dw) {   // (block-uniform)
+    preload(h.D, h.ldd, h.dP, h.ldp, h.dW, h.ldw, h.db, h.B, h.Gp, h.sq_part, h.n_w, h.n_ht, h.n_gt, h.diag, h.Hp, h.n_planes);   // (one batch: smx_device.h)
+    head_dw_body<NP, 0, 1>(h, (int)blockIdx.x - first_dw, lds);
+    return;
+  }
+  bn_wide_bwd_body<false>(a, lds);
+}
+
+// a: a wide BatchNorm-backward launch as launch_bn_act_bwd takes it (ReLU); h: the head's arguments as launch_out_head_bwd takes them (its d d fields unread)
+bool bn_wide_bwd_dw_supported(const BnBwdArgs& a, const HeadBwdArgs& h) {
+  return a.wide && !a.front && a.act == SMX_ACT_RELU && a.Hp % BN_COLS == 0 && a.B > 0 && a.B <= 128 && a.Hp <= 128 &&
+         !h.sep && h.bf16x3 && h.n_extra == 0 && (h.n_planes == 2 || h.n_planes == 3) && h.B == a.B && h.B > 0 && h.Hp % 32 == 0 && h.Gp % 32 == 0;
+}
+int launch_bn_wide_bwd_dw(hipStream_t st, const BnBwdArgs& a, const HeadBwdArgs& h_in) {
+  HeadBwdArgs h = h_in;
+  if (!bn_wide_bwd_dw_supported(a, h) || !a.dout || a.slab_stride < (long)a.Hp * 128 || (a.slab_stride % 4) || !h.D || !h.dP || !h.dW || !h.db || h.ldd < h.Hp ||
+      h.ldp < (long)h.n_planes * h.Gp || h.ldw < (long)h.n_planes * h.Gp) {
+    set_error("bn_wide_bwd_dw: bad shapes");
+    return SMX_ERR_INVALID;
+  }
+  h.n_ht = h.Hp / 32; h.n_gt = h.Gp / 32; h.n_ct = (h.B + 31) / 32;
+  h.n_w = h.n_ht * ((h.n_gt + 7) / 8 * 8);
+  h.skip_dd = 1; h.skip_dw = 0; h.diag = 0;
+  { static const int dg = (int)tuning("head_bwd_diag", 0); if (dg) h.diag = dg; }   // (timing only: bit 1 = the dW tiles return at once)
+  if (h.sq_count) *h.sq_count = h.n_ht * h.n_gt * 8;
+  const dim3 grid((unsigned)(a.Hp + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count + h.n_w));
+  if (h.n_planes == 3) hipLaunchKernelGGL(bn_wide_bwd_dw_kernel<3>, grid, dim3(BN_THREADS), 0, st, a, h);
+  else hipLaunchKernelGGL(bn_wide_bwd_dw_kernel<2>, grid, dim3(BN_THREADS), 0, st, a, h);
+  SMX_HIP(hipGetLastError());
+  return SMX_OK;
+}
 
 bool bn_wide_supported(int B, int Hp, int n_slabs) { return B > 0 && B <= 128 && Hp > 0 && Hp <= 128 && n_slabs > 0 && !tuning_on("no_bn_wide"); }
 

@@ -600,6 +600,13 @@ struct HeadBwdArgs {
 bool head_bwd_supported(int B, int Hp, int Gp);
 int head_bwd_slices(long ldp, int max_slabs, int* k_chunk);
 int launch_out_head_bwd(hipStream_t st, const HeadBwdArgs& a);
+// the decoder's wide BatchNorm-backward launch CARRYING the head's dW / db / sum-of-squares slots (smx_bn.hip: bn_wide_bwd_dw_kernel; the role-0
+// body of the launch above, smx_headdw.h): `a` as launch_bn_act_bwd takes it (wide, ReLU), `h` as the launch above takes it (plain bf16 x 3 form)
+bool bn_wide_bwd_dw_supported(const BnBwdArgs& a, const HeadBwdArgs& h);
+int launch_bn_wide_bwd_dw(hipStream_t st, const BnBwdArgs& a, const HeadBwdArgs& h);
+// ... the head's optimiser riders then start at the NEXT BatchNorm-backward launch (one decoder layer: the encoder's): the share of them it takes (the optimiser launch takes the rest;
+// knob adam_split_late; the A/B is in profiles/head_dw_late_ab.txt)
+#define SMX_ADAM_SPLIT_LATE_DEFAULT 1.0f
 
 // ---- products contracting over the gene axis of a wide panel: one workgroup per K slice + a reduce launch (smx_bigk.hip) ----
 struct BigKArgs {

@@ -312,6 +312,7 @@ struct smx_model {
   size_t bucket1_off = 0, bucket1_count = 0;   // gradients of the output / label heads: ready first, reduced early
   bool bucket1_in_flight = false;
   bool fold_dz_now = false;      // this backward pass: the d z product + latent backward run inside the encoder's BatchNorm-backward launch (smx_backward.hip)
+  bool dw_late_now = false;      // this backward pass: the decoder's BatchNorm-backward launch carries the output head's dW / db (smx_backward.hip: dw_late)
   bool chain_started = false;    // this step's head bucket went: all-reduce -> norms -> clip + Adam sweep on the communication stream (smx_backward.hip: dp_chain_start)
   // padding audit (smx_pad_audit, which = 4): rows of the last pass (stacked draws included), of the last discriminator pass, and the
   // layout the last stacked evaluation decoder used (set by its two callers, smx_predict.hip / smx_scoring.hip)

@@ -911,4 +911,6 @@ int64_t smx_head_fused_bytes(const smx_model* m, int32_t batch) {
   return head_fused_ok(m, batch) ? (int64_t)head_fused_bytes(batch, m->G, m->Gp, m->k) : 0;
 }
 
+int32_t smx_head_dw_late(const smx_model* m) { return (m && m->dw_late_now) ? 1 : 0; }   // (smx_backward.hip: dw_late)
+
 }  // extern "C"

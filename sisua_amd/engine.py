@@ -818,6 +818,10 @@ class Engine:
     """Algorithmic bytes of one launch of the fused output head when a training step of `batch` cells takes it, else 0."""
     return int(self.lib.smx_head_fused_bytes(self._h, int(batch)))
 
+  def head_dw_late(self) -> bool:
+    """The last training step left the output head's dW / db to the decoder's BatchNorm-backward launch (smx_head_dw_late)."""
+    return bool(self.lib.smx_head_dw_late(self._h))
+
   def synchronize(self):
     check(self.lib.smx_synchronize())
 
