@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 8
+#define SMX_ABI_VERSION 9
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -706,6 +706,37 @@ int smx_cluster_silhouette(const float* Z, int64_t n_cells, int32_t D, const int
  * anything else is SMX_ERR_INVALID before any device work.  Device memory: 12 x n_init x n_cells bytes. */
 int smx_cluster_kmeans(const float* Z, int64_t n_cells, int32_t D, int32_t K, const int32_t* init_idx, int32_t n_init, int32_t max_iter,
                        int32_t* labels_best, double* centres_best, double* inertia, int32_t* n_iter, int32_t* best, int32_t* labels_all);
+
+/* ---- 1-D Gaussian mixtures of ProbabilisticEmbedding (smx_gmm.hip; model-free: smx_init only) ----------- */
+/* One mixture of K Gaussians per column of the host matrix X [n_cells][C] (non-negative), R restarts per column, all C x R jobs together.
+ * The training set of a column is the reference's normalize(test_mode=False): with remove_zeros the positive cells in cell order plus ONE
+ * sample 0 if any cell was zero (else every cell); with log_norm t = log1p((double)fl32(fl32(x / fl32(s + eps)) * 1e4)), s the float64 sum
+ * of the column in cell order (col_sum [C]) and eps FLT_EPSILON, else t = x; float64 from there on.  Restart r of column c starts from the
+ * raw values init_raw [C][R][K] (normalised the same way): every sample goes to the nearest seed (ties to the lowest index), and from these
+ * one-hot responsibilities an M-step: nk = sum r + 10 DBL_EPSILON, mean = sum r t / nk, var = sum r t^2 / nk - mean^2 + reg_covar, w = nk /
+ * n_train.  Then for it = 1 .. max_iter: the E-step (log-sum-exp; lb = the mean log-likelihood), the M-step, stop at the first |lb - lb_prev|
+ * < tol (lb_prev = -inf at it = 1).  Nothing is special-cased: an empty component gets mean 0 and variance reg_covar.  lower_bound, n_iter,
+ * converged [C][R]: the last lb, the E-steps taken, whether the stop rule fired.  best [C]: the restart of highest lower bound, ties to the
+ * lowest index, NaN last; weights, means, variances [C][K] are its; n_train [C].  params_all [C][R][3][K] (may be NULL): every restart's
+ * weights, means, variances.  stats [5] (may be NULL): launches, host round trips of the loop, ms between the loop's events (its launches),
+ * ms of the loop, ms of the call.  Every sum has an order that is a function of n_cells alone (slices = min(64, ceil(n_cells / 4096)); no
+ * float atomics), so two calls give the same bits and a job's results do not depend on the other jobs of the call.  1 <= C <= 4096,
+ * 2 <= K <= 8, 1 <= R <= 64, K <= n_train of every column, 1 <= n_cells < 2^31, max_iter >= 1, tol > 0, reg_covar >= 0, no negative or
+ * non-finite entry in X or init_raw: anything else is SMX_ERR_INVALID before any device work.  Device memory: 12 x n_cells x C bytes (X and
+ * its normalised float64 copy) + 8 x C x R x (slices x (3 K + 1) + 5 K + 2) bytes. */
+int smx_gmm1d_fit(const float* X, int64_t n_cells, int32_t C, int32_t K, const float* init_raw, int32_t R, int32_t max_iter, double tol,
+                  double reg_covar, int32_t remove_zeros, int32_t log_norm, double* lower_bound, int32_t* n_iter, int32_t* converged,
+                  int32_t* best, double* weights, double* means, double* variances, int64_t* n_train, double* col_sum, double* params_all,
+                  double* stats);
+/* The embeddings of X [n_cells][C] under fitted mixtures weights, means, variances [C][K].  Normalisation as above in test mode: no zero
+ * removal, s the column sum of THIS matrix.  prob [n_cells][C]: the MEAN of the responsibilities of the components order[c][positive_component
+ * .. K - 1], order [C][K] being the components by increasing mean; bin [n_cells][C]: 1 where t >= threshold[c] (the normalised scale), else
+ * 0; score [n_cells][C] (may be NULL): the log-likelihood of the sample.  Limits on C, K, n_cells and X as above, 1 <= positive_component <
+ * K, order a permutation per column, positive finite weights and variances, finite means, no NaN threshold: anything else is
+ * SMX_ERR_INVALID before any device work.  Device memory: (16 or 24 with score) x n_cells x C bytes. */
+int smx_gmm1d_predict(const float* X, int64_t n_cells, int32_t C, int32_t K, const double* weights, const double* means, const double* variances,
+                      const int32_t* order, int32_t positive_component, const double* threshold, int32_t log_norm, double* prob, float* bin,
+                      double* score);
 
 /* ---- padding audit (test instrument; never on the path of a step) ----------- */
 /* The layout's invariant, read back from the device: every feature axis is padded to 32 and every tensor to 64 floats, and what lies

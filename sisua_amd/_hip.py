@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsisua_hip.so")
 
-SMX_ABI_VERSION = 8
+SMX_ABI_VERSION = 9
 SMX_MAX_LAYERS = 8
 SMX_MAX_LABELS = 4
 
@@ -181,6 +181,9 @@ SIGNATURES = {
     "smx_k_col_correlate": (C.c_int, [_FP, C.c_int32, C.c_int64, _IP, _DP, C.c_int32, _LP, _LP, _LP, _DP, _DP, _DP, _IP]),
     "smx_cluster_silhouette": (C.c_int, [_FP, C.c_int64, C.c_int32, _IP, C.c_int32, _DP, _DP]),
     "smx_cluster_kmeans": (C.c_int, [_FP, C.c_int64, C.c_int32, C.c_int32, _IP, C.c_int32, C.c_int32, _IP, _DP, _DP, _IP, _IP, _IP]),
+    "smx_gmm1d_fit": (C.c_int, [_FP, C.c_int64, C.c_int32, C.c_int32, _FP, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _DP, _IP,
+                            _IP, _IP, _DP, _DP, _DP, _LP, _DP, _DP, _DP]),
+    "smx_gmm1d_predict": (C.c_int, [_FP, C.c_int64, C.c_int32, C.c_int32, _DP, _DP, _DP, _IP, C.c_int32, _DP, C.c_int32, _DP, _FP, _DP]),
     "smx_pad_audit": (C.c_int, [_VP, C.c_int32, _LP, _IP, _LP, C.c_char_p, C.c_int32]),
     "smx_pad_poke": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_float]),
 }

@@ -308,6 +308,7 @@ class SingleCellOMIC:
   def __init__(self, X, var_names=None, name: str = "scOMICS", omic: str = "transcriptomic"):
     self.name = name
     self._data, self._vars = {}, {}
+    self._embeddings = {}   # omic -> (pbe, prob, bin) of probabilistic_embedding; a subset or a copy starts without
     self.add_omic(omic, X, var_names)
 
   def add_omic(self, omic: str, X, var_names=None):
@@ -316,6 +317,7 @@ class SingleCellOMIC:
     if self._data and X.shape[0] != self.n_obs:
       raise ValueError(f"Number of cell mismatch {self.n_obs} and {X.shape[0]}")
     self._data[str(omic)] = X
+    self._embeddings.pop(str(omic), None)
     self._vars[str(omic)] = np.array([f"{omic}{i}" for i in range(X.shape[1])]) if var_names is None else np.asarray(var_names)
     return self
 
@@ -381,6 +383,43 @@ class SingleCellOMIC:
 
   def library_size(self, omic=None):
     return library_matrix(self.numpy(omic))
+
+  def probabilistic_embedding(self, omic=None, n_components_per_class=2, positive_component=1, log_norm=True, clip_quartile=0.,
+                              remove_zeros=True, ci_threshold=-0.68, seed=1, pbe=None):
+    """The reference's SingleCellOMIC.probabilistic_embedding (_single_cell_analysis.py:311-383): one Gaussian mixture per column of the
+    omic, fitted on the device -> (the `ProbabilisticEmbedding`, prob [cells, C] clipped to [1e-8, 1 - 1e-8], bin [cells, C]).  A matrix
+    that holds only 0 / 1 is its own embedding (pbe None).  A given `pbe` is used without fitting.  The first result of an omic is kept on
+    the object and returned from then on; a sparse omic is densified for the call (a protein panel is narrow)."""
+    import warnings
+    from sisua_amd.label_threshold import ProbabilisticEmbedding
+    key = str(omic) if omic is not None else self.omics[0]
+    if pbe is not None and not isinstance(pbe, ProbabilisticEmbedding):
+      raise TypeError("pbe, if given, must be instance of sisua_amd.ProbabilisticEmbedding")
+    if float(clip_quartile) > 0:
+      raise ValueError("clip_quartile > 0 is not built: only clip_quartile = 0 is")
+    if key in self._embeddings:
+      return self._embeddings[key]
+    X = self.numpy(key)
+    X = X.toarray() if is_sparse(X) else X
+    if X.shape[1] >= 100:
+      warnings.warn("%d GMM will be trained!" % X.shape[1])
+    if np.all((X == 0) | (X == 1)):
+      self._embeddings[key] = (None, X, X)
+      return self._embeddings[key]
+    if pbe is None:
+      pbe = ProbabilisticEmbedding(n_components_per_class=n_components_per_class, positive_component=positive_component, log_norm=log_norm,
+                                   clip_quartile=clip_quartile, remove_zeros=remove_zeros, ci_threshold=ci_threshold, random_state=seed)
+      pbe.fit(X)
+    prob = np.clip(pbe.predict_proba(X), 0. + 1e-8, 1. - 1e-8)
+    self._embeddings[key] = (pbe, prob, pbe.predict(X))
+    return self._embeddings[key]
+
+  def get_x_probs(self, omic=None):
+    """The probability embedding of an omic (`probabilistic_embedding` with its defaults, or what an earlier call left)"""
+    return self.probabilistic_embedding(omic=omic)[1]
+
+  def get_x_bins(self, omic=None):
+    return self.probabilistic_embedding(omic=omic)[2]
 
   def get_rv(self, omic, distribution=None):
     from sisua_amd.config import RVmeta
