@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 9
+#define SMX_ABI_VERSION 10
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -737,6 +737,36 @@ int smx_gmm1d_fit(const float* X, int64_t n_cells, int32_t C, int32_t K, const f
 int smx_gmm1d_predict(const float* X, int64_t n_cells, int32_t C, int32_t K, const double* weights, const double* means, const double* variances,
                       const int32_t* order, int32_t positive_component, const double* threshold, int32_t log_norm, double* prob, float* bin,
                       double* score);
+
+/* ---- full-covariance Gaussian mixture of the clustering scores (smx_gmm_full.hip; model-free: smx_init only) ----------- */
+/* scikit-learn's GaussianMixture(K, covariance_type='full') loop on the host cells Z [n_cells][D], run from R starting labelings
+ * init_labels [R][n_cells] (each entry in 0 .. K - 1), all restarts together, float64 throughout.  Restart r: one-hot responsibilities from
+ * init_labels[r], then an M-step: nk = sum_n r_nk + 10 DBL_EPSILON, w_k = nk / n_cells, mu_k = sum_n r_nk z_n / nk, S_k = sum_n r_nk (z_n -
+ * mu_k)(z_n - mu_k)^T / nk + reg_covar I in the two-pass form (means first, then differences; the lower triangle, mirrored), L_k = chol(S_k),
+ * Linv_k = L_k^-1, logdet_k = -sum_d log L_k[d][d].  Then for it = 1 .. max_iter: the E-step l_nk = log w_k + logdet_k - (D log(2 pi) +
+ * |Linv_k (z_n - mu_k)|^2) / 2 (the difference before the triangular product), r_nk = exp(l_nk - lse_n) with the row maximum taken out, lb =
+ * the mean of lse_n; the M-step; stop at the first |lb - lb_prev| < tol (lb_prev = -inf at it = 1).  lower_bound, n_iter, converged [R]: the
+ * last lb, the E-steps taken, whether the stop rule fired (at max_iter without it: converged = 0 and the parameters of the last M-step).
+ * A restart whose covariance meets a Cholesky pivot that is not a positive finite number stops there: status[r] = 1, lower_bound[r] = NaN, it
+ * ranks last; SMX_ERR_INVALID is returned only when EVERY restart failed (lower_bound, n_iter, converged and status are filled even then).
+ * *best: the restart of highest lower bound, ties to the lowest index.  weights [K], means [K][D], covariances [K][D][D], chol_inv [K][D][D]
+ * (Linv_k: lower triangular, zeros above the diagonal -- the one thing the E-step reads) are its; labels [n_cells] = argmax_k l_nk of a final
+ * E-step under them, ties to the lowest k.  params_all (may be NULL): per restart K weights, K D means, K D D covariances, [R][K + K D + K D
+ * D].  Every sum has an order that is a function of n_cells alone (slices = min(64, ceil(n_cells / 1024)); no float atomics): two calls give
+ * the same bits, and a restart's results do not depend on the others of the call.  1 <= D <= 64, 2 <= K <= 256, K <= n_cells < 2^31, 1 <= R
+ * <= 8, max_iter >= 1, tol > 0, reg_covar >= 0, every init_labels entry in range, no non-finite entry in Z: anything else is SMX_ERR_INVALID
+ * before any device work.  Device memory: 8 R K n_cells bytes of responsibilities + 4 n_cells D (Z) + 4 (R + 1) n_cells (labels) + 8 R K
+ * slices (D (D + 1) / 2 + D + 1) of partial sums + 8 R K (2 D D + D + 2) of parameters. */
+int smx_gmm_full_fit(const float* Z, int64_t n_cells, int32_t D, int32_t K, const int32_t* init_labels, int32_t R, int32_t max_iter, double tol,
+                     double reg_covar, double* lower_bound, int32_t* n_iter, int32_t* converged, int32_t* status, int32_t* best,
+                     double* weights, double* means, double* covariances, double* chol_inv, int32_t* labels, double* params_all);
+/* The E-step above on Z [n_cells][D] under given parameters: labels [n_cells] = argmax_k l_nk (ties to the lowest k), resp [n_cells][K] (may
+ * be NULL) the responsibilities, score [n_cells] (may be NULL) lse_n, the log-likelihood of the cell.  logdet_k = sum_d log chol_inv_k[d][d].
+ * Limits on D, K, n_cells and Z as above; positive finite weights, finite means, a finite chol_inv with a positive diagonal (what lies above
+ * the diagonal is not read): anything else is SMX_ERR_INVALID before any device work.  Device memory: (8 K + 4 D + 4 (+ 8 with score)) n_cells
+ * bytes. */
+int smx_gmm_full_predict(const float* Z, int64_t n_cells, int32_t D, int32_t K, const double* weights, const double* means, const double* chol_inv,
+                         int32_t* labels, double* resp, double* score);
 
 /* ---- padding audit (test instrument; never on the path of a step) ----------- */
 /* The layout's invariant, read back from the device: every feature axis is padded to 32 and every tensor to 64 floats, and what lies

@@ -162,3 +162,52 @@ def clustering_scores(latent, labels, n_labels, prediction_algorithm="knn", n_in
   km = k_cluster_kmeans(z, draw_init_idx(z.shape[0], int(n_labels), n_init, seed), max_iter=max_iter)
   pred = km["labels"]
   return dict(ASW=asw, ARI=adjusted_rand(y, pred), NMI=normalized_mutual_info(y, pred), UCA=unsupervised_clustering_accuracy(y, pred))
+
+
+# ---- the reference's complete function: k-means, the Gaussian mixture, or both -------------------------------------------------------
+def _mixture_labels(z, n_labels, seed, n_init, max_iter):
+  from sisua_amd.engine import k_cluster_kmeans
+  from sisua_amd.mixture import GaussianMixture, starts_from_kmeans
+  km = k_cluster_kmeans(z, draw_init_idx(z.shape[0], n_labels, n_init, seed), max_iter=max_iter, all_labels=True)
+  gm = GaussianMixture(n_labels, random_state=seed, kmeans_n_init=n_init, kmeans_max_iter=max_iter)
+  labels = gm._fit_from_labels(z, starts_from_kmeans(km, 1))
+  return dict(labels=labels, kmeans_labels=km["labels"], mixture=gm)
+
+
+def mixture_labels(latent, n_labels, seed=DEFAULT_SEED, n_init=200, max_iter=300) -> dict:
+  """The two predicted labelings of the reference's `clustering_scores` from ONE run of the k-means restarts: dict(kmeans_labels -- the
+  restart of lowest inertia --, labels -- those of `mixture.GaussianMixture(n_labels)` (full covariances, max_iter 100, tol 1e-3, reg_covar
+  1e-6) started from that partition --, mixture: the fitted instance).  n_init, seed, max_iter: of the k-means restarts."""
+  from sisua_amd.mixture import check_cells, check_settings
+  n_labels, n_init, max_iter = int(n_labels), int(n_init), int(max_iter)
+  check_settings(n_labels, 1e-3, 1e-6, 100, 1, n_init, max_iter)   # (the mixture's own settings are its defaults)
+  z = check_cells(latent, n_labels)
+  return _mixture_labels(z, n_labels, seed, n_init, max_iter)
+
+
+def latent_scores(latent, labels, n_labels, prediction_algorithm="both", n_init=200, seed=DEFAULT_SEED, max_iter=300) -> Dict[str, float]:
+  """The reference's `clustering_scores` with its default (latent_benchmarks.py:69-117): {'ASW', 'ARI', 'NMI', 'UCA'} of a latent space with
+  the predicted labels of 'knn' (k-means: exactly `clustering_scores`), 'gmm' (the full-covariance Gaussian mixture, `mixture_labels`) or
+  'both': the per-key average (v1 + v2) / 2 of the two, ASW included as the reference has it.  The silhouette sums and the k-means restarts
+  run once.  The mixture is built for a latent width of 1 .. 64."""
+  if prediction_algorithm == "knn":
+    return clustering_scores(latent, labels, n_labels, "knn", n_init=n_init, seed=seed, max_iter=max_iter)
+  if prediction_algorithm not in ("gmm", "both"):
+    raise ValueError(f"Not support for prediction_algorithm: '{prediction_algorithm}'")
+  from sisua_amd.mixture import check_cells, check_settings
+  z, y = _check_latent(latent, labels, n_labels)
+  n_init, max_iter = int(n_init), int(max_iter)
+  check_settings(int(n_labels), 1e-3, 1e-6, 100, 1, n_init, max_iter)
+  z = check_cells(z, int(n_labels))   # (the mixture's limits: a width of 1 .. 64, no non-finite entry)
+  from sisua_amd.engine import k_cluster_silhouette
+  a, b = k_cluster_silhouette(z, y, int(n_labels))
+  counts = np.bincount(y, minlength=int(n_labels))
+  asw, _ = silhouette_from_sums(a, b, singleton=counts[y] == 1)
+  both = _mixture_labels(z, int(n_labels), seed, n_init, max_iter)
+  score = lambda pred: dict(ASW=asw, ARI=adjusted_rand(y, pred), NMI=normalized_mutual_info(y, pred),
+                            UCA=unsupervised_clustering_accuracy(y, pred))
+  s2 = score(both["labels"])
+  if prediction_algorithm == "gmm":
+    return s2
+  s1 = score(both["kmeans_labels"])
+  return {k: (s1[k] + s2[k]) / 2 for k in s1}

@@ -1100,6 +1100,68 @@ def k_gmm1d_predict(X, weights, means, variances, order, positive_component: int
   return prob, bins, sc
 
 
+ILL_DEFINED_COVARIANCE = ("Fitting the mixture model failed because some components have ill-defined empirical covariance (for instance "
+                          "caused by singleton or collapsed samples). Try to decrease the number of components, increase reg_covar, or "
+                          "scale the input data.")
+
+
+def k_gmm_full_fit(Z, init_labels, max_iter: int = 100, tol: float = 1e-3, reg_covar: float = 1e-6, all_params: bool = False,
+                   n_components=None) -> dict:
+  """smx_gmm_full_fit: scikit-learn's full-covariance EM loop on cells Z [N, D] from the starting labelings init_labels [R, N] (or [N]), K =
+  n_components (default: the largest label + 1) -> dict(lower_bound, n_iter, converged, status [R]; best; weights [K], means [K, D],
+  covariances, chol_inv [K, D, D] and labels [N] of the best restart; with all_params weights_all [R, K], means_all [R, K, D],
+  covariances_all [R, K, D, D]).  A restart with status 1 met an ill-defined covariance; ValueError when every restart did."""
+  z = _f32(Z)
+  lab = np.asarray(init_labels)
+  if lab.ndim == 1:
+    lab = lab[None, :]
+  if z.ndim != 2 or lab.ndim != 2 or lab.shape[1] != z.shape[0]:
+    raise ValueError(f"Z must be [cells, D] and init_labels [R, cells], got {z.shape} and {lab.shape}")
+  lab = np.ascontiguousarray(lab, dtype=np.int32)
+  K = (int(lab.max()) + 1 if lab.size else 0) if n_components is None else int(n_components)
+  (N, D), R = z.shape, lab.shape[0]
+  lib = _hip.require_gpu()
+  out = dict(lower_bound=np.empty((R,), np.float64), n_iter=np.empty((R,), np.int32), converged=np.empty((R,), np.int32),
+             status=np.zeros((R,), np.int32), weights=np.empty((max(K, 0),), np.float64), means=np.empty((max(K, 0), D), np.float64),
+             covariances=np.empty((max(K, 0), D, D), np.float64), chol_inv=np.empty((max(K, 0), D, D), np.float64), labels=np.empty((N,), np.int32))
+  best = C.c_int32(-1)
+  every = np.empty((R, max(K, 0) * (1 + D + D * D)), np.float64) if all_params else None
+  rc = lib.smx_gmm_full_fit(_fp(z), N, D, K, _ip(lab), R, int(max_iter), float(tol), float(reg_covar), _dp(out["lower_bound"]), _ip(out["n_iter"]),
+                            _ip(out["converged"]), _ip(out["status"]), C.byref(best), _dp(out["weights"]), _dp(out["means"]),
+                            _dp(out["covariances"]), _dp(out["chol_inv"]), _ip(out["labels"]), None if every is None else _dp(every))
+  if rc == -1 and R >= 1 and bool(np.all(out["status"] == 1)):   # (SMX_ERR_INVALID with every status set: every restart failed)
+    raise ValueError(ILL_DEFINED_COVARIANCE)
+  check(rc)
+  out["best"] = int(best.value)
+  if every is not None:
+    out["weights_all"] = every[:, :K].copy()
+    out["means_all"] = every[:, K:K + K * D].reshape(R, K, D).copy()
+    out["covariances_all"] = every[:, K + K * D:].reshape(R, K, D, D).copy()
+  return out
+
+
+def k_gmm_full_predict(Z, weights, means, chol_inv, resp: bool = False, score: bool = False) -> dict:
+  """smx_gmm_full_predict: cells Z [N, D] under the mixture weights [K], means [K, D], chol_inv [K, D, D] (lower triangular: the inverse of
+  the Cholesky factor of every covariance) -> dict(labels [N] int32; resp [N, K] and score [N] float64 when asked)"""
+  w, m, li = (np.ascontiguousarray(a, dtype=np.float64) for a in (weights, means, chol_inv))
+  if w.ndim != 1 or m.ndim != 2 or m.shape[0] != w.shape[0] or li.shape != (m.shape[0], m.shape[1], m.shape[1]):
+    raise ValueError(f"weights, means and chol_inv must be [K], [K, D] and [K, D, D], got {w.shape}, {m.shape} and {li.shape}")
+  K, D = m.shape
+  z = _f32(Z)
+  if z.ndim != 2 or z.shape[1] != D:
+    raise ValueError(f"the mixture has {D} features, Z is {z.shape}")
+  lib = _hip.require_gpu()
+  N = z.shape[0]
+  out = dict(labels=np.empty((N,), np.int32))
+  if resp:
+    out["resp"] = np.empty((N, K), np.float64)
+  if score:
+    out["score"] = np.empty((N,), np.float64)
+  check(lib.smx_gmm_full_predict(_fp(z), N, D, K, _dp(w), _dp(m), _dp(li), _ip(out["labels"]), _dp(out["resp"]) if resp else None,
+                                 _dp(out["score"]) if score else None))
+  return out
+
+
 def k_noise(seed, stream, step, cell_ids, width, p=0.0, sample=0):
   lib = _hip.require_gpu()
   ids = np.ascontiguousarray(cell_ids, dtype=np.int64)

@@ -10,7 +10,7 @@ from typing import Dict, Iterable, List, Mapping, Sequence, Tuple
 
 import numpy as np
 
-from sisua_amd.clustering import clustering_scores   # noqa: F401  (latent_benchmarks.py:69-117; the distances and restarts on the device)
+from sisua_amd.clustering import clustering_scores, latent_scores   # noqa: F401  (latent_benchmarks.py:69-117; distances, restarts and EM on the device)
 from sisua_amd.data import SingleCellOMIC, corrupt as _corrupt, is_sparse
 
 
@@ -86,21 +86,25 @@ class ClusteringScores:
   """The scores of sc_metrics.py:351-402: `clustering_scores` of the mean of every latent posterior of the model against the protein
   levels `extras` [cells, proteins] -- labels = argmax(extras, 1), n_labels = the number of proteins.  One entry per latent (`ASW_0`, ...;
   `_1` is SCVI's library latent), plus the plain keys as the mean over the latents; all values NEGATED, as the reference does (a loss:
-  lower is better).  inputs: the counts the cells are encoded from; kw: keywords of `clustering_scores` (n_init, seed, max_iter)."""
+  lower is better).  inputs: the counts the cells are encoded from; prediction_algorithm: 'knn' (k-means, `clustering_scores`), or 'gmm' /
+  'both' through `latent_scores`; kw: keywords of `clustering_scores` (n_init, seed, max_iter)."""
 
-  def __init__(self, inputs, extras, batch_size=64, **kw):
+  def __init__(self, inputs, extras, batch_size=64, prediction_algorithm="knn", **kw):
     self.inputs = _matrix(inputs)
     ex = _matrix(extras)
     ex = np.asarray(ex.toarray() if is_sparse(ex) else ex)
     if ex.ndim != 2 or ex.shape[0] != self.inputs.shape[0] or ex.shape[1] < 2:
       raise ValueError("extras must be [cells, proteins >= 2] for the cells of inputs")
     self.labels, self.n_labels = np.argmax(ex, axis=1), int(ex.shape[1])
-    self.batch_size, self.kw = int(batch_size), dict(kw)
+    self.batch_size, self.kw, self.prediction_algorithm = int(batch_size), dict(kw), prediction_algorithm
 
   def __call__(self, model) -> Dict[str, float]:
     scores, avg = {}, {}
+    knn = self.prediction_algorithm == "knn"
     for idx, z in enumerate(model._latent_means(self.inputs, None, self.batch_size)):
-      for key, val in clustering_scores(z, self.labels, self.n_labels, **self.kw).items():
+      found = clustering_scores(z, self.labels, self.n_labels, **self.kw) if knn else \
+          latent_scores(z, self.labels, self.n_labels, self.prediction_algorithm, **self.kw)
+      for key, val in found.items():
         scores[f"{key}_{idx}"] = -val
         avg.setdefault(key, []).append(-val)
     scores.update({k: float(np.mean(v)) for k, v in avg.items()})

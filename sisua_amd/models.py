@@ -968,20 +968,24 @@ class SingleCellModel:
     ex = extras.numpy() if isinstance(extras, SingleCellOMIC) else extras
     return self._imputation_handle(inputs, library, sample_shape, batch_size).correlation(ex, genes=genes)
 
-  def clustering_scores(self, inputs, labels, n_labels=None, library=None, batch_size=128, **kw):
+  def clustering_scores(self, inputs, labels, n_labels=None, library=None, batch_size=128, prediction_algorithm="knn", **kw):
     r"""The reference's `clustering_scores` (analysis/latent_benchmarks.py:69-117) of this model's latent space: the cells of `inputs`
     (dense or scipy.sparse) are encoded and the mean of the latent posterior -- a deterministic latent: the latent itself -- is scored
     against `labels` ([cells] class indices, or 2-D one-hot / protein levels: min-max per column, then argmax): {'ASW', 'ARI', 'NMI',
     'UCA'}.  The distances and the k-means restarts run on the device (`sisua_amd.clustering.clustering_scores`, whose keywords `kw` are).
     n_labels: default the columns of 2-D labels, else the number of distinct labels -- 1-D labels must lie in 0 .. n_labels - 1, so
     with the default they have to be the contiguous indices 0 .. n - 1; labels with gaps (say 0, 2, 5) need n_labels passed (6 there:
-    the unused ids are empty classes, which the silhouette passes over)."""
-    from sisua_amd.clustering import clustering_scores, prepare_labels
+    the unused ids are empty classes, which the silhouette passes over).  prediction_algorithm: 'knn' (k-means), or 'gmm' / 'both' (the
+    full-covariance Gaussian mixture, and the reference's default average of the two) through `sisua_amd.clustering.latent_scores`."""
+    from sisua_amd.clustering import clustering_scores, latent_scores, prepare_labels
     lab = labels.numpy() if isinstance(labels, SingleCellOMIC) else labels
     lab = np.asarray(lab.toarray() if is_sparse(lab) else lab)
     if n_labels is None:
       n_labels = lab.shape[1] if lab.ndim == 2 else np.unique(lab).size
-    return clustering_scores(self._latent_means(inputs, library, batch_size)[0], prepare_labels(lab), n_labels, **kw)
+    z = self._latent_means(inputs, library, batch_size)[0]
+    if prediction_algorithm != "knn":
+      return latent_scores(z, prepare_labels(lab), n_labels, prediction_algorithm, **kw)
+    return clustering_scores(z, prepare_labels(lab), n_labels, **kw)
 
   def _latent_means(self, inputs, library, batch_size):
     """What `encode(...)`'s distributions have as their mean, through the minibatch walk of `predict` and nothing else off the device:
