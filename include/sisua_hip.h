@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 10
+#define SMX_ABI_VERSION 11
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -767,6 +767,37 @@ int smx_gmm_full_fit(const float* Z, int64_t n_cells, int32_t D, int32_t K, cons
  * bytes. */
 int smx_gmm_full_predict(const float* Z, int64_t n_cells, int32_t D, int32_t K, const double* weights, const double* means, const double* chol_inv,
                          int32_t* labels, double* resp, double* score);
+
+/* ---- count-matrix preprocessing (smx_prep.hip; model-free: smx_init only) ----------- */
+/* Both entries take a host matrix of n_cells x n_genes either dense (x [n_cells][n_genes] float32; indptr = cols = vals = NULL) or as CSR
+ * (x = NULL; indptr / cols / vals in the layout of smx_predict_csr, every column in 0 .. n_genes - 1) and stream it through the device in
+ * blocks of block_rows rows (0: the library's choice, about 64 MiB of tile; a given value is rounded up to a multiple of 64 and capped at
+ * 1 GiB of tile; CSR blocks cross as CSR and are expanded on the device).  They work on a VIEW of the matrix: the value of entry (r, g) is
+ * f(x[r][g] / row_div[r]) in float32 with the IEEE division -- row_div [n_cells] float32 (NULL: no division), func 0 the identity,
+ * 1 log1pf, 2 expm1f.  n_cells < 2^31, n_genes <= 2^20, a row divisor finite and not 0: anything else is SMX_ERR_INVALID before any
+ * device work.
+ *
+ * smx_prep_stats: the statistics of the view.  cell_total [n_cells]: the float64 sum of the cell's values over the genes (with col_mask
+ * [n_genes] uint8, may be NULL: over the genes whose mask is not 0); cell_n_genes [n_cells]: its values > 0.  gene_sum, gene_sumsq
+ * [n_genes]: the float64 sums of the float32 values and of their (exact) squares over the cells; gene_n_cells [n_genes]: its values > 0;
+ * gene_n_above [n_genes] (with row_thresh [n_cells] float32, no NaN; both or neither): the cells whose value > row_thresh[r].  Every sum
+ * has an order that is a function of the global row and column ids alone (a cell: 64 lanes over the columns, then a fixed tree; a gene:
+ * slices of 64 consecutive rows added in row order, the slices in order; no atomics), so the results are the same bits for every
+ * block_rows, for dense and CSR input, from call to call, and for "the view of X" and "the identity view of what smx_prep_apply wrote for
+ * X under that view": the view is evaluated by the same kernel in both.
+ *
+ * smx_prep_apply: the view written out as float32.  out_dense [n_cells][n_genes] (may be x itself): with mean and sd [n_genes] float32
+ * (both or neither) the value is then (v - mean[g]) / sd[g], and with clip != 0 it is then min(., max_value) (a NaN stays).  out_vals
+ * [nnz], aligned with vals: CSR input without mean / sd / clip only -- the structure is unchanged, only the stored values cross.  Exactly
+ * one of out_dense and out_vals.  Device memory of either entry: the tile, the staged CSR block, and 24 bytes x (block_rows / 64) x
+ * n_genes of partial sums. */
+int smx_prep_stats(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_cells, int32_t n_genes,
+                   int32_t block_rows, int32_t func, const float* row_div, const uint8_t* col_mask, const float* row_thresh,
+                   double* cell_total, int32_t* cell_n_genes, double* gene_sum, double* gene_sumsq, int64_t* gene_n_cells,
+                   int64_t* gene_n_above);
+int smx_prep_apply(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_cells, int32_t n_genes,
+                   int32_t block_rows, int32_t func, const float* row_div, const float* mean, const float* sd, int32_t clip,
+                   float max_value, float* out_dense, float* out_vals);
 
 /* ---- padding audit (test instrument; never on the path of a step) ----------- */
 /* The layout's invariant, read back from the device: every feature axis is padded to 32 and every tensor to 64 floats, and what lies

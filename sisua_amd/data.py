@@ -303,7 +303,8 @@ class BatchDataset:
 
 class SingleCellOMIC:
   """Multi-omic cells x features container with the methods the training path calls on the
-  reference's SingleCellOMIC: split, corrupt, library statistics, create_dataset, get_rv."""
+  reference's SingleCellOMIC: split, corrupt, library statistics, create_dataset, get_rv, and the preprocessing its loaders call first:
+  filter_cells, filter_genes, normalize, expm1, filter_highly_variable_genes."""
 
   def __init__(self, X, var_names=None, name: str = "scOMICS", omic: str = "transcriptomic"):
     self.name = name
@@ -383,6 +384,80 @@ class SingleCellOMIC:
 
   def library_size(self, omic=None):
     return library_matrix(self.numpy(omic))
+
+  # ---- preprocessing (sisua_amd/preprocess.py; the matrix work runs on the device: smx_prep.hip) ----
+  def _first(self, omic=None) -> str:
+    return str(omic) if omic is not None else self.omics[0]
+
+  def _replace(self, key: str, X, var_names=None):
+    """A new matrix for an omic already held (same cells); its embedding, if any, no longer describes it"""
+    self._data[key] = as_csr(X) if is_sparse(X) else np.ascontiguousarray(X, dtype=np.float32)
+    self._embeddings.pop(key, None)
+    if var_names is not None:
+      self._vars[key] = np.asarray(var_names)
+
+  def filter_cells(self, min_counts=None, max_counts=None, min_genes=None, max_genes=None, inplace=True):
+    """The reference's filter_cells (scanpy.pp.filter_cells on the first omic): exactly one bound; a cell is kept when its total count
+    (`*_counts`) or its number of expressed genes (`*_genes`) is >= the minimum or <= the maximum.  The cells leave every omic."""
+    from sisua_amd import preprocess
+    keep, _ = preprocess.filter_cells(self.numpy(), min_counts, max_counts, min_genes, max_genes)
+    om = self if inplace else self.copy()
+    for key in om.omics:
+      om._replace(key, om._data[key][keep])
+    om.name += "_filtercell"
+    return om
+
+  def filter_genes(self, min_counts=None, max_counts=None, min_cells=None, max_cells=None, inplace=True):
+    """The reference's filter_genes (scanpy.pp.filter_genes on the first omic): exactly one bound on a gene's total count or on the number
+    of cells that express it.  The genes leave the first omic and its var_names."""
+    from sisua_amd import preprocess
+    keep, _ = preprocess.filter_genes(self.numpy(), min_counts, max_counts, min_cells, max_cells)
+    om = self if inplace else self.copy()
+    key = om.omics[0]
+    om._replace(key, om._data[key][:, keep], om._vars[key][keep])
+    om.name += "_filtergene"
+    return om
+
+  def filter_highly_variable_genes(self, min_disp=1.0, max_disp=np.inf, min_mean=0.01, max_mean=8, n_top_genes=1000, n_bins=20,
+                                   flavor="seurat", inplace=True):
+    """The reference's filter_highly_variable_genes (scanpy.pp.highly_variable_genes, subset=True; expects logarithmised data): the first
+    omic keeps its highly variable genes.  `highly_variable_features` of the result holds highly_variable, means, dispersions and
+    dispersions_norm of every gene it had before."""
+    from sisua_amd import preprocess
+    res = preprocess.highly_variable_genes(self.numpy(), min_disp, max_disp, min_mean, max_mean, n_top_genes, n_bins, flavor)
+    om = self if inplace else self.copy()
+    key, keep = om.omics[0], res["highly_variable"]
+    om._replace(key, om._data[key][:, keep], om._vars[key][keep])
+    om.highly_variable_features = {k: res[k] for k in ("highly_variable", "means", "dispersions", "dispersions_norm")}
+    om.name += "_vargene"
+    return om
+
+  def expm1(self, omic=None, inplace=True):
+    from sisua_amd import preprocess
+    key = self._first(omic)
+    X = preprocess.apply_view(self.numpy(key), func="expm1")
+    om = self if inplace else self.copy()
+    om._replace(key, X)
+    return om
+
+  def normalize(self, omic=None, total=False, log1p=False, scale=False, target_sum=None, exclude_highly_expressed=False,
+                max_fraction=0.05, max_value=None, inplace=True):
+    """The reference's normalize (scanpy.pp.normalize_total, log1p, scale, in this order, each where asked).  The stages are composed into
+    one view f(x / c) of the matrix, so it crosses to the device once per pass; a sparse omic stays sparse unless it is scaled.
+    max_value clips from above only."""
+    from sisua_amd import preprocess
+    preprocess.check_normalize(target_sum, max_fraction, max_value)
+    key = self._first(omic)
+    X = self.numpy(key)
+    suffix = ("_total" if total else "") + ("_log1p" if log1p else "") + ("_scale" if scale else "")
+    if suffix:
+      c = preprocess.total_size_factors(X, target_sum, exclude_highly_expressed, max_fraction) if total else None
+      X = preprocess.apply_view(X, func="log1p" if log1p else None, row_div=c, scale=bool(scale), max_value=max_value)
+    om = self if inplace else self.copy()
+    if suffix:
+      om._replace(key, X)
+      om.name += suffix
+    return om
 
   def probabilistic_embedding(self, omic=None, n_components_per_class=2, positive_component=1, log_norm=True, clip_quartile=0.,
                               remove_zeros=True, ci_threshold=-0.68, seed=1, pbe=None):
