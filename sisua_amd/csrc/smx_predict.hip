@@ -110,7 +110,8 @@ struct PackList {
 
 // ---- statistics of the gene output on the device (smx_predict_stat): what the reference's callers ask of predict()'s result --
 // y.mean() / .variance() / .log_prob(x), posterior.py:187-255 -- computed from the parameter planes of a pass WITHOUT the planes leaving
-// the device (24 KB per cell and draw at C2: predict's D2H traffic).  Formulas = sisua_amd/distributions.py (float32 here).
+// the device (24 KB per cell and draw at C2: predict's D2H traffic).  Formulas = sisua_amd/distributions.py (float32 here); held to
+// float64 at saturated planes by tests/test_gpu_plane_stats.py (bounds: tests/plane_stat_ref.py).
 struct StatArgs {
   const float* P; long ldp; long plane_stride;   // planes of `rows` = Sn * B stacked rows (row s * B + b = draw s of cell b)
   int B, Sn, G, lk, direct, count_only, stat;    // stat: 0 mean, 1 variance (per draw), 2 mean averaged over the draws, 3 log_prob
@@ -124,11 +125,14 @@ __device__ inline void plane_moments(int lk, int direct, int count_only, float p
   if (lk == SMX_LLK_NB || lk == SMX_LLK_ZINB) { const float el = expf(p1); mc = expf(p0) * el; vc = mc * (1.f + el); }
   else {
     const float mu = direct ? p0 : softplus_sigmoid(p0).sp, th = direct ? p1 : softplus_sigmoid(p1 + SMX_SOFTPLUS_INV_1).sp;
-    mc = mu; vc = mu + mu * mu / th;
+    // mu (1 + mu / th), not mu + mu mu / th: mu mu underflows where the variance is still a normal number (mu ~ th ~ 1e-26: 37 % off);
+    // mu == 0 (both underflowed: 0 / 0) has variance 0
+    mc = mu; vc = mu > 0.f ? mu * (1.f + mu / th) : 0.f;
   }
   if ((lk == SMX_LLK_ZINB || lk == SMX_LLK_ZINBD) && !count_only) {
-    const float pi = 1.f / (1.f + expf(-p2));
-    mean = (1.f - pi) * mc; var = (1.f - pi) * (vc + pi * mc * mc);
+    // 1 - pi as sigmoid(-p2): the difference 1 - pi cancels from a gate logit of a few units on and is exactly 0 from 17
+    const float pi = 1.f / (1.f + expf(-p2)), q = sigmoidf(-p2);
+    mean = q * mc; var = q * (vc + pi * mc * mc);
   } else { mean = mc; var = vc; }
 }
 __global__ __launch_bounds__(256) void plane_stat_kernel(StatArgs a) {
@@ -180,10 +184,10 @@ __global__ __launch_bounds__(256) void plane_logprob_kernel(StatArgs a) {
   if (threadIdx.x == 0) a.dst[(long)s * a.dst_draw + b] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 // The same statistics of the 'bernoulli' (logits) and 'normal' (loc | raw scale) outputs, as kernels of their own (the count kernels above
-// stay as they are): Bernoulli mean p = sigmoid(l), variance p (1 - p); normal mean m, variance sigma^2, sigma = softplus(s + softplus^-1(1));
+// stay as they are): Bernoulli mean p = sigmoid(l), variance sigmoid(l) sigmoid(-l); normal mean m, variance sigma^2, sigma = softplus(s + softplus^-1(1));
 // log_prob = the sum over the genes of smx_loss.h's bernoulli_elem / normal_elem (no count constant).  count_only changes nothing here.
 __device__ inline void rv_moments(int lk, float p0, float p1, float& mean, float& var) {
-  if (lk == SMX_LLK_BERNOULLI) { const float p = 1.f / (1.f + expf(-p0)); mean = p; var = p * (1.f - p); }
+  if (lk == SMX_LLK_BERNOULLI) { const float p = 1.f / (1.f + expf(-p0)); mean = p; var = sigmoidf(p0) * sigmoidf(-p0); }   // (not p (1 - p): see plane_moments)
   else { const float sd = softplus_sigmoid(p1 + SMX_SOFTPLUS_INV_1).sp; mean = p0; var = sd * sd; }
 }
 __global__ __launch_bounds__(256) void plane_stat_rv_kernel(StatArgs a) {

@@ -244,7 +244,9 @@ class NegativeBinomialDisp(Distribution):
     return np.broadcast_to(self.loc, np.broadcast_shapes(self.loc.shape, self.disp.shape)).copy()
 
   def variance(self):
-    return self.loc + self.loc ** 2 / self.disp
+    # mu (1 + mu / th): mu^2 underflows in float32 where the variance is still a normal number; mu == 0 has variance 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+      return np.where(self.loc > 0, self.loc * (1.0 + self.loc / self.disp), self.loc * 0.0)
 
   def log_prob(self, x):
     x, mu, th, e = np.asarray(x, np.float64), self.loc.astype(np.float64), self.disp.astype(np.float64), self.eps
@@ -271,12 +273,17 @@ class ZeroInflated(Distribution):
   def probs(self):
     return 1.0 / (1.0 + np.exp(-self.logits))
 
+  @property
+  def _complement(self):
+    """1 - probs as sigmoid(-logits): the difference cancels from a logit of a few units on (float32: exactly 0 from 17)"""
+    return expit(-self.logits)
+
   def mean(self):
-    return (1.0 - self.probs) * self.count_distribution.mean()
+    return self._complement * self.count_distribution.mean()
 
   def variance(self):
-    pi, m, v = self.probs, self.count_distribution.mean(), self.count_distribution.variance()
-    return (1.0 - pi) * (v + pi * m * m)
+    pi, q, m, v = self.probs, self._complement, self.count_distribution.mean(), self.count_distribution.variance()
+    return q * (v + pi * m * m)
 
   def log_prob(self, x):
     x = np.asarray(x, np.float64)
@@ -342,8 +349,8 @@ class Bernoulli(Distribution):
     return self.probs
 
   def variance(self):
-    p = self.probs
-    return p * (1 - p)
+    l = self.logits.astype(np.float64)
+    return expit(l) * expit(-l)   # (not p (1 - p): 1 - p cancels at saturated logits)
 
   def log_prob(self, x):
     l = self.logits.astype(np.float64)

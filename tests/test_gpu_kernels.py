@@ -84,6 +84,33 @@ def test_count_llk_edge_grid(eng, lk):
     assert (err <= tol).all(), (lk, i, err.max(), np.unravel_index(np.argmax(err - tol), err.shape))
 
 
+@pytest.mark.parametrize("lk", ["zinb", "zinbd"])
+def test_count_llk_saturated_gate(eng, lk):
+  """The edge grid above draws its gate plane from uniform(-6, 6).  Here the gate logit runs from -40 to 80 (the axis of
+  tests/plane_stat_ref.py) against x in {0, 1, 181, 10738} at two count points, every row ONE point repeated 64 times: a row sum is 64
+  times one element and cannot hide it.  Log-likelihood and the three gradients against float64 at the grid test's tolerances -- the gate
+  gradient at x = 0 is (1 - w) - sigmoid(g), a difference of two numbers near 1 once the gate saturates."""
+  gate = [-40.0, -20.0, -8.0, -1.0, 0.0, 1.0, 4.0, 8.0, 12.0, 16.5, 17.0, 20.0, 40.0, 80.0]
+  counts = [(0.5, -0.3), (-2.0, -5.0)] if lk == "zinb" else [(0.3, 0.2), (-3.0, 1.5)]
+  pts = np.array([(xv, a, l, g) for a, l in counts for g in gate for xv in (0.0, 1.0, 181.0, 10738.0)], np.float32)
+  x, a, l, g = [np.repeat(pts[:, i:i + 1], 64, axis=1) for i in range(4)]
+  planes = [a, l, g]
+  llk, grads = eng.k_count_llk(lk, x, np.stack(planes))
+  ref_e, ref_g = so.count_llk(x.astype(np.float64), [p.astype(np.float64) for p in planes], lk)
+  ref = ref_e.sum(1)
+  assert np.isfinite(llk).all() and np.isfinite(grads).all()
+  err = np.abs(llk - ref)
+  tol = 1e-2 + 1e-4 * np.abs(ref)
+  print(f"{lk} llk: worst error / tolerance {float((err / tol).max()):.3f} at (x, p0, p1, gate) = {pts[int(np.argmax(err / tol))]}")
+  assert (err <= tol).all(), (lk, pts[int(np.argmax(err / tol))], float(err.max()))
+  for i in range(3):
+    err = np.abs(grads[i] - ref_g[i])
+    tol = 1e-4 * np.abs(ref_g[i]) + 1e-4 * (1 + np.abs(x))
+    at = np.unravel_index(np.argmax(err / tol), err.shape)
+    print(f"{lk} gradient {i}: worst error / tolerance {float((err / tol).max()):.3f} at (x, p0, p1, gate) = {pts[at[0]]}")
+    assert (err <= tol).all(), (lk, i, float(err.max()), pts[at[0]])
+
+
 @pytest.mark.parametrize("lk", ["nb", "zinb"])
 def test_count_llk_tiny_total_count_stays_finite(eng, lk):
   """log total_count down to -69 (r = 1e-30, the kernel's clamp) with counts from 9 to 1e5: the Stirling branch's shift

@@ -93,7 +93,8 @@ def test_bernoulli_result_object():
   d = D.Bernoulli(logits, name="markers")
   p = 1.0 / (1.0 + np.exp(-logits.astype(np.float64)))
   assert np.allclose(d.probs, p, rtol=1e-12) and np.allclose(d.mean(), p, rtol=1e-12)
-  assert np.allclose(d.variance(), p * (1 - p), rtol=1e-10, atol=1e-300) and np.allclose(d.stddev(), np.sqrt(p * (1 - p)))
+  q = 1.0 / (1.0 + np.exp(logits.astype(np.float64)))   # 1 - p without the subtraction: p (1 - p) in float64 is 1e-3 off at l = 30 and 0 at 80
+  assert np.allclose(d.variance(), p * q, rtol=1e-10, atol=1e-300) and np.allclose(d.stddev(), np.sqrt(p * q))
   y = (rng.uniform(size=logits.shape) < 0.5).astype(np.float32)
   lp = d.log_prob(y)
   want = stats.bernoulli.logpmf(y, p)
