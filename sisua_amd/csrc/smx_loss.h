@@ -70,15 +70,18 @@ __device__ inline void count_elem(float x, float p0, float p1, float p2, float& 
   if (LK == SMX_LLK_ZINB || LK == SMX_LLK_ZINBD) {
     const SpSg sg = softplus_sigmoid(p2);
     if (x == 0.f) {
-      // lse = logaddexp(g, ell); w = d lse / d ell = sigmoid(ell - g): one exponential for both
+      // lse = logaddexp(g, ell); w = d lse / d ell = sigmoid(ell - g): one exponential for both.  1 - w = sigmoid(g - ell) is the other
+      // branch of the same quotient: formed as 1.f - w it carried w's rounding (6e-8) into a term of size e^(g - ell), and at a gate 17
+      // below ell the gate gradient came out as -sigmoid(g), the wrong sign
       const float dlt = ell - p2;
       const float e3 = fexp(-fabsf(dlt));
       const float inv3 = frcp(1.0f + e3);
       const float lse = fmaxf(p2, ell) + log1p_small(e3);
       const float w = dlt >= 0.f ? inv3 : e3 * inv3;
+      const float omw = dlt >= 0.f ? e3 * inv3 : inv3;
       llk = lse - sg.sp;
       d0 *= w; d1 *= w;
-      d2 = (1.f - w) - sg.sg;
+      d2 = omw - sg.sg;
     } else {
       llk = ell - sg.sp;
       d2 = -sg.sg;
@@ -252,11 +255,12 @@ __device__ inline void count_elem_vec(const float (&x)[N], const float (&p0)[N],
       const float inv3 = frcp(1.0f + e3);
       const float lse = fmaxf(p2[e], ell[e]) + log1p_small(e3);
       const float w = dlt >= 0.f ? inv3 : e3 * inv3;
+      const float omw = dlt >= 0.f ? e3 * inv3 : inv3;   // 1 - w (count_elem)
       const bool zero = x[e] == 0.f;
       llk[e] = (zero ? lse : ell[e]) - sg.sp;
       d0[e] = zero ? d0[e] * w : d0[e];
       d1[e] = zero ? d1[e] * w : d1[e];
-      d2[e] = (zero ? (1.f - w) : 0.f) - sg.sg;
+      d2[e] = (zero ? omw : 0.f) - sg.sg;
     }
   } else {
 #pragma unroll

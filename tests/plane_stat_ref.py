@@ -291,8 +291,9 @@ def _lgdiff_abs(x, r, rel_r):
   return carried + np.where(small, e_small, e_big)
 
 
-def logprob_elem_bound(kind, x, planes, direct=False, count_only=False):
-  """b_g: the absolute float32 error bound of one element of the row sum (the module docstring), float64"""
+def logprob_elem_bound(kind, x, planes, direct=False, count_only=False, double_const=False):
+  """b_g: the absolute float32 error bound of one element of the row sum (the module docstring), float64.  double_const: without the
+  lgammaf(x + 1) term -- for the kernels that take the count constant of a row from a double-precision sum"""
   p = _f64(planes)
   x = np.broadcast_to(np.asarray(x, np.float64), np.broadcast_shapes(np.shape(x), p[0].shape))
   v = np.abs(log_prob_elem(kind, x, planes, direct, count_only))
@@ -337,7 +338,7 @@ def logprob_elem_bound(kind, x, planes, direct=False, count_only=False):
     other = e + _sp_abs(g) + np.abs(ellv - spg)
     e = np.where(x == 0, zero, other)
   lgx = np.abs(gammaln(x + 1.0))
-  return (e + np.maximum(12.0 * lgx, 1.0) + v) * U
+  return (e + (0.0 if double_const else np.maximum(12.0 * lgx, 1.0)) + v) * U
 
 
 def gamma_sum(G):
