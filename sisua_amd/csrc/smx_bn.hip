@@ -180,10 +180,11 @@ __device__ inline void latent_tile_to_lds(const LatentArgs& a, float* zs, bool s
         const float4 sr = s4[it];
         auto one = [&](int e, float mu, float s_raw, float nn, float& z, float& s, float& en) {
           if (d0 + e < a.D) {
-            const float sg = softplusf(s_raw + SMX_SOFTPLUS_INV_1);
+            const float xs = s_raw + SMX_SOFTPLUS_INV_1;
+            const float sg = latent_sigma(xs);
             s = sg; en = nn;
             z = mu + sg * nn;
-            if (store) kl += 0.5f * (sg * sg + mu * mu - 1.f - 2.f * flog(sg));   // (block-uniform: the KL term belongs to the workgroup that stores)
+            if (store) kl += 0.5f * (sg * sg + mu * mu - 1.f - 2.f * log_sigma_fast(xs, sg));   // (block-uniform: the KL term belongs to the workgroup that stores)
           }
         };
         one(0, mq.x, sr.x, nq.x, zq.x, sq.x, eq.x);
@@ -606,6 +607,7 @@ __device__ inline void fold_dz_tile(const BnBwdArgs& a, const int bid, float* ti
       const bool live = d < e.D;
       const float dz = acc[nb][r];
       const float o0 = live ? dz + kls * e_mu[nb][r] : 0.f;
+      // (FLOOR, DESIGN.md 4t: below raw = -87.9 sigmoidf is 0 and this is -0 where the value is -kls; sigma >= 2^-126 from the forward keeps it from NaN)
       const float o1 = live ? (dz * e_ep[nb][r] + kls * (e_sg[nb][r] - frcp(e_sg[nb][r]))) * sigmoidf(e_sr[nb][r] + SMX_SOFTPLUS_INV_1) : 0.f;
       if (b < a.B) {
         tile[b * ldd + d] = o0;

@@ -143,6 +143,31 @@ __device__ inline float sigmoidf(float x) {
   const float s = frcp(1.0f + e);
   return x >= 0.f ? s : e * s;
 }
+// ---- the latent heads' scale sigma = softplus(x), x = raw + softplus^-1(1), far down its tail ----
+// From x = -87.3 down softplus(x) is a denormal, and 0 on the device (v_exp returns 0 for a result below 2^-126): v_log / v_rcp of it (and logf,
+// a division by it) give -inf / +inf, and the KL, the scale's gradient ((-inf) x 0) and the importance weight were inf / NaN / -inf there while
+// their values are ordinary numbers (87, -1, -87).
+//  * latent_sigma: the scale no smaller than the smallest normal float (an absolute error below 2^-126): 1 / sigma stays finite, so the
+//    training step's backward forms -- (dz eps + kls (sigma - rcp(sigma))) sigmoid(x), left as they were -- give 0 x finite, not NaN, below their
+//    floor of raw = -87 (DESIGN.md 4t has the floor and why it stands).
+//  * below SMX_SIGMA_TAIL sigma is e^x (1 - e^x / 2 + ...), so log sigma = x and (sigma - 1 / sigma) sigmoid(x) = -1, both to e^-20 / 2 = 1e-9
+//    (under 2^-24 of either): one compare and one select per formula, the ordinary branch spelled as before (its bits are kept).
+#define SMX_SIGMA_TAIL -20.f
+#define SMX_SIGMA_MIN 1.17549435e-38f
+__device__ inline float latent_sigma(float x) { const float s = softplusf(x); return s < SMX_SIGMA_MIN ? SMX_SIGMA_MIN : s; }   // (not fmaxf: a NaN pre-activation stays a NaN)
+__device__ inline float log_sigma_fast(float x, float sg) { return x < SMX_SIGMA_TAIL ? x : flog(sg); }   // beside flog(sg)
+__device__ inline float log_sigma(float x, float sg) { return x < SMX_SIGMA_TAIL ? x : logf(sg); }         // beside logf(sg)
+// scVI's library latent against N(mp, vp), sp = sqrt(vp): log(sp / sigma) and (dl eps + kls (sigma / vp - 1 / sigma)) sigmoid(x) in
+// correctly rounded divisions; the tail: log sp - x, and -kls (sigma sigmoid(x) / vp is e^2x / vp: the library's vp is no smaller than 1e-6)
+__device__ inline float lib_log_ratio(float sp, float sg, float x) { return x < SMX_SIGMA_TAIL ? logf(sp) - x : logf(sp / sg); }
+__device__ inline float lib_dsraw(float dl, float eps, float kls, float sg, float vp, float x) {
+  const float s = sigmoidf(x);
+  return x < SMX_SIGMA_TAIL ? dl * (eps * s) - kls : (dl * eps + kls * (sg / vp - 1.f / sg)) * s;
+}
+// e^(a - b) of a log-sum-exp against its maximum b: 1 when a == b, also at a = b = -inf (where a - b is NaN: every weight -inf gives
+// the sum's terms 1 and the result max + log(sum) = -inf, not NaN); expf(0) is 1 exactly, so nothing else changes
+__device__ inline float exp_below_max(float a, float b) { return a == b ? 1.f : expf(a - b); }
+
 // log1p for count inputs (x >= 0; 1 + x is exact for integer counts < 2^24)
 __device__ inline float log1p_count(float x) { return flog(1.0f + x); }
 

@@ -303,6 +303,7 @@ __device__ inline void gemm_body(const GemmArgs& g, const int bx, const int by, 
         o1[j] = live ? (dzt * ep[j] - kls * frcp(sg[j])) * sigmoidf(sr[j] + SMX_SOFTPLUS_INV_1) : 0.f;
       } else if (e.stochastic) {
         o0[j] = live ? dz + kls * mu[j] : 0.f;
+        // (FLOOR, DESIGN.md 4t: below raw = -87.9 sigmoidf is 0 and this is -0 where the value is -kls; sigma >= 2^-126 from the forward keeps it from NaN)
         o1[j] = live ? (dz * ep[j] + kls * (sg[j] - frcp(sg[j]))) * sigmoidf(sr[j] + SMX_SOFTPLUS_INV_1) : 0.f;
       } else {
         o0[j] = (live && !(e.relu && !(mu[j] > 0.f))) ? dz : 0.f;

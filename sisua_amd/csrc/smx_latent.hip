@@ -29,10 +29,11 @@ __global__ __launch_bounds__(64) void latent_fwd_quad_kernel(LatentArgs a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e)
         if (d0 + e < a.D) {
-          const float sg = softplusf(sr[e] + SMX_SOFTPLUS_INV_1);
+          const float xs = sr[e] + SMX_SOFTPLUS_INV_1;
+          const float sg = latent_sigma(xs);
           ss[e] = sg; ee[e] = nn[e];
           zz[e] = mu[e] + sg * nn[e];
-          kl += 0.5f * (sg * sg + mu[e] * mu[e] - 1.f - 2.f * flog(sg));
+          kl += 0.5f * (sg * sg + mu[e] * mu[e] - 1.f - 2.f * log_sigma_fast(xs, sg));
         }
     } else {
 #pragma unroll
@@ -62,14 +63,15 @@ __global__ __launch_bounds__(256) void latent_fwd_kernel(LatentArgs a) {
     if (d < a.D) {
       const float mu = a.lat[(long)b * a.ld + d];
       if (a.stochastic) {
-        sig = softplusf(a.lat[(long)b * a.ld + a.Dp + d] + SMX_SOFTPLUS_INV_1);
+        const float xs = a.lat[(long)b * a.ld + a.Dp + d] + SMX_SOFTPLUS_INV_1;
+        sig = latent_sigma(xs);
         if (a.inj_eps) eps = a.inj_eps[(long)b * a.inj_ld + d];
         else {
           const float4 n = normal4(philox_row(a.nk, (uint32_t)b, cell, (uint32_t)(d >> 2)));
           eps = (d & 3) == 0 ? n.x : (d & 3) == 1 ? n.y : (d & 3) == 2 ? n.z : n.w;
         }
         z = mu + sig * eps;
-        kl += 0.5f * (sig * sig + mu * mu - 1.f - 2.f * flog(sig));
+        kl += 0.5f * (sig * sig + mu * mu - 1.f - 2.f * log_sigma_fast(xs, sig));
       } else {
         z = a.relu ? fmaxf(mu, 0.f) : mu;
       }
@@ -761,7 +763,7 @@ __global__ void lib_latent_fwd_kernel(LibLatentArgs a) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.B) return;
   const long src = a.rows ? a.rows[b] : b;
-  const float mu = a.latl[(long)b * a.ld], sig = softplusf(a.latl[(long)b * a.ld + 1] + SMX_SOFTPLUS_INV_1);
+  const float mu = a.latl[(long)b * a.ld], xs = a.latl[(long)b * a.ld + 1] + SMX_SOFTPLUS_INV_1, sig = softplusf(xs);
   float eps;
   if (a.inj_eps) eps = a.inj_eps[(long)b * a.inj_ld];
   else eps = normal4(philox_row(a.nk, (uint32_t)b, a.cell_base + (uint32_t)src, 0u)).x;
@@ -770,7 +772,7 @@ __global__ void lib_latent_fwd_kernel(LibLatentArgs a) {
   a.l[b] = mu + sig * eps;
   a.sig[b] = sig;
   a.eps[b] = eps;
-  a.kl[b] = logf(sp / sig) + (sig * sig + (mu - mp) * (mu - mp)) / (2.f * vp) - 0.5f;
+  a.kl[b] = lib_log_ratio(sp, sig, xs) + (sig * sig + (mu - mp) * (mu - mp)) / (2.f * vp) - 0.5f;
 }
 int launch_lib_latent_fwd(hipStream_t st, const LibLatentArgs& a) {
   hipLaunchKernelGGL(lib_latent_fwd_kernel, dim3((a.B + 255) / 256), dim3(256), 0, st, a);
@@ -788,7 +790,7 @@ __global__ void lib_latent_bwd_kernel(LibLatentArgs a) {
   const float dl = a.dl[b];
   for (int j = 2; j < a.ld; ++j) a.dlatl[(long)b * a.ld + j] = 0.f;
   a.dlatl[(long)b * a.ld] = dl + kls * (mu - mp) / vp;
-  a.dlatl[(long)b * a.ld + 1] = (dl * eps + kls * (sig / vp - 1.f / sig)) * sigmoidf(sraw + SMX_SOFTPLUS_INV_1);
+  a.dlatl[(long)b * a.ld + 1] = lib_dsraw(dl, eps, kls, sig, vp, sraw + SMX_SOFTPLUS_INV_1);
 }
 int launch_lib_latent_bwd(hipStream_t st, const LibLatentArgs& a) {
   hipLaunchKernelGGL(lib_latent_bwd_kernel, dim3((a.B + 255) / 256), dim3(256), 0, st, a);

@@ -33,12 +33,13 @@ __global__ __launch_bounds__(256) void score_draws_kernel(ScoreDrawArgs a) {
     float z = 0.f;
     if (d < a.D) {
       const float mu = a.lat[(long)b * a.ld + d];
-      const float sig = softplusf(a.lat[(long)b * a.ld + a.Dp + d] + SMX_SOFTPLUS_INV_1);
+      const float xs = a.lat[(long)b * a.ld + a.Dp + d] + SMX_SOFTPLUS_INV_1;
+      const float sig = latent_sigma(xs);
       const float4 n = normal4(philox_block(nk, cell, (uint32_t)(d >> 2)));
       const float eps = (d & 3) == 0 ? n.x : (d & 3) == 1 ? n.y : (d & 3) == 2 ? n.z : n.w;
       z = mu + sig * eps;
       // log N(z; 0, I) - log N(z; mu, sigma), constants cancel (mixture prior: the q term only, the prior follows)
-      lw += (a.pr_logits ? 0.f : -0.5f * z * z) + 0.5f * eps * eps + (a.pr_logits ? flog(sig) : logf(sig));
+      lw += (a.pr_logits ? 0.f : -0.5f * z * z) + 0.5f * eps * eps + (a.pr_logits ? flog(sig) : log_sigma(xs, sig));
     }
     a.z[r * a.Dp + d] = z;
     z_mine = z;
@@ -66,13 +67,13 @@ __global__ __launch_bounds__(256) void score_draws_kernel(ScoreDrawArgs a) {
   if (lane != 0) return;
   if (a.latl) {
     const long src = a.lib_rows ? a.lib_rows[b] : b;
-    const float mu = a.latl[(long)b * a.ld_l], sig = softplusf(a.latl[(long)b * a.ld_l + 1] + SMX_SOFTPLUS_INV_1);
+    const float mu = a.latl[(long)b * a.ld_l], xs = a.latl[(long)b * a.ld_l + 1] + SMX_SOFTPLUS_INV_1, sig = softplusf(xs);
     NoiseKey nl = a.nk_l;
     nl.stream = (a.nk_l.stream & 0xFFu) | (((uint32_t)(a.s0 + s) & 0xFFFFFFu) << 8);
     const float eps = normal4(philox_block(nl, cell, 0u)).x;
     const float l = mu + sig * eps;
     const float mp = a.library[src * 2], vp = a.library[src * 2 + 1];
-    lw += -0.5f * (l - mp) * (l - mp) / vp - 0.5f * logf(vp) + 0.5f * eps * eps + logf(sig);
+    lw += -0.5f * (l - mp) * (l - mp) / vp - 0.5f * logf(vp) + 0.5f * eps * eps + log_sigma(xs, sig);
     a.l[r] = l;
   }
   a.lw[r] = lw;
@@ -354,11 +355,12 @@ __global__ __launch_bounds__(256) void score_decoder1_kernel(ScoreDec1Args a) {
     nk.stream = (d.nk.stream & 0xFFu) | (((uint32_t)(d.s0 + ss[p]) & 0xFFFFFFu) << 8);
     float lw = 0.f, z = 0.f;
     if (d_ok) {
-      const float sig = softplusf(srs[p] + SMX_SOFTPLUS_INV_1);
+      const float xs = srs[p] + SMX_SOFTPLUS_INV_1;
+      const float sig = latent_sigma(xs);
       const float4 n = normal4(philox_block(nk, d.cell_base + cells[p], (uint32_t)(dd >> 2)));
       const float eps = (dd & 3) == 0 ? n.x : (dd & 3) == 1 ? n.y : (dd & 3) == 2 ? n.z : n.w;
       z = mus[p] + sig * eps;
-      lw = -0.5f * z * z + 0.5f * eps * eps + logf(sig);
+      lw = -0.5f * z * z + 0.5f * eps * eps + log_sigma(xs, sig);
     }
     if (dd < d.Dp) zs[rl][dd] = z;
     lw = PAIR ? half_wave_sum(lw) : wave_sum(lw);
@@ -972,13 +974,13 @@ __global__ __launch_bounds__(512) void iw_stack_kernel(IwStackArgs a) {
   __syncthreads();
   if (threadIdx.x >= 64) return;
   float se = 0.f, sl = 0.f;
-  for (int s = lane; s < a.S; s += 64) { se += expf(lws[s] - mx); sl += llks[s]; }
+  for (int s = lane; s < a.S; s += 64) { se += exp_below_max(lws[s], mx); sl += llks[s]; }
   se = wave_sum(se); sl = wave_sum(sl);
   if (lane != 0) return;
   if (a.first) { a.run_max[b] = mx; a.run_sum[b] = se; if (a.llk_sum) a.llk_sum[b] = sl; }
   else {
     const float om = a.run_max[b], nm = fmaxf(om, mx);
-    a.run_sum[b] = a.run_sum[b] * expf(om - nm) + se * expf(mx - nm);
+    a.run_sum[b] = a.run_sum[b] * exp_below_max(om, nm) + se * exp_below_max(mx, nm);
     a.run_max[b] = nm;
     if (a.llk_sum) a.llk_sum[b] += sl;
   }

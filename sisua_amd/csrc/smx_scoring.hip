@@ -8,6 +8,7 @@ namespace smx {
 struct IwArgs {
   const float* llk_part; int n_chunks; const float* lgx1; const int32_t* rows;
   const float* z; const float* sig; const float* eps; int D, Dp, stochastic;
+  const float* lat; int ld; const float* latl; int ld_l;   // the heads' raw planes (null: none to read): log sigma far down sigma's tail (log_sigma)
   const float* l; const float* lsig; const float* leps; const float* library;  // scvi (library indexed like lgx1)
   float* run_max; float* run_sum; float* llk_sum; int B, first;
   const float* klmc;   // scale: log q(z|x) - log p_mixture(z) of this draw (replaces the N(0, I) prior terms)
@@ -27,19 +28,19 @@ __global__ __launch_bounds__(256) void iw_accum_kernel(IwArgs a) {
   else if (a.stochastic)
     for (int d = lane; d < a.D; d += 64) {
       const float z = a.z[(long)b * a.Dp + d], e = a.eps[(long)b * a.Dp + d], s = a.sig[(long)b * a.Dp + d];
-      lw += -0.5f * z * z + 0.5f * e * e + logf(s);
+      lw += -0.5f * z * z + 0.5f * e * e + (a.lat ? log_sigma(a.lat[(long)b * a.ld + a.Dp + d] + SMX_SOFTPLUS_INV_1, s) : logf(s));
     }
   lw = wave_sum(lw) + llk;
   if (lane != 0) return;
   if (a.l) {
     const float mp = a.library[src * 2], vp = a.library[src * 2 + 1];
     const float l = a.l[b], e = a.leps[b], s = a.lsig[b];
-    lw += -0.5f * (l - mp) * (l - mp) / vp - 0.5f * logf(vp) + 0.5f * e * e + logf(s);
+    lw += -0.5f * (l - mp) * (l - mp) / vp - 0.5f * logf(vp) + 0.5f * e * e + log_sigma(a.latl[(long)b * a.ld_l + 1] + SMX_SOFTPLUS_INV_1, s);   // (a.l and a.latl: both set for scvi)
   }
   if (a.first) { a.run_max[b] = lw; a.run_sum[b] = 1.f; if (a.llk_sum) a.llk_sum[b] = llk; }
   else {
     const float mx = a.run_max[b], nm = fmaxf(mx, lw);
-    a.run_sum[b] = a.run_sum[b] * expf(mx - nm) + expf(lw - nm);
+    a.run_sum[b] = a.run_sum[b] * exp_below_max(mx, nm) + exp_below_max(lw, nm);
     a.run_max[b] = nm;
     if (a.llk_sum) a.llk_sum[b] += llk;
   }
@@ -242,6 +243,8 @@ static int marginal_llk_run(smx_model* m, Pass& ps, int32_t batch, int32_t n_sam
     row_consts(m, &a.lgx1, &a.rows);
     a.z = m->z; a.sig = m->sig; a.eps = m->eps; a.stochastic = m->stochastic;
     a.l = m->scvi ? m->lsmp : nullptr; a.lsig = m->lsig; a.leps = m->leps; a.library = ps.lib;
+    a.lat = (m->stochastic && !m->latent_tril && !m->scale && !m->mixpost) ? m->latbuf : nullptr; a.ld = 2 * m->Dp;
+    a.latl = m->scvi ? m->latlbuf : nullptr; a.ld_l = 32;   // (the library head's row stride, as forward_pass and the backward set it)
     a.run_max = run; a.run_sum = run + batch; a.llk_sum = run + 2 * batch; a.first = (s == 0);
     a.klmc = (m->scale || m->mixpost) ? m->kl : nullptr;   // (Monte-Carlo KL models: log p(z) - log q(z|x) of the draw is minus that term)
     rc = iw_draw(m, ps, m->cfg.likelihood, ps.Xsrc, ps.x_u16, ps.xrows, a);

@@ -98,7 +98,7 @@ __global__ __launch_bounds__(NT) void scvi_head_train_kernel(ScviTrainArgs a) {
       const float sp = sqrtf(vp);
       const float l = mu_l + sig_l * eps_l;
       a.l[b] = l; a.sig[b] = sig_l; a.eps[b] = eps_l;
-      a.kl[b] = logf(sp / sig_l) + (sig_l * sig_l + (mu_l - mp) * (mu_l - mp)) / (2.f * vp) - 0.5f;
+      a.kl[b] = lib_log_ratio(sp, sig_l, sraw_l + SMX_SOFTPLUS_INV_1) + (sig_l * sig_l + (mu_l - mp) * (mu_l - mp)) / (2.f * vp) - 0.5f;
       a.latl[(long)b * a.ldl] = mu_l; a.latl[(long)b * a.ldl + 1] = sraw_l;
       shl[0] = l;
     }
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(NT) void scvi_head_train_kernel(ScviTrainArgs a) {
     a.dl[b] = dl;
     float* o = a.dlatl + (long)b * a.ldl;
     o[0] = dl + kls * (mu_l - mp) / vp;
-    o[1] = (dl * eps_l + kls * (sig_l / vp - 1.f / sig_l)) * sigmoidf(sraw_l + SMX_SOFTPLUS_INV_1);
+    o[1] = lib_dsraw(dl, eps_l, kls, sig_l, vp, sraw_l + SMX_SOFTPLUS_INV_1);
   }
   if (threadIdx.x >= 2 && (int)threadIdx.x < a.ldl) a.dlatl[(long)b * a.ldl + threadIdx.x] = 0.f;
 }

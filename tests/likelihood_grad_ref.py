@@ -64,7 +64,7 @@ the gate sits 87 above ell -- is no reason to drop the element: every bound carr
 underflow of the product.  (Dropping them instead would take a fifth of the 'zinb' points' zero counts off the grid.)  No axis value
 fails wholesale but one: GRAD_AXES is plane_stat_ref's AXES with the 'normal' raw scale -30 replaced by -22 (the note beside it)."""
 import numpy as np
-from scipy.special import digamma, expit, polygamma
+from scipy.special import digamma, expit, gammaln, polygamma
 
 from tests.plane_stat_ref import (AXES, CYCLE, EPS, F32_MAX, F32_MIN, GATE, MODERATE, SOFTPLUS_INV_1, U, _f64, _log1p_abs, _sp_abs,  # noqa: F401
                                   G_GRID, base_kind, bias_grid, grid_points, in_range, is_zi, log_prob_elem, logprob_elem_bound, softplus, targets)
@@ -324,3 +324,25 @@ def counts_for(kind):
   elif kind == "normal":
     c = c * 0.731 - 2.5
   return c.astype(np.float32)
+
+
+# ---- sums over the genes (the summation bound of tests/test_gpu_likelihood_grid.py's docstring) -----------------------------------------
+def count_const(kind, x):
+  """lgamma(x + 1) per element: what count_elem leaves to the caller (0 for 'bernoulli' / 'normal')"""
+  return gammaln(np.asarray(x, np.float64) + 1.0) if kind not in ("bernoulli", "normal") else np.zeros(np.shape(x))
+
+
+def row_sum_bound(kind, x, planes, n_add, direct=False, count_only=False, double_const=True, repeat=1):
+  """(ref, bound) of the sum over the last axis, every element taken `repeat` times"""
+  v = log_prob_elem(kind, x, planes, direct, count_only)
+  b = logprob_elem_bound(kind, x, planes, direct, count_only, double_const=double_const)
+  s = np.abs(v + count_const(kind, np.broadcast_to(x, v.shape)))
+  ref = repeat * v.sum(axis=-1)
+  return ref, repeat * (b.sum(axis=-1) + (n_add + 8.0) * U * s.sum(axis=-1) + v.shape[-1] * F32_MIN) + U * np.abs(ref)
+
+
+def draw_bound(kind, t, planes, count_only, n_add):
+  """(ref, bound) [rows] of one draw's log-likelihood per cell: the summation bound, and 2 u |sum lgamma(x + 1)| for the cell's count constant,
+  a float32 (of a double sum) that one float32 subtraction takes off"""
+  ref, bound = row_sum_bound(kind, t, planes, n_add, count_only=count_only)
+  return ref, bound + 2.0 * U * count_const(kind, t).sum(axis=-1)

@@ -41,7 +41,6 @@ EVERY LAUNCHER BRANCH that evaluates count_elem / count_elem_vec and is reachabl
 """
 import numpy as np
 import pytest
-from scipy.special import gammaln
 
 from tests import likelihood_grad_ref as L
 
@@ -70,18 +69,7 @@ def _outside(err, bound):
   return ~(err <= bound)
 
 
-def _count_const(kind, x):
-  """lgamma(x + 1) per element: what count_elem leaves to the caller (0 for 'bernoulli' / 'normal')"""
-  return gammaln(np.asarray(x, np.float64) + 1.0) if kind not in ("bernoulli", "normal") else np.zeros(np.shape(x))
-
-
-def row_sum_bound(kind, x, planes, n_add, direct=False, count_only=False, double_const=True, repeat=1):
-  """(ref, bound) of the sum over the last axis, every element taken `repeat` times: the module docstring's summation bound"""
-  v = L.log_prob_elem(kind, x, planes, direct, count_only)
-  b = L.logprob_elem_bound(kind, x, planes, direct, count_only, double_const=double_const)
-  s = np.abs(v + _count_const(kind, np.broadcast_to(x, v.shape)))
-  ref = repeat * v.sum(axis=-1)
-  return ref, repeat * (b.sum(axis=-1) + (n_add + 8.0) * U * s.sum(axis=-1) + v.shape[-1] * L.F32_MIN) + U * np.abs(ref)
+_count_const, row_sum_bound = L.count_const, L.row_sum_bound          # (shared with tests/test_gpu_latent_grid.py: they live in the reference module)
 
 
 def _check_grads(label, kind, direct, grads, x, planes, keep):
@@ -378,11 +366,7 @@ SCORE_FORMS = {   # (stacked_scoring, tuning knobs)
 }
 
 
-def _draw_bound(kind, t, planes, count_only, n_add):
-  """(ref, bound) [rows] of one draw's log-likelihood per cell: the summation bound, and 2 u |sum lgamma(x + 1)| for the cell's count constant,
-  a float32 (of a double sum) that one float32 subtraction takes off"""
-  ref, bound = row_sum_bound(kind, t, planes, n_add, count_only=count_only)
-  return ref, bound + 2.0 * U * _count_const(kind, t).sum(axis=-1)
+_draw_bound = L.draw_bound
 
 
 @pytest.mark.parametrize("form", list(SCORE_FORMS))
