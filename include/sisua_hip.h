@@ -668,6 +668,28 @@ int smx_k_hiprand(uint64_t seed, int32_t n, const uint32_t* counters, uint32_t* 
 /* Philox words / dropout multipliers / normals exactly as the kernels draw them. */
 int smx_k_noise(uint64_t seed, int32_t stream, int32_t step, int32_t sample, const int64_t* cell_ids, int32_t B,
                 int32_t width, float dropout_p, float* dropout_mult, float* normal);
+/* The BatchNorm launches of a hidden layer by themselves (smx_bn.hip): split-K slab sum -> (bias | BatchNorm) -> activation -> dropout, and
+ * its backward, over host arrays; the library's own dispatch picks the form (register-resident for 2 / 4 / 8 / 16 rows per thread, the
+ * round trip above 1024 rows, the wide column-major form, the forms of activations other than ReLU).  No front, no riders.
+ * ip (int32): S slabs, B rows, H columns, Hp (H padded to 8), ld (row stride of a slab, >= Hp), wide (slabs [S][Hp][128] column-major, B <= 128,
+ * Hp <= 128; otherwise [S][B][ld]), batchnorm, training, update_moving, act (smx_activation), mask_ld, Philox stream, step, cell_base, world.
+ * fp (float): momentum, eps, leak, drop_p.  gamma, beta, bias, the moving statistics: [Hp] (beyond H unread).  Dropout (training, drop_p > 0):
+ * `mask` [B][mask_ld] holds the multipliers, or (mask NULL) they are drawn from Philox under (seed, stream, step) for cell cell_base + rows[b]
+ * (rows NULL: b).  world > 0: SyncBatchNorm of `world` simulated ranks with B / world rows each -- phase 0 per rank into its own gather
+ * buffer, the buffers summed, phase 1 per rank (world = 1 included; 0: the ordinary launch).  Out: out, xhat [B][Hp]; inv_std, batch_mean,
+ * batch_var, the moving statistics after the launch [Hp] (any may be NULL).  Every output buffer lies between two guard bands of a fixed
+ * pattern and starts as NaN: *guards_ok = 1 if no band word changed. */
+int smx_k_bn_fwd(const int32_t* ip, const float* fp, const float* pre, const float* gamma, const float* beta, const float* bias,
+                 const float* moving_mean, const float* moving_var, const float* mask, const int32_t* rows, uint64_t seed, float* out,
+                 float* xhat, float* inv_std, float* batch_mean, float* batch_var, float* moving_mean_out, float* moving_var_out,
+                 int32_t* guards_ok);
+/* ... and the backward launch on ITS inputs: the d out slabs (laid out as `pre` above), the forward's out, xhat [B][Hp], inv_std [Hp], gamma,
+ * beta [Hp], the dropout source as above.  ip: S, B, H, Hp, ld, wide, batchnorm, training, act, mask_ld, stream, step, cell_base, world;
+ * fp: leak, drop_p.  Out: dpre [B][Hp]; dgamma, dbeta [max(world, 1)][Hp] (under SyncBatchNorm each rank's share); dbias [Hp] (without
+ * BatchNorm); *guards_ok as above. */
+int smx_k_bn_bwd(const int32_t* ip, const float* fp, const float* dout, const float* out, const float* xhat, const float* inv_std,
+                 const float* gamma, const float* beta, const float* mask, const int32_t* rows, uint64_t seed, float* dpre, float* dgamma,
+                 float* dbeta, float* dbias, int32_t* guards_ok);
 /* The predictive sampler by itself on caller-given planes [k][rows][G] (host; k planes of `likelihood`, direct / count_only as
  * smx_k_count_llk / smx_predict_sample): out [n_k][rows][G], the draws of rows 0 .. rows - 1 of a call with one Monte-Carlo draw
  * (s = 0) under `seed`.  rows <= 65535. */

@@ -175,6 +175,8 @@ SIGNATURES = {
     "smx_k_hiprand": (C.c_int, [C.c_uint64, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "smx_k_noise": (C.c_int, [C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_int32,
                               C.c_float, _FP, _FP]),
+    "smx_k_bn_fwd": (C.c_int, [_IP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _IP, C.c_uint64, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _IP]),
+    "smx_k_bn_bwd": (C.c_int, [_IP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _IP, C.c_uint64, _FP, _FP, _FP, _FP, _IP]),
     "smx_k_plane_sample": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _FP]),
     "smx_k_row_select": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]),
     "smx_k_col_rank2": (C.c_int, [_FP, C.c_int32, C.c_int64, _IP, _IP]),

@@ -1317,6 +1317,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_sync_apply_bwd_kernel(BnBwdArgs
 
 int launch_bn_sync_fwd(hipStream_t st, const BnFwdArgs& a, const BnSyncArgs& y, int phase) {
   if (a.Hp % BN_COLS || a.B <= 0 || !a.batchnorm || !a.training || y.world < 1 || !y.gather) { set_error("bn_sync_fwd: bad arguments"); return SMX_ERR_INVALID; }
+  if (a.leak != 0.f) { set_error("bn_sync_fwd: no leaky form (the only leaky layers, the discriminator's, have no BatchNorm)"); return SMX_ERR_INVALID; }
   if (phase == 0) hipLaunchKernelGGL(bn_sync_stats_fwd_kernel, dim3(a.Hp / BN_COLS), dim3(BN_THREADS), 0, st, a, y);
   else if (a.act != SMX_ACT_RELU) hipLaunchKernelGGL(bn_sync_apply_fwd_gen_kernel, dim3(a.Hp / BN_COLS), dim3(BN_THREADS), 0, st, a, y);
   else hipLaunchKernelGGL(bn_sync_apply_fwd_kernel, dim3(a.Hp / BN_COLS), dim3(BN_THREADS), 0, st, a, y);
@@ -1325,6 +1326,7 @@ int launch_bn_sync_fwd(hipStream_t st, const BnFwdArgs& a, const BnSyncArgs& y, 
 }
 int launch_bn_sync_bwd(hipStream_t st, const BnBwdArgs& a, const BnSyncArgs& y, int phase) {
   if (a.Hp % BN_COLS || a.B <= 0 || !a.batchnorm || !a.training || y.world < 1 || !y.gather) { set_error("bn_sync_bwd: bad arguments"); return SMX_ERR_INVALID; }
+  if (a.leak != 0.f) { set_error("bn_sync_bwd: no leaky form (the only leaky layers, the discriminator's, have no BatchNorm)"); return SMX_ERR_INVALID; }
   if (a.act != SMX_ACT_RELU && (!a.xhat || !a.beta)) { set_error("bn_sync_bwd: activations other than ReLU need xhat and beta"); return SMX_ERR_INVALID; }
   if (phase == 0 && a.act != SMX_ACT_RELU) hipLaunchKernelGGL(bn_sync_stats_bwd_gen_kernel, dim3(a.Hp / BN_COLS), dim3(BN_THREADS), 0, st, a, y);
   else if (phase == 0) hipLaunchKernelGGL(bn_sync_stats_bwd_kernel, dim3(a.Hp / BN_COLS), dim3(BN_THREADS), 0, st, a, y);

@@ -1,4 +1,5 @@
-// smx_kapi.hip -- kernel-level entry points (parity tests of single kernels): smx_k_count_llk, smx_k_adam, smx_k_gemm, smx_k_head_fused, smx_k_noise.
+// smx_kapi.hip -- kernel-level entry points (parity tests of single kernels): smx_k_count_llk, smx_k_adam, smx_k_gemm, smx_k_head_fused, smx_k_noise,
+// smx_k_bn_fwd / smx_k_bn_bwd.
 #include "smx_model.h"
 #include <hiprand/hiprand_kernel.h>
 
@@ -451,6 +452,198 @@ int smx_k_noise(uint64_t seed, int32_t stream, int32_t step, int32_t sample, con
   }
   hipFree(dIds); hipFree(dM); hipFree(dN);
   return rc;
+}
+
+}  // extern "C"
+
+// ---- the BatchNorm launches by themselves (smx_bn.hip: launch_bn_act_fwd / launch_bn_act_bwd pick the form; no front, no riders) ----------
+namespace {
+// An output buffer between two guard bands.  Bands and interior start as 0xFF bytes (a NaN no kernel computes): an element the launch
+// never wrote reads as NaN, and a store beside the buffer changes a band word.
+constexpr size_t KBN_GUARD = 256;   // floats on either side
+struct KbnOut {
+  float* base = nullptr; size_t n = 0;
+  ~KbnOut() { if (base) hipFree(base); }
+  float* p() const { return base + KBN_GUARD; }
+  int alloc(size_t count) {
+    n = count ? count : 1;
+    int rc = dmalloc(&base, n + 2 * KBN_GUARD);
+    if (rc) return rc;
+    SMX_HIP(hipMemset(base, 0xFF, (n + 2 * KBN_GUARD) * 4));
+    return SMX_OK;
+  }
+  int upload(const float* src, size_t count) { SMX_HIP(hipMemcpy(p(), src, count * 4, hipMemcpyHostToDevice)); return SMX_OK; }
+  int download(float* dst, size_t count) const { if (dst) SMX_HIP(hipMemcpy(dst, p(), count * 4, hipMemcpyDeviceToHost)); return SMX_OK; }
+  int intact(bool* ok) const {
+    std::vector<uint32_t> h(2 * KBN_GUARD);
+    SMX_HIP(hipMemcpy(h.data(), base, KBN_GUARD * 4, hipMemcpyDeviceToHost));
+    SMX_HIP(hipMemcpy(h.data() + KBN_GUARD, base + KBN_GUARD + n, KBN_GUARD * 4, hipMemcpyDeviceToHost));
+    for (uint32_t w : h) if (w != 0xFFFFFFFFu) *ok = false;
+    return SMX_OK;
+  }
+};
+struct KbnIn {   // a plain device copy of a host array (NULL stays NULL)
+  float* d = nullptr;
+  ~KbnIn() { if (d) hipFree(d); }
+  int put(const float* src, size_t count) {
+    if (!src) return SMX_OK;
+    int rc = dmalloc(&d, count);
+    if (rc) return rc;
+    SMX_HIP(hipMemcpy(d, src, count * 4, hipMemcpyHostToDevice));
+    return SMX_OK;
+  }
+};
+struct KbnRows {
+  int32_t* d = nullptr;
+  ~KbnRows() { if (d) hipFree(d); }
+  int put(const int32_t* src, size_t count) {
+    if (!src) return SMX_OK;
+    int rc = dmalloc(&d, count);
+    if (rc) return rc;
+    SMX_HIP(hipMemcpy(d, src, count * 4, hipMemcpyHostToDevice));
+    return SMX_OK;
+  }
+};
+NoiseKey kbn_key(uint64_t seed, int stream, int step) {
+  NoiseKey nk;
+  nk.k0 = (uint32_t)(seed & 0xFFFFFFFFu); nk.k1 = (uint32_t)(seed >> 32); nk.step = (uint32_t)step;
+  nk.stream = (uint32_t)(stream & 0xFF); nk.step_ptr = nullptr; nk.draw_rows = 0;
+  return nk;
+}
+// SyncBatchNorm on one device: the ranks' gather buffers [world][2][Hp] summed on the host (every other slot is a zero: the sum is exact) and
+// handed back to every rank
+int kbn_all_reduce(std::vector<KbnOut>& gather, size_t n) {
+  std::vector<float> sum(n, 0.f), one(n);
+  for (auto& g : gather) {
+    SMX_HIP(hipMemcpy(one.data(), g.p(), n * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) sum[i] += one[i];
+  }
+  for (auto& g : gather) SMX_HIP(hipMemcpy(g.p(), sum.data(), n * 4, hipMemcpyHostToDevice));
+  return SMX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// ip: S, B, H, Hp, ld, wide, batchnorm, training, update_moving, act, mask_ld, stream, step, cell_base, world; fp: momentum, eps, leak, drop_p
+int smx_k_bn_fwd(const int32_t* ip, const float* fp, const float* pre, const float* gamma, const float* beta, const float* bias,
+                 const float* moving_mean, const float* moving_var, const float* mask, const int32_t* rows, uint64_t seed, float* out,
+                 float* xhat, float* inv_std, float* batch_mean, float* batch_var, float* moving_mean_out, float* moving_var_out,
+                 int32_t* guards_ok) {
+  SMX_REQUIRE(ip && fp && pre && out && xhat && guards_ok, "k_bn_fwd: bad arguments");
+  const int S = ip[0], B = ip[1], H = ip[2], Hp = ip[3], ld = ip[4], wide = ip[5], batchnorm = ip[6], training = ip[7], update_moving = ip[8],
+            act = ip[9], mask_ld = ip[10], stream = ip[11], step = ip[12], world = ip[14];
+  const uint32_t cell_base = (uint32_t)ip[13];
+  SMX_REQUIRE(S > 0 && B > 0 && H > 0 && H <= Hp && Hp % 8 == 0 && (wide || ld >= Hp) && world >= 0 && (!mask || mask_ld >= Hp), "k_bn_fwd: bad shapes");
+  SMX_REQUIRE(!batchnorm || (gamma && beta && moving_mean && moving_var), "k_bn_fwd: BatchNorm needs gamma, beta and the moving statistics");
+  SMX_REQUIRE(!world || (!wide && batchnorm && training && B % world == 0), "k_bn_fwd: SyncBatchNorm takes plain slabs, training mode and equal shards");
+  const long slab = wide ? (long)Hp * 128 : (long)B * ld;
+  KbnIn dPre, dGamma, dBeta, dBias, dMask; KbnRows dRows;
+  KbnOut oOut, oXhat, oInv, oMean, oVar, oMm, oMv;
+  int rc;
+  if ((rc = dPre.put(pre, (size_t)S * slab)) || (rc = dGamma.put(gamma, Hp)) || (rc = dBeta.put(beta, Hp)) || (rc = dBias.put(bias, Hp)) ||
+      (rc = dMask.put(mask, (size_t)B * mask_ld)) || (rc = dRows.put(rows, B)) || (rc = oOut.alloc((size_t)B * Hp)) || (rc = oXhat.alloc((size_t)B * Hp)) ||
+      (rc = oInv.alloc(Hp)) || (rc = oMean.alloc(Hp)) || (rc = oVar.alloc(Hp)) || (rc = oMm.alloc(Hp)) || (rc = oMv.alloc(Hp)))
+    return rc;
+  if (moving_mean && ((rc = oMm.upload(moving_mean, Hp)) || (rc = oMv.upload(moving_var, Hp)))) return rc;
+  BnFwdArgs a;
+  a.pre = dPre.d; a.n_slabs = S; a.slab_stride = slab; a.ld = wide ? Hp : ld;
+  a.B = B; a.H = H; a.Hp = Hp; a.batchnorm = batchnorm; a.training = training; a.update_moving = update_moving;
+  a.gamma = dGamma.d; a.beta = dBeta.d; a.bias = dBias.d; a.moving_mean = oMm.p(); a.moving_var = oMv.p();
+  a.batch_mean = oMean.p(); a.batch_var = oVar.p(); a.momentum = fp[0]; a.eps = fp[1]; a.leak = fp[2]; a.drop_p = fp[3];
+  a.xhat = oXhat.p(); a.inv_std = oInv.p(); a.out = oOut.p();
+  a.nk = kbn_key(seed, stream, step); a.rows = dRows.d; a.cell_base = cell_base; a.inj_mask = dMask.d; a.inj_ld = mask_ld;
+  a.wide = wide; a.act = act;
+  std::vector<KbnOut> gather((size_t)world);
+  if (!world) rc = launch_bn_act_fwd(nullptr, a);
+  else {
+    const int Bs = B / world;
+    for (auto& g : gather) if ((rc = g.alloc((size_t)world * 2 * Hp))) return rc;
+    for (int phase = 0; phase < 2 && rc == SMX_OK; ++phase) {
+      for (int k = 0; k < world && rc == SMX_OK; ++k) {   // rank k: rows [k Bs, (k + 1) Bs) of every slab
+        BnFwdArgs r = a;
+        r.B = Bs; r.pre = a.pre + (long)k * Bs * ld; r.xhat = a.xhat + (long)k * Bs * Hp; r.out = a.out + (long)k * Bs * Hp;
+        if (a.inj_mask) r.inj_mask = a.inj_mask + (long)k * Bs * mask_ld;
+        if (a.rows) r.rows = a.rows + k * Bs; else r.cell_base = cell_base + (uint32_t)(k * Bs);
+        BnSyncArgs y; y.gather = gather[k].p(); y.rank = k; y.world = world;
+        rc = launch_bn_sync_fwd(nullptr, r, y, phase);
+      }
+      if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_bn_fwd: device synchronize failed"); rc = SMX_ERR_HIP; }
+      if (rc == SMX_OK && phase == 0) rc = kbn_all_reduce(gather, (size_t)world * 2 * Hp);
+    }
+  }
+  if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_bn_fwd: device synchronize failed"); rc = SMX_ERR_HIP; }
+  if (rc != SMX_OK) return rc;
+  bool ok = true;
+  for (const KbnOut* o : {&oOut, &oXhat, &oInv, &oMean, &oVar, &oMm, &oMv}) if ((rc = o->intact(&ok))) return rc;
+  for (const auto& g : gather) if ((rc = g.intact(&ok))) return rc;
+  *guards_ok = ok ? 1 : 0;
+  if ((rc = oOut.download(out, (size_t)B * Hp)) || (rc = oXhat.download(xhat, (size_t)B * Hp)) || (rc = oInv.download(inv_std, Hp)) ||
+      (rc = oMean.download(batch_mean, Hp)) || (rc = oVar.download(batch_var, Hp)) || (rc = oMm.download(moving_mean_out, Hp)) ||
+      (rc = oMv.download(moving_var_out, Hp)))
+    return rc;
+  return SMX_OK;
+}
+
+// ip: S, B, H, Hp, ld, wide, batchnorm, training, act, mask_ld, stream, step, cell_base, world; fp: leak, drop_p.  dgamma / dbeta:
+// [max(world, 1)][Hp] (under SyncBatchNorm every rank's share; their sum is the gradient)
+int smx_k_bn_bwd(const int32_t* ip, const float* fp, const float* dout, const float* out, const float* xhat, const float* inv_std,
+                 const float* gamma, const float* beta, const float* mask, const int32_t* rows, uint64_t seed, float* dpre, float* dgamma,
+                 float* dbeta, float* dbias, int32_t* guards_ok) {
+  SMX_REQUIRE(ip && fp && dout && out && xhat && dpre && guards_ok, "k_bn_bwd: bad arguments");
+  const int S = ip[0], B = ip[1], H = ip[2], Hp = ip[3], ld = ip[4], wide = ip[5], batchnorm = ip[6], training = ip[7], act = ip[8],
+            mask_ld = ip[9], stream = ip[10], step = ip[11], world = ip[13];
+  const uint32_t cell_base = (uint32_t)ip[12];
+  SMX_REQUIRE(S > 0 && B > 0 && H > 0 && H <= Hp && Hp % 8 == 0 && (wide || ld >= Hp) && world >= 0 && (!mask || mask_ld >= Hp), "k_bn_bwd: bad shapes");
+  SMX_REQUIRE(!batchnorm || (gamma && beta && inv_std), "k_bn_bwd: BatchNorm needs gamma, beta and inv_std");
+  SMX_REQUIRE(!world || (!wide && batchnorm && training && B % world == 0), "k_bn_bwd: SyncBatchNorm takes plain slabs, training mode and equal shards");
+  const long slab = wide ? (long)Hp * 128 : (long)B * ld;
+  const int nw = world > 1 ? world : 1;
+  KbnIn dDout, dOutF, dXhat, dInv, dGamma, dBeta, dMask; KbnRows dRows;
+  KbnOut oDpre, oDg, oDb, oDbias;
+  int rc;
+  if ((rc = dDout.put(dout, (size_t)S * slab)) || (rc = dOutF.put(out, (size_t)B * Hp)) || (rc = dXhat.put(xhat, (size_t)B * Hp)) || (rc = dInv.put(inv_std, Hp)) ||
+      (rc = dGamma.put(gamma, Hp)) || (rc = dBeta.put(beta, Hp)) || (rc = dMask.put(mask, (size_t)B * mask_ld)) || (rc = dRows.put(rows, B)) ||
+      (rc = oDpre.alloc((size_t)B * Hp)) || (rc = oDg.alloc((size_t)nw * Hp)) || (rc = oDb.alloc((size_t)nw * Hp)) || (rc = oDbias.alloc(Hp)))
+    return rc;
+  BnBwdArgs a;
+  a.dout = dDout.d; a.n_slabs = S; a.slab_stride = slab; a.ld = wide ? Hp : ld;
+  a.out = dOutF.d; a.xhat = dXhat.d; a.inv_std = dInv.d; a.gamma = dGamma.d; a.beta = dBeta.d;
+  a.B = B; a.H = H; a.Hp = Hp; a.batchnorm = batchnorm; a.training = training;
+  a.leak = fp[0]; a.drop_p = (training && fp[1] > 0.f) ? fp[1] : 0.f;
+  a.drop_scale = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
+  a.dpre = oDpre.p(); a.dgamma = oDg.p(); a.dbeta = oDb.p(); a.dbias = oDbias.p();
+  a.nk = kbn_key(seed, stream, step); a.rows = dRows.d; a.cell_base = cell_base; a.inj_mask = dMask.d; a.inj_ld = mask_ld;
+  a.wide = wide; a.act = act;
+  std::vector<KbnOut> gather((size_t)world);
+  if (!world) rc = launch_bn_act_bwd(nullptr, a);
+  else {
+    const int Bs = B / world;
+    for (auto& g : gather) if ((rc = g.alloc((size_t)world * 2 * Hp))) return rc;
+    for (int phase = 0; phase < 2 && rc == SMX_OK; ++phase) {
+      for (int k = 0; k < world && rc == SMX_OK; ++k) {
+        BnBwdArgs r = a;
+        r.B = Bs; r.dout = a.dout + (long)k * Bs * ld; r.out = a.out + (long)k * Bs * Hp; r.xhat = a.xhat + (long)k * Bs * Hp;
+        r.dpre = a.dpre + (long)k * Bs * Hp; r.dgamma = a.dgamma + (long)k * Hp; r.dbeta = a.dbeta + (long)k * Hp;
+        if (a.inj_mask) r.inj_mask = a.inj_mask + (long)k * Bs * mask_ld;
+        if (a.rows) r.rows = a.rows + k * Bs; else r.cell_base = cell_base + (uint32_t)(k * Bs);
+        BnSyncArgs y; y.gather = gather[k].p(); y.rank = k; y.world = world;
+        rc = launch_bn_sync_bwd(nullptr, r, y, phase);
+      }
+      if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_bn_bwd: device synchronize failed"); rc = SMX_ERR_HIP; }
+      if (rc == SMX_OK && phase == 0) rc = kbn_all_reduce(gather, (size_t)world * 2 * Hp);
+    }
+  }
+  if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_bn_bwd: device synchronize failed"); rc = SMX_ERR_HIP; }
+  if (rc != SMX_OK) return rc;
+  bool ok = true;
+  for (const KbnOut* o : {&oDpre, &oDg, &oDb, &oDbias}) if ((rc = o->intact(&ok))) return rc;
+  for (const auto& g : gather) if ((rc = g.intact(&ok))) return rc;
+  *guards_ok = ok ? 1 : 0;
+  if ((rc = oDpre.download(dpre, (size_t)B * Hp)) || (rc = oDg.download(dgamma, (size_t)nw * Hp)) || (rc = oDb.download(dbeta, (size_t)nw * Hp)) ||
+      (rc = oDbias.download(dbias, Hp)))
+    return rc;
+  return SMX_OK;
 }
 
 }  // extern "C"

@@ -1237,3 +1237,75 @@ def k_noise(seed, stream, step, cell_ids, width, p=0.0, sample=0):
   check(lib.smx_k_noise(int(seed), int(stream), int(step), int(sample), ids.ctypes.data_as(C.POINTER(C.c_int64)),
                         ids.size, int(width), float(p), _fp(mult), _fp(nrm)))
   return mult, nrm
+
+
+def _bn_vec(a, Hp):
+  """A per-column vector as the BatchNorm entries take it: [Hp] float32 (a shorter one is padded with zeros), None stays None"""
+  if a is None:
+    return None
+  a = np.asarray(a, np.float32).ravel()
+  if a.size < Hp:
+    a = np.concatenate([a, np.zeros(Hp - a.size, np.float32)])
+  return np.ascontiguousarray(a[:Hp])
+
+
+def _bn_slabs(x, wide):
+  """slabs [S][B][ld] (or [B][ld]) / wide [S][Hp][128] -> (array, S, rows, ld)"""
+  x = _f32(x)
+  if x.ndim == 2:
+    x = x[None]
+  if x.ndim != 3 or (wide and x.shape[2] != 128):
+    raise ValueError("slabs are [S][B][ld], wide ones [S][Hp][128]")
+  return x, x.shape[0], x.shape[1], x.shape[2]
+
+
+def k_bn_fwd(pre, B, H, Hp, gamma=None, beta=None, bias=None, moving_mean=None, moving_var=None, batchnorm=True, training=True,
+             update_moving=True, momentum=0.99, eps=1e-3, leak=0.0, act="relu", drop_p=0.0, mask=None, seed=0, stream=0, step=0,
+             rows=None, cell_base=0, wide=False, world=0):
+  """The forward BatchNorm launch by itself (smx_k_bn_fwd): `pre` = slabs [S][B][ld], or with `wide` the column-major [S][Hp][128].
+  Returns dict(out, xhat [B][Hp]; inv_std, batch_mean, batch_var, moving_mean, moving_var [Hp]; guards_ok).  What the launch does not
+  write (batch statistics in evaluation mode, everything of BatchNorm without it) comes back as NaN."""
+  lib = _hip.require_gpu()
+  pre, S, r, ld = _bn_slabs(pre, wide)
+  if (wide and r != Hp) or (not wide and r != B):
+    raise ValueError("slab rows do not match B (wide: Hp)")
+  g, b, bi, mm, mv = (_bn_vec(v, Hp) for v in (gamma, beta, bias, moving_mean, moving_var))
+  m = None if mask is None else _f32(mask)
+  rw = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+  ip = np.array([S, B, H, Hp, Hp if wide else ld, int(wide), int(batchnorm), int(training), int(update_moving), _hip.HIDDEN_ACTIVATIONS[act],
+                 0 if m is None else m.shape[1], stream, step, cell_base, world], np.int32)
+  fp = np.array([momentum, eps, leak, drop_p], np.float32)
+  o = dict(out=np.empty((B, Hp), np.float32), xhat=np.empty((B, Hp), np.float32))
+  for k in ("inv_std", "batch_mean", "batch_var", "moving_mean", "moving_var"):
+    o[k] = np.empty(Hp, np.float32)
+  ok = C.c_int32(0)
+  check(lib.smx_k_bn_fwd(_ip(ip), _fp(fp), _fp(pre), _fp(g), _fp(b), _fp(bi), _fp(mm), _fp(mv), _fp(m), None if rw is None else _ip(rw), int(seed),
+                         _fp(o["out"]), _fp(o["xhat"]), _fp(o["inv_std"]), _fp(o["batch_mean"]), _fp(o["batch_var"]), _fp(o["moving_mean"]),
+                         _fp(o["moving_var"]), C.byref(ok)))
+  o["guards_ok"] = bool(ok.value)
+  return o
+
+
+def k_bn_bwd(dout, out, xhat, B, H, Hp, inv_std=None, gamma=None, beta=None, batchnorm=True, training=True, leak=0.0, act="relu", drop_p=0.0,
+             mask=None, seed=0, stream=0, step=0, rows=None, cell_base=0, wide=False, world=0):
+  """The backward BatchNorm launch by itself (smx_k_bn_bwd) on its inputs: the d out slabs (laid out as k_bn_fwd's), the forward's out and
+  xhat [B][Hp], inv_std, gamma, beta.  Returns dict(dpre [B][Hp]; dgamma, dbeta [max(world, 1)][Hp]; dbias [Hp]; guards_ok)."""
+  lib = _hip.require_gpu()
+  dout, S, r, ld = _bn_slabs(dout, wide)
+  if (wide and r != Hp) or (not wide and r != B):
+    raise ValueError("slab rows do not match B (wide: Hp)")
+  out, xhat = _f32(out, (B, Hp)), _f32(xhat, (B, Hp))
+  iv, g, b = (_bn_vec(v, Hp) for v in (inv_std, gamma, beta))
+  m = None if mask is None else _f32(mask)
+  rw = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+  ip = np.array([S, B, H, Hp, Hp if wide else ld, int(wide), int(batchnorm), int(training), _hip.HIDDEN_ACTIVATIONS[act],
+                 0 if m is None else m.shape[1], stream, step, cell_base, world], np.int32)
+  fp = np.array([leak, drop_p], np.float32)
+  nw = max(int(world), 1)
+  o = dict(dpre=np.empty((B, Hp), np.float32), dgamma=np.empty((nw, Hp), np.float32), dbeta=np.empty((nw, Hp), np.float32),
+           dbias=np.empty(Hp, np.float32))
+  ok = C.c_int32(0)
+  check(lib.smx_k_bn_bwd(_ip(ip), _fp(fp), _fp(dout), _fp(out), _fp(xhat), _fp(iv), _fp(g), _fp(b), _fp(m), None if rw is None else _ip(rw),
+                         int(seed), _fp(o["dpre"]), _fp(o["dgamma"]), _fp(o["dbeta"]), _fp(o["dbias"]), C.byref(ok)))
+  o["guards_ok"] = bool(ok.value)
+  return o

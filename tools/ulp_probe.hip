@@ -1,5 +1,5 @@
 // ulp_probe.hip -- accuracy of the single-instruction transcendental forms the kernels use (smx_device.h) against
-// float64 on the device: max and mean relative error of v_log_f32 (as ln), v_exp_f32, v_rcp_f32, v_sqrt_f32 over the
+// float64 on the device: max and mean relative error of v_log_f32 (as ln), v_exp_f32, v_rcp_f32, v_sqrt_f32 and of rsqrtf over the
 // argument ranges that occur in the step.   hipcc --offload-arch=gfx950 -O3 tools/ulp_probe.hip -o tools/ulp_probe
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -18,6 +18,7 @@ __global__ void probe(int kind, float lo, float hi, int n, double* max_rel, doub
     case 2: got = __builtin_amdgcn_rcpf(x); ref = 1.0 / (double)x; break;
     case 3: got = __builtin_amdgcn_sqrtf(x); ref = sqrt((double)x); break;
     case 4: got = __builtin_amdgcn_logf(1.0f + x) * 0.6931471805599453f; ref = log1p((double)x); break;   // log(1 + e)
+    case 6: got = rsqrtf(x); ref = 1.0 / sqrt((double)x); break;   // (BatchNorm's inv = rsqrtf(var + eps): smx_bn.hip)
     default: got = __logf(x); ref = log((double)x); break;
   }
   const double ab = fabs((double)got - ref), rel = ref != 0.0 ? ab / fabs(ref) : ab;
@@ -33,7 +34,8 @@ int main() {
       {0, 0.97f, 1.03f, "ln x      x in [0.97, 1.03]"},
       {4, 0.03125f, 1.0f, "ln(1 + e) e in [1/32, 1] (log1p_small above its series)"},
       {1, 1e-6f, 80.f, "exp(-x)   = v_exp(x log2e), x in [1e-6, 80]"}, {2, 1e-30f, 1e30f, "1 / x     = v_rcp"},
-      {3, 1e-30f, 1e30f, "sqrt x    = v_sqrt"}, {5, 0.5f, 2.0f, "__logf    near 1 (the 14-instruction form)"}};
+      {3, 1e-30f, 1e30f, "sqrt x    = v_sqrt"}, {5, 0.5f, 2.0f, "__logf    near 1 (the 14-instruction form)"},
+      {6, 1e-18f, 1e18f, "rsqrtf x  x in [1e-18, 1e18]"}, {6, 1e-3f, 4e-3f, "rsqrtf x  x in [1e-3, 4e-3] (var + eps at small variances)"}};
   const int n = 1 << 22;
   for (auto& c : cases) {
     hipMemset(d, 0, 3 * sizeof(double));
