@@ -216,18 +216,6 @@ static int silhouette_slices(long N) {
   return (int)std::max<long>(1, std::min<long>(32, 1024 / tiles));
 }
 
-struct DeviceBuffers {   // freed on every way out
-  std::vector<void*> p;
-  ~DeviceBuffers() { for (void* q : p) hipFree(q); }
-  template <class T>
-  int get(T** d, size_t n) {
-    *d = nullptr;
-    SMX_CHECK(dmalloc(d, n));
-    p.push_back(*d);
-    return SMX_OK;
-  }
-};
-
 }  // namespace smx
 
 extern "C" {
@@ -257,7 +245,7 @@ int smx_cluster_silhouette(const float* Z, int64_t n_cells, int32_t D, const int
   const long tiles = (N + SMX_CL_TILE - 1) / SMX_CL_TILE;
   const int TJ = SMX_CL_LDS_DOUBLES / DP;
   const long slice_len = ((N + S - 1) / S + TJ - 1) / TJ * TJ;   // whole tiles of j
-  DeviceBuffers buf;
+  DeviceScratch buf;
   float* dZ; int32_t *dOff, *dCls; double *dPart, *dA, *dB;
   SMX_CHECK(buf.get(&dZ, (size_t)N * D)); SMX_CHECK(buf.get(&dOff, (size_t)K + 1)); SMX_CHECK(buf.get(&dCls, (size_t)N));
   SMX_CHECK(buf.get(&dPart, (size_t)S * K * N)); SMX_CHECK(buf.get(&dA, (size_t)N)); SMX_CHECK(buf.get(&dB, (size_t)N));
@@ -301,7 +289,7 @@ int smx_cluster_kmeans(const float* Z, int64_t n_cells, int32_t D, int32_t K, co
       hC[e * D + d] = std::isinf(v) ? (double)NAN : (double)v;
     }
   }
-  DeviceBuffers buf;
+  DeviceScratch buf;
   float* dZ; double *dC, *dMin, *dIn; int32_t *dLab, *dAct, *dActU, *dChg;   // (two lists: a copy into one never meets a launch that reads it)
   SMX_CHECK(buf.get(&dZ, (size_t)N * D)); SMX_CHECK(buf.get(&dC, hC.size())); SMX_CHECK(buf.get(&dMin, (size_t)R * N));
   SMX_CHECK(buf.get(&dIn, (size_t)R)); SMX_CHECK(buf.get(&dLab, (size_t)R * N)); SMX_CHECK(buf.get(&dAct, (size_t)R)); SMX_CHECK(buf.get(&dActU, (size_t)R));

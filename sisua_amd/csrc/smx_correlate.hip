@@ -260,20 +260,19 @@ int smx_k_col_rank2(const float* cols, int32_t n_cols, int64_t n_cells, int32_t*
   SMX_REQUIRE(cols && rank2 && nonfinite && n_cols > 0 && n_cells > 0, "bad arguments");
   SMX_REQUIRE(n_cells <= SMX_COR_MAX_CELLS, "column ranks take at most 2^20 cells");
   const size_t n = (size_t)n_cols * (size_t)n_cells;
-  float* d = nullptr;   // cols | rank2 | sort A | sort B | nonfinite
-  SMX_CHECK(dmalloc(&d, 4 * n + (size_t)n_cols));
+  DeviceScratch buf;
+  float* d;   // cols | rank2 | sort A | sort B | nonfinite
+  SMX_CHECK(buf.get(&d, 4 * n + (size_t)n_cols));
   int32_t* dr = reinterpret_cast<int32_t*>(d + n);
   unsigned* ds = reinterpret_cast<unsigned*>(d + 2 * n);
   int32_t* dn = reinterpret_cast<int32_t*>(d + 4 * n);
-  int rc = SMX_OK;
-  if (hipMemcpy(d, cols, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { set_error("smx_k_col_rank2: copy of the columns failed"); rc = SMX_ERR_HIP; }
-  if (rc == SMX_OK) rc = launch_col_rank2(nullptr, d, n_cols, (long)n_cells, ds, ds + n, dr, dn);
-  if (rc == SMX_OK && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(rank2, dr, n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess ||
-                       hipMemcpy(nonfinite, dn, (size_t)n_cols * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)) {
-    set_error("smx_k_col_rank2: the kernel or the copy of its result failed"); rc = SMX_ERR_HIP;
+  if (hipMemcpy(d, cols, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { set_error("smx_k_col_rank2: copy of the columns failed"); return SMX_ERR_HIP; }
+  SMX_CHECK(launch_col_rank2(nullptr, d, n_cols, (long)n_cells, ds, ds + n, dr, dn));
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(rank2, dr, n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(nonfinite, dn, (size_t)n_cols * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("smx_k_col_rank2: the kernel or the copy of its result failed"); return SMX_ERR_HIP;
   }
-  hipFree(d);
-  return rc;
+  return SMX_OK;
 }
 
 int smx_k_col_correlate(const float* cols, int32_t n_cols, int64_t n_cells, const int32_t* prot_rank2, const double* prot_unit, int32_t P,
@@ -282,29 +281,24 @@ int smx_k_col_correlate(const float* cols, int32_t n_cols, int64_t n_cells, cons
               n_cells > 0 && P > 0, "bad arguments");
   SMX_REQUIRE(n_cells <= SMX_COR_MAX_CELLS, "column correlations take at most 2^20 cells");
   const size_t n = (size_t)n_cols * (size_t)n_cells, pn = (size_t)P * (size_t)n_cells;
-  double* dp = nullptr;   // protein unit columns | their ranks (int32)
-  float* d = nullptr;     // cols | rank2 | sort A | sort B
-  char* ds = nullptr;     // the sums
-  int rc;
-  if ((rc = dmalloc(&dp, pn + (pn + 1) / 2)) || (rc = dmalloc(&d, 4 * n)) || (rc = dmalloc(&ds, correlate_sums_bytes((size_t)n_cols, (size_t)P)))) {
-    hipFree(dp); hipFree(d);
-    return rc;
-  }
+  DeviceScratch buf;
+  double* dp;   // protein unit columns | their ranks (int32)
+  float* d;     // cols | rank2 | sort A | sort B
+  char* ds;     // the sums
+  SMX_CHECK(buf.get(&dp, pn + (pn + 1) / 2));
+  SMX_CHECK(buf.get(&d, 4 * n));
+  SMX_CHECK(buf.get(&ds, correlate_sums_bytes((size_t)n_cols, (size_t)P)));
   int32_t* dpr = reinterpret_cast<int32_t*>(dp + pn);
   if (hipMemcpy(d, cols, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dp, prot_unit, pn * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(dpr, prot_rank2, pn * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
-    set_error("smx_k_col_correlate: copy of the operands failed"); rc = SMX_ERR_HIP;
+    set_error("smx_k_col_correlate: copy of the operands failed"); return SMX_ERR_HIP;
   }
-  if (rc == SMX_OK) {
-    CorrelateWork w;
-    w.cols = d; w.rank2 = reinterpret_cast<int32_t*>(d + n); w.sortA = reinterpret_cast<unsigned*>(d + 2 * n); w.sortB = w.sortA + n;
-    w.prot_rank2 = dpr; w.prot_unit = dp; w.sums = ds;
-    const CorrelateOut o{reinterpret_cast<long long*>(sp_Sa), reinterpret_cast<long long*>(sp_Saa), reinterpret_cast<long long*>(sp_Sab), pe_mean, pe_Sxx,
-                         pe_Sxy, nonfinite};
-    rc = correlate_kept(nullptr, w, n_cols, (long)n_cells, P, o);
-  }
-  hipFree(dp); hipFree(d); hipFree(ds);
-  return rc;
+  CorrelateWork w;
+  w.cols = d; w.rank2 = reinterpret_cast<int32_t*>(d + n); w.sortA = reinterpret_cast<unsigned*>(d + 2 * n); w.sortB = w.sortA + n;
+  w.prot_rank2 = dpr; w.prot_unit = dp; w.sums = ds;
+  const CorrelateOut o{reinterpret_cast<long long*>(sp_Sa), reinterpret_cast<long long*>(sp_Saa), reinterpret_cast<long long*>(sp_Sab), pe_mean, pe_Sxx,
+                       pe_Sxy, nonfinite};
+  return correlate_kept(nullptr, w, n_cols, (long)n_cells, P, o);
 }
 
 }  // extern "C"

@@ -54,11 +54,7 @@ int smx_dataset_upload_csr(smx_model* m, const int64_t* indptr, const int32_t* c
   for (int64_t i = 0; i < nnz; ++i) SMX_REQUIRE(cols[i] >= 0 && cols[i] < m->G, "CSR column index out of range");
   SMX_HIP(hipStreamSynchronize(m->st));
   drop_graphs(m);
-  auto fr = [](void* p) { if (p) hipFree(p); };
-  release_csr(m);
-  fr(m->X); fr(m->library); fr(m->mask); fr(m->lgx1);
-  m->X = nullptr; m->library = nullptr; m->mask = nullptr; m->lgx1 = nullptr;
-  for (int j = 0; j < SMX_MAX_LABELS; ++j) { fr(m->Y[j]); m->Y[j] = nullptr; }
+  release_dataset(m);
   m->N = n_cells; m->cell_base = cell_id_base; m->x_u16 = false; m->staged_steps = 0;   // (row ids staged against the matrix before are void)
   int rc;
   m->x_csr = true;
@@ -110,11 +106,7 @@ static int dataset_upload_impl(smx_model* m, const void* X, bool u16, int64_t n_
   for (int j = 0; j < m->cfg.n_labels; ++j) SMX_REQUIRE(labels && labels[j], "missing label matrix");
   SMX_HIP(hipStreamSynchronize(m->st));
   drop_graphs(m);
-  auto fr = [](void* p) { if (p) hipFree(p); };
-  release_csr(m);
-  fr(m->X); fr(m->library); fr(m->mask); fr(m->lgx1);
-  m->X = nullptr; m->library = nullptr; m->mask = nullptr; m->lgx1 = nullptr;
-  for (int j = 0; j < SMX_MAX_LABELS; ++j) { fr(m->Y[j]); m->Y[j] = nullptr; }
+  release_dataset(m);
   m->N = n_cells; m->cell_base = cell_id_base; m->staged_steps = 0;
   int rc;
   m->x_u16 = u16;
@@ -144,23 +136,19 @@ int smx_dataset_generate_lognormal(smx_model* m, uint64_t seed, int32_t rank, in
   SMX_REQUIRE(!m->scvi && m->cfg.n_labels == 0, "the generator makes counts only (no library prior, no labels)");
   SMX_HIP(hipStreamSynchronize(m->st));
   drop_graphs(m);
-  auto fr = [](void* p) { if (p) hipFree(p); };
-  release_csr(m);
-  fr(m->X); fr(m->library); fr(m->mask); fr(m->lgx1);
-  m->X = nullptr; m->library = nullptr; m->mask = nullptr; m->lgx1 = nullptr;
-  for (int j = 0; j < SMX_MAX_LABELS; ++j) { fr(m->Y[j]); m->Y[j] = nullptr; }
+  release_dataset(m);
   m->N = n_cells; m->cell_base = (int64_t)rank * n_cells; m->x_u16 = storage_u16 != 0; m->staged_steps = 0;
   const size_t bytes = (size_t)n_cells * (size_t)m->Gp * (m->x_u16 ? sizeof(uint16_t) : sizeof(float));
   hipError_t e = hipMalloc((void**)&m->X, bytes);   // (no memset of tens of GB: the generator writes every element of every padded row)
   if (e != hipSuccess) { m->X = nullptr; m->N = 0; set_error(std::string("hipMalloc of the resident matrix failed: ") + hipGetErrorString(e)); return SMX_ERR_NOMEM; }
   int rc;
-  float* mu = nullptr;
-  if ((rc = dmalloc(&m->lgx1, (size_t)n_cells)) || (rc = dmalloc(&mu, (size_t)m->Gp))) return rc;
+  DeviceScratch buf;
+  float* mu;
+  if ((rc = dmalloc(&m->lgx1, (size_t)n_cells)) || (rc = buf.get(&mu, (size_t)m->Gp))) return rc;
   // (Gp is a multiple of 32: the kernel covers the padded columns too, writing zeros beyond G)
   rc = launch_generate_lognormal(m->st, m->X, m->x_u16 ? 1 : 0, m->Gp, m->N, m->G, seed, (uint32_t)m->cell_base, (float)density, mu);
   if (rc == SMX_OK) rc = launch_row_stats(m->st, m->X, m->x_u16 ? 1 : 0, m->Gp, m->N, m->G, m->lgx1, nullptr);
   hipError_t es = hipStreamSynchronize(m->st);
-  hipFree(mu);
   if (rc == SMX_OK && es != hipSuccess) { set_error(std::string("generator failed: ") + hipGetErrorString(es)); rc = SMX_ERR_HIP; }
   return rc;
 }
@@ -171,10 +159,11 @@ int smx_dataset_library(smx_model* m, float stats[2]) {
   SMX_REQUIRE(m && m->X && m->N > 0, "no resident dataset");
   SMX_REQUIRE(!m->x_csr, "the resident-matrix kernels take a dense store (float32 / uint16), not the sparse one");
   SMX_HIP(hipStreamSynchronize(m->st));
-  double* work = nullptr;   // [N] log counts + [2] moments
+  DeviceScratch buf;
+  double* work;   // [N] log counts + [2] moments
   int rc;
-  if ((rc = dmalloc(&work, (size_t)m->N + 2))) return rc;
-  if (!m->library && (rc = dmalloc(&m->library, (size_t)m->N * 2))) { hipFree(work); return rc; }
+  if ((rc = buf.get(&work, (size_t)m->N + 2))) return rc;
+  if (!m->library && (rc = dmalloc(&m->library, (size_t)m->N * 2))) return rc;
   drop_graphs(m);   // a captured step may hold the old (null) library pointer
   rc = launch_row_stats(m->st, m->X, m->x_u16 ? 1 : 0, m->Gp, m->N, m->G, m->lgx1, work);
   if (rc == SMX_OK) rc = launch_library_stats(m->st, work, m->N, work + m->N, m->library);
@@ -184,7 +173,6 @@ int smx_dataset_library(smx_model* m, float stats[2]) {
     if (e == hipSuccess) e = hipStreamSynchronize(m->st);
     if (e != hipSuccess) { set_error(std::string("dataset_library failed: ") + hipGetErrorString(e)); rc = SMX_ERR_HIP; }
   }
-  hipFree(work);
   if (rc == SMX_OK && stats) { stats[0] = (float)h[0]; stats[1] = (float)h[1]; }
   return rc;
 }
@@ -197,9 +185,10 @@ int smx_dataset_corrupt(smx_model* m, double dropout, double retain_rate, uint64
   if (n_corrupted) *n_corrupted = 0;
   if (!((dropout > 0.0 && dropout < 1.0) || (retain_rate > 0.0 && retain_rate < 1.0))) return SMX_OK;   // utils.py:188-189
   SMX_HIP(hipStreamSynchronize(m->st));
-  unsigned long long* hist = nullptr;
+  DeviceScratch buf;
+  unsigned long long* hist;
   int rc;
-  if ((rc = dmalloc(&hist, 256))) return rc;
+  if ((rc = buf.get(&hist, 256))) return rc;
   CorruptArgs a;
   a.X = m->X; a.ld = m->Gp; a.N = m->N; a.G = m->G; a.u16 = m->x_u16 ? 1 : 0;
   a.k0 = (uint32_t)(seed & 0xFFFFFFFFu); a.k1 = (uint32_t)(seed >> 32); a.cell_base = (uint32_t)m->cell_base;
@@ -240,7 +229,6 @@ int smx_dataset_corrupt(smx_model* m, double dropout, double retain_rate, uint64
     if (e != hipSuccess) { set_error(std::string("dataset_corrupt failed: ") + hipGetErrorString(e)); rc = SMX_ERR_HIP; }
     if (rc == SMX_OK && n_corrupted) *n_corrupted = (int64_t)h[0];
   }
-  hipFree(hist);
   return rc;
 }
 

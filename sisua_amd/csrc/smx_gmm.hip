@@ -247,18 +247,6 @@ static int gm_slices(long N) {
   return (int)std::max<long>(1, std::min<long>(SMX_GM_MAX_SLICES, (N + SMX_GM_SLICE_CELLS - 1) / SMX_GM_SLICE_CELLS));
 }
 
-struct GmBuffers {   // freed on every way out
-  std::vector<void*> p;
-  ~GmBuffers() { for (void* q : p) hipFree(q); }
-  template <class T>
-  int get(T** d, size_t n) {
-    *d = nullptr;
-    SMX_CHECK(dmalloc(d, n));
-    p.push_back(*d);
-    return SMX_OK;
-  }
-};
-
 #define SMX_GM_DISPATCH(kernel, K, grid, args)                                                                     \
   switch (K) {                                                                                                     \
     case 2: hipLaunchKernelGGL(kernel<2>, grid, dim3(SMX_GM_TILE), 0, nullptr, args); break;                       \
@@ -329,7 +317,7 @@ int smx_gmm1d_fit(const float* X, int64_t n_cells, int32_t C, int32_t K, const f
   for (size_t e = 0; e < CR * K; ++e) SMX_REQUIRE(init_raw[e] >= 0.f && !std::isinf(init_raw[e]), "gmm1d_fit: a negative or non-finite init_raw");
   const int S = gm_slices(N), NV = 3 * K + 1;
   const long slice_len = ((N + S - 1) / S + SMX_GM_TILE - 1) / SMX_GM_TILE * SMX_GM_TILE;
-  GmBuffers buf;
+  DeviceScratch buf;
   float *dX, *dDen, *dInit; double *dT, *dNtr, *dPart, *dPar, *dLb; int32_t *dZero, *dAct, *dStop;
   SMX_CHECK(buf.get(&dX, (size_t)N * C)); SMX_CHECK(buf.get(&dT, (size_t)N * C)); SMX_CHECK(buf.get(&dDen, (size_t)C));
   SMX_CHECK(buf.get(&dInit, CR * K)); SMX_CHECK(buf.get(&dNtr, (size_t)C)); SMX_CHECK(buf.get(&dPart, CR * S * NV));
@@ -435,7 +423,7 @@ int smx_gmm1d_predict(const float* X, int64_t n_cells, int32_t C, int32_t K, con
   std::vector<long> n_pos;
   SMX_CHECK(gm_columns("gmm1d_predict", X, N, C, Xc, sum, n_pos));
   for (int c = 0; c < C; ++c) den[(size_t)c] = gm_den(sum[(size_t)c], log_norm);
-  GmBuffers buf;
+  DeviceScratch buf;
   float *dX, *dDen, *dBin; double *dPar, *dThr, *dProb, *dScore = nullptr; int32_t* dOrd;
   SMX_CHECK(buf.get(&dX, (size_t)N * C)); SMX_CHECK(buf.get(&dDen, (size_t)C)); SMX_CHECK(buf.get(&dBin, (size_t)N * C));
   SMX_CHECK(buf.get(&dPar, par.size())); SMX_CHECK(buf.get(&dThr, (size_t)C)); SMX_CHECK(buf.get(&dProb, (size_t)N * C));

@@ -353,18 +353,6 @@ static void gf_launch_scatter(int T, dim3 grid, const GfScatterArgs& sa) {
   else hipLaunchKernelGGL(gf_scatter_kernel<SMX_GF_MAX_ENTRIES>, grid, block, 0, nullptr, sa);
 }
 
-struct GfBuffers {   // freed on every way out
-  std::vector<void*> p;
-  ~GfBuffers() { for (void* q : p) hipFree(q); }
-  template <class T>
-  int get(T** d, size_t n) {
-    *d = nullptr;
-    const int rc = dmalloc(d, n);
-    if (*d) p.push_back(*d);   // (also when the clearing after a successful allocation failed)
-    return rc;
-  }
-};
-
 static int gf_check_shape(const char* who, const float* Z, int64_t n_cells, int32_t D, int32_t K) {
   const std::string w(who);
   if (!(D >= 1 && D <= SMX_GF_MAX_D)) { set_error(w + ": 1 <= D <= 64"); return SMX_ERR_INVALID; }
@@ -399,7 +387,7 @@ int smx_gmm_full_fit(const float* Z, int64_t n_cells, int32_t D, int32_t K, cons
   const size_t RK = (size_t)R * K, DD = (size_t)D * D;
   int DL = 1;
   while (DL < D) DL *= 2;
-  GfBuffers buf;
+  DeviceScratch buf;
   float* dZ; double *dResp, *dPm, *dPt, *dW, *dMu, *dCov, *dLinv, *dLogc, *dLb, *dLbPart; int32_t *dLab, *dAct, *dFlags, *dOut;
   SMX_CHECK(buf.get(&dZ, (size_t)N * D)); SMX_CHECK(buf.get(&dResp, RK * N)); SMX_CHECK(buf.get(&dPm, RK * S * (D + 1)));
   SMX_CHECK(buf.get(&dPt, RK * S * T)); SMX_CHECK(buf.get(&dW, RK)); SMX_CHECK(buf.get(&dMu, RK * D)); SMX_CHECK(buf.get(&dCov, RK * DD));
@@ -506,7 +494,7 @@ int smx_gmm_full_predict(const float* Z, int64_t n_cells, int32_t D, int32_t K, 
     logc[(size_t)k] = std::log(weights[k]) + ld;
   }
   const unsigned tiles = (unsigned)((N + SMX_GF_TILE - 1) / SMX_GF_TILE);
-  GfBuffers buf;
+  DeviceScratch buf;
   float* dZ; double *dResp, *dMu, *dLinv, *dLogc, *dScore = nullptr; int32_t *dAct, *dOut;
   SMX_CHECK(buf.get(&dZ, (size_t)N * D)); SMX_CHECK(buf.get(&dResp, (size_t)K * N)); SMX_CHECK(buf.get(&dMu, (size_t)K * D));
   SMX_CHECK(buf.get(&dLinv, K * DD)); SMX_CHECK(buf.get(&dLogc, (size_t)K)); SMX_CHECK(buf.get(&dAct, (size_t)1)); SMX_CHECK(buf.get(&dOut, (size_t)N));

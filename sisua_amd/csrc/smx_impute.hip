@@ -198,21 +198,18 @@ extern "C" {
 int smx_k_row_select(const float* rows, int32_t n_rows, int32_t G, int32_t ld, float* lo, float* hi) {
   SMX_REQUIRE(rows && lo && hi && n_rows > 0 && G > 0 && ld >= G, "bad arguments");
   const size_t n = (size_t)n_rows * (size_t)ld;
-  float *dR = nullptr, *dLo = nullptr;
-  int rc;
-  if ((rc = dmalloc(&dR, n)) || (rc = dmalloc(&dLo, 2 * (size_t)n_rows))) { hipFree(dR); return rc; }
-  rc = SMX_OK;
-  if (hipMemcpy(dR, rows, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { set_error("smx_k_row_select: copy of the rows failed"); rc = SMX_ERR_HIP; }
-  if (rc == SMX_OK) {
-    hipLaunchKernelGGL(row_select_kernel, dim3((unsigned)n_rows), dim3(256), 0, nullptr, dR, (int)G, (long)ld, dLo, dLo + n_rows);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(lo, dLo, (size_t)n_rows * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(hi, dLo + n_rows, (size_t)n_rows * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-      set_error("smx_k_row_select: the kernel or the copy of its result failed"); rc = SMX_ERR_HIP;
-    }
+  DeviceScratch buf;
+  float *dR, *dLo;
+  SMX_CHECK(buf.get(&dR, n));
+  SMX_CHECK(buf.get(&dLo, 2 * (size_t)n_rows));
+  if (hipMemcpy(dR, rows, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { set_error("smx_k_row_select: copy of the rows failed"); return SMX_ERR_HIP; }
+  hipLaunchKernelGGL(row_select_kernel, dim3((unsigned)n_rows), dim3(256), 0, nullptr, dR, (int)G, (long)ld, dLo, dLo + n_rows);
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpy(lo, dLo, (size_t)n_rows * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(hi, dLo + n_rows, (size_t)n_rows * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("smx_k_row_select: the kernel or the copy of its result failed"); return SMX_ERR_HIP;
   }
-  hipFree(dR); hipFree(dLo);
-  return rc;
+  return SMX_OK;
 }
 
 }  // extern "C"

@@ -49,20 +49,43 @@ int launch_noise_probe(hipStream_t st, NoiseKey nk, const int64_t* cell_ids, int
 }
 }  // namespace smx
 
+// Every entry point below takes its device memory from a DeviceScratch declared before its first allocation: whichever way it returns,
+// the memory is freed.
+namespace {
+// the key of a probe: what make_key gives a step's launches, from the caller's (seed, stream, sample, step)
+NoiseKey probe_key(uint64_t seed, int stream, int sample, int step) {
+  NoiseKey nk;
+  nk.k0 = (uint32_t)(seed & 0xFFFFFFFFu); nk.k1 = (uint32_t)(seed >> 32); nk.step = (uint32_t)step;
+  nk.stream = (uint32_t)((stream & 0xFF) | ((sample & 0xFFFFFF) << 8)); nk.step_ptr = nullptr; nk.draw_rows = 0;
+  return nk;
+}
+// llk[b] = the row's likelihood partials part[b][n_chunks] summed in float64, less sum_g lgamma(x + 1) (not of the 'bernoulli' /
+// 'normal' densities); x [B][G] on the host
+void llk_rows(const std::vector<float>& part, int n_chunks, const float* x, int B, int G, int likelihood, float* llk) {
+  for (int b = 0; b < B; ++b) {
+    double s = 0.0;
+    for (int c = 0; c < n_chunks; ++c) s += part[(size_t)b * n_chunks + c];
+    if (likelihood != SMX_LLK_BERNOULLI && likelihood != SMX_LLK_NORMAL)
+      for (int g = 0; g < G; ++g) { const float v = x[(size_t)b * G + g]; if (v > 0.f) s -= lgamma((double)v + 1.0); }
+    llk[b] = (float)s;
+  }
+}
+}  // namespace
+
 extern "C" {
 
 int smx_k_hiprand(uint64_t seed, int32_t n, const uint32_t* counters, uint32_t* ours, uint32_t* hiprand_words) {
   SMX_REQUIRE(n > 0 && counters && ours && hiprand_words, "bad arguments");
-  uint32_t *dC = nullptr, *dO = nullptr, *dH = nullptr;
-  int rc;
-  if ((rc = dmalloc(&dC, (size_t)4 * n)) || (rc = dmalloc(&dO, (size_t)4 * n)) || (rc = dmalloc(&dH, (size_t)4 * n))) return rc;
-  SMX_HIP(hipMemcpy(dC, counters, (size_t)16 * n, hipMemcpyHostToDevice));
+  DeviceScratch buf;
+  uint32_t *dC, *dO, *dH;
+  SMX_CHECK(buf.put(&dC, counters, (size_t)4 * n));
+  SMX_CHECK(buf.get(&dO, (size_t)4 * n));
+  SMX_CHECK(buf.get(&dH, (size_t)4 * n));
   hipLaunchKernelGGL(smx::hiprand_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, seed, (int)n, dC, dO, dH);
   SMX_HIP(hipGetLastError());
   SMX_HIP(hipDeviceSynchronize());
   SMX_HIP(hipMemcpy(ours, dO, (size_t)16 * n, hipMemcpyDeviceToHost));
   SMX_HIP(hipMemcpy(hiprand_words, dH, (size_t)16 * n, hipMemcpyDeviceToHost));
-  hipFree(dC); hipFree(dO); hipFree(dH);
   return SMX_OK;
 }
 
@@ -73,11 +96,12 @@ int smx_k_count_llk(int likelihood, int direct, const float* x, const float* pla
   const int k = llk_planes(likelihood);
   const int Gp = round_up(G, 32);
   const int nch = loss_chunks(Gp, B);
-  float *dX = nullptr, *dPl = nullptr, *dG = nullptr, *dPart = nullptr;
-  int rc;
-  if ((rc = dmalloc(&dX, (size_t)B * Gp)) || (rc = dmalloc(&dPl, (size_t)B * k * Gp)) || (rc = dmalloc(&dG, (size_t)B * k * Gp)) ||
-      (rc = dmalloc(&dPart, (size_t)B * nch)))
-    return rc;
+  DeviceScratch buf;
+  float *dX, *dPl, *dG, *dPart;
+  SMX_CHECK(buf.get(&dX, (size_t)B * Gp));
+  SMX_CHECK(buf.get(&dPl, (size_t)B * k * Gp));
+  SMX_CHECK(buf.get(&dG, (size_t)B * k * Gp));
+  SMX_CHECK(buf.get(&dPart, (size_t)B * nch));
   SMX_HIP(hipMemcpy2D(dX, (size_t)Gp * 4, x, (size_t)G * 4, (size_t)G * 4, (size_t)B, hipMemcpyHostToDevice));
   for (int c = 0; c < k; ++c)
     SMX_HIP(hipMemcpy2D(dPl + (size_t)c * Gp, (size_t)k * Gp * 4, planes + (size_t)c * B * G, (size_t)G * 4, (size_t)G * 4,
@@ -86,25 +110,16 @@ int smx_k_count_llk(int likelihood, int direct, const float* x, const float* pla
   lo.likelihood = likelihood; lo.direct = direct; lo.backward = grads != nullptr;
   lo.X = dX; lo.ldx = Gp; lo.P = dPl; lo.ldp = (long)k * Gp; lo.plane_stride = Gp; lo.dP = dG; lo.llk_part = dPart;
   lo.B = B; lo.G = G; lo.Gp = Gp; lo.grad_scale = 1.f;
-  rc = launch_count_loss(nullptr, lo);
-  if (rc == SMX_OK) {
-    std::vector<float> part((size_t)B * nch);
-    SMX_HIP(hipDeviceSynchronize());
-    SMX_HIP(hipMemcpy(part.data(), dPart, part.size() * 4, hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; ++b) {
-      double s = 0.0;
-      for (int c = 0; c < nch; ++c) s += part[(size_t)b * nch + c];
-      if (likelihood != SMX_LLK_BERNOULLI && likelihood != SMX_LLK_NORMAL)   // (-sum lgamma(x + 1): not of the 'bernoulli' / 'normal' densities)
-        for (int g = 0; g < G; ++g) { const float v = x[(size_t)b * G + g]; if (v > 0.f) s -= lgamma((double)v + 1.0); }
-      llk[b] = (float)s;
-    }
-    if (grads)
-      for (int c = 0; c < k; ++c)
-        SMX_HIP(hipMemcpy2D(grads + (size_t)c * B * G, (size_t)G * 4, dG + (size_t)c * Gp, (size_t)k * Gp * 4, (size_t)G * 4,
-                            (size_t)B, hipMemcpyDeviceToHost));
-  }
-  hipFree(dX); hipFree(dPl); hipFree(dG); hipFree(dPart);
-  return rc;
+  SMX_CHECK(launch_count_loss(nullptr, lo));
+  std::vector<float> part((size_t)B * nch);
+  SMX_HIP(hipDeviceSynchronize());
+  SMX_HIP(hipMemcpy(part.data(), dPart, part.size() * 4, hipMemcpyDeviceToHost));
+  llk_rows(part, nch, x, B, G, likelihood, llk);
+  if (grads)
+    for (int c = 0; c < k; ++c)
+      SMX_HIP(hipMemcpy2D(grads + (size_t)c * B * G, (size_t)G * 4, dG + (size_t)c * Gp, (size_t)k * Gp * 4, (size_t)G * 4,
+                          (size_t)B, hipMemcpyDeviceToHost));
+  return SMX_OK;
 }
 
 // the optimiser launch over caller-given tensors under `rule` (resolved hyper-parameters hp[4]): smx_k_adam / smx_k_opt
@@ -130,13 +145,22 @@ static int k_opt_launch(int rule, const float* hp, int32_t n_tensors, const int3
     }
     total += pad[t];
   }
-  float *dP = nullptr, *dG = nullptr, *dM = nullptr, *dV = nullptr, *dPart = nullptr, *dNorm = nullptr;
-  OptChunk* dCh = nullptr; StepState* dSt = nullptr; float2* dSch = nullptr;
-  int rc;
-  if ((rc = dmalloc(&dP, total)) || (rc = dmalloc(&dG, total)) || (rc = dmalloc(&dM, total)) || (rc = dmalloc(&dV, total)) ||
-      (rc = dmalloc(&dPart, chunks.size())) || (rc = dmalloc(&dNorm, (size_t)n_tensors)) || (rc = dmalloc(&dCh, chunks.size())) ||
-      (rc = dmalloc(&dSt, (size_t)3)) || (rc = dmalloc(&dSch, (size_t)1)))
-    return rc;
+  StepState st3[3];
+  memset(st3, 0, sizeof(st3));
+  st3[2].next = (uint32_t)(step - 1);   // optimiser steps completed so far
+  const float2 sch = make_float2(0.f, lr);   // the one-step schedule table: (beta, lr)
+  DeviceScratch buf;
+  float *dP, *dG, *dM, *dV, *dPart, *dNorm;
+  OptChunk* dCh; StepState* dSt; float2* dSch;
+  SMX_CHECK(buf.get(&dP, total));
+  SMX_CHECK(buf.get(&dG, total));
+  SMX_CHECK(buf.get(&dM, total));
+  SMX_CHECK(buf.get(&dV, total));
+  SMX_CHECK(buf.get(&dPart, chunks.size()));
+  SMX_CHECK(buf.get(&dNorm, (size_t)n_tensors));
+  SMX_CHECK(buf.put(&dCh, chunks.data(), chunks.size()));
+  SMX_CHECK(buf.put(&dSt, st3, (size_t)3));
+  SMX_CHECK(buf.put(&dSch, &sch, (size_t)1));
   auto put = [&](float* dst, const float* src) -> int {
     size_t lo = 0;
     for (int t = 0; t < n_tensors; ++t) {
@@ -153,31 +177,19 @@ static int k_opt_launch(int rule, const float* hp, int32_t n_tensors, const int3
     }
     return SMX_OK;
   };
-  rc = put(dP, params); if (rc == SMX_OK) rc = put(dG, grads); if (rc == SMX_OK) rc = put(dM, mom); if (rc == SMX_OK) rc = put(dV, vel);
-  if (rc == SMX_OK && hipMemcpy(dCh, chunks.data(), chunks.size() * sizeof(OptChunk), hipMemcpyHostToDevice) != hipSuccess) rc = SMX_ERR_HIP;
-  StepState st3[3];
-  memset(st3, 0, sizeof(st3));
-  st3[2].next = (uint32_t)(step - 1);   // optimiser steps completed so far
-  if (rc == SMX_OK && hipMemcpy(dSt, st3, sizeof(st3), hipMemcpyHostToDevice) != hipSuccess) rc = SMX_ERR_HIP;
-  const float2 sch = make_float2(0.f, lr);   // the one-step schedule table: (beta, lr)
-  if (rc == SMX_OK && hipMemcpy(dSch, &sch, sizeof(sch), hipMemcpyHostToDevice) != hipSuccess) rc = SMX_ERR_HIP;
+  SMX_CHECK(put(dP, params)); SMX_CHECK(put(dG, grads)); SMX_CHECK(put(dM, mom)); SMX_CHECK(put(dV, vel));
   // the step's scalars exactly as a training step prepares them (bias-corrected step size on the device)
   AdamArgs a;
   opt_scalars(rule, hp, a);   // (t0 = 0: the rule's count t is the step given)
-  if (rc == SMX_OK) rc = launch_step_begin(nullptr, dSt + 2, dSt, nullptr, nullptr, 0, 0, 0u, dSch, a.b1, a.b2, a.form, 0u);
-  if (rc == SMX_OK) {
-    a.params = dP; a.grads = dG; a.m = dM; a.v = dV; a.chunks = dCh; a.n_chunks = (int)chunks.size(); a.n_launch = a.n_chunks; a.gap_from = a.n_chunks; a.gap_len = 0;
-    a.partial = dPart; a.tensor_norm = dNorm; a.use_sq = 0; a.state = dSt;
-    a.clipnorm = clipnorm; a.grad_scale = 1.f; a.sched = dSch;
-    rc = launch_adam(nullptr, a);
-  }
-  if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_adam: device synchronize failed"); rc = SMX_ERR_HIP; }
-  if (rc == SMX_OK) rc = get(params, dP);
-  if (rc == SMX_OK) rc = get(mom, dM);
-  if (rc == SMX_OK) rc = get(vel, dV);
-  if (rc == SMX_OK && norms && hipMemcpy(norms, dNorm, (size_t)n_tensors * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = SMX_ERR_HIP;
-  hipFree(dP); hipFree(dG); hipFree(dM); hipFree(dV); hipFree(dPart); hipFree(dNorm); hipFree(dCh); hipFree(dSt); hipFree(dSch);
-  return rc;
+  SMX_CHECK(launch_step_begin(nullptr, dSt + 2, dSt, nullptr, nullptr, 0, 0, 0u, dSch, a.b1, a.b2, a.form, 0u));
+  a.params = dP; a.grads = dG; a.m = dM; a.v = dV; a.chunks = dCh; a.n_chunks = (int)chunks.size(); a.n_launch = a.n_chunks; a.gap_from = a.n_chunks; a.gap_len = 0;
+  a.partial = dPart; a.tensor_norm = dNorm; a.use_sq = 0; a.state = dSt;
+  a.clipnorm = clipnorm; a.grad_scale = 1.f; a.sched = dSch;
+  SMX_CHECK(launch_adam(nullptr, a));
+  SMX_HIP(hipDeviceSynchronize());
+  SMX_CHECK(get(params, dP)); SMX_CHECK(get(mom, dM)); SMX_CHECK(get(vel, dV));
+  if (norms) SMX_HIP(hipMemcpy(norms, dNorm, (size_t)n_tensors * sizeof(float), hipMemcpyDeviceToHost));
+  return SMX_OK;
 }
 
 int smx_k_adam(int32_t n_tensors, const int32_t* sizes, float* params, const float* grads, float* mom, float* vel,
@@ -211,22 +223,20 @@ int smx_k_gemm(int transA, int transB, const float* A, const float* B, int32_t M
   const int Kp = (direct || bigk) ? round_up(K, 32) : round_up(K, 4), Mp = wg ? round_up(M, 32) : round_up(M, 4);
   const int lda = transA ? Mp : Kp, a_rows = transA ? K : M, a_cols = transA ? M : K;
   const int ldb = transB ? Kp : Np, b_rows = transB ? N : K, b_cols = transB ? K : N;
-  float *dA = nullptr, *dB = nullptr, *dC = nullptr;
-  int rc;
   const int S = split_k < 1 ? 1 : split_k;
-  if ((rc = dmalloc(&dA, (size_t)a_rows * lda)) || (rc = dmalloc(&dB, (size_t)round_up(b_rows, 32) * ldb)) ||
-      (rc = dmalloc(&dC, (size_t)S * M * Np)))
-    return rc;
+  const int rowsC = transA ? Mp : M;   // (rows of C beyond M, when M was padded for k-major A, are never stored)
+  DeviceScratch buf;
+  float *dA, *dB, *dC;
+  SMX_CHECK(buf.get(&dA, (size_t)a_rows * lda));
+  SMX_CHECK(buf.get(&dB, (size_t)round_up(b_rows, 32) * ldb));
+  SMX_CHECK(buf.get(&dC, (size_t)S * rowsC * Np));
   SMX_HIP(hipMemcpy2D(dA, (size_t)lda * 4, A, (size_t)a_cols * 4, (size_t)a_cols * 4, (size_t)a_rows, hipMemcpyHostToDevice));
   SMX_HIP(hipMemcpy2D(dB, (size_t)ldb * 4, B, (size_t)b_cols * 4, (size_t)b_cols * 4, (size_t)b_rows, hipMemcpyHostToDevice));
   GemmArgs g;
   g.A = dA; g.lda = lda; g.a_kmajor = transA; g.B = dB; g.ldb = ldb; g.b_nmajor = transB;
-  g.C = dC; g.ldc = Np; g.slab_stride = (long)M * Np; g.M = transA ? Mp : M; g.N = Np; g.K = (transA) ? K : Kp;
-  if (transA) g.M = Mp;
+  g.C = dC; g.ldc = Np; g.slab_stride = (long)rowsC * Np; g.M = rowsC; g.N = Np; g.K = (transA) ? K : Kp;
   g.split_k = S; g.tile = tile_cfg;
-  int eff = 1;
-  // rows of C beyond M (when M was padded for k-major A) are never stored: allocate for Mp
-  if (transA && Mp != M) { hipFree(dC); dC = nullptr; if ((rc = dmalloc(&dC, (size_t)S * Mp * Np))) return rc; g.C = dC; g.slab_stride = (long)Mp * Np; }
+  int eff = 1, rc;
   if (direct) {
     g.K = Kp;   // (the padding of A and B is zero: dmalloc clears)
     SMX_REQUIRE(dgemm_supported(g), "tile 100 (dgemm): K >= 512 after padding to 32, split_k = 1");
@@ -236,21 +246,17 @@ int smx_k_gemm(int transA, int transB, const float* A, const float* B, int32_t M
     bk.A = dA; bk.lda = lda; bk.Bm = dB; bk.ldb = ldb; bk.b_kmajor = transB ? 0 : 1;
     bk.M = M; bk.N = Np; bk.K = Kp; bk.ldc = Np; bk.slab_stride = (long)M * Np; bk.out = dC;
     bk.n_slices = bigk_slices(bk.K, SMX_BIGK_MAX_SLICES, &bk.k_chunk);
-    float* dPart = nullptr;
-    if ((rc = dmalloc(&dPart, (size_t)bk.n_slices * (size_t)bk.slab_stride))) return rc;
-    bk.part = dPart;
-    if (!(S == 1 && bigk_supported(bk))) { hipFree(dPart); hipFree(dA); hipFree(dB); hipFree(dC); }
+    SMX_CHECK(buf.get(&bk.part, (size_t)bk.n_slices * (size_t)bk.slab_stride));
     SMX_REQUIRE(S == 1 && bigk_supported(bk), "tile 103 (bigk): K >= 4096 after padding to 32, split_k = 1");
     rc = launch_bigk(nullptr, bk);
-    if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_gemm: device synchronize failed"); rc = SMX_ERR_HIP; }
-    hipFree(dPart);
   } else if (wg) {
     g.split_k = 1; g.panel_hint = tile_cfg == 102;
     SMX_REQUIRE(S == 1 && wgrad_supported(g, K), "tiles 101 / 102: split_k = 1");
     rc = launch_wgrad_group(nullptr, &g, 1, K, 1);
   } else
   rc = launch_gemm(nullptr, g, &eff);
-  if (rc == SMX_OK && tuning("kgemm_reps", 0) > 0 && !direct && !wg && !bigk) {  // diagnostic: average launch time of this shape / tile
+  SMX_CHECK(rc);
+  if (tuning("kgemm_reps", 0) > 0 && !direct && !wg && !bigk) {  // diagnostic: average launch time of this shape / tile
     const int reps = (int)tuning("kgemm_reps", 0);
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
@@ -264,20 +270,48 @@ int smx_k_gemm(int transA, int transB, const float* A, const float* B, int32_t M
             1e3f * ms / reps);
     hipEventDestroy(e0); hipEventDestroy(e1);
   }
-  if (rc == SMX_OK) {
-    SMX_HIP(hipDeviceSynchronize());
-    const int rowsC = transA ? Mp : M;
-    std::vector<float> h((size_t)eff * rowsC * Np);
-    SMX_HIP(hipMemcpy(h.data(), dC, h.size() * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < M; ++i)
-      for (int j = 0; j < N; ++j) {
-        float s = 0.f;
-        for (int z = 0; z < eff; ++z) s += h[((size_t)z * rowsC + i) * Np + j];
-        C[(size_t)i * N + j] = s;
-      }
+  SMX_HIP(hipDeviceSynchronize());
+  std::vector<float> h((size_t)eff * rowsC * Np);
+  SMX_HIP(hipMemcpy(h.data(), dC, h.size() * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < M; ++i)
+    for (int j = 0; j < N; ++j) {
+      float s = 0.f;
+      for (int z = 0; z < eff; ++z) s += h[((size_t)z * rowsC + i) * Np + j];
+      C[(size_t)i * N + j] = s;
+    }
+  return SMX_OK;
+}
+
+// The fused head's operands on the device and its HeadFusedArgs but for the output pointers (dW, db, part, llk_part, sq_part): x [B][G] as
+// float32 and, u16 != 0, as the uint16 image the launch then reads; d [B][128]; W [128][k][G] plane by plane into [128][k * Gp]; bias
+// [k][G] into [k * Gp]; the table
+static int head_fused_stage(DeviceScratch& buf, int likelihood, int u16, const float* x, const float* d, const float* W, const float* bias,
+                            int B, int G, float grad_scale, HeadFusedArgs* a) {
+  const int k = llk_planes(likelihood), Gp = round_up(G, 32), H = 128;
+  float *dX, *dD, *dWt, *dBias, *dTab;
+  uint16_t* dX16;
+  SMX_CHECK(buf.get(&dTab, (size_t)SMX_HEAD_FUSED_TAB_BYTES / 4));
+  SMX_CHECK(buf.get(&dX, (size_t)B * Gp));
+  SMX_CHECK(buf.get(&dX16, (size_t)B * Gp));
+  SMX_CHECK(buf.put(&dD, d, (size_t)B * H));
+  SMX_CHECK(buf.get(&dWt, (size_t)H * k * Gp));
+  SMX_CHECK(buf.get(&dBias, (size_t)k * Gp));
+  SMX_HIP(hipMemcpy2D(dX, (size_t)Gp * 4, x, (size_t)G * 4, (size_t)G * 4, (size_t)B, hipMemcpyHostToDevice));
+  if (u16) {
+    std::vector<uint16_t> h16((size_t)B * Gp, 0);
+    for (int b = 0; b < B; ++b)
+      for (int g = 0; g < G; ++g) h16[(size_t)b * Gp + g] = (uint16_t)x[(size_t)b * G + g];
+    SMX_HIP(hipMemcpy(dX16, h16.data(), h16.size() * 2, hipMemcpyHostToDevice));
   }
-  hipFree(dA); hipFree(dB); hipFree(dC);
-  return rc;
+  for (int c = 0; c < k; ++c) {
+    SMX_HIP(hipMemcpy2D(dWt + (size_t)c * Gp, (size_t)k * Gp * 4, W + (size_t)c * G, (size_t)k * G * 4, (size_t)G * 4, (size_t)H, hipMemcpyHostToDevice));
+    SMX_HIP(hipMemcpy(dBias + (size_t)c * Gp, bias + (size_t)c * G, (size_t)G * 4, hipMemcpyHostToDevice));
+  }
+  a->D = dD; a->ldd = H; a->W = dWt; a->ldw = (long)k * Gp; a->bias = dBias;
+  a->X = u16 ? (const void*)dX16 : (const void*)dX; a->ldx = Gp; a->x_u16 = u16 ? 1 : 0;
+  a->slab_stride = (long)B * H; a->dtab = dTab;
+  a->B = B; a->G = G; a->Gp = Gp; a->likelihood = likelihood; a->grad_scale = grad_scale;
+  return SMX_OK;
 }
 
 // The fused output head of smx_headfused.hip over host arrays (H = 128 decoder columns, B <= 128 cells, G >= 4096 genes): W [128][k][G]
@@ -290,37 +324,22 @@ int smx_k_head_fused(int likelihood, int u16, const float* x, const float* d, co
   const int Gp = round_up(G, 32), H = 128;
   SMX_REQUIRE(head_fused_supported(B, H, Gp, k), "head_fused: unsupported shape (B <= 256, G >= 4096 after padding, 2 or 3 planes)");
   const int grid = head_fused_grid(Gp), n_gt = head_fused_chunks(Gp);
-  float *dX = nullptr, *dD = nullptr, *dWt = nullptr, *dBias = nullptr, *dGW = nullptr, *dGb = nullptr, *dPart = nullptr, *dLl = nullptr, *dSq = nullptr, *dDd = nullptr;
-  uint16_t* dX16 = nullptr; float* dTab = nullptr;
-  int rc;
-  if ((rc = dmalloc(&dTab, (size_t)SMX_HEAD_FUSED_TAB_BYTES / 4)) || (rc = dmalloc(&dX, (size_t)B * Gp)) || (rc = dmalloc(&dD, (size_t)B * H)) || (rc = dmalloc(&dWt, (size_t)H * k * Gp)) || (rc = dmalloc(&dBias, (size_t)k * Gp)) ||
-      (rc = dmalloc(&dGW, (size_t)H * k * Gp)) || (rc = dmalloc(&dGb, (size_t)k * Gp)) || (rc = dmalloc(&dPart, (size_t)grid * B * H)) ||
-      (rc = dmalloc(&dLl, (size_t)B * n_gt)) || (rc = dmalloc(&dSq, (size_t)grid * 8)) || (rc = dmalloc(&dDd, (size_t)B * H)) || (rc = dmalloc(&dX16, (size_t)B * Gp)))
-    return rc;
-  SMX_HIP(hipMemcpy2D(dX, (size_t)Gp * 4, x, (size_t)G * 4, (size_t)G * 4, (size_t)B, hipMemcpyHostToDevice));
-  if (u16) {
-    std::vector<uint16_t> h16((size_t)B * Gp, 0);
-    for (int b = 0; b < B; ++b)
-      for (int g = 0; g < G; ++g) h16[(size_t)b * Gp + g] = (uint16_t)x[(size_t)b * G + g];
-    SMX_HIP(hipMemcpy(dX16, h16.data(), h16.size() * 2, hipMemcpyHostToDevice));
-  }
-  SMX_HIP(hipMemcpy(dD, d, (size_t)B * H * 4, hipMemcpyHostToDevice));
-  for (int c = 0; c < k; ++c) {
-    SMX_HIP(hipMemcpy2D(dWt + (size_t)c * Gp, (size_t)k * Gp * 4, W + (size_t)c * G, (size_t)k * G * 4, (size_t)G * 4, (size_t)H, hipMemcpyHostToDevice));
-    SMX_HIP(hipMemcpy(dBias + (size_t)c * Gp, bias + (size_t)c * G, (size_t)G * 4, hipMemcpyHostToDevice));
-  }
+  DeviceScratch buf;
   HeadFusedArgs a;
-  a.D = dD; a.ldd = H; a.W = dWt; a.ldw = (long)k * Gp; a.bias = dBias;
-  a.X = u16 ? (const void*)dX16 : (const void*)dX; a.ldx = Gp; a.x_u16 = u16 ? 1 : 0;
-  a.dW = dGW; a.db = dGb; a.part = dPart; a.slab_stride = (long)B * H; a.llk_part = dLl; a.sq_part = dSq; a.dtab = dTab;
-  a.B = B; a.G = G; a.Gp = Gp; a.likelihood = likelihood; a.grad_scale = grad_scale;
-  int n_sq = 0;
-  long long* dDbg = nullptr;
-  if (tuning("hf_dbg", 0) > 0) { if ((rc = dmalloc(&dDbg, (size_t)128))) return rc; a.dbg = dDbg; }
-  int n_slabs = 0;
-  rc = launch_head_fused(nullptr, a, &n_slabs, &n_sq);
-  if (rc == SMX_OK) rc = launch_head_fused_reduce(nullptr, a, n_slabs, dDd);
-  if (rc == SMX_OK && reps > 0 && us) {
+  SMX_CHECK(head_fused_stage(buf, likelihood, u16, x, d, W, bias, B, G, grad_scale, &a));
+  float* dDd;
+  SMX_CHECK(buf.get(&a.dW, (size_t)H * k * Gp));
+  SMX_CHECK(buf.get(&a.db, (size_t)k * Gp));
+  SMX_CHECK(buf.get(&a.part, (size_t)grid * B * H));
+  SMX_CHECK(buf.get(&a.llk_part, (size_t)B * n_gt));
+  SMX_CHECK(buf.get(&a.sq_part, (size_t)grid * 8));
+  SMX_CHECK(buf.get(&dDd, (size_t)B * H));
+  if (tuning("hf_dbg", 0) > 0) SMX_CHECK(buf.get(&a.dbg, (size_t)128));
+  int n_sq = 0, n_slabs = 0;
+  SMX_CHECK(launch_head_fused(nullptr, a, &n_slabs, &n_sq));
+  SMX_CHECK(launch_head_fused_reduce(nullptr, a, n_slabs, dDd));
+  if (reps > 0 && us) {
+    int rc = SMX_OK;
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     hipEventRecord(e0, nullptr);
@@ -330,43 +349,33 @@ int smx_k_head_fused(int likelihood, int u16, const float* x, const float* d, co
     float ms = 0.f; hipEventElapsedTime(&ms, e0, e1);
     *us = 1e3f * ms / (float)reps;
     hipEventDestroy(e0); hipEventDestroy(e1);
+    SMX_CHECK(rc);
   }
-  if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_head_fused: device synchronize failed"); rc = SMX_ERR_HIP; }
-  if (rc == SMX_OK && dDbg) {
+  SMX_HIP(hipDeviceSynchronize());
+  if (a.dbg) {
     long long h[128];
-    hipMemcpy(h, dDbg, sizeof(h), hipMemcpyDeviceToHost);
+    hipMemcpy(h, a.dbg, sizeof(h), hipMemcpyDeviceToHost);
     for (int b = 0; b < 2; ++b) {
       fprintf(stderr, "hf stamps block %d: (prologue %lld)", b ? 100 : 0, h[64 * b] - h[64 * b + 63]);
       for (int i = 1; i < 62 && h[64 * b + i]; ++i) fprintf(stderr, " %lld", h[64 * b + i] - h[64 * b + i - 1]);
       fprintf(stderr, "\n");
     }
-
-    hipFree(dDbg);
   }
-  if (rc == SMX_OK) {
-    std::vector<float> part((size_t)B * n_gt), sq((size_t)n_sq);
-    SMX_HIP(hipMemcpy(part.data(), dLl, part.size() * 4, hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; ++b) {
-      double s = 0.0;
-      for (int c = 0; c < n_gt; ++c) s += part[(size_t)b * n_gt + c];
-      if (likelihood != SMX_LLK_BERNOULLI && likelihood != SMX_LLK_NORMAL)   // (-sum lgamma(x + 1): not of the 'bernoulli' / 'normal' densities)
-        for (int g = 0; g < G; ++g) { const float v = x[(size_t)b * G + g]; if (v > 0.f) s -= lgamma((double)v + 1.0); }
-      llk[b] = (float)s;
-    }
-    for (int c = 0; c < k; ++c) {
-      SMX_HIP(hipMemcpy2D(dW + (size_t)c * G, (size_t)k * G * 4, dGW + (size_t)c * Gp, (size_t)k * Gp * 4, (size_t)G * 4, (size_t)H, hipMemcpyDeviceToHost));
-      SMX_HIP(hipMemcpy(db + (size_t)c * G, dGb + (size_t)c * Gp, (size_t)G * 4, hipMemcpyDeviceToHost));
-    }
-    SMX_HIP(hipMemcpy(dd, dDd, (size_t)B * H * 4, hipMemcpyDeviceToHost));
-    if (sumsq) {
-      SMX_HIP(hipMemcpy(sq.data(), dSq, sq.size() * 4, hipMemcpyDeviceToHost));
-      double s = 0.0;
-      for (float v : sq) s += v;
-      *sumsq = (float)s;
-    }
+  std::vector<float> part((size_t)B * n_gt), sq((size_t)n_sq);
+  SMX_HIP(hipMemcpy(part.data(), a.llk_part, part.size() * 4, hipMemcpyDeviceToHost));
+  llk_rows(part, n_gt, x, B, G, likelihood, llk);
+  for (int c = 0; c < k; ++c) {
+    SMX_HIP(hipMemcpy2D(dW + (size_t)c * G, (size_t)k * G * 4, a.dW + (size_t)c * Gp, (size_t)k * Gp * 4, (size_t)G * 4, (size_t)H, hipMemcpyDeviceToHost));
+    SMX_HIP(hipMemcpy(db + (size_t)c * G, a.db + (size_t)c * Gp, (size_t)G * 4, hipMemcpyDeviceToHost));
   }
-  hipFree(dX); hipFree(dD); hipFree(dWt); hipFree(dBias); hipFree(dGW); hipFree(dGb); hipFree(dPart); hipFree(dLl); hipFree(dSq); hipFree(dDd); hipFree(dX16); hipFree(dTab);
-  return rc;
+  SMX_HIP(hipMemcpy(dd, dDd, (size_t)B * H * 4, hipMemcpyDeviceToHost));
+  if (sumsq) {
+    SMX_HIP(hipMemcpy(sq.data(), a.sq_part, sq.size() * 4, hipMemcpyDeviceToHost));
+    double s = 0.0;
+    for (float v : sq) s += v;
+    *sumsq = (float)s;
+  }
+  return SMX_OK;
 }
 
 // The fused head launched `launches` times on the same inputs; every launch after the first is compared on the device, bit for bit, with
@@ -381,38 +390,22 @@ int smx_k_head_fused_stress(int likelihood, int u16, const float* x, const float
   SMX_REQUIRE(head_fused_supported(B, H, Gp, k), "head_fused: unsupported shape");
   const int grid = head_fused_grid(Gp), n_gt = head_fused_chunks(Gp);
   const size_t nW = (size_t)H * k * Gp, nb = (size_t)k * Gp, nP = (size_t)grid * B * H, nL = (size_t)B * n_gt, nOut = nW + nb + nP + nL;
-  float *dX = nullptr, *dD = nullptr, *dWt = nullptr, *dBias = nullptr, *dOut = nullptr, *dRef = nullptr, *dSq = nullptr, *dTab = nullptr;
-  uint16_t* dX16 = nullptr; unsigned* dN = nullptr;
-  int rc;
-  if ((rc = dmalloc(&dTab, (size_t)SMX_HEAD_FUSED_TAB_BYTES / 4)) || (rc = dmalloc(&dX, (size_t)B * Gp)) || (rc = dmalloc(&dD, (size_t)B * H)) || (rc = dmalloc(&dWt, nW)) ||
-      (rc = dmalloc(&dBias, nb)) || (rc = dmalloc(&dOut, nOut)) || (rc = dmalloc(&dRef, nOut)) || (rc = dmalloc(&dSq, (size_t)grid * 8)) || (rc = dmalloc(&dX16, (size_t)B * Gp)) ||
-      (rc = dmalloc(&dN, (size_t)1)))
-    return rc;
-  SMX_HIP(hipMemset(dX, 0, (size_t)B * Gp * 4)); SMX_HIP(hipMemset(dWt, 0, nW * 4)); SMX_HIP(hipMemset(dBias, 0, nb * 4));
-  SMX_HIP(hipMemcpy2D(dX, (size_t)Gp * 4, x, (size_t)G * 4, (size_t)G * 4, (size_t)B, hipMemcpyHostToDevice));
-  if (u16) {
-    std::vector<uint16_t> h16((size_t)B * Gp, 0);
-    for (int b = 0; b < B; ++b)
-      for (int g = 0; g < G; ++g) h16[(size_t)b * Gp + g] = (uint16_t)x[(size_t)b * G + g];
-    SMX_HIP(hipMemcpy(dX16, h16.data(), h16.size() * 2, hipMemcpyHostToDevice));
-  }
-  SMX_HIP(hipMemcpy(dD, d, (size_t)B * H * 4, hipMemcpyHostToDevice));
-  for (int c = 0; c < k; ++c) {
-    SMX_HIP(hipMemcpy2D(dWt + (size_t)c * Gp, (size_t)k * Gp * 4, W + (size_t)c * G, (size_t)k * G * 4, (size_t)G * 4, (size_t)H, hipMemcpyHostToDevice));
-    SMX_HIP(hipMemcpy(dBias + (size_t)c * Gp, bias + (size_t)c * G, (size_t)G * 4, hipMemcpyHostToDevice));
-  }
+  DeviceScratch buf;
   HeadFusedArgs a;
-  a.D = dD; a.ldd = H; a.W = dWt; a.ldw = (long)k * Gp; a.bias = dBias;
-  a.X = u16 ? (const void*)dX16 : (const void*)dX; a.ldx = Gp; a.x_u16 = u16 ? 1 : 0;
-  a.dW = dOut; a.db = dOut + nW; a.part = dOut + nW + nb; a.slab_stride = (long)B * H; a.llk_part = dOut + nW + nb + nP; a.sq_part = dSq; a.dtab = dTab;
-  a.B = B; a.G = G; a.Gp = Gp; a.likelihood = likelihood; a.grad_scale = grad_scale;
+  SMX_CHECK(head_fused_stage(buf, likelihood, u16, x, d, W, bias, B, G, grad_scale, &a));
+  float *dOut, *dRef;
+  unsigned* dN;
+  SMX_CHECK(buf.get(&dOut, nOut));
+  SMX_CHECK(buf.get(&dRef, nOut));
+  SMX_CHECK(buf.get(&a.sq_part, (size_t)grid * 8));
+  SMX_CHECK(buf.get(&dN, (size_t)1));
+  a.dW = dOut; a.db = dOut + nW; a.part = dOut + nW + nb; a.llk_part = dOut + nW + nb + nP;
   int n_sq = 0, n_slabs = 0, differ = 0;
   long long first = -1;
   std::vector<uint32_t> ho, hr;
-  for (int it = 0; it < launches && rc == SMX_OK; ++it) {
+  for (int it = 0; it < launches; ++it) {
     SMX_HIP(hipMemsetAsync(dOut, 0xFF, nOut * 4, nullptr));
-    rc = launch_head_fused(nullptr, a, &n_slabs, &n_sq);
-    if (rc != SMX_OK) break;
+    SMX_CHECK(launch_head_fused(nullptr, a, &n_slabs, &n_sq));
     if (it == 0) { SMX_HIP(hipMemcpyAsync(dRef, dOut, nOut * 4, hipMemcpyDeviceToDevice, nullptr)); continue; }
     SMX_HIP(hipMemsetAsync(dN, 0, 4, nullptr));
     hipLaunchKernelGGL(smx::count_diff_kernel, dim3(1024), dim3(256), 0, nullptr, reinterpret_cast<const uint32_t*>(dOut), reinterpret_cast<const uint32_t*>(dRef), (long)nOut, dN);
@@ -427,31 +420,25 @@ int smx_k_head_fused_stress(int likelihood, int u16, const float* x, const float
       }
     }
   }
-  if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_head_fused_stress: device synchronize failed"); rc = SMX_ERR_HIP; }
+  SMX_HIP(hipDeviceSynchronize());
   *n_differ = differ;
   if (first_word) *first_word = first;
-  hipFree(dX); hipFree(dD); hipFree(dWt); hipFree(dBias); hipFree(dOut); hipFree(dRef); hipFree(dSq); hipFree(dX16); hipFree(dTab); hipFree(dN);
-  return rc;
+  return SMX_OK;
 }
 
 int smx_k_noise(uint64_t seed, int32_t stream, int32_t step, int32_t sample, const int64_t* cell_ids, int32_t B, int32_t width,
                 float dropout_p, float* dropout_mult, float* normal) {
   SMX_REQUIRE(cell_ids && B > 0 && width > 0, "bad arguments");
-  int64_t* dIds = nullptr; float *dM = nullptr, *dN = nullptr;
-  int rc;
-  if ((rc = dmalloc(&dIds, (size_t)B)) || (rc = dmalloc(&dM, (size_t)B * width)) || (rc = dmalloc(&dN, (size_t)B * width))) return rc;
-  SMX_HIP(hipMemcpy(dIds, cell_ids, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice));
-  NoiseKey nk;
-  nk.k0 = (uint32_t)(seed & 0xFFFFFFFFu); nk.k1 = (uint32_t)(seed >> 32); nk.step = (uint32_t)step;
-  nk.stream = (uint32_t)((stream & 0xFF) | ((sample & 0xFFFFFF) << 8)); nk.step_ptr = nullptr; nk.draw_rows = 0;
-  rc = launch_noise_probe(nullptr, nk, dIds, B, width, dropout_p, dM, dN);
-  if (rc == SMX_OK) {
-    SMX_HIP(hipDeviceSynchronize());
-    if (dropout_mult) SMX_HIP(hipMemcpy(dropout_mult, dM, (size_t)B * width * 4, hipMemcpyDeviceToHost));
-    if (normal) SMX_HIP(hipMemcpy(normal, dN, (size_t)B * width * 4, hipMemcpyDeviceToHost));
-  }
-  hipFree(dIds); hipFree(dM); hipFree(dN);
-  return rc;
+  DeviceScratch buf;
+  int64_t* dIds; float *dM, *dN;
+  SMX_CHECK(buf.put(&dIds, cell_ids, (size_t)B));
+  SMX_CHECK(buf.get(&dM, (size_t)B * width));
+  SMX_CHECK(buf.get(&dN, (size_t)B * width));
+  SMX_CHECK(launch_noise_probe(nullptr, probe_key(seed, stream, sample, step), dIds, B, width, dropout_p, dM, dN));
+  SMX_HIP(hipDeviceSynchronize());
+  if (dropout_mult) SMX_HIP(hipMemcpy(dropout_mult, dM, (size_t)B * width * 4, hipMemcpyDeviceToHost));
+  if (normal) SMX_HIP(hipMemcpy(normal, dN, (size_t)B * width * 4, hipMemcpyDeviceToHost));
+  return SMX_OK;
 }
 
 }  // extern "C"
@@ -459,16 +446,14 @@ int smx_k_noise(uint64_t seed, int32_t stream, int32_t step, int32_t sample, con
 // ---- the BatchNorm launches by themselves (smx_bn.hip: launch_bn_act_fwd / launch_bn_act_bwd pick the form; no front, no riders) ----------
 namespace {
 // An output buffer between two guard bands.  Bands and interior start as 0xFF bytes (a NaN no kernel computes): an element the launch
-// never wrote reads as NaN, and a store beside the buffer changes a band word.
+// never wrote reads as NaN, and a store beside the buffer changes a band word.  The memory is the call's DeviceScratch's.
 constexpr size_t KBN_GUARD = 256;   // floats on either side
 struct KbnOut {
   float* base = nullptr; size_t n = 0;
-  ~KbnOut() { if (base) hipFree(base); }
   float* p() const { return base + KBN_GUARD; }
-  int alloc(size_t count) {
+  int alloc(DeviceScratch& buf, size_t count) {
     n = count ? count : 1;
-    int rc = dmalloc(&base, n + 2 * KBN_GUARD);
-    if (rc) return rc;
+    SMX_CHECK(buf.get(&base, n + 2 * KBN_GUARD));
     SMX_HIP(hipMemset(base, 0xFF, (n + 2 * KBN_GUARD) * 4));
     return SMX_OK;
   }
@@ -482,34 +467,6 @@ struct KbnOut {
     return SMX_OK;
   }
 };
-struct KbnIn {   // a plain device copy of a host array (NULL stays NULL)
-  float* d = nullptr;
-  ~KbnIn() { if (d) hipFree(d); }
-  int put(const float* src, size_t count) {
-    if (!src) return SMX_OK;
-    int rc = dmalloc(&d, count);
-    if (rc) return rc;
-    SMX_HIP(hipMemcpy(d, src, count * 4, hipMemcpyHostToDevice));
-    return SMX_OK;
-  }
-};
-struct KbnRows {
-  int32_t* d = nullptr;
-  ~KbnRows() { if (d) hipFree(d); }
-  int put(const int32_t* src, size_t count) {
-    if (!src) return SMX_OK;
-    int rc = dmalloc(&d, count);
-    if (rc) return rc;
-    SMX_HIP(hipMemcpy(d, src, count * 4, hipMemcpyHostToDevice));
-    return SMX_OK;
-  }
-};
-NoiseKey kbn_key(uint64_t seed, int stream, int step) {
-  NoiseKey nk;
-  nk.k0 = (uint32_t)(seed & 0xFFFFFFFFu); nk.k1 = (uint32_t)(seed >> 32); nk.step = (uint32_t)step;
-  nk.stream = (uint32_t)(stream & 0xFF); nk.step_ptr = nullptr; nk.draw_rows = 0;
-  return nk;
-}
 // SyncBatchNorm on one device: the ranks' gather buffers [world][2][Hp] summed on the host (every other slot is a zero: the sum is exact) and
 // handed back to every rank
 int kbn_all_reduce(std::vector<KbnOut>& gather, size_t n) {
@@ -538,42 +495,42 @@ int smx_k_bn_fwd(const int32_t* ip, const float* fp, const float* pre, const flo
   SMX_REQUIRE(!batchnorm || (gamma && beta && moving_mean && moving_var), "k_bn_fwd: BatchNorm needs gamma, beta and the moving statistics");
   SMX_REQUIRE(!world || (!wide && batchnorm && training && B % world == 0), "k_bn_fwd: SyncBatchNorm takes plain slabs, training mode and equal shards");
   const long slab = wide ? (long)Hp * 128 : (long)B * ld;
-  KbnIn dPre, dGamma, dBeta, dBias, dMask; KbnRows dRows;
+  DeviceScratch buf;
+  float *dPre, *dGamma, *dBeta, *dBias, *dMask; int32_t* dRows;
   KbnOut oOut, oXhat, oInv, oMean, oVar, oMm, oMv;
   int rc;
-  if ((rc = dPre.put(pre, (size_t)S * slab)) || (rc = dGamma.put(gamma, Hp)) || (rc = dBeta.put(beta, Hp)) || (rc = dBias.put(bias, Hp)) ||
-      (rc = dMask.put(mask, (size_t)B * mask_ld)) || (rc = dRows.put(rows, B)) || (rc = oOut.alloc((size_t)B * Hp)) || (rc = oXhat.alloc((size_t)B * Hp)) ||
-      (rc = oInv.alloc(Hp)) || (rc = oMean.alloc(Hp)) || (rc = oVar.alloc(Hp)) || (rc = oMm.alloc(Hp)) || (rc = oMv.alloc(Hp)))
+  if ((rc = buf.put(&dPre, pre, (size_t)S * slab)) || (rc = buf.put(&dGamma, gamma, Hp)) || (rc = buf.put(&dBeta, beta, Hp)) || (rc = buf.put(&dBias, bias, Hp)) ||
+      (rc = buf.put(&dMask, mask, (size_t)B * mask_ld)) || (rc = buf.put(&dRows, rows, B)) || (rc = oOut.alloc(buf, (size_t)B * Hp)) || (rc = oXhat.alloc(buf, (size_t)B * Hp)) ||
+      (rc = oInv.alloc(buf, Hp)) || (rc = oMean.alloc(buf, Hp)) || (rc = oVar.alloc(buf, Hp)) || (rc = oMm.alloc(buf, Hp)) || (rc = oMv.alloc(buf, Hp)))
     return rc;
   if (moving_mean && ((rc = oMm.upload(moving_mean, Hp)) || (rc = oMv.upload(moving_var, Hp)))) return rc;
   BnFwdArgs a;
-  a.pre = dPre.d; a.n_slabs = S; a.slab_stride = slab; a.ld = wide ? Hp : ld;
+  a.pre = dPre; a.n_slabs = S; a.slab_stride = slab; a.ld = wide ? Hp : ld;
   a.B = B; a.H = H; a.Hp = Hp; a.batchnorm = batchnorm; a.training = training; a.update_moving = update_moving;
-  a.gamma = dGamma.d; a.beta = dBeta.d; a.bias = dBias.d; a.moving_mean = oMm.p(); a.moving_var = oMv.p();
+  a.gamma = dGamma; a.beta = dBeta; a.bias = dBias; a.moving_mean = oMm.p(); a.moving_var = oMv.p();
   a.batch_mean = oMean.p(); a.batch_var = oVar.p(); a.momentum = fp[0]; a.eps = fp[1]; a.leak = fp[2]; a.drop_p = fp[3];
   a.xhat = oXhat.p(); a.inv_std = oInv.p(); a.out = oOut.p();
-  a.nk = kbn_key(seed, stream, step); a.rows = dRows.d; a.cell_base = cell_base; a.inj_mask = dMask.d; a.inj_ld = mask_ld;
+  a.nk = probe_key(seed, stream, 0, step); a.rows = dRows; a.cell_base = cell_base; a.inj_mask = dMask; a.inj_ld = mask_ld;
   a.wide = wide; a.act = act;
   std::vector<KbnOut> gather((size_t)world);
-  if (!world) rc = launch_bn_act_fwd(nullptr, a);
+  if (!world) SMX_CHECK(launch_bn_act_fwd(nullptr, a));
   else {
     const int Bs = B / world;
-    for (auto& g : gather) if ((rc = g.alloc((size_t)world * 2 * Hp))) return rc;
-    for (int phase = 0; phase < 2 && rc == SMX_OK; ++phase) {
-      for (int k = 0; k < world && rc == SMX_OK; ++k) {   // rank k: rows [k Bs, (k + 1) Bs) of every slab
+    for (auto& g : gather) if ((rc = g.alloc(buf, (size_t)world * 2 * Hp))) return rc;
+    for (int phase = 0; phase < 2; ++phase) {
+      for (int k = 0; k < world; ++k) {   // rank k: rows [k Bs, (k + 1) Bs) of every slab
         BnFwdArgs r = a;
         r.B = Bs; r.pre = a.pre + (long)k * Bs * ld; r.xhat = a.xhat + (long)k * Bs * Hp; r.out = a.out + (long)k * Bs * Hp;
         if (a.inj_mask) r.inj_mask = a.inj_mask + (long)k * Bs * mask_ld;
         if (a.rows) r.rows = a.rows + k * Bs; else r.cell_base = cell_base + (uint32_t)(k * Bs);
         BnSyncArgs y; y.gather = gather[k].p(); y.rank = k; y.world = world;
-        rc = launch_bn_sync_fwd(nullptr, r, y, phase);
+        SMX_CHECK(launch_bn_sync_fwd(nullptr, r, y, phase));
       }
-      if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_bn_fwd: device synchronize failed"); rc = SMX_ERR_HIP; }
-      if (rc == SMX_OK && phase == 0) rc = kbn_all_reduce(gather, (size_t)world * 2 * Hp);
+      SMX_HIP(hipDeviceSynchronize());
+      if (phase == 0) SMX_CHECK(kbn_all_reduce(gather, (size_t)world * 2 * Hp));
     }
   }
-  if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_bn_fwd: device synchronize failed"); rc = SMX_ERR_HIP; }
-  if (rc != SMX_OK) return rc;
+  SMX_HIP(hipDeviceSynchronize());
   bool ok = true;
   for (const KbnOut* o : {&oOut, &oXhat, &oInv, &oMean, &oVar, &oMm, &oMv}) if ((rc = o->intact(&ok))) return rc;
   for (const auto& g : gather) if ((rc = g.intact(&ok))) return rc;
@@ -599,43 +556,43 @@ int smx_k_bn_bwd(const int32_t* ip, const float* fp, const float* dout, const fl
   SMX_REQUIRE(!world || (!wide && batchnorm && training && B % world == 0), "k_bn_bwd: SyncBatchNorm takes plain slabs, training mode and equal shards");
   const long slab = wide ? (long)Hp * 128 : (long)B * ld;
   const int nw = world > 1 ? world : 1;
-  KbnIn dDout, dOutF, dXhat, dInv, dGamma, dBeta, dMask; KbnRows dRows;
+  DeviceScratch buf;
+  float *dDout, *dOutF, *dXhat, *dInv, *dGamma, *dBeta, *dMask; int32_t* dRows;
   KbnOut oDpre, oDg, oDb, oDbias;
   int rc;
-  if ((rc = dDout.put(dout, (size_t)S * slab)) || (rc = dOutF.put(out, (size_t)B * Hp)) || (rc = dXhat.put(xhat, (size_t)B * Hp)) || (rc = dInv.put(inv_std, Hp)) ||
-      (rc = dGamma.put(gamma, Hp)) || (rc = dBeta.put(beta, Hp)) || (rc = dMask.put(mask, (size_t)B * mask_ld)) || (rc = dRows.put(rows, B)) ||
-      (rc = oDpre.alloc((size_t)B * Hp)) || (rc = oDg.alloc((size_t)nw * Hp)) || (rc = oDb.alloc((size_t)nw * Hp)) || (rc = oDbias.alloc(Hp)))
+  if ((rc = buf.put(&dDout, dout, (size_t)S * slab)) || (rc = buf.put(&dOutF, out, (size_t)B * Hp)) || (rc = buf.put(&dXhat, xhat, (size_t)B * Hp)) || (rc = buf.put(&dInv, inv_std, Hp)) ||
+      (rc = buf.put(&dGamma, gamma, Hp)) || (rc = buf.put(&dBeta, beta, Hp)) || (rc = buf.put(&dMask, mask, (size_t)B * mask_ld)) || (rc = buf.put(&dRows, rows, B)) ||
+      (rc = oDpre.alloc(buf, (size_t)B * Hp)) || (rc = oDg.alloc(buf, (size_t)nw * Hp)) || (rc = oDb.alloc(buf, (size_t)nw * Hp)) || (rc = oDbias.alloc(buf, Hp)))
     return rc;
   BnBwdArgs a;
-  a.dout = dDout.d; a.n_slabs = S; a.slab_stride = slab; a.ld = wide ? Hp : ld;
-  a.out = dOutF.d; a.xhat = dXhat.d; a.inv_std = dInv.d; a.gamma = dGamma.d; a.beta = dBeta.d;
+  a.dout = dDout; a.n_slabs = S; a.slab_stride = slab; a.ld = wide ? Hp : ld;
+  a.out = dOutF; a.xhat = dXhat; a.inv_std = dInv; a.gamma = dGamma; a.beta = dBeta;
   a.B = B; a.H = H; a.Hp = Hp; a.batchnorm = batchnorm; a.training = training;
   a.leak = fp[0]; a.drop_p = (training && fp[1] > 0.f) ? fp[1] : 0.f;
   a.drop_scale = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
   a.dpre = oDpre.p(); a.dgamma = oDg.p(); a.dbeta = oDb.p(); a.dbias = oDbias.p();
-  a.nk = kbn_key(seed, stream, step); a.rows = dRows.d; a.cell_base = cell_base; a.inj_mask = dMask.d; a.inj_ld = mask_ld;
+  a.nk = probe_key(seed, stream, 0, step); a.rows = dRows; a.cell_base = cell_base; a.inj_mask = dMask; a.inj_ld = mask_ld;
   a.wide = wide; a.act = act;
   std::vector<KbnOut> gather((size_t)world);
-  if (!world) rc = launch_bn_act_bwd(nullptr, a);
+  if (!world) SMX_CHECK(launch_bn_act_bwd(nullptr, a));
   else {
     const int Bs = B / world;
-    for (auto& g : gather) if ((rc = g.alloc((size_t)world * 2 * Hp))) return rc;
-    for (int phase = 0; phase < 2 && rc == SMX_OK; ++phase) {
-      for (int k = 0; k < world && rc == SMX_OK; ++k) {
+    for (auto& g : gather) if ((rc = g.alloc(buf, (size_t)world * 2 * Hp))) return rc;
+    for (int phase = 0; phase < 2; ++phase) {
+      for (int k = 0; k < world; ++k) {
         BnBwdArgs r = a;
         r.B = Bs; r.dout = a.dout + (long)k * Bs * ld; r.out = a.out + (long)k * Bs * Hp; r.xhat = a.xhat + (long)k * Bs * Hp;
         r.dpre = a.dpre + (long)k * Bs * Hp; r.dgamma = a.dgamma + (long)k * Hp; r.dbeta = a.dbeta + (long)k * Hp;
         if (a.inj_mask) r.inj_mask = a.inj_mask + (long)k * Bs * mask_ld;
         if (a.rows) r.rows = a.rows + k * Bs; else r.cell_base = cell_base + (uint32_t)(k * Bs);
         BnSyncArgs y; y.gather = gather[k].p(); y.rank = k; y.world = world;
-        rc = launch_bn_sync_bwd(nullptr, r, y, phase);
+        SMX_CHECK(launch_bn_sync_bwd(nullptr, r, y, phase));
       }
-      if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_bn_bwd: device synchronize failed"); rc = SMX_ERR_HIP; }
-      if (rc == SMX_OK && phase == 0) rc = kbn_all_reduce(gather, (size_t)world * 2 * Hp);
+      SMX_HIP(hipDeviceSynchronize());
+      if (phase == 0) SMX_CHECK(kbn_all_reduce(gather, (size_t)world * 2 * Hp));
     }
   }
-  if (rc == SMX_OK && hipDeviceSynchronize() != hipSuccess) { set_error("k_bn_bwd: device synchronize failed"); rc = SMX_ERR_HIP; }
-  if (rc != SMX_OK) return rc;
+  SMX_HIP(hipDeviceSynchronize());
   bool ok = true;
   for (const KbnOut* o : {&oDpre, &oDg, &oDb, &oDbias}) if ((rc = o->intact(&ok))) return rc;
   for (const auto& g : gather) if ((rc = g.intact(&ok))) return rc;

@@ -352,6 +352,29 @@ int dmalloc(T** p, size_t n) {
   if (e != hipSuccess) { set_error(std::string("hipMemset failed: ") + hipGetErrorString(e)); return SMX_ERR_HIP; }
   return SMX_OK;
 }
+// The device memory of one call of a model-free entry point: freed on every way out.  Declare it before the first allocation.
+struct DeviceScratch {
+  std::vector<void*> p;
+  DeviceScratch() = default;
+  DeviceScratch(const DeviceScratch&) = delete;
+  DeviceScratch& operator=(const DeviceScratch&) = delete;
+  ~DeviceScratch() { for (void* q : p) hipFree(q); }
+  template <class T>
+  int get(T** d, size_t n) {   // n zeros (dmalloc)
+    *d = nullptr;
+    const int rc = dmalloc(d, n);
+    if (*d) p.push_back(*d);
+    return rc;
+  }
+  template <class T>
+  int put(T** d, const T* host, size_t n) {   // a device copy of host[n]; NULL stays NULL
+    *d = nullptr;
+    if (!host) return SMX_OK;
+    SMX_CHECK(get(d, n));
+    SMX_HIP(hipMemcpy(*d, host, n * sizeof(T), hipMemcpyHostToDevice));
+    return SMX_OK;
+  }
+};
 // a scratch buffer kept across calls (*p, *cap elements): when need passes the capacity, the stream drains (work in flight may read the
 // buffer) and it is reallocated with max(need, want) elements
 template <typename T>
@@ -406,6 +429,7 @@ int add_tensor(smx_model* m, const std::string& name, int rows, int cols, int ch
 int build_mlp(smx_model* m, std::vector<MlpLayer>& mlp, const char* prefix, int n_in, int n, const int32_t* units,
               int stream0, float drop_p, bool batchnorm, float leak = 0.f);
 void release_csr(smx_model* m);
+void release_dataset(smx_model* m);
 NoiseKey make_key(smx_model* m, int stream, int sample, bool training);
 int alloc_rows(smx_model* m, size_t R);
 void set_row_caps(smx_model* m, size_t rows);

@@ -53,6 +53,13 @@ void release_csr(smx_model* m) {
   m->csr_indptr = nullptr; m->csr_cols = nullptr; m->csr_vals = nullptr; m->xbatch = nullptr;
   m->X = nullptr; m->x_csr = false;
 }
+// the resident dataset: the sparse store (m->X aliased its expansion tile), the dense store and the side arrays
+void release_dataset(smx_model* m) {
+  auto fr = [](auto*& p) { if (p) hipFree(p); p = nullptr; };
+  release_csr(m);
+  fr(m->X); fr(m->library); fr(m->mask); fr(m->lgx1);
+  for (int j = 0; j < SMX_MAX_LABELS; ++j) fr(m->Y[j]);
+}
 
 NoiseKey make_key(smx_model* m, int stream, int sample, bool training) {
   NoiseKey nk;
@@ -567,9 +574,9 @@ int smx_model_destroy(smx_model* m) {
   fr(m->params); fr(m->grads); fr(m->adam_m); fr(m->adam_v); fr(m->bn_moving);
   for (auto* mlp : {&m->enc, &m->encl, &m->dec})
     for (auto& L : *mlp) { fr(L.xhat); fr(L.out_buf); fr(L.dpre); fr(L.inv_std); fr(L.noise); }
-  release_csr(m);   // (the sparse store: m->X aliased its expansion tile)
-  fr(m->X); fr(m->library); fr(m->mask); fr(m->lgx1); fr(m->hostX); fr(m->hostLib); fr(m->hostLgx1); fr(m->zero_rows);
-  for (int j = 0; j < SMX_MAX_LABELS; ++j) { fr(m->Y[j]); fr(m->laby_raw[j]); fr(m->laby_draw[j]); }
+  release_dataset(m);
+  fr(m->hostX); fr(m->hostLib); fr(m->hostLgx1); fr(m->zero_rows);
+  for (int j = 0; j < SMX_MAX_LABELS; ++j) { fr(m->laby_raw[j]); fr(m->laby_draw[j]); }
   fr(m->rows2[0]); fr(m->rows2[1]); fr(m->order); fr(m->sched_tab); fr(m->state3); fr(m->mhist);
   fr(m->resp); fr(m->dklz); fr(m->zmean); fr(m->zpick); fr(m->tril_part); fr(m->ltril);
   for (auto& L : m->disc) { fr(L.xhat); fr(L.out_buf); fr(L.dpre); }

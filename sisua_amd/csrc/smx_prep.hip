@@ -164,18 +164,6 @@ __global__ __launch_bounds__(256) void prep_gene_combine_kernel(GenePart p, int 
 
 namespace {
 
-struct PrepBuffers {   // freed on every way out
-  std::vector<void*> p;
-  ~PrepBuffers() { for (void* q : p) hipFree(q); }
-  template <class T>
-  int get(T** d, size_t n) {
-    *d = nullptr;
-    SMX_CHECK(dmalloc(d, n));
-    p.push_back(*d);
-    return SMX_OK;
-  }
-};
-
 // the host matrix of both entry points and how it is cut into blocks of rows
 struct PrepInput {
   const float* x; CsrRows csr; long N; int G; long ld; long block; size_t max_nnz;
@@ -216,7 +204,7 @@ struct PrepStage {   // the device tile and, for CSR input, the staging of one b
   float* tile = nullptr; int64_t* ptr = nullptr; int32_t* cols = nullptr; float* vals = nullptr;
 };
 
-int prep_stage_alloc(PrepBuffers& buf, const PrepInput& in, PrepStage* st, bool want_tile) {
+int prep_stage_alloc(DeviceScratch& buf, const PrepInput& in, PrepStage* st, bool want_tile) {
   if (want_tile) SMX_CHECK(buf.get(&st->tile, (size_t)in.block * in.ld));
   if (!in.x) {
     SMX_CHECK(buf.get(&st->ptr, (size_t)in.block + 1));
@@ -251,15 +239,6 @@ int prep_launch_view(float* tile, long nb, int G, long ld, long r0, const PrepVi
   return SMX_OK;
 }
 
-template <class T>
-int prep_upload(PrepBuffers& buf, const T* host, size_t n, T** dev) {
-  *dev = nullptr;
-  if (!host) return SMX_OK;
-  SMX_CHECK(buf.get(dev, n));
-  SMX_HIP(hipMemcpy(*dev, host, n * sizeof(T), hipMemcpyHostToDevice));
-  return SMX_OK;
-}
-
 }  // namespace
 }  // namespace smx
 
@@ -279,13 +258,13 @@ int smx_prep_stats(const float* x, const int64_t* indptr, const int32_t* cols, c
     for (long i = 0; i < in.N; ++i) SMX_REQUIRE(row_thresh[i] == row_thresh[i], "prep_stats: a NaN row threshold");
   const long N = in.N, ld = in.ld;
   const int G = in.G, max_slices = (int)(in.block / SMX_PREP_SLICE);
-  PrepBuffers buf;
+  DeviceScratch buf;
   PrepStage st;
   SMX_CHECK(prep_stage_alloc(buf, in, &st, true));
   float *dDiv, *dThr; uint8_t* dMask;
-  SMX_CHECK(prep_upload(buf, row_div, (size_t)N, &dDiv));
-  SMX_CHECK(prep_upload(buf, row_thresh, (size_t)N, &dThr));
-  SMX_CHECK(prep_upload(buf, col_mask, (size_t)G, &dMask));
+  SMX_CHECK(buf.put(&dDiv, row_div, (size_t)N));
+  SMX_CHECK(buf.put(&dThr, row_thresh, (size_t)N));
+  SMX_CHECK(buf.put(&dMask, col_mask, (size_t)G));
   double* dTotal; int32_t* dNg;
   SMX_CHECK(buf.get(&dTotal, (size_t)N)); SMX_CHECK(buf.get(&dNg, (size_t)N));
   GenePart part; GeneAcc acc;   // (dmalloc zeroes: the accumulators start at 0)
@@ -329,13 +308,13 @@ int smx_prep_apply(const float* x, const int64_t* indptr, const int32_t* cols, c
   SMX_REQUIRE(!clip || max_value == max_value, "prep_apply: a NaN max_value");
   const long N = in.N, ld = in.ld;
   const int G = in.G;
-  PrepBuffers buf;
+  DeviceScratch buf;
   PrepStage st;
   SMX_CHECK(prep_stage_alloc(buf, in, &st, out_dense != nullptr));
   float *dDiv, *dMean, *dStd;
-  SMX_CHECK(prep_upload(buf, row_div, (size_t)N, &dDiv));
-  SMX_CHECK(prep_upload(buf, mean, (size_t)G, &dMean));
-  SMX_CHECK(prep_upload(buf, sd, (size_t)G, &dStd));
+  SMX_CHECK(buf.put(&dDiv, row_div, (size_t)N));
+  SMX_CHECK(buf.put(&dMean, mean, (size_t)G));
+  SMX_CHECK(buf.put(&dStd, sd, (size_t)G));
   const PrepView w{func, dDiv, dMean, dStd, clip != 0, max_value};
   for (long r0 = 0; r0 < N; r0 += in.block) {
     const long nb = std::min(in.block, N - r0);

@@ -149,26 +149,22 @@ int smx_k_plane_sample(int likelihood, int direct, int count_only, const float* 
   SMX_REQUIRE(planes && out && rows > 0 && rows <= 65535 && G > 0 && n_k > 0, "bad arguments");
   SMX_REQUIRE(likelihood >= SMX_LLK_NB && likelihood <= SMX_LLK_NORMAL, "unknown likelihood");
   const int k = llk_planes(likelihood), Gp = round_up(G, 32);
-  float *dPl = nullptr, *dOut = nullptr;
-  int rc;
-  if ((rc = dmalloc(&dPl, (size_t)rows * k * Gp)) || (rc = dmalloc(&dOut, (size_t)n_k * rows * G))) { hipFree(dPl); return rc; }
-  rc = SMX_OK;
-  for (int c = 0; c < k && rc == SMX_OK; ++c)
+  DeviceScratch buf;
+  float *dPl, *dOut;
+  SMX_CHECK(buf.get(&dPl, (size_t)rows * k * Gp));
+  SMX_CHECK(buf.get(&dOut, (size_t)n_k * rows * G));
+  for (int c = 0; c < k; ++c)
     if (hipMemcpy2D(dPl + (size_t)c * Gp, (size_t)k * Gp * 4, planes + (size_t)c * rows * G, (size_t)G * 4, (size_t)G * 4, (size_t)rows,
-                    hipMemcpyHostToDevice) != hipSuccess) { set_error("smx_k_plane_sample: copy of the planes failed"); rc = SMX_ERR_HIP; }
-  if (rc == SMX_OK) {
-    SampleArgs a;
-    a.P = dPl; a.ldp = (long)k * Gp; a.plane_stride = Gp; a.B = rows; a.Sn = 1; a.G = G; a.lk = likelihood; a.direct = direct ? 1 : 0;
-    a.count_only = count_only ? 1 : 0; a.n_k = n_k; a.k0 = (uint32_t)(seed & 0xFFFFFFFFu); a.k1 = (uint32_t)(seed >> 32);
-    a.dst = dOut; a.dst_k = (long)rows * G; a.dst_draw = 0;
-    rc = launch_plane_sample(nullptr, a);
+                    hipMemcpyHostToDevice) != hipSuccess) { set_error("smx_k_plane_sample: copy of the planes failed"); return SMX_ERR_HIP; }
+  SampleArgs a;
+  a.P = dPl; a.ldp = (long)k * Gp; a.plane_stride = Gp; a.B = rows; a.Sn = 1; a.G = G; a.lk = likelihood; a.direct = direct ? 1 : 0;
+  a.count_only = count_only ? 1 : 0; a.n_k = n_k; a.k0 = (uint32_t)(seed & 0xFFFFFFFFu); a.k1 = (uint32_t)(seed >> 32);
+  a.dst = dOut; a.dst_k = (long)rows * G; a.dst_draw = 0;
+  SMX_CHECK(launch_plane_sample(nullptr, a));
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, dOut, (size_t)n_k * rows * G * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("smx_k_plane_sample: the kernel or the copy of its result failed"); return SMX_ERR_HIP;
   }
-  if (rc == SMX_OK && (hipDeviceSynchronize() != hipSuccess ||
-                       hipMemcpy(out, dOut, (size_t)n_k * rows * G * 4, hipMemcpyDeviceToHost) != hipSuccess)) {
-    set_error("smx_k_plane_sample: the kernel or the copy of its result failed"); rc = SMX_ERR_HIP;
-  }
-  hipFree(dPl); hipFree(dOut);
-  return rc;
+  return SMX_OK;
 }
 
 }  // extern "C"

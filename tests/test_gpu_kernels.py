@@ -51,6 +51,20 @@ def test_gemm_layout_is_not_transposed(eng):
   assert np.array_equal(eng.k_gemm(np.eye(64, dtype=np.float32), B), B)
 
 
+def test_gemm_refusals_after_staging_leave_the_probe_usable(eng):
+  """smx_k_gemm checks these three argument combinations only after its operands are on the device: each is refused by the library's error
+  with its message (SMX_ERR_INVALID, no launch), and the next product is exact."""
+  from sisua_amd._hip import SmxError
+  A, At, B = np.ones((32, 64), np.float32), np.ones((64, 32), np.float32), np.ones((64, 32), np.float32)
+  for kw, a, text in ((dict(tile=100), A, "tile 100 (dgemm): K >= 512 after padding to 32, split_k = 1"),
+                      (dict(trans_a=True, tile=101, split_k=2), At, "tiles 101 / 102: split_k = 1"),
+                      (dict(tile=103), A, "tile 103 (bigk): K >= 4096 after padding to 32, split_k = 1")):
+    with pytest.raises(SmxError) as e:
+      eng.k_gemm(a, B, **kw)
+    assert e.value.code == -1 and str(e.value).endswith(text), (kw, str(e.value))
+  test_gemm_layout_is_not_transposed(eng)
+
+
 def _edge_grid():
   rng = np.random.default_rng(0)
   x = np.concatenate([np.zeros(24), np.arange(1, 13), rng.integers(1, 200, 20), [181, 1000, 10738, 8, 9]]).astype(np.float32)

@@ -26,6 +26,73 @@ static smx_config good_config() {
   return c;
 }
 
+// a call that must fail cleanly on a box without a device: a status other than SMX_OK and a message (SMX_ERR_INVALID would mean the
+// arguments here never reached the staging)
+#define NO_DEVICE(call) do { const int rc_ = (call); if (rc_ == SMX_OK || rc_ == SMX_ERR_INVALID || strlen(smx_last_error()) == 0) { \
+    printf("FAILED line %d: %s gave %d (last error: %s)\n", __LINE__, #call, rc_, smx_last_error()); ++failures; } } while (0)
+
+static void model_free_entries() {
+  const int N = 6, G = 4;
+  std::vector<float> x((size_t)N * G), ones(4096, 1.f), out(4096);
+  for (size_t i = 0; i < x.size(); ++i) x[i] = (float)((i * 7) % 5);   // non-negative counts, zeros among them
+  std::vector<double> dout(4096);
+  std::vector<int32_t> iout(4096);
+  std::vector<int64_t> lout(4096);
+  // -- the kernel probes
+  NO_DEVICE(smx_k_count_llk(SMX_LLK_NB, 0, x.data(), ones.data(), N, G, out.data(), out.data() + 64));
+  { const int32_t sizes[2] = {5, 70};
+    std::vector<float> p(75, 0.5f), g(75, 0.1f), m(75, 0.f), v(75, 0.f);
+    NO_DEVICE(smx_k_adam(2, sizes, p.data(), g.data(), m.data(), v.data(), 1, 1e-3f, 0.9f, 0.999f, 1e-7f, 1.f, out.data()));
+    NO_DEVICE(smx_k_opt(SMX_OPT_ADAM, nullptr, 0, 2, sizes, p.data(), g.data(), m.data(), v.data(), 1, 1e-3f, 1.f, out.data())); }
+  NO_DEVICE(smx_k_gemm(0, 0, ones.data(), ones.data(), 8, 8, 8, 1, 0, out.data()));
+  { const int B = 2, Gh = 4096;   // (the fused head's smallest panel)
+    std::vector<float> xh((size_t)B * Gh, 1.f), d((size_t)B * 128, 0.1f), W((size_t)128 * 2 * Gh, 0.01f), bias((size_t)2 * Gh, 0.f), dW(W.size()), db(bias.size());
+    int32_t n_differ = 0; int64_t first = 0;
+    NO_DEVICE(smx_k_head_fused(SMX_LLK_NB, 1, xh.data(), d.data(), W.data(), bias.data(), B, Gh, 1.f, 0, out.data(), dW.data(), db.data(), out.data() + 64, nullptr, nullptr));
+    NO_DEVICE(smx_k_head_fused_stress(SMX_LLK_NB, 0, xh.data(), d.data(), W.data(), bias.data(), B, Gh, 1.f, 2, &n_differ, &first)); }
+  { const uint32_t counters[8] = {0, 1, 2, 3, 4, 5, 6, 7}; uint32_t ours[8], theirs[8];
+    NO_DEVICE(smx_k_hiprand(8, 2, counters, ours, theirs)); }
+  { const int64_t ids[3] = {0, 5, 9};
+    NO_DEVICE(smx_k_noise(8, 1, 0, 0, ids, 3, 8, 0.1f, out.data(), out.data() + 64)); }
+  { const int32_t fwd[15] = {1, 4, 8, 8, 8, 0, 1, 1, 1, SMX_ACT_RELU, 0, 0, 0, 0, 0}, bwd[14] = {1, 4, 8, 8, 8, 0, 1, 1, SMX_ACT_RELU, 0, 0, 0, 0, 0};
+    const float ffp[4] = {0.99f, 1e-3f, 0.f, 0.f}, bfp[2] = {0.f, 0.f};
+    int32_t guards = 0;
+    NO_DEVICE(smx_k_bn_fwd(fwd, ffp, ones.data(), ones.data(), ones.data(), nullptr, ones.data(), ones.data(), nullptr, nullptr, 8, out.data(), out.data() + 64,
+                           nullptr, nullptr, nullptr, nullptr, nullptr, &guards));
+    NO_DEVICE(smx_k_bn_bwd(bwd, bfp, ones.data(), ones.data(), ones.data(), ones.data(), ones.data(), ones.data(), nullptr, nullptr, 8, out.data(), out.data() + 64,
+                           out.data() + 128, nullptr, &guards)); }
+  NO_DEVICE(smx_k_plane_sample(SMX_LLK_NB, 0, 1, ones.data(), N, G, 8, 1, out.data()));
+  NO_DEVICE(smx_k_row_select(x.data(), N, G, G, out.data(), out.data() + 64));
+  // -- correlation: G columns of N cells, one protein column
+  { std::vector<int32_t> prank(N); std::vector<double> punit(N, 0.25);
+    for (int i = 0; i < N; ++i) prank[i] = 2 * (i + 1);
+    NO_DEVICE(smx_k_col_rank2(x.data(), G, N, iout.data(), iout.data() + 64));
+    NO_DEVICE(smx_k_col_correlate(x.data(), G, N, prank.data(), punit.data(), 1, lout.data(), lout.data() + 64, lout.data() + 128, dout.data(), dout.data() + 64,
+                                  dout.data() + 128, iout.data())); }
+  // -- clustering and the mixtures: N cells, 2 classes / components
+  { const int32_t labels[N] = {0, 1, 0, 1, 0, 1}, init_idx[2] = {0, 1}, order[2 * G] = {0, 1, 0, 1, 0, 1, 0, 1};
+    const float init_raw[2 * G] = {0.f, 3.f, 0.f, 3.f, 0.f, 3.f, 0.f, 3.f};
+    const std::vector<double> half((size_t)2 * G, 0.5), thr(G, 1.0), chol = {1., 0., 0., 1., 1., 0., 0., 1.};
+    NO_DEVICE(smx_cluster_silhouette(x.data(), N, 2, labels, 2, dout.data(), dout.data() + 64));
+    NO_DEVICE(smx_cluster_kmeans(x.data(), N, 2, 2, init_idx, 1, 5, iout.data(), dout.data(), dout.data() + 64, iout.data() + 64, iout.data() + 128, nullptr));
+    NO_DEVICE(smx_gmm1d_fit(x.data(), N, G, 2, init_raw, 1, 5, 1e-3, 1e-6, 0, 1, dout.data(), iout.data(), iout.data() + 64, iout.data() + 128, dout.data() + 64,
+                            dout.data() + 128, dout.data() + 192, lout.data(), dout.data() + 256, nullptr, nullptr));
+    NO_DEVICE(smx_gmm1d_predict(x.data(), N, G, 2, half.data(), half.data(), half.data(), order, 1, thr.data(), 1, dout.data(), out.data(), nullptr));
+    NO_DEVICE(smx_gmm_full_fit(x.data(), N, 2, 2, labels, 1, 5, 1e-3, 1e-6, dout.data(), iout.data(), iout.data() + 64, iout.data() + 128, iout.data() + 192,
+                               dout.data() + 64, dout.data() + 128, dout.data() + 192, dout.data() + 256, iout.data() + 256, nullptr));
+    NO_DEVICE(smx_gmm_full_predict(x.data(), N, 2, 2, half.data(), half.data(), chol.data(), iout.data(), nullptr, nullptr)); }
+  // -- preprocessing: the dense matrix, and the same entries as CSR
+  { const int64_t indptr[N + 1] = {0, 1, 2, 2, 3, 4, 4};
+    const int32_t cols[4] = {0, 3, 1, 2};
+    const float vals[4] = {1.f, 2.f, 3.f, 4.f};
+    NO_DEVICE(smx_prep_stats(x.data(), nullptr, nullptr, nullptr, N, G, 0, 1, ones.data(), nullptr, nullptr, dout.data(), iout.data(), dout.data() + 64,
+                             dout.data() + 128, lout.data(), nullptr));
+    NO_DEVICE(smx_prep_stats(nullptr, indptr, cols, vals, N, G, 0, 0, nullptr, nullptr, nullptr, dout.data(), iout.data(), dout.data() + 64, dout.data() + 128,
+                             lout.data(), nullptr));
+    NO_DEVICE(smx_prep_apply(x.data(), nullptr, nullptr, nullptr, N, G, 0, 1, ones.data(), nullptr, nullptr, 0, 0.f, out.data(), nullptr));
+    NO_DEVICE(smx_prep_apply(nullptr, indptr, cols, vals, N, G, 0, 1, nullptr, nullptr, nullptr, 0, 0.f, nullptr, out.data())); }
+}
+
 int main() {
   EXPECT(smx_abi_version() == SMX_ABI_VERSION);
   EXPECT(smx_last_error() != nullptr);
@@ -95,6 +162,9 @@ int main() {
     if (n_dev > 0) { EXPECT(rc == SMX_OK && m != nullptr); if (rc == SMX_OK) { EXPECT(smx_num_tensors(m) > 0); EXPECT(smx_model_destroy(m) == SMX_OK); } }
     else EXPECT(rc == SMX_ERR_HIP && strlen(smx_last_error()) > 0);
   }
+  // ---- the model-free entry points, each once with valid, tiny arguments: without a device every one runs its host-side staging (argument
+  // checks, gm_columns, the CSR checks, the optimiser's chunk table), fails at its first allocation and returns with nothing held
+  if (n_dev == 0) model_free_entries();
   // ---- accessors on a null model
   EXPECT(smx_model_destroy(nullptr) == SMX_OK);
   EXPECT(smx_num_tensors(nullptr) == 0);
