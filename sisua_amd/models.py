@@ -16,12 +16,10 @@ import time
 import warnings
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
-from concurrent.futures import ThreadPoolExecutor
-
 import numpy as np
 
 from sisua_amd import distributions as D
-from sisua_amd import interpolation, optimizers
+from sisua_amd import fit_loop, interpolation, optimizers, parallel
 from sisua_amd.config import OUTPUT_ALIASES, REAL_OUTPUTS, TRIL_LATENT_POSTERIORS, ModelConfig, NetConf, RVmeta, init_params
 from sisua_amd.data import BatchDataset, SingleCellOMIC, as_csr, is_sparse, library_matrix
 from sisua_amd.engine import Engine
@@ -333,28 +331,33 @@ class SingleCellModel:
                          "SingleCellOMIC dataset to keep the dataset name and OMICs' "
                          "variables description.")
     batch_size = kwargs.pop("batch_size", 64)
-    need = len(self._outputs) - 1 + len(self._labels)   # target omics beside the counts: outputs[1:], then the label variables
-
-    def to_data(x):
-      # a SingleCellOMIC handed to a model with several variables: its first 1 + need OMICs (the reference's create_dataset default is
-      # the current OMIC alone, _single_cell_base.py:557-558, which such a model cannot train on); label variables stay unlabelled
-      # (labels_percent = 0, the reference's default) unless the caller prepares the dataset with its own labels_percent
-      if isinstance(x, SingleCellOMIC) and need > 0 and len(x.omics) > need:
-        # a variable that names one of the container's OMICs takes that OMIC, the others the remaining OMICs in order
-        rvs = self._outputs[1:] + self._labels
-        taken = [x.omics[0]] + [rv.name for rv in rvs if rv.name in x.omics[1:]]
-        rest = [o for o in x.omics[1:] if o not in taken]
-        omics = [x.omics[0]] + [rv.name if rv.name in x.omics[1:] else rest.pop(0) for rv in rvs]
-        for rv, om in zip(rvs, omics[1:]):
-          if x.get_dim(om) != rv.event_shape:
-            raise ValueError(f"variable '{rv.name}' has {rv.event_shape} dimensions but OMIC '{om}' has {x.get_dim(om)}")
-        return x.create_dataset(omics, batch_size=batch_size)
-      return _to_data(x, batch_size=batch_size)
-
-    train = to_data(train)
+    train = self._to_data(train, batch_size)
     if valid is not None:
-      valid = to_data(valid)
+      valid = self._to_data(valid, batch_size)
     return self._fit(train, valid, **kwargs)
+
+  @property
+  def _n_targets(self) -> int:
+    """Target arrays (omics) beside the counts: outputs[1:], then the label variables."""
+    return len(self._outputs) - 1 + len(self._labels)
+
+  def _to_data(self, x, batch_size) -> BatchDataset:
+    """fit's `train` / `valid` as a prepared dataset."""
+    # a SingleCellOMIC handed to a model with several variables: its first 1 + need OMICs (the reference's create_dataset default is
+    # the current OMIC alone, _single_cell_base.py:557-558, which such a model cannot train on); label variables stay unlabelled
+    # (labels_percent = 0, the reference's default) unless the caller prepares the dataset with its own labels_percent
+    need = self._n_targets
+    if isinstance(x, SingleCellOMIC) and need > 0 and len(x.omics) > need:
+      # a variable that names one of the container's OMICs takes that OMIC, the others the remaining OMICs in order
+      rvs = self._outputs[1:] + self._labels
+      taken = [x.omics[0]] + [rv.name for rv in rvs if rv.name in x.omics[1:]]
+      rest = [o for o in x.omics[1:] if o not in taken]
+      omics = [x.omics[0]] + [rv.name if rv.name in x.omics[1:] else rest.pop(0) for rv in rvs]
+      for rv, om in zip(rvs, omics[1:]):
+        if x.get_dim(om) != rv.event_shape:
+          raise ValueError(f"variable '{rv.name}' has {rv.event_shape} dimensions but OMIC '{om}' has {x.get_dim(om)}")
+      return x.create_dataset(omics, batch_size=batch_size)
+    return _to_data(x, batch_size=batch_size)
 
   def _fit(self, train: BatchDataset, valid: Optional[BatchDataset], optimizer="adam", learning_rate=1e-3, clipnorm=100.0,
            valid_freq=500, valid_interval=0, epochs=500, max_iter=-1, sample_shape=(), logging_interval=2,
@@ -395,46 +398,30 @@ class SingleCellModel:
     if n_draws > 1 and self._make_config().model == "fvae":
       raise ValueError(f"{type(self).__name__}: sample_shape {sample_shape!r} -- FactorVAE / SemiFVAE train with one draw per cell "
                        "(the discriminator's permute_dims over stacked draws has no agreed reading)")
-    from sisua_amd import data as _data
-    from sisua_amd.parallel import ControlPlane, attach_engine, env_rank_world
     # the learning rate is a schedule record (a const one for a number), keyed by the rule's own count step - t0; the engine's config keeps a
     # number (its value at count 0), the record itself is set on the engine -- on every rank of a data-parallel job alike
     self._lr_sched = learning_rate
     self._opt = dict(lr=float(learning_rate.value(0)), clipnorm=float(clipnorm or 0.0))
-    n_lab = len(self._outputs) - 1 + len(self._labels)   # target arrays beside the counts: outputs[1:], then the label variables
+    n_lab = self._n_targets
     self._check_inputs(train.arrays[0])
     if valid is not None:
       self._check_inputs(valid.arrays[0])
     if len(train.arrays) < 1 + n_lab:
       raise ValueError(f"{type(self).__name__} needs {1 + n_lab} omics per batch, the dataset has {len(train.arrays)}")
-    cp = None
-    if distributed in ("auto", True):
-      rank, local_rank, world = env_rank_world()
-    elif hasattr(distributed, "rank") and hasattr(distributed, "world"):   # a ready control plane (tests: LocalControlPlane)
-      cp, rank, local_rank, world = distributed, distributed.rank, self.device, distributed.world
-    else:
-      rank, local_rank, world = 0, 0, 1
+    cp, rank, local_rank, world = fit_loop.resolve_ranks(distributed, self.device)
     if n_draws > 1 and world > 1:
       raise ValueError(f"sample_shape {sample_shape!r}: several draws per cell are single-GPU only (world {world})")
-    B, drop_rem, lo, hi = train.batch_size, train.drop_remainder, 0, train.n_obs
+    B, drop_rem, lo, hi = fit_loop.rank_shard(train.n_obs, train.batch_size, train.drop_remainder, rank, world, dp_batch)
     if world > 1:
-      if dp_batch == "global":
-        if B % world:
-          raise ValueError(f"batch_size {B} is not divisible by the {world} ranks (dp_batch='global')")
-        B = B // world
-      elif dp_batch != "per_rank":
-        raise ValueError("dp_batch must be 'global' or 'per_rank'")
-      lo, hi = _data.shard_range(train.n_obs, rank, world)
-      drop_rem = True   # every rank runs the same number of equal-size steps
       self.device = local_rank
-      cp = cp or ControlPlane(rank, world)
+      cp = cp or parallel.ControlPlane(rank, world)
     e = self._ensure_engine(max(B, valid.batch_size if valid is not None else 1))
     e.set_train_draws(n_draws)
     if (opt_name, opt_hp) != optimizers.canonical("adam") or getattr(self, "_opt_rule", None) not in (None, optimizers.canonical("adam")):
       e.set_optimizer(opt_name, **opt_hp)   # (the same rule again: the state continues; another one starts fresh at this step)
     self._opt_rule = (opt_name, opt_hp)
     if world > 1 and e.world != world:
-      self._dp_mode = attach_engine(e, cp)
+      self._dp_mode = parallel.attach_engine(e, cp)
       self._dp_calibrated = False
     if world > 1:
       e.set_sync_bn(bool(sync_bn))
@@ -442,128 +429,36 @@ class SingleCellModel:
     if n_tr < 1 or (drop_rem and n_tr < B):
       raise ValueError(f"{n_tr} training cells cannot fill one batch of {B} (drop_remainder)")
     # train (this rank's shard) and validation cells live in ONE resident matrix; validation rows are offset
-    X = train.arrays[0][lo:hi]
-    labs = [train.arrays[1 + j][lo:hi] for j in range(n_lab)]
-    lib, mask = train.library[lo:hi], train.mask[lo:hi]
-    sparse_x = is_sparse(X) or (valid is not None and is_sparse(valid.arrays[0]))
-    if storage is None:   # (the sparse store cannot key input dropout: such a model keeps the float32 store, filled from the CSR rows)
-      storage = "csr" if (sparse_x and not self._make_config().input_dropout > 0) else "f32"
-    if valid is not None:
-      if sparse_x:   # (sparse counts stay sparse: the rows are joined as CSR)
-        import scipy.sparse as sp
-        X = sp.vstack([as_csr(sp.csr_matrix(a), copy=False) for a in (X, valid.arrays[0])], format="csr")
-      else:
-        X = np.concatenate([X, valid.arrays[0]], 0)
-      labs = [np.concatenate([a, valid.arrays[1 + j]], 0) for j, a in enumerate(labs)]
-      lib = np.concatenate([lib, valid.library], 0)
-      mask = np.concatenate([mask, valid.mask], 0)
+    X, labs, lib, mask, sparse_x = fit_loop.join_rows(train, valid, lo, hi, n_lab)
+    if storage is None:
+      storage = fit_loop.default_storage(sparse_x, self._make_config().input_dropout)
     e.upload(X, labs, lib, mask, cell_id_base=lo, storage=storage)   # Philox cell ids are GLOBAL: sharding-independent noise
     self._apply_schedules(e)   # (before the first step: a resumed fit passes its learning-rate schedule again; the step keys both)
     if cp is not None:
       cp.barrier()   # every rank's shard is resident before the first collective (the exchange's waits are bounded: no upload skew inside them)
     seed_r = train.seed + 7919 * rank
-
-    def _prepare(ep):   # pure function of (seed, epoch): prepared on a host thread while the device runs the epoch before
-      return _data.iter_batches(_data.epoch_order(n_tr, ep, train.shuffle, seed_r), B, drop_rem)
-
     if world > 1 and getattr(self, "_dp_mode", "loopback") != "loopback" and not getattr(self, "_dp_calibrated", True):
       # the exchange form of this job's steps, measured once per communicator on the job's own step and set identically on every rank
       # (parallel.calibrate_forms: trial steps from the current state, which is restored; SMX_DP_CALIBRATE=0 / SMX_DP_FORM switch it off)
-      from sisua_amd.parallel import calibrate_forms
-      ids = np.concatenate([np.asarray(b, np.int32) for b in _prepare(0) if len(b) == B] or [np.zeros(0, np.int32)])
+      ep_0 = fit_loop.epoch_batches(n_tr, B, drop_rem, train.shuffle, seed_r, 0)
+      ids = np.concatenate([np.asarray(b, np.int32) for b in ep_0 if len(b) == B] or [np.zeros(0, np.int32)])
       if ids.size >= B:
-        self.dp_report = calibrate_forms(e, cp, self._dp_mode, np.resize(ids, 35 * B), B)
+        self.dp_report = parallel.calibrate_forms(e, cp, self._dp_mode, np.resize(ids, 35 * B), B)
       self._dp_calibrated = True
-
-    spe = n_tr // B if drop_rem else -(-n_tr // B)
-    hist_t, hist_v = self.train_history, self.valid_history
-    it = int(e.step)
-    ep0 = it // spe
-    it_end = (int(epochs) if epochs_are_total else ep0 + int(epochs)) * spe
-    if max_iter and max_iter > 0:
-      # a resumed run (`epochs_are_total`: the schedule counts from step 0 of the experiment, train.py) keeps the ORIGINAL
-      # cap: max_iter is then an absolute step count as well, not `max_iter` more steps from the restored one
-      it_end = min(it_end, int(max_iter) if epochs_are_total else it + int(max_iter))
-    best, bad, t_log, stop = np.inf, 0, time.time(), False
-    pool = ThreadPoolExecutor(max_workers=1)
-    # One library call covers every step up to the next event on the host's side -- a validation pass, the end of the
-    # schedule, a ragged batch, a progress line -- across epoch boundaries (at 26 steps per epoch a call per epoch left
-    # the device idle for ~8 % of the time between calls).  The per-epoch history comes from the per-step scalars the
-    # device keeps (smx_metrics_history), cut at the epoch boundaries afterwards.
-    max_chunk = 4096 if not verbose else max(spe, 512)
-    cache, pending = {}, {}
-
-    def batches_of(ep):
-      if ep not in cache:
-        cache[ep] = pending.pop(ep).result() if ep in pending else _prepare(ep)
-      return cache[ep]
-
-    def prefetch(ep_from, ep_to):   # on the host thread, while the device runs the chunk just launched
-      for ep in range(ep_from, ep_to):
-        if ep not in cache and ep not in pending and ep * spe < it_end:
-          pending[ep] = pool.submit(_prepare, ep)
-
-    acc = {}
-    first_call = True
-    try:
-      prefetch(ep0, ep0 + 2)
-      while it < it_end and not stop:
-        until_valid = valid_freq - (it % valid_freq) if valid_freq and valid_freq > 0 else it_end - it
-        want = max(1, min(it_end - it, until_valid, max_chunk))
-        if first_call and want > 2 * spe:
-          # the call's FIRST chunk is two epochs: the device starts after two epochs' schedule instead of after the ~20 a valid_freq of 500 spans
-          # (4-6 ms of a 50-epoch fit), and the host thread prepares the rest while it runs; later chunks are as long as before
-          want = 2 * spe - (it % spe)
-        first_call = False
-        # gather `want` steps of equal batch size, walking over epoch boundaries
-        parts, n, bs, j = [], 0, None, it
-        while n < want:
-          ep, pos = divmod(j, spe)
-          if n > 0 and ep not in cache and ep in pending and not pending[ep].done():
-            break   # (the host thread is still preparing that epoch: launch what is gathered instead of waiting for it)
-          b = batches_of(ep)
-          take = 0
-          if drop_rem:   # every batch has B cells: the run's length is arithmetic
-            bs = B
-            take = min(spe - pos, want - n)
-          while not drop_rem and pos + take < spe and n + take < want and (bs is None or len(b[pos + take]) == bs):
-            if bs is None:
-              bs = len(b[pos])   # a ragged last batch (drop_remainder=False, the reference's default for fit(SingleCellOMIC)) is a step of its own
-            take += 1
-          if take == 0:
-            break
-          parts += b[pos:pos + take]
-          n += take
-          j += take
-          if pos + take < spe:   # stopped inside the epoch (ragged batch ahead or enough steps)
-            break
-        order = np.concatenate(parts).astype(np.int32)
-        first_ep, last_ep = it // spe, (it + n - 1) // spe
-        for ep in [k for k in cache if k < first_ep]:
-          del cache[ep]
+    spe = fit_loop.steps_per_epoch(n_tr, B, drop_rem)
+    plan = fit_loop.StepPlan(e.step, spe, epochs, max_iter, epochs_are_total, valid_freq, 4096 if not verbose else max(spe, 512))
+    history = fit_loop.EpochHistory(self.train_history, spe)   # from the per-step scalars the device keeps, cut at the epoch boundaries
+    early = fit_loop.EarlyStop(earlystop_threshold, earlystop_patience, earlystop_min_epoch)
+    it, t_log, stop = plan.it0, time.time(), False
+    with fit_loop.EpochFeed(n_tr, B, drop_rem, train.shuffle, seed_r, plan.it_end) as feed:
+      feed.prefetch(plan.ep0, plan.ep0 + 2)
+      while it < plan.it_end and not stop:
+        order, n, bs = feed.gather(it, plan.want(it))
         m = e.train_steps(order, n, bs, metrics=True)   # (eager launches: a captured hipGraph of the step replays 11 % slower)
-        nxt = min(it_end - (it + n), valid_freq if valid_freq and valid_freq > 0 else max_chunk, max_chunk)
-        prefetch(last_ep, last_ep + 2 + max(nxt, 0) // max(spe, 1))   # what the next call will walk
+        last_ep = (it + n - 1) // spe
+        feed.prefetch(last_ep, last_ep + plan.epochs_ahead(it + n))   # what the next call will walk
         h = e.metrics_history(n)
-        # per-epoch means: cut the per-step scalars at the epoch boundaries (every key at once: one reduction per epoch, not one per key and epoch)
-        keys = list(h)
-        H = np.stack([np.asarray(h[k], np.float32) for k in keys])   # [key][step]
-        s0 = 0
-        while s0 < n:
-          ep_here = (it + s0) // spe
-          s1 = min(n, (ep_here + 1) * spe - it)
-          done = it + s1 == (ep_here + 1) * spe   # the epoch is complete: one value per epoch, the mean over its steps
-          if done and not acc:
-            for k, mean in zip(keys, H[:, s0:s1].mean(axis=1)):
-              hist_t.setdefault(k, []).append(float(mean))
-          else:
-            for i_k, k in enumerate(keys):
-              acc.setdefault(k, []).append(H[i_k, s0:s1])
-            if done:
-              for k, seg in acc.items():
-                hist_t.setdefault(k, []).append(float(np.mean(np.concatenate(seg))))
-              acc = {}
-          s0 = s1
+        history.add(it, n, h)
         it += n
         epoch = (it - 1) // spe
         if m["nan_flag"] or not np.isfinite(h["loss"]).all():
@@ -575,23 +470,13 @@ class SingleCellModel:
           t_log = time.time()
         if valid is not None and valid_freq and it % valid_freq == 0:
           vl = self._validate(e, valid, n_tr, cp)
-          hist_v.setdefault("val_loss", []).append(vl)
-          improved = vl < best * (1.0 - float(earlystop_threshold)) if np.isfinite(best) else True
-          if vl < best:
-            best = vl
+          self.valid_history.setdefault("val_loss", []).append(vl)
+          better, stop = early.update(vl, epoch)
+          if better:
             self._checkpoint(checkpoint, rank, cp, e)
-          bad = 0 if improved else bad + 1
-          if earlystop_patience and bad >= int(earlystop_patience) and epoch >= int(earlystop_min_epoch):
-            stop = True
-      if acc:   # the schedule ended (max_iter, early stop) inside an epoch: its mean over the steps that ran
-        for k, seg in acc.items():
-          hist_t.setdefault(k, []).append(float(np.mean(np.concatenate(seg))))
-    finally:
-      for f in pending.values():
-        f.cancel()
-      pool.shutdown(wait=True)
-    if valid is not None and not hist_v.get("val_loss"):
-      hist_v.setdefault("val_loss", []).append(self._validate(e, valid, n_tr, cp))
+      history.flush()   # the schedule ended (max_iter, early stop) inside an epoch: its mean over the steps that ran
+    if valid is not None and not self.valid_history.get("val_loss"):
+      self.valid_history.setdefault("val_loss", []).append(self._validate(e, valid, n_tr, cp))
     if valid is None:
       self._checkpoint(checkpoint, rank, cp, e)
     if cp is not None:
