@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 11
+#define SMX_ABI_VERSION 12
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -820,6 +820,54 @@ int smx_prep_stats(const float* x, const int64_t* indptr, const int32_t* cols, c
 int smx_prep_apply(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_cells, int32_t n_genes,
                    int32_t block_rows, int32_t func, const float* row_div, const float* mean, const float* sd, int32_t clip,
                    float max_value, float* out_dense, float* out_vals);
+
+/* ---- exact PCA of a count matrix (smx_pca.hip; model-free: smx_init only) ----------- */
+/* Both entries take the host matrix in the forms of smx_prep_stats (dense x, or CSR with x = NULL) and stream it in blocks of block_rows
+ * rows as there.  n_genes <= 8192 on this route (the covariance takes 8 n_genes^2 bytes), and the limits of smx_prep_stats: anything else
+ * is SMX_ERR_INVALID before any device work.
+ *
+ * smx_pca_cov: mean [n_genes] = the float64 column sums / n_cells, the sums in the order of smx_prep_stats' gene_sum (slices of 64
+ * consecutive rows added in row order, the slices in order).  cov [n_genes][n_genes] = sum_r (x_r - mean)^T (x_r - mean) / (n_cells - 1),
+ * the two-pass form: the operands are the float64 differences (double)x - mean, the products and sums are float64 on the matrix pipe
+ * (v_mfma_f64_16x16x4_f64).  An entry's sum runs over the global rows in order, four at a time, in one accumulator that is carried exactly
+ * between blocks; no atomics.  The lower triangle is computed and mirrored, so cov is exactly symmetric, and mean and cov are the same
+ * bits for every block_rows, for dense and CSR input, and from call to call.  A constant column has variance exactly 0.  n_cells >= 2.
+ * Device memory: the tile and the staged CSR block, 24 bytes x (block_rows / 64) x n_genes of partial sums, and 8 x (n_genes rounded up
+ * to 64)^2 bytes of accumulators.
+ *
+ * smx_pca_project: out [n_cells][n_components] float32 = (x - mean) . components^T for mean [n_genes] and components
+ * [n_components][n_genes] float64 (finite), 1 <= n_components <= 128.  Differences, products and sums are float64 (the same pipe),
+ * rounded once to float32.  The genes of a sum are taken in chunks of 16; within chunk t the steps s = 0 .. 3 add genes 16 t + 4 q + s,
+ * q = 0 .. 3 in this order: a function of n_genes alone, so out is the same bits for every block_rows and for dense and CSR input.
+ * Device memory: the tile and the staged CSR block, 8 x n_components x n_genes bytes of components, 4 x block_rows x n_components of
+ * output. */
+int smx_pca_cov(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_cells, int32_t n_genes,
+                int32_t block_rows, double* mean, double* cov);
+int smx_pca_project(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_cells, int32_t n_genes,
+                    int32_t block_rows, const double* mean, const double* components, int32_t n_components, float* out);
+
+/* ---- exact nearest neighbours and UMAP connectivities (smx_knn.hip; model-free: smx_init only) ----------- */
+/* smx_knn: for every cell i of the host cells Z [n_cells][D] float32 the k OTHER cells j != i with the smallest d2(i, j) = sum_d (z_i[d] -
+ * z_j[d])^2, float64 in the direct form (four chains by d mod 4 with fma, then (s0 + s1) + (s2 + s3); never the Gram form).  The candidates
+ * are ordered by (d2, j) ascending, a total order: the result does not depend on how the library cuts the work (the j range is cut into
+ * max(1, min(32, 1024 / ceil(n_cells / 256))) slices whose sorted lists a second launch merges; developer knob "knn_slices"), and
+ * duplicated cells are ordinary neighbours at distance 0.  idx [n_cells][k] int32, dist [n_cells][k] float64 = sqrt(d2), nearest first.
+ * No float atomics; two calls give the same bits.  1 <= D <= 128, 1 <= k <= 256, k < n_cells < 2^31, every entry of Z finite: anything
+ * else is SMX_ERR_INVALID before any device work.  Device memory: 12 x slices x k x n_cells bytes of lists, 4 n_cells D (Z), 12 k
+ * n_cells (results).  The cost is n_cells^2 x D float64 operations: exact by design, no approximate search is built.
+ *
+ * smx_knn_umap: UMAP's smooth_knn_dist and compute_membership_strengths (local_connectivity = 1, bandwidth = 1) on a neighbour table
+ * idx / dist [n_cells][K] whose column 0 is the cell itself at distance 0 and whose other K - 1 columns are smx_knn's, float64, one thread
+ * per row.  target = log2(K).  rho = the first strictly positive distance of the row in column order, 0 without one.  lo = 0, hi = inf,
+ * mid = 1; at most 64 rounds: psum = the sum over columns 1 .. K - 1, in order, of exp(-(d - rho) / mid) where d - rho > 0 and of 1
+ * otherwise; stop when |psum - target| < 1e-5; if psum > target then hi = mid, mid = (lo + hi) / 2, else lo = mid and mid = 2 mid while
+ * hi is infinite, (lo + hi) / 2 after.  sigma = max(mid, floor), floor = 1e-3 x the mean of the row (column 0 included, summed in column
+ * order) when rho > 0, else 1e-3 x the mean of the whole table (ONE fixed-order float64 reduction: 256 strided partials, the lanes of a
+ * wave by halving, then the four waves).  weight [n_cells][K]: 0 where idx names the cell itself, 1 where d - rho <= 0 or sigma == 0,
+ * else exp(-(d - rho) / sigma).  rho, sigma [n_cells].  2 <= K <= 257, 1 <= n_cells < 2^31, every idx in 0 .. n_cells - 1, every dist
+ * finite and >= 0: anything else is SMX_ERR_INVALID before any device work.  Device memory: 28 K n_cells bytes. */
+int smx_knn(const float* Z, int64_t n_cells, int32_t D, int32_t k, int32_t* idx, double* dist);
+int smx_knn_umap(const int32_t* idx, const double* dist, int64_t n_cells, int32_t K, double* rho, double* sigma, double* weight);
 
 /* ---- padding audit (test instrument; never on the path of a step) ----------- */
 /* The layout's invariant, read back from the device: every feature axis is padded to 32 and every tensor to 64 floats, and what lies

@@ -19,6 +19,7 @@
 // No atomics, no workgroup waits on another, every loop is bounded by the block's rows, ld or a row's entries.  Both passes are
 // memory-bound and small beside the PCIe copy of the block, which is why the view costs a pass of its own instead of being fused.
 #include "smx_model.h"
+#include "smx_prep.h"   // PrepInput, PrepStage and the per-gene sums: shared with smx_pca.hip
 
 #include <algorithm>
 #include <cmath>
@@ -26,7 +27,6 @@
 
 namespace smx {
 
-#define SMX_PREP_SLICE 64                        // rows per partial sum of the per-gene pass
 #define SMX_PREP_TILE_BYTES ((size_t)64 << 20)   // the library's choice of block: about this much tile
 #define SMX_PREP_MAX_TILE_BYTES ((size_t)1 << 30)
 #define SMX_PREP_MAX_GENES (1 << 20)
@@ -119,9 +119,6 @@ __global__ __launch_bounds__(256) void prep_cell_kernel(const float* __restrict_
   }
 }
 
-struct GenePart { double* sum; double* sq; int32_t* pos; int32_t* above; };   // each [slices][ld]
-struct GeneAcc { double* sum; double* sq; int64_t* pos; int64_t* above; };    // each [ld]
-
 // slice blockIdx.y of the tile's rows, genes 4 t .. 4 t + 3 of thread t: the rows in order
 __global__ __launch_bounds__(64) void prep_gene_part_kernel(const float* __restrict__ tile, long n, long ld, long row0,
                                                             const float* __restrict__ thresh, GenePart p) {
@@ -162,13 +159,6 @@ __global__ __launch_bounds__(256) void prep_gene_combine_kernel(GenePart p, int 
   a.sum[g] = sum; a.sq[g] = sq; a.pos[g] = pos; a.above[g] = above;
 }
 
-namespace {
-
-// the host matrix of both entry points and how it is cut into blocks of rows
-struct PrepInput {
-  const float* x; CsrRows csr; long N; int G; long ld; long block; size_t max_nnz;
-};
-
 // every refusal of the shared arguments, before any device work
 int prep_check_input(const char* who, const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_cells,
                      int32_t n_genes, int32_t block_rows, int32_t func, const float* row_div, PrepInput* in) {
@@ -200,10 +190,6 @@ int prep_check_input(const char* who, const float* x, const int64_t* indptr, con
   return SMX_OK;
 }
 
-struct PrepStage {   // the device tile and, for CSR input, the staging of one block
-  float* tile = nullptr; int64_t* ptr = nullptr; int32_t* cols = nullptr; float* vals = nullptr;
-};
-
 int prep_stage_alloc(DeviceScratch& buf, const PrepInput& in, PrepStage* st, bool want_tile) {
   if (want_tile) SMX_CHECK(buf.get(&st->tile, (size_t)in.block * in.ld));
   if (!in.x) {
@@ -231,6 +217,27 @@ int prep_load_block(const PrepInput& in, const PrepStage& st, long r0, long nb) 
   return launch_csr_rows(nullptr, st.ptr, st.cols, st.vals, nb, in.G, in.ld, st.tile, nullptr);
 }
 
+int prep_gene_acc_alloc(DeviceScratch& buf, const PrepInput& in, GenePart* part, GeneAcc* acc) {   // (dmalloc zeroes: the accumulators start at 0)
+  const size_t ld = (size_t)in.ld, max_slices = (size_t)(in.block / SMX_PREP_SLICE);
+  SMX_CHECK(buf.get(&part->sum, max_slices * ld)); SMX_CHECK(buf.get(&part->sq, max_slices * ld));
+  SMX_CHECK(buf.get(&part->pos, max_slices * ld)); SMX_CHECK(buf.get(&part->above, max_slices * ld));
+  SMX_CHECK(buf.get(&acc->sum, ld)); SMX_CHECK(buf.get(&acc->sq, ld));
+  SMX_CHECK(buf.get(&acc->pos, ld)); SMX_CHECK(buf.get(&acc->above, ld));
+  return SMX_OK;
+}
+
+int prep_launch_gene_sums(const float* tile, long nb, long ld, long r0, const float* thresh, const GenePart& part, const GeneAcc& acc) {
+  const int slices = (int)((nb + SMX_PREP_SLICE - 1) / SMX_PREP_SLICE);
+  hipLaunchKernelGGL(prep_gene_part_kernel, dim3((unsigned)((ld / 4 + 63) / 64), (unsigned)slices), dim3(64), 0, nullptr, tile, nb, ld, r0,
+                     thresh, part);
+  SMX_HIP(hipGetLastError());
+  hipLaunchKernelGGL(prep_gene_combine_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, nullptr, part, slices, ld, acc);
+  SMX_HIP(hipGetLastError());
+  return SMX_OK;
+}
+
+namespace {
+
 int prep_launch_view(float* tile, long nb, int G, long ld, long r0, const PrepView& w) {
   const long quads = nb * (ld >> 2);
   const unsigned grid = (unsigned)std::min<long>(2048, (quads + 255) / 256);
@@ -257,7 +264,7 @@ int smx_prep_stats(const float* x, const int64_t* indptr, const int32_t* cols, c
   if (row_thresh)
     for (long i = 0; i < in.N; ++i) SMX_REQUIRE(row_thresh[i] == row_thresh[i], "prep_stats: a NaN row threshold");
   const long N = in.N, ld = in.ld;
-  const int G = in.G, max_slices = (int)(in.block / SMX_PREP_SLICE);
+  const int G = in.G;
   DeviceScratch buf;
   PrepStage st;
   SMX_CHECK(prep_stage_alloc(buf, in, &st, true));
@@ -267,25 +274,17 @@ int smx_prep_stats(const float* x, const int64_t* indptr, const int32_t* cols, c
   SMX_CHECK(buf.put(&dMask, col_mask, (size_t)G));
   double* dTotal; int32_t* dNg;
   SMX_CHECK(buf.get(&dTotal, (size_t)N)); SMX_CHECK(buf.get(&dNg, (size_t)N));
-  GenePart part; GeneAcc acc;   // (dmalloc zeroes: the accumulators start at 0)
-  SMX_CHECK(buf.get(&part.sum, (size_t)max_slices * ld)); SMX_CHECK(buf.get(&part.sq, (size_t)max_slices * ld));
-  SMX_CHECK(buf.get(&part.pos, (size_t)max_slices * ld)); SMX_CHECK(buf.get(&part.above, (size_t)max_slices * ld));
-  SMX_CHECK(buf.get(&acc.sum, (size_t)ld)); SMX_CHECK(buf.get(&acc.sq, (size_t)ld));
-  SMX_CHECK(buf.get(&acc.pos, (size_t)ld)); SMX_CHECK(buf.get(&acc.above, (size_t)ld));
+  GenePart part; GeneAcc acc;
+  SMX_CHECK(prep_gene_acc_alloc(buf, in, &part, &acc));
   const PrepView w{func, dDiv, nullptr, nullptr, 0, 0.f};
   const bool identity = func == 0 && !row_div;
   for (long r0 = 0; r0 < N; r0 += in.block) {
     const long nb = std::min(in.block, N - r0);
-    const int slices = (int)((nb + SMX_PREP_SLICE - 1) / SMX_PREP_SLICE);
     SMX_CHECK(prep_load_block(in, st, r0, nb));
     if (!identity) SMX_CHECK(prep_launch_view(st.tile, nb, G, ld, r0, w));
     hipLaunchKernelGGL(prep_cell_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, nullptr, st.tile, nb, G, ld, r0, dMask, dTotal, dNg);
     SMX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(prep_gene_part_kernel, dim3((unsigned)((ld / 4 + 63) / 64), (unsigned)slices), dim3(64), 0, nullptr, st.tile, nb, ld,
-                       r0, dThr, part);
-    SMX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(prep_gene_combine_kernel, dim3((unsigned)((ld + 255) / 256)), dim3(256), 0, nullptr, part, slices, ld, acc);
-    SMX_HIP(hipGetLastError());
+    SMX_CHECK(prep_launch_gene_sums(st.tile, nb, ld, r0, dThr, part, acc));
     SMX_HIP(hipDeviceSynchronize());   // the next block's copy overwrites the tile
   }
   SMX_HIP(hipMemcpy(cell_total, dTotal, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));

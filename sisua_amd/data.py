@@ -310,6 +310,8 @@ class SingleCellOMIC:
     self.name = name
     self._data, self._vars = {}, {}
     self._embeddings = {}   # omic -> (pbe, prob, bin) of probabilistic_embedding; a subset or a copy starts without
+    self._pca = {}          # omic -> (PCA, scores) of dimension_reduce; likewise
+    self._neighbors = {}    # omic -> (connectivities, distances, params) of neighbors; likewise
     self.add_omic(omic, X, var_names)
 
   def add_omic(self, omic: str, X, var_names=None):
@@ -318,7 +320,7 @@ class SingleCellOMIC:
     if self._data and X.shape[0] != self.n_obs:
       raise ValueError(f"Number of cell mismatch {self.n_obs} and {X.shape[0]}")
     self._data[str(omic)] = X
-    self._embeddings.pop(str(omic), None)
+    self._drop_derived(str(omic))
     self._vars[str(omic)] = np.array([f"{omic}{i}" for i in range(X.shape[1])]) if var_names is None else np.asarray(var_names)
     return self
 
@@ -389,10 +391,14 @@ class SingleCellOMIC:
   def _first(self, omic=None) -> str:
     return str(omic) if omic is not None else self.omics[0]
 
+  def _drop_derived(self, key: str):
+    for cache in (self._embeddings, self._pca, self._neighbors):
+      cache.pop(key, None)
+
   def _replace(self, key: str, X, var_names=None):
-    """A new matrix for an omic already held (same cells); its embedding, if any, no longer describes it"""
+    """A new matrix for an omic already held (same cells); its embedding, PCA and neighbour graph, if any, no longer describe it"""
     self._data[key] = as_csr(X) if is_sparse(X) else np.ascontiguousarray(X, dtype=np.float32)
-    self._embeddings.pop(key, None)
+    self._drop_derived(key)
     if var_names is not None:
       self._vars[key] = np.asarray(var_names)
 
@@ -495,6 +501,62 @@ class SingleCellOMIC:
 
   def get_x_bins(self, omic=None):
     return self.probabilistic_embedding(omic=omic)[2]
+
+  # ---- analysis (sisua_amd/neighbors.py; the matrix work runs on the device: smx_pca.hip, smx_knn.hip) ----
+  def dimension_reduce(self, omic=None, n_components=100, algo="pca", random_state=1):
+    """The reference's dimension_reduce(algo='pca'): the scores [cells, min(n_components, dim)] float32 of an EXACT PCA of the omic (the
+    reference's IncrementalPCA over batches of 4096 rows is exact for one batch and approximates it for several).  The model
+    (`sisua_amd.PCA`) and its scores are kept on the object: a later call that asks for no more components returns a column slice, one
+    that asks for more refits.  PCA is deterministic: random_state is accepted and unused.  'tsne' and 'umap' are not built."""
+    from sisua_amd import neighbors as nb
+    algo = str(algo).lower().strip()
+    if algo in ("tsne", "umap"):
+      raise NotImplementedError(f"dimension_reduce(algo={algo!r}) is not built: only algo='pca' is")
+    if algo != "pca":
+      raise ValueError(f"Only support algorithm: 'pca', 'tsne', 'umap'; but given: '{algo}'")
+    key = self._first(omic)
+    X = self.numpy(key)
+    if int(n_components) < 1:
+      raise ValueError(f"n_components must be >= 1, got {n_components}")
+    C = min(int(n_components), X.shape[1])
+    if key not in self._pca or self._pca[key][1].shape[1] < C:
+      self._pca[key] = nb.pca(X, C)
+    scores = self._pca[key][1]
+    return scores if scores.shape[1] == C else scores[:, :C]
+
+  def get_pca(self, omic=None):
+    """The fitted `sisua_amd.PCA` of an omic (what `dimension_reduce` left), or None"""
+    return self._pca.get(self._first(omic), (None, None))[0]
+
+  def neighbors(self, omic=None, n_neighbors=12, n_pcs=100, knn=True, method="umap", metric="euclidean", random_state=1):
+    """The reference's neighbors (scanpy.pp.neighbors there): each cell's n_neighbors - 1 nearest other cells, EXACT over all pairs, with
+    UMAP's connectivities -> (connectivities, distances, {'params': ...}), the graphs scipy.sparse CSR float32 [cells, cells].  As in the
+    reference an omic wider than 100 columns is first reduced with dimension_reduce(algo='pca'); the first min(n_pcs, width) columns of
+    the representation are used.  The first result of an omic is kept on the object and returned from then on.  Only knn=True,
+    method='umap' and metric='euclidean' are built; 2 <= n_neighbors <= min(257, cells)."""
+    from sisua_amd import neighbors as nb
+    if not knn:
+      raise NotImplementedError("neighbors(knn=False) is not built: only the hard k-nearest-neighbour graph (knn=True) is")
+    if str(method).lower() != "umap":
+      raise NotImplementedError(f"neighbors(method={method!r}) is not built: only method='umap' is")
+    if not isinstance(metric, str) or metric.lower() != "euclidean":
+      raise NotImplementedError(f"neighbors(metric={metric!r}) is not built: only metric='euclidean' is")
+    K = nb.check_n_neighbors(n_neighbors, self.n_obs)
+    if int(n_pcs) < 1:
+      raise ValueError(f"n_pcs must be >= 1, got {n_pcs}")
+    key = self._first(omic)
+    if key in self._neighbors:
+      return self._neighbors[key]
+    if self.get_dim(key) > 100:
+      rep, use_rep = self.dimension_reduce(key, algo="pca", random_state=random_state), key + "_pca"
+    else:
+      rep, use_rep = self.numpy(key), key
+      rep = rep.toarray() if is_sparse(rep) else rep
+    width = min(int(n_pcs), rep.shape[1])
+    conn, dist = nb.neighbors(np.ascontiguousarray(rep[:, :width]), K)
+    params = {"params": {"n_neighbors": K, "method": "umap", "metric": "euclidean", "n_pcs": width, "use_rep": use_rep}}
+    self._neighbors[key] = (conn, dist, params)
+    return self._neighbors[key]
 
   def get_rv(self, omic, distribution=None):
     from sisua_amd.config import RVmeta

@@ -1229,6 +1229,80 @@ def k_prep_apply(x, func=None, row_div=None, mean=None, std=None, max_value=None
   return out
 
 
+PCA_MAX_GENES = 8192        # smx_pca_cov / smx_pca_project: the covariance takes 8 G^2 bytes
+PCA_MAX_COMPONENTS = 128    # smx_pca_project, per call
+KNN_MAX_D, KNN_MAX_K = 128, 256
+
+
+def _pca_input(x, block_rows):
+  """The matrix of smx_pca_cov / smx_pca_project, checked here so that a refusal never asks for the device"""
+  dense, csr, N, G, _, _ = _prep_input(x, None, None, block_rows)
+  if G > PCA_MAX_GENES:
+    raise ValueError(f"PCA of {G} columns is not built: the covariance route takes at most {PCA_MAX_GENES} "
+                     "(8 G^2 bytes); select genes first, e.g. with filter_highly_variable_genes")
+  return dense, csr, N, G
+
+
+def k_pca_cov(x, block_rows: int = 0):
+  """smx_pca_cov: a dense or scipy.sparse matrix [N >= 2, G <= 8192] -> (mean [G], cov [G, G]) float64, the two-pass covariance with
+  n - 1 in the denominator"""
+  dense, csr, N, G = _pca_input(x, block_rows)
+  if N < 2:
+    raise ValueError(f"a covariance needs at least 2 cells, got {N}")
+  lib = _hip.require_gpu()
+  mean, cov = np.empty((G,), np.float64), np.empty((G, G), np.float64)
+  ptrs = (None, None, None) if csr is None else _csr_ptrs(csr)
+  check(lib.smx_pca_cov(_fp(dense), *ptrs, N, G, int(block_rows), _dp(mean), _dp(cov)))
+  return mean, cov
+
+
+def k_pca_project(x, mean, components, block_rows: int = 0):
+  """smx_pca_project: (x - mean) . components^T for mean [G] and components [C <= 128, G] float64 -> [N, C] float32"""
+  dense, csr, N, G = _pca_input(x, block_rows)
+  mu, w = np.ascontiguousarray(mean, dtype=np.float64), np.ascontiguousarray(components, dtype=np.float64)
+  if mu.shape != (G,) or w.ndim != 2 or w.shape[1] != G or not 1 <= w.shape[0] <= PCA_MAX_COMPONENTS:
+    raise ValueError(f"mean must be [{G}] and components [1 .. {PCA_MAX_COMPONENTS}, {G}], got {mu.shape} and {w.shape}")
+  if not (np.isfinite(mu).all() and np.isfinite(w).all()):
+    raise ValueError("mean and components must be finite")
+  lib = _hip.require_gpu()
+  out = np.empty((N, w.shape[0]), np.float32)
+  ptrs = (None, None, None) if csr is None else _csr_ptrs(csr)
+  check(lib.smx_pca_project(_fp(dense), *ptrs, N, G, int(block_rows), _dp(mu), _dp(w), w.shape[0], _fp(out)))
+  return out
+
+
+def k_knn(Z, k: int):
+  """smx_knn: cells Z [N, D] float32 -> (idx [N, k] int32, dist [N, k] float64), the k other cells nearest to each by (d2, index)"""
+  z = _f32(Z)
+  k = int(k)
+  if z.ndim != 2 or not 1 <= z.shape[1] <= KNN_MAX_D:
+    raise ValueError(f"Z must be [cells, 1 <= D <= {KNN_MAX_D}], got {z.shape}")
+  if not 1 <= k <= KNN_MAX_K or k >= z.shape[0]:
+    raise ValueError(f"k must be in 1 .. {KNN_MAX_K} and below the number of cells ({z.shape[0]}), got {k}")
+  if not np.isfinite(z).all():
+    raise ValueError("Z holds an entry that is not finite")
+  lib = _hip.require_gpu()
+  idx, dist = np.empty((z.shape[0], k), np.int32), np.empty((z.shape[0], k), np.float64)
+  check(lib.smx_knn(_fp(z), z.shape[0], z.shape[1], k, _ip(idx), _dp(dist)))
+  return idx, dist
+
+
+def k_knn_umap(idx, dist):
+  """smx_knn_umap: a neighbour table idx / dist [N, K] whose column 0 is the cell itself -> (rho [N], sigma [N], weight [N, K]) float64"""
+  ix, d = np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(dist, dtype=np.float64)
+  if ix.ndim != 2 or d.shape != ix.shape or not 2 <= ix.shape[1] <= KNN_MAX_K + 1 or ix.shape[0] < 1:
+    raise ValueError(f"idx and dist must both be [cells, 2 <= K <= {KNN_MAX_K + 1}], got {ix.shape} and {d.shape}")
+  N, K = ix.shape
+  if ix.min() < 0 or ix.max() >= N:
+    raise ValueError("idx holds an index outside 0 .. cells - 1")
+  if not (np.isfinite(d).all() and (d >= 0).all()):
+    raise ValueError("dist must be finite and non-negative")
+  lib = _hip.require_gpu()
+  rho, sigma, weight = np.empty((N,), np.float64), np.empty((N,), np.float64), np.empty((N, K), np.float64)
+  check(lib.smx_knn_umap(_ip(ix), _dp(d), N, K, _dp(rho), _dp(sigma), _dp(weight)))
+  return rho, sigma, weight
+
+
 def k_noise(seed, stream, step, cell_ids, width, p=0.0, sample=0):
   lib = _hip.require_gpu()
   ids = np.ascontiguousarray(cell_ids, dtype=np.int64)

@@ -90,7 +90,19 @@ static void model_free_entries() {
     NO_DEVICE(smx_prep_stats(nullptr, indptr, cols, vals, N, G, 0, 0, nullptr, nullptr, nullptr, dout.data(), iout.data(), dout.data() + 64, dout.data() + 128,
                              lout.data(), nullptr));
     NO_DEVICE(smx_prep_apply(x.data(), nullptr, nullptr, nullptr, N, G, 0, 1, ones.data(), nullptr, nullptr, 0, 0.f, out.data(), nullptr));
-    NO_DEVICE(smx_prep_apply(nullptr, indptr, cols, vals, N, G, 0, 1, nullptr, nullptr, nullptr, 0, 0.f, nullptr, out.data())); }
+    NO_DEVICE(smx_prep_apply(nullptr, indptr, cols, vals, N, G, 0, 1, nullptr, nullptr, nullptr, 0, 0.f, nullptr, out.data()));
+    // -- exact PCA on the same two forms: mean [G], two components [2][G]
+    const std::vector<double> mean(G, 0.5), comp((size_t)2 * G, 0.25);
+    NO_DEVICE(smx_pca_cov(x.data(), nullptr, nullptr, nullptr, N, G, 0, dout.data(), dout.data() + 64));
+    NO_DEVICE(smx_pca_cov(nullptr, indptr, cols, vals, N, G, 0, dout.data(), dout.data() + 64));
+    NO_DEVICE(smx_pca_project(x.data(), nullptr, nullptr, nullptr, N, G, 0, mean.data(), comp.data(), 2, out.data()));
+    NO_DEVICE(smx_pca_project(nullptr, indptr, cols, vals, N, G, 0, mean.data(), comp.data(), 2, out.data())); }
+  // -- neighbours: the N cells in G dimensions, 2 others each; then the table with the cell itself in front
+  { std::vector<int32_t> tidx((size_t)N * 3);
+    std::vector<double> tdist((size_t)N * 3);
+    for (int i = 0; i < N; ++i) for (int c = 0; c < 3; ++c) { tidx[(size_t)i * 3 + c] = (i + c) % N; tdist[(size_t)i * 3 + c] = 0.5 * c; }
+    NO_DEVICE(smx_knn(x.data(), N, G, 2, iout.data(), dout.data()));
+    NO_DEVICE(smx_knn_umap(tidx.data(), tdist.data(), N, 3, dout.data(), dout.data() + 64, dout.data() + 128)); }
 }
 
 int main() {
