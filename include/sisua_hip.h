@@ -304,6 +304,8 @@ int smx_set_train_draws(smx_model* m, int32_t n_draws);
  *   SMX_OPT_RMSPROP   rho (0.9), momentum (0), epsilon (1e-7)
  *   SMX_OPT_ADAGRAD   initial_accumulator_value (0.1), epsilon (1e-7)
  *   SMX_OPT_ADAMAX    beta_1 (0.9), beta_2 (0.999), epsilon (1e-7)
+ * Every epsilon must be a normal float32 (>= 2^-126), smx_config.adam_eps included: at 0 (or a denormal, whose reciprocal is inf) the update
+ * makes 0 * inf = NaN of every tensor's zero padding.  SMX_ERR_INVALID otherwise, before any device work.
  * Every rule keeps smx_config.lr, the per-tensor clipnorm in front of the update and the tied-variable norm of SCALE.  The rule
  * starts FRESH, as a new Keras optimiser object does: its slots (smx_get_tensor which = 2 / 3) are set to 0 -- Adagrad's
  * accumulator to initial_accumulator_value -- and t0 = the model's step count now (smx_set_step first to record another); the
@@ -639,6 +641,24 @@ int smx_k_adam(int32_t n_tensors, const int32_t* sizes, float* params, const flo
  * arrays are always given; a slot the rule does not use is left as it is).  step = the rule's 1-based count t. */
 int smx_k_opt(int32_t rule, const float* hp, int32_t n_hp, int32_t n_tensors, const int32_t* sizes, float* params, const float* grads,
               float* m, float* v, int32_t step, float lr, float clipnorm, float* norms);
+/* Clip + update by ANY of the launches that carry the optimiser's chunk body (smx_adam.h), over caller-given tensors laid out as smx_k_opt
+ * lays them out (every tensor padded to 64 floats, 4096-float chunks).  hp[n_hp], sizes, params, grads, m, v as smx_k_opt's, none updated in place.
+ * ip (int32): rule, n_tensors, carrier (smx_opt_carrier), wgs (sweep, sharded chain: persistent workgroups), world (sharded chain), use_sq,
+ *   step (the 1-based count of optimiser steps, this one included), t0 (the step index at which the rule's state began: the rule's count is
+ *   t = step - t0, and 1 while step <= t0), tied_t0, tied_t1 (tensor indices or -1), n_slots (length of sq_slots).
+ * fp (float): lr, clipnorm (0: off), grad_scale, tied_inv.
+ * use_sq = 0: the norms come from per-chunk partial sums made by the carrier's own norm pass.  use_sq != 0 (not the sharded chain): tensor i
+ *   takes its sum of squares from sq_slots[sq_first[i] .. + sq_count[i]) if sq_count[i] > 0, else from a sweep of its own gradient.
+ * SMX_CARRIER_SHARD runs the data-parallel chain of flag opt_shard on one device: the buffer cut into `world` equal slices at 64-float
+ *   boundaries (through chunks where they fall); the slice-wise sums of squares once per rank into that rank's own partial array; the arrays
+ *   summed in float32 in rank order (0 + rank 0 + rank 1 + ...); the norms; the update once per rank on its slice.
+ * Out: params_out, m_out, v_out: the WHOLE padded buffers (sum of the padded sizes); norms [n_tensors] and *lr_t (the device's step size, read
+ *   back from the step state) may be NULL.  Every device buffer lies between two guard bands of 0xFF bytes: *guards_ok = 1 if no band word
+ *   changed.  A slot the rule does not use is 0xFF bytes before the launch instead of the caller's values: *unused_ok = 1 if it came back so. */
+typedef enum { SMX_CARRIER_LAUNCH = 0, SMX_CARRIER_SWEEP = 1, SMX_CARRIER_SHARD = 2, SMX_CARRIER_BODY512 = 3 } smx_opt_carrier;
+int smx_k_opt_carrier(const int32_t* ip, const float* fp, const float* hp, int32_t n_hp, const int32_t* sizes, const float* params,
+                      const float* grads, const float* m, const float* v, const int32_t* sq_first, const int32_t* sq_count, const float* sq_slots,
+                      float* params_out, float* m_out, float* v_out, float* norms, float* lr_t, int32_t* guards_ok, int32_t* unused_ok);
 /* C[M,N] = op(A) * op(B) in fp32 on the MFMA path; transA: A given as [K,M];
  * transB: B given as [N,K]; split_k >= 1 (slabs summed on return).  tile_cfg 0: the library's choice of LDS tile; 100: the
  * direct bf16 x 3 form for deep contractions (transA = 0, K >= 512); 101 / 102: the minibatch-contracted weight-gradient forms

@@ -158,6 +158,7 @@ SIGNATURES = {
     "smx_k_adam": (C.c_int, [C.c_int32, _IP, _FP, _FP, _FP, _FP, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
                              C.c_float, _FP]),
     "smx_k_opt": (C.c_int, [C.c_int32, _FP, C.c_int32, C.c_int32, _IP, _FP, _FP, _FP, _FP, C.c_int32, C.c_float, C.c_float, _FP]),
+    "smx_k_opt_carrier": (C.c_int, [_IP, _FP, _FP, C.c_int32, _IP, _FP, _FP, _FP, _FP, _IP, _IP, _FP, _FP, _FP, _FP, _FP, _FP, _IP, _IP]),
     "smx_set_flag": (C.c_int, [_VP, C.c_char_p, C.c_int]),
     "smx_set_tuning": (C.c_int, [C.c_char_p, C.c_double]),
     "smx_clear_tuning": (C.c_int, [C.c_char_p]),

@@ -1,6 +1,7 @@
 // smx_kapi.hip -- kernel-level entry points (parity tests of single kernels): smx_k_count_llk, smx_k_adam, smx_k_gemm, smx_k_head_fused, smx_k_noise,
-// smx_k_bn_fwd / smx_k_bn_bwd.
+// smx_k_bn_fwd / smx_k_bn_bwd, smx_k_opt_carrier (clip + update by every launch that carries the optimiser's chunk body).
 #include "smx_model.h"
+#include "smx_adam.h"
 #include <hiprand/hiprand_kernel.h>
 
 namespace smx {
@@ -600,6 +601,146 @@ int smx_k_bn_bwd(const int32_t* ip, const float* fp, const float* dout, const fl
   if ((rc = oDpre.download(dpre, (size_t)B * Hp)) || (rc = oDg.download(dgamma, (size_t)nw * Hp)) || (rc = oDb.download(dbeta, (size_t)nw * Hp)) ||
       (rc = oDbias.download(dbias, Hp)))
     return rc;
+  return SMX_OK;
+}
+
+}  // extern "C"
+
+// ---- the optimiser's carriers by themselves (smx_adam.h / smx_adam.hip: every launch that runs adam_tensor_clip + opt_apply4) --------------
+namespace smx {
+// test only: the 512-thread chunk body (a rider of the 512-thread launches in a training step; it cannot be launched alone there)
+__global__ __launch_bounds__(512) void k_opt_body512_kernel(AdamArgs a) { adam_chunk_body<512, true>(a, (int)blockIdx.x); }
+}  // namespace smx
+
+namespace {
+// which of the slots 2 / 3 the rule `form` reads and writes (OptSlots<F> by value)
+void opt_slots_used(int form, bool* um, bool* uv) {
+  switch (form) {
+#define SMX_SLOTS_CASE(F) case F: *um = OptSlots<F>::m; *uv = OptSlots<F>::v; break
+    SMX_SLOTS_CASE(OPT_SGD); SMX_SLOTS_CASE(OPT_SGD_MOM); SMX_SLOTS_CASE(OPT_SGD_NESTEROV); SMX_SLOTS_CASE(OPT_RMSPROP); SMX_SLOTS_CASE(OPT_RMSPROP_MOM);
+    SMX_SLOTS_CASE(OPT_ADAGRAD); SMX_SLOTS_CASE(OPT_ADAMAX);
+#undef SMX_SLOTS_CASE
+    default: *um = OptSlots<OPT_ADAM>::m; *uv = OptSlots<OPT_ADAM>::v; break;
+  }
+}
+}  // namespace
+
+extern "C" {
+
+// ip: rule, n_tensors, carrier, wgs, world, use_sq, step, t0, tied_t0, tied_t1, n_slots; fp: lr, clipnorm, grad_scale, tied_inv
+int smx_k_opt_carrier(const int32_t* ip, const float* fp, const float* hp, int32_t n_hp, const int32_t* sizes, const float* params,
+                      const float* grads, const float* m, const float* v, const int32_t* sq_first, const int32_t* sq_count, const float* sq_slots,
+                      float* params_out, float* m_out, float* v_out, float* norms, float* lr_t, int32_t* guards_ok, int32_t* unused_ok) {
+  SMX_REQUIRE(ip && fp && sizes && params && grads && m && v && params_out && m_out && v_out && guards_ok && unused_ok, "k_opt_carrier: bad arguments");
+  const int rule = ip[0], n_tensors = ip[1], carrier = ip[2], wgs = ip[3], world = ip[4], use_sq = ip[5], step = ip[6], t0 = ip[7], tied_t0 = ip[8],
+            tied_t1 = ip[9], n_slots = ip[10];
+  static const float adam_hp[3] = {0.9f, 0.999f, 1e-7f};
+  float res[4];
+  SMX_CHECK(opt_resolve(rule, hp, n_hp, adam_hp, res));
+  SMX_REQUIRE(n_tensors > 0 && n_tensors <= SMX_MAX_TENSORS && step >= 1 && t0 >= 0, "k_opt_carrier: bad tensor count, step or t0");
+  SMX_REQUIRE(carrier >= SMX_CARRIER_LAUNCH && carrier <= SMX_CARRIER_BODY512, "k_opt_carrier: unknown carrier");
+  SMX_REQUIRE(carrier != SMX_CARRIER_SWEEP || wgs > 0, "k_opt_carrier: the sweep needs wgs > 0");
+  SMX_REQUIRE(carrier != SMX_CARRIER_SHARD || (wgs > 0 && world >= 1 && world <= 64 && !use_sq), "k_opt_carrier: the sharded chain needs wgs > 0, a world of 1 .. 64 and the partials' norm");
+  SMX_REQUIRE(tied_t0 < n_tensors && tied_t1 < n_tensors && std::isfinite(fp[0]) && std::isfinite(fp[1]) && std::isfinite(fp[2]) && std::isfinite(fp[3]),
+              "k_opt_carrier: bad tied tensors or scalars");
+  SMX_REQUIRE(!use_sq || (sq_first && sq_count && n_slots >= 0 && (n_slots == 0 || sq_slots)), "k_opt_carrier: use_sq needs the slot tables");
+  // the model's own layout, as k_opt_launch: every tensor padded to a multiple of 64 floats, 4096-float optimiser chunks
+  std::vector<size_t> off((size_t)n_tensors), pad((size_t)n_tensors);
+  std::vector<OptChunk> chunks;
+  size_t total = 0;
+  const int CH = 4096;
+  for (int t = 0; t < n_tensors; ++t) {
+    SMX_REQUIRE(sizes[t] > 0, "k_opt_carrier: empty tensor");
+    if (use_sq) SMX_REQUIRE(sq_count[t] >= 0 && (sq_count[t] == 0 || (sq_first[t] >= 0 && (long)sq_first[t] + sq_count[t] <= (long)n_slots)), "k_opt_carrier: a tensor's slots lie outside sq_slots");
+    off[t] = total; pad[t] = ((size_t)sizes[t] + 63) / 64 * 64;
+    const int first = (int)chunks.size(), n = (int)((pad[t] + CH - 1) / CH);
+    for (int i = 0; i < n; ++i) {
+      OptChunk c;
+      memset(&c, 0, sizeof(c));
+      c.tensor = t; c.offset = (int)(off[t] + (size_t)i * CH);
+      c.count = (int)((size_t)(i + 1) * CH <= pad[t] ? CH : pad[t] - (size_t)i * CH);
+      c.first_chunk = first; c.n_chunks = n; c.tensor_count = (int32_t)pad[t];
+      chunks.push_back(c);
+    }
+    total += pad[t];
+  }
+  const int n_chunks = (int)chunks.size();
+  AdamArgs a;
+  opt_scalars(rule, res, a);
+  a.t0 = (uint32_t)t0;
+  bool um = true, uv = true;
+  opt_slots_used(a.form, &um, &uv);
+  StepState st3[3];
+  memset(st3, 0, sizeof(st3));
+  st3[2].next = (uint32_t)(step - 1);   // optimiser steps completed so far: the rule's count is t = step - t0 (1 while step <= t0)
+  const float2 sch = make_float2(0.f, fp[0]);
+  DeviceScratch buf;
+  KbnOut oP, oG, oM, oV, oPart, oNorm;
+  std::vector<KbnOut> rank_part((size_t)(carrier == SMX_CARRIER_SHARD ? world : 0));
+  OptChunk* dCh; StepState* dSt; float2* dSch; float* dSlots;
+  int rc;
+  if ((rc = oP.alloc(buf, total)) || (rc = oG.alloc(buf, total)) || (rc = oM.alloc(buf, total)) || (rc = oV.alloc(buf, total)) || (rc = oPart.alloc(buf, (size_t)n_chunks)) ||
+      (rc = oNorm.alloc(buf, (size_t)n_tensors)) || (rc = buf.put(&dCh, chunks.data(), chunks.size())) || (rc = buf.put(&dSt, st3, (size_t)3)) ||
+      (rc = buf.put(&dSch, &sch, (size_t)1)) || (rc = buf.put(&dSlots, use_sq && n_slots > 0 ? sq_slots : nullptr, (size_t)std::max(n_slots, 1))))
+    return rc;
+  for (auto& r : rank_part) if ((rc = r.alloc(buf, (size_t)n_chunks))) return rc;
+  // a buffer the rule uses: zero padding around the caller's elements; one it does not use stays 0xFF bytes throughout
+  auto fill = [&](KbnOut& o, const float* src) -> int {
+    SMX_HIP(hipMemset(o.p(), 0, total * 4));
+    size_t lo = 0;
+    for (int t = 0; t < n_tensors; ++t) {
+      SMX_HIP(hipMemcpy(o.p() + off[t], src + lo, (size_t)sizes[t] * 4, hipMemcpyHostToDevice));
+      lo += (size_t)sizes[t];
+    }
+    return SMX_OK;
+  };
+  SMX_CHECK(fill(oP, params)); SMX_CHECK(fill(oG, grads));
+  if (um) SMX_CHECK(fill(oM, m));
+  if (uv) SMX_CHECK(fill(oV, v));
+  SMX_CHECK(launch_step_begin(nullptr, dSt + 2, dSt, nullptr, nullptr, 0, 0, 0u, dSch, a.b1, a.b2, a.form, a.t0));
+  a.params = oP.p(); a.grads = oG.p(); a.m = oM.p(); a.v = oV.p(); a.chunks = dCh; a.n_chunks = n_chunks; a.n_launch = n_chunks; a.gap_from = n_chunks; a.gap_len = 0;
+  a.partial = oPart.p(); a.tensor_norm = oNorm.p(); a.state = dSt; a.sched = dSch;
+  a.clipnorm = fp[1]; a.grad_scale = fp[2]; a.tied_t0 = tied_t0 >= 0 ? tied_t0 : -1; a.tied_t1 = tied_t1 >= 0 ? tied_t1 : -1; a.tied_inv = fp[3];
+  a.use_sq = use_sq ? 1 : 0; a.sq_slots = dSlots;
+  for (int t = 0; t < SMX_MAX_TENSORS; ++t) { a.sq_first[t] = use_sq && t < n_tensors ? sq_first[t] : 0; a.sq_count[t] = use_sq && t < n_tensors ? sq_count[t] : 0; }
+  switch (carrier) {
+    case SMX_CARRIER_LAUNCH: SMX_CHECK(launch_adam(nullptr, a)); break;
+    case SMX_CARRIER_SWEEP:
+      if (!use_sq) SMX_CHECK(launch_grad_sqsum_range(nullptr, a, 0, n_chunks));
+      SMX_CHECK(launch_adam_sweep(nullptr, a, 0, n_chunks, wgs));
+      break;
+    case SMX_CARRIER_BODY512:
+      if (!use_sq) SMX_CHECK(launch_grad_sqsum_range(nullptr, a, 0, n_chunks));
+      hipLaunchKernelGGL(smx::k_opt_body512_kernel, dim3((unsigned)n_chunks), dim3(512), 0, nullptr, a);
+      SMX_HIP(hipGetLastError());
+      break;
+    default: {   // the sharded chain of smx_backward.hip on one device: `world` equal slices cut at a 64-float boundary, through chunks where they fall
+      const size_t slice = ((total + world - 1) / world + 63) / 64 * 64;
+      auto rank_args = [&](int r) { AdamArgs x = a; x.shard_lo = (long)std::min((size_t)r * slice, total); x.shard_hi = (long)std::min(((size_t)r + 1) * slice, total); return x; };
+      for (int r = 0; r < world; ++r) { AdamArgs x = rank_args(r); x.partial = rank_part[r].p(); SMX_CHECK(launch_grad_sqsum_shard(nullptr, x, 0, n_chunks)); }
+      SMX_HIP(hipDeviceSynchronize());
+      // the all-reduce of the partials: float32 sums in rank order, 0 + rank 0 + rank 1 + ...
+      std::vector<float> sum((size_t)n_chunks, 0.f), one((size_t)n_chunks);
+      for (int r = 0; r < world; ++r) {
+        if ((rc = rank_part[r].download(one.data(), (size_t)n_chunks))) return rc;
+        for (int c = 0; c < n_chunks; ++c) sum[c] += one[c];
+      }
+      if ((rc = oPart.upload(sum.data(), (size_t)n_chunks))) return rc;
+      SMX_CHECK(launch_head_norms(nullptr, a, 0, n_chunks));
+      for (int r = 0; r < world; ++r) { const AdamArgs x = rank_args(r); if (x.shard_hi > x.shard_lo) SMX_CHECK(launch_adam_shard(nullptr, x, 0, n_chunks, wgs)); }
+    }
+  }
+  SMX_HIP(hipDeviceSynchronize());
+  bool ok = true;
+  for (const KbnOut* o : {&oP, &oG, &oM, &oV, &oPart, &oNorm}) if ((rc = o->intact(&ok))) return rc;
+  for (const auto& r : rank_part) if ((rc = r.intact(&ok))) return rc;
+  *guards_ok = ok ? 1 : 0;
+  if ((rc = oP.download(params_out, total)) || (rc = oM.download(m_out, total)) || (rc = oV.download(v_out, total)) || (rc = oNorm.download(norms, (size_t)n_tensors))) return rc;
+  bool same = true;
+  for (const float* q : {um ? nullptr : m_out, uv ? nullptr : v_out})
+    if (q) for (size_t i = 0; i < total; ++i) { uint32_t w; memcpy(&w, q + i, 4); if (w != 0xFFFFFFFFu) same = false; }
+  *unused_ok = same ? 1 : 0;
+  if (lr_t) { StepState h; SMX_HIP(hipMemcpy(&h, dSt, sizeof(h), hipMemcpyDeviceToHost)); *lr_t = h.lr_t; }
   return SMX_OK;
 }
 

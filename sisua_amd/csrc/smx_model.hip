@@ -1,4 +1,5 @@
 #include <atomic>
+#include <cfloat>
 // smx_model.hip -- model state: construction / destruction, tensors, BatchNorm statistics, noise injection, flags, timing.
 #include "smx_model.h"
 
@@ -223,10 +224,14 @@ int opt_resolve(int rule, const float* hp, int n_hp, const float* adam_hp, float
   for (int i = 0; i < 4; ++i) out[i] = i < n_hp ? hp[i] : (rule == 0 && i < 3 ? adam_hp[i] : defaults[rule][i]);
   for (int i = 0; i < counts[rule]; ++i) SMX_REQUIRE(std::isfinite(out[i]), "smx_set_optimizer: a hyper-parameter is not finite");
   switch (rule) {
-    case 0: case 4: SMX_REQUIRE(out[0] >= 0.f && out[0] < 1.f && out[1] >= 0.f && out[1] < 1.f && out[2] >= 0.f, "smx_set_optimizer: beta_1, beta_2 in [0, 1), epsilon >= 0"); break;
+    // epsilon a NORMAL float32 (>= 2^-126): a tensor's padding has g = m = v = 0, and at epsilon 0 every rule with a quotient makes
+    // -(lr 0) * (1 / (sqrt(0) + 0)) = 0 * inf = NaN of it -- padding the products read as operands and smx_model.h requires to be zero
+    // (DESIGN.md 4w).  A denormal epsilon does the same: its reciprocal is beyond float32, and v_rcp_f32 reads a denormal operand as 0.
+    // Adagrad's accumulator starts at its initial value in the logical elements only, so its padding needs this whatever that value is.
+    case 0: case 4: SMX_REQUIRE(out[0] >= 0.f && out[0] < 1.f && out[1] >= 0.f && out[1] < 1.f && out[2] >= FLT_MIN, "smx_set_optimizer: beta_1, beta_2 in [0, 1), epsilon a normal float32 (>= 2^-126)"); break;
     case 1: SMX_REQUIRE(out[0] >= 0.f && (out[1] == 0.f || out[1] == 1.f), "smx_set_optimizer: sgd momentum >= 0, nesterov 0 or 1"); break;
-    case 2: SMX_REQUIRE(out[0] >= 0.f && out[0] <= 1.f && out[1] >= 0.f && out[2] >= 0.f, "smx_set_optimizer: rmsprop rho in [0, 1], momentum >= 0, epsilon >= 0"); break;
-    case 3: SMX_REQUIRE(out[0] >= 0.f && out[1] >= 0.f, "smx_set_optimizer: adagrad initial_accumulator_value >= 0, epsilon >= 0"); break;
+    case 2: SMX_REQUIRE(out[0] >= 0.f && out[0] <= 1.f && out[1] >= 0.f && out[2] >= FLT_MIN, "smx_set_optimizer: rmsprop rho in [0, 1], momentum >= 0, epsilon a normal float32 (>= 2^-126)"); break;
+    case 3: SMX_REQUIRE(out[0] >= 0.f && out[1] >= FLT_MIN, "smx_set_optimizer: adagrad initial_accumulator_value >= 0, epsilon a normal float32 (>= 2^-126)"); break;
   }
   return SMX_OK;
 }
@@ -380,6 +385,7 @@ int smx_model_create(const smx_config* cfg, smx_model** out) {
   }
   SMX_REQUIRE(cfg->dropout_enc >= 0 && cfg->dropout_enc < 1 && cfg->dropout_dec >= 0 && cfg->dropout_dec < 1 &&
                   cfg->input_dropout >= 0 && cfg->input_dropout < 1, "dropout rates must be in [0,1)");
+  SMX_REQUIRE(cfg->adam_eps >= FLT_MIN, "adam_eps must be a normal float32 (>= 2^-126; below, the update turns every tensor's zero padding into NaN: opt_resolve)");
   int dev = 0;
   SMX_HIP(hipGetDevice(&dev));
   smx_model* m = new smx_model();

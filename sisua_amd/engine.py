@@ -902,6 +902,47 @@ def k_opt(rule: str, params, grads, m, v, step: int, lr=1e-3, clipnorm=100.0, **
   return un(P), un(M), un(V), norms
 
 
+OPT_CARRIERS = {"launch": 0, "sweep": 1, "shard": 2, "body512": 3}   # smx_opt_carrier
+
+
+def k_opt_carrier(rule: str, params, grads, m, v, step: int, carrier="launch", wgs=0, world=0, use_sq=False, sq=None, lr=1e-3, clipnorm=100.0,
+                  grad_scale=1.0, t0=0, tied=(), tied_inv=1.0, hp_raw=None, **hp):
+  """Clip + update by one of the launches that carry the optimiser's chunk body (smx_k_opt_carrier): the optimiser launch, the background
+  sweep with `wgs` workgroups, the sharded chain of `world` simulated ranks, the 512-thread body.  Lists of arrays as k_opt's.  `use_sq`: the
+  norms without the norm pass -- `sq[i]` holds tensor i's sum-of-squares slots, or None for the sweep of its own gradient (what lies behind a
+  tensor's slots in the device array is NaN).  `tied`: up to two tensor indices whose sum of squares is multiplied by `tied_inv`.  `hp_raw`: a
+  hyper-parameter vector handed to the library as it is, in place of **hp.  Returns dict(params, m, v: the whole padded flat buffers;
+  offsets, sizes, pads: where tensor i lies in them; norms; lr_t: the device's step size; guards_ok; unused_ok)."""
+  lib = _hip.require_gpu()
+  if hp_raw is None:
+    name, full = optimizers.canonical(rule, **hp)
+    hv = optimizers.hp_vector(name, full)
+  else:
+    name, hv = rule.lower(), np.ascontiguousarray(hp_raw, dtype=np.float32)
+  sizes = np.array([int(np.size(p)) for p in params], dtype=np.int32)
+  pads = (sizes.astype(np.int64) + 63) // 64 * 64
+  offsets = np.concatenate([[0], np.cumsum(pads)[:-1]])
+  total = int(pads.sum())
+  cat = lambda xs: np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).ravel() for x in xs]))
+  P, G, M, V = cat(params), cat(grads), cat(m), cat(v)
+  first, count, slots = np.zeros(len(sizes), np.int32), np.zeros(len(sizes), np.int32), [np.full(8, np.nan, np.float32)]
+  for i, s in enumerate(sq or []):
+    if s is not None:
+      first[i], count[i] = sum(len(x) for x in slots), np.size(s)
+      slots += [np.asarray(s, np.float32).ravel(), np.full(8, np.nan, np.float32)]
+  slots = np.ascontiguousarray(np.concatenate(slots))
+  tied = list(tied) + [-1, -1]
+  ip = np.array([optimizers.RULES[name][0], len(sizes), OPT_CARRIERS[carrier], wgs, world, int(bool(use_sq)), step, t0, tied[0], tied[1], len(slots)], np.int32)
+  fp = np.array([lr, clipnorm, grad_scale, tied_inv], np.float32)
+  o = dict(params=np.empty(total, np.float32), m=np.empty(total, np.float32), v=np.empty(total, np.float32), norms=np.empty(len(sizes), np.float32),
+           offsets=offsets, sizes=sizes.astype(np.int64), pads=pads)
+  lr_t, ok, same = C.c_float(0), C.c_int32(0), C.c_int32(0)
+  check(lib.smx_k_opt_carrier(_ip(ip), _fp(fp), _fp(hv), len(hv), _ip(sizes), _fp(P), _fp(G), _fp(M), _fp(V), _ip(first), _ip(count), _fp(slots),
+                              _fp(o["params"]), _fp(o["m"]), _fp(o["v"]), _fp(o["norms"]), C.byref(lr_t), C.byref(ok), C.byref(same)))
+  o.update(lr_t=np.float32(lr_t.value), guards_ok=bool(ok.value), unused_ok=bool(same.value))
+  return o
+
+
 def k_gemm(A, B, trans_a=False, trans_b=False, split_k=1, tile=0):
   lib = _hip.require_gpu()
   A, B = _f32(A), _f32(B)

@@ -50,6 +50,10 @@ def canonical(name: str, **hp) -> Tuple[str, Dict[str, float]]:
   for k, v in out.items():
     if not isinstance(v, bool) and not np.isfinite(v):
       raise ValueError(f"optimizer {key!r}: {k}={v!r} is not finite")
+  # (at epsilon 0, or a denormal float32 whose reciprocal is inf, the device's update makes 0 * inf = NaN of every tensor's zero padding,
+  # whatever Adagrad's accumulator starts at: its initial value goes into the logical elements only)
+  if "epsilon" in out and not np.float32(out["epsilon"]) >= np.finfo(np.float32).tiny:
+    raise ValueError(f"optimizer {key!r}: epsilon={out['epsilon']!r} must be a normal float32 (>= 2^-126)")
   return key, out
 
 

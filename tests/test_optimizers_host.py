@@ -109,6 +109,15 @@ BAD = [
     ({"class_name": "SGD", "config": {"rho": 0.9}}, "no hyper-parameter 'rho'"),
     ({"class_name": "Adamax", "config": {"momentum": 0.9}}, "no hyper-parameter 'momentum'"),
     ({"config": {}}, "class_name"),
+    # epsilon 0 (or a denormal float32, whose reciprocal is inf) makes 0 * inf = NaN of every tensor's zero padding
+    ({"class_name": "Adam", "config": {"epsilon": 0.0}}, "epsilon=0.0 must be a normal float32"),
+    ({"class_name": "RMSprop", "config": {"epsilon": 0.0}}, "epsilon=0.0 must be a normal float32"),
+    ({"class_name": "RMSprop", "config": {"momentum": 0.9, "epsilon": 0.0}}, "epsilon=0.0 must be a normal float32"),
+    ({"class_name": "Adagrad", "config": {"epsilon": 0.0}}, "epsilon=0.0 must be a normal float32"),
+    ({"class_name": "Adagrad", "config": {"initial_accumulator_value": 0.0, "epsilon": 0.0}}, "epsilon=0.0 must be a normal float32"),
+    ({"class_name": "Adamax", "config": {"epsilon": 0.0}}, "epsilon=0.0 must be a normal float32"),
+    ({"class_name": "Adam", "config": {"epsilon": 1e-39}}, "must be a normal float32"),
+    ({"class_name": "Adamax", "config": {"epsilon": -1e-7}}, "must be a normal float32"),
 ]
 
 
@@ -157,14 +166,14 @@ def test_a_built_rule_reaches_the_engine(monkeypatch, optimizer):
 def test_entry_points_are_declared_bound_and_exported():
   hdr = open(os.path.join(ROOT, "include", "sisua_hip.h")).read()
   assert re.search(r"int\s+smx_set_optimizer\s*\(\s*smx_model\s*\*\s*m\s*,\s*int32_t\s+rule\s*,\s*const\s+float\s*\*\s*hp\s*,\s*int32_t\s+n_hp\s*\)", hdr)
-  for name in ("smx_set_optimizer", "smx_get_optimizer", "smx_k_opt"):
+  for name in ("smx_set_optimizer", "smx_get_optimizer", "smx_k_opt", "smx_k_opt_carrier"):
     assert name in _hip.SIGNATURES
   lib = os.path.join(ROOT, "sisua_amd", "libsisua_hip.so")
   if not os.path.exists(lib):
     pytest.skip("library not built")
   import subprocess
   syms = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True).stdout
-  for name in ("smx_set_optimizer", "smx_get_optimizer", "smx_k_opt"):
+  for name in ("smx_set_optimizer", "smx_get_optimizer", "smx_k_opt", "smx_k_opt_carrier"):
     assert re.search(rf"\bT {name}\b", syms), name
 
 

@@ -43,7 +43,37 @@ static void model_free_entries() {
   { const int32_t sizes[2] = {5, 70};
     std::vector<float> p(75, 0.5f), g(75, 0.1f), m(75, 0.f), v(75, 0.f);
     NO_DEVICE(smx_k_adam(2, sizes, p.data(), g.data(), m.data(), v.data(), 1, 1e-3f, 0.9f, 0.999f, 1e-7f, 1.f, out.data()));
-    NO_DEVICE(smx_k_opt(SMX_OPT_ADAM, nullptr, 0, 2, sizes, p.data(), g.data(), m.data(), v.data(), 1, 1e-3f, 1.f, out.data())); }
+    NO_DEVICE(smx_k_opt(SMX_OPT_ADAM, nullptr, 0, 2, sizes, p.data(), g.data(), m.data(), v.data(), 1, 1e-3f, 1.f, out.data()));
+    // the carriers' entry: valid arguments reach the staging on every carrier; every refusal comes before any device work
+    const float fp[4] = {1e-3f, 5.f, 1.f, 1.f}, slots[4] = {1.f, 2.f, 3.f, 4.f};
+    const int32_t sq_first[2] = {0, 0}, sq_count[2] = {0, 4};
+    float lr_t = 0.f; int32_t guards = 0, unused = 0;
+    auto carrier = [&](std::vector<int32_t> ip, const float* hp, int n_hp, const int32_t* sz, const int32_t* first, const int32_t* count) {
+      return smx_k_opt_carrier(ip.data(), fp, hp, n_hp, sz, p.data(), g.data(), m.data(), v.data(), first, count, slots, out.data(), out.data() + 256,
+                               out.data() + 512, out.data() + 768, &lr_t, &guards, &unused);
+    };
+    // ip: rule, n_tensors, carrier, wgs, world, use_sq, step, t0, tied_t0, tied_t1, n_slots
+    NO_DEVICE(carrier({SMX_OPT_ADAM, 2, SMX_CARRIER_LAUNCH, 0, 0, 0, 1, 0, -1, -1, 0}, nullptr, 0, sizes, nullptr, nullptr));
+    NO_DEVICE(carrier({SMX_OPT_RMSPROP, 2, SMX_CARRIER_SWEEP, 2, 0, 1, 4, 3, 0, 1, 4}, nullptr, 0, sizes, sq_first, sq_count));
+    NO_DEVICE(carrier({SMX_OPT_ADAMAX, 2, SMX_CARRIER_SHARD, 2, 3, 0, 1, 0, -1, -1, 0}, nullptr, 0, sizes, nullptr, nullptr));
+    NO_DEVICE(carrier({SMX_OPT_SGD, 2, SMX_CARRIER_BODY512, 0, 0, 0, 1, 0, -1, -1, 0}, nullptr, 0, sizes, nullptr, nullptr));
+    const float eps0[3] = {0.9f, 0.999f, 0.f}, eps_denormal[3] = {0.9f, 0.999f, 1e-39f}, ada0[2] = {0.f, 0.f}, rms0[3] = {0.9f, 0.9f, 0.f};
+    const int32_t empty[2] = {5, 0}, beyond[2] = {0, 5};
+    EXPECT(carrier({SMX_OPT_ADAM, 2, SMX_CARRIER_LAUNCH, 0, 0, 0, 1, 0, -1, -1, 0}, eps0, 3, sizes, nullptr, nullptr) == SMX_ERR_INVALID);
+    EXPECT(carrier({SMX_OPT_ADAMAX, 2, SMX_CARRIER_LAUNCH, 0, 0, 0, 1, 0, -1, -1, 0}, eps_denormal, 3, sizes, nullptr, nullptr) == SMX_ERR_INVALID);
+    EXPECT(carrier({SMX_OPT_ADAGRAD, 2, SMX_CARRIER_LAUNCH, 0, 0, 0, 1, 0, -1, -1, 0}, ada0, 2, sizes, nullptr, nullptr) == SMX_ERR_INVALID);
+    EXPECT(carrier({SMX_OPT_RMSPROP, 2, SMX_CARRIER_LAUNCH, 0, 0, 0, 1, 0, -1, -1, 0}, rms0, 3, sizes, nullptr, nullptr) == SMX_ERR_INVALID);
+    EXPECT(smx_k_opt(SMX_OPT_ADAM, eps0, 3, 2, sizes, p.data(), g.data(), m.data(), v.data(), 1, 1e-3f, 1.f, out.data()) == SMX_ERR_INVALID);
+    EXPECT(carrier({SMX_OPT_ADAM, 2, 4, 0, 0, 0, 1, 0, -1, -1, 0}, nullptr, 0, sizes, nullptr, nullptr) == SMX_ERR_INVALID);                    // no such carrier
+    EXPECT(carrier({SMX_OPT_ADAM, 2, SMX_CARRIER_SWEEP, 0, 0, 0, 1, 0, -1, -1, 0}, nullptr, 0, sizes, nullptr, nullptr) == SMX_ERR_INVALID);    // sweep without workgroups
+    EXPECT(carrier({SMX_OPT_ADAM, 2, SMX_CARRIER_SHARD, 2, 0, 0, 1, 0, -1, -1, 0}, nullptr, 0, sizes, nullptr, nullptr) == SMX_ERR_INVALID);    // world 0
+    EXPECT(carrier({SMX_OPT_ADAM, 2, SMX_CARRIER_SHARD, 2, 2, 1, 1, 0, -1, -1, 4}, nullptr, 0, sizes, sq_first, sq_count) == SMX_ERR_INVALID);  // sharded chain with use_sq
+    EXPECT(carrier({SMX_OPT_ADAM, 2, SMX_CARRIER_LAUNCH, 0, 0, 1, 1, 0, -1, -1, 4}, nullptr, 0, sizes, sq_first, beyond) == SMX_ERR_INVALID);   // slots past n_slots
+    EXPECT(carrier({SMX_OPT_ADAM, 2, SMX_CARRIER_LAUNCH, 0, 0, 1, 1, 0, -1, -1, 4}, nullptr, 0, sizes, nullptr, nullptr) == SMX_ERR_INVALID);   // use_sq without tables
+    EXPECT(carrier({SMX_OPT_ADAM, 2, SMX_CARRIER_LAUNCH, 0, 0, 0, 0, 0, -1, -1, 0}, nullptr, 0, sizes, nullptr, nullptr) == SMX_ERR_INVALID);   // step 0
+    EXPECT(carrier({SMX_OPT_ADAM, 2, SMX_CARRIER_LAUNCH, 0, 0, 0, 1, 0, 2, -1, 0}, nullptr, 0, sizes, nullptr, nullptr) == SMX_ERR_INVALID);    // tied tensor 2 of 2
+    EXPECT(carrier({SMX_OPT_ADAM, 2, SMX_CARRIER_LAUNCH, 0, 0, 0, 1, 0, -1, -1, 0}, nullptr, 0, empty, nullptr, nullptr) == SMX_ERR_INVALID);   // an empty tensor
+    EXPECT(carrier({SMX_OPT_ADAM, 4096, SMX_CARRIER_LAUNCH, 0, 0, 0, 1, 0, -1, -1, 0}, nullptr, 0, sizes, nullptr, nullptr) == SMX_ERR_INVALID); }
   NO_DEVICE(smx_k_gemm(0, 0, ones.data(), ones.data(), 8, 8, 8, 1, 0, out.data()));
   { const int B = 2, Gh = 4096;   // (the fused head's smallest panel)
     std::vector<float> xh((size_t)B * Gh, 1.f), d((size_t)B * 128, 0.1f), W((size_t)128 * 2 * Gh, 0.01f), bias((size_t)2 * Gh, 0.f), dW(W.size()), db(bias.size());

@@ -1,6 +1,7 @@
 // ulp_probe.hip -- accuracy of the single-instruction transcendental forms the kernels use (smx_device.h) against
 // float64 on the device: max and mean relative error of v_log_f32 (as ln), v_exp_f32, v_rcp_f32, v_sqrt_f32 and of rsqrtf over the
-// argument ranges that occur in the step.   hipcc --offload-arch=gfx950 -O3 tools/ulp_probe.hip -o tools/ulp_probe
+// argument ranges that occur in the step; of powf(b, t) on the ladder of the optimiser's step size (adam_lr_t: smx_adam.hip); and what
+// v_sqrt_f32 returns at denormal arguments.   hipcc --offload-arch=gfx950 -O3 tools/ulp_probe.hip -o tools/ulp_probe
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -10,7 +11,7 @@ __global__ void probe(int kind, float lo, float hi, int n, double* max_rel, doub
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   // log-uniform sweep of [lo, hi]
-  const float x = lo * powf(hi / lo, (float)i / (float)(n - 1));
+  const float x = (float)((double)lo * pow((double)hi / (double)lo, (double)i / (double)(n - 1)));   // (hi / lo is beyond float32 for the widest ranges)
   float got; double ref;
   switch (kind) {
     case 0: got = __builtin_amdgcn_logf(x) * 0.6931471805599453f; ref = log((double)x); break;
@@ -27,7 +28,43 @@ __global__ void probe(int kind, float lo, float hi, int n, double* max_rel, doub
   atomicAdd(sum_rel, rel);
 }
 
+// powf(b, (float)t) as adam_lr_t forms it against pow in float64: relative error in units of u = 2^-24 (0 where b^t is below float32)
+__global__ void powf_probe(const float* b, const unsigned* t, int nb, int nt, double* rel_u) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nb * nt) return;
+  const float got = powf(b[i / nt], (float)t[i % nt]);
+  const double ref = pow((double)b[i / nt], (double)(float)t[i % nt]);
+  rel_u[i] = ref >= 1.1754943508222875e-38 ? fabs((double)got - ref) / ref * 16777216.0 : (got == 0.f || ref > 0.0 ? 0.0 : 1e300);
+}
+__global__ void sqrt_denormal_probe(const float* x, float* y, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) y[i] = __builtin_amdgcn_sqrtf(x[i]);
+}
+
 int main() {
+  {
+    const float b[4] = {0.5f, 0.9f, 0.999f, 0.99999f};
+    const unsigned t[7] = {1u, 2u, 3u, 10u, 1000u, 100000u, 16777217u};
+    float* db; unsigned* dt; double* dr; double h[28];
+    hipMalloc(&db, sizeof(b)); hipMalloc(&dt, sizeof(t)); hipMalloc(&dr, sizeof(h));
+    hipMemcpy(db, b, sizeof(b), hipMemcpyHostToDevice); hipMemcpy(dt, t, sizeof(t), hipMemcpyHostToDevice);
+    hipLaunchKernelGGL(powf_probe, dim3(1), dim3(64), 0, 0, db, dt, 4, 7, dr);
+    hipMemcpy(h, dr, sizeof(h), hipMemcpyDeviceToHost);
+    double worst = 0.0;
+    for (int i = 0; i < 4; ++i) {
+      printf("powf b^t   b = %-8g rel err / u at t = 1, 2, 3, 10, 1000, 1e5, 2^24 + 1:", b[i]);
+      for (int j = 0; j < 7; ++j) { printf(" %.3f", h[i * 7 + j]); if (h[i * 7 + j] > worst) worst = h[i * 7 + j]; }
+      printf("\n");
+    }
+    printf("%-58s max rel %.3f u\n", "powf b^t   over the ladder above", worst);
+    const float x[6] = {1e-45f, 1e-42f, 1e-40f, 9.99e-39f, 1.17549421e-38f, 1.17549435e-38f};
+    float *dx, *dy, y[6];
+    hipMalloc(&dx, sizeof(x)); hipMalloc(&dy, sizeof(y));
+    hipMemcpy(dx, x, sizeof(x), hipMemcpyHostToDevice);
+    hipLaunchKernelGGL(sqrt_denormal_probe, dim3(1), dim3(64), 0, 0, dx, dy, 6);
+    hipMemcpy(y, dy, sizeof(y), hipMemcpyDeviceToHost);
+    for (int i = 0; i < 6; ++i) printf("v_sqrt x   x = %.8e -> %.8e  (sqrt %.8e)\n", x[i], y[i], sqrt((double)x[i]));
+  }
   double* d; hipMalloc(&d, 3 * sizeof(double));
   struct { int kind; float lo, hi; const char* name; } cases[] = {
       {0, 1e-30f, 1e30f, "ln x      = v_log * ln2, x in [1e-30, 1e30]"}, {0, 0.5f, 2.0f, "ln x      near 1, x in [0.5, 2]"},
