@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 12
+#define SMX_ABI_VERSION 13
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -888,6 +888,60 @@ int smx_pca_project(const float* x, const int64_t* indptr, const int32_t* cols, 
  * finite and >= 0: anything else is SMX_ERR_INVALID before any device work.  Device memory: 28 K n_cells bytes. */
 int smx_knn(const float* Z, int64_t n_cells, int32_t D, int32_t k, int32_t* idx, double* dist);
 int smx_knn_umap(const int32_t* idx, const double* dist, int64_t n_cells, int32_t K, double* rho, double* sigma, double* weight);
+
+/* ---- t-SNE embeddings (smx_tsne.hip; model-free: smx_init only) ----------- */
+/* scikit-learn's TSNE(method='barnes_hut') objective with the tree replaced by the EXACT sum over all pairs (its angle -> 0 limit), all in
+ * float64.  The joint P between smx_tsne_affinities and the other two entries is host work: A = the CSR of cond_p on the kNN support,
+ * P = (A + A^T) / sum(A + A^T), columns sorted, explicit zeros kept out (sisua_amd/neighbors.py).
+ *
+ * smx_tsne_affinities: scikit-learn's _binary_search_perplexity on smx_knn's table idx / dist [n_cells][k] (the k OTHER cells; k =
+ * min(n_cells - 1, floor(3 perplexity + 1)) is scikit-learn's support and the caller's business), one thread per row.  d2_j = dist_j x
+ * dist_j.  beta = 1, beta_min = -inf, beta_max = +inf; at most 100 rounds: p_j = exp(-d2_j x beta), sum = the p_j added in column order,
+ * a sum equal to 0 replaced by (double)1e-8f; p_j = p_j / sum; H = log(sum) + beta x (the d2_j x p_j added in column order); stop when
+ * |H - log((double)(float)perplexity)| <= (double)1e-5f (both constants are float32 values in scikit-learn); if H is above the target
+ * then beta_min = beta and beta = 2 beta while beta_max is infinite, (beta + beta_max) / 2 after; else beta_max = beta and beta = beta / 2
+ * while beta_min is infinite, (beta + beta_min) / 2 after.  No row-minimum shift, as in scikit-learn: a row whose every exp underflows
+ * keeps p = 0.  No operation is fused.  cond_p [n_cells][k] = the p_j of the last round run, beta [n_cells] = the beta they were formed
+ * with.  1 <= k <= 256, 4 <= n_cells, k < n_cells < 2^31, 1 <= perplexity < n_cells, every idx in 0 .. n_cells - 1, every dist finite and
+ * >= 0: anything else is SMX_ERR_INVALID before any device work.  Device memory: 16 k n_cells bytes.
+ *
+ * The problem of the other two entries: P as CSR (indptr [n_cells + 1], cols, p) with indptr[0] = 0, rows that do not shrink, columns in
+ * 0 .. n_cells - 1 and strictly increasing within a row, every p finite and > 0; an embedding Y [n_cells][n_components] float64, finite;
+ * 1 <= n_components <= 3; 4 <= n_cells < 2^31.  Anything else is SMX_ERR_INVALID before any device work.
+ *   w_ij = 1 / (1 + |y_i - y_j|^2), the IEEE division, |.|^2 = d_0 d_0 then fma(d_c, d_c, .) for c = 1, 2;   Z = sum_{i != j} w_ij
+ *   grad_i = 4 [ sum_{j in row i of P} (exaggeration p_ij) w_ij (y_i - y_j)  -  (1 / Z) sum_{j != i} w_ij^2 (y_i - y_j) ]
+ *   KL = sum_{p_ij > 0} p_ij log((p_ij Z) / w_ij), always with the un-exaggerated p
+ * The repulsive pass is an n-body sweep: the j range is cut into max(1, min(32, 1024 / ceil(n_cells / 256))) slices (a function of
+ * n_cells alone; developer knob "tsne_slices"); a thread adds w and w^2 (y_i - y_j) over its slice in j order with fma, and the slices
+ * are added in slice order.  Z, the KL and the squared gradient norm are each ONE fixed-order reduction over the cells (1024 strided
+ * partials, the lanes of a wave by halving, the sixteen waves by halving).  The attractive sum of a row is taken by sixteen lanes: lane l
+ * adds the row's entries l, l + 16, ... (in column order) with fma, and the lanes are added by halving (l + 8, l + 4, l + 2, l + 1).
+ * No float atomics: two calls give the same bits.  Another slice count adds the repulsive sums in another order: the neighbour table
+ * and P do not depend on any slice knob, the gradient and the embedding may differ in their last bits and, the descent being chaotic,
+ * an embedding after many iterations may differ visibly.
+ *
+ * smx_tsne_gradient: one evaluation -> grad [n_cells][n_components], *kl, *Z.  exaggeration finite and > 0.
+ *
+ * smx_tsne_fit: scikit-learn's descent from Y0, with the kernels of smx_tsne_gradient; Y, update, gains and P stay on the device and
+ * only two doubles per reporting iteration come back.  The elementwise part is _gradient_descent's, every operation rounded: inc =
+ * update x grad < 0; gains + 0.2 where inc, else gains x 0.8; gains >= 0.01; grad = grad x gains; update = momentum x update -
+ * learning_rate x grad; Y = Y + update.  No recentring.  Schedule: iterations 0 .. min(250, max_iter) - 1 with exaggeration =
+ * early_exaggeration and momentum 0.5, the rest with exaggeration 1 and momentum 0.8; as scikit-learn's two calls do, each phase
+ * starts from update = 0 and gains = 1.  Iteration i reports when (i + 1) % 50 == 0 or it is the last of its phase: kl_trace[i] = KL at
+ * the embedding the iteration started from (every other entry of kl_trace [max_iter] is NaN).  Where (i + 1) % 50 == 0 the phase ends
+ * early when the norm of the gains-scaled gradient is <= min_grad_norm, and the second phase also when the KL has not improved for more
+ * than n_iter_without_progress iterations; as in scikit-learn an early end of the first phase starts the second at the next iteration.
+ * *n_iter = the number of iterations run.  Y [n_cells][n_components]; update_out and gains_out (each may be NULL) the descent's other
+ * state, same shape.  max_iter >= 1, early_exaggeration and learning_rate finite and > 0, min_grad_norm >= 0,
+ * n_iter_without_progress >= 0.  The cost of an iteration is n_cells^2 pair evaluations (about 30 float64 operations with the division):
+ * exact by design, no Barnes-Hut or FFT approximation is built.  Device memory: 8 x slices x (1 + n_components) x n_cells bytes of
+ * partial sums, 32 n_components n_cells (Y twice, update, gains), P, 16 n_cells. */
+int smx_tsne_affinities(const int32_t* idx, const double* dist, int64_t n_cells, int32_t k, double perplexity, double* cond_p, double* beta);
+int smx_tsne_gradient(const int64_t* indptr, const int32_t* cols, const double* p, int64_t n_cells, int32_t n_components, const double* Y,
+                      double exaggeration, double* grad, double* kl, double* Z);
+int smx_tsne_fit(const int64_t* indptr, const int32_t* cols, const double* p, int64_t n_cells, int32_t n_components, const double* Y0,
+                 int32_t max_iter, double early_exaggeration, double learning_rate, double min_grad_norm, int32_t n_iter_without_progress,
+                 double* Y, double* kl_trace, int32_t* n_iter, double* update_out, double* gains_out);
 
 /* ---- padding audit (test instrument; never on the path of a step) ----------- */
 /* The layout's invariant, read back from the device: every feature axis is padded to 32 and every tensor to 64 floats, and what lies

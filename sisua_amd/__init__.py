@@ -11,6 +11,6 @@ from sisua_amd.distributions import correlations_from_sums, protein_operands  # 
 from sisua_amd.label_threshold import ProbabilisticEmbedding  # noqa: F401
 from sisua_amd.metrics import correlation_list, marker_correlations  # noqa: F401
 from sisua_amd.mixture import GaussianMixture  # noqa: F401
-from sisua_amd.neighbors import PCA  # noqa: F401
+from sisua_amd.neighbors import PCA, TSNE  # noqa: F401
 
 __version__ = "0.1.0"

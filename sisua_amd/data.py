@@ -312,6 +312,7 @@ class SingleCellOMIC:
     self._embeddings = {}   # omic -> (pbe, prob, bin) of probabilistic_embedding; a subset or a copy starts without
     self._pca = {}          # omic -> (PCA, scores) of dimension_reduce; likewise
     self._neighbors = {}    # omic -> (connectivities, distances, params) of neighbors; likewise
+    self._tsne = {}         # (omic, n_components) -> the embedding of dimension_reduce(algo='tsne'); likewise
     self.add_omic(omic, X, var_names)
 
   def add_omic(self, omic: str, X, var_names=None):
@@ -394,6 +395,8 @@ class SingleCellOMIC:
   def _drop_derived(self, key: str):
     for cache in (self._embeddings, self._pca, self._neighbors):
       cache.pop(key, None)
+    for kc in [kc for kc in self._tsne if kc[0] == key]:
+      del self._tsne[kc]
 
   def _replace(self, key: str, X, var_names=None):
     """A new matrix for an omic already held (same cells); its embedding, PCA and neighbour graph, if any, no longer describe it"""
@@ -507,11 +510,27 @@ class SingleCellOMIC:
     """The reference's dimension_reduce(algo='pca'): the scores [cells, min(n_components, dim)] float32 of an EXACT PCA of the omic (the
     reference's IncrementalPCA over batches of 4096 rows is exact for one batch and approximates it for several).  The model
     (`sisua_amd.PCA`) and its scores are kept on the object: a later call that asks for no more components returns a column slice, one
-    that asks for more refits.  PCA is deterministic: random_state is accepted and unused.  'tsne' and 'umap' are not built."""
+    that asks for more refits.  PCA is deterministic: random_state is accepted and unused.
+    algo='tsne': the t-SNE embedding [cells, n_components] float32 of the omic (`sisua_amd.TSNE` with its defaults: scikit-learn's
+    objective with the exact repulsive sum).  n_components must be 1, 2 or 3 -- the signature's default of 100 belongs to 'pca' and is
+    refused.  As in `neighbors`, an omic wider than 100 columns goes through dimension_reduce(algo='pca') first (its 100 scores; a kept
+    PCA is reused).  The start is the PCA init, so random_state is unused.  The result is kept per omic and n_components.
+    'umap' is not built."""
     from sisua_amd import neighbors as nb
     algo = str(algo).lower().strip()
-    if algo in ("tsne", "umap"):
-      raise NotImplementedError(f"dimension_reduce(algo={algo!r}) is not built: only algo='pca' is")
+    if algo == "umap":
+      raise NotImplementedError(f"dimension_reduce(algo={algo!r}) is not built: only algo='pca' and algo='tsne' are")
+    if algo == "tsne":
+      C = nb.check_tsne_components(n_components)   # (before anything else is looked at)
+      key = self._first(omic)
+      if (key, C) not in self._tsne:
+        if self.get_dim(key) > 100:
+          rep = self.dimension_reduce(key, algo="pca", random_state=random_state)
+        else:
+          rep = self.numpy(key)
+          rep = rep.toarray() if is_sparse(rep) else rep
+        self._tsne[(key, C)] = nb.tsne(rep, n_components=C, random_state=random_state)
+      return self._tsne[(key, C)]
     if algo != "pca":
       raise ValueError(f"Only support algorithm: 'pca', 'tsne', 'umap'; but given: '{algo}'")
     key = self._first(omic)

@@ -7,12 +7,14 @@ runs in libsisua_hip.so (smx_pca.hip, smx_knn.hip; definitions in include/sisua_
   knn(Z, k)                    -> (idx [N, k] int32, dist [N, k] float64): the k OTHER cells nearest to each
   umap_connectivities(idx, dist) -> (connectivities, distances): the table's column 0 is the cell itself
   neighbors(Z, n_neighbors)    -> (connectivities, distances) of a latent space, e.g. model.encode's
+  tsne_affinities(Z, perplexity) -> P, t-SNE's joint affinities, CSR float64
+  tsne(Z, n_components, ...) / TSNE -> Y [N, C <= 3] float32: scikit-learn's t-SNE with the EXACT repulsive sum (smx_tsne.hip, section 4x)
 
 PCA here is EXACT: the eigen-decomposition of the two-pass float64 covariance.  The reference's IncrementalPCA over batches of 4096 rows
 is exact PCA for one batch and an approximation of it for several.
 
-Not built: t-SNE and UMAP embeddings, method='gauss', knn=False, metrics other than Euclidean, approximate neighbour search, PCA of
-matrices wider than 8192 columns."""
+Not built: the UMAP embedding, Barnes-Hut / FFT approximations of t-SNE, t-SNE into more than 3 dimensions or with a perplexity above 85,
+method='gauss', knn=False, metrics other than Euclidean, approximate neighbour search, PCA of matrices wider than 8192 columns."""
 from __future__ import annotations
 
 import numpy as np
@@ -21,6 +23,8 @@ import scipy.sparse as sp
 MAX_PCA_GENES = 8192     # smx_pca_cov: the covariance takes 8 G^2 bytes
 MAX_KNN_DIM = 128        # smx_knn
 MAX_NEIGHBORS = 257      # smx_knn: k <= 256 others, plus the cell itself
+MAX_TSNE_COMPONENTS = 3  # smx_tsne_fit
+MAX_PERPLEXITY = 85.0    # floor(3 perplexity + 1) <= 256 neighbours
 
 
 def _engine():
@@ -157,3 +161,134 @@ def neighbors(Z, n_neighbors: int = 12):
   Z = _check_cells(Z)
   K = check_n_neighbors(n_neighbors, Z.shape[0])
   return umap_connectivities(*self_table(*knn(Z, K - 1)))
+
+
+# ---- t-SNE (smx_tsne.hip; definitions in include/sisua_hip.h and DESIGN.md section 4x) ----
+def check_tsne_components(n_components) -> int:
+  if isinstance(n_components, bool) or n_components != int(n_components) or not 1 <= int(n_components) <= MAX_TSNE_COMPONENTS:
+    raise NotImplementedError(f"t-SNE embeds into at most {MAX_TSNE_COMPONENTS} dimensions here (n_components = 1, 2 or 3), got "
+                              f"{n_components}: pass n_components=2, or use algo='pca' for wider representations")
+  return int(n_components)
+
+
+def _check_tsne_cells(Z, perplexity):
+  """-> (Z float32 [cells, D], k): scikit-learn's support k = min(cells - 1, floor(3 perplexity + 1))"""
+  if getattr(Z, "ndim", 0) == 2 and Z.shape[1] > MAX_KNN_DIM:
+    raise ValueError(f"t-SNE of {Z.shape[1]} columns is not built: the exact neighbour search takes at most D <= {MAX_KNN_DIM}; reduce "
+                     "the matrix first with pca(X, n_components)")
+  Z = _check_cells(Z)
+  n, perplexity = Z.shape[0], float(perplexity)
+  if n < 4:
+    raise ValueError(f"t-SNE needs at least 4 cells, got {n}")
+  if not (np.isfinite(perplexity) and 1.0 <= perplexity <= MAX_PERPLEXITY):
+    raise ValueError(f"perplexity must be in 1 .. {MAX_PERPLEXITY:g} (the support of 3 perplexity + 1 neighbours is at most "
+                     f"{MAX_NEIGHBORS - 1} cells), got {perplexity}")
+  if perplexity >= n:
+    raise ValueError(f"perplexity must be below the number of cells ({n}), got {perplexity}")
+  return Z, min(n - 1, int(3.0 * perplexity + 1.0))
+
+
+def joint_probabilities(idx, cond_p):
+  """The joint P of a table of conditional affinities (host only): A = the CSR of cond_p [N, k] at (i, idx), P = (A + A^T) / sum(A + A^T),
+  float64 CSR [N, N] with sorted columns; explicit zeros are kept out."""
+  idx, cond_p = np.asarray(idx), np.asarray(cond_p, dtype=np.float64)
+  if idx.ndim != 2 or cond_p.shape != idx.shape:
+    raise ValueError(f"idx and cond_p must share one shape [cells, k], got {idx.shape} and {cond_p.shape}")
+  N, k = idx.shape
+  if idx.size and (idx.min() < 0 or idx.max() >= N):
+    raise ValueError("idx holds an index outside 0 .. cells - 1")
+  A = sp.csr_matrix((cond_p.ravel(), idx.ravel().astype(np.int64), np.arange(0, N * k + 1, k)), shape=(N, N))
+  P = (A + A.T).tocsr()
+  P.sum_duplicates()
+  P.eliminate_zeros()
+  P.sort_indices()
+  P /= P.sum()
+  P.eliminate_zeros()   # (an entry that the division took below the smallest float64)
+  return P
+
+
+def tsne_affinities(Z, perplexity: float = 30.0):
+  """The joint affinities P of t-SNE for the cells Z [cells >= 4, D <= 128], scikit-learn's: conditional Gaussians of the given perplexity
+  on each cell's min(cells - 1, floor(3 perplexity + 1)) exact nearest neighbours, symmetrised -> scipy.sparse CSR float64"""
+  Z, k = _check_tsne_cells(Z, perplexity)
+  idx, dist = _engine().k_knn(Z, k)
+  cond_p, _ = _engine().k_tsne_affinities(idx, dist, float(perplexity))
+  return joint_probabilities(idx, cond_p)
+
+
+def tsne_init(Z, n_components: int, init="pca", random_state=1):
+  """The start of the descent, float64 [cells, C].  'pca': the first C exact-PCA scores of Z over the standard deviation of the first,
+  times 1e-4 (scikit-learn's default; fewer than C columns in Z: the rest start at 0); 'random': RandomState(random_state)
+  .standard_normal times 1e-4; or an array [cells, C]"""
+  n, C = Z.shape[0], int(n_components)
+  if isinstance(init, str):
+    if init == "random":
+      return np.random.RandomState(random_state).standard_normal((n, C)) * 1e-4
+    if init != "pca":
+      raise ValueError(f"init must be 'pca', 'random' or an array [cells, {C}], got {init!r}")
+    scores = pca(Z, C)[1].astype(np.float64)
+    if scores.shape[1] < C:
+      scores = np.concatenate([scores, np.zeros((n, C - scores.shape[1]))], axis=1)
+    sd = np.std(scores[:, 0])
+    return scores / sd * 1e-4 if sd > 0 else scores
+  Y0 = np.array(init, dtype=np.float64)
+  if Y0.shape != (n, C):
+    raise ValueError(f"init must be 'pca', 'random' or an array [{n}, {C}], got an array of shape {Y0.shape}")
+  if not np.isfinite(Y0).all():
+    raise ValueError("init holds an entry that is not finite")
+  return Y0
+
+
+class TSNE:
+  """t-SNE with scikit-learn's objective, schedule and attribute names, the Barnes-Hut tree replaced by the exact sum over all pairs,
+  float64 on the device (smx_tsne.hip).  After fit_transform: embedding_ [cells, C] float32 (the float64 result rounded once),
+  kl_divergence_ (the last reported KL), n_iter_ (iterations run), learning_rate_, kl_trace_ [max_iter] (NaN where an iteration did not
+  report).  Duplicated cells under init='pca' start and stay on top of each other, as in scikit-learn: equal positions get equal
+  forces in the exact form."""
+
+  def __init__(self, n_components=2, perplexity=30.0, early_exaggeration=12.0, learning_rate="auto", max_iter=1000,
+               n_iter_without_progress=300, min_grad_norm=1e-7, init="pca", random_state=1):
+    self.n_components, self.perplexity, self.early_exaggeration = n_components, perplexity, early_exaggeration
+    self.learning_rate, self.max_iter, self.n_iter_without_progress = learning_rate, max_iter, n_iter_without_progress
+    self.min_grad_norm, self.init, self.random_state = min_grad_norm, init, random_state
+
+  def fit_transform(self, Z):
+    C = check_tsne_components(self.n_components)
+    Z, k = _check_tsne_cells(Z, self.perplexity)
+    n, ee = Z.shape[0], float(self.early_exaggeration)
+    if isinstance(self.learning_rate, str):
+      if self.learning_rate != "auto":
+        raise ValueError(f"learning_rate must be 'auto' or a positive number, got {self.learning_rate!r}")
+      lr = max(n / ee / 4.0, 50.0)
+    else:
+      lr = float(self.learning_rate)
+    if not (np.isfinite(ee) and ee > 0 and np.isfinite(lr) and lr > 0):
+      raise ValueError(f"early_exaggeration and learning_rate must be finite and positive, got {ee} and {lr}")
+    if int(self.max_iter) < 1 or int(self.n_iter_without_progress) < 0 or not float(self.min_grad_norm) >= 0:
+      raise ValueError("max_iter must be >= 1, n_iter_without_progress >= 0 and min_grad_norm >= 0")
+    if not isinstance(self.init, str):
+      tsne_init(Z, C, self.init)   # (a refusal comes before any device work)
+    elif self.init not in ("pca", "random"):
+      raise ValueError(f"init must be 'pca', 'random' or an array [cells, {C}], got {self.init!r}")
+    eng = _engine()
+    idx, dist = eng.k_knn(Z, k)
+    P = joint_probabilities(idx, eng.k_tsne_affinities(idx, dist, float(self.perplexity))[0])
+    Y0 = tsne_init(Z, C, self.init, self.random_state)
+    fit = eng.k_tsne_fit(P, Y0, int(self.max_iter), ee, lr, float(self.min_grad_norm), int(self.n_iter_without_progress))
+    reported = fit["kl_trace"][~np.isnan(fit["kl_trace"])]
+    self.embedding_ = fit["Y"].astype(np.float32)
+    self.kl_divergence_ = float(reported[-1]) if reported.size else float("nan")
+    self.kl_trace_, self.n_iter_, self.learning_rate_ = fit["kl_trace"], fit["n_iter"], lr
+    return self.embedding_
+
+  def fit(self, Z):
+    self.fit_transform(Z)
+    return self
+
+
+def tsne(Z, n_components: int = 2, perplexity: float = 30.0, early_exaggeration: float = 12.0, learning_rate="auto", max_iter: int = 1000,
+         n_iter_without_progress: int = 300, min_grad_norm: float = 1e-7, init="pca", random_state=1):
+  """The t-SNE embedding of the cells Z [cells >= 4, D <= 128], e.g. a latent space or PCA scores -> Y [cells, n_components <= 3] float32
+  (see `TSNE`)"""
+  return TSNE(n_components, perplexity, early_exaggeration, learning_rate, max_iter, n_iter_without_progress, min_grad_norm, init,
+              random_state).fit_transform(Z)
