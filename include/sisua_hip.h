@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 13
+#define SMX_ABI_VERSION 14
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -942,6 +942,45 @@ int smx_tsne_gradient(const int64_t* indptr, const int32_t* cols, const double* 
 int smx_tsne_fit(const int64_t* indptr, const int32_t* cols, const double* p, int64_t n_cells, int32_t n_components, const double* Y0,
                  int32_t max_iter, double early_exaggeration, double learning_rate, double min_grad_norm, int32_t n_iter_without_progress,
                  double* Y, double* kl_trace, int32_t* n_iter, double* update_out, double* gains_out);
+
+/* ---- gene x protein mutual information (smx_mi.hip; model-free: smx_init only) ----------- */
+/* scikit-learn's three kNN estimators per pair (gene column, protein column), float64, every distance the exact |a - b|.  The columns
+ * arrive gene-major, prepared by the host (sisua_amd/mutual_info.py: a continuous column divided by its standard deviation and noised,
+ * a discrete column as it is; labels compare by value, -0 as +0).  psi [n_cells + 1] and logn [n_cells + 1] are the host's tables
+ * digamma(n) and log(n), n = 0 .. n_cells (entry 0 is never read): the device adds table entries and evaluates neither function.
+ * k = n_neighbors, N = n_cells, nextafter(., 0) = the float64 just below.
+ *   cc (both continuous; Kraskov et al., _compute_mi_cc):  d_ij = max(|x_i - x_j|, |y_i - y_j|);  r_i = nextafter(the k-th smallest d_ij
+ *      over j != i, 0);  cx_i = #{j : |x_j - x_i| <= r_i} and cy_i alike, i itself counted (scikit-learn's nx + 1, ny + 1);
+ *      mi = psi(N) + psi(k) - (sum psi(cx_i)) / N - (sum psi(cy_i)) / N.
+ *   cd (continuous c, discrete d; Ross, _compute_mi_cd):  in a label group of count > 1, k_i = min(k, count - 1) and r_i = nextafter(the
+ *      k_i-th smallest |c_j - c_i| over the OTHER cells of the group, 0); the cells whose label occurs once are dropped from everything;
+ *      m_i = #{kept j : |c_j - c_i| <= r_i}, i among them; with n' kept cells mi = psi(n') + (sum psi(k_i)) / n' - (sum psi(count_i)) / n'
+ *      - (sum psi(m_i)) / n', and 0 when no cell is kept.
+ *   dd (both discrete; mutual_info_score):  over the non-empty cells of the contingency table in (gene label, protein label) order,
+ *      the sum of (n_ab / N) (((logn[n_ab] - logn[n_a]) - logn[n_b]) + logn[N]).
+ * Every value is clipped below at 0.  Two deviations from scikit-learn: its NearestNeighbors leaves the tree for the brute-force path in
+ * label groups of 2 .. 2k + 1 cells, whose distances sqrt(x^2 + y^2 - 2xy) lose the host's 1e-10 noise -- here they stay exact; and where
+ * no cell is kept scikit-learn raises.
+ * Every column is sorted once (a stable radix sort of the cell indices on the order-preserving 64-bit pattern).  cc is an exact sweep over
+ * the other cells, outward from the cell in the gene's sorted order, that stops where no cell further out can be among the k nearest: the
+ * k-th smallest distance is a set function, so the result is that of the full sweep.  Every sum over the cells is ONE fixed-order
+ * reduction, a function of n_cells alone (256 strided partials, the lanes of a wave by halving, the four waves); dd's terms are added
+ * the same way over the positions of the runs.  No float atomics: the same bits from call to call and for every gene_chunk (the genes
+ * sorted and held on the device at a time; 0: as many as 256 MB hold at 36 n_cells + 28 n_cells n_proteins bytes each).
+ * 2 <= n_cells <= 2^20; n_genes, n_proteins >= 1 and n_genes x n_proteins < 2^31; 1 <= n_neighbors <= 8 (the sweep's register list) and n_neighbors < n_cells, as scikit-learn asks; every value
+ * finite (SMX_ERR_INVALID names the first offending gene or protein column; checked on the device, before any estimator runs on the
+ * chunk).  mi [n_genes][n_proteins].
+ *
+ * smx_k_mi_cells: ONE pair of columns -> the per-cell quantities, for tests.  cells [4][n_cells] int32 and radius [n_cells], indexed by
+ * cell.  cc: planes 0, 1 = cx_i, cy_i; radius = r_i.  cd (either column discrete): plane 0 = k_i, 1 = count_i where kept else 0, 2 = m_i,
+ * 3 = count_i of every cell; radius = r_i (0 where not kept).  dd: indexed by POSITION in (gene label, protein label) order: plane 2 =
+ * n_ab at the first position of a run and 0 elsewhere, plane 3 = the cell at the position; planes 0 and 1 hold the terms as float64.
+ * *mi = the pair's value. */
+int smx_mutual_info(const double* xcols, const uint8_t* x_discrete, const double* ycols, const uint8_t* y_discrete, int64_t n_cells,
+                    int32_t n_genes, int32_t n_proteins, int32_t n_neighbors, int32_t gene_chunk, const double* psi, const double* logn,
+                    double* mi);
+int smx_k_mi_cells(const double* x, int32_t x_discrete, const double* y, int32_t y_discrete, int64_t n_cells, int32_t n_neighbors,
+                   const double* psi, const double* logn, int32_t* cells, double* radius, double* mi);
 
 /* ---- padding audit (test instrument; never on the path of a step) ----------- */
 /* The layout's invariant, read back from the device: every feature axis is padded to 32 and every tensor to 64 floats, and what lies

@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsisua_hip.so")
 
-SMX_ABI_VERSION = 13
+SMX_ABI_VERSION = 14
 SMX_MAX_LAYERS = 8
 SMX_MAX_LABELS = 4
 
@@ -201,6 +201,9 @@ SIGNATURES = {
     "smx_tsne_gradient": (C.c_int, [_LP, _IP, _DP, C.c_int64, C.c_int32, _DP, C.c_double, _DP, _DP, _DP]),
     "smx_tsne_fit": (C.c_int, [_LP, _IP, _DP, C.c_int64, C.c_int32, _DP, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _DP, _DP, _IP,
                                _DP, _DP]),
+    "smx_mutual_info": (C.c_int, [_DP, C.POINTER(C.c_uint8), _DP, C.POINTER(C.c_uint8), C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP,
+                                  _DP, _DP]),
+    "smx_k_mi_cells": (C.c_int, [_DP, C.c_int32, _DP, C.c_int32, C.c_int64, C.c_int32, _DP, _DP, _IP, _DP, _DP]),
     "smx_pad_audit": (C.c_int, [_VP, C.c_int32, _LP, _IP, _LP, C.c_char_p, C.c_int32]),
     "smx_pad_poke": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_float]),
 }

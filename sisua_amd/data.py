@@ -313,6 +313,7 @@ class SingleCellOMIC:
     self._pca = {}          # omic -> (PCA, scores) of dimension_reduce; likewise
     self._neighbors = {}    # omic -> (connectivities, distances, params) of neighbors; likewise
     self._tsne = {}         # (omic, n_components) -> the embedding of dimension_reduce(algo='tsne'); likewise
+    self._uns = {}          # the reference's .uns: 'mutualinfo_{omic}_{target}' -> (omic, target, matrix) of get_mutual_information; likewise
     self.add_omic(omic, X, var_names)
 
   def add_omic(self, omic: str, X, var_names=None):
@@ -397,6 +398,8 @@ class SingleCellOMIC:
       cache.pop(key, None)
     for kc in [kc for kc in self._tsne if kc[0] == key]:
       del self._tsne[kc]
+    for kc in [kc for kc, v in self._uns.items() if key in v[:2]]:
+      del self._uns[kc]
 
   def _replace(self, key: str, X, var_names=None):
     """A new matrix for an omic already held (same cells); its embedding, PCA and neighbour graph, if any, no longer describe it"""
@@ -542,6 +545,21 @@ class SingleCellOMIC:
       self._pca[key] = nb.pca(X, C)
     scores = self._pca[key][1]
     return scores if scores.shape[1] == C else scores[:, :C]
+
+  def get_mutual_information(self, omic="transcriptomic", target_omic="proteomic", n_neighbors=3, random_state=1):
+    """The reference's get_mutual_information (_single_cell_analysis.py:1148-1196): the mutual information [n_vars of omic, n_vars of
+    target_omic] float64 between every feature of one omic and every feature of another, scikit-learn's kNN estimators
+    (`sisua_amd.mutual_information`: discrete columns are those whose every value is an integer; the estimators run on the device,
+    smx_mi.hip).  As in the reference the seed is fixed at 1 whatever `random_state`, the two omics must differ, and the matrix is kept
+    under 'mutualinfo_{omic}_{target_omic}' until one of the two omics is replaced: a later call returns it whatever its n_neighbors."""
+    from sisua_amd.mutual_info import mutual_information
+    n_neighbors, random_state = int(n_neighbors), 1
+    om1, om2 = self._first(omic), self._first(target_omic)
+    assert om1 != om2, "Mutual information only for 2 different OMIC type"
+    uns_key = f"mutualinfo_{om1}_{om2}"
+    if uns_key not in self._uns:
+      self._uns[uns_key] = (om1, om2, mutual_information(self.numpy(om1), self.numpy(om2), n_neighbors=n_neighbors, random_state=random_state))
+    return self._uns[uns_key][2]
 
   def get_pca(self, omic=None):
     """The fitted `sisua_amd.PCA` of an omic (what `dimension_reduce` left), or None"""

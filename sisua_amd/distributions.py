@@ -761,6 +761,20 @@ class LazyCountOutput(Distribution):
     return correlations_from_sums(self._x.shape[0], r["sp_Sa"], r["sp_Saa"], r["sp_Sab"], ops["Sb"], ops["Sbb"], r["pe_Sxx"], r["pe_Sxy"],
                                   r["nonfinite"], ops["constant"])
 
+  def mutual_information(self, extras, genes=None, n_neighbors=3):
+    """The gene x protein mutual-information matrix [G', P] float64 (`sisua_amd.mutual_information`: scikit-learn's kNN estimators with
+    seed 1, on the device) between `mean_over_samples()` of this prediction and the protein levels `extras` [n_cells, P]; G' = all genes
+    or the list `genes` (any order, repeats allowed).  On a zero-inflated output the count distribution's mean is used, as `correlation`
+    does.  The columns come through `mean_over_samples(genes=...)`: the predict walk is what it was."""
+    from sisua_amd.mutual_info import mutual_information
+    ex = np.asarray(extras.toarray() if _sp.issparse(extras) else extras, np.float64)
+    if ex.ndim != 2 or ex.shape[0] != self._x.shape[0]:
+      raise ValueError(f"extras must be [{self._x.shape[0]}, proteins], got {ex.shape}")
+    h = self.count_distribution if self.is_zero_inflated else self
+    sel = list(range(self.event_shape[0])) if genes is None else [int(g) for g in genes]
+    cols = h.mean_over_samples(genes=sel)   # [n_cells, G'] float32
+    return mutual_information(cols, ex, n_neighbors=n_neighbors, random_state=1)
+
   def log_prob(self, x=None):
     """log p(x) summed over the genes, [n_samples, n_cells] ([n_cells] without a draw axis); x = None: of the input counts.  x may be
     scipy.sparse."""

@@ -1,8 +1,8 @@
 """Evaluation metrics of a fitted model as plain callables `metric(model) -> dict` (the reference's training-time metrics,
-sisua/analysis/sc_metrics.py:244-402, without its callback machinery): `ImputationError`, `CorrelationScores` and `ClusteringScores`
-(with `clustering_scores`, the function it is made of); and the views of the full gene x protein
-matrices of `SingleCellModel.correlation` that the reference's analysis reads (`correlation_list`, `marker_correlations`).  What needs the
-[cells, genes] mean of the gene output is reduced on the device (smx_impute.hip); the correlations over a few marker columns are SciPy's,
+sisua/analysis/sc_metrics.py:244-402, without its callback machinery): `ImputationError`, `CorrelationScores`, `MutualInformation` and
+`ClusteringScores` (with `clustering_scores`, the function it is made of); and the views of the full gene x protein matrices of
+`SingleCellModel.correlation` / `mutual_information` that the reference's analysis reads (`correlation_list`, `marker_correlations`, and
+`marker_scores`, which also takes the 'mi' matrix).  What needs the [cells, genes] mean of the gene output is reduced on the device (smx_impute.hip); the correlations over a few marker columns are SciPy's,
 called as the reference calls them."""
 from __future__ import annotations
 
@@ -111,6 +111,26 @@ class ClusteringScores:
     return scores
 
 
+class MutualInformation:
+  """`{'mi_mean', 'mi_med'}` of a model, beside `CorrelationScores` and with its arguments: the NEGATED mutual information (nats;
+  `sisua_amd.mutual_information`, scikit-learn's kNN estimators on the device) between the imputed expression of a marker gene and the
+  level of its protein, mean and median over the pairs ({} without pairs).  Only the marker genes' columns of the mean leave the device."""
+
+  def __init__(self, inputs, extras, pairs: Iterable[Tuple[int, int]], sample_shape=1, batch_size=64, n_neighbors=3):
+    c = CorrelationScores(inputs, extras, pairs, sample_shape, batch_size)   # (the same checks)
+    self.inputs, self.extras, self.pairs = c.inputs, c.extras, c.pairs
+    self.sample_shape, self.batch_size, self.n_neighbors = sample_shape, int(batch_size), int(n_neighbors)
+
+  def __call__(self, model) -> Dict[str, float]:
+    if not self.pairs:
+      return {}
+    genes = [g for g, _ in self.pairs]
+    mat = model.mutual_information(self.inputs, self.extras, sample_shape=self.sample_shape, batch_size=self.batch_size, genes=genes,
+                                   n_neighbors=self.n_neighbors)
+    mi = [-float(mat[j, p]) for j, (_, p) in enumerate(self.pairs)]
+    return {"mi_mean": float(np.mean(mi)), "mi_med": float(np.median(mi))}
+
+
 def correlation_list(pearson, spearman) -> List[Tuple[int, int, float, float]]:
   """`SingleCellOMIC.get_correlation`'s return (_single_cell_analysis.py:1199-1245) from the two [G, P] matrices: (gene index, protein
   index, pearson, spearman) of every pair, sorted by decreasing average of the two (the reference's `sorted(...)[::-1]`: among equal averages the later pair first); pairs whose
@@ -136,3 +156,12 @@ def marker_correlations(matrix, kind: str, gene_names: Sequence[str], protein_na
   var1 = {str(n): i for i, n in enumerate(gene_names)}
   var2 = {str(n): i for i, n in enumerate(protein_names)}
   return {f"{kind}_{g}_{p}": float(m[var1[str(g)], var2[str(p)]]) for p, g in markers.items() if str(g) in var1 and str(p) in var2}
+
+
+def marker_scores(matrix, kind: str, gene_names: Sequence[str], protein_names: Sequence[str], markers: Mapping[str, str]) -> Dict[str, float]:
+  """`Posterior._matrix_scores` (posterior.py:996-1024) of a 'pearson', 'spearman' or 'mi' matrix [genes, proteins]:
+  `marker_correlations` (which refuses 'mi') with the third kind: {f"{kind}_{gene}_{protein}": matrix[gene, protein]}."""
+  if kind != "mi":
+    return marker_correlations(matrix, kind, gene_names, protein_names, markers)
+  found = marker_correlations(matrix, "pearson", gene_names, protein_names, markers)   # (the same view; only the keys' prefix differs)
+  return {"mi" + key[len("pearson"):]: value for key, value in found.items()}

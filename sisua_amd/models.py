@@ -853,6 +853,14 @@ class SingleCellModel:
     ex = extras.numpy() if isinstance(extras, SingleCellOMIC) else extras
     return self._imputation_handle(inputs, library, sample_shape, batch_size).correlation(ex, genes=genes)
 
+  def mutual_information(self, inputs, extras, library=None, sample_shape=10, batch_size=128, genes=None, n_neighbors=3):
+    r"""The gene x protein mutual-information matrix that `Posterior.cal_mutual_information` / `get_correlation_matrix(corr_type='mi')`
+    read (analysis/posterior.py:896-912): `sisua_amd.mutual_information` (scikit-learn's kNN estimators, seed 1, on the device) between the
+    imputed expression -- as in `correlation`: the mean of the count distribution averaged over the draws -- and the protein levels
+    `extras` [cells, proteins] -> [G', P] float64 (`genes`: a list of gene indices, default all)."""
+    ex = extras.numpy() if isinstance(extras, SingleCellOMIC) else extras
+    return self._imputation_handle(inputs, library, sample_shape, batch_size).mutual_information(ex, genes=genes, n_neighbors=n_neighbors)
+
   def clustering_scores(self, inputs, labels, n_labels=None, library=None, batch_size=128, prediction_algorithm="knn", **kw):
     r"""The reference's `clustering_scores` (analysis/latent_benchmarks.py:69-117) of this model's latent space: the cells of `inputs`
     (dense or scipy.sparse) are encoded and the mean of the latent posterior -- a deterministic latent: the latent itself -- is scored
