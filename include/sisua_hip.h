@@ -624,6 +624,11 @@ int64_t smx_head_fused_bytes(const smx_model* m, int32_t batch);
 /* 1 when the model's LAST training step left the output head's dW / db to the decoder's BatchNorm-backward launch (a narrow panel, at most
  * 128 cells, the plain bf16 x 3 head, one GPU: DESIGN.md section 4; knob no_dw_late), else 0: the tests' check that this form is what ran. */
 int32_t smx_head_dw_late(const smx_model* m);
+/* How many steps of the model's LAST smx_train_steps call left their optimiser launch out: the next step's first launch -- the gathered
+ * encoder product -- then updates its block of the first encoder matrix in registers, and riders of the forward launches apply the update in
+ * place (eager steps of one GPU under Adam, every step of a call but its last: DESIGN.md section 4; knob no_lazy_adam).  The tests' check
+ * that this form is what ran. */
+int32_t smx_lazy_adam_steps(const smx_model* m);
 
 /* ---- kernel-level entry points (parity tests of single kernels) ------------ */
 /* Fused count log-likelihood forward+backward over host planes [k][B][G]:

@@ -14,18 +14,21 @@ typedef float smx_f32x4 __attribute__((ext_vector_type(4)));
 
 // the chunk's tensor: its gradient norm (written once per tensor, by the tensor's first chunk) and the factor its gradients are scaled by.
 // Every thread of the workgroup calls it (two barriers); the first 256 threads sum in the same order whatever NT is.
-template <int NT = 256>
-__device__ inline float adam_tensor_clip(const AdamArgs& a, const OptChunk& ch, int chunk) {
+// (adam_tensor_clip_at: the tensor's slot range handed in -- a caller that knows its tensor on the host passes it as kernel arguments instead of
+// indexing a.sq_count / a.sq_first by a value it would have to load first; the gathered encoder product's riding form, smx_gemm.hip)
+template <int NT = 256, bool AT = true>
+__device__ inline float adam_tensor_clip_at(const AdamArgs& a, const OptChunk& ch, int chunk, const int cnt_at, const int first_at) {
   __shared__ float sh[4];
   float s = 0.f;
   if (NT > 256 && threadIdx.x >= 256) {
   } else if (a.use_sq) {
-    const int cnt = a.sq_count[ch.tensor];
+    const int cnt = AT ? cnt_at : a.sq_count[ch.tensor];
+    const int first = AT ? first_at : a.sq_first[ch.tensor];
     if (cnt > 0) {   // partial sums written by the weight-gradient product's workgroups
       // (a thread's slots eight at a time in flight -- unconditional loads from a clamped index, masked at the add, added in the same order
       // as one by one: same bits.  As a rider of a 5-10 us launch a workgroup's LIFE is what counts, and 7 dependent round trips for the
       // 1672 slots of the one-launch output head were most of it)
-      const float* sl = a.sq_slots + a.sq_first[ch.tensor];
+      const float* sl = a.sq_slots + first;
       for (int k0 = threadIdx.x; k0 < cnt; k0 += 8 * 256) {
         float q[8];
 #pragma unroll
@@ -55,6 +58,10 @@ __device__ inline float adam_tensor_clip(const AdamArgs& a, const OptChunk& ch, 
   if (a.clipnorm > 0.f && norm > a.clipnorm) clip *= a.clipnorm / norm;
   if (threadIdx.x == 0 && chunk == ch.first_chunk) a.tensor_norm[ch.tensor] = norm;
   return clip;
+}
+template <int NT = 256>
+__device__ inline float adam_tensor_clip(const AdamArgs& a, const OptChunk& ch, int chunk) {
+  return adam_tensor_clip_at<NT, false>(a, ch, chunk, 0, 0);
 }
 
 // one quad of a tensor: the update itself.  Every contraction is SPELLED: the launches that carry this body (optimiser, riders, sweep, the sharded
@@ -243,6 +250,40 @@ __device__ inline void adam_sweep_body(const AdamArgs& a, int first, int count) 
 #define SMX_OPT_SWEEP(F) opt_sweep_chunk<NT, F>(a, clip, lr_t, n4, g4, m4, v4, p4)
     SMX_OPT_SWITCH(ALL, a.form, SMX_OPT_SWEEP)
 #undef SMX_OPT_SWEEP
+  }
+}
+
+__device__ inline float adam_lr_t(float lr, float b1, float b2, uint32_t t /* 1-based */) {
+  return lr * sqrtf(1.f - powf(b2, (float)t)) / (1.f - powf(b1, (float)t));
+}
+// the step size of the step with index `step` under the rule `form`, whose state began at step t0: t = step + 1 - t0 (t0 = 0 for Adam unless
+// the rule was switched: Adam's bits as before).  Adamax: lr / (1 - b1^t); the rules without bias correction: lr.
+__device__ inline float opt_lr_t(int form, float lr, float b1, float b2, uint32_t step, uint32_t t0) {
+  const uint32_t t = step >= t0 ? step + 1u - t0 : 1u;
+  if (form == OPT_ADAM) return adam_lr_t(lr, b1, b2, t);
+  if (form == OPT_ADAMAX) return lr / (1.f - powf(b1, (float)t));
+  return lr;
+}
+
+// closing the step (a.master != nullptr), by the first 256 threads of ONE workgroup: the master counter, and -- prepare_next -- the other parity's
+// state and row ids for the step after.  Nobody reads next_state / next_rows during this step, so the workgroup may be the optimiser launch's
+// last one or a rider of any backward launch of the step (BnBwdArgs::close: a step whose optimiser launch is left out, smx_step.hip).
+template <bool ALL>
+__device__ inline void step_close_body(const AdamArgs& a) {
+  const uint32_t step = a.state->step, cur = a.state->cursor;
+  if (a.hist_dp && threadIdx.x < 8) a.hist_dp[(long)cur * 8 + threadIdx.x] = a.tail_metrics[threadIdx.x];
+  const float2 w = a.prepare_next && threadIdx.x == 0 ? a.sched[cur + 1] : make_float2(0.f, 0.f);   // (beta, lr) of the next step, requested by cursor beside its row ids
+  if (a.prepare_next)
+    for (int i = threadIdx.x; i < a.batch; i += 256) a.next_rows[i] = a.order[(long)(cur + 1) * a.batch + i];
+  if (threadIdx.x == 0) {
+    a.master->next = step + 1;
+    if (a.prepare_next) {
+      a.next_state->step = step + 1;
+      a.next_state->cursor = cur + 1;
+      a.next_state->beta = w.x;
+      a.next_state->lr = w.y;
+      a.next_state->lr_t = opt_lr_t(ALL ? a.form : (int)OPT_ADAM, w.y, a.b1, a.b2, step + 1, a.t0);
+    }
   }
 }
 

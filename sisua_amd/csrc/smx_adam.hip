@@ -9,18 +9,7 @@ namespace smx {
 // ===========================================================================
 // per-step scalars, metrics
 // ===========================================================================
-__device__ inline float adam_lr_t(float lr, float b1, float b2, uint32_t t /* 1-based */) {
-  return lr * sqrtf(1.f - powf(b2, (float)t)) / (1.f - powf(b1, (float)t));
-}
-// the step size of the step with index `step` under the rule `form`, whose state began at step t0: t = step + 1 - t0 (t0 = 0 for Adam unless
-// the rule was switched: Adam's bits as before).  Adamax: lr / (1 - b1^t); the rules without bias correction: lr.
-__device__ inline float opt_lr_t(int form, float lr, float b1, float b2, uint32_t step, uint32_t t0) {
-  const uint32_t t = step >= t0 ? step + 1u - t0 : 1u;
-  if (form == OPT_ADAM) return adam_lr_t(lr, b1, b2, t);
-  if (form == OPT_ADAMAX) return lr / (1.f - powf(b1, (float)t));
-  return lr;
-}
-
+// (adam_lr_t / opt_lr_t: smx_adam.h, beside the step's closing body that shares them)
 __global__ void step_begin_kernel(StepState* master, StepState* dst, const int32_t* order, int32_t* rows, int batch,
                                   int cursor_from_master, uint32_t cursor, const float2* sched, float b1, float b2, int form, uint32_t t0) {
   const uint32_t cur = cursor_from_master ? master->cursor : cursor;
@@ -90,23 +79,7 @@ __global__ __launch_bounds__(256) void adam_update_kernel(AdamArgs a) {
   }
   // the LAST workgroup closes the step (nobody reads next_state / next_rows during this step).  As a duty of workgroup 0 behind its chunk --
   // state -> row ids -> stores: two more dependent round trips and a powf -- it was the launch's critical path.
-  if (a.master) {
-    const uint32_t step = a.state->step, cur = a.state->cursor;
-    if (a.hist_dp && threadIdx.x < 8) a.hist_dp[(long)cur * 8 + threadIdx.x] = a.tail_metrics[threadIdx.x];
-    const float2 w = a.prepare_next && threadIdx.x == 0 ? a.sched[cur + 1] : make_float2(0.f, 0.f);   // (beta, lr) of the next step, requested by cursor beside its row ids
-    if (a.prepare_next)
-      for (int i = threadIdx.x; i < a.batch; i += 256) a.next_rows[i] = a.order[(long)(cur + 1) * a.batch + i];
-    if (threadIdx.x == 0) {
-      a.master->next = step + 1;
-      if (a.prepare_next) {
-        a.next_state->step = step + 1;
-        a.next_state->cursor = cur + 1;
-        a.next_state->beta = w.x;
-        a.next_state->lr = w.y;
-        a.next_state->lr_t = opt_lr_t(ALL ? a.form : (int)OPT_ADAM, w.y, a.b1, a.b2, step + 1, a.t0);
-      }
-    }
-  }
+  if (a.master) step_close_body<ALL>(a);
 }
 
 // the heads' update as a background sweep beside the launches that follow the output head (smx_backward.hip: head_sweep_*): a FIXED

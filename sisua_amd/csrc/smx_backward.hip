@@ -314,6 +314,20 @@ static int mlp_backward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps
       // (the carrier WRITES dW_out and its slots: the head's riders wait -- adam_early_pending stays set -- for the next BatchNorm-backward launch)
       const HeadBwdArgs* hd = (last && o.head_dw && bn_wide_bwd_dw_supported(b, *o.head_dw)) ? o.head_dw : nullptr;
       if (!hd) attach_early_adam(m, b);
+      // (the carrier has rider slots and no riders of this step -- they wait for the encoder's launch --: W_enc's chunks of the step BEFORE, which
+      // the forward pass left pending for this launch (fwd_encoder: lazy_w_late), ride here with that step's arguments.  Nothing since this step's
+      // first launch reads W_enc, and its gradient and slots are rewritten by the weight-gradient launch, behind this one)
+      const bool w_rides = hd && b.adam_count == 0 && b.sqr_count == 0 && m->lazy_w_pending && !m->lazy_rest_pending;
+      if (w_rides) { b.adam = m->lazy_args; b.adam_first = m->lazy_w_first; b.adam_count = m->lazy_w_n; }
+      // a step that leaves its optimiser launch to the next step's forward launches (smx_step.hip: lazy_adam_wanted): what that launch's extra
+      // workgroups did -- the ELBO scalars, closing the step -- rides with the encoder's first BatchNorm-backward launch instead
+      // (lazy_l1: only a step whose first launch took the form the update needs -- every other step's launches stay exactly as they were)
+      if (m->lazy_want && m->lazy_l1 && !m->lazy_closed && &mlp == &m->enc && m->have_pending_metrics) {
+        b.metrics = m->pending_metrics; b.with_metrics = 1; m->have_pending_metrics = false;
+        if (!b.adam.params) fill_adam_args(m, b.adam);
+        fill_step_close(m, b.adam);
+        b.close = 1; m->lazy_closed = true;
+      }
       Timed t(m, "bn_bwd");
       const bool dual = last && b.front && b.fK <= 64 && o.twin && o.twin_front && o.twin_front->fK <= 64 && !o.twin->empty() && m->flags.twin && bn_dual_supported(ps.B) &&
                         bn_bwd_front_supported(ps.B, o.twin_front->fK) && o.twin->back().out_p % 8 == 0 &&
@@ -321,6 +335,7 @@ static int mlp_backward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps
       if (hd) {
         SMX_CHECK(launch_bn_wide_bwd_dw(m->st, b, *hd));
         dw_carried = true;
+        if (w_rides) m->lazy_w_pending = false;
       } else if (dual) {
         const BnBwdArgs b2 = make_b(o.twin->back(), 0, o.twin_front);
         SMX_CHECK(launch_bn_act_bwd_dual(m->st, b, b2));
@@ -928,6 +943,7 @@ int backward_pass(smx_model* m, const Pass& ps) {
   SMX_CHECK(bwd_head_group(m, ps, p));
   SMX_CHECK(bwd_heads_final(m));
   SMX_CHECK(bwd_decoder(m, ps, p));
+  SMX_CHECK(lazy_flush(m));   // (W_enc's chunks of the step before, if the decoder's launch did not take them after all: ahead of this step's weight gradients)
   for (const GemmArgs& g : p.lab_dw) p.tail.push_back(g);
   SMX_CHECK(bwd_latent_head(m, ps, p));
   SMX_CHECK(bwd_encoder(m, ps, p));

@@ -644,7 +644,8 @@ __device__ inline void bn_act_bwd_body(const BnBwdArgs& a, const int bid) {
       if (e < 0) metrics_body(a.metrics);                                                 // ELBO scalars
       else {                                                                              // or only their gradient norms
         const int i = e - a.adam_count;
-        sq_reduce_body(a.adam.sq_slots + a.sqr_first[i], a.sqr_n[i], a.sq_total + a.sqr_dst[i]);
+        if (i < a.sqr_count) sq_reduce_body(a.adam.sq_slots + a.sqr_first[i], a.sqr_n[i], a.sq_total + a.sqr_dst[i]);
+        else step_close_body<false>(a.adam);                                              // the LAST rider (a.close) closes the step
       }
       return;
     }
@@ -833,7 +834,7 @@ int launch_bn_act_bwd(hipStream_t st, const BnBwdArgs& a_in) {
       set_error("bn_act_bwd: gradient front not applicable");
       return SMX_ERR_INVALID;
     }
-    const int grid = a.Hp / BN_COLS + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count;
+    const int grid = a.Hp / BN_COLS + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count + (a.close ? 1 : 0);
     size_t lds = ((size_t)a.B * (a.fK + 4) + (size_t)BN_COLS * (a.fK + 4)) * sizeof(float);
     if (a.fold_dz) {
       const EpiLatentBwd& e = a.zlb;
@@ -863,12 +864,12 @@ int launch_bn_act_bwd(hipStream_t st, const BnBwdArgs& a_in) {
   if (a.Hp % BN_COLS || a.B <= 0) { set_error("bn_act_bwd: bad shapes"); return SMX_ERR_INVALID; }
   if (a.wide) {
     if (a.B > 128 || a.Hp > 128 || !a.dout || a.slab_stride < (long)a.Hp * 128 || (a.slab_stride % 4)) { set_error("bn_act_bwd: wide slabs take at most 128 x 128"); return SMX_ERR_INVALID; }
-    if (gen) hipLaunchKernelGGL(bn_wide_bwd_gen_kernel, dim3(a.Hp + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count), dim3(BN_THREADS), 0, st, a);
-    else hipLaunchKernelGGL(bn_wide_bwd_kernel, dim3(a.Hp + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count), dim3(BN_THREADS), 0, st, a);
+    if (gen) hipLaunchKernelGGL(bn_wide_bwd_gen_kernel, dim3(a.Hp + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count + (a.close ? 1 : 0)), dim3(BN_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(bn_wide_bwd_kernel, dim3(a.Hp + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count + (a.close ? 1 : 0)), dim3(BN_THREADS), 0, st, a);
     SMX_HIP(hipGetLastError());
     return SMX_OK;
   }
-  const int grid = a.Hp / BN_COLS + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count;
+  const int grid = a.Hp / BN_COLS + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count + (a.close ? 1 : 0);
   if (gen) {
     if (a.B <= BN_RL * 2) hipLaunchKernelGGL(bn_act_bwd_gen_kernel<2>, dim3(grid), dim3(BN_THREADS), 0, st, a);
     else if (a.B <= BN_RL * 4) hipLaunchKernelGGL(bn_act_bwd_gen_kernel<4>, dim3(grid), dim3(BN_THREADS), 0, st, a);
@@ -898,7 +899,7 @@ int launch_bn_act_bwd_dual(hipStream_t st, const BnBwdArgs& a_in, const BnBwdArg
     set_error("bn_act_bwd_dual: gradient fronts not applicable");
     return SMX_ERR_INVALID;
   }
-  const int na = a.Hp / BN_COLS + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count;
+  const int na = a.Hp / BN_COLS + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count + (a.close ? 1 : 0);
   const int grid = na + b.Hp / BN_COLS;
   auto need = [](const BnBwdArgs& x) { return ((size_t)x.B * (x.fK + 4) + (size_t)BN_COLS * (x.fK + 4)) * sizeof(float); };
   const size_t lds = need(a) > need(b) ? need(a) : need(b);
@@ -1053,7 +1054,8 @@ __device__ inline void bn_wide_bwd_body(const BnBwdArgs& a, float* lds) {
       if (e < 0) metrics_body(a.metrics);
       else {
         const int i = e - a.adam_count;
-        sq_reduce_body(a.adam.sq_slots + a.sqr_first[i], a.sqr_n[i], a.sq_total + a.sqr_dst[i]);
+        if (i < a.sqr_count) sq_reduce_body(a.adam.sq_slots + a.sqr_first[i], a.sqr_n[i], a.sq_total + a.sqr_dst[i]);
+        else step_close_body<false>(a.adam);
       }
       return;
     }
@@ -1167,7 +1169,7 @@ int launch_bn_wide_bwd_dw(hipStream_t st, const BnBwdArgs& a, const HeadBwdArgs&
   h.skip_dd = 1; h.skip_dw = 0; h.diag = 0;
   { static const int dg = (int)tuning("head_bwd_diag", 0); if (dg) h.diag = dg; }   // (timing only: bit 1 = the dW tiles return at once)
   if (h.sq_count) *h.sq_count = h.n_ht * h.n_gt * 8;
-  const dim3 grid((unsigned)(a.Hp + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count + h.n_w));
+  const dim3 grid((unsigned)(a.Hp + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count + (a.close ? 1 : 0) + h.n_w));
   if (h.n_planes == 3) hipLaunchKernelGGL(bn_wide_bwd_dw_kernel<3>, grid, dim3(BN_THREADS), 0, st, a, h);
   else hipLaunchKernelGGL(bn_wide_bwd_dw_kernel<2>, grid, dim3(BN_THREADS), 0, st, a, h);
   SMX_HIP(hipGetLastError());

@@ -95,6 +95,7 @@ static int mlp_forward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps,
     const bool epi_act = m->flags.act_epilogue && !dual && !with_front && !sync && L.bn < 0 && !(ps.training && L.drop_p > 0.f) &&
                          g.split_k <= 1 && !m->use_injected && L.act == SMX_ACT_RELU;   // (other activations: the BatchNorm launch without BatchNorm)
     if (epi_act) {
+      if (i == 0 && in_is_x) SMX_CHECK(lazy_flush(m));   // (this product reads the layer's bias: nothing may ride on it)
       g.bias = P_(m, L.tBias); g.act = 1; g.leak = L.leak; g.C = L.out_buf; g.ldc = L.out_p; g.split_k = 1;
       Timed t(m, (i == 0 && in_is_x) ? o.label : "gemm_mlp_fwd");
       // a deep contraction (the discriminator's 1000-wide layers): the direct-operand bf16 x 3 form (smx_dgemm.hip)
@@ -119,6 +120,11 @@ static int mlp_forward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps,
         bk.colmajor = 1; bk.slab_stride = 128L * 128;
       }
     }
+    // the first product that reads X: the launch the lazy encoder update is built around (smx_step.hip).  Only the plain gathered form below
+    // can apply the step before's pending update; before any other form it goes as the ordinary optimiser launch.
+    const bool x_first = (i == 0 && in_is_x);
+    const bool x_plain = x_first && &mlp == &m->enc && !bigk && !dual && !with_front;
+    if (x_first && !x_plain) SMX_CHECK(lazy_flush(m));
     if (bigk) {
       Timed t(m, o.label);
       SMX_CHECK(launch_bigk(m->st, bk));
@@ -134,8 +140,19 @@ static int mlp_forward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps,
           (size_t)g.split_k * 128 * (size_t)L.out_p <= m->slab_cap && !tuning_on("xf_tile")) {
         g.c_colmajor = 1; g.slab_stride = 128L * L.out_p;
       }
+      // INVARIANT of the riding form: no workgroup of this launch writes anything a tile workgroup of this launch reads.  The tile workgroups
+      // read X, the row ids, W_enc, its gradient, both its moments, its sum-of-squares slots and the pending step's state; they update W_enc in
+      // registers and store slabs only.  The riders write parameters / moments / norms of every OTHER pending tensor -- none of them read here
+      // (the product takes no bias: g.bias is null whenever the layer is split or has BatchNorm, and the bias epilogue form is flushed above).
+      // W_enc's own chunks ride with the latent head's product (fwd_encoder), which reads neither W_enc nor its gradient; the gradient buffer is
+      // rewritten only by this step's weight-gradient launch, later in stream order.
+      GemmRide ride;
+      const bool riding = x_plain && g.bias == nullptr && lazy_ride_tile(m, g, ride);
+      if (x_first && !riding) SMX_CHECK(lazy_flush(m));
       Timed t(m, (i == 0 && in_is_x) ? o.label : "gemm_mlp_fwd");
-      SMX_CHECK(launch_gemm(m->st, g, &eff));
+      SMX_CHECK(launch_gemm(m->st, g, &eff, riding ? &ride : nullptr));
+      if (riding) m->lazy_rest_pending = false;
+      if (x_plain && ps.training && g.bias == nullptr && gemm_ride_tile_supported(g)) m->lazy_l1 = true;   // (the next step's product takes the same form)
     }
     BnFwdArgs b = make_bn(L, m->slab, eff, g.slab_stride);
     if (bigk && bk.colmajor) { b.pre = bk.part; b.n_slabs = bk.n_slices; b.slab_stride = bk.slab_stride; b.wide = 1; }
@@ -260,8 +277,18 @@ static int fwd_encoder(smx_model* m, const Pass& ps, FwdPass& f) {
   const MlpLayer& eL = m->enc.back();
   const int lat_ld = m->lat_planes * m->Dp;
   const GemmArgs g = dense_fwd({eL.out_buf, eL.out_p}, {P_(m, m->t_latW), m->tensors[m->t_latW].ld}, m->latbuf, lat_ld, P_(m, m->t_latb), ps.B, lat_ld, eL.out_p);
+  // W_enc's own chunks of the lazy encoder update (smx_step.hip): riders of this launch, which reads neither W_enc nor its gradient and leaves
+  // most of the chip idle -- unless the step before ran the decoder's BatchNorm-backward launch as the head's dW carrier (dw_late_now is still
+  // that step's, and this step takes the same form): that launch has rider slots and no riders, is longer than a chunk workgroup lives
+  // (this one is not: it grew from 4.6 to 7.3 us under the tracer with them) and precedes the weight gradients too -- the chunks wait for
+  // it (mlp_backward; knob lazy_w_fwd: here in any case)
+  const bool lazy_w_late = m->lazy_w_pending && !m->lazy_rest_pending && m->dw_late_now && !tuning_on("lazy_w_fwd");
+  GemmRide ride;
+  const bool riding = !lazy_w_late && lazy_ride_w(m, ride);
+  if (!riding && !lazy_w_late) SMX_CHECK(lazy_flush(m));
   Timed t(m, "gemm_lat_fwd");
-  SMX_CHECK(launch_gemm(m->st, g));
+  SMX_CHECK(launch_gemm(m->st, g, nullptr, riding ? &ride : nullptr));
+  if (riding) m->lazy_w_pending = false;
   return SMX_OK;
 }
 

@@ -68,8 +68,16 @@ struct GemmSmem {
   static constexpr int FLOATS = FLOATS0 > STORE ? FLOATS0 : STORE;
 };
 
-template <int WM, int WN, int WK, int A_KM, int B_NM, int XF, int EPI = 0>
-__device__ inline void gemm_body(const GemmArgs& g, const int bx, const int by, const int bz, float* smem) {
+// the device's part of GemmRide
+struct GemmRideDev { int n_tiles, gx, gy, count, skip_from, skip_len; long w_off; OptChunk w_chunk; int sq_cnt, sq_first, xcd_map; };   // (sq_*: the tensor's sum-of-squares slots, as AdamArgs holds them per tensor)
+
+// RIDE = 1 (gemm_ride_kernel's tile form; k-major B): B is a tensor of the flat parameter buffer with a pending optimiser update (*ad; rd->w_off,
+// rd->w_chunk) -- every quad of B is updated in registers on its way to LDS, from the matching quads of the gradient and both moments, and
+// nothing of it is stored (smx_step.hip: the lazy encoder update)
+template <int WM, int WN, int WK, int A_KM, int B_NM, int XF, int EPI = 0, int RIDE = 0>
+__device__ inline void gemm_body(const GemmArgs& g, const int bx, const int by, const int bz, float* smem, const AdamArgs* ad = nullptr,
+                                 const GemmRideDev* rd = nullptr) {
+  static_assert(!RIDE || (!B_NM && EPI == 0), "the riding tile form: k-major B, no epilogue");
   constexpr int BM = 32 * WM, BN = 32 * WN, BK = 32 * WK;
   constexpr int LDAS = A_KM ? BM + 4 : BM + 1;
   constexpr int LDBS = B_NM ? BN + 1 : BN + 4;
@@ -82,6 +90,11 @@ __device__ inline void gemm_body(const GemmArgs& g, const int bx, const int by, 
 
   preload(g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.M, g.N, g.K, g.k_chunk, g.slab_stride, g.bias, g.colsum, g.sq_part, g.act, g.c_colmajor);   // (one batch: smx_device.h)
   if (XF) preload(g.xf.rows, g.xf.log1p, g.xf.inj_mask, g.xf.drop_p, g.xf.cell_base, g.xf.drop_scale, g.xf.inj_ld, g.wide_store);
+  if constexpr (RIDE != 0) {   // what the update reads of its two argument structs, in the same way: one batch, not a wait per field where it is first used
+    preload(ad->grads, ad->m, ad->v, ad->state, ad->sq_slots, rd->w_off, rd->sq_cnt, rd->sq_first, ad->use_sq, ad->clipnorm, ad->grad_scale, ad->b1, ad->b2, ad->eps,
+            ad->tied_t0, ad->tied_t1);
+    preload(ad->tied_inv, rd->w_chunk.tensor, rd->w_chunk.first_chunk, ad->tensor_norm, g.M, g.N, g.K, g.ldb);
+  }
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wk = wave / (WM * WN), wm = (wave / WN) % WM, wn = wave % WN;
@@ -93,6 +106,11 @@ __device__ inline void gemm_body(const GemmArgs& g, const int bx, const int by, 
   float4 ra[NA], rb[NB];
   uint2 ra_h[NA];   // (XF == 2: the uint16 counts as loaded)
   int a_src[NA];    // gathered source row of the A piece (XF)
+  // RIDE: the gradient and both moments of the quads in rb, the tensor's clip factor and the pending step's step size
+  constexpr int NR = RIDE ? NB : 1;
+  smx_f32x4 r_g[NR], r_m[NR], r_v[NR];
+  float r_clip = 0.f, r_lr = 0.f;
+  if constexpr (RIDE != 0) r_lr = ad->state->lr_t;   // (the PENDING step's parity entry: smx_step.hip)
 
   // The A pieces of a tile are requested in two batches -- every row id, then every piece from a clamped address -- and transformed
   // (uint16 -> float, log1p, dropout) only when they go to LDS.  As a lane-predicated block per piece (row id -> piece -> log1p inside
@@ -128,6 +146,15 @@ __device__ inline void gemm_body(const GemmArgs& g, const int bx, const int by, 
         const int nr = f / (BK / 4), kq = f % (BK / 4);
         const int n = n0 + nr, k = k0 + kq * 4;
         if (k < k_end) v = *reinterpret_cast<const float4*>(g.B + (long)n * g.ldb + k);
+      } else if constexpr (RIDE != 0) {
+        // the quad and, at the same element offset of the flat buffers, its gradient and moments: one batch of unconditional loads from a
+        // clamped row (rows >= k_end are zeroed behind the update, in store_tiles)
+        const int kr = f / (BN / 4), nq = f % (BN / 4);
+        const long off = (long)min(k0 + kr, k_end - 1) * g.ldb + n0 + nq * 4;
+        v = *reinterpret_cast<const float4*>(g.B + off);
+        r_g[j] = *reinterpret_cast<const smx_f32x4*>(ad->grads + rd->w_off + off);
+        r_m[j] = *reinterpret_cast<const smx_f32x4*>(ad->m + rd->w_off + off);
+        r_v[j] = *reinterpret_cast<const smx_f32x4*>(ad->v + rd->w_off + off);
       } else {
         const int kr = f / (BN / 4), nq = f % (BN / 4);
         const int k = k0 + kr, n = n0 + nq * 4;
@@ -171,6 +198,11 @@ __device__ inline void gemm_body(const GemmArgs& g, const int bx, const int by, 
         Bs[(kq * 4 + 3) * LDBS + nr] = rb[j].w;
       } else {
         const int kr = f / (BN / 4), nq = f % (BN / 4);
+        if constexpr (RIDE != 0) {   // the pending update of this quad: the optimiser's own function, so the same bits as its launch writes
+          smx_f32x4 p = {rb[j].x, rb[j].y, rb[j].z, rb[j].w};
+          adam_apply4(*ad, r_clip, r_lr, r_g[j], r_m[j], r_v[j], p);
+          rb[j] = (k0 + kr < k_end) ? make_float4(p[0], p[1], p[2], p[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
         *reinterpret_cast<float4*>(&Bs[kr * LDBS + nq * 4]) = rb[j];
       }
     }
@@ -228,6 +260,9 @@ __device__ inline void gemm_body(const GemmArgs& g, const int bx, const int by, 
   const bool do_colsum = (g.colsum != nullptr) && (bx == 0) && (tid < BN);
 
   if (k_begin < k_end) load_tiles(k_begin);
+  // RIDE: the tensor's clip factor, its slot loads issued behind the tile's (all of them in flight together; chunk -1: the norm itself is
+  // written by the rider that owns the tensor's first chunk).  Every thread of the workgroup, whatever its slab holds: two barriers inside.
+  if constexpr (RIDE != 0) r_clip = adam_tensor_clip_at<256>(*ad, rd->w_chunk, -1, rd->sq_cnt, rd->sq_first);
   for (int k0 = k_begin; k0 < k_end; k0 += BK) {
     store_tiles(k0);
     __syncthreads();
@@ -407,6 +442,31 @@ __global__ __launch_bounds__(256) void gemm_latent_bwd_ride_kernel(GemmArgs g, A
   gemm_body<1, 1, 4, 0, 1, 0, 2>(g, blockIdx.x, blockIdx.y, blockIdx.z, smem);
 }
 
+// a forward product carrying optimiser work of the step before (GemmRide; smx_step.hip: the lazy encoder update).  A FLAT grid: the product's
+// tile workgroups first, in the order of the plain launch's (x, y, z) grid -- the chain waits for them, so they are dispatched first -- then
+// r.count riders that each apply one pending chunk in place.  TILE: the tile workgroups update their block of B in registers (gemm_body's
+// RIDE form).  No workgroup waits for another: what a rider writes, no tile workgroup of the launch reads (the launch sites say why).
+template <int WM, int WN, int WK, int XF, int TILE>
+__global__ __launch_bounds__(256) void gemm_ride_kernel(GemmArgs g, AdamArgs a, GemmRideDev r) {
+  __shared__ __attribute__((aligned(16))) float smem[GemmSmem<WM, WN, WK, 0, 0>::FLOATS];
+  const int id = (int)blockIdx.x;
+  if (id >= r.n_tiles) {   // (block-uniform)
+    int li = id - r.n_tiles;
+    if (li >= r.skip_from) li += r.skip_len;
+    adam_chunk_body<256>(a, li >= a.gap_from ? li + a.gap_len : li);   // (launch index -> chunk: as adam_update_kernel)
+    return;
+  }
+  int bx = id % r.gx, by = (id / r.gx) % r.gy, bz = id / (r.gx * r.gy);
+  if (TILE && r.xcd_map) {
+    // the gx workgroups that share a block of B -- and now its gradient and both moments: four times the bytes -- 8 flat indices apart, i.e. on ONE
+    // XCD under the round-robin dispatch, so that the block crosses the fabric once and its other readers hit that XCD's L2 (in the plain order
+    // they sit on gx different XCDs: the launch measured 8.7 us against the plain product's 5.2).  Which workgroup forms which tile changes no bit.
+    const int xcd = id & 7, idx = id >> 3, q = (idx / r.gx) * 8 + xcd;   // (host: gy * gz is a multiple of 8)
+    bx = idx % r.gx; by = q % r.gy; bz = q / r.gy;
+  }
+  gemm_body<WM, WN, WK, 0, 0, XF, 0, TILE>(g, bx, by, bz, smem, &a, &r);
+}
+
 // ---------------------------------------------------------------------------
 // Grouped launch: several independent products share one grid, so the narrow ones fill the CUs
 // the wide one leaves idle and a whole kernel boundary disappears.  Tiles 128x32 and 32x32(K4).
@@ -450,7 +510,7 @@ __global__ __launch_bounds__(256) void gemm_group_kernel(GemmGroup G) {
 }
 
 template <int WM, int WN, int WK>
-static int launch_cfg(hipStream_t st, GemmArgs g, int* eff_split) {
+static int launch_cfg(hipStream_t st, GemmArgs g, int* eff_split, const GemmRide* ride = nullptr) {
   constexpr int BM = 32 * WM, BN = 32 * WN, BK = 32 * WK;
   g.k_chunk = round_up((g.K + g.split_k - 1) / g.split_k, BK);
   g.split_k = (g.K + g.k_chunk - 1) / g.k_chunk;  // drop empty slices
@@ -467,6 +527,32 @@ static int launch_cfg(hipStream_t st, GemmArgs g, int* eff_split) {
     if (g.sq_count) *g.sq_count = (int)(grid.x * grid.y) * 4;
   }
   const int mode = (g.a_kmajor ? 2 : 0) | (g.b_nmajor ? 1 : 0);
+  if (ride) {   // optimiser work of the step before rides along: gemm_ride_kernel's flat grid
+    constexpr bool K4 = (WM == 1 && WN == 1 && WK == 4);
+    if (mode != 0 || !ride->adam || ride->count < 0 || (ride->tile ? !(K4 && g.use_xform) : g.use_xform != 0)) {
+      set_error("gemm: this product cannot carry optimiser riders"); return SMX_ERR_INVALID;
+    }
+    GemmRideDev r;
+    r.n_tiles = (int)(grid.x * grid.y * grid.z); r.gx = (int)grid.x; r.gy = (int)grid.y;
+    r.count = ride->count; r.skip_from = ride->skip_from; r.skip_len = ride->skip_len; r.w_off = ride->w_off; r.w_chunk = ride->w_chunk;
+    r.sq_cnt = r.sq_first = 0;
+    r.xcd_map = (ride->tile && (grid.y * grid.z) % 8 == 0 && !tuning_on("lazy_no_xcd_map")) ? 1 : 0;
+    if (ride->tile) {
+      const int t = ride->w_chunk.tensor;
+      if (t < 0 || t >= SMX_MAX_TENSORS || !ride->adam->use_sq) { set_error("gemm: the riding tile form needs the tensor's sum-of-squares slots"); return SMX_ERR_INVALID; }
+      r.sq_cnt = ride->adam->sq_count[t]; r.sq_first = ride->adam->sq_first[t];
+    }
+    const dim3 flat((unsigned)(r.n_tiles + r.count));
+    if constexpr (K4) {
+      if (ride->tile && g.xf.u16) hipLaunchKernelGGL((gemm_ride_kernel<1, 1, 4, 2, 1>), flat, block, 0, st, g, *ride->adam, r);
+      else if (ride->tile) hipLaunchKernelGGL((gemm_ride_kernel<1, 1, 4, 1, 1>), flat, block, 0, st, g, *ride->adam, r);
+      else hipLaunchKernelGGL((gemm_ride_kernel<1, 1, 4, 0, 0>), flat, block, 0, st, g, *ride->adam, r);
+    } else {
+      hipLaunchKernelGGL((gemm_ride_kernel<WM, WN, WK, 0, 0>), flat, block, 0, st, g, *ride->adam, r);
+    }
+    SMX_HIP(hipGetLastError());
+    return SMX_OK;
+  }
   if (g.use_xform && g.xf.u16) {
     if (mode == 0) hipLaunchKernelGGL((gemm_kernel<WM, WN, WK, 0, 0, 2>), grid, block, 0, st, g);
     else if (mode == 2) hipLaunchKernelGGL((gemm_kernel<WM, WN, WK, 1, 0, 2>), grid, block, 0, st, g);
@@ -633,7 +719,13 @@ int launch_gemm_dual(hipStream_t st, const GemmArgs& g1_in, const GemmArgs& g2_i
   return SMX_OK;
 }
 
-int launch_gemm(hipStream_t st, const GemmArgs& g_in, int* eff_split) {
+// launch_gemm's choice for g is the gathered 32 x 32 K4 product with k-major operands: what GemmRide::tile needs
+bool gemm_ride_tile_supported(const GemmArgs& g) {
+  static const int xf_tile = (int)tuning("xf_tile", 0);
+  return g.use_xform && !g.a_kmajor && !g.b_nmajor && g.epi == 0 && !xf_tile && (g.tile == TILE_AUTO || g.tile == TILE_32x32_K4) && g.N % 32 == 0 && g.ldb % 4 == 0;
+}
+
+int launch_gemm(hipStream_t st, const GemmArgs& g_in, int* eff_split, const GemmRide* ride) {
   GemmArgs g = g_in;
   int rc = validate_gemm(g);
   if (rc != SMX_OK) return rc;
@@ -654,11 +746,11 @@ int launch_gemm(hipStream_t st, const GemmArgs& g_in, int* eff_split) {
     return SMX_ERR_INVALID;
   }
   switch (tile) {
-    case TILE_128x32: return launch_cfg<4, 1, 1>(st, g, eff_split);
-    case TILE_64x64: return launch_cfg<2, 2, 1>(st, g, eff_split);
-    case TILE_32x128: return launch_cfg<1, 4, 1>(st, g, eff_split);
-    case TILE_32x32_K4: return launch_cfg<1, 1, 4>(st, g, eff_split);
-    case TILE_64x32_K2: return launch_cfg<2, 1, 2>(st, g, eff_split);
+    case TILE_128x32: return launch_cfg<4, 1, 1>(st, g, eff_split, ride);
+    case TILE_64x64: return launch_cfg<2, 2, 1>(st, g, eff_split, ride);
+    case TILE_32x128: return launch_cfg<1, 4, 1>(st, g, eff_split, ride);
+    case TILE_32x32_K4: return launch_cfg<1, 1, 4>(st, g, eff_split, ride);
+    case TILE_64x32_K2: return launch_cfg<2, 1, 2>(st, g, eff_split, ride);
     default: set_error("gemm: unknown tile configuration"); return SMX_ERR_INVALID;
   }
 }

@@ -95,7 +95,9 @@ struct GemmArgs {
 double tuning(const char* name, double dflt);
 unsigned long long tuning_epoch();   // moves on with every smx_set_tuning / smx_clear_tuning
 inline bool tuning_on(const char* name) { return tuning(name, 0.0) != 0.0; }
-int launch_gemm(hipStream_t st, const GemmArgs& g, int* eff_split = nullptr);
+struct GemmRide;   // (below, behind AdamArgs) optimiser work of the step before riding on a forward product
+bool gemm_ride_tile_supported(const GemmArgs& g);   // launch_gemm would run g as the gathered 32 x 32 K4 product that GemmRide::tile needs
+int launch_gemm(hipStream_t st, const GemmArgs& g, int* eff_split = nullptr, const GemmRide* ride = nullptr);
 // Several independent products in ONE launch (tiles 128x32 / 32x32-K4 only); eff_splits[i] receives
 // the slab count of problem i.
 #define SMX_GROUP_MAX 8
@@ -307,6 +309,16 @@ struct AdamArgs {
   float momentum = 0.f; uint32_t t0 = 0;
 };
 int launch_adam(hipStream_t st, const AdamArgs& a);
+// Optimiser work of the step BEFORE riding on a forward product of this one (smx_step.hip: the lazy encoder update).  `count` trailing
+// workgroups each apply one chunk of *adam (a HOST pointer, copied into the launch): rider r takes launch index r (+ skip_len from skip_from
+// on), mapped through adam->gap_from / gap_len as the optimiser launch maps its own.  tile != 0 (the gathered 32 x 32 K4 first-layer product
+// only): the tile workgroups also update their block of B -- the tensor at float w_off of the flat buffers, whose chunk entry is w_chunk -- in
+// REGISTERS while staging it, and store nothing of it.
+struct GemmRide {
+  const AdamArgs* adam = nullptr;
+  int count = 0, skip_from = 0, skip_len = 0;
+  int tile = 0; long w_off = 0; OptChunk w_chunk{};
+};
 int launch_adam_sweep(hipStream_t st, const AdamArgs& a, int first, int count, int wgs);   // chunks [first, first + count) by `wgs` persistent workgroups
 int launch_grad_sqsum_range(hipStream_t st, const AdamArgs& a, int first, int count);   // a.partial[chunk] = the chunk's sum of squares, chunks [first, first + count)
 int opt_resolve(int rule, const float* hp, int n_hp, const float* adam_hp, float out[4]);   // smx_set_optimizer's hyper-parameters, defaults filled in
@@ -327,6 +339,8 @@ struct BnBwdArgs {
   // single GPU: the output / label heads' gradients are final before this launch, and this launch leaves most CUs
   // idle -- adam_count extra workgroups apply the optimiser to chunks [adam_first, adam_first + adam_count)
   AdamArgs adam; int adam_first = 0, adam_count = 0;
+  // ... and one more that closes the step in the optimiser launch's stead (adam.master, .next_state, ...: smx_adam.h: step_close_body), behind the others
+  int close = 0;
   // ... or, when that update is too large to ride along, sqr_count workgroups that only sum sum-of-squares slots:
   // rider i leaves the sum of sq_slots[sqr_first[i] .. + sqr_n[i]) in sq_total[sqr_dst[i]] (up to SMX_SQR_PER_TENSOR
   // riders per tensor; the optimiser's workgroups then read that many numbers instead of every slot)

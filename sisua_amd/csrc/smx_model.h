@@ -265,6 +265,16 @@ struct smx_model {
   int par = 0; uint32_t h_next = 0;
   MetricsArgs pending_metrics; bool have_pending_metrics = false, metrics_before_allreduce = false;
   int seq_batch = 0, seq_prepare_next = 0;
+  // the lazy encoder update (smx_step.hip): a step of an eager train_steps call that is not the call's last leaves its optimiser launch out;
+  // the NEXT step's first launch -- the gathered encoder product -- updates its block of W_enc in registers and carries the other chunks as
+  // riders, and a later forward launch carries W_enc's own chunks.  Never outlives a library call (the last step keeps the launch).
+  bool lazy_want = false;        // this step: the predicate holds so far (train_sequence)
+  bool lazy_l1 = false;          // this step's first launch took the form the next step's update needs (mlp_forward)
+  bool lazy_closed = false;      // this step: the ELBO scalars and the step's close rode with a BatchNorm-backward launch (mlp_backward)
+  bool lazy_rest_pending = false, lazy_w_pending = false;   // the step before: every chunk but W_enc's / W_enc's chunks still to apply
+  AdamArgs lazy_args;            // ... with these arguments (state: THAT step's parity entry of state3)
+  int lazy_w_first = 0, lazy_w_n = 0;   // W_enc's chunks as indices of the optimiser LAUNCH (before its gap)
+  int32_t lazy_steps = 0;        // steps of the last smx_train_steps call that left their optimiser launch out (smx_lazy_adam_steps)
   // this pass's first encoder BatchNorm launch has drawn, on otherwise idle CUs, what the decoder's front launch would
   // draw redundantly in each of its workgroups: eps of the latent sample (-> noise_eps) / the dropout multipliers of
   // the first decoder layer (-> dec[0].noise)
@@ -552,6 +562,12 @@ int head_sweep_join(smx_model* m);
 int dp_chain_start(smx_model* m);
 // smx_step.hip
 void fill_adam_args(smx_model* m, AdamArgs& a);
+void fill_step_close(smx_model* m, AdamArgs& a);   // what the step's closing workgroup reads (step_close_body), from the step in flight
+// the lazy encoder update (smx_step.hip)
+bool lazy_adam_wanted(smx_model* m, bool prepare_next);   // the predicate, as far as it is known when the step's launch sequence begins
+int lazy_flush(smx_model* m);                             // whatever is still pending, as the ordinary optimiser launch
+bool lazy_ride_tile(smx_model* m, const GemmArgs& g, GemmRide& r);   // the first launch's riders + tile update, if g is W_enc's gathered product
+bool lazy_ride_w(smx_model* m, GemmRide& r);                         // W_enc's own chunks as riders of a later forward product
 int optimizer_pass(smx_model* m);
 int csr_stage(smx_model* m, Pass& ps);
 int check_rows(smx_model* m, const int32_t* ids, size_t n);

@@ -925,5 +925,6 @@ int64_t smx_head_fused_bytes(const smx_model* m, int32_t batch) {
 }
 
 int32_t smx_head_dw_late(const smx_model* m) { return (m && m->dw_late_now) ? 1 : 0; }   // (smx_backward.hip: dw_late)
+int32_t smx_lazy_adam_steps(const smx_model* m) { return m ? m->lazy_steps : 0; }          // (smx_step.hip: the lazy encoder update)
 
 }  // extern "C"

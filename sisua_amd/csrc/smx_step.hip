@@ -35,6 +35,85 @@ void fill_adam_args(smx_model* m, AdamArgs& a) {
   }
 }
 
+void fill_step_close(smx_model* m, AdamArgs& a) {
+  a.state = cur_state(m);
+  a.master = master_state(m); a.sched = m->sched_tab; a.batch = m->seq_batch;
+  if (dp_active(m)) { a.hist_dp = m->mhist; a.tail_metrics = m->grads + m->tail_off_metrics; }
+  a.prepare_next = m->seq_prepare_next;
+  if (a.prepare_next) { a.next_state = m->state3 + (m->par ^ 1); a.next_rows = m->rows2[m->par ^ 1]; a.order = m->order; }
+}
+
+// ---- the lazy encoder update ----
+// The optimiser launch is the last of the step's ten dependent launches, and between two steps of one train_steps call only ONE launch needs its
+// largest tensor soon: the next step's first, the gathered encoder product, which loads exactly W_enc.  A step that is not the call's last therefore
+// leaves the launch out (lazy_adam_wanted + what mlp_forward / mlp_backward report of the step); the next step's forward pass applies it:
+//   launch 1 (gemm_ride_kernel, tile form): every tile workgroup updates its block of W_enc in REGISTERS while staging it (adam_apply4 on the
+//            quads it loads anyway, beside the matching quads of the gradient and both moments; nothing of them stored); trailing workgroups
+//            apply every pending chunk but W_enc's in place -- tensors first read by launches 2..5;
+//   a later forward product that reads neither W_enc nor its gradient (the latent head's) carries W_enc's own chunks in place.
+// The same function calls as the optimiser launch (adam_tensor_clip<256>, adam_apply4, adam_chunk_body<256>): every result bit for bit.
+// Knob no_lazy_adam; smx_lazy_adam_steps counts the steps that took the form.
+bool lazy_adam_wanted(smx_model* m, bool prepare_next) {
+  if (!prepare_next || m->capturing || tuning_on("no_lazy_adam")) return false;
+  if (m->comm || m->local || m->p2p || dp_active(m) || m->sync_bn || m->flags.opt_shard) return false;   // one GPU
+  if (!m->timing_label.empty() || m->use_injected) return false;   // (per-kernel timings keep the unfolded path)
+  if (m->opt_rule != SMX_OPT_ADAM) return false;                  // the riders carry Adam only
+  if (m->scvi || m->fvae || m->enc.empty()) return false;         // ONE encoder reads X, once per step
+  if (!m->sq_slots || tuning_on("no_sq_partials")) return false;
+  return true;
+}
+
+// W_enc's chunks in the table (smx_model.hip builds it tensor by tensor, SMX chunks_floats floats each)
+static void lazy_w_chunks(const smx_model* m, int* first, int* n) {
+  const int tW = m->enc[0].tW;
+  int f = 0;
+  for (int t = 0; t < tW; ++t) f += (int)((m->tensors[t].count + m->chunks_floats - 1) / m->chunks_floats);
+  *first = f; *n = (int)((m->tensors[tW].count + m->chunks_floats - 1) / m->chunks_floats);
+}
+
+// the step's optimiser launch as `a` describes it: left to the next step?  (the last gate: everything of the predicate that only the step's
+// own launches could tell)
+static bool lazy_defer(smx_model* m, const AdamArgs& a) {
+  if (!m->lazy_want || !m->lazy_l1 || !m->lazy_closed || m->have_pending_metrics || !a.use_sq || a.form != OPT_ADAM || !a.prepare_next) return false;
+  int wf, wn;
+  lazy_w_chunks(m, &wf, &wn);
+  if (wn <= 0 || wf + wn > a.gap_from) return false;   // (W_enc's chunks before the heads' gap: launch index == chunk index)
+  m->lazy_args = a;
+  m->lazy_args.master = nullptr; m->lazy_args.with_metrics = 0;   // (both rode with the encoder's BatchNorm-backward launch)
+  m->lazy_w_first = wf; m->lazy_w_n = wn;
+  m->lazy_rest_pending = m->lazy_w_pending = true;
+  ++m->lazy_steps;
+  return true;
+}
+
+int lazy_flush(smx_model* m) {
+  if (!m->lazy_rest_pending && !m->lazy_w_pending) return SMX_OK;
+  AdamArgs a = m->lazy_args;
+  if (!m->lazy_rest_pending) { a.gap_from = 0; a.gap_len = m->lazy_w_first; a.n_launch = m->lazy_w_n; }   // W_enc's chunks alone
+  m->lazy_rest_pending = m->lazy_w_pending = false;
+  return launch_adam(m->st, a);
+}
+
+bool lazy_ride_tile(smx_model* m, const GemmArgs& g, GemmRide& r) {
+  if (!m->lazy_rest_pending || !m->lazy_w_pending || m->capturing) return false;
+  const TensorInfo& tw = m->tensors[m->enc[0].tW];
+  if (g.B != m->params + tw.offset || g.ldb != (int)tw.ld || (size_t)g.K * (size_t)g.ldb > tw.count || g.N > g.ldb || !gemm_ride_tile_supported(g)) return false;   // (the tile's quads lie inside the tensor)
+  r.adam = &m->lazy_args;
+  r.count = m->lazy_args.n_launch - m->lazy_w_n; r.skip_from = m->lazy_w_first; r.skip_len = m->lazy_w_n;
+  r.tile = 1; r.w_off = (long)tw.offset;
+  memset(&r.w_chunk, 0, sizeof(r.w_chunk));
+  r.w_chunk.tensor = m->enc[0].tW; r.w_chunk.offset = (int32_t)tw.offset; r.w_chunk.count = (int32_t)std::min<size_t>(tw.count, (size_t)m->chunks_floats);
+  r.w_chunk.first_chunk = m->lazy_w_first; r.w_chunk.n_chunks = m->lazy_w_n; r.w_chunk.tensor_count = (int32_t)tw.count;
+  return true;   // (the caller clears lazy_rest_pending once the launch is out)
+}
+
+bool lazy_ride_w(smx_model* m, GemmRide& r) {
+  if (m->lazy_rest_pending || !m->lazy_w_pending || m->capturing) return false;
+  r.adam = &m->lazy_args;
+  r.count = m->lazy_w_n; r.skip_from = 0; r.skip_len = m->lazy_w_first; r.tile = 0;
+  return true;   // (the caller clears lazy_w_pending once the launch is out)
+}
+
 int optimizer_pass(smx_model* m) {
   const smx_config& c = m->cfg;
   if (dp_active(m) && m->have_pending_metrics) {   // no BatchNorm-backward launch took them along
@@ -83,10 +162,9 @@ int optimizer_pass(smx_model* m) {
   }
   m->adam_early_from = -1;
   if (m->have_pending_metrics) { a.metrics = m->pending_metrics; a.with_metrics = 1; m->have_pending_metrics = false; }
-  a.master = master_state(m); a.sched = m->sched_tab; a.batch = m->seq_batch;
-  if (dp_active(m)) { a.hist_dp = m->mhist; a.tail_metrics = m->grads + m->tail_off_metrics; }
-  a.prepare_next = m->seq_prepare_next;
-  if (a.prepare_next) { a.next_state = m->state3 + (m->par ^ 1); a.next_rows = m->rows2[m->par ^ 1]; a.order = m->order; }
+  fill_step_close(m, a);
+  if (m->lazy_closed) a.master = nullptr;   // (a rider of the encoder's BatchNorm-backward launch has closed the step)
+  if (lazy_defer(m, a)) return SMX_OK;      // the next step's forward launches apply it (the lazy encoder update, above)
   Timed t(m, "adam");
   SMX_CHECK(launch_adam(m->st, a));
   return SMX_OK;
@@ -113,6 +191,7 @@ int train_sequence(smx_model* m, int B, bool with_begin, bool begin_from_master,
   ps.cell_base = (uint32_t)m->cell_base; ps.training = 1; ps.sample = 0; ps.global_batch = B * m->world;
   ps.draw_rows = m->train_draws > 1 ? B / m->train_draws : 0;   // (B: the stacked rows, draws x cells)
   m->seq_batch = B; m->seq_prepare_next = prepare_next ? 1 : 0;
+  m->lazy_want = lazy_adam_wanted(m, prepare_next); m->lazy_l1 = false; m->lazy_closed = false;
   Timed t(m, "step");
   if (with_begin) {
     AdamArgs o;
@@ -258,7 +337,11 @@ int launch_train(smx_model* m, int B, bool use_graph, int s_idx, int n_steps) {
     // other parity's state + row ids, so a step is not fronted by a 1-workgroup latency kernel
     const bool first = (s_idx == 0), last = (s_idx == n_steps - 1);
     if (first) m->par = 0; else m->par ^= 1;
-    SMX_CHECK(train_sequence(m, B, first, false, (uint32_t)s_idx, !last));
+    const int rc = train_sequence(m, B, first, false, (uint32_t)s_idx, !last);
+    if (rc != SMX_OK) {   // an update of the step before still pending: as the ordinary launch, before the error goes up
+      (void)lazy_flush(m);
+      return rc;
+    }
   }
   m->h_next += 1;
   return SMX_OK;
@@ -404,7 +487,9 @@ int smx_train_steps(smx_model* m, const int32_t* order, int32_t n_steps, int32_t
   int rc = SMX_OK;
   ++m->params_epoch;   // (the parameters are about to change)
   smx::DrawCaps caps(m);
+  m->lazy_steps = 0;
   for (int s = 0; s < n_steps && rc == SMX_OK; ++s) rc = launch_train(m, batch * m->train_draws, use_graph != 0, s, n_steps);
+  { const int rf = smx::lazy_flush(m); if (rc == SMX_OK) rc = rf; }   // (nothing is pending here: the call's last step keeps its optimiser launch)
   { const int rj = smx::head_sweep_join(m); if (rc == SMX_OK) rc = rj; }   // every other entry point sees one stream
   if (rc != SMX_OK) return rc;
   if (m->use_injected) { m->use_injected = false; }
