@@ -18,6 +18,7 @@
 // never the smallest, so a NaN cell is assigned to centre 0.
 #include "smx_model.h"
 #include "smx_dist.h"   // sqdist, stage_rows, load_cell, nan_if_inf: shared with smx_knn.hip
+#include "smx_block.h"  // the fixed-order column sum
 
 #include <algorithm>
 #include <cmath>
@@ -158,16 +159,11 @@ __global__ __launch_bounds__(SMX_CL_TILE) void kmeans_update_kernel(UpdateArgs a
   }
 }
 
-// inertia[r] = the sum of mind2 [r][N]: per-thread strided partials, the lanes of a wave by halving, then the four waves
+// inertia[r] = the sum of mind2 [r][N] in the fixed order of smx_block.h's column sum
 __global__ __launch_bounds__(SMX_CL_TILE) void kmeans_inertia_kernel(const double* mind2, long N, double* inertia) {
   __shared__ double sh4[4];
-  const double* x = mind2 + (long)blockIdx.x * N;
-  double v = 0.0;
-  for (long i = threadIdx.x; i < N; i += SMX_CL_TILE) v += x[i];
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) inertia[blockIdx.x] = (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
+  const double total = halving_column_sum(mind2 + (long)blockIdx.x * N, N, sh4);
+  if (threadIdx.x == 0) inertia[blockIdx.x] = total;
 }
 
 // slices of the j range: enough workgroups for the machine at small N, one slice once the tiles of i alone fill it -- a function of N alone

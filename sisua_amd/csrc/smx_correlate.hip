@@ -4,30 +4,21 @@
 //                      32 x 32 LDS tile (reads coalesced along the genes, writes along the cells): a gene's N values are contiguous and do
 //                      not depend on the batch size or the chunking.
 //   column ranks       one workgroup per gene: rank2[i] = 2 x (average rank of cell i), an int32 in 2 .. 2N.  The float32 pattern maps to an
-//                      order-preserving unsigned key (-0 as +0); the cell indices go through a stable LSD radix sort, four 8-bit passes over
-//                      two ping-pong index arrays in global memory (4 N bytes each: cache-resident; the key is looked up from the column).
-//                      Each of the four waves owns a contiguous quarter of the positions: its digit counts are its own LDS histogram, the
-//                      offsets come from one scan over (digit, wave), and inside a tile of 64 the order among equal digits is a ballot -- no
-//                      workgroup barrier inside a pass.  Then the tie runs: a max-scan of the run heads gives every position its run's start,
-//                      the run's tail stores its end at the start, and rank2 = start + end + 2.  One form for every N <= 2^20.
+//                      order-preserving unsigned key (-0 as +0); the cell indices go through smx_block.h's stable radix sort, four 8-bit
+//                      passes (the key is looked up from the column), then through its tie-run pass: every position gets its run's start,
+//                      the run's end is stored at the start, and rank2 = start + end + 2.  One form for every N <= 2^20.
 //   column sums        one workgroup per gene reads the column and its ranks and, for every protein, accumulates
 //                      Spearman: Sa = sum a, Saa = sum a a, Sab[p] = sum a b_p in 64-bit integers (a, b_p doubled average ranks: 4 N^3 < 2^63
 //                      at N = 2^20), exact in any order;
 //                      Pearson: the mean, then Sxx = sum (x - mean)^2 and Sxy[p] = sum (x - mean) yhat_p in float64 FMAs -- per-thread strided
-//                      partials, then the lanes of a wave by halving, then the four waves: an order that is a function of N alone.
+//                      partials, then smx_block.h's fixed-order block sum: an order that is a function of N alone.
 //                      The proteins pass through registers four at a time, so any P works.
 // No float atomics; every loop is bounded by N or P.  The ranks are a pure function of the column, the integer sums of the ranks, and the
 // float64 sums of the column and N: nothing depends on the batch size, the chunking of the walk or the gene chunk.
 #include "smx_model.h"
+#include "smx_block.h"   // the radix sort, the tie-run pass, the keys and the fixed-order sums
 
 namespace smx {
-
-// order-preserving key of a float32: negative values below positive ones, -0 as +0
-__device__ inline unsigned order_key(float v) {
-  unsigned u = __float_as_uint(v);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 __global__ __launch_bounds__(256) void keep_cols_kernel(const float* src, long ld, int rows, const int32_t* idx, int n_sel, float* dst, long N,
                                                         long c0) {
@@ -42,120 +33,25 @@ __global__ __launch_bounds__(256) void keep_cols_kernel(const float* src, long l
     if (j0 + k < n_sel && r0 + tx < rows) dst[(long)(j0 + k) * N + c0 + r0 + tx] = tile[tx][k];
 }
 
-// what a wave wrote to its own LDS words is read back by its other lanes (the project's idiom: smx_loss.h)
-__device__ inline void wave_lds_sync() { __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_wave_barrier(); }
-
-struct RankShared { unsigned hist[4][256]; unsigned wtot[4]; };
-
 __global__ __launch_bounds__(256) void col_rank2_kernel(const float* cols, int N, unsigned* sortA, unsigned* sortB, int32_t* rank2,
                                                         int32_t* nonfinite) {
-  __shared__ RankShared sh;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  __shared__ SortShared sh;
+  const int tid = threadIdx.x;
   const long base = (long)blockIdx.x * N;
   const float* x = cols + base;
   unsigned* A = sortA + base;
-  unsigned* B = sortB + base;
   int32_t* rk = rank2 + base;
-  const int seg = (N + 255) / 256 * 64;   // wave w owns the positions [p0, p1): whole tiles of 64, in order
-  const int p0 = min(N, w * seg), p1 = min(N, p0 + seg);
   int bad = 0;
-  // ---- the cell indices sorted by key, stable: pass 0 reads the identity and writes A, then A -> B -> A -> B ----
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 8 * pass;
-    const unsigned* src = pass == 0 ? nullptr : (pass & 1) ? A : B;
-    unsigned* dst = (pass & 1) ? B : A;
-    for (int i = tid; i < 1024; i += 256) (&sh.hist[0][0])[i] = 0;
-    __syncthreads();
-    for (int p = p0 + lane; p < p1; p += 64) {
-      const float v = x[src ? src[p] : (unsigned)p];
-      if (pass == 0) bad |= (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u;
-      atomicAdd(&sh.hist[w][(order_key(v) >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    {   // thread = digit: where each wave's entries of the digit go = entries of smaller digits + those of earlier waves
-      const unsigned h0 = sh.hist[0][tid], h1 = sh.hist[1][tid], h2 = sh.hist[2][tid], h3 = sh.hist[3][tid];
-      const unsigned tot = h0 + h1 + h2 + h3;
-      unsigned inc = tot;
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-      }
-      if (lane == 63) sh.wtot[w] = inc;
-      __syncthreads();
-      unsigned exc = inc - tot;
-      for (int q = 0; q < w; ++q) exc += sh.wtot[q];
-      sh.hist[0][tid] = exc; sh.hist[1][tid] = exc + h0; sh.hist[2][tid] = exc + h0 + h1; sh.hist[3][tid] = exc + h0 + h1 + h2;
-    }
-    __syncthreads();
-    for (int p = p0; p < p1; p += 64) {   // (wave-uniform bounds: every lane takes part in the ballots)
-      const bool on = p + lane < p1;
-      unsigned i = 0, d = 0;
-      if (on) {
-        i = src ? src[p + lane] : (unsigned)(p + lane);
-        d = (order_key(x[i]) >> shift) & 255u;
-      }
-      unsigned long long peers = __ballot(on);   // the tile's lanes with this lane's digit
-      for (int b = 0; b < 8; ++b) {
-        const bool bit = (d >> b) & 1u;
-        const unsigned long long mb = __ballot(bit);
-        peers &= bit ? mb : ~mb;
-      }
-      const unsigned before = (unsigned)__popcll(peers & ((1ull << lane) - 1ull));
-      unsigned o = 0;
-      if (on) {
-        o = sh.hist[w][d];
-        dst[o + before] = i;
-      }
-      wave_lds_sync();
-      if (on && before == 0) sh.hist[w][d] = o + (unsigned)__popcll(peers);
-      wave_lds_sync();
-    }
-    __syncthreads();   // (the pass's stores are drained: the next pass reads them through the CU's own cache)
-  }
-  // ---- tie runs over the sorted order B: every position's run start (a max-scan of the heads), the run's end stored at its start ----
-  unsigned carry = 0;
-  for (int t0 = 0; t0 < N; t0 += 256) {
-    const int j = t0 + tid;
-    const bool on = j < N;
-    unsigned ci = 0;
-    bool head = false, tail = false;
-    if (on) {
-      ci = B[j];
-      const unsigned kj = order_key(x[ci]);
-      head = j == 0 || order_key(x[B[j - 1]]) != kj;
-      tail = j == N - 1 || order_key(x[B[j + 1]]) != kj;
-    }
-    unsigned v = head ? (unsigned)j : 0u;
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_up(v, o, 64);
-      if (lane >= o) v = max(v, t);
-    }
-    if (lane == 63) sh.wtot[w] = v;
-    __syncthreads();
-    unsigned start = max(v, carry);
-    for (int q = 0; q < w; ++q) start = max(start, sh.wtot[q]);
-    carry = max(carry, max(max(sh.wtot[0], sh.wtot[1]), max(sh.wtot[2], sh.wtot[3])));
-    if (on) {
-      rk[ci] = (int32_t)start;
-      if (tail) A[start] = (unsigned)j;
-    }
-    __syncthreads();
-  }
+  for (int i = tid; i < N; i += 256) bad |= is_nonfinite(x[i]);
+  const auto key = [x](unsigned i) { return order_key(x[i]); };
+  const unsigned* S = block_radix_sort(key, N, 4, nullptr, A, sortB + base, sh);   // (four passes: the result is in B)
+  block_tie_runs(key, [rk](int, unsigned ci, unsigned start) { rk[ci] = (int32_t)start; }, N, S, A, sh);
   for (int j = tid; j < N; j += 256) {
-    const unsigned ci = B[j], s = (unsigned)rk[ci];
+    const unsigned ci = S[j], s = (unsigned)rk[ci];
     rk[ci] = (int32_t)(s + A[s] + 2u);
   }
   bad = __syncthreads_or(bad);
   if (tid == 0) nonfinite[blockIdx.x] = bad ? 1 : 0;
-}
-
-template <class T>
-__device__ inline T block_sum(T v, T* sh4) {   // fixed order: the lanes of a wave by halving, then the four waves
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
 }
 
 #define SMX_COR_PT 4   // proteins per register tile
@@ -173,9 +69,9 @@ __global__ __launch_bounds__(256) void col_correlate_kernel(CorrelateArgs a) {
     const long long v = r[i];
     s += (double)x[i]; sa += v; saa += v * v;
   }
-  const double mean = block_sum(s, sd) / (double)N;
-  sa = block_sum(sa, si);
-  saa = block_sum(saa, si);
+  const double mean = halving_block_sum(s, sd) / (double)N;
+  sa = halving_block_sum(sa, si);
+  saa = halving_block_sum(saa, si);
   if (tid == 0) { a.pe_mean[g] = mean; a.sp_Sa[g] = sa; a.sp_Saa[g] = saa; }
   for (int p0 = 0; p0 < P; p0 += SMX_COR_PT) {
     const int np = min(SMX_COR_PT, P - p0);
@@ -194,14 +90,14 @@ __global__ __launch_bounds__(256) void col_correlate_kernel(CorrelateArgs a) {
         }
     }
     if (p0 == 0) {
-      sxx = block_sum(sxx, sd);
+      sxx = halving_block_sum(sxx, sd);
       if (tid == 0) a.pe_Sxx[g] = sxx;
     }
 #pragma unroll
     for (int q = 0; q < SMX_COR_PT; ++q)
       if (q < np) {   // (block-uniform)
-        const double dy = block_sum(sxy[q], sd);
-        const long long iy = block_sum(sab[q], si);
+        const double dy = halving_block_sum(sxy[q], sd);
+        const long long iy = halving_block_sum(sab[q], si);
         if (tid == 0) { a.pe_Sxy[g * P + p0 + q] = dy; a.sp_Sab[g * P + p0 + q] = iy; }
       }
   }

@@ -8,14 +8,9 @@
 
 #include "smx_internal.h"
 #include "../../include/sisua_hip.h"
+#include "smx_block.h"   // wave_sum_f64
 
 namespace smx {
-
-__device__ inline double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // One wave per row.  lgx1[row] = sum_g lgamma(x+1) (the likelihood's data-only constant);
 // logcount[row] = log(float(sum_g x) + 1e-8) in fp32 as NumPy evaluates it on the float32 matrix.

@@ -16,6 +16,7 @@
 // alone or in a batch, a column the same bits alone or among others.  No float atomics; every loop is bounded by N, K, the slices or max_iter;
 // no workgroup waits on another.
 #include "smx_model.h"
+#include "smx_block.h"   // the fixed-order wave sum
 
 #include <algorithm>
 #include <cfloat>
@@ -45,15 +46,11 @@ __device__ inline void gm_consts(double w, double var, double* A, double* B) {
   *B = 0.5 / var;
 }
 
-// NV running sums of every thread -> out [NV]: the lanes of a wave by halving, then the four waves
+// NV running sums of every thread -> out [NV]: smx_block.h's wave sum, then the four waves in its order, NV wide (thread v closes sum v)
 template <int NV>
 __device__ inline void gm_block_sum(double (&acc)[NV], double* sh, double* out) {
 #pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    double x = acc[v];
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    acc[v] = x;
-  }
+  for (int v = 0; v < NV; ++v) acc[v] = halving_wave_sum(acc[v]);
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
     for (int v = 0; v < NV; ++v) sh[(threadIdx.x >> 6) * NV + v] = acc[v];

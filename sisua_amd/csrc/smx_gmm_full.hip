@@ -15,12 +15,13 @@
 //   E-step            one thread per cell, z in registers (D padded to 4, 8, 16, 32 or 64 with zeros); per component mu and the packed lower
 //                     triangle of Linv pass through LDS (every lane reads the same address); diff = z - mu first, then y = Linv diff row by row
 //                     (one chain per row, j ascending), q = sum y^2 (rows ascending).  l_nk is parked in resp, then the row maximum, the sum of
-//                     exponentials in k order, and r = exp(l - lse) overwrite it.  The lower-bound partial of a workgroup: lanes by halving, the
-//                     four waves as (0 + 1) + (2 + 3).
+//                     exponentials in k order, and r = exp(l - lse) overwrite it.  The lower-bound partial of a workgroup: smx_block.h's
+//                     fixed-order block sum.
 //   host loop         after every iteration ONE copy of 2 R flags (stop, bad); finished restarts leave the list of the later launches.
 // The number of slices is a function of N alone, and so is the order of every sum: two calls give the same bits and a restart gives the same
 // bits alone or in a batch.  No float atomics; every loop is bounded by N, K, D, the slices or max_iter; no workgroup waits on another.
 #include "smx_model.h"
+#include "smx_block.h"   // the fixed-order block sum
 
 #include <algorithm>
 #include <cfloat>
@@ -319,11 +320,8 @@ __global__ __launch_bounds__(SMX_GF_TILE) void gf_estep_kernel(GfEArgs a) {
     if (a.score) a.score[i] = lse;
   }
   if (a.lb_part) {
-    double v = lse;
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) a.lb_part[r * gridDim.x + blockIdx.x] = (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
+    const double total = halving_block_sum(lse, sh4);
+    if (threadIdx.x == 0) a.lb_part[r * gridDim.x + blockIdx.x] = total;
   }
 }
 

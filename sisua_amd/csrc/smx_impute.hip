@@ -11,10 +11,11 @@
 //                  model takes has the same form and the LDS use is 10 KB whatever G is.
 //   level kernel   levels 2 and 3 of the global selection (10 bits each) for the two ranks' prefixes at once, over d.
 //   column gather  [rows][n_sel] of the mean over the draws (smx_predict_stat_cols).
-// THE ROW SUMS are accumulated in float64 in a fixed order.  The reference compares float32 np.sum(row) of the two rows: for integer
+// THE ROW SUMS are accumulated in float64 in a fixed order (smx_block.h's block sum).  The reference compares float32 np.sum(row) of the two rows: for integer
 // counts with row sums below 2^24 (every count matrix this project reads) every partial sum of either form is an exact integer, so the
 // two comparisons agree.  Every loop is bounded by G or by the element count; nothing waits on device memory.
 #include "smx_model.h"
+#include "smx_block.h"   // the wave scan and the fixed-order block sum
 
 namespace smx {
 
@@ -37,11 +38,7 @@ __device__ inline unsigned block_select(const Key& key, int G, unsigned k, SelSh
     if (tid < 64) {   // wave 0: four bins per lane, an inclusive scan across the lanes; exactly one lane holds the rank
       const unsigned c0 = sh.hist[4 * tid], c1 = sh.hist[4 * tid + 1], c2 = sh.hist[4 * tid + 2], c3 = sh.hist[4 * tid + 3];
       const unsigned s = c0 + c1 + c2 + c3;
-      unsigned inc = s;
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(inc, o, 64);
-        if (tid >= o) inc += t;
-      }
+      const unsigned inc = wave_scan_add(s);
       const unsigned exc = inc - s;
       if (rank >= exc && rank < inc) {
         unsigned r = rank - exc, b = 4u * tid, c = c0, bl = exc;
@@ -84,18 +81,11 @@ struct DiffKey {   // pattern of |original - mean| (fabsf clears the sign bit: n
   const float* o; const float* mu;
   __device__ unsigned operator()(int g) const { return __float_as_uint(fabsf(o[g] - mu[g])); }
 };
-struct PlainKey {   // pattern of a non-negative (or NaN) value, -0 as +0
+struct PlainKey {   // pattern of a non-negative (or NaN) value, -0 as +0.  (The raw pattern, not smx_block.h's order_key: a NaN with the
+                    // sign bit set stays above +inf here and would fall below every number there.)
   const float* r;
   __device__ unsigned operator()(int g) const { const unsigned v = __float_as_uint(r[g]); return v == 0x80000000u ? 0u : v; }
 };
-
-__device__ inline double block_sum_f64(double v, double* sh4) {   // fixed order: the lanes of a wave by halving, then the four waves
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
-}
 
 __global__ __launch_bounds__(256) void impute_row_kernel(ImputeRowArgs a) {
   __shared__ SelShared sh;
@@ -123,8 +113,8 @@ __global__ __launch_bounds__(256) void impute_row_kernel(ImputeRowArgs a) {
     nan |= v > 0x7F800000u;
     so += (double)og; sc += (double)c[g];
   }
-  so = block_sum_f64(so, sd);
-  sc = block_sum_f64(sc, sd);   // (its first barrier comes after every read of sd above)
+  so = halving_block_sum(so, sd);
+  sc = halving_block_sum(sc, sd);
   nan = __syncthreads_or(nan);
   for (int i = tid; i < SMX_IMP_L1_BINS; i += 256)
     if (h1[i]) atomicAdd(&a.hist[i], (unsigned long long)h1[i]);

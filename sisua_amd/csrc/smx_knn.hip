@@ -13,10 +13,11 @@
 //                 A second launch merges the slices' lists, one thread per cell, by the same order.
 //   UMAP rows     smooth_knn_dist and compute_membership_strengths of umap-learn with local_connectivity = 1, bandwidth = 1, as the
 //                 header states them: one thread per row, at most 64 rounds of bisection, every sum in column order.  The mean of the
-//                 whole table is one launch of one workgroup: per-thread strided partials, the lanes of a wave by halving, the 4 waves.
+//                 whole table is one launch of one workgroup: smx_block.h's fixed-order column sum.
 // No float atomics; no workgroup waits on another; every loop is bounded by N, k, D or 64.
 #include "smx_model.h"
 #include "smx_dist.h"
+#include "smx_block.h"   // the fixed-order column sum
 
 #include <algorithm>
 #include <climits>
@@ -97,15 +98,11 @@ __global__ __launch_bounds__(SMX_CL_TILE) void knn_merge_kernel(const double* li
   }
 }
 
-// *out = the sum of x [n] in a fixed order: per-thread strided partials, the lanes of a wave by halving, then the four waves
+// *out = the sum of x [n] in the fixed order of smx_block.h's column sum
 __global__ __launch_bounds__(SMX_CL_TILE) void knn_table_sum_kernel(const double* x, long n, double* out) {
   __shared__ double sh4[4];
-  double v = 0.0;
-  for (long i = threadIdx.x; i < n; i += SMX_CL_TILE) v += x[i];
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
+  const double total = halving_column_sum(x, n, sh4);
+  if (threadIdx.x == 0) *out = total;
 }
 
 // one thread per row of the table idx / dist [N][K] (column 0: the cell itself): rho, sigma, weight [K]

@@ -3,11 +3,10 @@
 // the exact |a - b|.  The definitions are in include/sisua_hip.h and tests/mutual_info_ref.py.  Model-free entries: they upload,
 // compute, download and free their own buffers.  The columns arrive prepared by the host (scaled, noised); the device never evaluates
 // digamma or log: it adds entries of the host's two tables.
-//   column sort   one workgroup per column: the cell indices through a stable LSD radix sort on the 64-bit order-preserving pattern of the
-//                 double (-0 as +0), eight 8-bit passes in the shape of col_rank2_kernel (a wave owns a contiguous quarter of the positions,
-//                 its digit counts are its own LDS histogram, a ballot orders equal digits inside a tile of 64).  Leaves, per column: the
-//                 order, the sorted values, every cell's position, and every cell's run of equal values (start, length) -- the label
-//                 groups of a discrete column.
+//   column sort   one workgroup per column: the cell indices through smx_block.h's stable radix sort on the 64-bit order-preserving pattern
+//                 of the double (-0 as +0), eight 8-bit passes, then its tie-run pass (col_rank2_kernel runs the same two on float32).
+//                 Leaves, per column: the order, the sorted values, every cell's position, and every cell's run of equal values
+//                 (start, length) -- the label groups of a discrete column.
 //   cc            Kraskov: threads = 256 consecutive cells of the gene's SORTED order, four continuous proteins per workgroup.  The k-th
 //                 smallest Chebyshev distance is a set function, so the sweep over the other cells may take them in any order: it takes
 //                 tiles of 128 outward from the workgroup's own cells in the gene's order, (x_j, y_j) through LDS as broadcasts, the 8 best
@@ -19,9 +18,10 @@
 //                 nearest in its group are among the k cells either side of it -- and for dd the (gene label, protein label) runs.
 //                 m_i of cd: two binary searches in the continuous column's order and a prefix count of the kept cells.
 //   closing       one workgroup per pair: the sums of table entries over the cells in ONE order, a function of N alone (256 strided
-//                 partials, the lanes of a wave by halving, the four waves), then the estimator's expression and the clip at 0.
+//                 partials, then smx_block.h's fixed-order block sum), then the estimator's expression and the clip at 0.
 // No float atomics; every loop is bounded by N, P or k; nothing depends on the gene chunk.
 #include "smx_model.h"
+#include "smx_block.h"   // the radix sort, the tie-run pass, the keys, the scans and the fixed-order sums
 
 #include <algorithm>
 #include <cmath>
@@ -34,86 +34,6 @@ namespace smx {
 #define SMX_MI_MAX_K 8     // the register list of the cc sweep
 #define SMX_MI_PT 4        // continuous proteins per workgroup of the cc sweep
 #define SMX_MI_TJ 128      // cells j per LDS tile
-
-// order-preserving key of a float64: negative values below positive ones, -0 as +0
-__device__ inline unsigned long long mi_key(double v) {
-  unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  if (u == 0x8000000000000000ull) u = 0ull;
-  return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-
-// what a wave wrote to its own LDS words is read back by its other lanes (the project's idiom: smx_loss.h)
-__device__ inline void mi_wave_lds_sync() { __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_wave_barrier(); }
-
-struct MiSortShared { unsigned hist[4][256]; unsigned wtot[4]; };
-
-// The cell indices `init` [N] (NULL: the identity) sorted by key(cell), stable, `passes` 8-bit LSD passes over the ping-pong arrays A and B
-// (pass p writes A when p is even, B when odd).  Returns the array that holds the result.  Called by all 256 threads.
-template <class KeyFn>
-__device__ unsigned* mi_radix_sort(KeyFn key, int N, int passes, const unsigned* init, unsigned* A, unsigned* B, MiSortShared& sh) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int seg = (N + 255) / 256 * 64;   // wave w owns the positions [p0, p1): whole tiles of 64, in order
-  const int p0 = min(N, w * seg), p1 = min(N, p0 + seg);
-  const unsigned* src = init;
-  for (int pass = 0; pass < passes; ++pass) {
-    const int shift = 8 * pass;
-    unsigned* dst = (pass & 1) ? B : A;
-    for (int i = tid; i < 1024; i += 256) (&sh.hist[0][0])[i] = 0;
-    __syncthreads();
-    for (int p = p0 + lane; p < p1; p += 64) atomicAdd(&sh.hist[w][(unsigned)(key(src ? src[p] : (unsigned)p) >> shift) & 255u], 1u);
-    __syncthreads();
-    {   // thread = digit: where each wave's entries of the digit go = entries of smaller digits + those of earlier waves
-      const unsigned h0 = sh.hist[0][tid], h1 = sh.hist[1][tid], h2 = sh.hist[2][tid], h3 = sh.hist[3][tid];
-      const unsigned tot = h0 + h1 + h2 + h3;
-      unsigned inc = tot;
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-      }
-      if (lane == 63) sh.wtot[w] = inc;
-      __syncthreads();
-      unsigned exc = inc - tot;
-      for (int q = 0; q < w; ++q) exc += sh.wtot[q];
-      sh.hist[0][tid] = exc; sh.hist[1][tid] = exc + h0; sh.hist[2][tid] = exc + h0 + h1; sh.hist[3][tid] = exc + h0 + h1 + h2;
-    }
-    __syncthreads();
-    for (int p = p0; p < p1; p += 64) {   // (wave-uniform bounds: every lane takes part in the ballots)
-      const bool on = p + lane < p1;
-      unsigned i = 0, d = 0;
-      if (on) {
-        i = src ? src[p + lane] : (unsigned)(p + lane);
-        d = (unsigned)(key(i) >> shift) & 255u;
-      }
-      unsigned long long peers = __ballot(on);   // the tile's lanes with this lane's digit
-      for (int b = 0; b < 8; ++b) {
-        const bool bit = (d >> b) & 1u;
-        const unsigned long long mb = __ballot(bit);
-        peers &= bit ? mb : ~mb;
-      }
-      const unsigned before = (unsigned)__popcll(peers & ((1ull << lane) - 1ull));
-      unsigned o = 0;
-      if (on) {
-        o = sh.hist[w][d];
-        dst[o + before] = i;
-      }
-      mi_wave_lds_sync();
-      if (on && before == 0) sh.hist[w][d] = o + (unsigned)__popcll(peers);
-      mi_wave_lds_sync();
-    }
-    __syncthreads();   // (the pass's stores are drained: the next pass reads them through the CU's own cache)
-    src = dst;
-  }
-  return const_cast<unsigned*>(src);
-}
-
-template <class T>
-__device__ inline T mi_block_sum(T v, T* sh4) {   // fixed order: the lanes of a wave by halving, then the four waves
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
-}
 
 // what the column sort leaves per column, each [n_cols][N]
 struct MiCols {
@@ -128,50 +48,18 @@ struct MiCols {
 };
 
 __global__ __launch_bounds__(256) void mi_col_sort_kernel(MiCols c, int N) {
-  __shared__ MiSortShared sh;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  __shared__ SortShared sh;
+  const int tid = threadIdx.x;
   const long base = (long)blockIdx.x * N;
   const double* x = c.v + base;
   int bad = 0;
-  for (int i = tid; i < N; i += 256)
-    bad |= ((unsigned long long)__double_as_longlong(x[i]) & 0x7FF0000000000000ull) == 0x7FF0000000000000ull;
+  for (int i = tid; i < N; i += 256) bad |= is_nonfinite(x[i]);
   unsigned* A = c.tmp + base;
-  unsigned* B = c.ord + base;
-  unsigned* S = mi_radix_sort([x](unsigned i) { return mi_key(x[i]); }, N, 8, nullptr, A, B, sh);   // (eight passes: the result is in B)
+  const auto key = [x](unsigned i) { return order_key(x[i]); };
+  const unsigned* S = block_radix_sort(key, N, 8, nullptr, A, c.ord + base, sh);   // (eight passes: the result is in ord)
   double* sv = c.sv + base;
   int32_t *pos = c.pos + base, *start = c.start + base, *count = c.count + base;
-  // ---- runs of equal values over the sorted order: every position's run start (a max-scan of the heads), the run's end stored at its start ----
-  unsigned carry = 0;
-  for (int t0 = 0; t0 < N; t0 += 256) {
-    const int j = t0 + tid;
-    const bool on = j < N;
-    unsigned ci = 0;
-    bool head = false, tail = false;
-    if (on) {
-      ci = S[j];
-      const double vj = x[ci];
-      const unsigned long long kj = mi_key(vj);
-      head = j == 0 || mi_key(x[S[j - 1]]) != kj;
-      tail = j == N - 1 || mi_key(x[S[j + 1]]) != kj;
-      sv[j] = vj;
-      pos[ci] = j;
-    }
-    unsigned v = head ? (unsigned)j : 0u;
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_up(v, o, 64);
-      if (lane >= o) v = max(v, t);
-    }
-    if (lane == 63) sh.wtot[w] = v;
-    __syncthreads();
-    unsigned st = max(v, carry);
-    for (int q = 0; q < w; ++q) st = max(st, sh.wtot[q]);
-    carry = max(carry, max(max(sh.wtot[0], sh.wtot[1]), max(sh.wtot[2], sh.wtot[3])));
-    if (on) {
-      start[ci] = (int32_t)st;
-      if (tail) A[st] = (unsigned)j;
-    }
-    __syncthreads();
-  }
+  block_tie_runs(key, [=](int j, unsigned ci, unsigned st) { sv[j] = x[ci]; pos[ci] = j; start[ci] = (int32_t)st; }, N, S, A, sh);
   for (int j = tid; j < N; j += 256) {
     const unsigned ci = S[j];
     const unsigned st = (unsigned)start[ci];
@@ -312,7 +200,7 @@ __global__ __launch_bounds__(256) void mi_cc_kernel(MiArgs a) {
 // one workgroup per pair of which at least one column is discrete
 __global__ __launch_bounds__(256) void mi_pair_kernel(MiArgs a) {
 #pragma clang fp contract(off)
-  __shared__ MiSortShared sh;
+  __shared__ SortShared sh;
   const int g = blockIdx.y, p = blockIdx.x, N = a.N, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const bool xd = a.xdisc[g], yd = a.ydisc[p];
   if (!xd && !yd) return;   // (block-uniform)
@@ -324,7 +212,7 @@ __global__ __launch_bounds__(256) void mi_pair_kernel(MiArgs a) {
   if (xd && yd) {
     // ---- dd: the proteins' order sorted by the gene's label: runs of (gene label, protein label) ----
     const int32_t *sa = a.x.start + xo, *sb = a.y.start + yo;
-    const unsigned* S = mi_radix_sort([sa](unsigned i) { return (unsigned long long)sa[i]; }, N, passes, a.y.ord + yo, A, B, sh);
+    const unsigned* S = block_radix_sort([sa](unsigned i) { return (unsigned long long)sa[i]; }, N, passes, a.y.ord + yo, A, B, sh);
     double* term = reinterpret_cast<double*>(out);   // [N] over the first two planes: a run's term at its head, 0 elsewhere
     const double dN = (double)N, logN = a.logn[N];
     for (int j = tid; j < N; j += 256) {
@@ -361,18 +249,14 @@ __global__ __launch_bounds__(256) void mi_pair_kernel(MiArgs a) {
   const double* csv = cc.sv + co;
   const unsigned* cord = cc.ord + co;
   const int32_t *dstart = dc.start + dof, *dcount = dc.count + dof;
-  const unsigned* S = mi_radix_sort([dstart](unsigned i) { return (unsigned long long)dstart[i]; }, N, passes, cord, A, B, sh);
+  const unsigned* S = block_radix_sort([dstart](unsigned i) { return (unsigned long long)dstart[i]; }, N, passes, cord, A, B, sh);
   // prefix[m] = the kept cells (label group of more than one) among the first m of the continuous column's order
   int32_t* prefix = a.prefix + pair * (N + 1);
   unsigned carry = 0;
   for (int t0 = 0; t0 < N; t0 += 256) {
     const int j = t0 + tid;
     const unsigned one = j < N && dcount[cord[j]] > 1 ? 1u : 0u;
-    unsigned inc = one;
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
+    const unsigned inc = wave_scan_add(one);
     if (lane == 63) sh.wtot[w] = inc;
     __syncthreads();
     unsigned before = carry + inc - one;
@@ -424,12 +308,12 @@ __global__ __launch_bounds__(256) void mi_close_kernel(MiArgs a) {
     const double* term = reinterpret_cast<const double*>(in);
     double s = 0.0;
     for (int j = tid; j < N; j += 256) s += term[j];
-    v = mi_block_sum(s, sd);
+    v = halving_block_sum(s, sd);
   } else if (!xd && !yd) {
     double sx = 0.0, sy = 0.0;
     for (int i = tid; i < N; i += 256) { sx += a.psi[in[i]]; sy += a.psi[in[(long)N + i]]; }
-    sx = mi_block_sum(sx, sd);
-    sy = mi_block_sum(sy, sd);
+    sx = halving_block_sum(sx, sd);
+    sy = halving_block_sum(sy, sd);
     v = a.psi[N] + a.psi[a.k] - sx / (double)N - sy / (double)N;
   } else {
     double sk = 0.0, sc = 0.0, sm = 0.0;
@@ -438,10 +322,10 @@ __global__ __launch_bounds__(256) void mi_close_kernel(MiArgs a) {
       const int c = in[(long)N + i];
       if (c) { sk += a.psi[in[i]]; sc += a.psi[c]; sm += a.psi[in[2l * N + i]]; ++kept; }
     }
-    sk = mi_block_sum(sk, sd);
-    sc = mi_block_sum(sc, sd);
-    sm = mi_block_sum(sm, sd);
-    kept = mi_block_sum(kept, si);
+    sk = halving_block_sum(sk, sd);
+    sc = halving_block_sum(sc, sd);
+    sm = halving_block_sum(sm, sd);
+    kept = halving_block_sum(kept, si);
     const double n = (double)kept;
     v = kept ? a.psi[kept] + sk / n - sc / n - sm / n : 0.0;   // (no cell kept: 0, where scikit-learn raises)
   }

@@ -20,6 +20,7 @@
 // memory-bound and small beside the PCIe copy of the block, which is why the view costs a pass of its own instead of being fused.
 #include "smx_model.h"
 #include "smx_prep.h"   // PrepInput, PrepStage and the per-gene sums: shared with smx_pca.hip
+#include "smx_block.h"  // wave_sum_f64: the per-cell pass's butterfly, shared with row_stats_kernel
 
 #include <algorithm>
 #include <cmath>
@@ -44,12 +45,6 @@ __device__ __forceinline__ float prep_view(float x, int func, bool has_div, floa
   float v = has_div ? x / c : x;
   if (func == 1) v = log1pf(v);
   else if (func == 2) v = expm1f(v);
-  return v;
-}
-
-__device__ inline double prep_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
 
@@ -110,7 +105,7 @@ __global__ __launch_bounds__(256) void prep_cell_kernel(const float* __restrict_
         cnt += e[q] > 0.f ? 1 : 0;
       }
   }
-  tot = prep_wave_sum(tot);
+  tot = wave_sum_f64(tot);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
   if (lane == 0) {

@@ -21,6 +21,7 @@
 // another; every loop is bounded by N, k, the row's entries, max_iter or 100; 1 / (1 + d2) is the IEEE float64 division.
 #include "smx_model.h"
 #include "smx_dist.h"
+#include "smx_block.h"   // the fixed-order wave sum
 
 #include <algorithm>
 #include <cmath>
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(SMX_TSNE_SUM_THREADS) void tsne_sum_kernel(const do
     for (int s = 1; s < S; ++s) r += x[(long)s * stride + i];
     v += r;
   }
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  v = halving_wave_sum(v);
   if ((threadIdx.x & 63) == 0) sh16[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x < 64) {   // (the first wave: lanes 0 .. 15 hold the waves' sums)
