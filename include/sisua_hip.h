@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 14
+#define SMX_ABI_VERSION 15
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -986,6 +986,33 @@ int smx_mutual_info(const double* xcols, const uint8_t* x_discrete, const double
                     double* mi);
 int smx_k_mi_cells(const double* x, int32_t x_discrete, const double* y, int32_t y_discrete, int64_t n_cells, int32_t n_neighbors,
                    const double* psi, const double* logn, int32_t* cells, double* radius, double* mi);
+
+/* ---- ranking genes between groups of cells (smx_rankgroups.hip; model-free: smx_init only) ----------- */
+/* What scanpy.tl.rank_genes_groups (the reference's SingleCellOMIC.rank_vars_groups) needs of size n_cells x n_genes; the closing formulas
+ * are the host's (sisua_amd/rank_groups.py).  labels [n_cells] int32 in 0 .. n_groups - 1.
+ *
+ * smx_group_moments: the host matrix in the forms of smx_prep_stats (dense x, or CSR with x = NULL, streamed in blocks of block_rows rows
+ * as there), twice.  count [n_groups]: the cells of every group.  sum, css [n_groups][n_genes] float64 and nnz [n_groups][n_genes] int64:
+ * per group and gene the float64 sum of the float32 values, the sum of the squares of the float64 differences (double)x - mean with mean
+ * = sum / count (the two-pass form, one FMA per term; 0 for an empty group), and the values != 0 (-0 is 0).  Every sum runs over the
+ * group's GLOBAL rows in row order in one accumulator that is carried exactly between blocks; no atomics: the same bits for every
+ * block_rows, for dense and CSR input, and from call to call.  A non-finite entry of x shows as a non-finite sum.  The limits of
+ * smx_prep_stats, 1 <= n_groups <= 65535 and n_groups x (n_genes rounded up to 4) <= 2^26: anything else is SMX_ERR_INVALID before any
+ * device work.  Device memory: the tile, the staged CSR block, and 24 bytes x n_groups x n_genes of accumulators.
+ *
+ * smx_group_ranksums: host columns cols [n_cols][n_cells] float32, gene-major (the layout of smx_k_col_rank2), finite.  reference = -1
+ * (every group against the rest): the average ranks of a column over all n_cells cells (-0 ties with +0); rank2_sum [n_groups][n_cols] =
+ * 2 x the sum of the ranks of the group's cells, tie_term [n_cols] = sum (t^3 - t) over the column's runs of t equal values.  reference
+ * = a group: for every other group g the ranks are those within the cells of g and of the reference; rank2_sum [g] = 2 x the rank sum
+ * of g's cells there and tie_term [n_groups][n_cols] row g = the tie sum of that comparison; the rows of the reference itself and of
+ * an empty group are 0.  int64, exact: 1 <= n_cells <= 2^20 (2 n_cells^2 and n_cells^3 stay below 2^63), 1 <= n_groups <= 256: anything
+ * else is SMX_ERR_INVALID before any device work.  One sort per column in either case (with a reference by (value, label),
+ * and a prefix count of the reference's cells over the sorted order).  The columns are sorted and held on the device as many at a time
+ * as 256 MB hold (16 n_cells bytes each, 28 n_cells with a reference); the integers do not depend on it. */
+int smx_group_moments(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_cells, int32_t n_genes,
+                      int32_t block_rows, const int32_t* labels, int32_t n_groups, int64_t* count, double* sum, double* css, int64_t* nnz);
+int smx_group_ranksums(const float* cols, int32_t n_cols, int64_t n_cells, const int32_t* labels, int32_t n_groups, int32_t reference,
+                       int64_t* rank2_sum, int64_t* tie_term);
 
 /* ---- padding audit (test instrument; never on the path of a step) ----------- */
 /* The layout's invariant, read back from the device: every feature axis is padded to 32 and every tensor to 64 floats, and what lies

@@ -13,5 +13,6 @@ from sisua_amd.metrics import correlation_list, marker_correlations, marker_scor
 from sisua_amd.mixture import GaussianMixture  # noqa: F401
 from sisua_amd.mutual_info import mutual_information  # noqa: F401
 from sisua_amd.neighbors import PCA, TSNE  # noqa: F401
+from sisua_amd.rank_groups import rank_genes_groups  # noqa: F401
 
 __version__ = "0.1.0"

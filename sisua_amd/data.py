@@ -313,7 +313,8 @@ class SingleCellOMIC:
     self._pca = {}          # omic -> (PCA, scores) of dimension_reduce; likewise
     self._neighbors = {}    # omic -> (connectivities, distances, params) of neighbors; likewise
     self._tsne = {}         # (omic, n_components) -> the embedding of dimension_reduce(algo='tsne'); likewise
-    self._uns = {}          # the reference's .uns: 'mutualinfo_{omic}_{target}' -> (omic, target, matrix) of get_mutual_information; likewise
+    self._uns = {}          # the reference's .uns: 'mutualinfo_{omic}_{target}' -> (omic, target, matrix) of get_mutual_information and
+                            # '{omic}_{group_by}_rank' -> (omic, grouping omic or None, dict) of rank_vars_groups; likewise
     self.add_omic(omic, X, var_names)
 
   def add_omic(self, omic: str, X, var_names=None):
@@ -560,6 +561,49 @@ class SingleCellOMIC:
     if uns_key not in self._uns:
       self._uns[uns_key] = (om1, om2, mutual_information(self.numpy(om1), self.numpy(om2), n_neighbors=n_neighbors, random_state=random_state))
     return self._uns[uns_key][2]
+
+  def rank_vars_groups(self, n_vars=100, group_by="proteomic", clustering="kmeans", method="logreg", corr_method="benjamini-hochberg",
+                       max_iter=1000, reference="rest"):
+    """The reference's rank_vars_groups (_single_cell_analysis.py:862-918, scanpy.tl.rank_genes_groups there): the variables of the FIRST
+    omic ranked for characterising groups of cells (`sisua_amd.rank_genes_groups`; the matrix work runs on the device, smx_rankgroups.hip).
+    group_by: a [cells] array of labels, or the name of an omic with clustering=None -- each cell's label is then the variable name at
+    the argmax of `get_x_probs(omic)`, as the reference's '{omic}_labels'.  method: 't-test', 't-test_overestim_var' or 'wilcoxon'.
+    The result is kept under '{omic}_{group_by}_rank' ('labels' for an array) until an omic it was made from is replaced; a later call
+    returns what is kept, whatever its other arguments.  Returns the key, as the reference does: `get_rank_vars_groups(key)` gives the dict.
+    Deviations: there is no use_raw (the omic is ranked as it stands); `SingleCellOMIC.clustering` is not built, so an omic with
+    clustering='kmeans' (the reference's default) raises NotImplementedError; logistic regression (the reference's default method) is
+    not built and raises NotImplementedError; max_iter belongs to it and is unused."""
+    from sisua_amd.rank_groups import METHODS, rank_genes_groups
+    built = (f"rank_vars_groups is built for method in {METHODS} with group_by a [cells] label array or an omic's name with "
+             "clustering=None")
+    if method == "logreg":
+      raise NotImplementedError(f"method='logreg' is not built: {built}")
+    om1 = self.omics[0]
+    if isinstance(group_by, str):
+      if group_by not in self._data:
+        raise ValueError(f"group_by={group_by!r} is neither a [cells] label array nor one of the omics {self.omics}")
+      if clustering is not None:
+        raise NotImplementedError(f"clustering={clustering!r} is not built (SingleCellOMIC.clustering): {built}")
+      om2, name = group_by, group_by
+    else:
+      om2, name = None, "labels"
+    key = f"{om1}_{name}_rank"
+    if key not in self._uns:
+      if om2 is None:
+        labels = np.asarray(group_by)
+        if labels.shape != (self.n_obs,):
+          raise ValueError(f"group_by must be [{self.n_obs}] labels, got {labels.shape}")
+      else:
+        labels = np.asarray(self._vars[om2])[np.argmax(self.get_x_probs(om2), axis=1)]
+      self._uns[key] = (om1, om2, rank_genes_groups(self.numpy(om1), labels, reference=reference, method=method, corr_method=corr_method,
+                                                   n_genes=int(n_vars), var_names=self._vars[om1]))
+    return key
+
+  def get_rank_vars_groups(self, key):
+    """The dict `rank_vars_groups` left under `key`"""
+    if key not in self._uns or not str(key).endswith("_rank"):
+      raise KeyError(f"no ranked groups under {key!r}: call rank_vars_groups first")
+    return self._uns[key][2]
 
   def get_pca(self, omic=None):
     """The fitted `sisua_amd.PCA` of an omic (what `dimension_reduce` left), or None"""
