@@ -715,6 +715,27 @@ int smx_k_bn_fwd(const int32_t* ip, const float* fp, const float* pre, const flo
 int smx_k_bn_bwd(const int32_t* ip, const float* fp, const float* dout, const float* out, const float* xhat, const float* inv_std,
                  const float* gamma, const float* beta, const float* mask, const int32_t* rows, uint64_t seed, float* dpre, float* dgamma,
                  float* dbeta, float* dbias, int32_t* guards_ok);
+/* The scVI gene head's launches by themselves (smx_scvi.hip), over host arrays in a training step's own layout: raw / planes [B][ld], plane c
+ * of a row at c * plane_stride, Gp columns of which G are live (a step has Gp = G rounded up to 32, plane_stride = Gp, ld = k Gp; k = 2 for
+ * nbd, 3 for zinbd).  The library's own dispatch picks the instance by Gp.  Every output lies between guard bands and starts as NaN
+ * (*guards_ok as smx_k_bn_fwd).  The entries refuse shapes that would take a kernel outside a buffer; alignment (ld, plane_stride, Gp
+ * multiples of 4), the train form's limit Gp <= 20480 and its null outputs are refused by the launchers: SMX_ERR_INVALID, no fallback.
+ * smx_k_scvi_head_train -- the row-local training launch.  ip (int32): B, G, Gp, plane_stride, ld, likelihood (SMX_LLK_NBD / _ZINBD), x_u16,
+ * n_x, ldx, Kl, ldh, ldwl, n_lib, x_identity, ldl, Philox stream, step, cell_base.  fp: clip_library, grad_scale, kl_weight (what multiplies
+ * the library KL's gradient).  x [n_x][ldx]: float counts, or (x_u16) uint16; hl [B][ldh]; Wl [Kl][ldwl] (columns mu, s); bl [2]; library
+ * [n_lib][2] (prior mean, variance); rows [B] or NULL (cell b = row b): the library row, and with x_identity = 0 the row of x; eps_in [B]
+ * the injected library noise, or NULL (drawn from Philox under seed, stream, step for cell cell_base + rows[b]).  Out, all of the kernel's:
+ * draw [B][ld]; llk_part (without the count constant), l, sig, eps, kl, dl [B]; latl, dlatl [B][ldl].  A NULL output reaches the launcher
+ * as NULL. */
+int smx_k_scvi_head_train(const int32_t* ip, const float* fp, const float* raw, const void* x, const float* hl, const float* Wl, const float* bl,
+                          const float* library, const int32_t* rows, const float* eps_in, uint64_t seed, float* draw, float* llk_part, float* l,
+                          float* sig, float* eps, float* kl, float* latl, float* dlatl, float* dl, int32_t* guards_ok);
+/* ... the separate forward (ip: B, G, Gp, plane_stride, ld, k; fp: clip_library): raw [B][ld], l [B] -> planes [B][ld] (rate, theta[, gate]),
+ * rho_raw [B][Gp] (the softmax before its clip) ... */
+int smx_k_scvi_head_fwd(const int32_t* ip, const float* fp, const float* raw, const float* l, float* planes, float* rho_raw, int32_t* guards_ok);
+/* ... and the separate backward on ITS inputs: planes, dplanes [B][ld], rho_raw [B][Gp], l [B] -> draw [B][ld], dl [B]. */
+int smx_k_scvi_head_bwd(const int32_t* ip, const float* fp, const float* planes, const float* dplanes, const float* rho_raw, const float* l,
+                        float* draw, float* dl, int32_t* guards_ok);
 /* The predictive sampler by itself on caller-given planes [k][rows][G] (host; k planes of `likelihood`, direct / count_only as
  * smx_k_count_llk / smx_predict_sample): out [n_k][rows][G], the draws of rows 0 .. rows - 1 of a call with one Monte-Carlo draw
  * (s = 0) under `seed`.  rows <= 65535. */

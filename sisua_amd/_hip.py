@@ -179,6 +179,9 @@ SIGNATURES = {
                               C.c_float, _FP, _FP]),
     "smx_k_bn_fwd": (C.c_int, [_IP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _IP, C.c_uint64, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _IP]),
     "smx_k_bn_bwd": (C.c_int, [_IP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _IP, C.c_uint64, _FP, _FP, _FP, _FP, _IP]),
+    "smx_k_scvi_head_train": (C.c_int, [_IP, _FP, _FP, _VP, _FP, _FP, _FP, _FP, _IP, _FP, C.c_uint64, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _IP]),
+    "smx_k_scvi_head_fwd": (C.c_int, [_IP, _FP, _FP, _FP, _FP, _FP, _IP]),
+    "smx_k_scvi_head_bwd": (C.c_int, [_IP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _IP]),
     "smx_k_plane_sample": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _FP]),
     "smx_k_row_select": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]),
     "smx_k_col_rank2": (C.c_int, [_FP, C.c_int32, C.c_int64, _IP, _IP]),

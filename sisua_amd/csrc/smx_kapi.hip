@@ -1,5 +1,6 @@
 // smx_kapi.hip -- kernel-level entry points (parity tests of single kernels): smx_k_count_llk, smx_k_adam, smx_k_gemm, smx_k_head_fused, smx_k_noise,
-// smx_k_bn_fwd / smx_k_bn_bwd, smx_k_opt_carrier (clip + update by every launch that carries the optimiser's chunk body).
+// smx_k_bn_fwd / smx_k_bn_bwd, smx_k_opt_carrier (clip + update by every launch that carries the optimiser's chunk body),
+// smx_k_scvi_head_train / _fwd / _bwd (the scVI gene head's three launch forms).
 #include "smx_model.h"
 #include "smx_adam.h"
 #include <hiprand/hiprand_kernel.h>
@@ -741,6 +742,111 @@ int smx_k_opt_carrier(const int32_t* ip, const float* fp, const float* hp, int32
     if (q) for (size_t i = 0; i < total; ++i) { uint32_t w; memcpy(&w, q + i, 4); if (w != 0xFFFFFFFFu) same = false; }
   *unused_ok = same ? 1 : 0;
   if (lr_t) { StepState h; SMX_HIP(hipMemcpy(&h, dSt, sizeof(h), hipMemcpyDeviceToHost)); *lr_t = h.lr_t; }
+  return SMX_OK;
+}
+
+}  // extern "C"
+
+// ---- the scVI gene head's launches by themselves (smx_scvi.hip: launch_scvi_head_train / _fwd / _bwd pick the instance by Gp) ---------------
+// Host arrays in the step's own layout (raw / planes [B][ld], plane c of a row at c * plane_stride, Gp live + padded columns); every output
+// between guard bands and NaN before the launch (KbnOut).  The entries check what keeps the kernels' accesses inside the buffers; alignment,
+// the width limit and null outputs are the launchers' to refuse.
+extern "C" {
+
+// ip: B, G, Gp, plane_stride, ld, likelihood, x_u16, n_x, ldx, Kl, ldh, ldwl, n_lib, x_identity, ldl, stream, step, cell_base;
+// fp: clip_library, grad_scale, kl_weight
+int smx_k_scvi_head_train(const int32_t* ip, const float* fp, const float* raw, const void* x, const float* hl, const float* Wl, const float* bl,
+                          const float* library, const int32_t* rows, const float* eps_in, uint64_t seed, float* draw, float* llk_part, float* l,
+                          float* sig, float* eps, float* kl, float* latl, float* dlatl, float* dl, int32_t* guards_ok) {
+  SMX_REQUIRE(ip && fp && raw && x && hl && Wl && bl && library && guards_ok, "k_scvi_head_train: bad arguments");
+  const int B = ip[0], G = ip[1], Gp = ip[2], ps = ip[3], ld = ip[4], likelihood = ip[5], x_u16 = ip[6], n_x = ip[7], ldx = ip[8], Kl = ip[9],
+            ldh = ip[10], ldwl = ip[11], n_lib = ip[12], x_identity = ip[13], ldl = ip[14], stream = ip[15], step = ip[16];
+  SMX_REQUIRE(likelihood == SMX_LLK_NBD || likelihood == SMX_LLK_ZINBD, "k_scvi_head_train: likelihood must be nbd or zinbd");
+  const int k = llk_planes(likelihood);
+  SMX_REQUIRE(B > 0 && G > 0 && G <= Gp && ps >= Gp && (long)ld >= (long)(k - 1) * ps + Gp && n_x > 0 && ldx >= Gp && Kl > 0 && ldh >= Kl && ldwl >= 2 &&
+              n_lib > 0 && ldl >= 2 && ldl <= 256, "k_scvi_head_train: bad shapes");
+  SMX_REQUIRE(rows ? true : (n_lib >= B), "k_scvi_head_train: library needs a row per cell");
+  SMX_REQUIRE((x_identity || !rows) ? n_x >= B : true, "k_scvi_head_train: x needs a row per cell");
+  if (rows)
+    for (int b = 0; b < B; ++b) SMX_REQUIRE(rows[b] >= 0 && rows[b] < n_lib && (x_identity || rows[b] < n_x), "k_scvi_head_train: a row id lies outside x or library");
+  DeviceScratch buf;
+  float *dRaw, *dHl, *dWl, *dBl, *dLib, *dEps; int32_t* dRows; uint8_t* dX;
+  KbnOut oDraw, oLlk, oL, oSig, oEps, oKl, oLatl, oDlatl, oDl;
+  int rc;
+  if ((rc = buf.put(&dRaw, raw, (size_t)B * ld)) || (rc = buf.put(&dX, static_cast<const uint8_t*>(x), (size_t)n_x * ldx * (x_u16 ? 2 : 4))) ||
+      (rc = buf.put(&dHl, hl, (size_t)B * ldh)) || (rc = buf.put(&dWl, Wl, (size_t)Kl * ldwl)) || (rc = buf.put(&dBl, bl, (size_t)2)) ||
+      (rc = buf.put(&dLib, library, (size_t)n_lib * 2)) || (rc = buf.put(&dRows, rows, (size_t)B)) || (rc = buf.put(&dEps, eps_in, (size_t)B)) ||
+      (rc = oDraw.alloc(buf, (size_t)B * ld)) || (rc = oLlk.alloc(buf, B)) || (rc = oL.alloc(buf, B)) || (rc = oSig.alloc(buf, B)) || (rc = oEps.alloc(buf, B)) ||
+      (rc = oKl.alloc(buf, B)) || (rc = oLatl.alloc(buf, (size_t)B * ldl)) || (rc = oDlatl.alloc(buf, (size_t)B * ldl)) || (rc = oDl.alloc(buf, B)))
+    return rc;
+  ScviTrainArgs a;
+  a.raw = dRaw; a.ld = ld; a.plane_stride = ps; a.B = B; a.G = G; a.Gp = Gp; a.likelihood = likelihood;
+  a.X = reinterpret_cast<const float*>(dX); a.ldx = ldx; a.x_u16 = x_u16 ? 1 : 0; a.rows = dRows; a.x_identity = x_identity ? 1 : 0;
+  a.clip_library = fp[0]; a.grad_scale = fp[1]; a.klw = KlWeight{nullptr, fp[2], 1.f, 0};
+  a.hl = dHl; a.ldh = ldh; a.Kl = Kl; a.Wl = dWl; a.ldwl = ldwl; a.bl = dBl; a.library = dLib; a.cell_base = (uint32_t)ip[17];
+  a.nk = probe_key(seed, stream, 0, step); a.inj_eps = dEps; a.inj_ld = 1; a.ldl = ldl;
+  // (an output the caller leaves out reaches the launcher as NULL: its refusal)
+  a.draw = draw ? oDraw.p() : nullptr; a.llk_part = llk_part ? oLlk.p() : nullptr; a.l = l ? oL.p() : nullptr; a.sig = sig ? oSig.p() : nullptr;
+  a.eps = eps ? oEps.p() : nullptr; a.kl = kl ? oKl.p() : nullptr; a.latl = latl ? oLatl.p() : nullptr; a.dlatl = dlatl ? oDlatl.p() : nullptr;
+  a.dl = dl ? oDl.p() : nullptr;
+  SMX_CHECK(launch_scvi_head_train(nullptr, a));
+  SMX_HIP(hipDeviceSynchronize());
+  bool ok = true;
+  for (const KbnOut* o : {&oDraw, &oLlk, &oL, &oSig, &oEps, &oKl, &oLatl, &oDlatl, &oDl}) if ((rc = o->intact(&ok))) return rc;
+  *guards_ok = ok ? 1 : 0;
+  if ((rc = oDraw.download(draw, (size_t)B * ld)) || (rc = oLlk.download(llk_part, B)) || (rc = oL.download(l, B)) || (rc = oSig.download(sig, B)) ||
+      (rc = oEps.download(eps, B)) || (rc = oKl.download(kl, B)) || (rc = oLatl.download(latl, (size_t)B * ldl)) ||
+      (rc = oDlatl.download(dlatl, (size_t)B * ldl)) || (rc = oDl.download(dl, B)))
+    return rc;
+  return SMX_OK;
+}
+
+// ip: B, G, Gp, plane_stride, ld, k; fp: clip_library.  raw [B][ld], l [B] -> planes [B][ld] (rate, theta[, gate]), rho_raw [B][Gp]
+int smx_k_scvi_head_fwd(const int32_t* ip, const float* fp, const float* raw, const float* l, float* planes, float* rho_raw, int32_t* guards_ok) {
+  SMX_REQUIRE(ip && fp && raw && l && planes && rho_raw && guards_ok, "k_scvi_head_fwd: bad arguments (an input or an output is NULL)");
+  const int B = ip[0], G = ip[1], Gp = ip[2], ps = ip[3], ld = ip[4], k = ip[5];
+  SMX_REQUIRE(B > 0 && G > 0 && G <= Gp && (k == 2 || k == 3) && ps >= Gp && (long)ld >= (long)(k - 1) * ps + Gp, "k_scvi_head_fwd: bad shapes");
+  DeviceScratch buf;
+  float *dRaw, *dL;
+  KbnOut oPl, oRho;
+  int rc;
+  if ((rc = buf.put(&dRaw, raw, (size_t)B * ld)) || (rc = buf.put(&dL, l, (size_t)B)) || (rc = oPl.alloc(buf, (size_t)B * ld)) ||
+      (rc = oRho.alloc(buf, (size_t)B * Gp)))
+    return rc;
+  ScviHeadArgs a;
+  a.raw = dRaw; a.planes = oPl.p(); a.ld = ld; a.plane_stride = ps; a.B = B; a.G = G; a.Gp = Gp; a.k = k; a.l = dL; a.clip_library = fp[0];
+  a.rho_raw = oRho.p();
+  SMX_CHECK(launch_scvi_head_fwd(nullptr, a));
+  SMX_HIP(hipDeviceSynchronize());
+  bool ok = true;
+  if ((rc = oPl.intact(&ok)) || (rc = oRho.intact(&ok))) return rc;
+  *guards_ok = ok ? 1 : 0;
+  if ((rc = oPl.download(planes, (size_t)B * ld)) || (rc = oRho.download(rho_raw, (size_t)B * Gp))) return rc;
+  return SMX_OK;
+}
+
+// ip, fp as the forward entry's.  planes, dplanes [B][ld], rho_raw [B][Gp], l [B] -> draw [B][ld], dl [B]
+int smx_k_scvi_head_bwd(const int32_t* ip, const float* fp, const float* planes, const float* dplanes, const float* rho_raw, const float* l,
+                        float* draw, float* dl, int32_t* guards_ok) {
+  SMX_REQUIRE(ip && fp && planes && dplanes && rho_raw && l && draw && dl && guards_ok, "k_scvi_head_bwd: bad arguments (an input or an output is NULL)");
+  const int B = ip[0], G = ip[1], Gp = ip[2], ps = ip[3], ld = ip[4], k = ip[5];
+  SMX_REQUIRE(B > 0 && G > 0 && G <= Gp && (k == 2 || k == 3) && ps >= Gp && (long)ld >= (long)(k - 1) * ps + Gp, "k_scvi_head_bwd: bad shapes");
+  DeviceScratch buf;
+  float *dPl, *dDp, *dRho, *dL;
+  KbnOut oDraw, oDl;
+  int rc;
+  if ((rc = buf.put(&dPl, planes, (size_t)B * ld)) || (rc = buf.put(&dDp, dplanes, (size_t)B * ld)) || (rc = buf.put(&dRho, rho_raw, (size_t)B * Gp)) ||
+      (rc = buf.put(&dL, l, (size_t)B)) || (rc = oDraw.alloc(buf, (size_t)B * ld)) || (rc = oDl.alloc(buf, B)))
+    return rc;
+  ScviHeadArgs a;
+  a.planes = dPl; a.dplanes = dDp; a.rho_raw = dRho; a.l = dL; a.ld = ld; a.plane_stride = ps; a.B = B; a.G = G; a.Gp = Gp; a.k = k;
+  a.clip_library = fp[0]; a.draw = oDraw.p(); a.dl = oDl.p();
+  SMX_CHECK(launch_scvi_head_bwd(nullptr, a));
+  SMX_HIP(hipDeviceSynchronize());
+  bool ok = true;
+  if ((rc = oDraw.intact(&ok)) || (rc = oDl.intact(&ok))) return rc;
+  *guards_ok = ok ? 1 : 0;
+  if ((rc = oDraw.download(draw, (size_t)B * ld)) || (rc = oDl.download(dl, B))) return rc;
   return SMX_OK;
 }
 

@@ -1651,3 +1651,85 @@ def k_bn_bwd(dout, out, xhat, B, H, Hp, inv_std=None, gamma=None, beta=None, bat
                          int(seed), _fp(o["dpre"]), _fp(o["dgamma"]), _fp(o["dbeta"]), _fp(o["dbias"]), C.byref(ok)))
   o["guards_ok"] = bool(ok.value)
   return o
+
+
+def _scvi_layout(G, k, Gp, plane_stride, ld):
+  """The step's layout of the scVI head's planes unless overridden: Gp = G rounded up to 32, plane_stride = Gp, ld = k Gp"""
+  Gp = (int(G) + 31) // 32 * 32 if Gp is None else int(Gp)
+  ps = Gp if plane_stride is None else int(plane_stride)
+  return Gp, ps, (k - 1) * ps + Gp if ld is None else int(ld)
+
+
+def k_scvi_head_train(raw, x, hl, Wl, bl, library, G, likelihood="zinbd", rows=None, x_identity=False, eps=None, clip_library=1e3,
+                      grad_scale=1.0, kl_weight=0.0, ldl=2, Gp=None, plane_stride=None, ld=None, seed=0, stream=65, step=0, cell_base=0, omit=()):
+  """The row-local training launch of the scVI gene head by itself (smx_k_scvi_head_train).  raw [B][ld] in the step's layout (plane c of a
+  row at c * plane_stride); x [n_x][Gp] counts, float32 or uint16 (the dtype picks the kernel's load path); hl [B][Kl]; Wl [Kl][2]; bl [2];
+  library [n_lib][2]; rows [B] (optional; with x_identity the rows of x are the minibatch's already); eps [B] the injected library noise
+  (None: drawn on the device).  Returns every output of the kernel: draw [B][ld]; llk_part, l, sig, eps, kl, dl [B]; latl, dlatl [B][ldl];
+  guards_ok.  A word the kernel did not write comes back as NaN.  omit: names of outputs handed to the launcher as NULL (it refuses)."""
+  lib = _hip.require_gpu()
+  k = 3 if likelihood == "zinbd" else 2
+  Gp, ps, ld = _scvi_layout(G, k, Gp, plane_stride, ld)
+  raw = _f32(raw)
+  B = raw.shape[0]
+  raw = _f32(raw.reshape(B, -1), (B, ld))
+  u16 = np.asarray(x).dtype == np.uint16
+  x = np.ascontiguousarray(x, dtype=np.uint16 if u16 else np.float32)
+  if x.ndim != 2 or x.shape[1] < Gp:
+    raise ValueError(f"x must be [rows][>= Gp = {Gp}], got {x.shape}")
+  hl, Wl = _f32(hl), _f32(Wl)
+  if hl.ndim != 2 or hl.shape[0] != B or Wl.shape != (hl.shape[1], 2):
+    raise ValueError(f"hl must be [B, Kl] and Wl [Kl, 2], got {hl.shape} and {Wl.shape}")
+  bl, library = _f32(bl, (2,)), _f32(library)
+  if library.ndim != 2 or library.shape[1] != 2:
+    raise ValueError(f"library must be [n, 2], got {library.shape}")
+  rw = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+  ep = None if eps is None else _f32(eps, (B,))
+  ip = np.array([B, G, Gp, ps, ld, _hip.LIKELIHOODS[likelihood], int(u16), x.shape[0], x.shape[1], hl.shape[1], hl.shape[1], 2, library.shape[0],
+                 int(bool(x_identity)), ldl, stream, step, cell_base], np.int32)
+  fp = np.array([clip_library, grad_scale, kl_weight], np.float32)
+  o = dict(draw=np.empty((B, ld), np.float32), latl=np.empty((B, ldl), np.float32), dlatl=np.empty((B, ldl), np.float32))
+  for name in ("llk_part", "l", "sig", "eps", "kl", "dl"):
+    o[name] = np.empty(B, np.float32)
+  p = {name: (None if name in omit else _fp(a)) for name, a in o.items()}
+  ok = C.c_int32(0)
+  check(lib.smx_k_scvi_head_train(_ip(ip), _fp(fp), _fp(raw), x.ctypes.data_as(C.c_void_p), _fp(hl), _fp(Wl), _fp(bl), _fp(library),
+                                  None if rw is None else _ip(rw), _fp(ep), int(seed), p["draw"], p["llk_part"], p["l"], p["sig"], p["eps"], p["kl"],
+                                  p["latl"], p["dlatl"], p["dl"], C.byref(ok)))
+  o["guards_ok"] = bool(ok.value)
+  return o
+
+
+def k_scvi_head_fwd(raw, l, G, k=3, clip_library=1e3, Gp=None, plane_stride=None, ld=None, omit=()):
+  """The separate forward launch of the scVI gene head (smx_k_scvi_head_fwd): raw [B][ld], l [B] -> dict(planes [B][ld], rho_raw [B][Gp],
+  guards_ok)"""
+  lib = _hip.require_gpu()
+  Gp, ps, ld = _scvi_layout(G, k, Gp, plane_stride, ld)
+  raw = _f32(raw)
+  B = raw.shape[0]
+  raw, l = _f32(raw.reshape(B, -1), (B, ld)), _f32(l, (B,))
+  ip, fp = np.array([B, G, Gp, ps, ld, k], np.int32), np.array([clip_library], np.float32)
+  o = dict(planes=np.empty((B, ld), np.float32), rho_raw=np.empty((B, Gp), np.float32))
+  p = {name: (None if name in omit else _fp(a)) for name, a in o.items()}
+  ok = C.c_int32(0)
+  check(lib.smx_k_scvi_head_fwd(_ip(ip), _fp(fp), _fp(raw), _fp(l), p["planes"], p["rho_raw"], C.byref(ok)))
+  o["guards_ok"] = bool(ok.value)
+  return o
+
+
+def k_scvi_head_bwd(planes, dplanes, rho_raw, l, G, k=3, clip_library=1e3, Gp=None, plane_stride=None, ld=None, omit=()):
+  """The separate backward launch of the scVI gene head (smx_k_scvi_head_bwd) on its inputs: planes, dplanes [B][ld], rho_raw [B][Gp],
+  l [B] -> dict(draw [B][ld], dl [B], guards_ok)"""
+  lib = _hip.require_gpu()
+  Gp, ps, ld = _scvi_layout(G, k, Gp, plane_stride, ld)
+  planes = _f32(planes)
+  B = planes.shape[0]
+  planes, dplanes = _f32(planes.reshape(B, -1), (B, ld)), _f32(np.asarray(dplanes).reshape(B, -1), (B, ld))
+  rho_raw, l = _f32(rho_raw, (B, Gp)), _f32(l, (B,))
+  ip, fp = np.array([B, G, Gp, ps, ld, k], np.int32), np.array([clip_library], np.float32)
+  o = dict(draw=np.empty((B, ld), np.float32), dl=np.empty(B, np.float32))
+  p = {name: (None if name in omit else _fp(a)) for name, a in o.items()}
+  ok = C.c_int32(0)
+  check(lib.smx_k_scvi_head_bwd(_ip(ip), _fp(fp), _fp(planes), _fp(dplanes), _fp(rho_raw), _fp(l), p["draw"], p["dl"], C.byref(ok)))
+  o["guards_ok"] = bool(ok.value)
+  return o

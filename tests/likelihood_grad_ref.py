@@ -17,6 +17,8 @@ tests/test_likelihood_grad_host.py checks all of it against mpmath on the whole 
 THE BOUNDS.  u = 2^-24, operation counts as in plane_stat_ref's docstring (a rounding 1, v_exp / v_log / v_rcp 2, fexp's argument
 2 |x| u), and its building blocks: r = fexp(p0) good to rel_r = 2 + 2 |p0|; softplus absolute `_sp_abs`; sigmoid of softplus_sigmoid good to
 6 + 2 |x| relative (7 + 3 |x| with softplus^-1(1) added first); mu, th good to 38 + 2 |p0|, 39 + 3 |p1| relative (0 where `direct`).
+Under `direct` a caller whose kernel formed the mean and the dispersion itself (the scVI head: tests/scvi_head_ref.py) passes their
+relative errors as rel_in = (rel_mu, rel_th) and the float64 planes with exact=True; the default is 0 and float32 planes, as before.
 Every bound is ABSOLUTE and in term sizes: sum over the terms of (operations of the term) x |term|, plus every input's relative
 error times |input x exact partial derivative| (the partials are written out below), plus one rounding of the sum of the sizes per
 addition.  Nothing is relative to the result: d1 = x - (x + r) sg and d2 at x = 0 are differences of near-equal numbers.
@@ -115,20 +117,24 @@ def _bc(p, shape):
   return [np.broadcast_to(v, shape) for v in p]
 
 
-def _nbd_inputs(p, direct):
-  """mu, th, g0, g1 and their relative float32 errors in u"""
+def _nbd_inputs(p, direct, rel_in=None):
+  """mu, th, g0, g1 and their relative float32 errors in u.  rel_in = (rel_mu, rel_th), `direct` only: the errors of a mean and a dispersion
+  that the kernel formed itself (None: exact inputs, 0)"""
   if direct:
     one = np.ones_like(p[0])
-    return p[0], p[1], one, one, 0.0 * one, 0.0 * one, 0.0 * one, 0.0 * one
+    if rel_in is None:
+      return p[0], p[1], one, one, 0.0 * one, 0.0 * one, 0.0 * one, 0.0 * one
+    return p[0], p[1], one, one, rel_in[0] + 0.0 * one, rel_in[1] + 0.0 * one, 0.0 * one, 0.0 * one
   mu, th = softplus(p[0]), softplus(p[1] + SOFTPLUS_INV_1)
   return (mu, th, expit(p[0]), expit(p[1] + SOFTPLUS_INV_1), 38.0 + 2.0 * np.abs(p[0]), 39.0 + 3.0 * np.abs(p[1]),
           6.0 + 2.0 * np.abs(p[0]), 7.0 + 3.0 * np.abs(p[1]))
 
 
-def count_terms(kind, x, planes, direct=False):
+def count_terms(kind, x, planes, direct=False, rel_in=None, exact=False):
   """dict of float64 arrays: everything grad_elem, grad_elem_bound and grad_in_range share -- the count part's gradients d0c, d1c (before
-  the zero branch scales them), their terms, ell at x = 0, w and 1 - w"""
-  p = _f64(planes)
+  the zero branch scales them), their terms, ell at x = 0, w and 1 - w.  exact: the planes are float64 values, not rounded to float32 first
+  (plane_stat_ref._f64); rel_in: _nbd_inputs"""
+  p = _f64(planes, exact)
   x = _xb(x, p)
   p = _bc(p, x.shape)
   t = dict(x=x)
@@ -138,7 +144,7 @@ def count_terms(kind, x, planes, direct=False):
     dg, dgp = digamma_diff(x, r)
     t.update(r=r, sp=sp, sg=sg, dg=dg, dgp=dgp, d0c=r * (dg - sp), d1c=x * expit(-p[1]) - r * sg, ell0=-r * sp)
   else:
-    mu, th, g0, g1, rel_mu, rel_th, rel_g0, rel_g1 = _nbd_inputs(p, direct)
+    mu, th, g0, g1, rel_mu, rel_th, rel_g0, rel_g1 = _nbd_inputs(p, direct, rel_in)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
       T = th + mu + EPS
       dg, dgp = digamma_diff(x, np.clip(th, 1e-30, 1e30))
@@ -157,9 +163,9 @@ def count_terms(kind, x, planes, direct=False):
   return t
 
 
-def grad_elem(kind, x, planes, direct=False):
+def grad_elem(kind, x, planes, direct=False, exact=False):
   """[3, ...] float64: d log p / d p0, p1, p2 per element (0 where the kind has no such plane)"""
-  p = _f64(planes)
+  p = _f64(planes, exact)
   x = _xb(x, p)
   p = _bc(p, x.shape)
   zero = np.zeros(x.shape)
@@ -170,7 +176,7 @@ def grad_elem(kind, x, planes, direct=False):
     z = (x - p[0]) / sd
     with np.errstate(over="ignore"):
       return np.stack([z / sd, (z * z - 1.0) / sd * expit(p[1] + SOFTPLUS_INV_1), zero])
-  t = count_terms(kind, x, planes, direct)
+  t = count_terms(kind, x, planes, direct, exact=exact)
   if not is_zi(kind):
     return np.stack([t["d0c"], t["d1c"], zero])
   at0 = x == 0
@@ -196,9 +202,11 @@ def _dgdiff_abs(x, r, dg):
   return np.where(small, (5.0 * x + 3.0) * dg, big)
 
 
-def grad_elem_bound(kind, x, planes, direct=False):
-  """[3, ...] float64: the absolute first-order float32 bound of every gradient component (the module docstring's table)"""
-  p = _f64(planes)
+def grad_elem_bound(kind, x, planes, direct=False, rel_in=None, exact=False):
+  """[3, ...] float64: the absolute first-order float32 bound of every gradient component (the module docstring's table).  rel_in =
+  (rel_mu, rel_th) in u, `direct` only: the table's input-error terms for a mean and a dispersion the kernel formed itself (None: 0, the
+  planes are the kernel's inputs)"""
+  p = _f64(planes, exact)
   x = _xb(x, p)
   p = _bc(p, x.shape)
   zero = np.zeros(x.shape)
@@ -214,7 +222,7 @@ def grad_elem_bound(kind, x, planes, direct=False):
       d0, d1 = z / sd, (z * z - 1.0) / sd * sg
       return np.stack([(2.0 * rel_sd + 7.0) * np.abs(d0) + FLUSH,
                        ((2.0 * rel_zz + 2.0) * z * z + 1.0) * sg / sd + (rel_sd + 11.0 + 3.0 * np.abs(p[1])) * np.abs(d1) + FLUSH, zero]) * U
-  t = count_terms(kind, x, planes, direct)
+  t = count_terms(kind, x, planes, direct, rel_in, exact)
   with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
     if base_kind(kind, True) == "nb":
       r, sp, sg, dg = t["r"], t["sp"], t["sg"], t["dg"]
@@ -257,11 +265,11 @@ def _below_max(v):
     return np.isfinite(v) & (np.abs(v) < F32_MAX)
 
 
-def grad_in_range(kind, x, planes, direct=False):
+def grad_in_range(kind, x, planes, direct=False, exact=False):
   """the grid condition per element (the module docstring)"""
-  p = _f64(planes)
+  p = _f64(planes, exact)
   x = _xb(x, p)
-  g = grad_elem(kind, x, planes, direct)
+  g = grad_elem(kind, x, planes, direct, exact)
   ok = _below_max(g[0]) & _below_max(g[1]) & _below_max(g[2])
   if kind == "bernoulli":
     return ok & _normal32(expit(p[0] + 0.0 * x))
@@ -271,7 +279,7 @@ def grad_in_range(kind, x, planes, direct=False):
       z2 = ((x - p[0]) / sd) ** 2
       ok &= _normal32((z2 - 1.0) / sd)          # ((zz zz - 1) inv, formed before the product by sg)
     return ok & _normal32(sd) & _normal32(1.0 / sd) & _normal32(z2, True) & _normal32(expit(p[1] + SOFTPLUS_INV_1) + 0.0 * x)
-  t = count_terms(kind, x, planes, direct)
+  t = count_terms(kind, x, planes, direct, exact=exact)
   pos = x > 0
   ok &= _below_max(t["d0c"]) & _below_max(t["d1c"]) & _normal32(t["dg"], ~pos)
   if base_kind(kind, True) == "nb":
@@ -332,10 +340,10 @@ def count_const(kind, x):
   return gammaln(np.asarray(x, np.float64) + 1.0) if kind not in ("bernoulli", "normal") else np.zeros(np.shape(x))
 
 
-def row_sum_bound(kind, x, planes, n_add, direct=False, count_only=False, double_const=True, repeat=1):
-  """(ref, bound) of the sum over the last axis, every element taken `repeat` times"""
-  v = log_prob_elem(kind, x, planes, direct, count_only)
-  b = logprob_elem_bound(kind, x, planes, direct, count_only, double_const=double_const)
+def row_sum_bound(kind, x, planes, n_add, direct=False, count_only=False, double_const=True, repeat=1, rel_in=None, exact=False):
+  """(ref, bound) of the sum over the last axis, every element taken `repeat` times (rel_in, exact: logprob_elem_bound's)"""
+  v = log_prob_elem(kind, x, planes, direct, count_only, exact)
+  b = logprob_elem_bound(kind, x, planes, direct, count_only, double_const=double_const, rel_in=rel_in, exact=exact)
   s = np.abs(v + count_const(kind, np.broadcast_to(x, v.shape)))
   ref = repeat * v.sum(axis=-1)
   return ref, repeat * (b.sum(axis=-1) + (n_add + 8.0) * U * s.sum(axis=-1) + v.shape[-1] * F32_MIN) + U * np.abs(ref)

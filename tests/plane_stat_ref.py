@@ -87,8 +87,10 @@ MODERATE["zinbd"] = tuple(p + (g,) for p, g in zip(MODERATE["nbd"], (-0.5, 0.3, 
 CYCLE = (0.0, 1.0, 2.0, 12.0, 181.0, 1000.0, 10738.0)
 
 
-def _f64(planes):
-  return [np.asarray(p, np.float32).astype(np.float64) for p in planes]
+def _f64(planes, exact=False):
+  """the planes as float64: rounded to float32 first (what a kernel reads), or with `exact` as they are -- float64 values that a kernel only
+  knows to a stated relative error (tests/scvi_head_ref.py: the rate and the dispersion the scVI head forms in registers)"""
+  return [np.asarray(p, np.float64) if exact else np.asarray(p, np.float32).astype(np.float64) for p in planes]
 
 
 def softplus(x):
@@ -153,10 +155,10 @@ def log_binom(x, r):
   return out
 
 
-def log_prob_elem(kind, x, planes, direct=False, count_only=False):
+def log_prob_elem(kind, x, planes, direct=False, count_only=False, exact=False):
   """the per-element log-probability the kernels sum over the genes, float64 (count kinds: including - lgamma(x + 1);
   'mse': -(x - mean)^2 / G, G the last axis)"""
-  p = _f64(planes)
+  p = _f64(planes, exact)
   x = np.broadcast_to(np.asarray(x, np.float64), np.broadcast_shapes(np.shape(x), p[0].shape))
   if kind == "mse":
     return -((x - p[0]) ** 2) / float(x.shape[-1])
@@ -291,12 +293,13 @@ def _lgdiff_abs(x, r, rel_r):
   return carried + np.where(small, e_small, e_big)
 
 
-def logprob_elem_bound(kind, x, planes, direct=False, count_only=False, double_const=False):
+def logprob_elem_bound(kind, x, planes, direct=False, count_only=False, double_const=False, rel_in=None, exact=False):
   """b_g: the absolute float32 error bound of one element of the row sum (the module docstring), float64.  double_const: without the
-  lgammaf(x + 1) term -- for the kernels that take the count constant of a row from a double-precision sum"""
-  p = _f64(planes)
+  lgammaf(x + 1) term -- for the kernels that take the count constant of a row from a double-precision sum.  rel_in = (rel_mu, rel_th), `direct`
+  only: the relative errors, in u, of the mean and the dispersion a kernel holds (None: exact inputs, 0)"""
+  p = _f64(planes, exact)
   x = np.broadcast_to(np.asarray(x, np.float64), np.broadcast_shapes(np.shape(x), p[0].shape))
-  v = np.abs(log_prob_elem(kind, x, planes, direct, count_only))
+  v = np.abs(log_prob_elem(kind, x, planes, direct, count_only, exact))
   if kind == "mse":
     return 4.0 * v * U
   if kind == "bernoulli":
@@ -315,7 +318,8 @@ def logprob_elem_bound(kind, x, planes, direct=False, count_only=False, double_c
          + (rel_r + 1.0) * t3 + r * _sp_abs(p[1]) + 2.0 * (lg + t2 + t3))
   else:
     if direct:
-      mu, th, rel_mu, rel_th = p[0], p[1], 0.0, 0.0
+      mu, th = p[0], p[1]
+      rel_mu, rel_th = (0.0, 0.0) if rel_in is None else rel_in
     else:
       mu, th = softplus(p[0]), softplus(p[1] + SOFTPLUS_INV_1)
       rel_mu, rel_th = 38.0 + 2.0 * np.abs(p[0]), 39.0 + 3.0 * np.abs(p[1])
@@ -330,7 +334,7 @@ def logprob_elem_bound(kind, x, planes, direct=False, count_only=False, double_c
   if is_zi(kind) and not count_only:
     g = p[2]
     spg = softplus(g)
-    ellv = log_prob_elem(base_kind(kind, True), x, planes[:2], direct) + gammaln(x + 1.0)   # (the kernel's ell has no count constant)
+    ellv = log_prob_elem(base_kind(kind, True), x, planes[:2], direct, exact=exact) + gammaln(x + 1.0)   # (the kernel's ell has no count constant)
     dlt = np.abs(ellv - g)
     w3 = expit(-dlt)                                                       # e3 / (1 + e3)
     lse = np.abs(np.logaddexp(g, ellv))

@@ -26,6 +26,8 @@ def test_header_and_binding_agree(lib):
   for name in declared:
     assert hasattr(lib, name)
   assert lib.smx_abi_version() == _hip.SMX_ABI_VERSION
+  # the kernel-level entries of the scVI gene head (tests/test_gpu_scvi_head.py)
+  assert {"smx_k_scvi_head_train", "smx_k_scvi_head_fwd", "smx_k_scvi_head_bwd"} <= declared
 
 
 def test_config_struct_layout_matches_header(tmp_path):

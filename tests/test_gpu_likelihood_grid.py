@@ -35,8 +35,8 @@ EVERY LAUNCHER BRANCH that evaluates count_elem / count_elem_vec and is reachabl
   smx_score.hip   score_tile_llk (count_elem_vec<LK, 0, 8>) in score_head_kernel (tile) and score_walk_kernel (walk), the queue and -- knob
                   no_score_queue -- the straight-line lgamma_digamma_diff_vec                   test_scoring_on_the_grid[*-stacked, *-stacked_no_queue] (walk: forced)
                   count_loss_kernel BWD = 0 (the draw-by-draw form; 'bernoulli' always)         test_scoring_on_the_grid[*-per_draw, bernoulli-*]
-                  the scvi form count_elem_vec<LK, 1, 4>                                        out of scope (as smx_scvi.hip)
-  smx_scvi.hip    count_elem_vec<LK, 1, 4>                                                      out of scope (the rate cannot be pinned); forward: test_gpu_plane_stats
+                  the scvi form count_elem_vec<LK, 1, 4>                                        the instance held in tests/test_gpu_scvi_head.py (smx_scvi.hip); this launch: not reached
+  smx_scvi.hip    count_elem_vec<LK, 1, 4>                                                      tests/test_gpu_scvi_head.py (the rate pinned from raw_0 and l); forward planes also: test_gpu_plane_stats
   smx_predict.hip plane_logprob (count_elem<LK, DIRECT>)                                        tests/test_gpu_plane_stats.py
 """
 import numpy as np

@@ -91,6 +91,23 @@ static void model_free_entries() {
                            nullptr, nullptr, nullptr, nullptr, nullptr, &guards));
     NO_DEVICE(smx_k_bn_bwd(bwd, bfp, ones.data(), ones.data(), ones.data(), ones.data(), ones.data(), ones.data(), nullptr, nullptr, 8, out.data(), out.data() + 64,
                            out.data() + 128, nullptr, &guards)); }
+  { // the scVI head's entries: B 2, G 5, Gp 32, k 3 (ld 96); a row id beyond the library and a stride short of the planes are refused before staging
+    const int32_t tr[18] = {2, 5, 32, 32, 96, SMX_LLK_ZINBD, 0, 2, 32, 3, 3, 2, 2, 0, 4, 65, 0, 0}, sep[6] = {2, 5, 32, 32, 96, 3}, rows_bad[2] = {0, 2};
+    const float tfp[3] = {1e3f, -0.5f, 0.1f};
+    int32_t guards = 0;
+    float* o = out.data();
+    auto train = [&](const int32_t* ip, const int32_t* rows, float* draw) {
+      return smx_k_scvi_head_train(ip, tfp, ones.data(), ones.data(), ones.data(), ones.data(), ones.data(), ones.data(), rows, nullptr, 8, draw, o + 256, o + 300,
+                                   o + 310, o + 320, o + 330, o + 340, o + 360, o + 380, &guards);
+    };
+    NO_DEVICE(train(tr, nullptr, o));
+    EXPECT(train(tr, rows_bad, o) == SMX_ERR_INVALID);
+    { int32_t bad[18]; memcpy(bad, tr, sizeof(bad)); bad[4] = 64; EXPECT(train(bad, nullptr, o) == SMX_ERR_INVALID); }
+    { int32_t bad[18]; memcpy(bad, tr, sizeof(bad)); bad[5] = SMX_LLK_NB; EXPECT(train(bad, nullptr, o) == SMX_ERR_INVALID); }
+    NO_DEVICE(smx_k_scvi_head_fwd(sep, tfp, ones.data(), ones.data(), o, o + 256, &guards));
+    EXPECT(smx_k_scvi_head_fwd(sep, tfp, ones.data(), ones.data(), nullptr, o + 256, &guards) == SMX_ERR_INVALID);
+    NO_DEVICE(smx_k_scvi_head_bwd(sep, tfp, ones.data(), ones.data(), ones.data(), ones.data(), o, o + 256, &guards));
+    EXPECT(smx_k_scvi_head_bwd(sep, tfp, ones.data(), ones.data(), ones.data(), ones.data(), o, nullptr, &guards) == SMX_ERR_INVALID); }
   NO_DEVICE(smx_k_plane_sample(SMX_LLK_NB, 0, 1, ones.data(), N, G, 8, 1, out.data()));
   NO_DEVICE(smx_k_row_select(x.data(), N, G, G, out.data(), out.data() + 64));
   // -- correlation: G columns of N cells, one protein column
