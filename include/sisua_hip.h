@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 15
+#define SMX_ABI_VERSION 16
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -1034,6 +1034,42 @@ int smx_group_moments(const float* x, const int64_t* indptr, const int32_t* cols
                       int32_t block_rows, const int32_t* labels, int32_t n_groups, int64_t* count, double* sum, double* css, int64_t* nnz);
 int smx_group_ranksums(const float* cols, int32_t n_cols, int64_t n_cells, const int32_t* labels, int32_t n_groups, int32_t reference,
                        int64_t* rank2_sum, int64_t* tie_term);
+
+/* ---- mini-batch k-means on the count matrix (smx_mbkmeans.hip; model-free: smx_init only) ----------- */
+/* The matrix work of scikit-learn's MiniBatchKMeans.partial_fit / predict (the reference's SingleCellOMIC.clustering); the random draws,
+ * the reassignment of starved centres and the bookkeeping are the host's (sisua_amd/minibatch_kmeans.py).  The host matrix comes in the
+ * forms of smx_prep_stats: dense x [n_rows][n_genes] float32, or CSR with x = NULL.  centres [n_clusters][n_genes] float64.  Every squared
+ * distance is the direct form sum_j ((double)x_j - c_j)^2 in float64, the columns added in an order that is a function of n_genes alone
+ * (a zero of a CSR row adds its c_j^2 at its place): dense and CSR input give the same bits, and so do two calls.  The nearest centre:
+ * ties go to the lowest index and a NaN distance is never the smallest (a row whose every distance is NaN or +inf: centre 0, distance
+ * +inf).  No atomics.  Limits of all three: 2 <= n_clusters <= 256, 1 <= n_genes <= 32768, 1 <= n_rows < 2^31; anything else, a null
+ * pointer or a malformed CSR is SMX_ERR_INVALID before any device work.
+ *
+ * smx_mbkmeans_seed: scikit-learn's _kmeans_plusplus with unit weights on one block of n_clusters <= n_rows <= 65536 rows (rows x
+ * (n_genes rounded up to 4) <= 2^31: the block is held whole).  first: the first centre's row; u [n_clusters - 1][n_trials] float64 in
+ * [0, 1), 1 <= n_trials <= 16: the draws of every further centre.  Per centre: the inclusive float64 scan of the rows' distances to their
+ * closest centre; per trial the first row whose scan value is >= u x potential, the last row where there is none; the candidates'
+ * distances to every row, min with the closest so far; every candidate's potential as a fixed-order sum; the lowest potential is kept
+ * (ties to the lowest trial).  All n_clusters rounds run in stream order without a host round trip.  indices [n_clusters] int32: the
+ * chosen rows; centres: those rows; potential [n_clusters]: the potential after each pick.  Device memory: the tile, the staged CSR
+ * block, 8 x (n_trials + 1) x n_rows and 8 x (n_clusters + n_trials) x n_genes bytes.
+ *
+ * smx_mbkmeans_step: scikit-learn's _mini_batch_step without the reassignment, on one block (held whole, as above).  The block's labels
+ * against `centres` (labels [n_rows] int32, or NULL) and *inertia, the fixed-order sum of the rows' smallest distances.  Then in place,
+ * for every centre with m > 0 rows: centre = (centre x count + the sum of its rows in row order) / (count + m), each operation rounded
+ * once, and count += m; a centre without rows is left alone.  counts [n_clusters] float64 in/out, finite and >= 0.  Device memory: the
+ * tile, the staged CSR block, 12 x n_rows and 8 x n_clusters x n_genes bytes.
+ *
+ * smx_mbkmeans_predict: labels [n_rows] int32 and, where distance is not NULL, the smallest squared distance [n_rows] float64 of every
+ * row.  The matrix is streamed in blocks of block_rows rows as in smx_prep_stats (0: the library's choice); no result depends on it.
+ * Device memory: the tile, the staged CSR block, 12 x n_rows and 8 x n_clusters x n_genes bytes. */
+int smx_mbkmeans_seed(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_rows, int32_t n_genes,
+                      int32_t n_clusters, int32_t n_trials, int64_t first, const double* u, int32_t* indices, double* centres,
+                      double* potential);
+int smx_mbkmeans_step(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_rows, int32_t n_genes,
+                      int32_t n_clusters, double* centres, double* counts, int32_t* labels, double* inertia);
+int smx_mbkmeans_predict(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_rows, int32_t n_genes,
+                         int32_t block_rows, int32_t n_clusters, const double* centres, int32_t* labels, double* distance);
 
 /* ---- padding audit (test instrument; never on the path of a step) ----------- */
 /* The layout's invariant, read back from the device: every feature axis is padded to 32 and every tensor to 64 floats, and what lies

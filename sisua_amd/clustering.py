@@ -211,3 +211,36 @@ def latent_scores(latent, labels, n_labels, prediction_algorithm="both", n_init=
     return s2
   s1 = score(both["kmeans_labels"])
   return {k: (s1[k] + s2[k]) / 2 for k in s1}
+
+
+# ---- mini-batch k-means of a whole matrix (the reference's SingleCellOMIC.clustering: _single_cell_analysis.py:679-700, 714-726) -----
+BATCH_SIZE = 4096   # the reference's
+
+
+def minibatch_kmeans(X, n_clusters, batch_size: int = BATCH_SIZE, random_state=1) -> np.ndarray:
+  """The k-means part of the reference's `clustering` for a matrix without a container (an omic, a latent space): a
+  `sisua_amd.MiniBatchKMeans(n_clusters, batch_size, compute_labels=False, random_state)` takes one `partial_fit` per batch of rows
+  (s, min(s + batch_size, n)) in the order `RandomState(random_state).permutation(n_batches)` -- our reading of the reference's
+  `odin.utils.batching(seed=...)`, which is not at hand -- and then predicts every row.  X: dense or scipy.sparse, never densified whole.
+  Returns the labels [rows] int32.  The distance sweeps run on the device (smx_mbkmeans.hip)."""
+  from sisua_amd.minibatch_kmeans import MiniBatchKMeans
+  if getattr(X, "ndim", 0) != 2:
+    raise ValueError(f"X must be a matrix [rows, features], got shape {getattr(X, 'shape', None)}")
+  model = MiniBatchKMeans(n_clusters=n_clusters, batch_size=batch_size, compute_labels=False, random_state=random_state)
+  n = X.shape[0]
+  starts = np.arange(0, n, model.batch_size)
+  for s in starts[np.random.RandomState(random_state).permutation(len(starts))]:
+    model.partial_fit(X[int(s):int(min(s + model.batch_size, n))])
+  return model.predict(X)
+
+
+def match_clusters(labels, probs, n_clusters) -> np.ndarray:
+  """ids [n_vars]: the cluster that takes each variable's name.  corr[i, c] = the float64 sum of probs[:, i] over the cells of cluster c;
+  the linear assignment that maximises sum_i corr[i, ids[i]] -- our reading of the reference's `diagonal_linear_assignment`, which is
+  not at hand."""
+  from scipy.optimize import linear_sum_assignment
+  p, lab = np.asarray(probs, np.float64), np.asarray(labels)
+  corr = np.zeros((p.shape[1], int(n_clusters)), np.float64)
+  for c in range(int(n_clusters)):
+    corr[:, c] = p[lab == c].sum(axis=0)
+  return linear_sum_assignment(corr, maximize=True)[1]

@@ -1,4 +1,4 @@
-// smx_prep.h -- the block streamer of smx_prep.hip for the other model-free entries that read a whole count matrix (smx_pca.hip, smx_rankgroups.hip): the host
+// smx_prep.h -- the block streamer of smx_prep.hip for the other model-free entries that read a whole count matrix (smx_pca.hip, smx_rankgroups.hip, smx_mbkmeans.hip): the host
 // matrix, dense or CSR, crosses in blocks of rows through one device tile [block][ld] float32, ld = G rounded up to 4, padding zero.  A
 // block is a whole number of slices of SMX_PREP_SLICE rows of the GLOBAL row ids, whatever block_rows was asked for.
 #pragma once

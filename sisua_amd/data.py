@@ -19,6 +19,7 @@ the dense twin's bits (for library_size: integer counts with row sums below 2**2
 """
 from __future__ import annotations
 
+import numbers
 from typing import List, Optional, Sequence, Tuple
 
 import ctypes as _C
@@ -315,6 +316,7 @@ class SingleCellOMIC:
     self._tsne = {}         # (omic, n_components) -> the embedding of dimension_reduce(algo='tsne'); likewise
     self._uns = {}          # the reference's .uns: 'mutualinfo_{omic}_{target}' -> (omic, target, matrix) of get_mutual_information and
                             # '{omic}_{group_by}_rank' -> (omic, grouping omic or None, dict) of rank_vars_groups; likewise
+    self._obs = {}          # the reference's .obs: '{omic}_{algo}{n_clusters}' -> (omic, cluster omic or None, labels) of clustering; likewise
     self.add_omic(omic, X, var_names)
 
   def add_omic(self, omic: str, X, var_names=None):
@@ -399,8 +401,9 @@ class SingleCellOMIC:
       cache.pop(key, None)
     for kc in [kc for kc in self._tsne if kc[0] == key]:
       del self._tsne[kc]
-    for kc in [kc for kc, v in self._uns.items() if key in v[:2]]:
-      del self._uns[kc]
+    for store in (self._uns, self._obs):
+      for kc in [kc for kc, v in store.items() if key in v[:2]]:
+        del store[kc]
 
   def _replace(self, key: str, X, var_names=None):
     """A new matrix for an omic already held (same cells); its embedding, PCA and neighbour graph, if any, no longer describe it"""
@@ -570,18 +573,26 @@ class SingleCellOMIC:
     the argmax of `get_x_probs(omic)`, as the reference's '{omic}_labels'.  method: 't-test', 't-test_overestim_var' or 'wilcoxon'.
     The result is kept under '{omic}_{group_by}_rank' ('labels' for an array) until an omic it was made from is replaced; a later call
     returns what is kept, whatever its other arguments.  Returns the key, as the reference does: `get_rank_vars_groups(key)` gives the dict.
-    Deviations: there is no use_raw (the omic is ranked as it stands); `SingleCellOMIC.clustering` is not built, so an omic with
-    clustering='kmeans' (the reference's default) raises NotImplementedError; logistic regression (the reference's default method) is
-    not built and raises NotImplementedError; max_iter belongs to it and is unused."""
+    group_by may also be a key that `clustering(..., return_key=True)` left (the reference's `if str(group_by) in self.obs`): its labels
+    are ranked, under '{omic}_{that key}_rank', until the first omic or the clustered one is replaced.  The reference's default --
+    an omic's name with clustering='kmeans' -- takes two calls here: `key = sco.clustering(first omic, n_clusters=group_by,
+    return_key=True)`, then `sco.rank_vars_groups(group_by=key, ...)`.
+    Deviations: there is no use_raw (the omic is ranked as it stands); an omic's name with clustering='kmeans' (the reference's
+    default) raises NotImplementedError naming clustering=None; logistic regression (the reference's default method) is not built and
+    raises NotImplementedError; max_iter belongs to it and is unused."""
     from sisua_amd.rank_groups import METHODS, rank_genes_groups
     built = (f"rank_vars_groups is built for method in {METHODS} with group_by a [cells] label array or an omic's name with "
              "clustering=None")
     if method == "logreg":
       raise NotImplementedError(f"method='logreg' is not built: {built}")
     om1 = self.omics[0]
-    if isinstance(group_by, str):
+    kept = None
+    if isinstance(group_by, str) and group_by in self._obs:
+      kept, (om2, name) = self._obs[group_by][2], (self._obs[group_by][0], group_by)
+    elif isinstance(group_by, str):
       if group_by not in self._data:
-        raise ValueError(f"group_by={group_by!r} is neither a [cells] label array nor one of the omics {self.omics}")
+        raise ValueError(f"group_by={group_by!r} is neither a [cells] label array, one of the omics {self.omics} nor a key that "
+                         f"clustering(return_key=True) left ({sorted(self._obs)})")
       if clustering is not None:
         raise NotImplementedError(f"clustering={clustering!r} is not built (SingleCellOMIC.clustering): {built}")
       om2, name = group_by, group_by
@@ -589,7 +600,9 @@ class SingleCellOMIC:
       om2, name = None, "labels"
     key = f"{om1}_{name}_rank"
     if key not in self._uns:
-      if om2 is None:
+      if kept is not None:
+        labels = kept
+      elif om2 is None:
         labels = np.asarray(group_by)
         if labels.shape != (self.n_obs,):
           raise ValueError(f"group_by must be [{self.n_obs}] labels, got {labels.shape}")
@@ -604,6 +617,55 @@ class SingleCellOMIC:
     if key not in self._uns or not str(key).endswith("_rank"):
       raise KeyError(f"no ranked groups under {key!r}: call rank_vars_groups first")
     return self._uns[key][2]
+
+  def clustering(self, omic=None, n_clusters=None, n_init="auto", algo="kmeans", matching_labels=True, return_key=False, random_state=1):
+    """The reference's clustering (_single_cell_analysis.py:632-730) for algo in ('kmeans', 'pca', 'tsne'): `sisua_amd.MiniBatchKMeans`
+    (n_clusters, batch_size=4096, compute_labels=False, random_state) -- scikit-learn's class there, its distance sweeps on the device
+    here (smx_mbkmeans.hip) -- takes one `partial_fit` per batch of 4096 cells and then predicts every cell.
+    n_clusters: None -> the omic's own width, a number as given, an omic's name -> that omic's width; None and a name make that omic
+    the cluster omic.  algo='kmeans' clusters the omic as it stands (dense or CSR, never densified whole), 'pca' its
+    dimension_reduce(n_components=100, algo='pca') and 'tsne' its dimension_reduce(n_components=2, algo='tsne') (the reference's 100 is
+    refused there).  With a cluster omic and matching_labels each cluster is named after one of its variables: corr[i, c] = the float64
+    sum of get_x_probs(cluster omic)[:, i] over the cells of cluster c, `scipy.optimize.linear_sum_assignment(corr, maximize=True)`
+    gives every variable i its cluster ids[i], and cluster ids[i] takes the name of variable i.
+    The labels [cells] (int64 ids, or names) are kept under '{omic}_{algo}{n_clusters}' until the omic or the cluster omic is replaced; a
+    later call returns what is kept, whatever its other arguments.  return_key: the key instead of the labels (for
+    `rank_vars_groups(group_by=key)`).
+    Two readings of code that is not at hand, stated as such: the reference's `odin.utils.batching(4096, n, seed=random_state)` is
+    taken as the batches (s, min(s + 4096, n)) in the order RandomState(random_state).permutation(n_batches), and its
+    `diagonal_linear_assignment` as the assignment above.  n_init is accepted and unused (partial_fit never reads it).
+    Not built: algo='knn' (spectral clustering) and 'umap' raise NotImplementedError, as does any other algo."""
+    from sisua_amd.clustering import BATCH_SIZE, match_clusters, minibatch_kmeans
+    algo = str(algo).strip().lower()
+    key = self._first(omic)
+    if key not in self._data:
+      raise ValueError(f"omic={omic!r} is not one of the omics {self.omics}")
+    cluster_omic = None
+    if n_clusters is None:
+      cluster_omic = key
+    elif isinstance(n_clusters, numbers.Number):
+      n_clusters = int(n_clusters)
+    else:
+      cluster_omic = str(n_clusters)
+      if cluster_omic not in self._data:
+        raise ValueError(f"n_clusters={n_clusters!r} is neither a number nor one of the omics {self.omics}")
+    K = self.get_dim(cluster_omic) if cluster_omic is not None else n_clusters
+    name = f"{key}_{algo}{K}"
+    if name in self._obs:
+      return name if return_key else self._obs[name][2]
+    if algo not in ("kmeans", "pca", "tsne"):
+      raise NotImplementedError(f"clustering(algo={algo!r}) is not built: only algo='kmeans', 'pca' and 'tsne' are")
+    if algo == "kmeans":
+      X = self.numpy(key)
+    else:
+      X = self.dimension_reduce(omic=key, n_components=100 if algo == "pca" else 2, algo=algo)
+    labels = minibatch_kmeans(X, K, batch_size=BATCH_SIZE, random_state=random_state).astype(np.int64)
+    if cluster_omic is not None and matching_labels:
+      ids = match_clusters(labels, self.get_x_probs(cluster_omic), K)
+      names = {int(c): n for c, n in zip(ids, self._vars[cluster_omic])}
+      labels = np.array([names[int(c)] for c in labels])
+    self._obs[name] = (key, cluster_omic, labels)
+    return name if return_key else labels
 
   def get_pca(self, omic=None):
     """The fitted `sisua_amd.PCA` of an omic (what `dimension_reduce` left), or None"""

@@ -143,7 +143,21 @@ static void model_free_entries() {
     NO_DEVICE(smx_pca_cov(x.data(), nullptr, nullptr, nullptr, N, G, 0, dout.data(), dout.data() + 64));
     NO_DEVICE(smx_pca_cov(nullptr, indptr, cols, vals, N, G, 0, dout.data(), dout.data() + 64));
     NO_DEVICE(smx_pca_project(x.data(), nullptr, nullptr, nullptr, N, G, 0, mean.data(), comp.data(), 2, out.data()));
-    NO_DEVICE(smx_pca_project(nullptr, indptr, cols, vals, N, G, 0, mean.data(), comp.data(), 2, out.data())); }
+    NO_DEVICE(smx_pca_project(nullptr, indptr, cols, vals, N, G, 0, mean.data(), comp.data(), 2, out.data()));
+    // -- mini-batch k-means on the same two forms: 2 centres, 2 trials; each entry also refuses one argument set before any staging
+    const double u[2] = {0.25, 0.75}, u_bad[2] = {0.25, 1.0};
+    std::vector<double> cent((size_t)2 * G, 0.5), cnt(2, 0.0), cnt_bad = {1.0, -1.0};
+    double inertia = 0.0;
+    NO_DEVICE(smx_mbkmeans_seed(x.data(), nullptr, nullptr, nullptr, N, G, 2, 2, 1, u, iout.data(), dout.data(), dout.data() + 64));
+    NO_DEVICE(smx_mbkmeans_seed(nullptr, indptr, cols, vals, N, G, 2, 2, 1, u, iout.data(), dout.data(), dout.data() + 64));
+    EXPECT(smx_mbkmeans_seed(x.data(), nullptr, nullptr, nullptr, N, G, 2, 2, 1, u_bad, iout.data(), dout.data(), dout.data() + 64) == SMX_ERR_INVALID);
+    EXPECT(smx_mbkmeans_seed(x.data(), nullptr, nullptr, nullptr, N, G, N + 1, 2, 1, u, iout.data(), dout.data(), dout.data() + 64) == SMX_ERR_INVALID);
+    NO_DEVICE(smx_mbkmeans_step(x.data(), nullptr, nullptr, nullptr, N, G, 2, cent.data(), cnt.data(), iout.data(), &inertia));
+    NO_DEVICE(smx_mbkmeans_step(nullptr, indptr, cols, vals, N, G, 2, cent.data(), cnt.data(), nullptr, &inertia));
+    EXPECT(smx_mbkmeans_step(x.data(), nullptr, nullptr, nullptr, N, G, 2, cent.data(), cnt_bad.data(), iout.data(), &inertia) == SMX_ERR_INVALID);
+    NO_DEVICE(smx_mbkmeans_predict(x.data(), nullptr, nullptr, nullptr, N, G, 0, 2, cent.data(), iout.data(), dout.data()));
+    NO_DEVICE(smx_mbkmeans_predict(nullptr, indptr, cols, vals, N, G, 4, 2, cent.data(), iout.data(), nullptr));
+    EXPECT(smx_mbkmeans_predict(x.data(), nullptr, nullptr, nullptr, N, G, 0, 257, cent.data(), iout.data(), nullptr) == SMX_ERR_INVALID); }
   // -- neighbours: the N cells in G dimensions, 2 others each; then the table with the cell itself in front
   { std::vector<int32_t> tidx((size_t)N * 3);
     std::vector<double> tdist((size_t)N * 3);
