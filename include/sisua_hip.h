@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 16
+#define SMX_ABI_VERSION 17
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -1070,6 +1070,39 @@ int smx_mbkmeans_step(const float* x, const int64_t* indptr, const int32_t* cols
                       int32_t n_clusters, double* centres, double* counts, int32_t* labels, double* inertia);
 int smx_mbkmeans_predict(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_rows, int32_t n_genes,
                          int32_t block_rows, int32_t n_clusters, const double* centres, int32_t* labels, double* distance);
+
+/* ---- Louvain communities of a symmetric graph (smx_louvain.hip; model-free: smx_init only) ----------- */
+/* The reference's SingleCellOMIC.louvain (scanpy.tl.louvain there) as a deterministic method: synchronous within the colour classes of a
+ * fixed colouring, every sum an exact integer (tests/louvain_ref.py restates it in NumPy and the device reproduces
+ * that label for label).  The graph: a CSR adjacency [n][n], indptr int64 [n + 1], cols int32, weights float64 or NULL (unit weights on
+ * the stored support).  Weights are quantised once, q = llrint(w / max w x 2^30); entries of q == 0 are dropped; every degree, total and
+ * internal weight is an int64 sum of q, so no result depends on the order of a row's columns, on the launch geometry or on the call.  A
+ * diagonal entry counts once in its vertex's degree k_v and once in its community's internal weight; m2 = sum k_v; Q = sum_c (in_c / m2 -
+ * resolution (tot_c / m2)^2), the communities' terms added in the halving order of the analysis kernels' fixed-order sums.
+ * Limits: 1 <= n <= 2^24, at most 2^31 - 1 entries, weights finite and >= 0, no column twice in a row, symmetric support and values,
+ * resolution and tol finite and >= 0, max_sweeps >= 1, max_levels >= 1: anything else is SMX_ERR_INVALID before any device work.
+ *
+ * smx_louvain: the whole multi-level loop.  A level colours its graph (greedy in decreasing (mix32(v), -v), self loops ignored), starts
+ * from singletons and sweeps over the colours; the vertices of one colour decide from the state at the start of the colour's turn: gain(D)
+ * = kin_D - (resolution k_v tot_D) / m2 for a neighbouring community, tot_own - k_v in place of tot_D for the own one, float64 with every
+ * operation rounded once; a vertex moves to the best (ties to the lowest id) only if that is strictly better than staying.  A level
+ * ends when a sweep moves nothing, gains at most tol in Q, or lowers Q (its labels are then put back), or after max_sweeps.  Communities
+ * are numbered in order of their lowest member and become the next level's vertices; levels repeat until one merges nothing or max_levels
+ * have run.  labels [n] int32: the final ids by decreasing size, ties to the lowest member.  *n_levels: the levels run, the last (which
+ * merged nothing) included, 0 for a graph without weight (every vertex its own community).  Per level, arrays of max_levels entries:
+ * modularity (Q at its end), level_size (its communities), sweeps, colours.  The graph crosses to the device once; the host reads back a
+ * few scalars per pair of colouring rounds, per sweep and per level.  Device memory: about 64 bytes per entry and 180 per vertex.
+ *
+ * smx_louvain_modularity: *q = Q of any partition, labels [n] int32 in 0 .. n - 1, with the same quantised integers.
+ *
+ * smx_louvain_table_degree: rows of up to this many stored entries are moved by one wave with a hash table in LDS, longer ones by one
+ * workgroup with a sort (the developer knob louvain_table_degree lowers it; no result depends on it).  Needs no device. */
+int smx_louvain(const int64_t* indptr, const int32_t* cols, const double* weights, int64_t n, double resolution, double tol,
+                int32_t max_sweeps, int32_t max_levels, int32_t* labels, int32_t* n_communities, int32_t* n_levels, double* modularity,
+                int64_t* level_size, int32_t* sweeps, int32_t* colours);
+int smx_louvain_modularity(const int64_t* indptr, const int32_t* cols, const double* weights, int64_t n, const int32_t* labels,
+                           double resolution, double* q);
+int32_t smx_louvain_table_degree(void);
 
 /* ---- padding audit (test instrument; never on the path of a step) ----------- */
 /* The layout's invariant, read back from the device: every feature axis is padded to 32 and every tensor to 64 floats, and what lies

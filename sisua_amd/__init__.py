@@ -6,6 +6,7 @@ is no CPU fallback: without the built library and a visible MI355X every
 compute entry point raises `SmxError`.
 """
 from sisua_amd._hip import SmxError  # noqa: F401
+from sisua_amd.communities import louvain, modularity  # noqa: F401
 from sisua_amd.config import ModelConfig, NetConf, RVmeta  # noqa: F401
 from sisua_amd.distributions import correlations_from_sums, protein_operands  # noqa: F401
 from sisua_amd.label_threshold import ProbabilisticEmbedding  # noqa: F401

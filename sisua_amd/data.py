@@ -316,7 +316,8 @@ class SingleCellOMIC:
     self._tsne = {}         # (omic, n_components) -> the embedding of dimension_reduce(algo='tsne'); likewise
     self._uns = {}          # the reference's .uns: 'mutualinfo_{omic}_{target}' -> (omic, target, matrix) of get_mutual_information and
                             # '{omic}_{group_by}_rank' -> (omic, grouping omic or None, dict) of rank_vars_groups; likewise
-    self._obs = {}          # the reference's .obs: '{omic}_{algo}{n_clusters}' -> (omic, cluster omic or None, labels) of clustering; likewise
+    self._obs = {}          # the reference's .obs: '{omic}_{algo}{n_clusters}' -> (omic, cluster omic or None, labels) of clustering, and
+                            # '{omic}_louvain' / '{omic}_louvain_labels' -> (omic, None, ids / names) of louvain; likewise
     self.add_omic(omic, X, var_names)
 
   def add_omic(self, omic: str, X, var_names=None):
@@ -573,7 +574,8 @@ class SingleCellOMIC:
     the argmax of `get_x_probs(omic)`, as the reference's '{omic}_labels'.  method: 't-test', 't-test_overestim_var' or 'wilcoxon'.
     The result is kept under '{omic}_{group_by}_rank' ('labels' for an array) until an omic it was made from is replaced; a later call
     returns what is kept, whatever its other arguments.  Returns the key, as the reference does: `get_rank_vars_groups(key)` gives the dict.
-    group_by may also be a key that `clustering(..., return_key=True)` left (the reference's `if str(group_by) in self.obs`): its labels
+    group_by may also be a key that `clustering(..., return_key=True)` or `louvain` ('{omic}_louvain') left (the reference's `if
+    str(group_by) in self.obs`): its labels
     are ranked, under '{omic}_{that key}_rank', until the first omic or the clustered one is replaced.  The reference's default --
     an omic's name with clustering='kmeans' -- takes two calls here: `key = sco.clustering(first omic, n_clusters=group_by,
     return_key=True)`, then `sco.rank_vars_groups(group_by=key, ...)`.
@@ -666,6 +668,42 @@ class SingleCellOMIC:
       labels = np.array([names[int(c)] for c in labels])
     self._obs[name] = (key, cluster_omic, labels)
     return name if return_key else labels
+
+  def louvain(self, omic=None, resolution=None, restrict_to=None, adjacency=None, flavor="vtraag", directed=True, use_weights=False,
+              partition_type=None, partition_kwargs={}, random_state=1):
+    """The reference's louvain (_single_cell_analysis.py:732-835, scanpy.tl.louvain there): the Louvain communities of the omic's
+    neighbour graph -- `self.neighbors(omic)[0]`, or `adjacency` (any symmetric scipy.sparse matrix over the cells) -- found on the
+    device (`sisua_amd.louvain`, smx_louvain.hip) -> (y float32 [cells], y_labels str [cells]).  resolution=None is 1.0; use_weights takes
+    the graph's weights instead of unit weights on its support.  y: the ids by decreasing size.  y_labels: each community named as in the
+    reference -- `get_x_probs(omic)` summed over its cells, thresholded (`sisua_amd.communities.threshold_variables`), the chosen
+    variables' names joined with '_'; an omic of fewer than 5 variables names a community str(id).  The ids (int64) are kept under
+    '{omic}_louvain' and the names under '{omic}_louvain_labels' until the omic is replaced, and a later call returns what is kept,
+    whatever its arguments; `rank_vars_groups(group_by='{omic}_louvain')` ranks the communities.
+    Deviations: the method is deterministic, so random_state is accepted and unused; a symmetric graph has one
+    modularity, so `directed` is accepted either way; flavor 'vtraag' and 'igraph' are the same call; restrict_to, partition_type and a
+    non-empty partition_kwargs raise NotImplementedError; the names come from `sisua_amd.GaussianMixture`, not scikit-learn's."""
+    from sisua_amd import communities
+    if restrict_to is not None or partition_type is not None or partition_kwargs:
+      raise NotImplementedError("louvain(restrict_to=, partition_type=, partition_kwargs=) are not built: only the modularity partition "
+                                "of all cells is")
+    if flavor not in ("vtraag", "igraph"):
+      raise ValueError(f"flavor must be 'vtraag' or 'igraph', got {flavor!r}")
+    key = self._first(omic)
+    if key not in self._data:
+      raise ValueError(f"omic={omic!r} is not one of the omics {self.omics}")
+    name, name_labels = f"{key}_louvain", f"{key}_louvain_labels"
+    if name not in self._obs:
+      if adjacency is not None and (not hasattr(adjacency, "shape") or tuple(adjacency.shape) != (self.n_obs, self.n_obs)):
+        raise ValueError(f"adjacency must be a sparse matrix [{self.n_obs}, {self.n_obs}] over the cells")
+      graph = self.neighbors(key)[0] if adjacency is None else adjacency
+      ids = communities.louvain(graph, resolution=1.0 if resolution is None else resolution, use_weights=bool(use_weights))
+      self._obs[name] = (key, None, ids)
+      self._obs.pop(name_labels, None)
+    ids = self._obs[name][2]
+    if name_labels not in self._obs:
+      names = communities.community_names(ids, self.get_x_probs(key), self._vars[key])
+      self._obs[name_labels] = (key, None, np.array([names[int(c)] for c in ids]))
+    return ids.astype(np.float32), self._obs[name_labels][2]
 
   def get_pca(self, omic=None):
     """The fitted `sisua_amd.PCA` of an omic (what `dimension_reduce` left), or None"""

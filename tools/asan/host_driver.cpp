@@ -164,6 +164,32 @@ static void model_free_entries() {
     for (int i = 0; i < N; ++i) for (int c = 0; c < 3; ++c) { tidx[(size_t)i * 3 + c] = (i + c) % N; tdist[(size_t)i * 3 + c] = 0.5 * c; }
     NO_DEVICE(smx_knn(x.data(), N, G, 2, iout.data(), dout.data()));
     NO_DEVICE(smx_knn_umap(tidx.data(), tdist.data(), N, 3, dout.data(), dout.data() + 64, dout.data() + 128)); }
+  // -- Louvain: a ring of the N vertices, columns out of order; the host's checks (two transposes) and the quantisation run before the device is
+  //    asked for; a graph without weight needs no device at all
+  { int64_t indptr[N + 1], lsize[4];
+    int32_t cols[2 * N], labels[N], nc = 0, nl = 0, sweeps[4], colours[4];
+    double w[2 * N], q[4], qq = 1.0;
+    for (int i = 0; i <= N; ++i) indptr[i] = 2 * i;
+    for (int i = 0; i < N; ++i) {
+      cols[2 * i] = (i + 1) % N; cols[2 * i + 1] = (i + N - 1) % N;
+      w[2 * i] = 1.0 + ((i + 1) % N == 0 ? 0 : i); w[2 * i + 1] = 1.0 + ((i + N - 1) % N == N - 1 ? 0 : i - 1);   // w(i, i + 1) = 1 + i, the closing edge 1
+    }
+    w[1] = 1.0;
+    NO_DEVICE(smx_louvain(indptr, cols, nullptr, N, 1.0, 1e-7, 10, 4, labels, &nc, &nl, q, lsize, sweeps, colours));
+    NO_DEVICE(smx_louvain(indptr, cols, w, N, 1.0, 1e-7, 10, 4, labels, &nc, &nl, q, lsize, sweeps, colours));
+    NO_DEVICE(smx_louvain_modularity(indptr, cols, w, N, labels, 1.0, &qq));
+    EXPECT(smx_louvain_table_degree() >= 64);
+    { double bad[2 * N]; memcpy(bad, w, sizeof(bad)); bad[0] += 1.0;   // the values are not symmetric
+      EXPECT(smx_louvain(indptr, cols, bad, N, 1.0, 1e-7, 10, 4, labels, &nc, &nl, q, lsize, sweeps, colours) == SMX_ERR_INVALID); }
+    { int32_t bad[2 * N]; memcpy(bad, cols, sizeof(bad)); bad[0] = 3;   // the support is not
+      EXPECT(smx_louvain(indptr, bad, nullptr, N, 1.0, 1e-7, 10, 4, labels, &nc, &nl, q, lsize, sweeps, colours) == SMX_ERR_INVALID); }
+    { int32_t bad[2 * N]; memcpy(bad, cols, sizeof(bad)); bad[1] = bad[0];   // a column twice
+      EXPECT(smx_louvain(indptr, bad, nullptr, N, 1.0, 1e-7, 10, 4, labels, &nc, &nl, q, lsize, sweeps, colours) == SMX_ERR_INVALID); }
+    EXPECT(smx_louvain(indptr, cols, nullptr, N, -1.0, 1e-7, 10, 4, labels, &nc, &nl, q, lsize, sweeps, colours) == SMX_ERR_INVALID);
+    { const double zero[2 * N] = {0.0};
+      EXPECT(smx_louvain(indptr, cols, zero, N, 1.0, 1e-7, 10, 4, labels, &nc, &nl, q, lsize, sweeps, colours) == SMX_OK);
+      EXPECT(nc == N && nl == 0 && labels[N - 1] == N - 1);
+      EXPECT(smx_louvain_modularity(indptr, cols, zero, N, labels, 1.0, &qq) == SMX_OK && qq == 0.0); } }
 }
 
 int main() {
