@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 17
+#define SMX_ABI_VERSION 18
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -1103,6 +1103,46 @@ int smx_louvain(const int64_t* indptr, const int32_t* cols, const double* weight
 int smx_louvain_modularity(const int64_t* indptr, const int32_t* cols, const double* weights, int64_t n, const int32_t* labels,
                            double resolution, double* q);
 int32_t smx_louvain_table_degree(void);
+
+/* ---- L2-penalised logistic regression on the count matrix (smx_logreg.hip; model-free: smx_init only) ----------- */
+/* What the reference's rank_vars_groups(method='logreg') asks of scikit-learn's LogisticRegression, as a deterministic full-batch solve
+ * (tests/logreg_ref.py restates it in NumPy).  The host matrix comes in the forms of smx_prep_stats and is held whole in
+ * one device tile [n_rows rounded up to 64][ld] float32, ld = n_genes rounded up to 4, across all iterations.  labels [n_rows] int32 in
+ * 0 .. n_classes - 1; a fit needs at least one row of every class, an evaluation does not.  The objective, scikit-learn's in its mean form:
+ *   F(W, b) = (1/N) sum_i loss_i + ||W||^2 / (2 C N), the intercept unpenalised (fit_intercept = 0: b is taken as 0 and gb is 0)
+ * form 0, multinomial, 3 <= n_classes <= 256: W [n_classes][n_genes], b [n_classes] float64, loss_i = logsumexp(z_i) - z_{i, y_i}.
+ * form 1, binary, n_classes = 2: ONE logit row, W [1][n_genes], b [1], loss_i = softplus(z_i) - y_i z_i (what scikit-learn fits for two
+ * classes; not the two-class softmax, whose penalty differs by a factor of two).  Below Kz is the number of logit rows.
+ * Everything is float64 from the float32 matrix on, every sum has an order that is a function of the shape alone and there are no
+ * atomics: dense and CSR input give the same bits, and so do two calls.  A logit: each of 64 lanes adds its columns 256 i + 4 l .. + 3 in
+ * rising order by fma from 0, the lanes by halving, the intercept last.  The gradient g_kj = (1/N) sum_i r_ik x_ij + w_kj / (C N), r_ik =
+ * p_ik - [y_i = k]: slices of 64 global row ids in row order, then the slices in order; g_b,k = (1/N) sum_i r_ik.
+ * Limits: n_genes <= 32768, n_rows < 2^31, rows x ld <= 2^31; C finite and > 0; matrix values, weights and intercepts finite: anything
+ * else, a null pointer, a label out of range, a fit with a class without a row or a malformed CSR is SMX_ERR_INVALID before any device work.
+ * Device memory: the tile, the staged CSR, 8 x n_rows x (Kz rounded up to 4), 8 x (n_rows / 64) x Kz x ld for the slices' partials
+ * and, for the fit, 27 vectors of 8 x Kz x ld bytes.
+ *
+ * smx_logreg_eval: *F, gW [Kz][n_genes] and gb [Kz] at the given (W, b): the two matrix launches and their two closing launches alone.
+ *
+ * smx_logreg_fit: L-BFGS with memory 10 from zero (W0 = b0 = NULL) or from (W0, b0), all vectors on the device.  Armijo backtracking,
+ * F(theta + t d) <= F + 1e-4 t g.d: the first trial is t = 1, or 1 / max|g| on the first iteration; each failure halves t; at most 30
+ * trials (then the solve ends unconverged).  Where a trial changes F by at most 2^-43 |F| -- the rounding of two evaluations -- the
+ * Armijo test would decide on noise: the trial is then accepted if it lowers max|g|.  A pair with s.y <= 0 is skipped.  It stops when max(|gW|, |gb|) <= tol (tol finite and > 0)
+ * or after max_iter >= 1 iterations.  Out: W, b, *F and *gmax at them, *n_iter, *n_eval (evaluations of F and g), *converged.  An
+ * objective that is not finite at the start point is SMX_ERR_NAN.  The host reads two scalars per evaluation and up to 69 dot products
+ * per iteration.
+ *
+ * smx_logreg_decision: logits [n_rows][Kz] float64 (z = x.w + b as above), the matrix streamed in blocks of block_rows rows as in
+ * smx_prep_stats (0: the library's choice); no bit depends on it. */
+int smx_logreg_eval(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_rows, int32_t n_genes,
+                    const int32_t* labels, int32_t n_classes, int32_t form, double C, int32_t fit_intercept, const double* W, const double* b,
+                    double* F, double* gW, double* gb);
+int smx_logreg_fit(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_rows, int32_t n_genes,
+                   const int32_t* labels, int32_t n_classes, int32_t form, double C, int32_t fit_intercept, double tol, int32_t max_iter,
+                   const double* W0, const double* b0, double* W, double* b, double* F, double* gmax, int32_t* n_iter, int32_t* n_eval,
+                   int32_t* converged);
+int smx_logreg_decision(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_rows, int32_t n_genes,
+                        int32_t block_rows, int32_t n_classes, int32_t form, const double* W, const double* b, double* logits);
 
 /* ---- padding audit (test instrument; never on the path of a step) ----------- */
 /* The layout's invariant, read back from the device: every feature axis is padded to 32 and every tensor to 64 floats, and what lies

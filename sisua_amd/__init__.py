@@ -10,11 +10,12 @@ from sisua_amd.communities import louvain, modularity  # noqa: F401
 from sisua_amd.config import ModelConfig, NetConf, RVmeta  # noqa: F401
 from sisua_amd.distributions import correlations_from_sums, protein_operands  # noqa: F401
 from sisua_amd.label_threshold import ProbabilisticEmbedding  # noqa: F401
+from sisua_amd.logistic import LogisticRegression  # noqa: F401
 from sisua_amd.metrics import correlation_list, marker_correlations, marker_scores  # noqa: F401
 from sisua_amd.minibatch_kmeans import MiniBatchKMeans  # noqa: F401
 from sisua_amd.mixture import GaussianMixture  # noqa: F401
 from sisua_amd.mutual_info import mutual_information  # noqa: F401
 from sisua_amd.neighbors import PCA, TSNE  # noqa: F401
-from sisua_amd.rank_groups import rank_genes_groups  # noqa: F401
+from sisua_amd.rank_groups import rank_genes_groups, rank_genes_groups_logreg  # noqa: F401
 
 __version__ = "0.1.0"

@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsisua_hip.so")
 
-SMX_ABI_VERSION = 17
+SMX_ABI_VERSION = 18
 SMX_MAX_LAYERS = 8
 SMX_MAX_LABELS = 4
 
@@ -216,6 +216,11 @@ SIGNATURES = {
     "smx_louvain": (C.c_int, [_LP, _IP, _DP, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_int32, _IP, _IP, _IP, _DP, _LP, _IP, _IP]),
     "smx_louvain_modularity": (C.c_int, [_LP, _IP, _DP, C.c_int64, _IP, C.c_double, _DP]),
     "smx_louvain_table_degree": (C.c_int32, []),
+    "smx_logreg_eval": (C.c_int, [_FP, _LP, _IP, _FP, C.c_int64, C.c_int32, _IP, C.c_int32, C.c_int32, C.c_double, C.c_int32, _DP, _DP, _DP, _DP,
+                                  _DP]),
+    "smx_logreg_fit": (C.c_int, [_FP, _LP, _IP, _FP, C.c_int64, C.c_int32, _IP, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32,
+                                 _DP, _DP, _DP, _DP, _DP, _DP, _IP, _IP, _IP]),
+    "smx_logreg_decision": (C.c_int, [_FP, _LP, _IP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, _DP, _DP]),
     "smx_pad_audit": (C.c_int, [_VP, C.c_int32, _LP, _IP, _LP, C.c_char_p, C.c_int32]),
     "smx_pad_poke": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_float]),
 }

@@ -571,7 +571,9 @@ class SingleCellOMIC:
     """The reference's rank_vars_groups (_single_cell_analysis.py:862-918, scanpy.tl.rank_genes_groups there): the variables of the FIRST
     omic ranked for characterising groups of cells (`sisua_amd.rank_genes_groups`; the matrix work runs on the device, smx_rankgroups.hip).
     group_by: a [cells] array of labels, or the name of an omic with clustering=None -- each cell's label is then the variable name at
-    the argmax of `get_x_probs(omic)`, as the reference's '{omic}_labels'.  method: 't-test', 't-test_overestim_var' or 'wilcoxon'.
+    the argmax of `get_x_probs(omic)`, as the reference's '{omic}_labels'.  method: 't-test', 't-test_overestim_var', 'wilcoxon', or
+    'logreg' (the reference's default: `sisua_amd.rank_genes_groups_logreg`, one L2-penalised logistic regression solved on the device,
+    smx_logreg.hip, with at most max_iter iterations; its dict holds 'params', 'names' and 'scores' only, and corr_method is ignored).
     The result is kept under '{omic}_{group_by}_rank' ('labels' for an array) until an omic it was made from is replaced; a later call
     returns what is kept, whatever its other arguments.  Returns the key, as the reference does: `get_rank_vars_groups(key)` gives the dict.
     group_by may also be a key that `clustering(..., return_key=True)` or `louvain` ('{omic}_louvain') left (the reference's `if
@@ -580,13 +582,11 @@ class SingleCellOMIC:
     an omic's name with clustering='kmeans' -- takes two calls here: `key = sco.clustering(first omic, n_clusters=group_by,
     return_key=True)`, then `sco.rank_vars_groups(group_by=key, ...)`.
     Deviations: there is no use_raw (the omic is ranked as it stands); an omic's name with clustering='kmeans' (the reference's
-    default) raises NotImplementedError naming clustering=None; logistic regression (the reference's default method) is not built and
-    raises NotImplementedError; max_iter belongs to it and is unused."""
-    from sisua_amd.rank_groups import METHODS, rank_genes_groups
+    default) raises NotImplementedError naming clustering=None, whatever the method; max_iter belongs to method='logreg' and is unused
+    by the others."""
+    from sisua_amd.rank_groups import METHODS, rank_genes_groups, rank_genes_groups_logreg
     built = (f"rank_vars_groups is built for method in {METHODS} with group_by a [cells] label array or an omic's name with "
              "clustering=None")
-    if method == "logreg":
-      raise NotImplementedError(f"method='logreg' is not built: {built}")
     om1 = self.omics[0]
     kept = None
     if isinstance(group_by, str) and group_by in self._obs:
@@ -610,8 +610,13 @@ class SingleCellOMIC:
           raise ValueError(f"group_by must be [{self.n_obs}] labels, got {labels.shape}")
       else:
         labels = np.asarray(self._vars[om2])[np.argmax(self.get_x_probs(om2), axis=1)]
-      self._uns[key] = (om1, om2, rank_genes_groups(self.numpy(om1), labels, reference=reference, method=method, corr_method=corr_method,
-                                                   n_genes=int(n_vars), var_names=self._vars[om1]))
+      if method == "logreg":   # (corr_method is ignored, as in the reference: a logistic fit has no p-values)
+        res = rank_genes_groups_logreg(self.numpy(om1), labels, reference=reference, n_genes=int(n_vars), var_names=self._vars[om1],
+                                       max_iter=int(max_iter))
+      else:
+        res = rank_genes_groups(self.numpy(om1), labels, reference=reference, method=method, corr_method=corr_method, n_genes=int(n_vars),
+                                var_names=self._vars[om1])
+      self._uns[key] = (om1, om2, res)
     return key
 
   def get_rank_vars_groups(self, key):

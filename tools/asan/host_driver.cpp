@@ -3,6 +3,7 @@
 // `hipcc --cuda-host-only -fsanitize=address,undefined` (no device code, no GPU needed) and this program walks what can run without a device:
 // the ABI queries, smx_shuffle_order, every argument / configuration check of smx_model_create up to its first device call, and the error paths
 // of the accessors on a null model.  Any sanitizer report aborts with a non-zero status; "HOST DRIVER OK" is printed last.
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -157,7 +158,47 @@ static void model_free_entries() {
     EXPECT(smx_mbkmeans_step(x.data(), nullptr, nullptr, nullptr, N, G, 2, cent.data(), cnt_bad.data(), iout.data(), &inertia) == SMX_ERR_INVALID);
     NO_DEVICE(smx_mbkmeans_predict(x.data(), nullptr, nullptr, nullptr, N, G, 0, 2, cent.data(), iout.data(), dout.data()));
     NO_DEVICE(smx_mbkmeans_predict(nullptr, indptr, cols, vals, N, G, 4, 2, cent.data(), iout.data(), nullptr));
-    EXPECT(smx_mbkmeans_predict(x.data(), nullptr, nullptr, nullptr, N, G, 0, 257, cent.data(), iout.data(), nullptr) == SMX_ERR_INVALID); }
+    EXPECT(smx_mbkmeans_predict(x.data(), nullptr, nullptr, nullptr, N, G, 0, 257, cent.data(), iout.data(), nullptr) == SMX_ERR_INVALID);
+    // -- logistic regression on the same two forms: three classes (multinomial) and two (binary, one logit row); every refusal -- a label out
+    //    of range, a class without a row, C, tol, max_iter, a value that is not finite, a form that does not fit the classes -- before any staging
+    const int32_t y3[N] = {0, 1, 2, 0, 1, 2}, y2[N] = {0, 1, 0, 1, 0, 1}, y_out[N] = {0, 1, 3, 0, 1, 2}, y_gap[N] = {0, 2, 2, 0, 2, 2};
+    std::vector<double> W((size_t)3 * G, 0.1), b(3, 0.0), gW((size_t)3 * G), gb(3), W_nan = W;
+    W_nan[5] = NAN;
+    std::vector<float> x_inf = x;
+    x_inf[7] = INFINITY;
+    double F = 0.0, gmax = 0.0;
+    int32_t n_iter = 0, n_eval = 0, conv = 0;
+    auto eval = [&](const float* xd, const int32_t* y, int K, int form, double C, const double* w) {
+      return smx_logreg_eval(xd, xd ? nullptr : indptr, xd ? nullptr : cols, xd ? nullptr : vals, N, G, y, K, form, C, 1, w, b.data(), &F, gW.data(), gb.data());
+    };
+    auto fit = [&](const float* xd, const int32_t* y, int K, int form, double C, double tol, int max_iter, const double* w0, const double* b0) {
+      return smx_logreg_fit(xd, xd ? nullptr : indptr, xd ? nullptr : cols, xd ? nullptr : vals, N, G, y, K, form, C, 1, tol, max_iter, w0, b0, gW.data(),
+                            gb.data(), &F, &gmax, &n_iter, &n_eval, &conv);
+    };
+    NO_DEVICE(eval(x.data(), y3, 3, 0, 1.0, W.data()));
+    NO_DEVICE(eval(nullptr, y2, 2, 1, 0.5, W.data()));
+    NO_DEVICE(fit(x.data(), y2, 2, 1, 1.0, 1e-4, 10, nullptr, nullptr));
+    NO_DEVICE(fit(nullptr, y3, 3, 0, 1.0, 1e-4, 10, W.data(), b.data()));
+    NO_DEVICE(smx_logreg_decision(x.data(), nullptr, nullptr, nullptr, N, G, 0, 3, 0, W.data(), b.data(), dout.data()));
+    NO_DEVICE(smx_logreg_decision(nullptr, indptr, cols, vals, N, G, 4, 2, 1, W.data(), b.data(), dout.data()));
+    EXPECT(eval(x.data(), y_out, 3, 0, 1.0, W.data()) == SMX_ERR_INVALID);
+    NO_DEVICE(eval(x.data(), y_gap, 3, 0, 1.0, W.data()));                   // (an evaluation needs no row of every class; a fit does)
+    EXPECT(fit(x.data(), y_gap, 3, 0, 1.0, 1e-4, 10, nullptr, nullptr) == SMX_ERR_INVALID);
+    EXPECT(eval(x.data(), y3, 3, 0, 0.0, W.data()) == SMX_ERR_INVALID);
+    EXPECT(eval(x.data(), y3, 3, 0, 1.0, W_nan.data()) == SMX_ERR_INVALID);
+    EXPECT(eval(x.data(), y3, 3, 0, 1.0, nullptr) == SMX_ERR_INVALID);
+    EXPECT(eval(x_inf.data(), y3, 3, 0, 1.0, W.data()) == SMX_ERR_INVALID);
+    EXPECT(eval(x.data(), y3, 3, 1, 1.0, W.data()) == SMX_ERR_INVALID);      // the binary form with three classes
+    EXPECT(eval(x.data(), y2, 2, 0, 1.0, W.data()) == SMX_ERR_INVALID);      // the multinomial form with two
+    EXPECT(eval(x.data(), y3, 257, 0, 1.0, W.data()) == SMX_ERR_INVALID);
+    EXPECT(fit(x.data(), y3, 3, 0, 1.0, 0.0, 10, nullptr, nullptr) == SMX_ERR_INVALID);
+    EXPECT(fit(x.data(), y3, 3, 0, 1.0, NAN, 10, nullptr, nullptr) == SMX_ERR_INVALID);
+    EXPECT(fit(x.data(), y3, 3, 0, 1.0, 1e-4, 0, nullptr, nullptr) == SMX_ERR_INVALID);
+    EXPECT(fit(x.data(), y3, 3, 0, -1.0, 1e-4, 10, nullptr, nullptr) == SMX_ERR_INVALID);
+    EXPECT(fit(x.data(), y3, 3, 0, 1.0, 1e-4, 10, W.data(), nullptr) == SMX_ERR_INVALID);   // half a warm start
+    EXPECT(fit(x.data(), y3, 3, 0, 1.0, 1e-4, 10, W_nan.data(), b.data()) == SMX_ERR_INVALID);
+    EXPECT(smx_logreg_decision(x.data(), nullptr, nullptr, nullptr, N, G, -1, 3, 0, W.data(), b.data(), dout.data()) == SMX_ERR_INVALID);
+    EXPECT(smx_logreg_decision(x.data(), nullptr, nullptr, nullptr, N, G, 0, 3, 0, W.data(), b.data(), nullptr) == SMX_ERR_INVALID); }
   // -- neighbours: the N cells in G dimensions, 2 others each; then the table with the cell itself in front
   { std::vector<int32_t> tidx((size_t)N * 3);
     std::vector<double> tdist((size_t)N * 3);
