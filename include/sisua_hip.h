@@ -629,6 +629,11 @@ int32_t smx_head_dw_late(const smx_model* m);
  * place (eager steps of one GPU under Adam, every step of a call but its last: DESIGN.md section 4; knob no_lazy_adam).  The tests' check
  * that this form is what ran. */
 int32_t smx_lazy_adam_steps(const smx_model* m);
+/* How many steps of the model's LAST smx_train_steps call ran the decoder's BatchNorm-backward launch (carrying the output head's dW) and the
+ * encoder's (with the d z product folded in) as ONE launch whose encoder workgroups wait inside it for the decoder's d pre-activation (one
+ * decoder layer of 128 units, an encoder of at most 128, at most 128 cells, one GPU, eager untimed steps: DESIGN.md section 4; knob
+ * no_bwd_seam).  A wait that gives up sets an error word: the next metrics read-back fails with a message naming the seam. */
+int32_t smx_bwd_seam_steps(const smx_model* m);
 
 /* ---- kernel-level entry points (parity tests of single kernels) ------------ */
 /* Fused count log-likelihood forward+backward over host planes [k][B][G]:

@@ -168,6 +168,7 @@ SIGNATURES = {
     "smx_head_fused_bytes": (C.c_int64, [_VP, C.c_int32]),
     "smx_head_dw_late": (C.c_int32, [_VP]),
     "smx_lazy_adam_steps": (C.c_int32, [_VP]),
+    "smx_bwd_seam_steps": (C.c_int32, [_VP]),
     "smx_k_count_llk": (C.c_int, [C.c_int, C.c_int, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP]),
     "smx_k_head_fused": (C.c_int, [C.c_int, C.c_int, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32, C.c_float, C.c_int32, _FP, _FP, _FP, _FP, _FP,
                                    _FP]),

@@ -257,6 +257,42 @@ struct MlpBwdOpts {
   // the LAST layer's wide BatchNorm-backward launch also carries the output head's dW / db (bn_wide_bwd_dw_kernel; dw_late below)
   const HeadBwdArgs* head_dw = nullptr;
 };
+// ---- the seam form: the decoder's carrier launch (dw_late) and the encoder's fold_dz launch behind it as ONE launch (smx_bn.hip: bn_bwd_seam_kernel) ----
+// Both are latency-bound links of the step's chain, and the second one's 16 chain workgroups wait for nothing but the 64 KB of d pre_dec the first
+// one's columns write: held in one launch they start their independent prologue at once and wait inside it (smx_handoff.h).  Taken when dw_late_now
+// and fold_dz_now hold, the carrier's layer is the decoder's only one (its d pre IS the fold's zD), on one GPU without SyncBatchNorm, outside a
+// timed step and outside graph capture (the wait's target is an argument).  Knob no_bwd_seam (read per step): the two launches.
+// The head's optimiser riders read what the carrier's dW tiles write, so they cannot ride here: their chunks go with the optimiser launch (or the
+// lazy set of the next step's first launch), as under the knob no_adam_early -- the same update, bit for bit.
+static bool seam_wanted(const smx_model* m, const Pass& ps) {
+  return m->dw_late_now && m->fold_dz_now && m->dec.size() == 1 && !dp_active(m) && !m->comm && !m->local && !m->p2p && m->world == 1 && !m->sync_bn && !sync_bn_on(m, ps.training) &&
+         m->timing_label.empty() && !m->capturing && !m->lazy_rest_pending && m->enc.back().out_p / 8 <= HANDOFF_MAX_WAITERS && !tuning_on("no_bwd_seam");
+}
+// the carrier alone after all (the encoder's launch did not take it along)
+static int seam_flush(smx_model* m) {
+  if (!m->seam_pending) return SMX_OK;
+  m->seam_pending = false;
+  return launch_bn_wide_bwd_dw(m->st, m->seam_dec, m->seam_head);
+}
+static int seam_launch(smx_model* m, const BnBwdArgs& enc) {
+  m->seam_pending = false;
+  if (!m->seam_state) {
+    SMX_HIP(hipMalloc((void**)&m->seam_state, HANDOFF_STATE_BYTES));
+    m->seam_epochs = 0;
+  }
+  if (m->seam_epochs == 0) SMX_HIP(hipMemsetAsync(m->seam_state, 0, HANDOFF_STATE_BYTES, m->st));   // once per library call: the counter counts within it
+  BwdSeamArgs sm;
+  sm.seam.counter = m->seam_state; sm.seam.error = m->seam_state + HANDOFF_MAX_SHARDS * HANDOFF_SHARD_STRIDE;
+  sm.seam.shards = HANDOFF_MAX_SHARDS;
+  sm.seam.target = (unsigned)m->seam_dec.Hp * (m->seam_epochs + 1);
+  sm.seam.timeout_ticks = (long long)(std::min(std::max((double)tuning("bwd_seam_timeout_s", 2.0), 0.01), 60.0) * 1e8);
+  sm.preread = tuning_on("bwd_seam_preread") ? 1 : 0;
+  sm.cons_first = tuning_on("bwd_seam_cons_first") ? 1 : 0;
+  SMX_CHECK(launch_bn_bwd_seam(m->st, m->seam_dec, enc, m->seam_head, sm));
+  ++m->seam_epochs; ++m->seam_steps;
+  return SMX_OK;
+}
+
 static int mlp_backward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps, Mat in0, bool in_is_x, int n_slabs, const MlpBwdOpts& o) {
   auto make_b = [&](MlpLayer& L, int slabs, const BnBwdArgs* front) {
     BnBwdArgs b;
@@ -298,6 +334,10 @@ static int mlp_backward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps
     have_carried = false;
     const bool dpre_ready = dpre_done;
     dpre_done = false;
+    // (the seam form: the decoder's carrier launch is waiting for the encoder's fold_dz launch -- this one, or it goes out alone first)
+    const bool seam = m->seam_pending && &mlp == &m->enc && last && b.front && b.fold_dz && !o.last_bn_done && !dpre_ready && !(sync_bn_on(m, ps.training) && L.bn >= 0) &&
+                      !(m->metrics_before_allreduce && m->have_pending_metrics) && bn_bwd_seam_supported(m->seam_dec, b, m->seam_head);
+    if (m->seam_pending && &mlp != &m->dec && !seam) SMX_CHECK(seam_flush(m));
     if ((last && o.last_bn_done) || dpre_ready) {
       // (this layer's BatchNorm-backward ran beside the other MLP's / its d pre-activation came with the product above)
     } else if (sync_bn_on(m, ps.training) && L.bn >= 0) {   // the ELBO scalars then go with a launch of their own (optimizer_pass)
@@ -313,7 +353,9 @@ static int mlp_backward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps
       }
       // (the carrier WRITES dW_out and its slots: the head's riders wait -- adam_early_pending stays set -- for the next BatchNorm-backward launch)
       const HeadBwdArgs* hd = (last && o.head_dw && bn_wide_bwd_dw_supported(b, *o.head_dw)) ? o.head_dw : nullptr;
-      if (!hd) attach_early_adam(m, b);
+      // (the seam form: the head's riders would read what the launch's dW tiles write -- their chunks stay with the optimiser launch / the lazy set)
+      if (seam) m->adam_early_pending = false;
+      else if (!hd) attach_early_adam(m, b);
       // (the carrier has rider slots and no riders of this step -- they wait for the encoder's launch --: W_enc's chunks of the step BEFORE, which
       // the forward pass left pending for this launch (fwd_encoder: lazy_w_late), ride here with that step's arguments.  Nothing since this step's
       // first launch reads W_enc, and its gradient and slots are rewritten by the weight-gradient launch, behind this one)
@@ -332,10 +374,17 @@ static int mlp_backward(smx_model* m, std::vector<MlpLayer>& mlp, const Pass& ps
       const bool dual = last && b.front && b.fK <= 64 && o.twin && o.twin_front && o.twin_front->fK <= 64 && !o.twin->empty() && m->flags.twin && bn_dual_supported(ps.B) &&
                         bn_bwd_front_supported(ps.B, o.twin_front->fK) && o.twin->back().out_p % 8 == 0 &&
                         !(sync_bn_on(m, ps.training) && o.twin->back().bn >= 0);
-      if (hd) {
+      if (hd && &mlp == &m->dec && (w_rides || !m->lazy_w_pending) && seam_wanted(m, ps)) {
+        // held back: the encoder's fold_dz launch takes the carrier along (seam_launch) -- nothing is launched in between
+        m->seam_dec = b; m->seam_head = *hd; m->seam_pending = true;
+        dw_carried = true;
+        if (w_rides) m->lazy_w_pending = false;
+      } else if (hd) {
         SMX_CHECK(launch_bn_wide_bwd_dw(m->st, b, *hd));
         dw_carried = true;
         if (w_rides) m->lazy_w_pending = false;
+      } else if (seam) {
+        SMX_CHECK(seam_launch(m, b));
       } else if (dual) {
         const BnBwdArgs b2 = make_b(o.twin->back(), 0, o.twin_front);
         SMX_CHECK(launch_bn_act_bwd_dual(m->st, b, b2));

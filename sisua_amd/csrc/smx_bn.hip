@@ -3,6 +3,7 @@
 // The backward launches carry the step's ELBO scalars and optimiser chunks as riders (smx_adam.h).
 #include "smx_internal.h"
 #include "smx_adam.h"
+#include "smx_handoff.h"
 
 namespace smx {
 
@@ -543,7 +544,10 @@ __device__ inline bnf_f32x4 bnf_mfma16x3(const Split8& a, const Split8& b, bnf_f
 }
 #define SMX_FOLD_WROW 136   /* bf16 per row of the W image: 128 + 8 (rows 272 bytes apart: 16-byte reads of 16 rows spread over the banks) */
 #define SMX_FOLD_WIMG_BYTES (3 * 32 * SMX_FOLD_WROW * 2)
-__device__ inline void fold_dz_tile(const BnBwdArgs& a, const int bid, float* tile, const int ldd, unsigned char* wimg) {
+// SEAM (bn_bwd_seam_kernel): zD is written by other workgroups of THIS launch -- everything that does not read it first ((1), (2) and
+// what the caller requested before), then the wait of smx_handoff.h, then (3) behind its acquire.  false: the wait gave up (nothing stored).
+template <bool SEAM = false>
+__device__ inline bool fold_dz_tile(const BnBwdArgs& a, const int bid, float* tile, const int ldd, unsigned char* wimg, const BwdSeamArgs* sm = nullptr, int* seam_ok = nullptr) {
   const EpiLatentBwd& e = a.zlb;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, kg = lane >> 4;
   // (1) what the latent backward reads at the accumulators' positions -- cell 16 w + 4 kg + r, latent dim 16 nb + li -- requested first (64-byte runs per
@@ -571,6 +575,12 @@ __device__ inline void fold_dz_tile(const BnBwdArgs& a, const int bid, float* ti
     row[0] = sp.t0;
     row[(32 * SMX_FOLD_WROW * 2) / 16] = sp.t1;
     row[(2 * 32 * SMX_FOLD_WROW * 2) / 16] = sp.t2;
+  }
+  if constexpr (SEAM) {
+    if (sm->preread) {   // (diagnostic: every line of zD into this CU's L1 ahead of the wait -- what a missing acquire would then read)
+      for (int i = tid; i < a.B * 4; i += BN_THREADS) { const float t = a.zD[(long)(i >> 2) * a.zld + (i & 3) * 32]; asm volatile("" ::"v"(t)); }
+    }
+    if (!handoff_wait<true>(sm->seam, seam_ok)) return false;
   }
   // (3) the wave's rows of zD in the A operand's layout
   Split8 A[4];
@@ -615,6 +625,7 @@ __device__ inline void fold_dz_tile(const BnBwdArgs& a, const int bid, float* ti
         if (bid == 0) { e.dlat[(long)b * e.ld + d] = o0; e.dlat[(long)b * e.ld + e.Dp + d] = o1; }
       }
     }
+  return true;
 }
 
 // GEN_ACT forms: the multiplier the forward applied to element (r, col) -- from the same source, bit for bit (BnBwdArgs::act)
@@ -630,12 +641,13 @@ __device__ inline float bn_gen_dy(const BnBwdArgs& a, int r, int col, float dout
   return dout * bn_keep(a, r, col) * act_grad(a.act, act_fwd(a.act, y));
 }
 
-template <int RPT, int FRONT, bool GEN_ACT = false>
-__device__ inline void bn_act_bwd_body(const BnBwdArgs& a, const int bid) {
+template <int RPT, int FRONT, bool GEN_ACT = false, bool SEAM = false>
+__device__ inline void bn_act_bwd_body(const BnBwdArgs& a, const int bid, const BwdSeamArgs* sm = nullptr) {
   constexpr bool SMALL = RPT > 0;
   constexpr int BN_RPT = SMALL ? RPT : BN_RPT_DEFAULT;
+  static_assert(!SEAM || (FRONT == 1 && !GEN_ACT), "the seam form is the fold_dz front's");
   extern __shared__ __attribute__((aligned(16))) float ds[];   // FRONT: d lat tile [B][fK + 4] | this workgroup's rows of W [8][fK + 4]
-  {
+  if constexpr (!SEAM) {   // (bn_bwd_seam_kernel deals its riders itself)
     const int nb = a.Hp / BN_COLS, extra = bid - nb;
     if (extra >= 0) {
       const int e = extra - (a.with_metrics ? 1 : 0);
@@ -690,6 +702,10 @@ __device__ inline void bn_act_bwd_body(const BnBwdArgs& a, const int bid) {
     const bool wl_on = (int)threadIdx.x < BN_COLS * kq && !(a.diag & 64);   // (8 rows x fK / 4 <= 256 float4: one per thread)
     if (wl_on) wl = *reinterpret_cast<const float4*>(a.fW + (long)(bid * BN_COLS + ((int)threadIdx.x >> ksh)) * a.fldw + ((int)threadIdx.x & kmask) * 4);
     if (FRONT == 1 && a.fold_dz) {   // (block-uniform) the tile is computed here: d z product + latent backward (fold_dz_tile)
+      if constexpr (SEAM) {
+        __shared__ int seam_ok;
+        if (!fold_dz_tile<true>(a, bid, ds, ldd, reinterpret_cast<unsigned char*>(ws + BN_COLS * ldw_s), sm, &seam_ok)) return;
+      } else
       fold_dz_tile(a, bid, ds, ldd, reinterpret_cast<unsigned char*>(ws + BN_COLS * ldw_s));
       if ((int)threadIdx.x < BN_COLS * kq) *reinterpret_cast<float4*>(&ws[((int)threadIdx.x >> ksh) * ldw_s + ((int)threadIdx.x & kmask) * 4]) = wl;
     } else
@@ -1041,11 +1057,12 @@ __global__ __launch_bounds__(BN_THREADS) void bn_wide_fwd_gen_kernel(BnFwdArgs a
 
 // `lds`: BN_WIDE_BWD_SMEM_FLOATS floats, 16-byte aligned, of the calling kernel (bn_wide_bwd_dw_kernel hands over a view of a larger array)
 constexpr int BN_WIDE_BWD_SMEM_FLOATS = 16 * 128 + 128 + 128 + 4;   // sh | vs | xs | st
-template <bool GEN_ACT>
-__device__ inline void bn_wide_bwd_body(const BnBwdArgs& a, float* lds) {
+// SEAM (bn_bwd_seam_kernel): `bid` is the column; d pre is stored write-through and published to the launch's waiting workgroups
+// (smx_handoff.h) -- every thread reaches the publish.
+template <bool GEN_ACT, bool SEAM = false>
+__device__ inline void bn_wide_bwd_body(const BnBwdArgs& a, float* lds, const int bid, const BwdSeamArgs* sm = nullptr) {
 #pragma clang fp contract(off)
-  const int bid = (int)blockIdx.x;
-  {
+  if constexpr (!SEAM) {
     const int extra = bid - a.Hp;
     if (extra >= 0) {   // the riders of bn_act_bwd_body
       const int e = extra - (a.with_metrics ? 1 : 0);
@@ -1110,10 +1127,25 @@ __device__ inline void bn_wide_bwd_body(const BnBwdArgs& a, float* lds) {
   SMX_STAMP(2, 5);
   if (!a.batchnorm) {
     if (r == 0 && a.dbias && live) a.dbias[col] = s1;
+    if constexpr (SEAM) {
+      if (on) handoff_store(a.dpre + (long)r * a.Hp + col, dy);
+      handoff_publish(sm->seam, col);
+    } else
     if (on) a.dpre[(long)r * a.Hp + col] = dy;
     return;
   }
   if (r == 0) { a.dgamma[col] = live ? s2 : 0.f; a.dbeta[col] = live ? s1 : 0.f; }
+  if constexpr (SEAM) {
+    if (on) {
+      const float invB = 1.f / (float)a.B;
+      float d;
+      if (a.training) d = (gamma * inv) * __builtin_fmaf(-__builtin_fmaf(xh, s2, s1), invB, dy);
+      else d = dy * gamma * inv;
+      handoff_store(a.dpre + (long)r * a.Hp + col, d);
+    }
+    handoff_publish(sm->seam, col);
+    return;
+  }
   if (!on) return;
   const float invB = 1.f / (float)a.B;
   float d;
@@ -1124,11 +1156,11 @@ __device__ inline void bn_wide_bwd_body(const BnBwdArgs& a, float* lds) {
 }
 __global__ __launch_bounds__(BN_THREADS) void bn_wide_bwd_kernel(BnBwdArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[BN_WIDE_BWD_SMEM_FLOATS];
-  bn_wide_bwd_body<false>(a, lds);
+  bn_wide_bwd_body<false>(a, lds, (int)blockIdx.x);
 }
 __global__ __launch_bounds__(BN_THREADS) void bn_wide_bwd_gen_kernel(BnBwdArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[BN_WIDE_BWD_SMEM_FLOATS];
-  bn_wide_bwd_body<true>(a, lds);
+  bn_wide_bwd_body<true>(a, lds, (int)blockIdx.x);
 }
 
 // ---- bn_wide_bwd_kernel that also CARRIES the output head's dW / db / sum-of-squares slots (role 0 of out_head_bwd_kernel: smx_headdw.h) --------------
@@ -1149,7 +1181,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_wide_bwd_dw_kernel(BnBwdArgs a,
     head_dw_body<NP, 0, 1>(h, (int)blockIdx.x - first_dw, lds);
     return;
   }
-  bn_wide_bwd_body<false>(a, lds);
+  bn_wide_bwd_body<false>(a, lds, (int)blockIdx.x);
 }
 
 // a: a wide BatchNorm-backward launch as launch_bn_act_bwd takes it (ReLU); h: the head's arguments as launch_out_head_bwd takes them (its d d fields unread)
@@ -1172,6 +1204,74 @@ int launch_bn_wide_bwd_dw(hipStream_t st, const BnBwdArgs& a, const HeadBwdArgs&
   const dim3 grid((unsigned)(a.Hp + (a.with_metrics ? 1 : 0) + a.adam_count + a.sqr_count + (a.close ? 1 : 0) + h.n_w));
   if (h.n_planes == 3) hipLaunchKernelGGL(bn_wide_bwd_dw_kernel<3>, grid, dim3(BN_THREADS), 0, st, a, h);
   else hipLaunchKernelGGL(bn_wide_bwd_dw_kernel<2>, grid, dim3(BN_THREADS), 0, st, a, h);
+  SMX_HIP(hipGetLastError());
+  return SMX_OK;
+}
+
+// ---- the carrier above and the encoder's fold_dz launch behind it in ONE launch (smx_handoff.h; smx_backward.hip: the seam form) ----------------------
+// The encoder's enc.Hp / 8 chain workgroups (at most HANDOFF_MAX_WAITERS) wait for nothing but d pre_dec, the 64 KB the decoder's Hp column
+// workgroups write: in one launch they run everything that does not read it -- argument fields, the W_dec image, their rows of W_lat, the latent
+// head's operands, out / xhat / gamma / inv_std of their columns -- while the columns work, and wait inside the launch.  The same device
+// functions as the two launches, SEAM forms: the same additions in the same order, the same bits.  Block order: the Hp columns, the chain
+// workgroups straight behind them (sm.cons_first: ahead of them -- results do not depend on it, smx_handoff.h: Progress), then the riders that read
+// nothing the launch writes -- the ELBO scalars (enc.with_metrics), W_enc's lazy chunks (dec.adam*), the step's close (enc.close) --, then the
+// head's dW tiles.  The head's optimiser riders read what the tiles write: they are not here (smx_backward.hip).  One LDS array, each body its view.
+template <int NP>
+__global__ __launch_bounds__(BN_THREADS) void bn_bwd_seam_kernel(BnBwdArgs dec, BnBwdArgs enc, HeadBwdArgs h, BwdSeamArgs sm) {
+  extern __shared__ __attribute__((aligned(16))) float ds[];
+  const int b = (int)blockIdx.x, np = dec.Hp, nc = enc.Hp / BN_COLS;
+  const int first_dw = (int)gridDim.x - h.n_w;
+  if (b >= first_dw) {   // (block-uniform, like every branch below)
+    preload(h.D, h.ldd, h.dP, h.ldp, h.dW, h.ldw, h.db, h.B, h.Gp, h.sq_part, h.n_w, h.n_ht, h.n_gt, h.diag, h.Hp, h.n_planes);
+    head_dw_body<NP, 0, 1>(h, b - first_dw, ds);
+    return;
+  }
+  if (b < np + nc) {
+    const bool cons = sm.cons_first ? b < nc : b >= np;
+    if (cons) bn_act_bwd_body<2, 1, false, true>(enc, sm.cons_first ? b : b - np, &sm);
+    else bn_wide_bwd_body<false, true>(dec, ds, sm.cons_first ? b - nc : b, &sm);
+    return;
+  }
+  int e = b - np - nc;
+  if (enc.with_metrics) {
+    if (e == 0) { if (threadIdx.x < 256) metrics_body(enc.metrics); return; }
+    --e;
+  }
+  if (e < dec.adam_count) { adam_chunk_body<BN_THREADS>(dec.adam, dec.adam_first + e); return; }
+  if (enc.close && threadIdx.x < 256) step_close_body<false>(enc.adam);
+}
+
+bool bn_bwd_seam_supported(const BnBwdArgs& dec, const BnBwdArgs& enc, const HeadBwdArgs& h) {
+  return bn_wide_bwd_dw_supported(dec, h) && !dec.with_metrics && !dec.close && dec.sqr_count == 0 && dec.dpre &&
+         enc.front && enc.fold_dz && enc.act == SMX_ACT_RELU && enc.B == dec.B && enc.B <= BN_RL * 2 && enc.Hp % BN_COLS == 0 &&
+         enc.Hp / BN_COLS <= HANDOFF_MAX_WAITERS && enc.adam_count == 0 && enc.sqr_count == 0 && enc.zD == dec.dpre && enc.zld == dec.Hp && dec.Hp == 128 &&
+         bn_bwd_front_supported(enc.B, enc.fK) && bn_bwd_fold_supported(enc.B, enc.fK, enc.zlb.Dp);
+}
+int launch_bn_bwd_seam(hipStream_t st, const BnBwdArgs& dec, const BnBwdArgs& enc_in, const HeadBwdArgs& h_in, const BwdSeamArgs& sm) {
+  HeadBwdArgs h = h_in;
+  BnBwdArgs enc = enc_in;
+  enc.diag = 0;
+  const EpiLatentBwd& e = enc.zlb;
+  if (!bn_bwd_seam_supported(dec, enc, h) || !dec.dout || dec.slab_stride < (long)dec.Hp * 128 || (dec.slab_stride % 4) || !h.D || !h.dP || !h.dW || !h.db || h.ldd < h.Hp ||
+      h.ldp < (long)h.n_planes * h.Gp || h.ldw < (long)h.n_planes * h.Gp || !enc.fD || !enc.fW || (enc.fld % 4) || (enc.fldw % 4) || !enc.zW || (enc.zld % 4) || (enc.zldw % 4) ||
+      enc.zldw < 128 || !e.lat || !e.sig || !e.eps || !e.dlat || !e.stochastic || e.dklz || e.dz_add || (e.ld % 4) || e.ld < 2 * e.Dp ||
+      !sm.seam.counter || !sm.seam.error || sm.seam.target == 0 || sm.seam.shards < 1 || sm.seam.shards > HANDOFF_MAX_SHARDS || (sm.seam.shards & (sm.seam.shards - 1))) {
+    set_error("bn_bwd_seam: bad shapes");
+    return SMX_ERR_INVALID;
+  }
+  h.n_ht = h.Hp / 32; h.n_gt = h.Gp / 32; h.n_ct = (h.B + 31) / 32;
+  h.n_w = h.n_ht * ((h.n_gt + 7) / 8 * 8);
+  h.skip_dd = 1; h.skip_dw = 0; h.diag = 0;
+  if (h.sq_count) *h.sq_count = h.n_ht * h.n_gt * 8;
+  size_t lds = ((size_t)enc.B * (enc.fK + 4) + (size_t)BN_COLS * (enc.fK + 4)) * sizeof(float) + SMX_FOLD_WIMG_BYTES;
+  lds = std::max(lds, (size_t)SMX_HEAD_DW_SMEM_FLOATS * sizeof(float));
+  static_assert(SMX_HEAD_DW_SMEM_FLOATS >= BN_WIDE_BWD_SMEM_FLOATS, "bn_bwd_seam: the column body's view fits the head's");
+  static const bool ok3 = hipFuncSetAttribute(reinterpret_cast<const void*>(&bn_bwd_seam_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess;
+  static const bool ok2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&bn_bwd_seam_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) == hipSuccess;
+  if (!ok3 || !ok2 || lds > 96 * 1024) { set_error("bn_bwd_seam: cannot reserve the dynamic LDS"); return SMX_ERR_HIP; }
+  const dim3 grid((unsigned)(dec.Hp + enc.Hp / BN_COLS + (enc.with_metrics ? 1 : 0) + dec.adam_count + (enc.close ? 1 : 0) + h.n_w));
+  if (h.n_planes == 3) hipLaunchKernelGGL(bn_bwd_seam_kernel<3>, grid, dim3(BN_THREADS), lds, st, dec, enc, h, sm);
+  else hipLaunchKernelGGL(bn_bwd_seam_kernel<2>, grid, dim3(BN_THREADS), lds, st, dec, enc, h, sm);
   SMX_HIP(hipGetLastError());
   return SMX_OK;
 }

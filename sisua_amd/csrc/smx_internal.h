@@ -7,6 +7,7 @@
 
 #include "smx_device.h"
 #include "smx_act.h"
+#include "smx_handoff.h"
 #include "../../include/sisua_hip.h"
 
 namespace smx {
@@ -621,6 +622,16 @@ int launch_bn_wide_bwd_dw(hipStream_t st, const BnBwdArgs& a, const HeadBwdArgs&
 // ... the head's optimiser riders then start at the NEXT BatchNorm-backward launch (one decoder layer: the encoder's): the share of them it takes (the optimiser launch takes the rest;
 // knob adam_split_late; the A/B is in profiles/head_dw_late_ab.txt)
 #define SMX_ADAM_SPLIT_LATE_DEFAULT 1.0f
+// that carrier and the encoder's fold_dz launch behind it as ONE launch (smx_bn.hip: bn_bwd_seam_kernel): the encoder's chain workgroups wait inside
+// the launch for d pre_dec (smx_handoff.h).  dec / h as the carrier takes them (no riders but W_enc's lazy chunks), enc as launch_bn_act_bwd takes the
+// fold_dz front (no optimiser riders: they read what the tiles write; the ELBO scalars and the step's close ride)
+struct BwdSeamArgs {
+  HandoffSeam seam;
+  int preread = 0;      // diagnostic (knob bwd_seam_preread): the waiting workgroups plain-load every line of d pre_dec before they wait
+  int cons_first = 0;   // the waiting workgroups ahead of the columns in block order (knob bwd_seam_cons_first) instead of straight behind them
+};
+bool bn_bwd_seam_supported(const BnBwdArgs& dec, const BnBwdArgs& enc, const HeadBwdArgs& h);
+int launch_bn_bwd_seam(hipStream_t st, const BnBwdArgs& dec, const BnBwdArgs& enc, const HeadBwdArgs& h, const BwdSeamArgs& sm);
 
 // ---- products contracting over the gene axis of a wide panel: one workgroup per K slice + a reduce launch (smx_bigk.hip) ----
 struct BigKArgs {

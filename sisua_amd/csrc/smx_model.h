@@ -323,6 +323,12 @@ struct smx_model {
   bool bucket1_in_flight = false;
   bool fold_dz_now = false;      // this backward pass: the d z product + latent backward run inside the encoder's BatchNorm-backward launch (smx_backward.hip)
   bool dw_late_now = false;      // this backward pass: the decoder's BatchNorm-backward launch carries the output head's dW / db (smx_backward.hip: dw_late)
+  // the seam form (smx_backward.hip): the decoder's carrier launch and the encoder's fold_dz launch as ONE launch (smx_bn.hip: bn_bwd_seam_kernel)
+  bool seam_pending = false;     // this backward pass: the carrier's launch is held back for the encoder's (seam_dec / seam_head / seam_w_rides)
+  BnBwdArgs seam_dec; HeadBwdArgs seam_head;
+  unsigned* seam_state = nullptr;   // [HANDOFF_STATE_BYTES]: the counter's shards | the error word; zeroed by the first step of a library call that takes the form
+  unsigned seam_epochs = 0;      // steps of this library call that took the form: the next target is producers x (seam_epochs + 1)
+  int32_t seam_steps = 0;        // ... of the last smx_train_steps call (smx_bwd_seam_steps)
   bool chain_started = false;    // this step's head bucket went: all-reduce -> norms -> clip + Adam sweep on the communication stream (smx_backward.hip: dp_chain_start)
   // padding audit (smx_pad_audit, which = 4): rows of the last pass (stacked draws included), of the last discriminator pass, and the
   // layout the last stacked evaluation decoder used (set by its two callers, smx_predict.hip / smx_scoring.hip)
@@ -572,6 +578,7 @@ int optimizer_pass(smx_model* m);
 int csr_stage(smx_model* m, Pass& ps);
 int check_rows(smx_model* m, const int32_t* ids, size_t n);
 int read_metrics(smx_model* m, smx_metrics* out);
+int seam_error_check(smx_model* m);   // the seam form's error word (smx_step.hip)
 // host rows given as CSR (smx_predict.hip): indptr int64 [n + 1] (absolute offsets into cols / vals), cols int32, vals float32
 struct CsrRows { const int64_t* indptr; const int32_t* cols; const float* vals; };
 int check_csr_rows(const CsrRows& c, size_t n, int G);

@@ -594,6 +594,7 @@ int smx_model_destroy(smx_model* m) {
   if (m->pinned) hipHostFree(m->pinned);
   if (m->order_pin) hipHostFree(m->order_pin);
   if (m->metrics_pin) hipHostFree(m->metrics_pin);
+  if (m->seam_state) hipFree(m->seam_state);
   if (m->score_pin) hipHostFree(m->score_pin);
   if (m->ev_order) hipEventDestroy(m->ev_order);
   if (m->pred_stage) hipFree(m->pred_stage);
@@ -926,5 +927,6 @@ int64_t smx_head_fused_bytes(const smx_model* m, int32_t batch) {
 
 int32_t smx_head_dw_late(const smx_model* m) { return (m && m->dw_late_now) ? 1 : 0; }   // (smx_backward.hip: dw_late)
 int32_t smx_lazy_adam_steps(const smx_model* m) { return m ? m->lazy_steps : 0; }          // (smx_step.hip: the lazy encoder update)
+int32_t smx_bwd_seam_steps(const smx_model* m) { return m ? m->seam_steps : 0; }            // (smx_backward.hip: the seam form)
 
 }  // extern "C"

@@ -208,19 +208,37 @@ int train_sequence(smx_model* m, int B, bool with_begin, bool begin_from_master,
   return SMX_OK;
 }
 
+// the seam form's error word (smx_backward.hip, smx_handoff.h): non-zero after a wait inside the fused BatchNorm-backward launch gave up -- that
+// step's encoder gradients were never written.  Read wherever the step's scalars are read; reported once, then cleared.
+static unsigned* seam_error_word(smx_model* m) { return m->seam_state + HANDOFF_MAX_SHARDS * HANDOFF_SHARD_STRIDE; }
+int seam_error_check(smx_model* m) {
+  if (!m->seam_state) return SMX_OK;
+  unsigned e = 0;
+  SMX_HIP(hipStreamSynchronize(m->st));
+  SMX_HIP(hipMemcpy(&e, seam_error_word(m), sizeof(e), hipMemcpyDeviceToHost));
+  if (!e) return SMX_OK;
+  SMX_HIP(hipMemset(seam_error_word(m), 0, sizeof(e)));
+  set_error("BatchNorm-backward seam: the encoder's workgroups gave up waiting for the decoder's d pre-activation inside the fused launch (knob no_bwd_seam runs the two launches)");
+  return SMX_ERR_HIP;
+}
+
 int read_metrics(smx_model* m, smx_metrics* out) {
   if (!out) return SMX_OK;
   // into pinned memory (two real DMA copies; into pageable arrays the runtime stages each one synchronously)
   const size_t nt = m->tensors.size();
-  if (!m->metrics_pin) SMX_HIP(hipHostMalloc((void**)&m->metrics_pin, (8 + nt + 1) * sizeof(float), hipHostMallocDefault));
+  if (!m->metrics_pin) SMX_HIP(hipHostMalloc((void**)&m->metrics_pin, (8 + nt + 2) * sizeof(float), hipHostMallocDefault));
   float* h = m->metrics_pin;
   float* norms_p = m->metrics_pin + 8;
   unsigned* p2p_err = reinterpret_cast<unsigned*>(m->metrics_pin + 8 + nt);
   *p2p_err = 0u;
+  unsigned* seam_err = p2p_err + 1;
+  *seam_err = 0u;
   SMX_HIP(hipMemcpyAsync(h, m->grads + m->tail_off_metrics, 8 * sizeof(float), hipMemcpyDeviceToHost, m->st));
   SMX_HIP(hipMemcpyAsync(norms_p, m->tensor_norm, nt * sizeof(float), hipMemcpyDeviceToHost, m->st));
   if (m->p2p && m->p2p->error) SMX_HIP(hipMemcpyAsync(p2p_err, m->p2p->error, sizeof(unsigned), hipMemcpyDeviceToHost, m->st));
+  if (m->seam_state) SMX_HIP(hipMemcpyAsync(seam_err, seam_error_word(m), sizeof(unsigned), hipMemcpyDeviceToHost, m->st));
   SMX_HIP(hipStreamSynchronize(m->st));
+  if (*seam_err) SMX_CHECK(seam_error_check(m));
   if (*p2p_err) {   // a bounded wait of the peer-to-peer exchange gave up on this rank or on a peer: every rank's step is garbage
     set_error(*p2p_err == 1u ? "peer-to-peer all-reduce: a wait on a peer's flag timed out (SMX_P2P_TIMEOUT_S)" :
                                "peer-to-peer all-reduce: a peer reported a timed-out wait");
@@ -488,6 +506,7 @@ int smx_train_steps(smx_model* m, const int32_t* order, int32_t n_steps, int32_t
   ++m->params_epoch;   // (the parameters are about to change)
   smx::DrawCaps caps(m);
   m->lazy_steps = 0;
+  m->seam_steps = 0; m->seam_epochs = 0;   // (the seam's counter counts within this call: its first step that takes the form zeroes it)
   for (int s = 0; s < n_steps && rc == SMX_OK; ++s) rc = launch_train(m, batch * m->train_draws, use_graph != 0, s, n_steps);
   { const int rf = smx::lazy_flush(m); if (rc == SMX_OK) rc = rf; }   // (nothing is pending here: the call's last step keeps its optimiser launch)
   { const int rj = smx::head_sweep_join(m); if (rc == SMX_OK) rc = rj; }   // every other entry point sees one stream
@@ -513,6 +532,7 @@ int smx_train_stage(smx_model* m, const int32_t* order, int32_t n_steps, int32_t
 int smx_metrics_history(smx_model* m, int32_t n_steps, float* host) {
   SMX_REQUIRE(m && host && n_steps > 0 && n_steps <= m->mhist_steps, "no such history (steps of the last smx_train_steps call)");
   SMX_HIP(hipStreamSynchronize(m->st));
+  SMX_CHECK(smx::seam_error_check(m));
   SMX_HIP(hipMemcpy(host, m->mhist, (size_t)n_steps * 8 * sizeof(float), hipMemcpyDeviceToHost));
   return SMX_OK;
 }

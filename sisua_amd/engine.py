@@ -822,6 +822,10 @@ class Engine:
     """The last training step left the output head's dW / db to the decoder's BatchNorm-backward launch (smx_head_dw_late)."""
     return bool(self.lib.smx_head_dw_late(self._h))
 
+  def bwd_seam_steps(self) -> int:
+    """Steps of the last train_steps call that ran the decoder's and the encoder's BatchNorm-backward launches as one launch (smx_bwd_seam_steps)."""
+    return int(self.lib.smx_bwd_seam_steps(self._h))
+
   def lazy_adam_steps(self) -> int:
     """Steps of the last train_steps call whose optimiser launch was left to the next step's forward launches (smx_lazy_adam_steps)."""
     return int(self.lib.smx_lazy_adam_steps(self._h))
