@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 18
+#define SMX_ABI_VERSION 19
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -741,6 +741,17 @@ int smx_k_scvi_head_fwd(const int32_t* ip, const float* fp, const float* raw, co
 /* ... and the separate backward on ITS inputs: planes, dplanes [B][ld], rho_raw [B][Gp], l [B] -> draw [B][ld], dl [B]. */
 int smx_k_scvi_head_bwd(const int32_t* ip, const float* fp, const float* planes, const float* dplanes, const float* rho_raw, const float* l,
                         float* draw, float* dl, int32_t* guards_ok);
+/* The label heads' launch by itself (smx_loss.hip), over host arrays in a training step's layout; the library's own dispatch picks the kernel
+ * (the 'mixtril' head has its own).  ip (int32): kind (smx_label_likelihood), C (mixture components), B, P (label dimension), Pp (P rounded
+ * up to 32), ld (row stride of raw / draw, >= planes x Pp; planes: 1 onehot / bernoulli, 2 nb / nbd / normal, 3 zinb / zinbd, 3 C mixnb /
+ * mixgauss, 4 C mixzinb, C (2 + P) mixtril), ldy, n_rows, observed, add, backward.  fp: grad_scale.  raw [B][ld]; Y [n_rows][ldy]; rows [B]
+ * or NULL (cell b = row b): the row of Y and of mask; mask [n_rows] bytes or NULL (every cell unlabelled unless observed).  llk [B] and
+ * draw [B][ld] are read AND written: they reach the device as the caller filled them (the accumulator that add = 1 adds to; any pattern that
+ * tells a word the launch left alone from a written zero) between guard bands (*guards_ok as smx_k_bn_fwd).  Refused with SMX_ERR_INVALID:
+ * P < 1, 'mixtril' outside 1..64 dimensions or 2..4 components, another mixture outside 1..4 components, Pp != round_up(P, 32), ld below
+ * planes x Pp, a row index outside Y. */
+int smx_k_label_loss(const int32_t* ip, const float* fp, const float* raw, const float* Y, const int32_t* rows, const uint8_t* mask, float* llk,
+                     float* draw, int32_t* guards_ok);
 /* The predictive sampler by itself on caller-given planes [k][rows][G] (host; k planes of `likelihood`, direct / count_only as
  * smx_k_count_llk / smx_predict_sample): out [n_k][rows][G], the draws of rows 0 .. rows - 1 of a call with one Monte-Carlo draw
  * (s = 0) under `seed`.  rows <= 65535. */

@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsisua_hip.so")
 
-SMX_ABI_VERSION = 18
+SMX_ABI_VERSION = 19
 SMX_MAX_LAYERS = 8
 SMX_MAX_LABELS = 4
 
@@ -183,6 +183,7 @@ SIGNATURES = {
     "smx_k_scvi_head_train": (C.c_int, [_IP, _FP, _FP, _VP, _FP, _FP, _FP, _FP, _IP, _FP, C.c_uint64, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _IP]),
     "smx_k_scvi_head_fwd": (C.c_int, [_IP, _FP, _FP, _FP, _FP, _FP, _IP]),
     "smx_k_scvi_head_bwd": (C.c_int, [_IP, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _IP]),
+    "smx_k_label_loss": (C.c_int, [_IP, _FP, _FP, _FP, _IP, C.POINTER(C.c_uint8), _FP, _FP, _IP]),
     "smx_k_plane_sample": (C.c_int, [C.c_int, C.c_int, C.c_int, _FP, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _FP]),
     "smx_k_row_select": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]),
     "smx_k_col_rank2": (C.c_int, [_FP, C.c_int32, C.c_int64, _IP, _IP]),

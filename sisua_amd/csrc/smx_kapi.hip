@@ -1,6 +1,6 @@
 // smx_kapi.hip -- kernel-level entry points (parity tests of single kernels): smx_k_count_llk, smx_k_adam, smx_k_gemm, smx_k_head_fused, smx_k_noise,
 // smx_k_bn_fwd / smx_k_bn_bwd, smx_k_opt_carrier (clip + update by every launch that carries the optimiser's chunk body),
-// smx_k_scvi_head_train / _fwd / _bwd (the scVI gene head's three launch forms).
+// smx_k_scvi_head_train / _fwd / _bwd (the scVI gene head's three launch forms), smx_k_label_loss (the label heads' launch).
 #include "smx_model.h"
 #include "smx_adam.h"
 #include <hiprand/hiprand_kernel.h>
@@ -847,6 +847,44 @@ int smx_k_scvi_head_bwd(const int32_t* ip, const float* fp, const float* planes,
   if ((rc = oDraw.intact(&ok)) || (rc = oDl.intact(&ok))) return rc;
   *guards_ok = ok ? 1 : 0;
   if ((rc = oDraw.download(draw, (size_t)B * ld)) || (rc = oDl.download(dl, B))) return rc;
+  return SMX_OK;
+}
+
+// ---- the label heads' launch by itself (smx_loss.hip: launch_label_loss picks label_loss_kernel or, for 'mixtril', label_tril_kernel) ------
+// ip: kind, C, B, P, Pp, ld, ldy, n_rows, observed, add, backward; fp: grad_scale.  llk [B] and draw [B][ld] go in AND out: the device copies
+// start as the caller's values (the incoming accumulator; a pattern that tells "not written" from "written 0") between guard bands.
+int smx_k_label_loss(const int32_t* ip, const float* fp, const float* raw, const float* Y, const int32_t* rows, const uint8_t* mask, float* llk,
+                     float* draw, int32_t* guards_ok) {
+  SMX_REQUIRE(ip && fp && raw && Y && llk && draw && guards_ok, "k_label_loss: bad arguments (an input or an output is NULL)");
+  const int kind = ip[0], C = ip[1], B = ip[2], P = ip[3], Pp = ip[4], ld = ip[5], ldy = ip[6], n_rows = ip[7];
+  SMX_REQUIRE(kind >= SMX_LABEL_NB && kind <= SMX_LABEL_NORMAL, "unknown label likelihood");
+  SMX_REQUIRE(P > 0, "label_dim must be > 0");
+  const bool tril = kind == SMX_LABEL_MIXTRIL, mix = kind == SMX_LABEL_MIXNB || kind == SMX_LABEL_MIXGAUSS || kind == SMX_LABEL_MIXZINB;
+  if (tril) SMX_REQUIRE(P <= 64 && C >= 2 && C <= 4, "label_loss: 'mixtril' heads take 1..64 label dimensions and 2..4 components");
+  if (mix) SMX_REQUIRE(C >= 1 && C <= 4, "k_label_loss: mixture label heads have 1..4 components");
+  SMX_REQUIRE(P <= (1 << 20) && Pp == round_up(P, 32), "k_label_loss: Pp is the label dimension rounded up to 32");
+  const long planes = tril ? (long)C * (2 + P) : kind == SMX_LABEL_MIXZINB ? 4L * C : mix ? 3L * C :
+                      (kind == SMX_LABEL_NB || kind == SMX_LABEL_NBD || kind == SMX_LABEL_NORMAL) ? 2 : (kind == SMX_LABEL_ZINB || kind == SMX_LABEL_ZINBD) ? 3 : 1;
+  SMX_REQUIRE((long)ld >= planes * Pp, "k_label_loss: ld is below planes x Pp");
+  SMX_REQUIRE(B > 0 && ldy >= P && n_rows > 0 && (rows || n_rows >= B), "k_label_loss: bad shapes");
+  if (rows) for (int b = 0; b < B; ++b) SMX_REQUIRE(rows[b] >= 0 && rows[b] < n_rows, "k_label_loss: a row index lies outside Y");
+  DeviceScratch buf;
+  float *dRaw, *dY; int32_t* dRows; uint8_t* dMask;
+  KbnOut oLlk, oDraw;
+  int rc;
+  if ((rc = buf.put(&dRaw, raw, (size_t)B * ld)) || (rc = buf.put(&dY, Y, (size_t)n_rows * ldy)) || (rc = buf.put(&dRows, rows, (size_t)B)) ||
+      (rc = buf.put(&dMask, mask, (size_t)n_rows)) || (rc = oLlk.alloc(buf, (size_t)B)) || (rc = oDraw.alloc(buf, (size_t)B * ld)) ||
+      (rc = oLlk.upload(llk, (size_t)B)) || (rc = oDraw.upload(draw, (size_t)B * ld)))
+    return rc;
+  LabelArgs a;
+  a.kind = kind; a.C = C; a.raw = dRaw; a.ld = ld; a.Y = dY; a.ldy = ldy; a.rows = dRows; a.mask = dMask; a.observed = ip[8];
+  a.B = B; a.P = P; a.Pp = Pp; a.grad_scale = fp[0]; a.draw = oDraw.p(); a.llk = oLlk.p(); a.add = ip[9]; a.backward = ip[10];
+  SMX_CHECK(launch_label_loss(nullptr, a));
+  SMX_HIP(hipDeviceSynchronize());
+  bool ok = true;
+  if ((rc = oLlk.intact(&ok)) || (rc = oDraw.intact(&ok))) return rc;
+  *guards_ok = ok ? 1 : 0;
+  if ((rc = oLlk.download(llk, (size_t)B)) || (rc = oDraw.download(draw, (size_t)B * ld))) return rc;
   return SMX_OK;
 }
 

@@ -28,7 +28,7 @@ from sisua_amd.engine._gmm import (ILL_DEFINED_COVARIANCE, _gmm_matrix, gmm_n_tr
 from sisua_amd.engine._groups import (MOMENT_MAX_ACC, MOMENT_MAX_GROUPS, RANK_MAX_CELLS, RANK_MAX_GROUPS, _group_labels, k_group_moments,
                                       k_group_ranksums)
 from sisua_amd.engine._kernels import (OPT_CARRIERS, _bn_slabs, _bn_vec, _scvi_layout, k_adam, k_bn_bwd, k_bn_fwd, k_count_llk, k_gemm,
-                                       k_head_fused, k_head_fused_stress, k_noise, k_opt, k_opt_carrier, k_row_select, k_scvi_head_bwd,
+                                       k_head_fused, k_head_fused_stress, k_label_loss, k_noise, k_opt, k_opt_carrier, k_row_select, k_scvi_head_bwd,
                                        k_scvi_head_fwd, k_scvi_head_train)
 from sisua_amd.engine._logreg import (LR_MAX_CLASSES, LR_MAX_GENES, LR_MAX_RESIDENT, _lr_input, _lr_params, _lr_penalty, k_logreg_decision,
                                       k_logreg_eval, k_logreg_fit)

@@ -309,3 +309,44 @@ def k_scvi_head_bwd(planes, dplanes, rho_raw, l, G, k=3, clip_library=1e3, Gp=No
   check(lib.smx_k_scvi_head_bwd(_ip(ip), _fp(fp), _fp(planes), _fp(dplanes), _fp(rho_raw), _fp(l), p["draw"], p["dl"], C.byref(ok)))
   o["guards_ok"] = bool(ok.value)
   return o
+
+
+def _label_kind(kind: str):
+  """'nb' .. 'normal', 'mixnb3' .. 'mixtril2' -> (smx_label_likelihood, components)"""
+  from sisua_amd.config import MIXTURE_HEAD_KINDS
+  for base in MIXTURE_HEAD_KINDS:
+    if kind.startswith(base) and kind[len(base):].isdigit():
+      return _hip.LABEL_LIKELIHOODS[base], int(kind[len(base):])
+  return _hip.LABEL_LIKELIHOODS[kind], 1
+
+
+def k_label_loss(kind: str, raw, Y, P: int, Pp=None, ld=None, rows=None, mask=None, observed=False, grad_scale=1.0, add=False, backward=True,
+                 llk_in=None, fill=np.nan):
+  """The label heads' launch by itself (smx_k_label_loss).  kind: 'nb', 'nbd', 'zinb', 'zinbd', 'bernoulli', 'normal', 'onehot', 'mixnbC',
+  'mixzinbC', 'mixgaussC', 'mixtrilC'.  raw [B][ld] in the step's layout (plane c of a row at c * Pp, Pp = P rounded up to 32 unless given,
+  ld = planes * Pp unless given); Y [n_rows][ldy]; rows [B] (None: cell b = row b); mask [n_rows] (None: no cell is labelled).  llk_in [B]:
+  the accumulator the launch finds (zeros); fill: what draw [B][ld] holds before the launch, a scalar or an array.  Returns dict(llk [B],
+  draw [B][ld], guards_ok)."""
+  lib = _hip.require_gpu()
+  code, C_ = _label_kind(kind)
+  P = int(P)
+  Pp = (P + 31) // 32 * 32 if Pp is None else int(Pp)
+  raw = _f32(raw)
+  if raw.ndim != 2:
+    raise ValueError(f"raw must be [B][ld], got {raw.shape}")
+  B = raw.shape[0]
+  ld = raw.shape[1] if ld is None else int(ld)
+  raw, Y = _f32(raw, (B, ld)), _f32(Y)
+  if Y.ndim != 2:
+    raise ValueError(f"Y must be [n_rows][ldy], got {Y.shape}")
+  rw = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+  mk = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+  if (rw is not None and rw.shape != (B,)) or (mk is not None and mk.shape != (Y.shape[0],)):
+    raise ValueError("rows must be [B] and mask [n_rows]")
+  llk = np.zeros(B, np.float32) if llk_in is None else _f32(llk_in, (B,)).copy()
+  draw = np.ascontiguousarray(np.broadcast_to(np.asarray(fill, np.float32), (B, ld))).copy()
+  ip = np.array([code, C_, B, P, Pp, ld, Y.shape[1], Y.shape[0], int(bool(observed)), int(bool(add)), int(bool(backward))], np.int32)
+  fp = np.array([grad_scale], np.float32)
+  ok = C.c_int32(0)
+  check(lib.smx_k_label_loss(_ip(ip), _fp(fp), _fp(raw), _fp(Y), _ip(rw), _ptr(mk, np.uint8), _fp(llk), _fp(draw), C.byref(ok)))
+  return dict(llk=llk, draw=draw, guards_ok=bool(ok.value))

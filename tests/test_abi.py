@@ -28,6 +28,8 @@ def test_header_and_binding_agree(lib):
   assert lib.smx_abi_version() == _hip.SMX_ABI_VERSION
   # the kernel-level entries of the scVI gene head (tests/test_gpu_scvi_head.py)
   assert {"smx_k_scvi_head_train", "smx_k_scvi_head_fwd", "smx_k_scvi_head_bwd"} <= declared
+  # the kernel-level entry of the label heads (tests/test_gpu_label_heads.py)
+  assert {"smx_k_label_loss"} <= declared and _hip.SMX_ABI_VERSION >= 19
 
 
 def test_config_struct_layout_matches_header(tmp_path):

@@ -23,7 +23,7 @@ EVERY LAUNCHER BRANCH that evaluates count_elem / count_elem_vec and is reachabl
                   VEC = 4 (from 8 M elements: beyond the limits)                                 not reachable: test_count_llk_wide_access_forms, ordinary data
                   BWD = 0 (scoring draw by draw)                                                 test_scoring_on_the_grid[*-per_draw]
                   likelihood -2 (a diagnostic, not a result)                                     NOT REACHED
-                  label_loss_kernel's count_elem calls                                           out of scope (label heads)
+                  label_loss_kernel's count_elem calls                                           tests/test_gpu_label_heads.py (smx_k_label_loss; tests/label_heads_ref.py)
   smx_headloss.hip  out_head_loss_kernel<LK, U16 = 0, EPI = 1, NW = 8, 128, B3 = 0 / 1>, count_elem_vec through the per-wave queue (QUEUE: EPI == 1, NW >= 4)
                     nb, zinb, nbd, zinbd, normal; B3 by the bf16x3 flag                         test_training_step_on_the_grid[*-b128_bf16x3_0 / _1, b4, b130, ...]
                   U16 = 1 (the uint16 store in a training step)                                 test_training_step_on_the_grid[*-b128_u16]
