@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 19
+#define SMX_ABI_VERSION 20
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -984,6 +984,55 @@ int smx_tsne_gradient(const int64_t* indptr, const int32_t* cols, const double* 
 int smx_tsne_fit(const int64_t* indptr, const int32_t* cols, const double* p, int64_t n_cells, int32_t n_components, const double* Y0,
                  int32_t max_iter, double early_exaggeration, double learning_rate, double min_grad_norm, int32_t n_iter_without_progress,
                  double* Y, double* kl_trace, int32_t* n_iter, double* update_out, double* gains_out);
+
+/* ---- UMAP layout (smx_umap.hip; model-free: smx_init only) ----------- */
+/* The layout optimisation of umap-learn's simplicial_set_embedding / optimize_layout_euclidean in its PER-EPOCH form (cuML's reproducible
+ * mode): every force of an epoch is evaluated from the positions at the epoch's start and then applied, so the result does not depend
+ * on the order in which threads run.  All float64; no operation is fused; int n -> double is exact.
+ *
+ * The problem: the prepared graph as CSR (indptr [n_cells + 1], cols, epochs_per_sample) -- host work in sisua_amd/neighbors.py: the
+ * symmetric fuzzy graph with its entries below max / n_epochs dropped, e = max / w per stored entry, both directions of an edge stored.
+ * indptr[0] = 0, rows that do not shrink, columns in 0 .. n_cells - 1, strictly increasing within a row and never the row itself, every e
+ * finite and > 0, at most 2^31 - 1 entries; the graph is symmetric (the caller's business: the factor 2 below relies on it); Y0
+ * [n_cells][n_components] finite; 1 <= n_components <= 3; 2 <= n_cells <= 2^31 - 1; 1 <= n_epochs <= 10000; 0 <= epoch_begin <=
+ * epoch_end <= n_epochs; a, b, gamma finite and >= 0; initial_alpha finite; 0 <= negative_sample_rate <= 64; next_sample and
+ * next_negative [entries] finite.  Anything else is SMX_ERR_INVALID before any device work.
+ *
+ * Schedule state of entry x (position in the CSR) with e = epochs_per_sample[x], S = negative_sample_rate, e_neg = e / S.  A run from
+ * epoch 0 starts at next_sample = e, next_negative = e_neg (S = 0: next_negative = e; it is then never read or written).  In epoch n
+ * (epoch_begin <= n < epoch_end) the entry is ACTIVE iff next_sample <= n.  An active entry draws m negatives,
+ *   m = min(max(trunc((n - next_negative) / e_neg), 0), S x n_epochs)   (S = 0: m = 0)
+ * (trunc: towards zero, umap-learn's (int); the clamp never acts on a state reached from the start above and bounds every other one),
+ * then next_sample = next_sample + e and next_negative = next_negative + m x e_neg (the product rounded, then the sum).
+ * alpha_n = initial_alpha x (1 - n / n_epochs).
+ *
+ * Forces on cell j in epoch n, all from Y as it stood when the epoch began: d = y_j - y_k per component, d2 = d_0 d_0 (+ d_1 d_1 (+ d_2 d_2))
+ * added in component order, clip(x) = min(4, max(-4, x)), pb = pow(d2, b): ONE pow per pair, d2^(b-1) is formed as pb / d2.
+ *   attraction of an active entry (j, k), when d2 > 0:   g = (((-2 a) b) (pb / d2)) / (a pb + 1);   term_c = 2 clip(g d_c)
+ *     (the 2: the entry's own head term plus the tail term of the mirror entry (k, j), which has the same weight, hence the same
+ *     schedule, and from the same positions is the same number);
+ *   negative p = 0 .. m - 1 of that entry: r = word (p & 3) of philox4x32_10(x, n, p >> 2, 100; seed & 0xFFFFFFFF, seed >> 32) -- the Philox
+ *     of every other kernel here, stream id 100 (ST_UMAP_NEG) -- and k = r % n_cells; skipped when d2 == 0 (k == j, or cells on top of each
+ *     other: umap-learn >= 0.5 adds 0); otherwise   g = ((2 gamma) b) / ((0.001 + d2) (a pb + 1));   term_c = clip(g d_c).   Only j moves.
+ *   y_j <- y_j + alpha_n x (the sum of the cell's terms).  A cell whose row is empty never moves.
+ * The sum of a cell is taken by L lanes over the row in chunks of L entries: L = 16 for a row of at most 64 entries, L = 256 (a workgroup
+ * of its own) for a longer one -- the hub of a kNN graph holds hundreds of entries.  Entry L c + l of the row belongs to lane l, which
+ * alone reads and writes its two schedule doubles.  Per chunk, lane l first adds the attraction of its own entry, then the chunk's
+ * negatives: they are numbered q = 0, 1, .. through the chunk's entries in row order (entry by entry, p ascending) and lane l adds the
+ * negatives q = l, l + L, l + 2 L, ... in this order.  After the last chunk the lanes are added by halving: L = 16: l + 8, l + 4, l + 2,
+ * l + 1; L = 256: within each wave of 64 lanes l + 32, l + 16, .. l + 1, then the four waves as (0 + 1) + (2 + 3).  The order
+ * is a function of the row and its schedule alone: no float atomics, two calls give the same bits, and a run cut into pieces
+ * (0 .. s, then s .. E with the schedule arrays and Y of the first piece) gives the bits of the whole.
+ * One launch per epoch, Y in two copies (one read, one written, then swapped), no host round trip inside a call.  On return Y is the
+ * embedding after epoch epoch_end - 1 and next_sample / next_negative (in/out) the schedule state at epoch_end.  Work: about entries x
+ * (1 + negative_sample_rate) x n_epochs x mean(w / max) pair evaluations with one float64 pow each.  Device memory: 16 n_components
+ * n_cells + 28 entries + 12 n_cells bytes.
+ *
+ * smx_umap_pow (tests): out[i] = the device's pow(x[i], b), the function the forces use; n >= 1, x finite and > 0, b finite. */
+int smx_umap_layout(const int64_t* indptr, const int32_t* cols, const double* epochs_per_sample, int64_t n_cells, int32_t n_components,
+                    const double* Y0, int32_t n_epochs, int32_t epoch_begin, int32_t epoch_end, double a, double b, double gamma,
+                    double initial_alpha, int32_t negative_sample_rate, uint64_t seed, double* next_sample, double* next_negative, double* Y);
+int smx_umap_pow(const double* x, double b, int64_t n, double* out);
 
 /* ---- gene x protein mutual information (smx_mi.hip; model-free: smx_init only) ----------- */
 /* scikit-learn's three kNN estimators per pair (gene column, protein column), float64, every distance the exact |a - b|.  The columns

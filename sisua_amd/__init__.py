@@ -15,7 +15,7 @@ from sisua_amd.metrics import correlation_list, marker_correlations, marker_scor
 from sisua_amd.minibatch_kmeans import MiniBatchKMeans  # noqa: F401
 from sisua_amd.mixture import GaussianMixture  # noqa: F401
 from sisua_amd.mutual_info import mutual_information  # noqa: F401
-from sisua_amd.neighbors import PCA, TSNE  # noqa: F401
+from sisua_amd.neighbors import PCA, TSNE, UMAP, umap  # noqa: F401
 from sisua_amd.rank_groups import rank_genes_groups, rank_genes_groups_logreg  # noqa: F401
 
 __version__ = "0.1.0"

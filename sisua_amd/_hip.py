@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsisua_hip.so")
 
-SMX_ABI_VERSION = 19
+SMX_ABI_VERSION = 20
 SMX_MAX_LAYERS = 8
 SMX_MAX_LABELS = 4
 
@@ -207,6 +207,9 @@ SIGNATURES = {
     "smx_tsne_gradient": (C.c_int, [_LP, _IP, _DP, C.c_int64, C.c_int32, _DP, C.c_double, _DP, _DP, _DP]),
     "smx_tsne_fit": (C.c_int, [_LP, _IP, _DP, C.c_int64, C.c_int32, _DP, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _DP, _DP, _IP,
                                _DP, _DP]),
+    "smx_umap_layout": (C.c_int, [_LP, _IP, _DP, C.c_int64, C.c_int32, _DP, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                  C.c_double, C.c_int32, C.c_uint64, _DP, _DP, _DP]),
+    "smx_umap_pow": (C.c_int, [_DP, C.c_double, C.c_int64, _DP]),
     "smx_mutual_info": (C.c_int, [_DP, C.POINTER(C.c_uint8), _DP, C.POINTER(C.c_uint8), C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP,
                                   _DP, _DP]),
     "smx_k_mi_cells": (C.c_int, [_DP, C.c_int32, _DP, C.c_int32, C.c_int64, C.c_int32, _DP, _DP, _IP, _DP, _DP]),

@@ -1,5 +1,5 @@
 // smx_block.h -- the workgroup building blocks of the model-free analysis kernels (smx_impute, smx_correlate, smx_cluster, smx_gmm,
-// smx_gmm_full, smx_knn, smx_tsne, smx_mi, smx_rankgroups, smx_mbkmeans, smx_louvain, smx_data, smx_prep), for 256-thread workgroups of four waves.  These pieces carry the entries'
+// smx_gmm_full, smx_knn, smx_tsne, smx_umap, smx_mi, smx_rankgroups, smx_mbkmeans, smx_louvain, smx_data, smx_prep), for 256-thread workgroups of four waves.  These pieces carry the entries'
 // determinism promises (the same bits for every chunking, exact ranks, exact order statistics), so each exists once:
 //   sums    the lanes of a wave by halving (lane l += lane l + 32, 16, .. 1: the result in lane 0), then the four waves as
 //           (0 + 1) + (2 + 3).  NOT the order of smx_device.h's float wave_sum / block_sum (the training step's), which stay where they are.

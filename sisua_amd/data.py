@@ -314,6 +314,7 @@ class SingleCellOMIC:
     self._pca = {}          # omic -> (PCA, scores) of dimension_reduce; likewise
     self._neighbors = {}    # omic -> (connectivities, distances, params) of neighbors; likewise
     self._tsne = {}         # (omic, n_components) -> the embedding of dimension_reduce(algo='tsne'); likewise
+    self._umap = {}         # (omic, n_components) -> the embedding of umap; likewise
     self._uns = {}          # the reference's .uns: 'mutualinfo_{omic}_{target}' -> (omic, target, matrix) of get_mutual_information and
                             # '{omic}_{group_by}_rank' -> (omic, grouping omic or None, dict) of rank_vars_groups; likewise
     self._obs = {}          # the reference's .obs: '{omic}_{algo}{n_clusters}' -> (omic, cluster omic or None, labels) of clustering, and
@@ -400,8 +401,9 @@ class SingleCellOMIC:
   def _drop_derived(self, key: str):
     for cache in (self._embeddings, self._pca, self._neighbors):
       cache.pop(key, None)
-    for kc in [kc for kc in self._tsne if kc[0] == key]:
-      del self._tsne[kc]
+    for cache in (self._tsne, self._umap):
+      for kc in [kc for kc in cache if kc[0] == key]:
+        del cache[kc]
     for store in (self._uns, self._obs):
       for kc in [kc for kc, v in store.items() if key in v[:2]]:
         del store[kc]
@@ -523,11 +525,12 @@ class SingleCellOMIC:
     objective with the exact repulsive sum).  n_components must be 1, 2 or 3 -- the signature's default of 100 belongs to 'pca' and is
     refused.  As in `neighbors`, an omic wider than 100 columns goes through dimension_reduce(algo='pca') first (its 100 scores; a kept
     PCA is reused).  The start is the PCA init, so random_state is unused.  The result is kept per omic and n_components.
-    'umap' is not built."""
+    'umap' is not built under this name: the UMAP embedding is `SingleCellOMIC.umap`."""
     from sisua_amd import neighbors as nb
     algo = str(algo).lower().strip()
     if algo == "umap":
-      raise NotImplementedError(f"dimension_reduce(algo={algo!r}) is not built: only algo='pca' and algo='tsne' are")
+      raise NotImplementedError(f"dimension_reduce(algo={algo!r}) is not built: only algo='pca' and algo='tsne' are; the UMAP embedding "
+                                "is SingleCellOMIC.umap")
     if algo == "tsne":
       C = nb.check_tsne_components(n_components)   # (before anything else is looked at)
       key = self._first(omic)
@@ -661,7 +664,8 @@ class SingleCellOMIC:
     if name in self._obs:
       return name if return_key else self._obs[name][2]
     if algo not in ("kmeans", "pca", "tsne"):
-      raise NotImplementedError(f"clustering(algo={algo!r}) is not built: only algo='kmeans', 'pca' and 'tsne' are")
+      raise NotImplementedError(f"clustering(algo={algo!r}) is not built: only algo='kmeans', 'pca' and 'tsne' are (the UMAP embedding "
+                                "itself is SingleCellOMIC.umap)")
     if algo == "kmeans":
       X = self.numpy(key)
     else:
@@ -709,6 +713,33 @@ class SingleCellOMIC:
       names = communities.community_names(ids, self.get_x_probs(key), self._vars[key])
       self._obs[name_labels] = (key, None, np.array([names[int(c)] for c in ids]))
     return ids.astype(np.float32), self._obs[name_labels][2]
+
+  def umap(self, omic=None, n_components=2, min_dist=0.5, spread=1.0, n_epochs=None, random_state=1):
+    """The UMAP embedding [cells, n_components] float32 of the omic (the reference's dimension_reduce(algo='umap'), which calls cuML or
+    umap-learn; scanpy's tl.umap defaults min_dist = 0.5, spread = 1): the layout (`sisua_amd.neighbors.umap_layout`, the per-epoch form
+    on the device, smx_umap.hip) of `self.neighbors(omic)`'s connectivities -- the kept graph, or the one a first call of neighbors with
+    its defaults leaves.  n_components must be 1, 2 or 3.  The start is the PCA init as in dimension_reduce(algo='tsne'): the first
+    n_components exact-PCA scores of the representation (an omic wider than 100 columns goes through dimension_reduce(algo='pca') first;
+    a kept PCA is reused), mapped per axis to [0, 10]; random_state seeds the negative samples.  The result is kept per omic and
+    n_components until the omic is replaced, and a later call returns it whatever its other arguments.
+    Not built: spectral init, transform of new cells, other output metrics; dimension_reduce(algo='umap') and clustering(algo='umap')
+    keep raising NotImplementedError."""
+    from sisua_amd import neighbors as nb
+    C = nb.check_umap_components(n_components)   # (before anything else is looked at)
+    key = self._first(omic)
+    if key not in self._data:
+      raise ValueError(f"omic={omic!r} is not one of the omics {self.omics}")
+    if (key, C) not in self._umap:
+      nb._umap_params(self.n_obs, C, min_dist, spread, n_epochs, 1.0, 1.0, 5, random_state)   # (refusals before any device work)
+      graph = self.neighbors(key)[0]
+      if self.get_dim(key) > 100:
+        rep = self.dimension_reduce(key, algo="pca")
+      else:
+        rep = self.numpy(key)
+        rep = rep.toarray() if is_sparse(rep) else rep
+      Y0 = nb.umap_init(self.n_obs, C, "pca", random_state, rep)
+      self._umap[(key, C)] = nb.umap_layout(graph, C, min_dist, spread, n_epochs, init=Y0, random_state=random_state)
+    return self._umap[(key, C)]
 
   def get_pca(self, omic=None):
     """The fitted `sisua_amd.PCA` of an omic (what `dimension_reduce` left), or None"""

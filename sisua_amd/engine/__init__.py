@@ -11,7 +11,7 @@ as `engine.<name>`:
   _kernels     single launches of the training step by themselves (tests)
   _correlate   gene x protein correlation sums        _cluster     silhouette, Lloyd's k-means
   _gmm         the 1-D and the full-covariance mixture  _prep        count-matrix preprocessing
-  _neighbors   PCA, kNN, UMAP connectivities, t-SNE   _mi          mutual information
+  _neighbors   PCA, kNN, UMAP graph and layout, t-SNE _mi          mutual information
   _groups      group moments and rank sums            _mbkmeans    mini-batch k-means
   _logreg      logistic regression                    _louvain     Louvain communities, modularity
 
@@ -39,7 +39,7 @@ from sisua_amd.engine._mbkmeans import (MBK_MAX_CLUSTERS, MBK_MAX_GENES, MBK_MAX
 from sisua_amd.engine._mi import MI_MAX_CELLS, MI_MAX_NEIGHBORS, _mi_check, _mi_cols, _mi_tables, k_mi_cells, mutual_info
 from sisua_amd.engine._model import (STREAM_DEC_DROPOUT, STREAM_ENC_DROPOUT, STREAM_ENCL_DROPOUT, STREAM_EPS_L, STREAM_EPS_Z,
                                      STREAM_INPUT_DROPOUT, _SCHED_TARGETS, Engine, _check_u16, _tril_scale, gene_indices, make_smx_config)
-from sisua_amd.engine._neighbors import (KNN_MAX_D, KNN_MAX_K, PCA_MAX_COMPONENTS, PCA_MAX_GENES, TSNE_MAX_COMPONENTS, _pca_input,
-                                         _tsne_problem, k_knn, k_knn_umap, k_pca_cov, k_pca_project, k_tsne_affinities, k_tsne_fit,
-                                         k_tsne_gradient)
+from sisua_amd.engine._neighbors import (KNN_MAX_D, KNN_MAX_K, PCA_MAX_COMPONENTS, PCA_MAX_GENES, TSNE_MAX_COMPONENTS, UMAP_MAX_COMPONENTS,
+                                         UMAP_MAX_EPOCHS, UMAP_MAX_NEGATIVES, _pca_input, _tsne_problem, _umap_problem, k_knn, k_knn_umap,
+                                         k_pca_cov, k_pca_project, k_tsne_affinities, k_tsne_fit, k_tsne_gradient, k_umap_layout, k_umap_pow)
 from sisua_amd.engine._prep import PREP_FUNCS, _prep_input, k_prep_apply, k_prep_stats

@@ -1,4 +1,5 @@
-"""Neighbour graphs and embeddings: PCA (smx_pca.hip), exact kNN and UMAP connectivities (smx_knn.hip), t-SNE (smx_tsne.hip)."""
+"""Neighbour graphs and embeddings: PCA (smx_pca.hip), exact kNN and UMAP connectivities (smx_knn.hip), t-SNE (smx_tsne.hip), the UMAP
+layout (smx_umap.hip)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -166,3 +167,93 @@ def k_tsne_fit(P, Y0, max_iter: int = 1000, early_exaggeration: float = 12.0, le
   check(lib.smx_tsne_fit(_ptr(indptr), _ip(cols), _dp(p), y0.shape[0], y0.shape[1], _dp(y0), max_iter, ee, lr,
                          mgn, nwp, _dp(Y), _dp(trace), _ip(n_iter), _dp(update), _dp(gains)))
   return dict(Y=Y, update=update, gains=gains, kl_trace=trace, n_iter=int(n_iter[0]))
+
+
+UMAP_MAX_COMPONENTS = 3
+UMAP_MAX_EPOCHS = 10000
+UMAP_MAX_NEGATIVES = 64
+
+
+def _umap_problem(E, Y):
+  """The prepared graph E (scipy.sparse CSR [N, N] of epochs_per_sample: symmetric support and values, sorted columns, no diagonal,
+  entries > 0) and an embedding Y [N, 1 .. 3] as smx_umap_layout takes them, checked here so that a refusal never asks for the device
+  -> (indptr int64, cols int32, eps float64, y float64)"""
+  import scipy.sparse as sp
+  if not sp.issparse(E) or E.format != "csr" or E.ndim != 2 or E.shape[0] != E.shape[1]:
+    raise ValueError(f"the graph must be a square scipy.sparse CSR matrix, got {type(E).__name__} of shape {getattr(E, 'shape', None)}")
+  N = E.shape[0]
+  if not 2 <= N < 2 ** 31:
+    raise ValueError(f"a UMAP layout needs 2 .. 2^31 - 1 cells, got {N}")
+  y = np.ascontiguousarray(Y, dtype=np.float64)
+  if y.ndim != 2 or y.shape[0] != N or not 1 <= y.shape[1] <= UMAP_MAX_COMPONENTS:
+    raise ValueError(f"Y must be [{N}, 1 .. {UMAP_MAX_COMPONENTS}], got {y.shape}")
+  if not np.isfinite(y).all():
+    raise ValueError("Y holds an entry that is not finite")
+  indptr, cols = np.ascontiguousarray(E.indptr, dtype=np.int64), np.ascontiguousarray(E.indices, dtype=np.int32)
+  eps = np.ascontiguousarray(E.data, dtype=np.float64)
+  if indptr.shape != (N + 1,) or indptr[0] != 0 or (np.diff(indptr) < 0).any() or indptr[-1] != cols.size or eps.size != cols.size:
+    raise ValueError("the graph's indptr does not describe its entries")
+  if cols.size >= 2 ** 31:
+    raise ValueError(f"the graph holds {cols.size} entries, at most 2^31 - 1 are taken")
+  if cols.size and (cols.min() < 0 or cols.max() >= N):
+    raise ValueError("the graph holds a column outside 0 .. cells - 1")
+  inner = np.ones(cols.size, bool)
+  inner[indptr[:-1][indptr[:-1] < cols.size]] = False   # (the first entry of a row has no entry in front of it)
+  if (np.diff(cols.astype(np.int64), prepend=-1)[inner] <= 0).any():
+    raise ValueError("the columns of a row of the graph must increase strictly (sort_indices, sum_duplicates)")
+  if (cols == np.repeat(np.arange(N), np.diff(indptr))).any():
+    raise ValueError("the graph holds an entry on the diagonal")
+  if not (np.isfinite(eps).all() and (eps > 0).all()):
+    raise ValueError("every epochs_per_sample must be finite and positive")
+  if (E != E.T).nnz:
+    raise ValueError("the graph is not symmetric")
+  return indptr, cols, eps, y
+
+
+def k_umap_layout(E, Y0, n_epochs: int, a: float, b: float, gamma: float = 1.0, initial_alpha: float = 1.0, negative_sample_rate: int = 5,
+                  seed: int = 0, epoch_begin: int = 0, epoch_end=None, next_sample=None, next_negative=None):
+  """smx_umap_layout: the epochs epoch_begin .. epoch_end - 1 (None: n_epochs) of the per-epoch UMAP layout from Y0 [N, C] on the prepared
+  graph E (CSR of epochs_per_sample).  next_sample / next_negative [entries]: the schedule state at epoch_begin (None: the start of a
+  run, e and e / negative_sample_rate) -> dict(Y [N, C], next_sample, next_negative [entries]) float64, the state at epoch_end"""
+  indptr, cols, eps, y0 = _umap_problem(E, Y0)
+  n_epochs, S, seed = int(n_epochs), int(negative_sample_rate), int(seed)
+  if not 1 <= n_epochs <= UMAP_MAX_EPOCHS:
+    raise ValueError(f"n_epochs must be in 1 .. {UMAP_MAX_EPOCHS}, got {n_epochs}")
+  begin, end = int(epoch_begin), n_epochs if epoch_end is None else int(epoch_end)
+  if not 0 <= begin <= end <= n_epochs:
+    raise ValueError(f"the epochs must obey 0 <= epoch_begin <= epoch_end <= n_epochs = {n_epochs}, got {begin} and {end}")
+  if not 0 <= S <= UMAP_MAX_NEGATIVES:
+    raise ValueError(f"negative_sample_rate must be in 0 .. {UMAP_MAX_NEGATIVES}, got {S}")
+  a, b, gamma, alpha = float(a), float(b), float(gamma), float(initial_alpha)
+  if not (np.isfinite(a) and a >= 0 and np.isfinite(b) and b >= 0 and np.isfinite(gamma) and gamma >= 0):
+    raise ValueError(f"a, b and gamma must be finite and >= 0, got {a}, {b} and {gamma}")
+  if not np.isfinite(alpha):
+    raise ValueError(f"initial_alpha must be finite, got {alpha}")
+  if not 0 <= seed < 2 ** 64:
+    raise ValueError(f"seed must be in 0 .. 2^64 - 1, got {seed}")
+  if (next_sample is None) != (next_negative is None):
+    raise ValueError("next_sample and next_negative come together or not at all")
+  if next_sample is None:
+    nxt, neg = eps.copy(), (eps / S if S > 0 else eps.copy())
+  else:
+    nxt, neg = np.array(next_sample, dtype=np.float64), np.array(next_negative, dtype=np.float64)
+    if nxt.shape != eps.shape or neg.shape != eps.shape:
+      raise ValueError(f"next_sample and next_negative must be [{eps.size}], one per entry, got {nxt.shape} and {neg.shape}")
+    if not (np.isfinite(nxt).all() and np.isfinite(neg).all()):
+      raise ValueError("next_sample and next_negative must be finite")
+  lib = _hip.require_gpu()
+  Y = np.empty_like(y0)
+  check(lib.smx_umap_layout(_ptr(indptr), _ip(cols), _dp(eps), y0.shape[0], y0.shape[1], _dp(y0), n_epochs, begin, end, a, b, gamma, alpha, S,
+                            seed, _dp(nxt), _dp(neg), _dp(Y)))
+  return dict(Y=Y, next_sample=nxt, next_negative=neg)
+
+
+def k_umap_pow(x, b: float):
+  """smx_umap_pow: the device's pow(x, b) for x [n] float64, finite and > 0 -- the function the UMAP forces use (tests)"""
+  x, b = np.ascontiguousarray(x, dtype=np.float64), float(b)
+  if x.ndim != 1 or x.size < 1 or not (np.isfinite(x).all() and (x > 0).all()) or not np.isfinite(b):
+    raise ValueError("x must be [n >= 1], finite and positive, and b finite")
+  lib = _hip.require_gpu()
+  out = np.empty_like(x)
+  check(lib.smx_umap_pow(_dp(x), b, x.size, _dp(out)))
+  return out

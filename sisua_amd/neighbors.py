@@ -9,11 +9,14 @@ runs in libsisua_hip.so (smx_pca.hip, smx_knn.hip; definitions in include/sisua_
   neighbors(Z, n_neighbors)    -> (connectivities, distances) of a latent space, e.g. model.encode's
   tsne_affinities(Z, perplexity) -> P, t-SNE's joint affinities, CSR float64
   tsne(Z, n_components, ...) / TSNE -> Y [N, C <= 3] float32: scikit-learn's t-SNE with the EXACT repulsive sum (smx_tsne.hip, section 4x)
+  umap_layout(graph, ...)      -> Y [N, C <= 3] float32: UMAP's layout of a fuzzy graph, the per-epoch form (smx_umap.hip, section 4zd)
+  umap(Z, n_neighbors, ...) / UMAP -> Y: kNN, connectivities and the layout
 
 PCA here is EXACT: the eigen-decomposition of the two-pass float64 covariance.  The reference's IncrementalPCA over batches of 4096 rows
 is exact PCA for one batch and an approximation of it for several.
 
-Not built: the UMAP embedding, Barnes-Hut / FFT approximations of t-SNE, t-SNE into more than 3 dimensions or with a perplexity above 85,
+Not built: UMAP's spectral init, `transform` of new cells, output metrics other than Euclidean, UMAP into more than 3 dimensions, parity
+with umap-learn's random stream; Barnes-Hut / FFT approximations of t-SNE, t-SNE into more than 3 dimensions or with a perplexity above 85,
 method='gauss', knn=False, metrics other than Euclidean, approximate neighbour search, PCA of matrices wider than 8192 columns."""
 from __future__ import annotations
 
@@ -25,6 +28,9 @@ MAX_KNN_DIM = 128        # smx_knn
 MAX_NEIGHBORS = 257      # smx_knn: k <= 256 others, plus the cell itself
 MAX_TSNE_COMPONENTS = 3  # smx_tsne_fit
 MAX_PERPLEXITY = 85.0    # floor(3 perplexity + 1) <= 256 neighbours
+MAX_UMAP_COMPONENTS = 3  # smx_umap_layout
+MAX_UMAP_EPOCHS = 10000
+MAX_UMAP_NEGATIVES = 64
 
 
 def _engine():
@@ -292,3 +298,181 @@ def tsne(Z, n_components: int = 2, perplexity: float = 30.0, early_exaggeration:
   (see `TSNE`)"""
   return TSNE(n_components, perplexity, early_exaggeration, learning_rate, max_iter, n_iter_without_progress, min_grad_norm, init,
               random_state).fit_transform(Z)
+
+
+# ---- UMAP (smx_umap.hip; definitions in include/sisua_hip.h and DESIGN.md section 4zd) ----
+def check_umap_components(n_components) -> int:
+  if isinstance(n_components, bool) or n_components != int(n_components) or not 1 <= int(n_components) <= MAX_UMAP_COMPONENTS:
+    raise NotImplementedError(f"UMAP embeds into at most {MAX_UMAP_COMPONENTS} dimensions here (n_components = 1, 2 or 3), got "
+                              f"{n_components}: pass n_components=2, or use pca(X, n_components) for wider representations")
+  return int(n_components)
+
+
+def find_ab_params(spread: float = 1.0, min_dist: float = 0.5):
+  """umap-learn's find_ab_params: a, b of 1 / (1 + a x^(2b)) fitted (scipy.optimize.curve_fit, its defaults) to the curve that is 1 up to
+  min_dist and exp(-(x - min_dist) / spread) after, on 300 points of [0, 3 spread] -> (a, b) floats"""
+  from scipy.optimize import curve_fit
+  spread, min_dist = float(spread), float(min_dist)
+  if not (np.isfinite(spread) and spread > 0 and np.isfinite(min_dist) and 0 <= min_dist <= spread):
+    raise ValueError(f"spread must be finite and positive and 0 <= min_dist <= spread, got spread = {spread} and min_dist = {min_dist}")
+
+  def curve(x, a, b):
+    return 1.0 / (1.0 + a * x ** (2 * b))
+
+  xv = np.linspace(0, spread * 3, 300)
+  yv = np.zeros(xv.shape)
+  yv[xv < min_dist] = 1.0
+  yv[xv >= min_dist] = np.exp(-(xv[xv >= min_dist] - min_dist) / spread)
+  params, _ = curve_fit(curve, xv, yv)
+  return float(params[0]), float(params[1])
+
+
+def umap_n_epochs(n_cells: int, n_epochs=None) -> int:
+  """umap-learn's default: 500 epochs up to 10000 cells, 200 above; a given n_epochs must be in 1 .. 10000"""
+  if n_epochs is None:
+    return 500 if int(n_cells) <= 10000 else 200
+  if isinstance(n_epochs, bool) or n_epochs != int(n_epochs) or not 1 <= int(n_epochs) <= MAX_UMAP_EPOCHS:
+    raise ValueError(f"n_epochs must be None or a whole number in 1 .. {MAX_UMAP_EPOCHS}, got {n_epochs}")
+  return int(n_epochs)
+
+
+def umap_prepare_graph(graph, n_epochs: int):
+  """The graph as the layout takes it (host only; umap-learn's simplicial_set_embedding): a symmetric scipy.sparse matrix [cells, cells]
+  of weights > 0 without diagonal -> CSR float64 [cells, cells] of epochs_per_sample = max / w, columns sorted, duplicates summed, the
+  entries below max / n_epochs dropped (the cut is symmetric; a row may become empty: that cell never moves)"""
+  if not sp.issparse(graph) or graph.ndim != 2 or graph.shape[0] != graph.shape[1]:
+    raise ValueError(f"the graph must be a square scipy.sparse matrix over the cells, got {type(graph).__name__} of shape "
+                     f"{getattr(graph, 'shape', None)}")
+  n = graph.shape[0]
+  if not 2 <= n < 2 ** 31:
+    raise ValueError(f"a UMAP layout needs 2 .. 2^31 - 1 cells, got {n}")
+  G = sp.csr_matrix(graph, dtype=np.float64, copy=True)
+  G.sum_duplicates()
+  G.sort_indices()
+  if not np.isfinite(G.data).all() or (G.data < 0).any():
+    raise ValueError("the graph's weights must be finite and not negative")
+  G.eliminate_zeros()
+  if (G.diagonal() != 0).any():
+    raise ValueError("the graph holds entries on its diagonal: a cell is not its own neighbour")
+  if (G != G.T).nnz:
+    raise ValueError("the graph is not symmetric: symmetrise it first, e.g. with umap_connectivities")
+  if G.nnz >= 2 ** 31:
+    raise ValueError(f"the graph holds {G.nnz} entries, at most 2^31 - 1 are taken")
+  if G.nnz:
+    top = float(G.data.max())
+    G.data[G.data < top / float(n_epochs)] = 0.0
+    G.eliminate_zeros()
+    G.data = top / G.data
+  return G
+
+
+def umap_normalise(Y0):
+  """The start mapped per axis to [0, 10]: 10 (Y - min) / (max - min); an axis with max == min becomes 5 (float64)"""
+  Y0 = np.asarray(Y0, dtype=np.float64)
+  lo, hi = Y0.min(axis=0), Y0.max(axis=0)
+  flat = hi == lo
+  out = 10.0 * (Y0 - lo) / np.where(flat, 1.0, hi - lo)
+  out[:, flat] = 5.0
+  return out
+
+
+def umap_init(n_cells: int, n_components: int, init="random", random_state=1, Z=None):
+  """The start of the layout before umap_normalise, float64 [cells, C].  'random': RandomState(random_state).uniform(-10, 10); 'pca' (needs
+  the cells Z): the first C exact-PCA scores (fewer than C columns in Z: the rest start at 0); or an array [cells, C]"""
+  n, C = int(n_cells), int(n_components)
+  if isinstance(init, str):
+    if init == "spectral":
+      raise NotImplementedError("init='spectral' is not built: use init='pca' (the default of `umap`), 'random' or an array")
+    if init == "random":
+      return np.random.RandomState(random_state).uniform(-10.0, 10.0, size=(n, C))
+    if init != "pca":
+      raise ValueError(f"init must be 'pca', 'random' or an array [cells, {C}], got {init!r}")
+    if Z is None:
+      raise ValueError("init='pca' needs the cells, which a graph does not hold: call umap(Z, ...) or pass the PCA scores as init")
+    scores = pca(Z, C)[1].astype(np.float64)
+    if scores.shape[1] < C:
+      scores = np.concatenate([scores, np.zeros((n, C - scores.shape[1]))], axis=1)
+    return scores
+  Y0 = np.array(init, dtype=np.float64)
+  if Y0.shape != (n, C):
+    raise ValueError(f"init must be 'pca', 'random' or an array [{n}, {C}], got an array of shape {Y0.shape}")
+  if not np.isfinite(Y0).all():
+    raise ValueError("init holds an entry that is not finite")
+  return Y0
+
+
+def _umap_params(n_cells, n_components, min_dist, spread, n_epochs, alpha, gamma, negative_sample_rate, random_state):
+  """every scalar of the layout, checked on the host -> (C, n_epochs, alpha, gamma, S, seed)"""
+  C = check_umap_components(n_components)
+  E = umap_n_epochs(n_cells, n_epochs)
+  alpha, gamma = float(alpha), float(gamma)
+  if not (np.isfinite(alpha) and alpha > 0):
+    raise ValueError(f"alpha (the initial learning rate) must be finite and positive, got {alpha}")
+  if not (np.isfinite(gamma) and gamma >= 0):
+    raise ValueError(f"gamma (the repulsion strength) must be finite and >= 0, got {gamma}")
+  S = negative_sample_rate
+  if isinstance(S, bool) or S != int(S) or not 0 <= int(S) <= MAX_UMAP_NEGATIVES:
+    raise ValueError(f"negative_sample_rate must be a whole number in 0 .. {MAX_UMAP_NEGATIVES}, got {negative_sample_rate}")
+  if isinstance(random_state, bool) or not isinstance(random_state, (int, np.integer)) or not 0 <= int(random_state) < 2 ** 32:
+    raise ValueError(f"random_state must be an integer in 0 .. 2^32 - 1 (it seeds RandomState and the negative samples), got {random_state!r}")
+  spread, min_dist = float(spread), float(min_dist)
+  if not (np.isfinite(spread) and spread > 0 and np.isfinite(min_dist) and 0 <= min_dist <= spread):
+    raise ValueError(f"spread must be finite and positive and 0 <= min_dist <= spread, got spread = {spread} and min_dist = {min_dist}")
+  return C, E, alpha, gamma, int(S), int(random_state)
+
+
+def umap_layout(graph, n_components: int = 2, min_dist: float = 0.5, spread: float = 1.0, n_epochs=None, alpha: float = 1.0,
+                gamma: float = 1.0, negative_sample_rate: int = 5, init="random", random_state=1, return_info: bool = False):
+  """UMAP's layout of a symmetric fuzzy graph (e.g. `neighbors(Z)[0]`), umap-learn's simplicial_set_embedding with the optimiser in its
+  PER-EPOCH form (every force of an epoch from the positions at its start; float64 on the device, smx_umap.hip) -> Y [cells, C <= 3]
+  float32 (the float64 result rounded once).  init: 'random' (the default: a graph holds no cells to take a PCA of) or an array
+  [cells, C]; the start is mapped per axis to [0, 10].  return_info: (Y, dict(n_epochs, a, b, graph = the prepared CSR of
+  epochs_per_sample, init = the normalised start))"""
+  n = graph.shape[0] if hasattr(graph, "shape") and len(graph.shape) == 2 else 0
+  C, E, alpha, gamma, S, seed = _umap_params(n, n_components, min_dist, spread, n_epochs, alpha, gamma, negative_sample_rate, random_state)
+  G = umap_prepare_graph(graph, E)
+  Y0 = umap_normalise(umap_init(n, C, init, seed))
+  a, b = find_ab_params(spread, min_dist)
+  fit = _engine().k_umap_layout(G, Y0, E, a, b, gamma, alpha, S, seed)
+  Y = fit["Y"].astype(np.float32)
+  return (Y, dict(n_epochs=E, a=a, b=b, graph=G, init=Y0)) if return_info else Y
+
+
+class UMAP:
+  """UMAP with umap-learn's graph, schedule and attribute names and scanpy's defaults (min_dist = 0.5, spread = 1): exact neighbours,
+  the fuzzy union, and the layout in its per-epoch form (smx_knn.hip, smx_umap.hip).  After fit_transform: embedding_ [cells, C]
+  float32, graph_ (the connectivities, CSR float32), n_epochs_, a_, b_.  init='pca' (the default, as `TSNE` here), 'random' or an array."""
+
+  def __init__(self, n_neighbors=12, n_components=2, min_dist=0.5, spread=1.0, n_epochs=None, alpha=1.0, gamma=1.0,
+               negative_sample_rate=5, init="pca", random_state=1):
+    self.n_neighbors, self.n_components, self.min_dist, self.spread, self.n_epochs = n_neighbors, n_components, min_dist, spread, n_epochs
+    self.alpha, self.gamma, self.negative_sample_rate, self.init, self.random_state = alpha, gamma, negative_sample_rate, init, random_state
+
+  def fit_transform(self, Z):
+    if getattr(Z, "ndim", 0) == 2 and Z.shape[1] > MAX_KNN_DIM:
+      raise ValueError(f"UMAP of {Z.shape[1]} columns is not built: the exact neighbour search takes at most D <= {MAX_KNN_DIM}; reduce "
+                       "the matrix first with pca(X, n_components)")
+    Z = _check_cells(Z)
+    n = Z.shape[0]
+    C, _, _, _, _, seed = _umap_params(n, self.n_components, self.min_dist, self.spread, self.n_epochs, self.alpha, self.gamma,
+                                       self.negative_sample_rate, self.random_state)
+    K = check_n_neighbors(self.n_neighbors, n)
+    if not isinstance(self.init, str) or self.init != "pca":
+      umap_init(n, C, self.init, seed)   # (a refusal comes before any device work)
+    conn, _ = neighbors(Z, K)
+    Y0 = umap_init(n, C, self.init, seed, Z)
+    Y, info = umap_layout(conn, C, self.min_dist, self.spread, self.n_epochs, self.alpha, self.gamma, self.negative_sample_rate, Y0, seed,
+                          return_info=True)
+    self.embedding_, self.graph_, self.n_epochs_, self.a_, self.b_ = Y, conn, info["n_epochs"], info["a"], info["b"]
+    return Y
+
+  def fit(self, Z):
+    self.fit_transform(Z)
+    return self
+
+
+def umap(Z, n_neighbors: int = 12, n_components: int = 2, min_dist: float = 0.5, spread: float = 1.0, n_epochs=None, alpha: float = 1.0,
+         gamma: float = 1.0, negative_sample_rate: int = 5, init="pca", random_state=1):
+  """The UMAP embedding of the cells Z [cells, D <= 128], e.g. a latent space or PCA scores -> Y [cells, n_components <= 3] float32 (see
+  `UMAP`)"""
+  return UMAP(n_neighbors, n_components, min_dist, spread, n_epochs, alpha, gamma, negative_sample_rate, init, random_state).fit_transform(Z)
