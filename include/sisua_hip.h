@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 20
+#define SMX_ABI_VERSION 21
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -1208,6 +1208,60 @@ int smx_logreg_fit(const float* x, const int64_t* indptr, const int32_t* cols, c
                    int32_t* converged);
 int smx_logreg_decision(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_rows, int32_t n_genes,
                         int32_t block_rows, int32_t n_classes, int32_t form, const double* W, const double* b, double* logits);
+
+/* ---- gradient-boosted classification trees on a histogram of the count matrix (smx_gbt.hip; model-free: smx_init only) ----------- */
+/* What the reference's get_importance_matrix / cal_importance / cal_dci ask of scikit-learn's GradientBoostingClassifier (loss='log_loss',
+ * criterion='friedman_mse', subsample=1.0, max_features=None, prior init, Newton leaf values, x <= threshold goes left), with four stated
+ * deviations that make the result one answer whatever the order of the sums (tests/gbt_ref.py restates it in NumPy):
+ *   bins        a column (float32) with at most 256 distinct values has a bin per value; a wider one is cut between the sorted positions
+ *               p - 1 and p, p = floor(j N / 256), j = 1 .. 255, wherever the two values differ.  A threshold is the float32 midpoint
+ *               a/2 + b/2 of the two values a cut lies between (a where that rounds to b): bin(x) <= b exactly where x <= thresholds[b].
+ *   statistics  per stage and class, the residual y_k - p_k and the curvature p_k (1 - p_k) as rint(v 2^40) int64: every per-(node, bin)
+ *               sum, every count and every per-leaf sum is an exact integer (integer LDS and global atomics; n_rows <= 2^20).
+ *   split rule  a candidate leaves min(nL, nR) >= min_samples_leaf; its improvement SL SL / nL + SR SR / nR - S S / n is evaluated in
+ *               float64 from the integers in that order, without contraction; the largest wins, ties go to the lowest feature, then the
+ *               lowest bin.  A node is a leaf at max_depth, with n < min_samples_split, n < 2 min_samples_leaf or no improvement > 0.
+ *   leaf value  scale * sum r / sum h, 0 where sum h is 0; scale = (K - 1) / K, 1 for two classes; learning_rate is applied when the
+ *               value is added to the raw scores (float64).
+ * A tree is M = 2^(max_depth + 1) - 1 slots in heap order (the children of slot t are 2 t + 1 and 2 t + 2): feature int32 (-1: a leaf or
+ * an unreached slot), threshold float32, left / right int32 (-1 on a leaf), value float64 (leaves), n int32 (0: unreached), improvement
+ * float64 in residual units (the integer improvement x 2^-80).  Two classes fit ONE tree per stage (Kz = 1: the class-1 logit), K >= 3
+ * classes K trees (Kz = K).  Dense and CSR input give the same bits, and so do two calls and every pass_pairs.
+ * Limits: n_rows <= 2^20, n_genes <= 32768, rows x ld <= 2^31 (the float32 matrix is held whole while it is binned), 2 .. 32 classes,
+ * max_depth 1 .. 6, learning_rate finite and > 0, min_samples_split >= 2, min_samples_leaf >= 1, every entry finite, every class with a
+ * row: anything else is SMX_ERR_INVALID before any device work.
+ *
+ * smx_gbt_bin: thresholds [n_genes][255] float32 (zero behind the column's count), n_thresholds [n_genes], bins [n_genes][n_rows] uint8.
+ * One workgroup per column sorts it (four 8-bit passes).
+ *
+ * smx_gbt_grow: the n_trees trees of one stage from given statistics q_r, q_h [n_trees][n_rows] int64 (|q_r| <= 2^41, 0 <= q_h <= 2^41)
+ * over a bin matrix in smx_gbt_bin's layout; four launches per level, nothing read back in between.  leaf [n_trees][n_rows]: each cell's
+ * leaf slot.  pass_pairs: the (class, node) pairs whose histograms one workgroup of the sweep holds in LDS, 1 .. 16 (0: 16 = 48 KiB); it
+ * changes no bit.
+ *
+ * smx_gbt_fit: the stage loop.  init [Kz]: the raw scores of the prior.  n_iter_no_change > 0: scikit-learn's early stopping on the
+ * validation rows (xv .. labels_val, the forms of x; they take no part in the bins or the trees): stage i is the last when its
+ * validation loss + tol is below none of the last n_iter_no_change ones.  Out: the tree arrays [n_estimators][Kz][M] (stages behind
+ * *n_estimators_out stay unreached), train_score / val_score [n_estimators]: the mean loss after each stage (x 2 for two classes, as
+ * scikit-learn reports it).  The host reads two scalars per stage.
+ *
+ * smx_gbt_decision: raw [n_rows][n_outputs] float64 = init, then stage by stage + learning_rate * the row's leaf value, by x <=
+ * threshold on the float32 entries; the matrix streamed in blocks of block_rows rows (0: the library's choice; no bit depends on it). */
+int smx_gbt_bin(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_rows, int32_t n_genes,
+                float* thresholds, int32_t* n_thresholds, uint8_t* bins);
+int smx_gbt_grow(const uint8_t* bins, const int32_t* n_thresholds, const float* thresholds, const int64_t* q_r, const int64_t* q_h,
+                 int64_t n_rows, int32_t n_genes, int32_t n_trees, int32_t max_depth, int64_t min_samples_split, int64_t min_samples_leaf,
+                 double scale, int32_t pass_pairs, int32_t* feature, float* threshold, int32_t* left, int32_t* right, double* value,
+                 int32_t* n, double* improvement, int32_t* leaf);
+int smx_gbt_fit(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_rows, int32_t n_genes,
+                const int32_t* labels, int32_t n_classes, const float* xv, const int64_t* v_indptr, const int32_t* v_cols, const float* v_vals,
+                int64_t n_val, const int32_t* labels_val, int32_t n_estimators, double learning_rate, int32_t max_depth,
+                int64_t min_samples_split, int64_t min_samples_leaf, int32_t n_iter_no_change, double tol, int32_t pass_pairs,
+                const double* init, int32_t* feature, float* threshold, int32_t* left, int32_t* right, double* value, int32_t* n,
+                double* improvement, int32_t* n_estimators_out, double* train_score, double* val_score);
+int smx_gbt_decision(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n_rows, int32_t n_genes,
+                     int32_t block_rows, int32_t n_stages, int32_t n_outputs, int32_t max_depth, const int32_t* feature, const float* threshold,
+                     const int32_t* left, const int32_t* right, const double* value, const double* init, double learning_rate, double* raw);
 
 /* ---- padding audit (test instrument; never on the path of a step) ----------- */
 /* The layout's invariant, read back from the device: every feature axis is padded to 32 and every tensor to 64 floats, and what lies

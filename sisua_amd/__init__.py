@@ -6,12 +6,13 @@ is no CPU fallback: without the built library and a visible MI355X every
 compute entry point raises `SmxError`.
 """
 from sisua_amd._hip import SmxError  # noqa: F401
+from sisua_amd.boosting import GradientBoostingClassifier, importance_matrix  # noqa: F401
 from sisua_amd.communities import louvain, modularity  # noqa: F401
 from sisua_amd.config import ModelConfig, NetConf, RVmeta  # noqa: F401
 from sisua_amd.distributions import correlations_from_sums, protein_operands  # noqa: F401
 from sisua_amd.label_threshold import ProbabilisticEmbedding  # noqa: F401
 from sisua_amd.logistic import LogisticRegression  # noqa: F401
-from sisua_amd.metrics import correlation_list, marker_correlations, marker_scores  # noqa: F401
+from sisua_amd.metrics import correlation_list, dci_scores, marker_correlations, marker_scores  # noqa: F401
 from sisua_amd.minibatch_kmeans import MiniBatchKMeans  # noqa: F401
 from sisua_amd.mixture import GaussianMixture  # noqa: F401
 from sisua_amd.mutual_info import mutual_information  # noqa: F401

@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsisua_hip.so")
 
-SMX_ABI_VERSION = 20
+SMX_ABI_VERSION = 21
 SMX_MAX_LAYERS = 8
 SMX_MAX_LABELS = 4
 
@@ -69,6 +69,7 @@ _IP = C.POINTER(C.c_int32)
 _LP = C.POINTER(C.c_int64)
 _DP = C.POINTER(C.c_double)
 _VP = C.c_void_p
+_BP = C.POINTER(C.c_uint8)
 
 # name -> (restype, argtypes); every symbol include/sisua_hip.h declares
 SIGNATURES = {
@@ -226,6 +227,14 @@ SIGNATURES = {
     "smx_logreg_fit": (C.c_int, [_FP, _LP, _IP, _FP, C.c_int64, C.c_int32, _IP, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32,
                                  _DP, _DP, _DP, _DP, _DP, _DP, _IP, _IP, _IP]),
     "smx_logreg_decision": (C.c_int, [_FP, _LP, _IP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP, _DP, _DP]),
+    "smx_gbt_bin": (C.c_int, [_FP, _LP, _IP, _FP, C.c_int64, C.c_int32, _FP, _IP, _BP]),
+    "smx_gbt_grow": (C.c_int, [_BP, _IP, _FP, _LP, _LP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_double, C.c_int32,
+                               _IP, _FP, _IP, _IP, _DP, _IP, _DP, _IP]),
+    "smx_gbt_fit": (C.c_int, [_FP, _LP, _IP, _FP, C.c_int64, C.c_int32, _IP, C.c_int32, _FP, _LP, _IP, _FP, C.c_int64, _IP, C.c_int32, C.c_double,
+                              C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_int32, _DP, _IP, _FP, _IP, _IP, _DP, _IP, _DP, _IP, _DP,
+                              _DP]),
+    "smx_gbt_decision": (C.c_int, [_FP, _LP, _IP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _IP, _FP, _IP, _IP, _DP,
+                                   _DP, C.c_double, _DP]),
     "smx_pad_audit": (C.c_int, [_VP, C.c_int32, _LP, _IP, _LP, C.c_char_p, C.c_int32]),
     "smx_pad_poke": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_float]),
 }

@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsisua_hip.so")
-SOURCES = ["smx_gemm.hip", "smx_dgemm.hip", "smx_bn.hip", "smx_latent.hip", "smx_adam.hip", "smx_loss.hip", "smx_data.hip", "smx_headloss.hip", "smx_headbwd.hip", "smx_headfused.hip", "smx_bigk.hip", "smx_factor.hip", "smx_scvi.hip", "smx_score.hip", "smx_model.hip", "smx_dataset.hip", "smx_comm.hip", "smx_p2p.hip", "smx_forward.hip", "smx_backward.hip", "smx_step.hip", "smx_predict.hip", "smx_sample.hip", "smx_impute.hip", "smx_correlate.hip", "smx_cluster.hip", "smx_gmm.hip", "smx_gmm_full.hip", "smx_prep.hip", "smx_pca.hip", "smx_knn.hip", "smx_tsne.hip", "smx_umap.hip", "smx_mi.hip", "smx_rankgroups.hip", "smx_mbkmeans.hip", "smx_louvain.hip", "smx_logreg.hip", "smx_scoring.hip", "smx_schedule.hip", "smx_kapi.hip"]
+SOURCES = ["smx_gemm.hip", "smx_dgemm.hip", "smx_bn.hip", "smx_latent.hip", "smx_adam.hip", "smx_loss.hip", "smx_data.hip", "smx_headloss.hip", "smx_headbwd.hip", "smx_headfused.hip", "smx_bigk.hip", "smx_factor.hip", "smx_scvi.hip", "smx_score.hip", "smx_model.hip", "smx_dataset.hip", "smx_comm.hip", "smx_p2p.hip", "smx_forward.hip", "smx_backward.hip", "smx_step.hip", "smx_predict.hip", "smx_sample.hip", "smx_impute.hip", "smx_correlate.hip", "smx_cluster.hip", "smx_gmm.hip", "smx_gmm_full.hip", "smx_prep.hip", "smx_pca.hip", "smx_knn.hip", "smx_tsne.hip", "smx_umap.hip", "smx_mi.hip", "smx_rankgroups.hip", "smx_mbkmeans.hip", "smx_louvain.hip", "smx_logreg.hip", "smx_gbt.hip", "smx_scoring.hip", "smx_schedule.hip", "smx_kapi.hip"]
 HEADERS = ["smx_device.h", "smx_act.h", "smx_internal.h", "smx_loss.h", "smx_model.h", "smx_panel.h", "smx_dgemm.h", "smx_adam.h", "smx_headdw.h", "smx_handoff.h", "smx_dist.h", "smx_block.h", "smx_prep.h", os.path.join("..", "..", "include", "sisua_hip.h")]
 # -fno-slp-vectorize: the SLP vectoriser pairs scalar f32 operations into v_pk_*_f32, with an op_sel swizzle where the operands do not
 # line up -- and a packed-f32 op_sel that takes src1's HIGH dword for the LOW result reads it as 0 in lanes 48-63 while the SIMD's other

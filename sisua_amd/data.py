@@ -569,6 +569,35 @@ class SingleCellOMIC:
       self._uns[uns_key] = (om1, om2, mutual_information(self.numpy(om1), self.numpy(om2), n_neighbors=n_neighbors, random_state=random_state))
     return self._uns[uns_key][2]
 
+  def get_importance_matrix(self, omic="transcriptomic", target_omic="proteomic", random_state=1):
+    """The reference's get_importance_matrix (_single_cell_analysis.py:1107-1145): the importance [n_vars of omic, n_vars of target_omic]
+    float64 of every feature of one omic for every feature of another -- per target feature one gradient-boosted tree classifier on the
+    device (`sisua_amd.importance_matrix`, smx_gbt.hip), whose feature_importances_ are the column.  As in the reference: the two omics
+    must differ; a target that is not discrete (`mutual_info.is_discrete` of the whole matrix) is cut into 10 quantile bins per column
+    (`boosting.quantile_codes`: the ordinal KBinsDiscretizer(strategy='quantile')); the seed is 1 whatever `random_state`; the cells are
+    split 75 / 25 by RandomState(1).permutation and the fits take random_state=rand.randint(1e8).  A sparse omic stays CSR.  A target
+    feature with a single class among the training cells gives a zero column (with a RuntimeWarning).  The matrix is kept under
+    'importance_{omic}_{target_omic}' until one of the two omics is replaced."""
+    from sisua_amd.boosting import importance_matrix, quantile_codes
+    from sisua_amd.mutual_info import is_discrete
+    random_state = 1
+    om1, om2 = self._first(omic), self._first(target_omic)
+    assert om1 != om2, "Mutual information only for 2 different OMIC type"
+    uns_key = f"importance_{om1}_{om2}"
+    if uns_key not in self._uns:
+      X, y = self.numpy(om1), self.numpy(om2)
+      X = X.tocsr() if is_sparse(X) else X
+      y = np.asarray(y.toarray() if is_sparse(y) else y)
+      if not is_discrete(y):
+        y = np.stack([quantile_codes(y[:, j], 10) for j in range(y.shape[1])], axis=1)
+      rand = np.random.RandomState(random_state)
+      ids = rand.permutation(X.shape[0])
+      cut = int(0.75 * X.shape[0])
+      train, test = ids[:cut], ids[cut:]
+      matrix, _, _ = importance_matrix(X[train], y[train], X[test], y[test], random_state=rand.randint(1e8))
+      self._uns[uns_key] = (om1, om2, matrix)
+    return self._uns[uns_key][2]
+
   def rank_vars_groups(self, n_vars=100, group_by="proteomic", clustering="kmeans", method="logreg", corr_method="benjamini-hochberg",
                        max_iter=1000, reference="rest"):
     """The reference's rank_vars_groups (_single_cell_analysis.py:862-918, scanpy.tl.rank_genes_groups there): the variables of the FIRST

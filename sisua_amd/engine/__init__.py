@@ -14,6 +14,7 @@ as `engine.<name>`:
   _neighbors   PCA, kNN, UMAP graph and layout, t-SNE _mi          mutual information
   _groups      group moments and rank sums            _mbkmeans    mini-batch k-means
   _logreg      logistic regression                    _louvain     Louvain communities, modularity
+  _gbt         gradient-boosted trees
 
 A new feature's wrappers go into a new `_feature.py` beside these (the underscore keeps a module from shadowing an exported name).  Its
 names are then added to the imports below and to tests/golden/engine_api.json, which tests/test_engine_namespace_host.py holds this
@@ -23,6 +24,9 @@ from sisua_amd._hip import SmxError, check, smx_config, smx_metrics
 from sisua_amd.engine._args import (_csr3, _csr_ptrs, _dp, _f32, _fp, _fps, _ip, _label_ids, _matrix_ptrs, _ptr, _sparse)
 from sisua_amd.engine._cluster import k_cluster_kmeans, k_cluster_silhouette
 from sisua_amd.engine._correlate import _col_operands, _col_outputs, k_col_correlate, k_col_rank2
+from sisua_amd.engine._gbt import (GBT_MAX_BINS, GBT_MAX_CELLS, GBT_MAX_CLASSES, GBT_MAX_DEPTH, GBT_MAX_GENES, GBT_MAX_PASS, GBT_MAX_Q,
+                                   GBT_MAX_RESIDENT, _gbt_input, _gbt_tree_params, gbt_init_raw, k_gbt_bin, k_gbt_decision, k_gbt_fit,
+                                   k_gbt_grow)
 from sisua_amd.engine._gmm import (ILL_DEFINED_COVARIANCE, _gmm_matrix, gmm_n_train, k_gmm1d_fit, k_gmm1d_predict, k_gmm_full_fit,
                                    k_gmm_full_predict)
 from sisua_amd.engine._groups import (MOMENT_MAX_ACC, MOMENT_MAX_GROUPS, RANK_MAX_CELLS, RANK_MAX_GROUPS, _group_labels, k_group_moments,

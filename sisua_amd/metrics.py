@@ -159,9 +159,36 @@ def marker_correlations(matrix, kind: str, gene_names: Sequence[str], protein_na
 
 
 def marker_scores(matrix, kind: str, gene_names: Sequence[str], protein_names: Sequence[str], markers: Mapping[str, str]) -> Dict[str, float]:
-  """`Posterior._matrix_scores` (posterior.py:996-1024) of a 'pearson', 'spearman' or 'mi' matrix [genes, proteins]:
-  `marker_correlations` (which refuses 'mi') with the third kind: {f"{kind}_{gene}_{protein}": matrix[gene, protein]}."""
-  if kind != "mi":
+  """`Posterior._matrix_scores` (posterior.py:996-1024) of a 'pearson', 'spearman', 'mi' or 'importance' matrix [genes, proteins]:
+  `marker_correlations` (which refuses 'mi' and 'importance') with the third and fourth kinds: {f"{kind}_{gene}_{protein}": matrix[gene,
+  protein]}.  'lasso' is not built."""
+  if kind not in ("mi", "importance"):
     return marker_correlations(matrix, kind, gene_names, protein_names, markers)
   found = marker_correlations(matrix, "pearson", gene_names, protein_names, markers)   # (the same view; only the keys' prefix differs)
-  return {"mi" + key[len("pearson"):]: value for key, value in found.items()}
+  return {kind + key[len("pearson"):]: value for key, value in found.items()}
+
+
+def dci_scores(matrix, test_acc=None) -> Dict[str, float]:
+  """Disentanglement, completeness and informativeness (Eastwood & Williams 2018, as disentanglement_lib states them) of an importance
+  matrix [n_codes, n_factors] (`sisua_amd.importance_matrix`) -> dict(disentanglement, completeness, informativeness).
+  disentanglement: per code 1 - entropy(row + 1e-11, base=n_factors), weighted by the row's share of the matrix's total;
+  completeness: the mean over the factors of 1 - entropy(column + 1e-11, base=n_codes); informativeness: the mean of test_acc over the
+  factors that have one (NaN without test_acc, or where every accuracy is NaN).  Entropies are scipy.stats.entropy's.  Defined without a
+  NaN at the edges: with one factor (or one code) the logarithm's base is 1, and the score is 1 -- a single factor cannot be entangled
+  with another; an all-zero matrix gives every row the weight 0, so disentanglement 0, and uniform columns, so completeness 0."""
+  from scipy.stats import entropy
+  m = np.abs(np.asarray(matrix, np.float64))
+  if m.ndim != 2 or m.shape[0] < 1 or m.shape[1] < 1 or not np.isfinite(m).all():
+    raise ValueError(f"matrix must be a finite [n_codes >= 1, n_factors >= 1], got {m.shape}")
+  n_codes, n_factors = m.shape
+  per_code = 1.0 - entropy(m.T + 1e-11, base=n_factors) if n_factors > 1 else np.ones(n_codes)
+  total = m.sum()
+  weight = m.sum(axis=1) / total if total > 0 else np.zeros(n_codes)
+  per_factor = 1.0 - entropy(m + 1e-11, base=n_codes) if n_codes > 1 else np.ones(n_factors)
+  info = float("nan")
+  if test_acc is not None:
+    acc = np.asarray(test_acc, np.float64).reshape(-1)
+    if acc.shape != (n_factors,):
+      raise ValueError(f"test_acc must be [{n_factors}], got {acc.shape}")
+    info = float(np.nanmean(acc)) if np.isfinite(acc).any() else float("nan")
+  return dict(disentanglement=float(np.sum(per_code * weight)), completeness=float(np.mean(per_factor)), informativeness=info)

@@ -880,6 +880,39 @@ class SingleCellModel:
       return latent_scores(z, prepare_labels(lab), n_labels, prediction_algorithm, **kw)
     return clustering_scores(z, prepare_labels(lab), n_labels, **kw)
 
+  def dci_scores(self, inputs, factors, n_bins=5, library=None, batch_size=128, random_state=1, **gbt_kw):
+    r"""Disentanglement, completeness and informativeness of this model's latent space against `factors` (what `Posterior.cal_dci` reads
+    from its criticizer, analysis/posterior.py:304-375): the cells of `inputs` are encoded, the means of the latent posterior are the
+    codes, and per factor one gradient-boosted tree classifier on the device predicts the factor from the codes
+    (`sisua_amd.importance_matrix`, smx_gbt.hip) -> {'dci_disentanglement', 'dci_completeness', 'dci_informativeness'}
+    (`sisua_amd.dci_scores` of the importance matrix [latent_dim, n_factors] and the test accuracies).
+    factors [cells, n_factors] (or a SingleCellOMIC) are made discrete as `get_criticizer` does: one-hot rows (every row sums to 1)
+    collapse to ONE categorical factor, their argmax; anything else is cut into n_bins quantile bins per column
+    (`boosting.quantile_codes`; n_bins=None takes the values as the classes); a factor with a single class is dropped, and without any
+    factor left the call is a ValueError.  The cells are split 75 / 25 by RandomState(random_state).permutation; the fits take
+    random_state=rand.randint(1e8) and `gbt_kw` (`importance_matrix`'s keywords)."""
+    from sisua_amd.boosting import importance_matrix, quantile_codes
+    from sisua_amd.metrics import dci_scores
+    f = factors.numpy() if isinstance(factors, SingleCellOMIC) else factors
+    f = np.asarray(f.toarray() if is_sparse(f) else f)
+    f = f[:, None] if f.ndim == 1 else f
+    z = np.ascontiguousarray(self._latent_means(inputs, library, batch_size)[0], dtype=np.float32)
+    if f.ndim != 2 or f.shape[0] != z.shape[0]:
+      raise ValueError(f"factors must be [{z.shape[0]}, n_factors], got {f.shape}")
+    if f.shape[1] > 1 and np.all(np.sum(f, axis=1) == 1):
+      f = np.argmax(f, axis=1)[:, None]
+    elif n_bins is not None:
+      f = np.stack([quantile_codes(f[:, j], int(n_bins)) for j in range(f.shape[1])], axis=1)
+    f = f[:, [len(np.unique(c)) > 1 for c in f.T]]
+    if f.shape[1] == 0:
+      raise ValueError("no factor with more than one class")
+    rand = np.random.RandomState(random_state)
+    ids = rand.permutation(z.shape[0])
+    cut = int(0.75 * z.shape[0])
+    train, test = ids[:cut], ids[cut:]
+    matrix, _, test_acc = importance_matrix(z[train], f[train], z[test], f[test], random_state=rand.randint(1e8), **gbt_kw)
+    return {"dci_" + k: v for k, v in dci_scores(matrix, test_acc).items()}
+
   def _latent_means(self, inputs, library, batch_size):
     """What `encode(...)`'s distributions have as their mean, through the minibatch walk of `predict` and nothing else off the device:
     [z [cells, D]] and, for scvi, the library latent [cells, 1] after it."""
