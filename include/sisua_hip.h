@@ -14,6 +14,20 @@
  * library owns every device buffer.  One host thread (process) per GPU; all
  * kernels of a model run on one HIP stream owned by the model.  Host arrays
  * are dense row-major with LOGICAL shapes (the padded HBM layout is private).
+ *
+ * THE ROWS CONVENTION.  An entry that takes a host matrix of n rows x n_genes
+ * columns "dense or CSR" takes it as the four arguments (x, indptr, cols, vals),
+ * in this order, EXACTLY ONE of x / indptr non-NULL (SMX_ERR_INVALID before any
+ * device work otherwise):
+ *   dense  x float32 [n][n_genes], row-major; indptr = cols = vals = NULL;
+ *   CSR    x = NULL; indptr int64 [n + 1] (absolute offsets: row i is entries
+ *          indptr[i] .. indptr[i + 1] - 1 of cols / vals, never decreasing, at
+ *          most n_genes entries per row), cols int32 (sorted within a row, each
+ *          < n_genes), vals float32.
+ * Both forms of the same counts give the same result bits.  In the model entries
+ * the dense pointer is called host_x; a second matrix of a call (a target, the
+ * original counts, a validation set) is the same four arguments under a prefix
+ * (t_, o_, v_).
  */
 #ifndef SISUA_HIP_H_
 #define SISUA_HIP_H_
@@ -24,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 21
+#define SMX_ABI_VERSION 22
 #define SMX_MAX_LAYERS 8
 #define SMX_MAX_LABELS 4
 
@@ -362,16 +376,18 @@ int smx_forward_samples(smx_model* m, const int32_t* row_ids, const float* host_
 
 /* SingleCellModel.predict(inputs, sample_shape, batch_size) over a whole host matrix in ONE call
  * (sisua/models/single_cell_model.py:153-211: "predict on minibatches then return a single distribution by
- * concatenation").  host_x [n_cells, n_genes] (host_library [n_cells, 2] for scvi) is walked in minibatches of `batch`
+ * concatenation").  The n_cells host rows (host_library [n_cells, 2] for scvi) are walked in minibatches of `batch`
  * (<= max_batch; the last one may be smaller) and every result is written straight to its final place:
  * z_mean / z_scale [n_cells, D]; l_mean / l_scale [n_cells]; z_samples [n_samples, n_cells, D]; l_samples
  * [n_samples, n_cells]; x_params [n_samples, k, n_cells, n_genes]; y_params[j] [n_samples, n_cells, ky * P_j].  Same draws
  * as smx_forward_samples batch by batch (draw s uses Philox sample index s; the noise of a cell is keyed by its index
  * within its minibatch, as there); the same numbers bit for bit at one draw, to rounding with several (their decodes
- * then run as rows of one pass, flag "stacked_scoring").  Any output may be NULL. */
-int smx_predict(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch,
-                int32_t n_samples, float* z_mean, float* z_scale, float* z_samples, float* l_mean, float* l_scale,
-                float* l_samples, float* x_params, float* const* y_params);
+ * then run as rows of one pass, flag "stacked_scoring").  Any output may be NULL.  The rows (host_x, indptr, cols,
+ * vals): the rows convention above -- CSR rows are expanded on the device into the tile a dense chunk is re-pitched
+ * into, their likelihood constants from the same launch, and chunks are cut by non-zeros as well as by cells. */
+int smx_predict(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                int64_t n_cells, int32_t batch, int32_t n_samples, float* z_mean, float* z_scale, float* z_samples, float* l_mean,
+                float* l_scale, float* l_samples, float* x_params, float* const* y_params);
 
 /* The same walk over a host matrix, but what leaves the device is a STATISTIC of the gene output instead of its parameter planes -- what
  * the reference's callers ask of predict()'s result: `y.mean()`, `.variance()`, `.log_prob(x)` of the output distribution or of its
@@ -379,23 +395,13 @@ int smx_predict(smx_model* m, const float* host_x, const float* host_library, in
  * are 4 k G bytes per cell and draw (24 KB at 1998 genes, zinb) and a fresh result array of that size is first-touched by the copy;
  * a mean is a third of it, the mean over the draws 1 / (3 n_samples), a log_prob 4 bytes.  Same passes, same draws as smx_predict.
  *   stat 0 mean, 1 variance: out [n_samples, n_cells, n_genes];  2 mean averaged over the draws: out [n_cells, n_genes];
- *   stat 3 log_prob (summed over the genes: Independent(..., 1)): out [n_samples, n_cells], of `target` [n_cells, n_genes] or, target = NULL,
- *          of host_x itself;  count_only != 0: the count distribution (NB / NBD) of a zero-inflated output. */
-int smx_predict_stat(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
-                     int32_t stat, int32_t count_only, const float* target, float* out);
-
-/* Host rows given as CSR instead of a dense host_x: indptr int64 [n_cells + 1] (absolute offsets: row i is entries
- * indptr[i] .. indptr[i + 1] - 1 of cols / vals), cols int32 (sorted within a row, each < n_genes), vals float32.  Rows hold at most
- * n_genes entries.  Every other argument, and every result bit, is that of the dense entry point on the same counts: a chunk's rows are
- * expanded on the device into the tile a dense chunk is re-pitched into, their likelihood constants from the same launch.  Chunks are
- * cut by non-zeros as well as by cells.  smx_predict_stat_csr: the log_prob target (stat 3) is dense (`target`), CSR (t_indptr /
- * t_cols / t_vals, n_cells rows, same layout) or neither (the input rows themselves). */
-int smx_predict_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
-                    int64_t n_cells, int32_t batch, int32_t n_samples, float* z_mean, float* z_scale, float* z_samples,
-                    float* l_mean, float* l_scale, float* l_samples, float* x_params, float* const* y_params);
-int smx_predict_stat_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
-                         int64_t n_cells, int32_t batch, int32_t n_samples, int32_t stat, int32_t count_only, const float* target,
-                         const int64_t* t_indptr, const int32_t* t_cols, const float* t_vals, float* out);
+ *   stat 3 log_prob (summed over the genes: Independent(..., 1)): out [n_samples, n_cells], of the target rows or, without a target,
+ *          of the input rows themselves;  count_only != 0: the count distribution (NB / NBD) of a zero-inflated output.
+ * The rows, and the log_prob target (target, t_indptr, t_cols, t_vals; n_cells rows; at most one of target / t_indptr): the rows
+ * convention. */
+int smx_predict_stat(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                     int64_t n_cells, int32_t batch, int32_t n_samples, int32_t stat, int32_t count_only, const float* target,
+                     const int64_t* t_indptr, const int32_t* t_cols, const float* t_vals, float* out);
 
 /* POSTERIOR-PREDICTIVE SAMPLES of the gene output, drawn on the device from the parameter planes of the same walk (its stat 4; the passes
  * of a chunk run once): out [n_k, n_samples, n_cells, n_genes] float32, n_k independent draws x ~ p(x | planes) per Monte-Carlo draw, cell
@@ -407,19 +413,16 @@ int smx_predict_stat_csr(smx_model* m, const int64_t* indptr, const int32_t* col
  * the counter (gene, row, k, 96 | attempt << 8 | s << 16) -- so the batch size, the chunking and dense / CSR input change no bit.  Every
  * rejection loop is bounded (16 Gamma attempts, 24 Poisson attempts, then the proposal's mean / the rounded rate).  Count outputs are
  * non-negative integers in float32; a NaN parameter, or a Gamma-Poisson rate that is not finite, gives NaN.  n_cells < 2^32,
- * n_samples <= 65536.  smx_predict_sample_csr: the rows as CSR (layout of smx_predict_csr), same bits. */
-int smx_predict_sample(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
-                       int32_t count_only, uint64_t seed, int32_t n_k, float* out);
-int smx_predict_sample_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
-                           int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, uint64_t seed, int32_t n_k, float* out);
+ * n_samples <= 65536.  The rows: the rows convention. */
+int smx_predict_sample(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                       int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, uint64_t seed, int32_t n_k, float* out);
 
 /* Stat 2 (the mean averaged over the draws) for n_sel gene columns only: out [n_cells, n_sel], column j = gene genes[j] (any order,
- * repeats allowed, each in 0 .. n_genes - 1) -- the same bits as those columns of smx_predict_stat's [n_cells, n_genes]. */
-int smx_predict_stat_cols(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
-                          int32_t count_only, const int32_t* genes, int32_t n_sel, float* out);
-int smx_predict_stat_cols_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
-                              int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, const int32_t* genes, int32_t n_sel,
-                              float* out);
+ * repeats allowed, each in 0 .. n_genes - 1) -- the same bits as those columns of smx_predict_stat's [n_cells, n_genes].  The rows: the rows
+ * convention. */
+int smx_predict_stat_cols(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals,
+                          const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, const int32_t* genes,
+                          int32_t n_sel, float* out);
 
 /* IMPUTATION SCORES (sisua/analysis/imputation_benchmarks.py:102-127) of the matrix smx_predict_stat's stat 2 returns for host_x, the
  * CORRUPTED counts -- same passes, same draws -- against `original` [n_cells, n_genes], reduced on the device: with
@@ -432,14 +435,10 @@ int smx_predict_stat_cols_csr(smx_model* m, const int64_t* indptr, const int32_t
  * Every selection is exact (integer histograms of the float32 patterns; no float atomics): the results do not depend on the batch size,
  * the chunking or the input form.  The global selection's later levels read d kept on the device when n_cells x n_genes x 4 bytes fit
  * the knob "impute_keep_bytes" (default: half of the free device memory) and otherwise repeat the walk twice; same answer.
- * smx_predict_impute_csr: the input rows dense (host_x) or CSR (indptr / cols / vals), the original rows dense (`original`) or CSR
- * (o_indptr / o_cols / o_vals) -- exactly one of each pair, layout of smx_predict_csr. */
-int smx_predict_impute(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
-                       int32_t count_only, const float* original, float* cell_median, int32_t* cell_changed, float* global_lohi);
-int smx_predict_impute_csr(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals,
-                           const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only,
-                           const float* original, const int64_t* o_indptr, const int32_t* o_cols, const float* o_vals, float* cell_median,
-                           int32_t* cell_changed, float* global_lohi);
+ * The input rows, and the original rows (original, o_indptr, o_cols, o_vals; n_cells rows): the rows convention, exactly one form each. */
+int smx_predict_impute(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                       int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, const float* original, const int64_t* o_indptr,
+                       const int32_t* o_cols, const float* o_vals, float* cell_median, int32_t* cell_changed, float* global_lohi);
 
 /* GENE x PROTEIN CORRELATION SUMS (SingleCellOMIC.get_correlation, sisua/data/_single_cell_analysis.py:1199-1245: pearsonr and spearmanr of
  * every pair) of the matrix smx_predict_stat's stat 2 returns -- same passes, same draws -- against P protein columns the caller has
@@ -453,14 +452,11 @@ int smx_predict_impute_csr(smx_model* m, const float* host_x, const int64_t* ind
  * Spearman = (N Sab - Sa Sb) / sqrt((N Saa - Sa^2)(N Sbb - Sb^2)), Pearson = Sxy / sqrt(Sxx).  Nothing depends on the batch size, the
  * chunking or the input form.  n_cells <= 2^20 (4 n_cells^3 < 2^63), else SMX_ERR_INVALID before any device work.  The kept columns, their
  * ranks and the sort arrays take 16 n_cells bytes per gene: as many genes at a time as fit the knob "correlate_keep_bytes" (default: half
- * of the free device memory), the walk being repeated once per such chunk -- same bits.  smx_predict_correlate_csr: the rows as CSR. */
-int smx_predict_correlate(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
-                          int32_t count_only, const int32_t* genes, int32_t n_sel, const int32_t* prot_rank2, const double* prot_unit, int32_t P,
-                          int64_t* sp_Sa, int64_t* sp_Saa, int64_t* sp_Sab, double* pe_mean, double* pe_Sxx, double* pe_Sxy, int32_t* nonfinite);
-int smx_predict_correlate_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
-                              int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, const int32_t* genes, int32_t n_sel,
-                              const int32_t* prot_rank2, const double* prot_unit, int32_t P, int64_t* sp_Sa, int64_t* sp_Saa, int64_t* sp_Sab,
-                              double* pe_mean, double* pe_Sxx, double* pe_Sxy, int32_t* nonfinite);
+ * of the free device memory), the walk being repeated once per such chunk -- same bits.  The rows: the rows convention. */
+int smx_predict_correlate(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals,
+                          const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, const int32_t* genes,
+                          int32_t n_sel, const int32_t* prot_rank2, const double* prot_unit, int32_t P, int64_t* sp_Sa, int64_t* sp_Saa,
+                          int64_t* sp_Sab, double* pe_mean, double* pe_Sxx, double* pe_Sxy, int32_t* nonfinite);
 
 /* Decoder only (SingleCellModel.decode, single_cell_model.py:141-151; scvi.py:108-171):
  * z [batch,D] (and l [batch] for scvi) -> the same x_params / y_params as smx_forward,
@@ -472,12 +468,10 @@ int smx_decode(smx_model* m, const float* z, const float* l, int32_t batch, floa
  * then the n_samples draws (z of draw s from Philox sample index s) go through decoder, output head and forward-only
  * likelihood as rows of one pass (up to 16 384 rows at a time; flag "stacked_scoring" = 0: draw by draw) with
  * a running log-sum-exp per cell on the device.  mllk[batch] = log mean_s p(x|z_s) p(z_s) / q(z_s|x);
- * llk_mean[batch] = mean_s log p(x|z_s) (may be NULL).  Cells: row_ids or host_x (+ host_library for scvi). */
-int smx_marginal_llk(smx_model* m, const int32_t* row_ids, const float* host_x, const float* host_library, int32_t batch,
-                     int32_t n_samples, float* mllk, float* llk_mean);
-/* The same for `batch` host rows given as CSR (layout as smx_predict_csr); the same bits as smx_marginal_llk on the dense rows. */
-int smx_marginal_llk_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
-                         int32_t batch, int32_t n_samples, float* mllk, float* llk_mean);
+ * llk_mean[batch] = mean_s log p(x|z_s) (may be NULL).  Cells: row_ids into the resident matrix, or (row_ids = NULL) `batch` host rows in
+ * the rows convention (+ host_library for scvi) -- never both. */
+int smx_marginal_llk(smx_model* m, const int32_t* row_ids, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals,
+                     const float* host_library, int32_t batch, int32_t n_samples, float* mllk, float* llk_mean);
 
 /* Posterior-predictive scoring, Posterior.cal_llk (sisua/analysis/posterior.py:919-938): the cells given by
  * row_ids / host_x are encoded once, then n_samples posterior draws are decoded and the output distribution is
@@ -853,13 +847,12 @@ int smx_gmm_full_predict(const float* Z, int64_t n_cells, int32_t D, int32_t K, 
                          int32_t* labels, double* resp, double* score);
 
 /* ---- count-matrix preprocessing (smx_prep.hip; model-free: smx_init only) ----------- */
-/* Both entries take a host matrix of n_cells x n_genes either dense (x [n_cells][n_genes] float32; indptr = cols = vals = NULL) or as CSR
- * (x = NULL; indptr / cols / vals in the layout of smx_predict_csr, every column in 0 .. n_genes - 1) and stream it through the device in
- * blocks of block_rows rows (0: the library's choice, about 64 MiB of tile; a given value is rounded up to a multiple of 64 and capped at
- * 1 GiB of tile; CSR blocks cross as CSR and are expanded on the device).  They work on a VIEW of the matrix: the value of entry (r, g) is
- * f(x[r][g] / row_div[r]) in float32 with the IEEE division -- row_div [n_cells] float32 (NULL: no division), func 0 the identity,
- * 1 log1pf, 2 expm1f.  n_cells < 2^31, n_genes <= 2^20, a row divisor finite and not 0: anything else is SMX_ERR_INVALID before any
- * device work.
+/* Both entries take a host matrix of n_cells x n_genes in the rows convention (x, indptr, cols, vals; the top of this header; every CSR
+ * column in 0 .. n_genes - 1) and stream it through the device in blocks of block_rows rows (0: the library's choice, about 64 MiB of
+ * tile; a given value is rounded up to a multiple of 64 and capped at 1 GiB of tile; CSR blocks cross as CSR and are expanded on the
+ * device).  They work on a VIEW of the matrix: the value of entry (r, g) is f(x[r][g] / row_div[r]) in float32 with the IEEE division --
+ * row_div [n_cells] float32 (NULL: no division), func 0 the identity, 1 log1pf, 2 expm1f.  n_cells < 2^31, n_genes <= 2^20, a row
+ * divisor finite and not 0: anything else is SMX_ERR_INVALID before any device work.
  *
  * smx_prep_stats: the statistics of the view.  cell_total [n_cells]: the float64 sum of the cell's values over the genes (with col_mask
  * [n_genes] uint8, may be NULL: over the genes whose mask is not 0); cell_n_genes [n_cells]: its values > 0.  gene_sum, gene_sumsq

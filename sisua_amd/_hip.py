@@ -13,7 +13,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsisua_hip.so")
 
-SMX_ABI_VERSION = 21
+SMX_ABI_VERSION = 22
 SMX_MAX_LAYERS = 8
 SMX_MAX_LABELS = 4
 
@@ -70,6 +70,7 @@ _LP = C.POINTER(C.c_int64)
 _DP = C.POINTER(C.c_double)
 _VP = C.c_void_p
 _BP = C.POINTER(C.c_uint8)
+_ROWS = (_FP, _LP, _IP, _FP)   # a host matrix, dense or CSR: (x, indptr, cols, vals), the rows convention of include/sisua_hip.h
 
 # name -> (restype, argtypes); every symbol include/sisua_hip.h declares
 SIGNATURES = {
@@ -115,30 +116,18 @@ SIGNATURES = {
     "smx_forward_samples": (C.c_int, [_VP, _IP, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
                                       C.POINTER(_FP)]),
     "smx_shuffle_order": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
-    "smx_predict": (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
-                              C.POINTER(_FP)]),
-    "smx_predict_stat": (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP, _FP]),
-    "smx_predict_csr": (C.c_int, [_VP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP,
-                                  C.POINTER(_FP)]),
-    "smx_predict_stat_csr": (C.c_int, [_VP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP,
-                                       _LP, _IP, _FP, _FP]),
-    "smx_predict_sample": (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _FP]),
-    "smx_predict_sample_csr": (C.c_int, [_VP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _FP]),
-    "smx_predict_stat_cols": (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _IP, C.c_int32, _FP]),
-    "smx_predict_stat_cols_csr": (C.c_int, [_VP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _IP, C.c_int32, _FP]),
-    "smx_predict_impute": (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, _IP, _FP]),
-    "smx_predict_impute_csr": (C.c_int, [_VP, _FP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _LP, _IP, _FP,
-                                         _FP, _IP, _FP]),
-    "smx_predict_correlate": (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _IP, C.c_int32, _IP, _DP, C.c_int32,
+    "smx_predict": (C.c_int, [_VP, *_ROWS, _FP, C.c_int64, C.c_int32, C.c_int32, _FP, _FP, _FP, _FP, _FP, _FP, _FP, C.POINTER(_FP)]),
+    "smx_predict_stat": (C.c_int, [_VP, *_ROWS, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, *_ROWS, _FP]),
+    "smx_predict_sample": (C.c_int, [_VP, *_ROWS, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, _FP]),
+    "smx_predict_stat_cols": (C.c_int, [_VP, *_ROWS, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _IP, C.c_int32, _FP]),
+    "smx_predict_impute": (C.c_int, [_VP, *_ROWS, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, *_ROWS, _FP, _IP, _FP]),
+    "smx_predict_correlate": (C.c_int, [_VP, *_ROWS, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _IP, C.c_int32, _IP, _DP, C.c_int32,
                                         _LP, _LP, _LP, _DP, _DP, _DP, _IP]),
-    "smx_predict_correlate_csr": (C.c_int, [_VP, _LP, _IP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _IP, C.c_int32, _IP, _DP,
-                                            C.c_int32, _LP, _LP, _LP, _DP, _DP, _DP, _IP]),
     "smx_decode": (C.c_int, [_VP, _FP, _FP, C.c_int32, _FP, C.POINTER(_FP)]),
     "smx_dataset_library": (C.c_int, [_VP, _FP]),
     "smx_dataset_corrupt": (C.c_int, [_VP, C.c_double, C.c_double, C.c_uint64, C.POINTER(C.c_int64)]),
     "smx_dataset_read": (C.c_int, [_VP, C.c_int64, C.c_int64, _FP, _FP, _FP]),
-    "smx_marginal_llk": (C.c_int, [_VP, _IP, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP]),
-    "smx_marginal_llk_csr": (C.c_int, [_VP, _LP, _IP, _FP, _FP, C.c_int32, C.c_int32, _FP, _FP]),
+    "smx_marginal_llk": (C.c_int, [_VP, _IP, *_ROWS, _FP, C.c_int32, C.c_int32, _FP, _FP]),
     "smx_score_llk": (C.c_int, [_VP, _IP, _FP, _FP, C.POINTER(_FP), C.c_int32, C.c_int32, C.c_int32, _FP]),
     "smx_set_noise": (C.c_int, [_VP, C.c_int32, _FP, C.c_int32, C.c_int32]),
     "smx_clear_noise": (C.c_int, [_VP]),

@@ -83,7 +83,7 @@ int launch_csr_expand(hipStream_t st, const int64_t* indptr, const int32_t* cols
   return SMX_OK;
 }
 
-// Host rows handed in as CSR (smx_predict_csr and kin): rows [0, n) of a chunk -> the dense [n][ld] float32 tile every
+// Host rows handed in as CSR (the rows convention of sisua_hip.h): rows [0, n) of a chunk -> the dense [n][ld] float32 tile every
 // consumer of a host batch reads, and the rows' lgx1 in the same launch -- what the dense path gets from a re-pitch, a
 // memset and launch_row_stats.  indptr holds the chunk's n + 1 ABSOLUTE offsets; cols / vals start at entry indptr[0].
 // One workgroup per row.  The row is built in LDS one segment of CSR_SEG columns at a time (zero, scatter the segment's

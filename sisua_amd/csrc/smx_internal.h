@@ -780,7 +780,7 @@ int launch_csr_row_stats(hipStream_t st, const int64_t* indptr, const float* val
 int launch_csr_expand(hipStream_t st, const int64_t* indptr, const int32_t* cols, const float* vals, const int32_t* rows, long row0,
                       int B, long ld, float* out);
 // host rows given as CSR: a chunk's rows -> dense [n][ld] tile (float32, or uint16 with u16) + their lgx1 (may be NULL), one launch
-// (smx_predict_csr and kin; a dense store uploaded from CSR)
+// (host rows in the rows convention of sisua_hip.h; a dense store uploaded from CSR)
 int launch_csr_rows(hipStream_t st, const int64_t* indptr, const int32_t* cols, const float* vals, long n, int G, long ld, void* out,
                     float* lgx1, int u16 = 0);
 int launch_library_stats(hipStream_t st, const double* logcount, long N, double* stats, float* library);

@@ -248,7 +248,7 @@ struct smx_model {
   // pinned staging for the row ids (and, behind them, the schedule table) of a train_steps call: hipMemcpyAsync from the caller's pageable array cost ~80 us per call
   int32_t* order_pin = nullptr; size_t order_pin_cap = 0; hipEvent_t ev_order = nullptr; bool order_pin_busy = false;
   int32_t* pred_ids = nullptr; int pred_ids_batch = 0;   // smx_predict super-batches: noise ids (row % batch)
-  char* csr_host = nullptr; size_t csr_host_bytes = 0;   // a batch of host rows given as CSR, staged (smx_marginal_llk_csr, CSR log_prob targets)
+  char* csr_host = nullptr; size_t csr_host_bytes = 0;   // a batch of host rows given as CSR, staged (setup_pass, CSR log_prob targets)
   float* pred_target = nullptr; size_t pred_target_floats = 0;   // smx_predict_stat(log_prob): a batch of target rows [Bmax][Gp]
   float* imp_d = nullptr; size_t imp_d_floats = 0;   // smx_predict_impute: |original - mean| of every cell [N][G] (kept form) or of one pass's rows
   unsigned long long* imp_hist = nullptr;            // ... its histograms: level 1 [2048] | levels 2 and 3 [2][1024] | NaN flag (smx_impute.hip)
@@ -583,8 +583,12 @@ int seam_error_check(smx_model* m);   // the seam form's error word (smx_step.hi
 struct CsrRows { const int64_t* indptr; const int32_t* cols; const float* vals; };
 int check_csr_rows(const CsrRows& c, size_t n, int G);
 int csr_host_rows(smx_model* m, const CsrRows& c, size_t r0, size_t n, void* out, float* lgx1, int u16 = 0);
-// the cells of a pass: resident rows by id, or host rows x [batch][G] with their library prior [batch][2] (scvi)
-struct CellSrc { const int32_t* row_ids; const float* host_x; const float* host_library; };
+// a host matrix as the C entries take it (the rows convention of sisua_hip.h): dense x [n][G], or CSR (x NULL, csr.indptr set)
+struct HostRows { const float* x; CsrRows csr; };
+// the four raw pointers of an entry -> *out, refusing "both" and "neither" (and n < 1, and CSR rows check_csr_rows refuses)
+int host_rows(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n, int G, HostRows* out);
+// the cells of a pass: resident rows by id, or host rows (`batch` of them, either form) with their library prior [batch][2] (scvi)
+struct CellSrc { const int32_t* row_ids; HostRows rows; const float* host_library; };
 int setup_pass(smx_model* m, Pass& ps, const CellSrc& src, int32_t batch, int training, int sample, int draw_rows = 0);   // draw_rows > 0: row_ids are stacked draws (up to Rmax rows)
 // smx_predict.hip
 bool stacked_scoring_ok(const smx_model* m);

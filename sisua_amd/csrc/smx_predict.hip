@@ -233,17 +233,23 @@ static int launch_plane_stat(hipStream_t st, const StatArgs& a) {
 // what smx_predict_stat asks of the batch loop below in place of the parameter planes
 // (stat 4: n_k predictive samples per draw under `seed`, smx_sample.hip)
 struct StatReq {
-  int stat = 0, count_only = 0; const float* target = nullptr; const CsrRows* tcsr = nullptr; float* out = nullptr;
+  int stat = 0, count_only = 0; HostRows target{}; float* out = nullptr;   // target: neither form = the input rows themselves
   uint64_t seed = 0; int n_k = 1;
   // stat 2 only.  sel: n_sel gene indices (device) -- out is [n_cells][n_sel].  impute: nothing of the mean leaves the device; the scores
-  // of |target - mean| do (smx_impute.hip), `target` / `tcsr` being the original rows
+  // of |target - mean| do (smx_impute.hip), `target` being the original rows
   const int32_t* sel = nullptr; int n_sel = 0;
   int impute = 0; float* imp_median = nullptr; int32_t* imp_changed = nullptr; float* imp_lohi = nullptr;
   // keep_cols (with sel): nothing leaves the device; the selected columns are kept gene-major [n_sel][n_cells] there (smx_correlate.hip)
   float* keep_cols = nullptr;
 };
+// what a call wants of predict_core's walk: the statistic `sr` (NULL: none) and / or smx_predict's arrays (NULL: not asked for)
+struct PredWant {
+  const StatReq* sr = nullptr;
+  float *z_mean = nullptr, *z_scale = nullptr, *z_samples = nullptr, *l_mean = nullptr, *l_scale = nullptr, *l_samples = nullptr, *x_params = nullptr;
+  float* const* y_params = nullptr;
+};
 
-// ---- host rows given as CSR (smx_predict_csr and kin): (indptr int64 [n + 1], cols int32, vals float32), indptr absolute ----
+// ---- host rows given as CSR (the rows convention of sisua_hip.h): (indptr int64 [n + 1], cols int32, vals float32), indptr absolute ----
 // what the C entry points check before any device work: offsets that never go back, at most G entries per row (so a batch of rows
 // holds at most batch x G of them: the bound every staging buffer is sized by)
 int check_csr_rows(const CsrRows& c, size_t n, int G) {
@@ -254,6 +260,13 @@ int check_csr_rows(const CsrRows& c, size_t n, int G) {
                 "CSR indptr must be non-decreasing with at most n_genes entries per row");
   SMX_REQUIRE((c.cols && c.vals) || c.indptr[n] == c.indptr[0], "CSR rows need cols and vals");
   return SMX_OK;
+}
+// ... and of a matrix given in either form: every entry that takes (x, indptr, cols, vals) calls this once per matrix
+int host_rows(const float* x, const int64_t* indptr, const int32_t* cols, const float* vals, int64_t n, int G, HostRows* out) {
+  SMX_REQUIRE((x != nullptr) != (indptr != nullptr), "host rows: exactly one of the dense matrix and the CSR arrays");
+  SMX_REQUIRE(n >= 1, "host rows: at least one row");
+  *out = HostRows{x, CsrRows{indptr, cols, vals}};
+  return x ? SMX_OK : check_csr_rows(out->csr, (size_t)n, G);
 }
 
 // bytes of a block of n CSR rows with nnz entries as staged on the device: indptr | cols | vals, each 16-byte aligned
@@ -277,7 +290,7 @@ static int stage_csr_rows(smx_model* m, const CsrRows& c, size_t r0, size_t n, c
   }
   return launch_csr_rows(m->st, d_ptr, d_cols, d_vals, (long)n, m->G, (long)m->Gp, out, lgx1, u16);
 }
-// the same through the model's growable buffer m->csr_host (one batch of rows: smx_marginal_llk_csr, a batch of CSR targets; a block of
+// the same through the model's growable buffer m->csr_host (one batch of rows: setup_pass, a batch of CSR targets; a block of
 // a dense store uploaded from CSR, u16: the uint16 store)
 int csr_host_rows(smx_model* m, const CsrRows& c, size_t r0, size_t n, void* out, float* lgx1, int u16) {
   SMX_CHECK(dgrow(m, &m->csr_host, &m->csr_host_bytes, csr_stage_bytes(n, (size_t)(c.indptr[r0 + n] - c.indptr[r0]))));
@@ -351,10 +364,9 @@ struct PredChunk {
 // the caller's pageable array is staged synchronously by the runtime -- ~60 us per batch, at batch 8 (Posterior's default) most of the call.
 // Dense rows: raw [Cn][G] -> a device re-pitch to [Cn][Gp] and the rows' likelihood constants from row_stats.  CSR rows: whole batches while
 // their non-zeros fit nnz_cap (the first batch always does; Cn shrinks to them), the tile and the constants from one launch.
-static int load_chunk(smx_model* m, PredChunk& c, const float* host_x, const CsrRows* cx, const float* host_library, size_t c0, size_t batch,
-                      size_t nnz_cap) {
+static int load_chunk(smx_model* m, PredChunk& c, const HostRows& rows, const float* host_library, size_t c0, size_t batch, size_t nnz_cap) {
   const size_t G = (size_t)m->G, Gp = (size_t)m->Gp;
-  if (cx) {
+  if (const CsrRows* cx = rows.x ? nullptr : &rows.csr) {
     size_t end = c0;
     while (end < c0 + c.Cn) {
       const size_t nxt = std::min(end + batch, c0 + c.Cn);
@@ -365,7 +377,7 @@ static int load_chunk(smx_model* m, PredChunk& c, const float* host_x, const Csr
     SMX_REQUIRE((size_t)(cx->indptr[c0 + c.Cn] - cx->indptr[c0]) <= nnz_cap, "CSR chunk exceeds its staging");
     SMX_CHECK(stage_csr_rows(m, *cx, c0, c.Cn, c.csr, c.in_x, c.in_lgx1));
   } else {
-    SMX_HIP(hipMemcpyAsync(c.in_raw, host_x + c0 * G, c.Cn * G * sizeof(float), hipMemcpyHostToDevice, m->st));
+    SMX_HIP(hipMemcpyAsync(c.in_raw, rows.x + c0 * G, c.Cn * G * sizeof(float), hipMemcpyHostToDevice, m->st));
     if (Gp != G) SMX_HIP(hipMemsetAsync(c.in_x, 0, c.Cn * Gp * sizeof(float), m->st));
     PackList pl(m->st, (unsigned)std::min<size_t>(1024, (c.Cn * G + 255) / 256), 1, (int)c.Cn);
     SMX_CHECK(pl.add(c.in_x, Gp, c.in_raw, G, G));
@@ -395,7 +407,7 @@ static int stat_of(smx_model* m, const PredChunk& c, const Pass& ps, const float
   if (sr.stat == 2) { a.dst = c.st + b0 * G; a.dst_draw = 0; }
   else if (sr.stat == 3) {
     a.dst = c.st + s0 * Cn + b0; a.dst_draw = (long)Cn;
-    if (sr.target || sr.tcsr) { a.T = m->pred_target; a.ldt = m->Gp; }
+    if (sr.target.x || sr.target.csr.indptr) { a.T = m->pred_target; a.ldt = m->Gp; }
     else { a.T = ps.Xsrc; a.ldt = m->Gp; a.trows = ps.xrows; a.t_u16 = ps.x_u16; }   // the input rows themselves
   } else { a.dst = c.st + (s0 * Cn + b0) * G; a.dst_draw = (long)(Cn * G); }
   return launch_plane_stat(m->st, a);
@@ -508,7 +520,7 @@ int smx_forward(smx_model* m, const int32_t* row_ids, const float* host_x, const
                 float* l_scale, float* l_sample, float* x_params, float* const* y_params) {
   SMX_REQUIRE(m, "null model");
   Pass ps;
-  SMX_CHECK(setup_pass(m, ps, {row_ids, host_x, host_library}, batch, training, sample_index));
+  SMX_CHECK(setup_pass(m, ps, {row_ids, {host_x}, host_library}, batch, training, sample_index));
   SMX_REQUIRE(!(training && !row_ids), "training-mode forward needs resident rows");
   SMX_CHECK(forward_pass(m, ps, Loss::None));
   return fetch_forward(m, batch, z_mean, z_scale, z_sample, l_mean, l_scale, l_sample, x_params, y_params, 0);
@@ -521,9 +533,9 @@ int smx_forward_samples(smx_model* m, const int32_t* row_ids, const float* host_
   // several draws of a host batch: smx_predict over this one batch (same cell ids, same draws, same output layouts) decodes
   // them as rows of one pass instead of one decoder pass per draw
   if (!row_ids && host_x && n_samples > 1 && batch > 0 && batch <= m->Bmax && stacked_scoring_ok(m) && !m->scvi)
-    return smx_predict(m, host_x, host_library, batch, batch, n_samples, z_mean, z_scale, z_samples, l_mean, l_scale, l_samples, x_params, y_params);
+    return smx_predict(m, host_x, nullptr, nullptr, nullptr, host_library, batch, batch, n_samples, z_mean, z_scale, z_samples, l_mean, l_scale, l_samples, x_params, y_params);
   Pass ps;
-  SMX_CHECK(setup_pass(m, ps, {row_ids, host_x, host_library}, batch, 0, 0));
+  SMX_CHECK(setup_pass(m, ps, {row_ids, {host_x}, host_library}, batch, 0, 0));
   const size_t B = (size_t)batch;
   for (int s = 0; s < n_samples; ++s) {
     ps.sample = s;
@@ -537,22 +549,20 @@ int smx_forward_samples(smx_model* m, const int32_t* row_ids, const float* host_
   return SMX_OK;
 }
 
-// host_x: dense rows [n_cells][G]; or cx: the same rows as CSR (exactly one of the two)
-static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, const float* host_library, int64_t n_cells, int32_t batch,
-                        int32_t n_samples, float* z_mean, float* z_scale, float* z_samples, float* l_mean, float* l_scale, float* l_samples,
-                        float* x_params, float* const* y_params, const StatReq* sr) {
-  SMX_REQUIRE(m && (host_x != nullptr) != (cx != nullptr) && n_cells > 0 && n_samples > 0, "bad arguments");
+// rows (and a statistic's target): n_cells rows each, as the entry's host_rows checked them
+static int predict_core(smx_model* m, const HostRows& rows, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples, PredWant o) {
+  SMX_REQUIRE(n_samples > 0, "bad arguments");
   SMX_REQUIRE(batch > 0 && batch <= m->Bmax, "batch must be in 1..max_batch");
-  if (cx) SMX_CHECK(check_csr_rows(*cx, (size_t)n_cells, m->G));
-  if (sr && sr->tcsr) SMX_CHECK(check_csr_rows(*sr->tcsr, (size_t)n_cells, m->G));
+  const StatReq* const sr = o.sr;
+  const bool cx = rows.x == nullptr;   // CSR rows
   const size_t N = (size_t)n_cells, G = (size_t)m->G, Gp = (size_t)m->Gp, D = (size_t)m->D, k = (size_t)m->k, S = (size_t)n_samples;
   const size_t DS = m->latent_tril ? D * D : D;   // z_scale per cell: the factor L [D][D] of a tril posterior, the standard deviations otherwise
-  if (!m->stochastic) z_scale = nullptr;
-  if (!m->scvi) l_mean = l_scale = l_samples = nullptr;
+  if (!m->stochastic) o.z_scale = nullptr;
+  if (!m->scvi) o.l_mean = o.l_scale = o.l_samples = nullptr;
   PredChunk ch;
   ch.S = S; ch.sr = sr;
   for (int j = 0; j < m->n_heads; ++j)
-    if (y_params && y_params[j]) ch.wy[j] = (size_t)m->lab_ky[j] * (size_t)m->cfg.label_dim[j];
+    if (o.y_params && o.y_params[j]) ch.wy[j] = (size_t)m->lab_ky[j] * (size_t)m->cfg.label_dim[j];
   // the requested statistic of the gene output, per cell: S G (mean / variance per draw), G (mean over the draws), S (log_prob)
   // (predictive samples: n_k S G)
   const size_t w_stat = !sr ? 0 : sr->stat == 2 ? G : sr->stat == 3 ? S : sr->stat == 4 ? (size_t)sr->n_k * S * G : S * G;
@@ -562,9 +572,9 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
   struct Seg { float** at; size_t w; bool on; };
   static_assert(SMX_MAX_LABELS == 4, "one segment per label head");
   const Seg plan[] = {
-      {&ch.in_x, Gp, cx != nullptr},
-      {&ch.zm, D, z_mean != nullptr}, {&ch.zs, DS, z_scale != nullptr}, {&ch.lm, 1, l_mean != nullptr}, {&ch.ls, 1, l_scale != nullptr},
-      {&ch.zd, S * D, z_samples != nullptr}, {&ch.ld, S, l_samples != nullptr}, {&ch.xp, S * k * G, x_params != nullptr},
+      {&ch.in_x, Gp, cx},
+      {&ch.zm, D, o.z_mean != nullptr}, {&ch.zs, DS, o.z_scale != nullptr}, {&ch.lm, 1, o.l_mean != nullptr}, {&ch.ls, 1, o.l_scale != nullptr},
+      {&ch.zd, S * D, o.z_samples != nullptr}, {&ch.ld, S, o.l_samples != nullptr}, {&ch.xp, S * k * G, o.x_params != nullptr},
       {&ch.st, w_stat, w_stat > 0},
       {&ch.sel, sr ? (size_t)sr->n_sel : 0, sr && sr->n_sel > 0 && !sr->keep_cols}, {&ch.imed, 1, sr && sr->impute}, {&ch.ichg, 1, sr && sr->impute},
       {&ch.in_raw, G, !cx}, {&ch.in_x, Gp, !cx}, {&ch.in_lib, 2, true}, {&ch.in_lgx1, 1, true},
@@ -574,7 +584,7 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
   for (const Seg& g : plan) per_cell += g.on ? g.w : 0;
   SMX_REQUIRE(per_cell > (cx ? 0 : G) + Gp + 3, "no output requested");
   const bool impute = sr && sr->impute;
-  const bool t_dev = sr && (sr->stat == 3 || impute) && (sr->target || sr->tcsr);   // targets other than the input rows
+  const bool t_dev = sr && (sr->stat == 3 || impute) && (sr->target.x || sr->target.csr.indptr);   // targets other than the input rows
   if (t_dev) SMX_CHECK(dgrow(m, &m->pred_target, &m->pred_target_floats, (size_t)batch * Gp, (size_t)m->Bmax * Gp));   // a batch of target rows
   // 128 MB of staging (knob predict_stage_floats: tests force several chunks on small problems)
   const size_t cap_floats = (size_t)std::max(1.0, tuning("predict_stage_floats", (double)((size_t)32 << 20)));
@@ -606,7 +616,7 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
       m->pred_ids_batch = batch;
     }
   }
-  SMX_REQUIRE(!m->scvi || host_library, "scvi needs host_library with host_x");
+  SMX_REQUIRE(!m->scvi || host_library, "scvi needs host_library with host rows");
   bool any_y = false;
   for (int j = 0; j < m->n_heads; ++j) any_y = any_y || ch.y[j] != nullptr;
   const bool need_dec = ch.xp || ch.st || any_y;   // (latents only: the decoder and the heads are not run at all)
@@ -638,15 +648,15 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
   for (size_t c0 = 0; c0 < N; c0 += ch.Cn) {
     ch.Cn = std::min(C, N - c0);   // cells of this chunk (CSR rows: load_chunk may take fewer)
     ch.c0 = c0;
-    SMX_CHECK(load_chunk(m, ch, host_x, cx, host_library, c0, (size_t)batch, nnz_cap));
+    SMX_CHECK(load_chunk(m, ch, rows, host_library, c0, (size_t)batch, nnz_cap));
     const size_t Cn = ch.Cn;
     for (size_t b0 = 0; b0 < Cn; b0 += step) {
       const int B = (int)std::min<size_t>(step, Cn - b0);
       const size_t g0 = c0 + b0;
       Pass ps = host_rows_pass(B, ch.in_x + b0 * Gp, ch.in_lib + b0 * 2, ch.in_lgx1 + b0);   // (on the chunk's resident copy)
-      if (t_dev && sr->tcsr) SMX_CHECK(csr_host_rows(m, *sr->tcsr, g0, (size_t)B, m->pred_target, nullptr));
-      else if (t_dev && sr->target)
-        SMX_HIP(hipMemcpy2DAsync(m->pred_target, Gp * sizeof(float), sr->target + g0 * G, G * sizeof(float), G * sizeof(float), (size_t)B,
+      if (t_dev && sr->target.csr.indptr) SMX_CHECK(csr_host_rows(m, sr->target.csr, g0, (size_t)B, m->pred_target, nullptr));
+      else if (t_dev)
+        SMX_HIP(hipMemcpy2DAsync(m->pred_target, Gp * sizeof(float), sr->target.x + g0 * G, G * sizeof(float), G * sizeof(float), (size_t)B,
                                  hipMemcpyHostToDevice, m->st));
       if (stack) SMX_CHECK(predict_batch_stacked(m, ch, ps, b0, step > (size_t)batch ? m->pred_ids : nullptr, need_dec));
       else SMX_CHECK(predict_batch_drawwise(m, ch, ps, b0, need_dec));
@@ -661,10 +671,10 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
     }
     if (level > 0) { SMX_HIP(hipStreamSynchronize(m->st)); continue; }
     // ---- the chunk leaves the device: every segment's rows are contiguous here and in the caller's arrays ----
-    if (ch.zm) SMX_CHECK(out(z_mean + c0 * D, ch.zm, Cn * D));
-    if (ch.zs) SMX_CHECK(out(z_scale + c0 * DS, ch.zs, Cn * DS));
-    if (ch.lm) SMX_CHECK(out(l_mean + c0, ch.lm, Cn));
-    if (ch.ls) SMX_CHECK(out(l_scale + c0, ch.ls, Cn));
+    if (ch.zm) SMX_CHECK(out(o.z_mean + c0 * D, ch.zm, Cn * D));
+    if (ch.zs) SMX_CHECK(out(o.z_scale + c0 * DS, ch.zs, Cn * DS));
+    if (ch.lm) SMX_CHECK(out(o.l_mean + c0, ch.lm, Cn));
+    if (ch.ls) SMX_CHECK(out(o.l_scale + c0, ch.ls, Cn));
     if (ch.st && sr->keep_cols) SMX_CHECK(launch_keep_cols(m->st, ch.st, (long)G, (long)Cn, sr->sel, sr->n_sel, sr->keep_cols, (long)N, (long)c0));
     else if (ch.st && sr->stat == 2 && !impute && !ch.sel) SMX_CHECK(out(sr->out + c0 * G, ch.st, Cn * G));
     if (ch.sel) {
@@ -682,12 +692,12 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
       else SMX_CHECK(out(sr->out + (s * N + c0) * G, ch.st + s * Cn * G, Cn * G));
     }
     for (size_t s = 0; s < S; ++s) {
-      if (ch.zd) SMX_CHECK(out(z_samples + (s * N + c0) * D, ch.zd + s * Cn * D, Cn * D));
-      if (ch.ld) SMX_CHECK(out(l_samples + s * N + c0, ch.ld + s * Cn, Cn));
+      if (ch.zd) SMX_CHECK(out(o.z_samples + (s * N + c0) * D, ch.zd + s * Cn * D, Cn * D));
+      if (ch.ld) SMX_CHECK(out(o.l_samples + s * N + c0, ch.ld + s * Cn, Cn));
       if (ch.xp)
-        for (size_t c = 0; c < k; ++c) SMX_CHECK(out(x_params + ((s * k + c) * N + c0) * G, ch.xp + (s * k + c) * Cn * G, Cn * G));
+        for (size_t c = 0; c < k; ++c) SMX_CHECK(out(o.x_params + ((s * k + c) * N + c0) * G, ch.xp + (s * k + c) * Cn * G, Cn * G));
       for (int j = 0; j < m->n_heads; ++j)
-        if (ch.y[j]) SMX_CHECK(out(y_params[j] + (s * N + c0) * ch.wy[j], ch.y[j] + s * Cn * ch.wy[j], Cn * ch.wy[j]));
+        if (ch.y[j]) SMX_CHECK(out(o.y_params[j] + (s * N + c0) * ch.wy[j], ch.y[j] + s * Cn * ch.wy[j], Cn * ch.wy[j]));
     }
     SMX_HIP(hipStreamSynchronize(m->st));
   }
@@ -730,80 +740,57 @@ static int predict_core(smx_model* m, const float* host_x, const CsrRows* cx, co
   return SMX_OK;
 }
 
-int smx_predict(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
-                float* z_mean, float* z_scale, float* z_samples, float* l_mean, float* l_scale, float* l_samples,
-                float* x_params, float* const* y_params) {
-  return predict_core(m, host_x, nullptr, host_library, n_cells, batch, n_samples, z_mean, z_scale, z_samples, l_mean, l_scale, l_samples, x_params,
-                      y_params, nullptr);
+int smx_predict(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                int64_t n_cells, int32_t batch, int32_t n_samples, float* z_mean, float* z_scale, float* z_samples, float* l_mean,
+                float* l_scale, float* l_samples, float* x_params, float* const* y_params) {
+  SMX_REQUIRE(m, "null model");
+  HostRows rows;
+  SMX_CHECK(host_rows(host_x, indptr, cols, vals, n_cells, m->G, &rows));
+  return predict_core(m, rows, host_library, n_cells, batch, n_samples,
+                      {nullptr, z_mean, z_scale, z_samples, l_mean, l_scale, l_samples, x_params, y_params});
 }
 
-int smx_predict_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library, int64_t n_cells,
-                    int32_t batch, int32_t n_samples, float* z_mean, float* z_scale, float* z_samples, float* l_mean, float* l_scale,
-                    float* l_samples, float* x_params, float* const* y_params) {
-  SMX_REQUIRE(indptr, "null indptr");
-  const CsrRows cx{indptr, cols, vals};
-  return predict_core(m, nullptr, &cx, host_library, n_cells, batch, n_samples, z_mean, z_scale, z_samples, l_mean, l_scale, l_samples, x_params,
-                      y_params, nullptr);
-}
-
-int smx_predict_stat(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
-                     int32_t stat, int32_t count_only, const float* target, float* out) {
+int smx_predict_stat(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                     int64_t n_cells, int32_t batch, int32_t n_samples, int32_t stat, int32_t count_only, const float* target,
+                     const int64_t* t_indptr, const int32_t* t_cols, const float* t_vals, float* out) {
   SMX_REQUIRE(m && out && stat >= 0 && stat <= 3, "bad arguments (stat: 0 mean, 1 variance, 2 mean over the draws, 3 log_prob)");
   SMX_REQUIRE(!(count_only && m->cfg.likelihood == SMX_LLK_MSE), "the deterministic 'mse' output has no count distribution");
+  HostRows rows;
   StatReq sr;
-  sr.stat = stat; sr.count_only = count_only ? 1 : 0; sr.target = target; sr.out = out;
-  return predict_core(m, host_x, nullptr, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr);
-}
-
-int smx_predict_stat_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library, int64_t n_cells,
-                         int32_t batch, int32_t n_samples, int32_t stat, int32_t count_only, const float* target, const int64_t* t_indptr,
-                         const int32_t* t_cols, const float* t_vals, float* out) {
-  SMX_REQUIRE(m && out && stat >= 0 && stat <= 3, "bad arguments (stat: 0 mean, 1 variance, 2 mean over the draws, 3 log_prob)");
-  SMX_REQUIRE(!(count_only && m->cfg.likelihood == SMX_LLK_MSE), "the deterministic 'mse' output has no count distribution");
-  SMX_REQUIRE(!(target && t_indptr), "a target is dense or CSR, not both");
-  const CsrRows cx{indptr, cols, vals}, tc{t_indptr, t_cols, t_vals};
-  const CsrRows* in = indptr ? &cx : nullptr;
-  StatReq sr;
-  sr.stat = stat; sr.count_only = count_only ? 1 : 0; sr.target = target; sr.tcsr = t_indptr ? &tc : nullptr; sr.out = out;
-  return predict_core(m, nullptr, in, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr);
+  SMX_CHECK(host_rows(host_x, indptr, cols, vals, n_cells, m->G, &rows));
+  if (target || t_indptr) SMX_CHECK(host_rows(target, t_indptr, t_cols, t_vals, n_cells, m->G, &sr.target));
+  sr.stat = stat; sr.count_only = count_only ? 1 : 0; sr.out = out;
+  return predict_core(m, rows, host_library, n_cells, batch, n_samples, {&sr});
 }
 
 // stat 2 restricted to n_sel gene columns: the indices are checked here and go to the device once
-static int predict_stat_cols(smx_model* m, const float* host_x, const CsrRows* cx, const float* host_library, int64_t n_cells, int32_t batch,
-                             int32_t n_samples, int32_t count_only, const int32_t* genes, int32_t n_sel, float* out) {
+int smx_predict_stat_cols(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals,
+                          const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, const int32_t* genes,
+                          int32_t n_sel, float* out) {
   SMX_REQUIRE(m && out && genes && n_sel > 0, "bad arguments");
   SMX_REQUIRE(!(count_only && m->cfg.likelihood == SMX_LLK_MSE), "the deterministic 'mse' output has no count distribution");
+  HostRows rows;
+  SMX_CHECK(host_rows(host_x, indptr, cols, vals, n_cells, m->G, &rows));
   for (int i = 0; i < n_sel; ++i) SMX_REQUIRE(genes[i] >= 0 && genes[i] < m->G, "gene index out of range");
   SMX_CHECK(dgrow(m, &m->pred_sel, &m->pred_sel_n, (size_t)n_sel));
   SMX_HIP(hipMemcpy(m->pred_sel, genes, (size_t)n_sel * sizeof(int32_t), hipMemcpyHostToDevice));
   StatReq sr;
   sr.stat = 2; sr.count_only = count_only ? 1 : 0; sr.out = out; sr.sel = m->pred_sel; sr.n_sel = n_sel;
-  return predict_core(m, host_x, cx, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr);
-}
-
-int smx_predict_stat_cols(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
-                          int32_t count_only, const int32_t* genes, int32_t n_sel, float* out) {
-  return predict_stat_cols(m, host_x, nullptr, host_library, n_cells, batch, n_samples, count_only, genes, n_sel, out);
-}
-
-int smx_predict_stat_cols_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
-                              int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, const int32_t* genes, int32_t n_sel,
-                              float* out) {
-  SMX_REQUIRE(indptr, "null indptr");
-  const CsrRows cx{indptr, cols, vals};
-  return predict_stat_cols(m, nullptr, &cx, host_library, n_cells, batch, n_samples, count_only, genes, n_sel, out);
+  return predict_core(m, rows, host_library, n_cells, batch, n_samples, {&sr});
 }
 
 // the correlation sums of the walk's stat 2 (smx_correlate.hip): the selected genes in chunks of Gc whose kept columns, ranks and sort arrays
 // (16 N bytes per gene) fit the knob correlate_keep_bytes; every chunk repeats the walk -- the same passes, the same bits
-static int predict_correlate(smx_model* m, const float* host_x, const CsrRows* cx, const float* host_library, int64_t n_cells, int32_t batch,
-                             int32_t n_samples, int32_t count_only, const int32_t* genes, int32_t n_sel, const int32_t* prot_rank2,
-                             const double* prot_unit, int32_t P, int64_t* sp_Sa, int64_t* sp_Saa, int64_t* sp_Sab, double* pe_mean, double* pe_Sxx,
-                             double* pe_Sxy, int32_t* nonfinite) {
+int smx_predict_correlate(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals,
+                          const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, const int32_t* genes,
+                          int32_t n_sel, const int32_t* prot_rank2, const double* prot_unit, int32_t P, int64_t* sp_Sa, int64_t* sp_Saa,
+                          int64_t* sp_Sab, double* pe_mean, double* pe_Sxx, double* pe_Sxy, int32_t* nonfinite) {
   SMX_REQUIRE(m && prot_rank2 && prot_unit && P > 0 && sp_Sa && sp_Saa && sp_Sab && pe_mean && pe_Sxx && pe_Sxy && nonfinite, "bad arguments");
   SMX_REQUIRE(n_cells > 0 && n_cells <= SMX_COR_MAX_CELLS, "correlations take 1 .. 2^20 cells");
   SMX_REQUIRE(!(count_only && m->cfg.likelihood == SMX_LLK_MSE), "the deterministic 'mse' output has no count distribution");
   SMX_REQUIRE(genes ? n_sel > 0 : true, "an empty gene list");
+  HostRows rows;
+  SMX_CHECK(host_rows(host_x, indptr, cols, vals, n_cells, m->G, &rows));
   const size_t n = genes ? (size_t)n_sel : (size_t)m->G, N = (size_t)n_cells, pn = (size_t)P * N;
   std::vector<int32_t> idx(n);
   for (size_t i = 0; i < n; ++i) {
@@ -834,7 +821,7 @@ static int predict_correlate(smx_model* m, const float* host_x, const CsrRows* c
     const int gc = (int)std::min(Gc, n - g0);
     StatReq sr;
     sr.stat = 2; sr.count_only = count_only ? 1 : 0; sr.sel = m->pred_sel + g0; sr.n_sel = gc; sr.keep_cols = w.cols;
-    SMX_CHECK(predict_core(m, host_x, cx, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr));
+    SMX_CHECK(predict_core(m, rows, host_library, n_cells, batch, n_samples, {&sr}));
     const CorrelateOut o{reinterpret_cast<long long*>(sp_Sa) + g0, reinterpret_cast<long long*>(sp_Saa) + g0, reinterpret_cast<long long*>(sp_Sab) + g0 * (size_t)P,
                          pe_mean + g0, pe_Sxx + g0, pe_Sxy + g0 * (size_t)P, nonfinite + g0};
     SMX_CHECK(correlate_kept(m->st, w, gc, (long)N, P, o));
@@ -842,73 +829,32 @@ static int predict_correlate(smx_model* m, const float* host_x, const CsrRows* c
   return SMX_OK;
 }
 
-int smx_predict_correlate(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
-                          int32_t count_only, const int32_t* genes, int32_t n_sel, const int32_t* prot_rank2, const double* prot_unit, int32_t P,
-                          int64_t* sp_Sa, int64_t* sp_Saa, int64_t* sp_Sab, double* pe_mean, double* pe_Sxx, double* pe_Sxy, int32_t* nonfinite) {
-  return predict_correlate(m, host_x, nullptr, host_library, n_cells, batch, n_samples, count_only, genes, n_sel, prot_rank2, prot_unit, P, sp_Sa,
-                           sp_Saa, sp_Sab, pe_mean, pe_Sxx, pe_Sxy, nonfinite);
-}
-
-int smx_predict_correlate_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
-                              int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, const int32_t* genes, int32_t n_sel,
-                              const int32_t* prot_rank2, const double* prot_unit, int32_t P, int64_t* sp_Sa, int64_t* sp_Saa, int64_t* sp_Sab,
-                              double* pe_mean, double* pe_Sxx, double* pe_Sxy, int32_t* nonfinite) {
-  SMX_REQUIRE(indptr, "null indptr");
-  const CsrRows cx{indptr, cols, vals};
-  return predict_correlate(m, nullptr, &cx, host_library, n_cells, batch, n_samples, count_only, genes, n_sel, prot_rank2, prot_unit, P, sp_Sa,
-                           sp_Saa, sp_Sab, pe_mean, pe_Sxx, pe_Sxy, nonfinite);
-}
-
 // the imputation scores of the walk's stat 2 (smx_impute.hip)
-static int predict_impute(smx_model* m, const float* host_x, const CsrRows* cx, const float* host_library, int64_t n_cells, int32_t batch,
-                          int32_t n_samples, int32_t count_only, const float* original, const CsrRows* ocsr, float* cell_median,
-                          int32_t* cell_changed, float* global_lohi) {
+int smx_predict_impute(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                       int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, const float* original, const int64_t* o_indptr,
+                       const int32_t* o_cols, const float* o_vals, float* cell_median, int32_t* cell_changed, float* global_lohi) {
   SMX_REQUIRE(m && cell_median && cell_changed && global_lohi, "bad arguments");
-  SMX_REQUIRE((original != nullptr) != (ocsr != nullptr), "the original rows are dense or CSR (exactly one of the two)");
   SMX_REQUIRE(!(count_only && m->cfg.likelihood == SMX_LLK_MSE), "the deterministic 'mse' output has no count distribution");
+  HostRows rows;
   StatReq sr;
-  sr.stat = 2; sr.count_only = count_only ? 1 : 0; sr.target = original; sr.tcsr = ocsr;
+  SMX_CHECK(host_rows(host_x, indptr, cols, vals, n_cells, m->G, &rows));
+  SMX_CHECK(host_rows(original, o_indptr, o_cols, o_vals, n_cells, m->G, &sr.target));
+  sr.stat = 2; sr.count_only = count_only ? 1 : 0;
   sr.impute = 1; sr.imp_median = cell_median; sr.imp_changed = cell_changed; sr.imp_lohi = global_lohi;
-  return predict_core(m, host_x, cx, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr);
-}
-
-int smx_predict_impute(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
-                       int32_t count_only, const float* original, float* cell_median, int32_t* cell_changed, float* global_lohi) {
-  return predict_impute(m, host_x, nullptr, host_library, n_cells, batch, n_samples, count_only, original, nullptr, cell_median, cell_changed,
-                        global_lohi);
-}
-
-int smx_predict_impute_csr(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals,
-                           const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only,
-                           const float* original, const int64_t* o_indptr, const int32_t* o_cols, const float* o_vals, float* cell_median,
-                           int32_t* cell_changed, float* global_lohi) {
-  SMX_REQUIRE((host_x != nullptr) != (indptr != nullptr), "the input rows are dense or CSR (exactly one of the two)");
-  const CsrRows cx{indptr, cols, vals}, oc{o_indptr, o_cols, o_vals};
-  return predict_impute(m, host_x, indptr ? &cx : nullptr, host_library, n_cells, batch, n_samples, count_only, original,
-                        o_indptr ? &oc : nullptr, cell_median, cell_changed, global_lohi);
+  return predict_core(m, rows, host_library, n_cells, batch, n_samples, {&sr});
 }
 
 // stat 4 of the walk: n_k samples of the gene output per draw and cell, out [n_k, n_samples, n_cells, n_genes]
-static int predict_sample(smx_model* m, const float* host_x, const CsrRows* cx, const float* host_library, int64_t n_cells, int32_t batch,
-                          int32_t n_samples, int32_t count_only, uint64_t seed, int32_t n_k, float* out) {
+int smx_predict_sample(smx_model* m, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
+                       int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, uint64_t seed, int32_t n_k, float* out) {
   SMX_REQUIRE(m && out && n_k > 0, "bad arguments");
   SMX_REQUIRE(!(count_only && m->cfg.likelihood == SMX_LLK_MSE), "the deterministic 'mse' output has no count distribution");
   SMX_REQUIRE(n_cells <= (int64_t)0xFFFFFFFFll && n_samples <= 65536, "the sampler's counters hold 2^32 cells and 2^16 draws");
+  HostRows rows;
+  SMX_CHECK(host_rows(host_x, indptr, cols, vals, n_cells, m->G, &rows));
   StatReq sr;
   sr.stat = 4; sr.count_only = count_only ? 1 : 0; sr.out = out; sr.seed = seed; sr.n_k = n_k;
-  return predict_core(m, host_x, cx, host_library, n_cells, batch, n_samples, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sr);
-}
-
-int smx_predict_sample(smx_model* m, const float* host_x, const float* host_library, int64_t n_cells, int32_t batch, int32_t n_samples,
-                       int32_t count_only, uint64_t seed, int32_t n_k, float* out) {
-  return predict_sample(m, host_x, nullptr, host_library, n_cells, batch, n_samples, count_only, seed, n_k, out);
-}
-
-int smx_predict_sample_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library,
-                           int64_t n_cells, int32_t batch, int32_t n_samples, int32_t count_only, uint64_t seed, int32_t n_k, float* out) {
-  SMX_REQUIRE(indptr, "null indptr");
-  const CsrRows cx{indptr, cols, vals};
-  return predict_sample(m, nullptr, &cx, host_library, n_cells, batch, n_samples, count_only, seed, n_k, out);
+  return predict_core(m, rows, host_library, n_cells, batch, n_samples, {&sr});
 }
 
 int smx_decode(smx_model* m, const float* z, const float* l, int32_t batch, float* x_params, float* const* y_params) {

@@ -1,5 +1,5 @@
 // smx_sample.hip -- posterior-predictive draws of the gene output from the parameter planes of a pass: smx_predict_stat's walk with
-// stat 4 (smx_predict_sample / _csr, smx_predict.hip) and the kernel-test entry smx_k_plane_sample.  DESIGN.md section 4j.
+// stat 4 (smx_predict_sample, smx_predict.hip) and the kernel-test entry smx_k_plane_sample.  DESIGN.md section 4j.
 //
 // One draw x ~ p(x | planes) per (sample k, draw s, cell, gene), float32:
 //   nb / zinb    Poisson(Gamma(shape = exp(p0), scale = exp(p1)));   nbd / zinbd   Poisson(Gamma(shape = theta, scale = mu / theta)),

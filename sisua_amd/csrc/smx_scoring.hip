@@ -224,7 +224,7 @@ static int land_scores(smx_model* m, int rc, const float* run, size_t floats, co
   return SMX_OK;
 }
 
-// smx_marginal_llk(_csr) after the batch's pass is set up
+// smx_marginal_llk after the batch's pass is set up
 static int marginal_llk_run(smx_model* m, Pass& ps, int32_t batch, int32_t n_samples, float* mllk, float* llk_mean) {
   const bool stacked = stacked_scores_ok(m);
   // a deterministic latent (DCA) decodes to the same parameters in every draw: one pass is the whole estimate
@@ -262,27 +262,15 @@ static int marginal_llk_run(smx_model* m, Pass& ps, int32_t batch, int32_t n_sam
 
 extern "C" {
 
-int smx_marginal_llk(smx_model* m, const int32_t* row_ids, const float* host_x, const float* host_library, int32_t batch,
-                     int32_t n_samples, float* mllk, float* llk_mean) {
+int smx_marginal_llk(smx_model* m, const int32_t* row_ids, const float* host_x, const int64_t* indptr, const int32_t* cols, const float* vals,
+                     const float* host_library, int32_t batch, int32_t n_samples, float* mllk, float* llk_mean) {
   SMX_REQUIRE(m && mllk && n_samples > 0, "bad arguments");
   SMX_REQUIRE(m->cfg.likelihood != SMX_LLK_MSE, "the 'mse' output is not a normalised density: no marginal likelihood");
+  CellSrc src{row_ids, {}, host_library};
+  if (row_ids) SMX_REQUIRE(!host_x && !indptr, "the cells are row_ids or host rows, not both");
+  else SMX_CHECK(host_rows(host_x, indptr, cols, vals, batch, m->G, &src.rows));
   Pass ps;
-  SMX_CHECK(setup_pass(m, ps, {row_ids, host_x, host_library}, batch, 0, 0));
-  return marginal_llk_run(m, ps, batch, n_samples, mllk, llk_mean);
-}
-
-int smx_marginal_llk_csr(smx_model* m, const int64_t* indptr, const int32_t* cols, const float* vals, const float* host_library, int32_t batch,
-                         int32_t n_samples, float* mllk, float* llk_mean) {
-  SMX_REQUIRE(m && mllk && n_samples > 0, "bad arguments");
-  SMX_REQUIRE(m->cfg.likelihood != SMX_LLK_MSE, "the 'mse' output is not a normalised density: no marginal likelihood");
-  SMX_REQUIRE(batch > 0 && batch <= m->Bmax, "batch must be in 1..max_batch");
-  SMX_REQUIRE(!m->scvi || host_library, "scvi needs host_library with host rows");
-  const CsrRows cx{indptr, cols, vals};
-  SMX_CHECK(check_csr_rows(cx, (size_t)batch, m->G));
-  // (what setup_pass does for dense host rows; the rows' tile and constants from one launch)
-  SMX_CHECK(csr_host_rows(m, cx, 0, (size_t)batch, m->hostX, m->hostLgx1));
-  if (host_library) SMX_HIP(hipMemcpy(m->hostLib, host_library, (size_t)batch * 2 * sizeof(float), hipMemcpyHostToDevice));
-  Pass ps = host_rows_pass(batch, m->hostX, m->hostLib, m->hostLgx1);
+  SMX_CHECK(setup_pass(m, ps, src, batch, 0, 0));
   return marginal_llk_run(m, ps, batch, n_samples, mllk, llk_mean);
 }
 
@@ -292,7 +280,7 @@ int smx_score_llk(smx_model* m, const int32_t* row_ids, const float* host_x, con
   SMX_REQUIRE(m->cfg.likelihood != SMX_LLK_MSE, "the 'mse' output is not a normalised density: no posterior-predictive scores");
   if (!m->stochastic) n_samples = 1;   // (deterministic latent: every draw decodes to the same parameters)
   Pass ps;
-  SMX_CHECK(setup_pass(m, ps, {row_ids, host_x, host_library}, batch, 0, 0));
+  SMX_CHECK(setup_pass(m, ps, {row_ids, {host_x}, host_library}, batch, 0, 0));
   const int lk = m->cfg.likelihood;
   const bool zi = (lk == SMX_LLK_ZINB || lk == SMX_LLK_ZINBD);
   const int n_dist = zi ? 2 : 1;

@@ -367,7 +367,7 @@ int launch_train(smx_model* m, int B, bool use_graph, int s_idx, int n_steps) {
 
 int setup_pass(smx_model* m, Pass& ps, const CellSrc& src, int32_t batch, int training, int sample, int draw_rows) {
   const int32_t* row_ids = src.row_ids;
-  const float *host_x = src.host_x, *host_library = src.host_library;
+  const float *host_x = src.rows.x, *host_library = src.host_library;
   SMX_REQUIRE(batch > 0 && batch <= (draw_rows > 0 ? m->Rmax : m->Bmax), "batch must be in 1..max_batch");
   ps.B = batch; ps.training = training; ps.sample = sample; ps.global_batch = batch; ps.draw_rows = draw_rows;
   if (row_ids) {
@@ -377,12 +377,14 @@ int setup_pass(smx_model* m, Pass& ps, const CellSrc& src, int32_t batch, int tr
     ps.rows = cur_rows(m); ps.xrows = ps.rows; ps.Xsrc = m->X; ps.x_u16 = m->x_u16; ps.lib = m->library; ps.lgx1 = m->lgx1; ps.cell_base = (uint32_t)m->cell_base;
     SMX_CHECK(csr_stage(m, ps));
   } else {
-    SMX_REQUIRE(host_x, "need row_ids or host_x");
-    SMX_REQUIRE(!m->scvi || host_library, "scvi needs host_library with host_x");
-    SMX_HIP(hipMemsetAsync(m->hostX, 0, (size_t)batch * m->Gp * sizeof(float), m->st));
-    SMX_HIP(hipMemcpy2DAsync(m->hostX, (size_t)m->Gp * sizeof(float), host_x, (size_t)m->G * sizeof(float),
-                             (size_t)m->G * sizeof(float), (size_t)batch, hipMemcpyHostToDevice, m->st));
-    SMX_CHECK(launch_row_stats(m->st, m->hostX, 0, m->Gp, batch, m->G, m->hostLgx1, nullptr));
+    SMX_REQUIRE(host_x || src.rows.csr.indptr, "need row_ids or host rows");
+    SMX_REQUIRE(!m->scvi || host_library, "scvi needs host_library with host rows");
+    if (host_x) {
+      SMX_HIP(hipMemsetAsync(m->hostX, 0, (size_t)batch * m->Gp * sizeof(float), m->st));
+      SMX_HIP(hipMemcpy2DAsync(m->hostX, (size_t)m->Gp * sizeof(float), host_x, (size_t)m->G * sizeof(float),
+                               (size_t)m->G * sizeof(float), (size_t)batch, hipMemcpyHostToDevice, m->st));
+      SMX_CHECK(launch_row_stats(m->st, m->hostX, 0, m->Gp, batch, m->G, m->hostLgx1, nullptr));
+    } else SMX_CHECK(csr_host_rows(m, src.rows.csr, 0, (size_t)batch, m->hostX, m->hostLgx1));   // (CSR rows, checked by the entry's host_rows: the tile and the constants from one launch)
     if (host_library) SMX_HIP(hipMemcpy(m->hostLib, host_library, (size_t)batch * 2 * sizeof(float), hipMemcpyHostToDevice));
     ps = host_rows_pass(batch, m->hostX, m->hostLib, m->hostLgx1);
     ps.training = training; ps.sample = sample; ps.draw_rows = draw_rows;
@@ -546,10 +548,10 @@ int smx_eval_step(smx_model* m, const int32_t* row_ids, int32_t batch, smx_metri
     SMX_REQUIRE(batch > 0 && batch <= m->Bmax, "batch must be in 1..max_batch");
     SMX_CHECK(check_rows(m, row_ids, (size_t)batch));
     const std::vector<int32_t> tiled = smx::tile_draws(m, row_ids, 1, batch);
-    SMX_CHECK(setup_pass(m, ps, {tiled.data(), nullptr, nullptr}, batch * m->train_draws, 0, 0, batch));
+    SMX_CHECK(setup_pass(m, ps, {tiled.data(), {}, nullptr}, batch * m->train_draws, 0, 0, batch));
     SMX_HIP(hipStreamSynchronize(m->st));   // (the row ids went from `tiled`, a host vector about to go)
   } else {
-    SMX_CHECK(setup_pass(m, ps, {row_ids, nullptr, nullptr}, batch, 0, 0));
+    SMX_CHECK(setup_pass(m, ps, {row_ids, {}, nullptr}, batch, 0, 0));
   }
   SMX_CHECK(forward_pass(m, ps, Loss::Eval));
   SMX_CHECK(read_metrics(m, out));

@@ -56,8 +56,8 @@ def _csr_ptrs(t):
 
 
 def _matrix_ptrs(dense, csr):
-  """The four leading pointers (x, indptr, cols, vals) of a model-free C entry for the (dense, csr) pair `_prep_input` returns: one of the
-  two is None."""
+  """The four pointers (x, indptr, cols, vals) of a host matrix in the rows convention of include/sisua_hip.h, for a (dense, csr) pair: one
+  of the two is None (both: a matrix the entry lets the caller leave out)."""
   return (_fp(dense), *((None, None, None) if csr is None else _csr_ptrs(csr)))
 
 

@@ -14,7 +14,7 @@ import numpy as np
 from sisua_amd import _hip, interpolation, optimizers
 from sisua_amd._hip import SmxError, check, smx_config, smx_metrics
 from sisua_amd.config import ModelConfig, init_params, label_planes, manifest
-from sisua_amd.engine._args import _csr3, _csr_ptrs, _dp, _f32, _fp, _fps, _ip, _ptr, _sparse
+from sisua_amd.engine._args import _csr3, _csr_ptrs, _dp, _f32, _fp, _fps, _ip, _matrix_ptrs, _ptr, _sparse
 from sisua_amd.engine._correlate import _col_operands, _col_outputs
 
 STREAM_INPUT_DROPOUT = 0
@@ -45,6 +45,14 @@ def _out_f32(out, shape):
   if out.dtype != np.float32 or tuple(out.shape) != shape or not out.flags.c_contiguous:
     raise ValueError(f"out must be a C-contiguous float32 array of shape {shape}")
   return out
+
+
+def _host_rows(x, n_genes: int, n_rows: Optional[int] = None):
+  """Host rows as the (dense, csr) pair `_matrix_ptrs` takes: float32 [N, G] (shape-checked where n_rows is given) or, from scipy.sparse,
+  their `_csr3` triple."""
+  if _sparse(x):
+    return None, _csr3(x, n_genes, n_rows)
+  return _f32(x, None if n_rows is None else (n_rows, n_genes)), None
 
 
 def gene_indices(genes, n_genes: int) -> np.ndarray:
@@ -451,30 +459,23 @@ class Engine:
     return _tril_scale(out)
 
   def _staged(self, x, library, batch):
-    """The input of a predict-family call, staged once: (xa, N, B, la) -- the rows as float32 [N, G] or, from scipy.sparse, as their
-    `_csr3` triple; the cells per pass (`batch`, at most max_batch); the library prior [N, 2] or None."""
-    xa = _csr3(x, self.cfg.n_genes) if _sparse(x) else _f32(x)
-    N = xa[0].size - 1 if isinstance(xa, tuple) else xa.shape[0]
+    """The input of a predict-family call, staged once: (rows, N, B, la) -- rows: the (dense, csr) pair `_matrix_ptrs` takes, float32
+    [N, G] or, from scipy.sparse, the `_csr3` triple; the cells per pass (`batch`, at most max_batch); the library prior [N, 2] or None."""
+    rows = _host_rows(x, self.cfg.n_genes)
+    N = rows[0].shape[0] if rows[1] is None else rows[1][0].size - 1
     B = min(int(batch or self.max_batch), self.max_batch)
     la = None if library is None else _f32(library, (N, 2))
-    return xa, N, B, la
-
-  def _rows_call(self, name, xa, *tail):
-    """smx_<name> on dense rows, smx_<name>_csr on a CSR triple: the two entries share every argument behind the rows (`tail`)."""
-    if isinstance(xa, tuple):
-      check(getattr(self.lib, f"smx_{name}_csr")(self._h, *_csr_ptrs(xa), *tail))
-    else:
-      check(getattr(self.lib, f"smx_{name}")(self._h, _fp(xa), *tail))
+    return rows, N, B, la
 
   def predict(self, x, library=None, n_samples: int = 1, batch: Optional[int] = None, want_x_params: bool = True, want=None):
     """Eval-mode forward of a whole host matrix in one call (smx_predict): arrays over ALL cells, with a leading draw
     axis for z_sample / l_sample / x_params / y_params -- the layout of forward_samples with n = every cell.
     want_x_params=False: everything but the gene output's parameter planes (what a lazy result keeps on the device side).
     want: only the named outputs leave the device (see `_outputs`; the clustering scores ask for the latent means alone).
-    x may be scipy.sparse (smx_predict_csr: the same results bit for bit)."""
-    (xa, N, B, la), S = self._staged(x, library, batch), int(n_samples)
+    x may be scipy.sparse (the same results bit for bit)."""
+    (rows, N, B, la), S = self._staged(x, library, batch), int(n_samples)
     out, res = self._outputs(N, S, want_x_params and (want is None or "x_params" in want), want)
-    self._rows_call("predict", xa, _fp(la), N, B, S, *res)
+    check(self.lib.smx_predict(self._h, *_matrix_ptrs(*rows), _fp(la), N, B, S, *res))
     return _tril_scale(out)
 
   STATS = {"mean": 0, "variance": 1, "mean_over_samples": 2, "log_prob": 3, "sample": 4}
@@ -484,33 +485,25 @@ class Engine:
     """A statistic of the gene output over a whole host matrix (smx_predict_stat): the same passes and draws as predict(), but only the
     statistic leaves the device.  'mean' / 'variance' [n_samples, N, G]; 'mean_over_samples' [N, G]; 'log_prob' [n_samples, N] of `target`
     (default: of x itself).  count_only: the count distribution without the zero-inflation wrapper.  `out`: a float32 array of the
-    result's shape to write into (a reused array saves the first-touch page faults of a fresh one).  x and target may be scipy.sparse
-    (smx_predict_stat_csr).  'sample': [n, n_samples, N, G], n posterior-predictive draws of the gene output per Monte-Carlo draw and cell
-    under the integer `seed` (smx_predict_sample / _csr: drawn on the device, the same bits at any batch size and from dense or sparse x).
+    result's shape to write into (a reused array saves the first-touch page faults of a fresh one).  x and target may each be scipy.sparse.
+    'sample': [n, n_samples, N, G], n posterior-predictive draws of the gene output per Monte-Carlo draw and cell
+    under the integer `seed` (smx_predict_sample: drawn on the device, the same bits at any batch size and from dense or sparse x).
     genes ('mean_over_samples' only): gene indices -- [N, len(genes)] leaves the device, the same bits as those columns (smx_predict_stat_cols)."""
     cfg = self.cfg
     if genes is not None:
       return self._predict_stat_cols(x, stat, library, n_samples, batch, count_only, target, out, genes)
-    (xa, N, B, la), S, G = self._staged(x, library, batch), int(n_samples), cfg.n_genes
+    (rows, N, B, la), S, G = self._staged(x, library, batch), int(n_samples), cfg.n_genes
     code = self.STATS[stat]
     shape = (N, G) if code == 2 else (S, N) if code == 3 else (int(n), S, N, G) if code == 4 else (S, N, G)
     if code == 4 and (int(n) < 1 or target is not None):
       raise ValueError("'sample' takes n >= 1 and no target")
     out = _out_f32(out, shape)
     if code == 4:
-      self._rows_call("predict_sample", xa, _fp(la), N, B, S, int(bool(count_only)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(n), _fp(out))
+      check(self.lib.smx_predict_sample(self._h, *_matrix_ptrs(*rows), _fp(la), N, B, S, int(bool(count_only)), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        int(n), _fp(out)))
       return out
-    tc = _csr3(target, G, N) if (target is not None and _sparse(target)) else None
-    ta = None if (target is None or tc is not None) else _f32(target, (N, G))
-    if isinstance(xa, tuple) or tc is not None:
-      if not isinstance(xa, tuple):   # (a dense input with a CSR target: the CSR entry point takes both)
-        import scipy.sparse as sp
-        xa = _csr3(sp.csr_matrix(xa), G)
-      xc = xa
-      tp = _csr_ptrs(tc) if tc is not None else (None, None, None)
-      check(self.lib.smx_predict_stat_csr(self._h, *_csr_ptrs(xc), _fp(la), N, B, S, code, int(bool(count_only)), _fp(ta), *tp, _fp(out)))
-    else:
-      check(self.lib.smx_predict_stat(self._h, _fp(xa), _fp(la), N, B, S, code, int(bool(count_only)), _fp(ta), _fp(out)))
+    trows = (None, None) if target is None else _host_rows(target, G, N)   # (no target: the log_prob of the input rows themselves)
+    check(self.lib.smx_predict_stat(self._h, *_matrix_ptrs(*rows), _fp(la), N, B, S, code, int(bool(count_only)), *_matrix_ptrs(*trows), _fp(out)))
     return out
 
   def _predict_stat_cols(self, x, stat, library, n_samples, batch, count_only, target, out, genes):
@@ -518,9 +511,9 @@ class Engine:
     if stat != "mean_over_samples" or target is not None:
       raise ValueError("genes= goes with 'mean_over_samples' (and no target)")
     idx = gene_indices(genes, cfg.n_genes)
-    (xa, N, B, la), S = self._staged(x, library, batch), int(n_samples)
+    (rows, N, B, la), S = self._staged(x, library, batch), int(n_samples)
     out = _out_f32(out, (N, idx.size))
-    self._rows_call("predict_stat_cols", xa, _fp(la), N, B, S, int(bool(count_only)), _ip(idx), idx.size, _fp(out))
+    check(self.lib.smx_predict_stat_cols(self._h, *_matrix_ptrs(*rows), _fp(la), N, B, S, int(bool(count_only)), _ip(idx), idx.size, _fp(out)))
     return out
 
   def predict_impute(self, x, original, library=None, n_samples: int = 1, batch: Optional[int] = None, count_only: bool = False):
@@ -530,21 +523,15 @@ class Engine:
     differences).  x and original may each be scipy.sparse; the bits do not depend on that, on the batch size or on the chunking."""
     cfg = self.cfg
     G = cfg.n_genes
-    (xa, N, B, la), S = self._staged(x, library, batch), int(n_samples)
-    if not isinstance(xa, tuple) and (xa.ndim != 2 or xa.shape[1] != G):
-      raise ValueError(f"expected rows [n_cells, {G}], got {xa.shape}")
+    (rows, N, B, la), S = self._staged(x, library, batch), int(n_samples)
+    if rows[1] is None and (rows[0].ndim != 2 or rows[0].shape[1] != G):
+      raise ValueError(f"expected rows [n_cells, {G}], got {rows[0].shape}")
     if original is None:
       raise ValueError("predict_impute needs the original counts")
-    oc = _csr3(original, G, N) if _sparse(original) else None
-    oa = None if oc is not None else _f32(original, (N, G))
+    orows = _host_rows(original, G, N)
     med, chg, lohi = np.empty((N,), np.float32), np.empty((N,), np.int32), np.empty((2,), np.float32)
-    res = (_fp(med), _ip(chg), _fp(lohi))
-    if isinstance(xa, tuple) or oc is not None:
-      xp = (None,) + _csr_ptrs(xa) if isinstance(xa, tuple) else (_fp(xa), None, None, None)
-      op = _csr_ptrs(oc) if oc is not None else (None, None, None)
-      check(self.lib.smx_predict_impute_csr(self._h, *xp, _fp(la), N, B, S, int(bool(count_only)), _fp(oa), *op, *res))
-    else:
-      check(self.lib.smx_predict_impute(self._h, _fp(xa), _fp(la), N, B, S, int(bool(count_only)), _fp(oa), *res))
+    check(self.lib.smx_predict_impute(self._h, *_matrix_ptrs(*rows), _fp(la), N, B, S, int(bool(count_only)), *_matrix_ptrs(*orows),
+                                      _fp(med), _ip(chg), _fp(lohi)))
     return dict(cell_median=med, cell_changed=chg, global_lohi=lohi)
 
   def predict_correlate(self, x, prot_rank2, prot_unit, library=None, n_samples: int = 1, batch: Optional[int] = None, count_only: bool = False,
@@ -556,14 +543,15 @@ class Engine:
     on that, on the batch size or on the chunking.  More than 2^20 cells: the library refuses (SmxError)."""
     cfg = self.cfg
     G = cfg.n_genes
-    (xa, N, B, la), S = self._staged(x, library, batch), int(n_samples)
-    if not isinstance(xa, tuple) and (xa.ndim != 2 or xa.shape[1] != G):
-      raise ValueError(f"expected rows [n_cells, {G}], got {xa.shape}")
+    (rows, N, B, la), S = self._staged(x, library, batch), int(n_samples)
+    if rows[1] is None and (rows[0].ndim != 2 or rows[0].shape[1] != G):
+      raise ValueError(f"expected rows [n_cells, {G}], got {rows[0].shape}")
     idx = None if genes is None else gene_indices(genes, G)
     pr, pu = _col_operands(prot_rank2, prot_unit, N)
     out, res = _col_outputs(G if idx is None else idx.size, pr.shape[0])
     sel = (None, 0) if idx is None else (_ip(idx), idx.size)
-    self._rows_call("predict_correlate", xa, _fp(la), N, B, S, int(bool(count_only)), *sel, _ip(pr), _dp(pu), pr.shape[0], *res)
+    check(self.lib.smx_predict_correlate(self._h, *_matrix_ptrs(*rows), _fp(la), N, B, S, int(bool(count_only)), *sel, _ip(pr), _dp(pu),
+                                         pr.shape[0], *res))
     return out
 
   def decode(self, z, l=None):
@@ -580,16 +568,13 @@ class Engine:
     return dict(x_params=xp, y_params=ys)
 
   def marginal_llk(self, row_ids=None, x=None, library=None, n_samples: int = 100):
-    """Importance-weighted log p(x) per cell and the mean reconstruction log-likelihood (GPU).  x may be scipy.sparse
-    (smx_marginal_llk_csr)."""
-    if row_ids is None and _sparse(x):
-      xc = _csr3(x, self.cfg.n_genes)
-      B = xc[0].size - 1
-      la = None if library is None else _f32(library, (B, 2))
-      mllk, llk = np.empty(B, np.float32), np.empty(B, np.float32)
-      check(self.lib.smx_marginal_llk_csr(self._h, *_csr_ptrs(xc), _fp(la), B, int(n_samples), _fp(mllk), _fp(llk)))
-      return mllk, llk
-    B, keep, cells = self._cells(row_ids, x, library)
+    """Importance-weighted log p(x) per cell and the mean reconstruction log-likelihood (GPU).  x may be scipy.sparse."""
+    if row_ids is not None:
+      ids = self._ids(row_ids)
+      B, cells = ids.size, (_ip(ids), None, None, None, None, None)
+    else:
+      rows, B, _, la = self._staged(x, library, None)
+      cells = (None, *_matrix_ptrs(*rows), _fp(la))
     mllk, llk = np.empty(B, np.float32), np.empty(B, np.float32)
     check(self.lib.smx_marginal_llk(self._h, *cells, B, int(n_samples), _fp(mllk), _fp(llk)))
     return mllk, llk

@@ -603,7 +603,7 @@ class SingleCellModel:
       library = library_matrix(x)
     n = int(np.prod(sample_shape)) if np.size(sample_shape) else 0
     e = self._ensure_engine(x.shape[0])
-    if is_sparse(x):   # the whole input is one batch of smx_predict_csr: the numbers of smx_forward(_samples) on the dense rows
+    if is_sparse(x):   # the whole input is one batch of smx_predict on CSR rows: the numbers of smx_forward(_samples) on the dense rows
       pX, first = self._drawn(e.predict(x, library=library, n_samples=max(n, 1), batch=x.shape[0]), n)
       return pX, self._latent_dists(first)
     if n > 1:   # every draw in one call: the encoders run once, the draws re-sample the latents and decode
@@ -621,7 +621,7 @@ class SingleCellModel:
     if self._cfg.model == "scvi" and library is None:
       library = library_matrix(x)
     e = self._ensure_engine(x.shape[0])
-    if is_sparse(x):   # (one batch of smx_predict_csr; the whole forward pass, as smx_forward runs it)
+    if is_sparse(x):   # (one batch of smx_predict on CSR rows; the whole forward pass, as smx_forward runs it)
       _, out = self._drawn(e.predict(x, library=library, n_samples=1, batch=x.shape[0]), 1, outputs=None)
     else:
       out = e.forward(x=x, library=library, want_x_params=False)

@@ -32,6 +32,41 @@ def test_header_and_binding_agree(lib):
   assert {"smx_k_label_loss"} <= declared and _hip.SMX_ABI_VERSION >= 19
 
 
+def test_rows_convention_of_the_header():
+  """One entry per operation for a host matrix that is dense or CSR (the rows convention at the top of include/sisua_hip.h): no `_csr`
+  twins, and wherever a declaration takes a CSR triple of float32 values -- `indptr, cols, vals`, bare or under one prefix (t_, o_, v_)
+  -- the triple follows a `const float*` parameter, the dense form of the same matrix, directly and in that order.  The two device STORES
+  filled from CSR, smx_dataset_upload_csr / _csr_dense, are the only entries named after the form and the only ones that take a triple
+  alone: they differ from smx_dataset_upload by store, not by input form.  Graph entries (t-SNE, UMAP, Louvain: `indptr, cols` and
+  float64 weights of an n x n graph) hold no such matrix; a declaration that names `indptr` without `cols, vals` behind it must be one
+  of them, with no `const float*` matrix to pair it with."""
+  hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sisua_hip.h")).read(), flags=re.S)
+  decls = {name: [p.strip() for p in params.split(",")] for name, params in re.findall(r"\b(smx_[a-z_0-9]+)\s*\(([^)]*)\)\s*;", hdr)}
+  stores = {"smx_dataset_upload_csr", "smx_dataset_upload_csr_dense"}
+  assert {n for n in decls if n.endswith("_csr") or "_csr_" in n} == stores
+  pname = lambda p: re.split(r"[\s*]+", p)[-1]
+  ptype = lambda p: " ".join(p[:len(p) - len(pname(p))].replace("*", " * ").split())
+  seen = set()
+  for name, params in decls.items():
+    names = [pname(p) for p in params]
+    for i, n in enumerate(names):
+      if not n.endswith("indptr"):
+        continue
+      pre = n[:-len("indptr")]
+      assert pre in ("", "t_", "o_", "v_"), (name, n)
+      if names[i + 1:i + 3] != [pre + "cols", pre + "vals"]:   # a graph, not a count matrix
+        assert pre == "" and names[i + 1] == "cols" and ptype(params[i + 2]) == "const double *", (name, params)
+        assert not any(ptype(p) == "const float *" for p in params), (name, params)
+        continue
+      assert [ptype(p) for p in params[i:i + 3]] == ["const int64_t *", "const int32_t *", "const float *"], (name, params)
+      if name in stores:
+        continue
+      assert i >= 1 and ptype(params[i - 1]) == "const float *" and not pname(params[i - 1]).endswith("vals"), (name, params)
+      seen.add(name)
+  assert {"smx_predict", "smx_predict_stat", "smx_predict_sample", "smx_predict_stat_cols", "smx_predict_impute", "smx_predict_correlate",
+          "smx_marginal_llk", "smx_prep_stats", "smx_gbt_fit"} <= seen
+
+
 def test_config_struct_layout_matches_header(tmp_path):
   """sizeof / offsetof of every field of smx_config and smx_metrics as gcc lays include/sisua_hip.h out == the ctypes
   mirror in sisua_amd/_hip.py."""

@@ -105,6 +105,6 @@ def test_marker_correlations_keys():
 
 def test_entry_points_are_declared():
   from sisua_amd import _hip, build
-  for name in ("smx_predict_correlate", "smx_predict_correlate_csr", "smx_k_col_rank2", "smx_k_col_correlate"):
+  for name in ("smx_predict_correlate", "smx_k_col_rank2", "smx_k_col_correlate"):
     assert name in _hip.SIGNATURES
   assert "smx_correlate.hip" in build.SOURCES

@@ -1,6 +1,7 @@
-"""Sparse count matrices end to end on the GPU: every inference and scoring entry point given CSR rows (smx_predict_csr,
-smx_predict_stat_csr, smx_marginal_llk_csr) returns the bits it returns for the dense rows of the same counts, and a fit on a
-sparse SingleCellOMIC is the fit on its dense twin."""
+"""Sparse count matrices end to end on the GPU: every inference and scoring entry point given CSR rows (the rows convention of
+include/sisua_hip.h: smx_predict and its statistics, smx_marginal_llk) returns the bits it returns for the dense rows of the same
+counts, a fit on a sparse SingleCellOMIC is the fit on its dense twin, and every such entry refuses rows given in both forms or in
+neither."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -226,3 +227,56 @@ def test_experiment_on_sparse_cortex(api, monkeypatch):
     assert exp.sco.is_sparse() == sparse and exp.train.is_sparse() == sparse
     runs.append(_fit_state(m))
   _same_fit(*runs)
+
+
+def test_rows_in_both_forms_or_in_neither_are_refused(api):
+  """The rows convention at the raw binding: each of the seven entries that take (host_x, indptr, cols, vals) answers SMX_ERR_INVALID
+  with the one shared wording when given both forms of the rows and when given neither -- as do smx_predict_stat for both forms of its
+  target, smx_predict_impute for neither form of the original, and smx_marginal_llk for row_ids beside CSR rows (its own wording).  All
+  are host refusals in front of any device work: no result array is touched.  33 genes (ragged against the 32-column padding), 70 cells
+  in batches of 32 (ragged last batch), 2 draws."""
+  from sisua_amd import _hip
+  from sisua_amd.engine._args import _csr3, _dp, _fp, _ip, _matrix_ptrs, _ptr
+  G, N, B, S, P, D = 33, 70, 32, 2, 2, 6
+  x = np.ascontiguousarray(synth_counts(N, G, sparsity=0.8, seed=11), dtype=np.float32)
+  csr = _csr3(sp.csr_matrix(x), G)
+  csr_b = (np.ascontiguousarray(csr[0][:B + 1]), csr[1], csr[2])   # the first batch's rows: what smx_marginal_llk takes
+  m = _model(api, "vae_zinb", G)
+  m._ensure_engine(B)
+  h, lib = m._engine._h, _hip.load()
+  f32 = lambda *shape: np.full(shape, np.nan, np.float32)
+  out = dict(z_mean=f32(N, D), stat=f32(N, G), logp=f32(S, N), sample=f32(1, S, N, G), cols=f32(N, 3), med=f32(N), lohi=f32(2), mllk=f32(B), llk=f32(B),
+             pe=np.full((3, G + G + G * P), np.nan, np.float64), chg=np.full(N, -7, np.int32), nonfinite=np.full(G, -7, np.int32),
+             sp=np.full((2 * G + G * P,), -7, np.int64))
+  genes = np.array([0, 32, 7], np.int32)
+  pr, pu, ids = np.zeros((P, N), np.int32), np.zeros((P, N), np.float64), np.zeros(B, np.int32)
+  none4, good, good_b = (None,) * 4, _matrix_ptrs(None, csr), _matrix_ptrs(None, csr_b)
+  lp = lambda a: _ptr(a, np.int64)
+  cor_out = (lp(out["sp"][:G]), lp(out["sp"][G:2 * G]), lp(out["sp"][2 * G:]), _dp(out["pe"][0]), _dp(out["pe"][1]), _dp(out["pe"][2]), _ip(out["nonfinite"]))
+  head = (None, N, B, S)   # host_library, n_cells, batch, n_samples
+  entries = {   # name -> the call, given the four rows pointers
+      "smx_predict": lambda r: lib.smx_predict(h, *r, *head, _fp(out["z_mean"]), None, None, None, None, None, None, None),
+      "smx_predict_stat": lambda r: lib.smx_predict_stat(h, *r, *head, 2, 0, *none4, _fp(out["stat"])),
+      "smx_predict_sample": lambda r: lib.smx_predict_sample(h, *r, *head, 0, 5, 1, _fp(out["sample"])),
+      "smx_predict_stat_cols": lambda r: lib.smx_predict_stat_cols(h, *r, *head, 0, _ip(genes), genes.size, _fp(out["cols"])),
+      "smx_predict_impute": lambda r: lib.smx_predict_impute(h, *r, *head, 0, *_matrix_ptrs(x, None), _fp(out["med"]), _ip(out["chg"]), _fp(out["lohi"])),
+      "smx_predict_correlate": lambda r: lib.smx_predict_correlate(h, *r, *head, 0, None, 0, _ip(pr), _dp(pu), P, *cor_out),
+      "smx_marginal_llk": lambda r: lib.smx_marginal_llk(h, None, *r, None, B, S, _fp(out["mllk"]), _fp(out["llk"])),
+  }
+  shared = b"exactly one of the dense matrix and the CSR arrays"
+
+  def refused(status, wording):
+    assert status == -1, (status, lib.smx_last_error())   # SMX_ERR_INVALID
+    assert wording in lib.smx_last_error(), lib.smx_last_error()
+
+  for name, call in entries.items():
+    both = (_fp(x), *(good_b if name == "smx_marginal_llk" else good)[1:])
+    refused(call(both), shared)
+    refused(call(none4), shared)
+  # a second matrix is held to the same rule: both forms of the target, neither form of the original
+  refused(lib.smx_predict_stat(h, *good, *head, 3, 0, _fp(x), *good[1:], _fp(out["logp"])), shared)
+  refused(lib.smx_predict_impute(h, *good, *head, 0, *none4, _fp(out["med"]), _ip(out["chg"]), _fp(out["lohi"])), shared)
+  # resident cells by id, or host rows: not both
+  refused(lib.smx_marginal_llk(h, _ip(ids), *good_b, None, B, S, _fp(out["mllk"]), _fp(out["llk"])), b"row_ids or host rows")
+  for k, a in out.items():
+    assert (np.isnan(a) if a.dtype.kind == "f" else a == -7).all(), k

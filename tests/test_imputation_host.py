@@ -133,7 +133,7 @@ def test_correlation_scores_metric():
 def test_abi_declares_and_binds_the_new_symbols():
   from sisua_amd import _hip
   hdr = open(os.path.join(ROOT, "include", "sisua_hip.h")).read()
-  for name in ("smx_predict_impute", "smx_predict_impute_csr", "smx_predict_stat_cols", "smx_predict_stat_cols_csr", "smx_k_row_select",
+  for name in ("smx_predict_impute", "smx_predict_stat_cols", "smx_k_row_select",
                "smx_pad_audit", "smx_pad_poke"):
     assert name + "(" in hdr and name in _hip.SIGNATURES
   assert _hip.SMX_ABI_VERSION >= 6 and "smx_impute.hip" in __import__("sisua_amd.build", fromlist=["SOURCES"]).SOURCES

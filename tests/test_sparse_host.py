@@ -202,6 +202,6 @@ def test_csr_symbols_declared_and_exported():
   lib = _hip.load()
   hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sisua_hip.h")).read(), flags=re.S)
   declared = set(re.findall(r"\b(smx_[a-z_0-9]+)\s*\(", hdr))
-  for name in ("smx_predict_csr", "smx_predict_stat_csr", "smx_marginal_llk_csr", "smx_dataset_upload_csr_dense",
+  for name in ("smx_predict", "smx_predict_stat", "smx_marginal_llk", "smx_dataset_upload_csr", "smx_dataset_upload_csr_dense",
                "smx_pad_audit", "smx_pad_poke"):
     assert name in declared and name in _hip.SIGNATURES and hasattr(lib, name)
